@@ -9,8 +9,14 @@ device, 30 lock-step Lanczos steps, on-device Gauss quadrature, sum f(theta)*tau
 operator is resident in HBM before the timed region. Probes shard across GPUs with no data-path
 collective (weak scaling: 256 probes per GPU; probe ids are global, so results do not depend on N).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--orth R] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--orth R] [--scaling weak|strong] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line. --full also measures what the headline figure does not
+need: the card's stream rates (roofline.measured_stream_GBps), the other operators of BASELINE.md §2 (extra; default
+invocation, N = 1) and the CPU baselines (N = 1). --dump-outputs DIR writes what the last timed step computed on rank 0 -
+the per-probe quadrature values and the Lanczos coefficients - as DIR/<name>.npy; the inputs are seeded, so two builds
+can be compared output for output.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment (a bare `python bench.py --gpus N`) the process starts its own N
 ranks (spawn_ranks: child processes with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, before anything here touches
@@ -184,10 +190,12 @@ def shard_range(nprobes, rank, world):
 	return lo, lo + base + (1 if rank < rem else 0)
 
 
-def measure(ctx, workload, dtype, P, deg_req, orth_req, steps, warmup, fun, rank, world, dist, red_dev, profiled=True, stream_rates=True, scaling="weak"):
+def measure(ctx, workload, dtype, P, deg_req, orth_req, steps, warmup, fun, rank, world, dist, red_dev, profiled=True, stream_rates=True, scaling="weak",
+            keep_outputs=False):
 	"""One bench measurement: `warmup` untimed + `steps` timed passes of the hot path on `workload`; returns the JSON line.
 	scaling = "weak": every rank advances P probes per step; "strong": P is the GLOBAL batch of a step and rank r advances its
-	contiguous shard of it (256 probes over 8 GPUs = 32 per GPU: the narrow-panel plans; src/primate/trace.py:36 draws 32 per batch)."""
+	contiguous shard of it (256 probes over 8 GPUs = 32 per GPU: the narrow-panel plans; src/primate/trace.py:36 draws 32 per batch).
+	keep_outputs: also return what the last timed step computed ("outputs": name -> array)."""
 	import torch
 
 	from primate_amd.engine import DeviceOperator, LanczosPlan
@@ -213,11 +221,14 @@ def measure(ctx, workload, dtype, P, deg_req, orth_req, steps, warmup, fun, rank
 	plan = LanczosPlan(op, P, deg, orth)
 	plan_s = time.perf_counter() - t_plan
 
+	last = {}
+
 	def step(it: int):
 		## probe ids are global: step `it` draws ids [it * P_global, (it + 1) * P_global), rank r its block of them
 		plan.generate_probes("rademacher", seed=1234, probe_offset=it * P_global + lo)
 		plan.run(1e-8)
 		q = plan.quadrature(fun)  # device QL + reduction; returns P doubles (synchronises)
+		last["quad"] = q
 		if dist is not None:
 			st = torch.tensor([q.sum(), (q * q).sum(), float(len(q))], dtype=torch.float64, device=red_dev)
 			dist.all_reduce(st)  # RCCL over xGMI: the only collective on the path
@@ -249,6 +260,12 @@ def measure(ctx, workload, dtype, P, deg_req, orth_req, steps, warmup, fun, rank
 		tmax = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
 		dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
 		elapsed = float(tmax.item())
+	outputs = None
+	if keep_outputs:  # the last timed step's results, read back before any other step runs on the plan
+		alpha, beta, _ = plan.tridiag()
+		outputs = {"quad": np.asarray(last["quad"], dtype=np.float64), "alpha": alpha, "beta": beta}
+		if dist is not None:
+			outputs["stats"] = ests[-1].cpu().numpy()  # the all-reduced (sum, sum of squares, count)
 	prof_steps = steps
 	if not profiled:  # A/B mode: kernel events from ONE extra step outside the timed region
 		plan.profile_enable(True)
@@ -333,7 +350,7 @@ def measure(ctx, workload, dtype, P, deg_req, orth_req, steps, warmup, fun, rank
 	}  # fmt: skip
 
 	del plan, op
-	return {"line": line, "A": A, "n": n, "deg": deg, "orth": orth}
+	return {"line": line, "A": A, "n": n, "deg": deg, "orth": orth, "outputs": outputs}
 
 
 SPAWN_TIMEOUT_S = 3000.0  # overall limit of a self-launched N-rank run (--timeout)
@@ -408,21 +425,26 @@ def spawn_ranks(n, argv, cmd=None, timeout=None):
 def main():
 	ap = argparse.ArgumentParser()
 	ap.add_argument("--gpus", type=int, default=1)
-	ap.add_argument("--steps", type=int, default=10)
-	ap.add_argument("--warmup", type=int, default=2)
+	ap.add_argument("--steps", type=int, default=10, help="timed steps")
+	ap.add_argument("--warmup", type=int, default=2, help="untimed steps before them")
 	ap.add_argument("--orth", type=int, default=3, help="reorthogonalisation depth (MatrixFunction default: 3)")
 	ap.add_argument("--deg", type=int, default=30)
 	ap.add_argument("--probes", type=int, default=256, help="probes per GPU")
 	ap.add_argument("--workload", default="lap2d_1000", help="lap2d_<m> | lap3d_<m>")
 	ap.add_argument("--fun", default="log")
 	ap.add_argument("--dtype", default="f64", choices=["f64", "f32"], help="arithmetic type of the operator and the Lanczos vectors")
-	ap.add_argument("--no-cpu-baseline", action="store_true")
-	ap.add_argument("--no-extra", action="store_true", help="skip the extra operators appended to the default line")
+	ap.add_argument("--full", action="store_true",
+	                help="also measure what the headline figure does not need: stream rates, the extra operators, the CPU baselines")
+	ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
+	ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baselines")
+	ap.add_argument("--no-extra", action="store_true", help="(--full) skip the extra operators appended to the default line")
 	ap.add_argument("--cpu-seconds", type=float, default=15.0)
 	ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
 	                help="weak: --probes per GPU (default); strong: --probes is the GLOBAL count, rank r takes its contiguous shard")
 	ap.add_argument("--timeout", type=float, default=SPAWN_TIMEOUT_S, help="overall limit (s) of a self-launched N-rank run")
 	args = ap.parse_args()
+	if args.steps < 1 or args.warmup < 0:
+		ap.error("--steps must be at least 1 and --warmup at least 0")
 
 	N = args.gpus
 	if N > 1 and "WORLD_SIZE" not in os.environ:
@@ -456,9 +478,15 @@ def main():
 
 	ctx = Context(device=local_rank)
 	res = measure(ctx, args.workload, args.dtype, args.probes, args.deg, args.orth, args.steps, args.warmup, args.fun,
-				  rank, world, dist, red_dev, profiled=not os.environ.get("BENCH_NO_PROFILE"), scaling=args.scaling)
+				  rank, world, dist, red_dev, profiled=not os.environ.get("BENCH_NO_PROFILE"), stream_rates=args.full, scaling=args.scaling,
+				  keep_outputs=bool(args.dump_outputs))
 	line, A, n, deg, orth = res["line"], res["A"], res["n"], res["deg"], res["orth"]
 	line["steps"], line["warmup"] = args.steps, args.warmup
+	if args.dump_outputs and rank == 0:
+		out = Path(args.dump_outputs)
+		out.mkdir(parents=True, exist_ok=True)
+		for name, arr in res["outputs"].items():
+			np.save(out / f"{name}.npy", arr)
 
 	## ---- what a reader needs to verify an N-rank run: backend, world size, one distinct device per rank
 	if dist is not None:
@@ -475,10 +503,10 @@ def main():
 			ids = {(d["pci"], d["uuid"]) for d in devs}
 			assert len(ids) == world, f"ranks share a GPU: {devs}"
 
-	## ---- the other operators of BASELINE.md §2 in the same record (N = 1, default invocation only): the north_star's
+	## ---- the other operators of BASELINE.md §2 in the same record (--full, N = 1, default invocation only): the north_star's
 	## 3-D 100^3 operator (nnz = 6.94 M) at the default and at no reorthogonalisation, and configs[1] at orth = 0
 	default_run = args.workload == "lap2d_1000" and args.dtype == "f64" and args.orth == 3 and args.probes == 256 and args.deg == 30
-	if rank == 0 and world == 1 and default_run and not args.no_extra:
+	if args.full and rank == 0 and world == 1 and default_run and not args.no_extra:
 		extra = {}
 		## ... and the shapes the reference's drivers submit next to the 256-probe batch: a 64-probe panel (an 8-GPU shard of 512 probes;
 		## hutch's batches are 32, src/primate/trace.py:36) and a six-column reorthogonalisation window
@@ -501,8 +529,8 @@ def main():
 			}  # fmt: skip
 		line["extra"] = extra
 
-	## ---- CPU baseline: the oracle (C restatement of the reference kernel), rank 0, N = 1 only ---
-	if rank == 0 and world == 1 and not args.no_cpu_baseline:
+	## ---- CPU baseline (--full): the oracle (C restatement of the reference kernel), rank 0, N = 1 only
+	if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
 		from oracle import oracle
 
 		rng = np.random.default_rng(1234)

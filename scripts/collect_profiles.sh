@@ -15,24 +15,24 @@ SHA=$(cd $ROOT && python3 -c "import bench; print(bench.kernel_sources_sha256())
 echo "kernel sources sha256 $SHA" | tee $OUT/kernel_sha256.txt
 if [ "$PART" = "lines" ] || [ "$PART" = "all" ]; then
   echo "== bench lines"
-  python3 $B > $OUT/bench_default_line.json
-  python3 $B --orth 0 --no-cpu-baseline --no-extra > $OUT/bench_orth0_line.json
-  python3 $B --orth 30 --no-cpu-baseline --no-extra --steps 4 > $OUT/bench_orth30_line.json
-  python3 $B --orth 6 --no-cpu-baseline --no-extra > $OUT/bench_orth6_line.json
-  python3 $B --workload lap3d_100 --no-cpu-baseline --no-extra > $OUT/bench_lap3d_100_line.json
-  python3 $B --workload lap3d_100 --orth 0 --no-cpu-baseline --no-extra > $OUT/bench_lap3d_100_orth0_line.json
-  python3 $B --workload lap3d_100 --orth 30 --no-cpu-baseline --no-extra --steps 4 > $OUT/bench_lap3d_100_orth30_line.json
-  python3 $B --probes 64 --no-cpu-baseline --no-extra > $OUT/bench_p64_line.json
-  python3 $B --workload lap3d_100 --probes 64 --no-cpu-baseline --no-extra > $OUT/bench_lap3d_100_p64_line.json
-  python3 $B --probes 32 --no-cpu-baseline --no-extra > $OUT/bench_p32_line.json
-  BENCH_NO_PROFILE=1 python3 $B --no-cpu-baseline --no-extra > $OUT/bench_default_line_no_events.json
+  python3 $B --full > $OUT/bench_default_line.json
+  python3 $B --full --orth 0 --no-cpu-baseline --no-extra > $OUT/bench_orth0_line.json
+  python3 $B --full --orth 30 --no-cpu-baseline --no-extra --steps 4 > $OUT/bench_orth30_line.json
+  python3 $B --full --orth 6 --no-cpu-baseline --no-extra > $OUT/bench_orth6_line.json
+  python3 $B --full --workload lap3d_100 --no-cpu-baseline --no-extra > $OUT/bench_lap3d_100_line.json
+  python3 $B --full --workload lap3d_100 --orth 0 --no-cpu-baseline --no-extra > $OUT/bench_lap3d_100_orth0_line.json
+  python3 $B --full --workload lap3d_100 --orth 30 --no-cpu-baseline --no-extra --steps 4 > $OUT/bench_lap3d_100_orth30_line.json
+  python3 $B --full --probes 64 --no-cpu-baseline --no-extra > $OUT/bench_p64_line.json
+  python3 $B --full --workload lap3d_100 --probes 64 --no-cpu-baseline --no-extra > $OUT/bench_lap3d_100_p64_line.json
+  python3 $B --full --probes 32 --no-cpu-baseline --no-extra > $OUT/bench_p32_line.json
+  BENCH_NO_PROFILE=1 python3 $B --full --no-cpu-baseline --no-extra > $OUT/bench_default_line_no_events.json
 fi
 if [ "$PART" = "stats" ] || [ "$PART" = "all" ]; then
   for cfg in "lap2d_1000 3 256" "lap2d_1000 0 256" "lap2d_1000 30 256" "lap2d_1000 6 256" "lap3d_100 3 256" "lap3d_100 0 256" "lap3d_100 30 256" "lap3d_100 3 64"; do
     set -- $cfg; w=$1; o=$2; pr=$3
     name=${w}_orth${o}; [ "$pr" != "256" ] && name=${name}_p$pr
     echo "== kernel stats $name"
-    rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats_$name -o run -- python3 $B --workload $w --orth $o --probes $pr --steps 4 --warmup 2 --no-cpu-baseline --no-extra > $OUT/bench_${name}_line_under_rocprof.json
+    rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats_$name -o run -- python3 $B --full --workload $w --orth $o --probes $pr --steps 4 --warmup 2 --no-cpu-baseline --no-extra > $OUT/bench_${name}_line_under_rocprof.json
   done
   echo "== kernel stats dense (configs[0] operator: 5000^2, 64 / 128 probes)"
   rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/stats_dense -o run -- python3 $ROOT/scripts/bench_dense.py > $OUT/bench_dense.log 2>&1
@@ -44,7 +44,7 @@ if [ "$PART" = "pmc" ] || [ "$PART" = "all" ]; then
     sfx=""; [ "$pr" != "256" ] && sfx=_p$pr
     for c in FETCH_SIZE WRITE_SIZE; do
       echo "== pmc $c $w orth $o probes $pr"
-      rocprofv3 --output-format csv --kernel-trace --pmc $c -d $OUT/pmc_${c}_${w}_orth$o$sfx -o run -- python3 $B --workload $w --orth $o --probes $pr --steps 2 --warmup 1 --no-cpu-baseline --no-extra > /dev/null
+      rocprofv3 --output-format csv --kernel-trace --pmc $c -d $OUT/pmc_${c}_${w}_orth$o$sfx -o run -- python3 $B --full --workload $w --orth $o --probes $pr --steps 2 --warmup 1 --no-cpu-baseline --no-extra > /dev/null
     done
   done
   python3 $ROOT/scripts/summarise_pmc.py $OUT > $OUT/pmc_summary.json

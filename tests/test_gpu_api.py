@@ -616,3 +616,42 @@ def quad_fresh(op, X):
 	q = plan.quadrature("log")
 	plan.close()
 	return q
+
+
+def test_bench_plain_line_dumped_outputs_and_full(tmp_path):
+	"""bench.py at a small size: a plain run times --steps steps and carries none of --full's measurements; --dump-outputs
+	holds what the last timed step computed (the same probes on a fresh plan give the same numbers); --full adds the
+	stream rates and the CPU baselines."""
+	import json
+	import subprocess
+	import sys
+
+	from primate_amd.engine import DeviceOperator, LanczosPlan
+
+	args = [sys.executable, str(ROOT / "bench.py"), "--workload", "lap2d_64", "--probes", "32", "--deg", "12", "--steps", "3", "--warmup", "1"]
+
+	def line_of(cmd):
+		r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+		assert r.returncode == 0, r.stderr[-2000:]
+		return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+
+	line = line_of(args + ["--dump-outputs", str(tmp_path / "out")])
+	dumped = {k: np.load(tmp_path / "out" / f"{k}.npy") for k in ("quad", "alpha", "beta")}
+	assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+	assert line["value"] == pytest.approx(32 * 12 / (line["ms_per_step"] * 1e-3), rel=5e-3)  # (ms_per_step is rounded to 1 us)
+	assert "cpu_baseline" not in line and "extra" not in line and line["roofline"]["measured_stream_GBps"] is None
+	assert dumped["quad"].shape == (32,) and dumped["quad"].dtype == np.float64
+	assert dumped["alpha"].shape == dumped["beta"].shape == (32, 13) and dumped["alpha"].dtype == np.float64
+	## the last timed step is step warmup + steps - 1: probe ids [3 * 32, 4 * 32)
+	op = DeviceOperator(laplacian_2d(64))
+	plan = LanczosPlan(op, 32, 12, 3)
+	plan.generate_probes("rademacher", seed=1234, probe_offset=3 * 32)
+	plan.run(1e-8)
+	q = plan.quadrature("log")
+	alpha, beta, _ = plan.tridiag()
+	plan.close(), op.close()
+	np.testing.assert_allclose(dumped["quad"], q, rtol=1e-12, atol=0)
+	np.testing.assert_allclose(dumped["alpha"], alpha, rtol=1e-12, atol=0)
+	np.testing.assert_allclose(dumped["beta"], beta, rtol=1e-12, atol=0)
+	full = line_of(args + ["--full", "--cpu-seconds", "0.5"])
+	assert full["steps"] == 3 and "cpu_baseline" in full and set(full["roofline"]["measured_stream_GBps"]) == {"read", "triad"}

@@ -346,3 +346,12 @@ def test_bench_strong_scaling_shards():
 
 	h = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], capture_output=True, text=True).stdout
 	assert "--scaling" in h and "strong" in h and "--timeout" in h
+
+
+def test_bench_options_of_a_plain_run():
+	"""`bench.py --full` holds what the headline figure does not need, `--dump-outputs DIR` saves the last timed step, and a
+	run with no timed step is refused before anything touches torch or a device."""
+	h = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], capture_output=True, text=True).stdout
+	assert "--full" in h and "--dump-outputs" in h and "--steps" in h
+	r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+	assert r.returncode == 2 and "--steps" in r.stderr and r.stdout == ""
