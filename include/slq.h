@@ -21,6 +21,8 @@
  *   - eigh_tridiag / eigvalsh_tridiag, src/primate/tridiag.py:25-62 -> slq_eigh_tridiag_batch
  *   - random.isotropic, src/primate/random.py:22-41,47-80 -> slq_plan_generate_probes
  *   - the spectral-function registry, src/primate/special.py:78-107 -> SLQ_FUN_* ids
+ *   - the planned spectral_density (src/primate/__init__.py:10, README.md:22; the measure of
+ *       src/primate/integrate.py:30-35)           -> slq_density_*
  *
  * Conventions kept from the reference: alpha/beta have deg+1 entries, beta[0] = 0
  * (lanczos.h:121); rtol is scaled by sqrt(n) (lanczos.h:110); `orth` = number of most recent
@@ -74,11 +76,15 @@ enum {
 /* Probe distributions (src/primate/random.py:12-18). */
 enum { SLQ_PDF_RADEMACHER = 0, SLQ_PDF_NORMAL = 1, SLQ_PDF_SPHERE = 2 };
 
+/* Spectral density kernels (slq_density_create): K(x, theta) of the smoothed per-probe measure. */
+enum { SLQ_DENSITY_GAUSSIAN = 0, SLQ_DENSITY_LORENTZIAN = 1, SLQ_DENSITY_HISTOGRAM = 2, SLQ_DENSITY_CDF = 3 };
+
 typedef struct slq_context slq_context;   /* one per (process, GPU): device id + HIP stream      */
 typedef struct slq_operator slq_operator; /* a symmetric linear operator resident on that GPU    */
 typedef struct slq_plan slq_plan;         /* workspace + state of one batched Lanczos run        */
 typedef struct slq_diag slq_diag;         /* device-resident accumulators of the diagonal estimator */
 typedef struct slq_dmat slq_dmat;         /* column-major n x m fp64 matrix resident on the device  */
+typedef struct slq_density slq_density;   /* device-resident statistics of a spectral density estimate */
 
 /* Host-callback operator: y = A x on HOST memory (the fallback for arbitrary Python
  * LinearOperators; mirrors PyLinearOperator::matvec, src/primate/include/pylinop.h:32-40).
@@ -264,6 +270,29 @@ int slq_diag_destroy(slq_diag *d);
 int slq_diag_update(slq_diag *d, slq_plan *plan, int fun_id, const double *fun_params);
 /* any of numer / denom / running_mean (n doubles each) and count may be NULL */
 int slq_diag_get(slq_diag *d, double *numer, double *denom, double *running_mean, int64_t *count);
+
+/* Spectral density of stochastic Lanczos quadrature (the reference plans it but does not ship it: the commented-out
+ * `from .integrate import spectral_density`, src/primate/__init__.py:10, and README.md:22, after Lin, Saad, Yang,
+ * SIAM Review 2016). Every probe's Gauss rule is a discrete form of the per-probe measure
+ * psi(x; A, v) = sum_i |u_i^T v|^2 delta(x - lambda_i) (src/primate/integrate.py:30-35); an update evaluates
+ *   phi_p(x_g) = ||v_p||^2 sum_k tau_pk K(x_g, theta_pk)
+ * for every probe p of a completed run and grid point g, and folds the values into per-point running (count, mean,
+ * M2) in probe order with the batch-Welford formula (no float atomics: identical runs give identical bits). Kinds:
+ *   GAUSSIAN    exp(-(x-theta)^2 / 2 bw^2) / (bw sqrt(2 pi))    ngrid points
+ *   LORENTZIAN  (bw / pi) / ((x-theta)^2 + bw^2)                  ngrid points
+ *   HISTOGRAM   1[e_g <= theta < e_{g+1}]                         ngrid bins, grid holds ngrid + 1 edges
+ *   CDF         1[theta < x]                                      ngrid thresholds
+ * grid must be strictly increasing; bw > 0 for the two smooth kinds (ignored otherwise). outside[0] / [1]: the mean
+ * node mass below x_0 / above x_{ngrid-1} (theta >= the last edge for HISTOGRAM), so that a grid that misses part of
+ * the spectrum shows it. Zero-weight nodes of an early stop add nothing.
+ * slq_density_update is asynchronous on the context stream; it runs the QL of the plan's Jacobi matrices only if
+ * slq_plan_quadrature has not already done so for this run (and a later slq_plan_quadrature reuses the rule). QL
+ * non-convergence (SLQ_ENOTCONV) and a ring-pass bail-out (SLQ_EHIP) are reported by slq_density_get, which
+ * synchronises. mean, m2: ngrid doubles each; any output may be NULL. */
+int slq_density_create(slq_context *ctx, int kind, int ngrid, const double *grid, double bw, slq_density **out);
+int slq_density_update(slq_density *d, slq_plan *plan);
+int slq_density_get(slq_density *d, double *mean, double *m2, double *outside, int64_t *count);
+int slq_density_destroy(slq_density *d);
 
 /* Per-kernel device time accumulated by HIP events on the context stream (for bench.py's
  * roofline line). enable != 0 turns event recording on for subsequent slq_plan_run calls. */

@@ -23,6 +23,7 @@ FUN_IDS = {
 	"softsign": 8,
 }  # fmt: skip
 PDF_IDS = {"rademacher": 0, "signs": 0, "normal": 1, "gaussian": 1, "sphere": 2}
+DENSITY_KINDS = {"gaussian": 0, "lorentzian": 1, "histogram": 2, "cdf": 3}
 KERNEL_CLASSES = ["spmm_3term", "axpy_norm", "reorth_dot", "reorth_update", "finalize", "probes", "quadrature", "fun_combine"]
 
 MATVEC_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
@@ -95,6 +96,10 @@ _SIGNATURES = {
 	"slq_diag_destroy": (C.c_int, [_P]),
 	"slq_diag_update": (C.c_int, [_P, _P, C.c_int, _P]),
 	"slq_diag_get": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int64)]),
+	"slq_density_create": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_double, _PP]),
+	"slq_density_destroy": (C.c_int, [_P]),
+	"slq_density_update": (C.c_int, [_P, _P]),
+	"slq_density_get": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int64)]),
 	"slq_plan_profile_enable": (C.c_int, [_P, C.c_int]),
 	"slq_plan_sweep_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
 	"slq_plan_profile_read": (C.c_int, [_P, C.POINTER(SlqProfile), C.c_int]),

@@ -26,6 +26,7 @@
 #include "slq_ring_api.h"
 #include "slq_ring.hpp"  // (RingGeo constants: no kernel of it is instantiated here)
 #include "slq_build.hpp"  // an operator's derived data built on the device
+#include "slq_density.hpp"  // spectral density accumulator (slq_density_*)
 
 using namespace slq;
 
@@ -214,6 +215,10 @@ struct slq_plan {
   double *quad_d, *nodes_d, *weights_d;
   int *fail_d;
   int *ring_fail_d;
+  // the Gauss rule of the last run in nodes_d / weights_d: 0 not computed yet, 1 by slq_plan_quadrature (QL status in
+  // rule_fail_h), 2 by slq_density_update (QL status in the device word fail_d[2]); a run resets it to 0
+  int rule_src = 0;
+  int rule_fail_h = 0;
   int rmax;
   bool probes_ready, ran;
   int pdf_sphere;
@@ -2740,7 +2745,7 @@ extern "C" int slq_plan_create(slq_context *ctx, slq_operator *op, int nprobes, 
   p->st.steps = p->st.active + bp;
   p->fail_d = p->st.steps + bp;
   p->ring_fail_d = p->fail_d + 1;  // raised by k_csr_ring_pass when a bounded spin ran out (never cleared: the plan is dead)
-  if (hipMemset(p->ring_fail_d, 0, sizeof(int)) != hipSuccess) {
+  if (hipMemset(p->ring_fail_d, 0, 2 * sizeof(int)) != hipSuccess) {  // (and fail_d[2]: the QL status of a density update)
     slq_plan_destroy(p);
     return fail(SLQ_EHIP, "hipMemset failed");
   }
@@ -3833,6 +3838,7 @@ extern "C" int slq_plan_run(slq_plan *p, double rtol) {
   }
   p->probes_ready = false;
   p->ran = true;
+  p->rule_src = 0;
   return SLQ_OK;
 }
 
@@ -3877,23 +3883,34 @@ extern "C" int slq_plan_quadrature(slq_plan *p, int fun_id, const double *fun_pa
   hipStream_t st = p->ctx->stream;
   const int deg = p->deg, P = p->nprobes;
   const double p0 = fun_params ? fun_params[0] : 0.0, p1 = fun_params ? fun_params[1] : 0.0;
-  const int lanes = quadrature_lanes(deg);
-  const size_t lds = (size_t)3 * deg * lanes * 8;
-  if (lds > 48 * 1024)
-    HIP_TRY(hipFuncSetAttribute((const void *)k_quadrature, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIP_TRY(hipMemsetAsync(p->fail_d, 0, sizeof(int), st));
-  PROFILED(p, SLQ_K_QUADRATURE,
-           hipLaunchKernelGGL(k_quadrature, dim3((P + lanes - 1) / lanes), dim3(64), lds, st, p->st, lanes, fun_id, p0, p1,
-                              p->quad_d, (nodes ? p->nodes_d : nullptr), (weights ? p->weights_d : nullptr), p->fail_d));
+  if (p->rule_src == 2) {
+    // slq_density_update already ran the QL of this run: only the reduction over the stored rule
+    hipLaunchKernelGGL(k_rule_reduce, dim3((P + 63) / 64), dim3(64), 0, st, P, deg, p->nodes_d, p->weights_d, p->st.vnorm2, fun_id, p0,
+                       p1, p->quad_d);
+  } else {
+    const int lanes = quadrature_lanes(deg);
+    const size_t lds = (size_t)3 * deg * lanes * 8;
+    if (lds > 48 * 1024)
+      HIP_TRY(hipFuncSetAttribute((const void *)k_quadrature, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIP_TRY(hipMemsetAsync(p->fail_d, 0, sizeof(int), st));
+    // (the rule always lands in nodes_d / weights_d: a density update of the same run then needs no QL of its own)
+    PROFILED(p, SLQ_K_QUADRATURE,
+             hipLaunchKernelGGL(k_quadrature, dim3((P + lanes - 1) / lanes), dim3(64), lds, st, p->st, lanes, fun_id, p0, p1,
+                                p->quad_d, p->nodes_d, p->weights_d, p->fail_d));
+  }
   HIP_TRY(hipGetLastError());
-  int bad2[2] = {0, 0};  // fail_d, ring_fail_d
-  HIP_TRY(hipMemcpyAsync(bad2, p->fail_d, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  int bad3[3] = {0, 0, 0};  // fail_d[0..2]: the QL of this call, the ring bail-out word, the QL of a density update
+  HIP_TRY(hipMemcpyAsync(bad3, p->fail_d, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
   if (quad) HIP_TRY(hipMemcpyAsync(quad, p->quad_d, (size_t)P * 8, hipMemcpyDeviceToHost, st));
   if (nodes) HIP_TRY(hipMemcpyAsync(nodes, p->nodes_d, (size_t)P * deg * 8, hipMemcpyDeviceToHost, st));
   if (weights) HIP_TRY(hipMemcpyAsync(weights, p->weights_d, (size_t)P * deg * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  const int bad = bad2[0];
-  SLQ_TRY(ring_flag_status(bad2[1]));
+  const int bad = p->rule_src == 2 ? bad3[2] : bad3[0];
+  if (p->rule_src != 2) {
+    p->rule_src = 1;
+    p->rule_fail_h = bad ? 1 : 0;
+  }
+  SLQ_TRY(ring_flag_status(bad3[1]));
   if (bad) return fail(SLQ_ENOTCONV, "tridiagonal QL did not converge for at least one probe");
   return SLQ_OK;
 }
@@ -4068,6 +4085,134 @@ extern "C" int slq_diag_get(slq_diag *d, double *numer, double *denom, double *r
     }
   }
   if (count) *count = d->count;
+  return SLQ_OK;
+}
+
+
+// ---- spectral density accumulator (device-resident; kernels in slq_density.hpp) -----------------------
+struct slq_density {
+  slq_context *ctx;
+  int kind, G;
+  double c0, c1;     // the kernel's constants (k_density_eval)
+  int64_t count;     // probes folded so far
+  double *grid;      // G points or G + 1 edges
+  double *stat;      // mean | M2, G + 2 doubles each (columns G, G + 1: node mass below / above the grid)
+  int *flags;        // [0] QL non-convergence, [1] ring bail-out word of a plan
+  double *phi;       // P x (G + 2) scratch of the per-probe values
+  int64_t phi_cap;   // probes the scratch holds
+};
+
+extern "C" int slq_density_create(slq_context *ctx, int kind, int ngrid, const double *grid, double bw, slq_density **out) {
+  if (!ctx || !out || !grid) return fail(SLQ_EINVAL, "slq_density_create: NULL argument");
+  *out = nullptr;
+  if (kind < SLQ_DENSITY_GAUSSIAN || kind > SLQ_DENSITY_CDF) return fail(SLQ_EINVAL, "slq_density_create: unknown kind %d", kind);
+  if (ngrid < 1) return fail(SLQ_EINVAL, "slq_density_create: ngrid = %d < 1", ngrid);
+  const int npts = ngrid + (kind == SLQ_DENSITY_HISTOGRAM ? 1 : 0);
+  for (int i = 0; i < npts; ++i) {
+    if (!std::isfinite(grid[i])) return fail(SLQ_EINVAL, "slq_density_create: grid[%d] is not finite", i);
+    if (i > 0 && !(grid[i] > grid[i - 1])) return fail(SLQ_EINVAL, "slq_density_create: the grid is not strictly increasing at %d", i);
+  }
+  const bool smooth = kind == SLQ_DENSITY_GAUSSIAN || kind == SLQ_DENSITY_LORENTZIAN;
+  if (smooth && !(bw > 0.0 && std::isfinite(bw))) return fail(SLQ_EINVAL, "slq_density_create: bandwidth %g must be > 0", bw);
+  HIP_TRY(hipSetDevice(ctx->device));
+  slq_density *d = new (std::nothrow) slq_density();
+  if (!d) return fail(SLQ_ENOMEM, "host allocation failed");
+  d->ctx = ctx; d->kind = kind; d->G = ngrid; d->count = 0;
+  d->c0 = d->c1 = 0.0;
+  if (kind == SLQ_DENSITY_GAUSSIAN) { d->c0 = 1.0 / (2.0 * bw * bw); d->c1 = 1.0 / (bw * std::sqrt(2.0 * M_PI)); }
+  if (kind == SLQ_DENSITY_LORENTZIAN) { d->c0 = bw * bw; d->c1 = bw / M_PI; }
+  d->grid = d->stat = d->phi = nullptr; d->flags = nullptr; d->phi_cap = 0;
+  const size_t G2 = (size_t)ngrid + 2;
+  hipError_t e = hipMalloc((void **)&d->grid, (size_t)npts * 8);
+  if (e == hipSuccess) e = hipMalloc((void **)&d->stat, 2 * G2 * 8 + 2 * sizeof(int));
+  if (e == hipSuccess) {
+    d->flags = (int *)(d->stat + 2 * G2);
+    e = hipMemcpyAsync(d->grid, grid, (size_t)npts * 8, hipMemcpyHostToDevice, ctx->stream);
+  }
+  if (e == hipSuccess) e = hipMemsetAsync(d->stat, 0, 2 * G2 * 8 + 2 * sizeof(int), ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (the host grid may go away when this returns)
+  if (e != hipSuccess) {
+    if (d->grid) hipFree(d->grid);
+    if (d->stat) hipFree(d->stat);
+    delete d;  // (not yet retained)
+    return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "density accumulators: %s", hipGetErrorString(e));
+  }
+  ctx_retain(ctx);
+  *out = d;
+  return SLQ_OK;
+}
+
+extern "C" int slq_density_destroy(slq_density *d) {
+  if (!d) return SLQ_OK;
+  hipSetDevice(d->ctx->device);
+  if (d->grid) hipFree(d->grid);
+  if (d->stat) hipFree(d->stat);
+  if (d->phi) hipFree(d->phi);
+  ctx_release(d->ctx);
+  delete d;
+  return SLQ_OK;
+}
+
+extern "C" int slq_density_update(slq_density *d, slq_plan *p) {
+  if (!d || !p) return fail(SLQ_EINVAL, "slq_density_update: density/plan is NULL");
+  if (d->ctx != p->ctx) return fail(SLQ_EINVAL, "slq_density_update: the plan belongs to another context");
+  if (!p->ran) return fail(SLQ_EINVAL, "slq_density_update: no completed run");
+  HIP_TRY(hipSetDevice(p->ctx->device));
+  hipStream_t st = p->ctx->stream;
+  const int P = p->nprobes, deg = p->deg, G2 = d->G + 2;
+  if (d->phi_cap < P) {
+    if (d->phi) {
+      HIP_TRY(hipStreamSynchronize(st));  // (the old scratch may still be read by the previous update)
+      hipFree(d->phi);
+      d->phi = nullptr;
+      d->phi_cap = 0;
+    }
+    hipError_t e = hipMalloc((void **)&d->phi, (size_t)P * G2 * 8);
+    if (e != hipSuccess) return fail(SLQ_ENOMEM, "density scratch (%zu bytes): %s", (size_t)P * G2 * 8, hipGetErrorString(e));
+    d->phi_cap = P;
+  }
+  // the Gauss rule of this run: once per run, whoever asks first (slq_plan_quadrature or a density update)
+  int *rule_fail = p->fail_d + 2;
+  if (p->rule_src == 0) {
+    const int lanes = quadrature_lanes(deg);
+    const size_t lds = (size_t)3 * deg * lanes * 8;
+    if (lds > 48 * 1024)
+      HIP_TRY(hipFuncSetAttribute((const void *)k_quadrature, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIP_TRY(hipMemsetAsync(rule_fail, 0, sizeof(int), st));
+    PROFILED(p, SLQ_K_QUADRATURE,
+             hipLaunchKernelGGL(k_quadrature, dim3((P + lanes - 1) / lanes), dim3(64), lds, st, p->st, lanes, (int)SLQ_FUN_NONE, 0.0, 0.0,
+                                (double *)nullptr, p->nodes_d, p->weights_d, rule_fail));
+    HIP_TRY(hipGetLastError());
+    p->rule_src = 2;
+  }
+  const int nbg = (G2 + kDensEvalThreads - 1) / kDensEvalThreads;
+  hipLaunchKernelGGL(k_density_eval, dim3((unsigned)((int64_t)P * nbg)), dim3(kDensEvalThreads), 0, st, d->kind, d->G, deg, p->nodes_d,
+                     p->weights_d, p->st.vnorm2, d->grid, d->c0, d->c1, nbg, d->phi);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_density_fold, dim3((G2 + 63) / 64), dim3(64 * kDensFoldWaves), 0, st, P, G2, d->count, d->phi, d->stat,
+                     d->stat + G2, (p->rule_src == 2 ? (const int *)rule_fail : nullptr), (p->rule_src == 1 ? p->rule_fail_h : 0),
+                     (const int *)p->ring_fail_d, d->flags);
+  HIP_TRY(hipGetLastError());
+  d->count += P;
+  return SLQ_OK;
+}
+
+extern "C" int slq_density_get(slq_density *d, double *mean, double *m2, double *outside, int64_t *count) {
+  if (!d) return fail(SLQ_EINVAL, "slq_density_get: density is NULL");
+  HIP_TRY(hipSetDevice(d->ctx->device));
+  hipStream_t st = d->ctx->stream;
+  const size_t G = (size_t)d->G, G2 = G + 2;
+  std::vector<double> h(2 * G2);
+  int flags[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(h.data(), d->stat, 2 * G2 * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(flags, d->flags, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (mean) memcpy(mean, h.data(), G * 8);
+  if (m2) memcpy(m2, h.data() + G2, G * 8);
+  if (outside) { outside[0] = h[G]; outside[1] = h[G + 1]; }
+  if (count) *count = d->count;
+  SLQ_TRY(ring_flag_status(flags[1]));
+  if (flags[0]) return fail(SLQ_ENOTCONV, "tridiagonal QL did not converge for at least one probe of an update");
   return SLQ_OK;
 }
 

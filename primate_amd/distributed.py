@@ -57,6 +57,25 @@ def merge_statistics(stats: np.ndarray) -> tuple:
 	return acc.n, acc.mu.item(), var
 
 
+def merge_statistics_vec(stats) -> tuple:
+	"""Fold per-rank (count, mean[G], M2[G]) in rank order, elementwise, with the batch-Welford formula of
+	`Covariance.merge` (the vector form of `merge_statistics`). Returns (count, mean, M2)."""
+	n, mu, S = 0, None, None
+	for cnt, m, s in stats:
+		m, s = np.asarray(m, dtype=np.float64), np.asarray(s, dtype=np.float64)
+		if mu is None:
+			mu, S = np.zeros_like(m), np.zeros_like(s)
+		cnt = int(cnt)
+		if cnt == 0:
+			continue
+		delta = m - mu
+		new_n = n + cnt
+		S = S + (s + (n * cnt / new_n) * (delta * delta))
+		mu = mu + (cnt / new_n) * delta
+		n = new_n
+	return n, mu, S
+
+
 def allreduce_trace(samples: np.ndarray, group=None, device: Optional[str] = None, gather_samples: bool = False):
 	"""The single collective of a sharded hutch(): all-gather each rank's (count, mean, M2) — 3 doubles
 	per rank — and merge in rank order, so every rank ends with the same, order-deterministic result.
@@ -412,3 +431,39 @@ def sharded_xtrace(M, count: int, batch: int = 128, pdf: str = "sphere", seed: i
 	rank, world = dist.get_rank(group), dist.get_world_size(group)
 	shard = (rank, world, lambda src, ncols, dst: allgather_columns(src, ncols, dst, group))
 	return xtrace(M, batch=batch, pdf=pdf, seed=seed, count=count, full=full, device_rng=device_rng, _shard=shard)
+
+
+def sharded_spectral_density(A, nprobes: int = 256, bins: int = 200, interval=None, bw=None, kernel: str = "gaussian", deg: int = 20, orth: int = 3,
+							 batch: int = 256, pdf: str = "rademacher", seed=None, group=None, full: bool = False, **kwargs):  # fmt: skip
+	"""`integrate.spectral_density` with the probe ids sharded over the ranks of `group` (`shard_range`): every rank
+	accumulates its ids on its own GPU, then ONE all-gather of (count, mean[G], M2[G], outside) per rank, folded in rank
+	order (`merge_statistics_vec`), gives every rank the same result. With more than one rank, `interval` and `seed` are
+	required (every rank must use the same grid and the same probe stream)."""
+	import torch.distributed as dist
+
+	from .integrate import _density_accumulate, _density_args, _density_result
+	from .operators import MatrixFunction
+
+	rank, world = (dist.get_rank(group), dist.get_world_size(group)) if dist.is_initialized() else (0, 1)
+	bins, interval, bw = _density_args(kernel, bins, interval, bw, nprobes, batch, pdf)
+	if world > 1 and interval is None:
+		raise ValueError("sharded_spectral_density over several ranks needs an explicit interval (one grid for every rank)")
+	if world > 1 and seed is None:
+		raise ValueError("sharded_spectral_density over several ranks needs a seed (one probe stream for every rank)")
+	M = A if isinstance(A, MatrixFunction) else MatrixFunction(A, deg=deg, orth=orth, **kwargs)
+	lo, hi = shard_range(nprobes, rank, world)
+	mean, m2, outside, cnt, grid, interval, bw = _density_accumulate(M, kernel, bins, interval, bw, lo, hi, int(batch), pdf, seed)
+	if world > 1:
+		import torch
+
+		G = mean.size
+		row = np.concatenate([[float(cnt)], mean, outside, m2])
+		dev = _collective_device(group, None)
+		t = torch.as_tensor(row, device=dev)
+		bufs = [torch.zeros_like(t) for _ in range(world)]
+		dist.all_gather(bufs, t, group=group)
+		rows = [b.cpu().numpy() for b in bufs]
+		stats = [(int(r[0]), r[1 : G + 3], np.concatenate([r[G + 3 :], [0.0, 0.0]])) for r in rows]
+		cnt, mu, S = merge_statistics_vec(stats)
+		mean, outside, m2 = mu[:G], mu[G:], S[:G]
+	return _density_result(kernel, mean, m2, outside, cnt, grid, interval, bw, full)

@@ -496,6 +496,46 @@ class DiagAccumulator:
 			pass
 
 
+class DensityAccumulator:
+	"""Device-resident (count, mean, M2) of a spectral density estimate over a fixed grid (slq_density_*): every
+	`update(plan)` folds the per-probe values ||v||^2 sum_k tau_k K(x_g, theta_k) of a completed run, in probe order.
+	kind: "gaussian" | "lorentzian" (G points, bandwidth bw > 0), "histogram" (G bins: G + 1 edges) or "cdf"
+	(G thresholds)."""
+
+	def __init__(self, kind: str, grid: np.ndarray, bw: float = 0.0, ctx: Optional[Context] = None):
+		if kind not in _capi.DENSITY_KINDS:
+			raise ValueError(f"unknown density kernel '{kind}' (one of {', '.join(_capi.DENSITY_KINDS)})")
+		self.ctx = ctx or default_context()
+		self.kind = kind
+		self.grid = np.ascontiguousarray(grid, dtype=np.float64).ravel()
+		self.ngrid = self.grid.size - (1 if kind == "histogram" else 0)
+		h = C.c_void_p()
+		check(_capi.lib().slq_density_create(self.ctx._h, _capi.DENSITY_KINDS[kind], int(self.ngrid), ptr(self.grid), float(bw), C.byref(h)))
+		self._h = h
+
+	def update(self, plan: LanczosPlan):
+		"""Asynchronous on the context stream; the QL of the run is shared with `plan.quadrature`."""
+		check(_capi.lib().slq_density_update(self._h, plan._h))
+
+	def get(self) -> tuple:
+		"""(mean, M2, outside, count): mean and M2 per grid point, outside = the mean node mass (below, above) the grid."""
+		mean, m2, out = np.zeros(self.ngrid), np.zeros(self.ngrid), np.zeros(2)
+		cnt = C.c_int64()
+		check(_capi.lib().slq_density_get(self._h, ptr(mean), ptr(m2), ptr(out), C.byref(cnt)))
+		return mean, m2, out, cnt.value
+
+	def close(self):
+		if getattr(self, "_h", None):
+			_capi.lib().slq_density_destroy(self._h)
+			self._h = None
+
+	def __del__(self):
+		try:
+			self.close()
+		except Exception:  # noqa: BLE001
+			pass
+
+
 class _CudaArrayView:
 	"""Flat fp64 device array described by the CUDA array interface (v2); keeps its owner alive."""
 
