@@ -167,14 +167,14 @@ typedef struct {
   int ring_slots;    /* S                                                                               */
   int sequence;      /* steps with r_j <= 8: 0 store-and-revisit sweeps, 1 fused recompute passes,      */
                      /* 2 fused passes with the intermediate stored (operators without gather locality),  */
-                     /* 3 sweeps with the fp32 archive ring (SLQ_RING32 opt-in), 4 ring-fed passes with the  */
+                     /* 3 retired: never returned, 4 ring-fed passes with the                               */
                      /* projections taken from Gram rows of the update passes (one gather pass fewer panel reads) */
   int pipelined;     /* dots/update passes use the pipelined row loop                                   */
   int reordered;     /* rows stored in the XCD-aware reverse Cuthill-McKee order                        */
   int upper_alpha;   /* alpha pass walks the upper triangle (exactly symmetric CSR)                     */
   double far_per_row;/* stored nonzeros per row further than 4096 rows from the diagonal                */
   int tiles;         /* fused passes run on LDS workgroup tiles: 0 no, 1 behind barriers, 2 ring-fed (SLQ_TILES) */
-  int fused_alpha;   /* sequence 4 only: the update pass of step j also takes step j + 1's alpha dot (no alpha-only pass after step 0) */
+  int fused_alpha;   /* retired: always 0 (kept so that the struct's layout does not change)             */
 } slq_plan_info;
 int slq_plan_describe(const slq_plan *plan, slq_plan_info *out);
 

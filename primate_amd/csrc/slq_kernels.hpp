@@ -1652,7 +1652,7 @@ __global__ __launch_bounds__(kBlock) void k_axpy_norm(int n, F *W, const F *Wc,
 
 // ---- sweep B (orth > 0): w -= cB*Wc ; partD[i] += W_{t_i} . w ------------------------------------
 // apply_axpy: 0 - w is final as stored; 1 - the three-term step's `w -= cB W_c` (lanczos.h:130) is applied AND stored (first
-// chunk of the MGS-order and fp32-archive sequences, which update w in place between dots); 2 (r04) - it is applied in
+// chunk of the MGS-order sequence, which updates w in place between dots); 2 (r04) - it is applied in
 // registers only: the sweep stays read-only, and k_reorth_update applies the same term (same fma, same order: bitwise the
 // same w) together with its projections and makes the step's one store. A store among 17 read streams costs this sweep a
 // fifth of its rate whatever its flavour (scripts/microbench_reorth.hip: 17 reads 6.5-6.9 TB/s, 17 reads + 1 write 5.2-5.4),
@@ -1800,205 +1800,6 @@ __global__ __launch_bounds__(kBlock) void k_reorth_update(
     }
   }
   block_reduce_columns<F, LPR>(nacc, red, partN + (int64_t)blockIdx.x * bpad + panel * PW);
-}
-
-// ---- opt-in fp32 archive of finished Lanczos vectors (SLQ_RING32, fp64 plans) ---------------------
-// The fp64 ring holds only the three live vectors (slots t % 3); every finished vector is also kept as fp32 in an archive
-// ring (slot t % S32, same panel layout). Reorthogonalisation columns i >= 2 (vectors j-2 and older) are read from the
-// archive - half the bytes - and accumulated in fp64. For the archive rows to be read at full width (16 bytes per lane)
-// these sweeps use their own lane layout: a lane owns FOUR probe columns (4 floats of the archive = one 16-byte load, 4
-// doubles of an fp64 vector = two), LR = PW/4 lanes per row, RW = 64/LR rows per wave instruction.
-typedef double d2a_t __attribute__((ext_vector_type(2)));
-typedef float f4a_t __attribute__((ext_vector_type(4)));
-#ifndef SLQ_CHUNK32
-#define SLQ_CHUNK32 8
-#endif
-constexpr int kReorthChunk32 = SLQ_CHUNK32;  // reorth columns per dots launch (4 accumulators per column and lane)
-
-template <int LPR> struct Geo32 {
-  static constexpr int PW = LPR * 2, LR = PW / 4, RW = 64 / LR;
-};
-// column sums of 4 partials per lane over the RW row groups of a wave and the waves of the block, fixed order
-template <int LPR>
-__device__ __forceinline__ void block_reduce_columns4(const double (&acc)[4], double *red /* kWaves*64*4 */, double *out) {
-  constexpr int PW = Geo32<LPR>::PW, LR = Geo32<LPR>::LR, RW = Geo32<LPR>::RW;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int v = 0; v < 4; ++v) red[(wave * 64 + lane) * 4 + v] = acc[v];
-  __syncthreads();
-  if ((int)threadIdx.x < PW) {
-    const int t = threadIdx.x, c4 = t / 4, v = t % 4;
-    double s = 0.0;
-    for (int w = 0; w < kWaves; ++w)
-#pragma unroll
-      for (int g = 0; g < RW; ++g) s += red[(w * 64 + g * LR + c4) * 4 + v];
-    out[t] = s;
-  }
-  __syncthreads();
-}
-// ring column gi of step j as 4 doubles: W_c / W_p from the fp64 ring, older vectors from the archive
-__device__ __forceinline__ void ring_column4(const double *ring, int64_t slot_stride, int S, const float *ring32, int64_t stride32, int S32,
-                                             int64_t off, int t, int gi, double (&u)[4]) {
-  if (gi >= 2) {
-    const f4a_t x = *(const f4a_t *)(ring32 + (int64_t)ring_slot(t, S32) * stride32 + off);
-#pragma unroll
-    for (int v = 0; v < 4; ++v) u[v] = (double)x[v];
-  } else {
-    const double *p = ring + (int64_t)ring_slot(t, S) * slot_stride + off;
-    const d2a_t a = *(const d2a_t *)p, b = *(const d2a_t *)(p + 2);
-    u[0] = a[0]; u[1] = a[1]; u[2] = b[0]; u[3] = b[1];
-  }
-}
-
-template <int LPR>
-__global__ __launch_bounds__(kBlock) void k_reorth_dot32(
-    int n, double *ring, int64_t slot_stride, int S, int j, int i0, int rc, int apply_axpy, const double *__restrict__ coefB,
-    double *__restrict__ partD /* [rc][nblk][bpad] */, int bpad, const float *__restrict__ ring32, int64_t stride32, int S32) {
-  constexpr int PW = Geo32<LPR>::PW, LR = Geo32<LPR>::LR, RW = Geo32<LPR>::RW;
-  __shared__ double red[kWaves * 64 * 4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int g = lane / LR, c4 = lane % LR;
-  const int panel = blockIdx.y;
-  const int64_t poff = (int64_t)panel * n * PW + c4 * 4;
-  double *W = ring + (int64_t)((j + 1) % S) * slot_stride + poff;
-  const double *Wc = ring + (int64_t)(j % S) * slot_stride + poff;
-  double cb[4] = {0.0, 0.0, 0.0, 0.0};
-  if (apply_axpy) {
-#pragma unroll
-    for (int v = 0; v < 4; ++v) cb[v] = coefB[panel * PW + c4 * 4 + v];
-  }
-  double dacc[kReorthChunk32][4];
-#pragma unroll
-  for (int i = 0; i < kReorthChunk32; ++i)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) dacc[i][v] = 0.0;
-  const int stride = gridDim.x * kWaves * RW;
-  for (int row = (blockIdx.x * kWaves + wave) * RW + g; row < n; row += stride) {
-    const int64_t ro = (int64_t)row * PW;
-    d2a_t wa = *(const d2a_t *)(W + ro), wb = *(const d2a_t *)(W + ro + 2);
-    if (apply_axpy) {
-      const d2a_t ca = *(const d2a_t *)(Wc + ro), cc = *(const d2a_t *)(Wc + ro + 2);
-      wa[0] -= cb[0] * ca[0]; wa[1] -= cb[1] * ca[1]; wb[0] -= cb[2] * cc[0]; wb[1] -= cb[3] * cc[1];
-      *(d2a_t *)(W + ro) = wa;
-      *(d2a_t *)(W + ro + 2) = wb;
-    }
-    const double w[4] = {wa[0], wa[1], wb[0], wb[1]};
-    double u[kReorthChunk32][4];
-#pragma unroll
-    for (int i = 0; i < kReorthChunk32; ++i)
-      if (i < rc) ring_column4(ring, slot_stride, S, ring32, stride32, S32, poff + ro, j - i0 - i, i0 + i, u[i]);
-#pragma unroll
-    for (int i = 0; i < kReorthChunk32; ++i)
-      if (i < rc) {
-#pragma unroll
-        for (int v = 0; v < 4; ++v) dacc[i][v] += u[i][v] * w[v];
-      }
-  }
-  const int64_t nblk = gridDim.x;
-#pragma unroll
-  for (int i = 0; i < kReorthChunk32; ++i)
-    if (i < rc) block_reduce_columns4<LPR>(dacc[i], red, partD + ((int64_t)i * nblk + blockIdx.x) * bpad + panel * PW);
-}
-
-template <int LPR>
-__global__ __launch_bounds__(kBlock) void k_reorth_update32(
-    int n, double *ring, int64_t slot_stride, int S, int j, int i0, int r, const double *__restrict__ gamma /* [r][bpad], offset to i0 */,
-    double *__restrict__ partN, int bpad, float *ring32, int64_t stride32, int S32, int archive /* w is final: store it as fp32 too */,
-    unsigned long long *__restrict__ cols_stat, int skip_zero_cols /* as k_reorth_update */) {
-  constexpr int PW = Geo32<LPR>::PW, LR = Geo32<LPR>::LR, RW = Geo32<LPR>::RW;
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  double *red = (double *)lds_raw;               // kWaves*64*4 doubles
-  double *gl = red + kWaves * 64 * 4;            // r * PW
-  int *fl = (int *)(gl + (size_t)r * PW);        // r flags, then the list of the columns to read and its length (r + 1 ints)
-  int *lst = fl + r;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int g = lane / LR, c4 = lane % LR;
-  const int panel = blockIdx.y;
-  const int64_t poff = (int64_t)panel * n * PW + c4 * 4;
-  for (int t = threadIdx.x; t < r; t += kBlock) fl[t] = 0;
-  __syncthreads();
-  for (int t = threadIdx.x; t < r * PW; t += kBlock) {
-    const double gv = gamma[(int64_t)(t / PW) * bpad + panel * PW + (t % PW)];
-    gl[t] = gv;
-    if (gv != 0.0) fl[t / PW] = 1;
-  }
-  __syncthreads();
-  // columns nobody of this panel projects on are not read (k_reorth_update, r04): the list of the others, ascending - the order of the subtractions is kept
-  if (threadIdx.x == 0) {
-    int m = 0;
-    for (int i = 0; i < r; ++i)
-      if (fl[i] || !skip_zero_cols) lst[m++] = i;
-    lst[r] = m;
-    if (cols_stat && blockIdx.x == 0) {
-      atomicAdd(cols_stat, (unsigned long long)m);
-      atomicAdd(cols_stat + 1, (unsigned long long)r);
-    }
-  }
-  __syncthreads();
-  const int nlive = lst[r];
-  double *W = ring + (int64_t)((j + 1) % S) * slot_stride + poff;
-  float *W32 = ring32 + (int64_t)ring_slot(j + 1, S32) * stride32 + poff;
-  double nacc[4] = {0.0, 0.0, 0.0, 0.0};
-  const int stride = gridDim.x * kWaves * RW;
-  for (int row = (blockIdx.x * kWaves + wave) * RW + g; row < n; row += stride) {
-    const int64_t ro = (int64_t)row * PW;
-    const d2a_t wa = *(const d2a_t *)(W + ro), wb = *(const d2a_t *)(W + ro + 2);
-    double w[4] = {wa[0], wa[1], wb[0], wb[1]};
-    int ii = 0;
-    for (; ii + 4 <= nlive; ii += 4) {  // four columns' loads in flight
-      double u[4][4];
-      int ci[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        ci[q] = lst[ii + q];
-        ring_column4(ring, slot_stride, S, ring32, stride32, S32, poff + ro, j - i0 - ci[q], i0 + ci[q], u[q]);
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const d2a_t ga = *(const d2a_t *)(gl + ci[q] * PW + c4 * 4), gb = *(const d2a_t *)(gl + ci[q] * PW + c4 * 4 + 2);
-        w[0] -= ga[0] * u[q][0]; w[1] -= ga[1] * u[q][1]; w[2] -= gb[0] * u[q][2]; w[3] -= gb[1] * u[q][3];
-      }
-    }
-    for (; ii < nlive; ++ii) {
-      const int i = lst[ii];
-      double u[4];
-      ring_column4(ring, slot_stride, S, ring32, stride32, S32, poff + ro, j - i0 - i, i0 + i, u);
-      const d2a_t ga = *(const d2a_t *)(gl + i * PW + c4 * 4), gb = *(const d2a_t *)(gl + i * PW + c4 * 4 + 2);
-      w[0] -= ga[0] * u[0]; w[1] -= ga[1] * u[1]; w[2] -= gb[0] * u[2]; w[3] -= gb[1] * u[3];
-    }
-    d2a_t oa, ob;
-    oa[0] = w[0]; oa[1] = w[1]; ob[0] = w[2]; ob[1] = w[3];
-    *(d2a_t *)(W + ro) = oa;
-    *(d2a_t *)(W + ro + 2) = ob;
-    if (archive) {
-      f4a_t y;
-#pragma unroll
-      for (int v = 0; v < 4; ++v) y[v] = (float)w[v];
-      *(f4a_t *)(W32 + ro) = y;
-    }
-#pragma unroll
-    for (int v = 0; v < 4; ++v) nacc[v] += w[v] * w[v];
-  }
-  block_reduce_columns4<LPR>(nacc, red, partN + (int64_t)blockIdx.x * bpad + panel * PW);
-}
-
-// fp64 panel slot -> fp32 archive slot (the probes, vector 0 of a run)
-template <int LPR>
-__global__ __launch_bounds__(kBlock) void k_archive32(int n, const double *__restrict__ W, float *__restrict__ W32) {
-  constexpr int PW = Geo<double, LPR>::PW, RPW = Geo<double, LPR>::RPW;
-  typedef double d2_t __attribute__((ext_vector_type(2)));
-  typedef float f2_t __attribute__((ext_vector_type(2)));
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int g = lane / LPR, cl = lane % LPR;
-  const int64_t poff = (int64_t)blockIdx.y * n * PW + cl * 2;
-  const int stride = gridDim.x * kWaves * RPW;
-  for (int row = (blockIdx.x * kWaves + wave) * RPW + g; row < n; row += stride) {
-    const d2_t x = *(const d2_t *)(W + poff + (int64_t)row * PW);
-    f2_t y;
-    y[0] = (float)x[0];
-    y[1] = (float)x[1];
-    *(f2_t *)(W32 + poff + (int64_t)row * PW) = y;
-  }
 }
 
 // ---- per-step scalar kernels ("finalize"): partials -> alpha / beta / next coefficients ---------
@@ -2158,16 +1959,11 @@ __global__ __launch_bounds__(kFinThreads) void k_fin_adots(StepState st, const d
 // 2-8 columns behind a three-term step only ever removes rounding-level components, most of them below the
 // reference's own threshold (lanczos.h:53,62).
 // k_fin_gram: blockIdx.y = i as in k_fin_adots. part: alpha partials of the alpha-only pass.
-// part2 / nblk2 (may be 0) / raw: the alpha dot taken by the previous step's fused update pass (slq_ring_fa.hpp) and the edge kernel's share of it
-// (k_alpha_edges) - raw sums W_j . (A W_j), normalised here by 1 / nu_j^2 (= coefA^2) instead of term by term.
-__global__ __launch_bounds__(kFinThreads) void k_fin_gram(StepState st, const double *__restrict__ part, int nblk, int j, int RC, double orth_tol,
-                                                          const double *__restrict__ part2, int nblk2, int raw) {
+__global__ __launch_bounds__(kFinThreads) void k_fin_gram(StepState st, const double *__restrict__ part, int nblk, int j, int RC, double orth_tol) {
   __shared__ double red4[kFinThreads];
   const int i = blockIdx.y;
   const int col = blockIdx.x * 64 + (threadIdx.x & 63);
-  double a_raw = sum_partials(part, nblk, st.bpad, col, red4);
-  if (nblk2 > 0) a_raw += sum_partials(part2, nblk2, st.bpad, col, red4);
-  if (raw && col < st.bpad) a_raw *= st.coefA[col] * st.coefA[col];
+  const double a_raw = sum_partials(part, nblk, st.bpad, col, red4);
   if ((threadIdx.x >> 6) == 0 && col < st.bpad) {
     constexpr int R1 = kFusedMaxR + 1;
     const int64_t bp = st.bpad;
@@ -2990,27 +2786,6 @@ __global__ __launch_bounds__(64) void k_gemm_nn(int n, double *OUT, int64_t ldo,
       }
     }
   }
-}
-
-// The upper-triangle entries that cross from one XCD chunk into the next: alpha's share of them, after the pass (a kernel boundary
-// makes every chunk's rows visible everywhere). One wave per edge and iteration: acc += val * W[r] * W[c] (val = the doubled
-// off-diagonal entry, as in the upper-triangle streams); per-block column sums into out[blockIdx.x][bpad].
-template <typename F, int LPR>
-__global__ __launch_bounds__(kBlock) void k_alpha_edges(int n, int nedges, const int32_t *__restrict__ er, const int32_t *__restrict__ ec, const F *__restrict__ ev,
-                                                        const F *__restrict__ W /* slot of W_{j+1} */, double *__restrict__ out, int bpad) {
-  using VF = typename VecT<F>::type;
-  constexpr int V = Geo<F, LPR>::V, PW = Geo<F, LPR>::PW;
-  static_assert(LPR == 64, "whole-row panels");
-  __shared__ double red[kWaves * 64 * V];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int panel = blockIdx.y;
-  const F *Wp = W + (int64_t)panel * n * PW + lane * V;
-  VF acc = (VF)(F)0;
-  for (int e = blockIdx.x * kWaves + wave; e < nedges; e += gridDim.x * kWaves) {
-    const VF a = *(const VF *)(Wp + (int64_t)er[e] * PW), b = *(const VF *)(Wp + (int64_t)ec[e] * PW);
-    acc += (ev[e] * a) * b;
-  }
-  block_reduce_columns<F, LPR>(acc, red, out + (int64_t)blockIdx.x * bpad + panel * PW);
 }
 
 }  // namespace slq

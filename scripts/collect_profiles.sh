@@ -53,7 +53,7 @@ if [ "$PART" = "configs" ] || [ "$PART" = "all" ]; then
   echo "== configs[2]..[4] at full size (scripts/run_configs.py), then configs[3] / [4] under rocprofv3 (scripts/profile_configs.sh)"
   rm -f $ROOT/gpurun_out/${TAG}_configs.json
   RUN_TAG=$TAG python3 $ROOT/scripts/run_configs.py c3 c3x c4 > $OUT/run_configs.log 2>&1
-  C5_RING32=both RUN_TAG=$TAG python3 $ROOT/scripts/run_configs.py c5 >> $OUT/run_configs.log 2>&1
+  RUN_TAG=$TAG python3 $ROOT/scripts/run_configs.py c5 >> $OUT/run_configs.log 2>&1
   RUN_TAG=$TAG bash $ROOT/scripts/profile_configs.sh ${TAG}_configs
   python3 - "$ROOT/gpurun_out/${TAG}_configs.json" "$SHA" "$OUT/pmc_summary.json" <<'PY'
 import json, sys

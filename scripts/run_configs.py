@@ -159,7 +159,6 @@ if "c5" in which:
 	## one GPU's share of configs[4] as worded - eigencount by the step function, full reorthogonalisation: 2048 probes / 8 GPUs
 	## = 256 probes, in batches of as many as the ring admits. The operator is the symmetric circulant band of
 	## tests/test_gpu_fullsize.py (15 per row, closed-form spectrum), the cut its median: the count is known exactly.
-	## C5_RING32=1 runs the opt-in fp32 archive of finished vectors: twice the probes per batch.
 	from test_gpu_fullsize import circulant_band
 
 	n, k, share = 10_000_000, 80, int(os.environ.get("C5_PROBES", 256))
@@ -168,30 +167,26 @@ if "c5" in which:
 	exact = int(np.count_nonzero(lam >= cut))
 	del lam
 	op = DeviceOperator(A)
-	for ring32 in ([0, 1] if os.environ.get("C5_RING32", "both") == "both" else [int(os.environ["C5_RING32"])]):
-		B = int(os.environ.get("C5_BATCH", 64 if ring32 else 32))  # 81 ring slots x n x 32 x 8 B = 207 GB of the 288 GB
-		if ring32:
-			os.environ["SLQ_RING32"] = "1"
-		plan = LanczosPlan(op, B, k, k)
-		plan.profile_enable(True)
-		plan.profile_read(reset=True)
-		qs = []
-		op.ctx.synchronize()
-		t0 = time.time()
-		for c in range(0, share, B):
-			plan.generate_probes("rademacher", seed=1234, probe_offset=c)
-			plan.run()
-			qs.append(plan.quadrature("step", c=cut))
-			print(f"c5 ring32={ring32} batch at probe {c}: {time.time() - t0:.1f} s", flush=True)
-		dt = time.time() - t0
-		q = np.concatenate(qs)
-		key = "configs[4]_one_gpu_share" + ("_ring32" if ring32 else "")
-		out[key] = dict(n=n, nnz=int(A.nnz), k=k, probes=share, batch=B, orth=k, fun=f"step(c={cut:.6f})", seconds=round(dt, 3), probe_matvecs_per_s=round(share * k / dt, 1),
-		                eigencount=float(q.mean()), exact_count=exact, rel_err=float(q.mean() / exact - 1), stderr=float(q.std(ddof=1) / np.sqrt(share)),
-		                **lanczos_roofline(plan, A, B, k, k, share // B))  # fmt: skip
-		print(json.dumps({"c5": out[key]}), flush=True)
-		plan.close()
-		os.environ.pop("SLQ_RING32", None)
+	B = int(os.environ.get("C5_BATCH", 32))  # 81 ring slots x n x 32 x 8 B = 207 GB of the 288 GB
+	plan = LanczosPlan(op, B, k, k)
+	plan.profile_enable(True)
+	plan.profile_read(reset=True)
+	qs = []
+	op.ctx.synchronize()
+	t0 = time.time()
+	for c in range(0, share, B):
+		plan.generate_probes("rademacher", seed=1234, probe_offset=c)
+		plan.run()
+		qs.append(plan.quadrature("step", c=cut))
+		print(f"c5 batch at probe {c}: {time.time() - t0:.1f} s", flush=True)
+	dt = time.time() - t0
+	q = np.concatenate(qs)
+	key = "configs[4]_one_gpu_share"
+	out[key] = dict(n=n, nnz=int(A.nnz), k=k, probes=share, batch=B, orth=k, fun=f"step(c={cut:.6f})", seconds=round(dt, 3), probe_matvecs_per_s=round(share * k / dt, 1),
+	                eigencount=float(q.mean()), exact_count=exact, rel_err=float(q.mean() / exact - 1), stderr=float(q.std(ddof=1) / np.sqrt(share)),
+	                **lanczos_roofline(plan, A, B, k, k, share // B))  # fmt: skip
+	print(json.dumps({"c5": out[key]}), flush=True)
+	plan.close()
 	op.close()
 
 out_path.parent.mkdir(exist_ok=True)

@@ -849,23 +849,6 @@ def test_update_sweep_skips_columns_nobody_projects_on(oracle, eng, monkeypatch)
 	rd0, off0 = res["0"][2]
 	assert off1 == off0 > 0 and rd0 == off0 and rd1 < 0.5 * off1, (rd1, off1, rd0, off0)
 	np.testing.assert_allclose(res["1"][0][[0, 39]], oracle.quad_batch(A, np.asfortranarray(X[:, [0, 39]]), 24, 24, fun="log", fresh_q=True), rtol=1e-10)
-	## the same with the fp32 archive of finished vectors (SLQ_RING32=1, k_reorth_update32): skipping zero columns is bitwise neutral there too
-	monkeypatch.setenv("SLQ_RING32", "1")
-	r32 = {}
-	for skip in ("1", "0"):
-		monkeypatch.setenv("SLQ_SWEEP_SKIP", skip)
-		plan = eng.LanczosPlan(op, 40, 24, 24)
-		assert plan.describe()["sequence"] == "sweeps_ring32"
-		plan.set_probes(X)
-		plan.run()
-		r32[skip] = (plan.quadrature("log"), plan.tridiag(), plan.sweep_columns())
-		plan.close()
-	monkeypatch.delenv("SLQ_SWEEP_SKIP")
-	monkeypatch.delenv("SLQ_RING32")
-	assert np.array_equal(r32["1"][0], r32["0"][0]) and all(np.array_equal(a, b) for a, b in zip(r32["1"][1], r32["0"][1]))
-	## (hardly anything IS skipped there: against vectors rounded to fp32 the projections are 1e-8, not below 2 eps sqrt(n) - measured 251 of 300 columns read)
-	assert r32["1"][2][0] <= r32["1"][2][1] and r32["0"][2][0] == r32["0"][2][1], (r32["1"][2], r32["0"][2])
-	np.testing.assert_allclose(r32["1"][0], res["1"][0], rtol=1e-7)
 	op.close()
 	## an operator on which the window's projections are NOT small: dense SPD with eigenvalues over seven decades, full reorthogonalisation
 	m = 300
@@ -885,19 +868,15 @@ def test_update_sweep_skips_columns_nobody_projects_on(oracle, eng, monkeypatch)
 	np.testing.assert_allclose(got, oracle.quad_batch(D, Xd, 40, 40, fun="log", fresh_q=True), rtol=1e-8)
 
 
-def test_opt_in_fp32_archive_ring(oracle, eng, monkeypatch):
-	"""SLQ_RING32=1 (opt-in): finished Lanczos vectors archived as fp32, reorthogonalisation columns j-2 and older read
-	from the archive. Not bit-compatible by construction; the bar here is 1e-7 relative per probe against the oracle
-	(the north_star's is 1e-6; measured worst case 2e-9, profiles/r02_ring32_eval.json). Only plans with reorthogonalisation
-	deeper than 8 columns and no kept basis take the path."""
+def test_deep_reorthogonalisation_on_random_graph(oracle, eng):
+	"""Reorthogonalisation deeper than the fused passes reach (orth 12: sweeps from step 9 on; orth 40: full) on a random graph whose
+	gathers have no locality: per-probe values against the oracle, and every probe runs all deg steps."""
 	A = random_spd_graph(3000, 6.0, seed=21)
 	rng = np.random.default_rng(4)
 	X = np.asfortranarray(rng.standard_normal((3000, 70)))
 	op = eng.DeviceOperator(A)
-	monkeypatch.setenv("SLQ_RING32", "1")
 	for deg, orth in ((40, 12), (40, 40)):
 		plan = eng.LanczosPlan(op, 70, deg, orth)
-		assert plan.describe()["sequence"] == "sweeps_ring32" and plan.describe()["ring_slots"] == 3
 		plan.set_probes(X)
 		plan.run()
 		got = plan.quadrature("log")
@@ -905,11 +884,8 @@ def test_opt_in_fp32_archive_ring(oracle, eng, monkeypatch):
 		assert np.all(steps == deg)
 		plan.close()
 		ref = oracle.quad_batch(A, X, deg, orth, fun="log", fresh_q=True)
-		np.testing.assert_allclose(got, ref, rtol=1e-7)
-	assert eng.LanczosPlan(op, 70, 40, 3).describe()["sequence"] != "sweeps_ring32"  # shallow reorthogonalisation: untouched
-	assert eng.LanczosPlan(op, 8, 40, 40, keep_basis=True).describe()["sequence"] != "sweeps_ring32"  # kept basis: untouched
-	monkeypatch.delenv("SLQ_RING32")
-	assert eng.LanczosPlan(op, 70, 40, 40).describe()["sequence"] != "sweeps_ring32"
+		np.testing.assert_allclose(got, ref, rtol=1e-7, err_msg=f"orth={orth}")
+	op.close()
 
 
 @pytest.mark.parametrize("variant", ["1", "2"])
@@ -1063,12 +1039,10 @@ def test_alpha_pass_stream_forms(oracle, eng, monkeypatch, env):
 		op.close()
 
 
-def test_opt_in_fused_update_and_alpha_pass(oracle, eng, monkeypatch):
-	"""SLQ_FUSED_ALPHA=1 (opt-in, slq_ring_fa.hpp): the update pass of step j also takes step j + 1's alpha dot a fixed lag of tile
-	rounds behind its own write front (same-XCD hand-off through L2 counters), entries that cross XCD chunks by a small edge kernel.
-	Same alpha as the alpha-only pass up to the order of the sum (q_c . (A q_c - beta q_p), lanczos.h:127-129): per-probe values
-	against the oracle on a 2-D and a 3-D grid, orth 1..3, and against the default sequence to rounding. Measured slower than the
-	two passes it replaces, hence not the default."""
+def test_gram_sequence_on_ring_fed_tiles(oracle, eng, monkeypatch):
+	"""The default sequence of wide panels on ring-fed tiles (SLQ_TILES=2): an alpha-only pass, projections from the Gram rows of
+	the update passes (sequence "fused_gram"), orth 1..3, on a 2-D and a 3-D grid. Per-probe values against the oracle at the
+	first, middle and last probe of a two-panel batch."""
 	monkeypatch.setenv("SLQ_TILES", "2")
 	rng = np.random.default_rng(41)
 	for A in (laplacian_2d(200), laplacian_3d(40)):
@@ -1078,17 +1052,12 @@ def test_opt_in_fused_update_and_alpha_pass(oracle, eng, monkeypatch):
 		cols = [0, P // 2, P - 1]
 		op = eng.DeviceOperator(A)
 		for orth in (1, 2, 3):
-			base = eng.quad_batch(op, X, 14, orth, fun="log")
-			monkeypatch.setenv("SLQ_FUSED_ALPHA", "1")
 			plan = eng.LanczosPlan(op, P, 14, orth)
-			assert plan.describe()["fused_alpha"] == 1 and plan.describe()["sequence"] == "fused_gram"
-			plan.set_probes(X)
-			plan.run()
-			got = plan.quadrature("log")
+			assert plan.describe()["sequence"] == "fused_gram", plan.describe()
 			plan.close()
-			monkeypatch.delenv("SLQ_FUSED_ALPHA")
-			np.testing.assert_allclose(got, base, rtol=1e-12)
-			np.testing.assert_allclose(got[cols], oracle.quad_batch(A, np.asfortranarray(X[:, cols]), 14, orth, fun="log", fresh_q=True), rtol=1e-10)
+			got = eng.quad_batch(op, X, 14, orth, fun="log")
+			ref = oracle.quad_batch(A, np.asfortranarray(X[:, cols]), 14, orth, fun="log", fresh_q=True)
+			np.testing.assert_allclose(got[cols], ref, rtol=1e-10, err_msg=f"n={n} orth={orth}")
 		op.close()
 
 
