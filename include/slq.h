@@ -189,7 +189,8 @@ int slq_plan_generate_probes(slq_plan *plan, int pdf, uint64_t seed, uint64_t pr
 /* Copy the current probes back as a column-major n x nprobes host panel. */
 int slq_plan_get_probes(slq_plan *plan, void *X, int64_t ldx);
 
-/* deg Lanczos steps for all probes (asynchronous on the context stream). */
+/* deg Lanczos steps for all probes (asynchronous on the context stream). Without keep_basis the
+ * residual slot deg % S holds no defined value after the run: the last step need not store W_deg. */
 int slq_plan_run(slq_plan *plan, double rtol);
 /* alpha, beta: nprobes x (deg+1) row-major of the plan dtype; steps: nprobes ints. Any may be
  * NULL. Synchronises. */

@@ -16,29 +16,42 @@ from .integrate import quadrature
 
 ## Operators already on the device, by CONTENT of the sparse matrix they were built from: creating one costs 0.1-0.2 s of host-side analysis
 ## (row order, tile clusters, streams) and an upload, a Lanczos run over it 0.06 s - and the reference's MatrixFunction(A) costs nothing to construct
-## (src/primate/operators.py:55-100), so drivers build one per call. Key: shape, dtype, GPU and a 64-bit hash of indptr / indices / data (xxh3: ~10 GB/s,
-## 6 ms for configs[1]); values are weak references, so an operator lives exactly as long as something uses it. A matrix modified in place hashes
-## differently and gets a new operator.
+## (src/primate/operators.py:55-100), so drivers build one per call. Key: shape, dtype, GPU and a 64-bit hash of indptr / indices / data (xxh3 when
+## xxhash is installed: ~10 GB/s, 6 ms for configs[1]; BLAKE2b from the standard library otherwise); values are weak references, so an operator lives
+## exactly as long as something uses it. A matrix modified in place hashes differently and gets a new operator. Sparse matrices of other formats are
+## hashed as the CSR the operator is built from.
 _OPERATORS: "weakref.WeakValueDictionary" = None
 
 
-def _sparse_key(A, dtype):
+def _content_hash(arrays) -> int:
 	try:
 		import xxhash
-	except Exception:  # noqa: BLE001
-		return None
+	except ImportError:
+		xxhash = None
+	if xxhash is not None:
+		h = xxhash.xxh3_64()
+	else:
+		import hashlib
+
+		h = hashlib.blake2b(digest_size=8)
+	for arr in arrays:
+		h.update(memoryview(np.ascontiguousarray(arr)).cast("B"))
+	return h.intdigest() if xxhash is not None else int.from_bytes(h.digest(), "little")
+
+
+def _sparse_key(A, dtype):
 	import scipy.sparse as sp
 
-	if not (sp.issparse(A) and A.format == "csr"):
+	if not sp.issparse(A):
 		return None
-	h = xxhash.xxh3_64()
-	for arr in (A.indptr, A.indices, A.data):
-		h.update(memoryview(np.ascontiguousarray(arr)).cast("B"))
+	M = A if A.format == "csr" else sp.csr_matrix(A)
+	if not M.has_sorted_indices:  # (the operator is built from the sorted form)
+		M = M.sorted_indices()
 	ctx = engine.default_context()
 	import os
 
 	switches = tuple(sorted((k, v) for k, v in os.environ.items() if k.startswith("SLQ_")))  # (libslq reads its switches when an operator is created)
-	return (A.shape, str(A.dtype), str(np.dtype(dtype if dtype is not None else A.dtype)), ctx.device, int(A.nnz), h.intdigest(), switches)
+	return (M.shape, str(M.dtype), str(np.dtype(dtype if dtype is not None else M.dtype)), ctx.device, int(M.nnz), _content_hash((M.indptr, M.indices, M.data)), switches)
 
 
 def _as_device_operator(A, dtype=None) -> engine.DeviceOperator:

@@ -121,10 +121,11 @@ while time.time() - t0 < budget:
 			elif orth < deg:
 				## a partial window that has LOST orthogonality (r04, seed 22 case 4705: n = 1488, k = 37, orth = 1 - alpha of any two implementations parts ways at
 				## step 25 by O(1), the quadrature moves by 1e-7): the value is determined no better than the distance between the oracle's own partial-
-				## and full-reorthogonalisation runs on the same probes, per probe
+				## and full-reorthogonalisation runs on the same probes, per probe - but never above north_star's 1e-6: a miss
+				## beyond that counts as a failure whatever the spread (tests/test_gpu_parity.py pins this class of case)
 				ref_full = oracle.quad_batch(Ad, X, deg, deg, fun=fun, fresh_q=True, prefer="csr", **kw)
 				spread = np.abs(ref_full - ref) / np.maximum(np.abs(ref), 1e-300)
-				if np.all(rel <= np.maximum(3.0 * spread, tol)):
+				if np.all(rel <= np.maximum(3.0 * spread, tol)) and np.all(rel <= 1e-6):
 					bad = False
 					lost_orth_skipped += 1
 					print(f"note: kind={kind} n={n} P={P} deg={deg} orth={orth} fun={fun}: err {np.nanmax(rel):.2e} within 3x the oracle's partial-vs-full reorthogonalisation spread {np.max(spread):.2e}", flush=True)

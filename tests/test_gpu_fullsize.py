@@ -263,3 +263,38 @@ def test_config5_eigencount_by_step_function_full_reorth_n1e7(eng):
 	assert abs(est - exact) < 3 * stderr + bracket.mean(), (est, exact, stderr, bracket.mean())
 	assert abs(est / exact - 1) < 0.05
 	assert stderr < 0.01 * n  # full reorthogonalisation: the per-probe counts scatter by well under a per cent of n
+
+
+def test_config5_plan_shape_against_the_oracle(eng, oracle):
+	"""configs[4]'s plan shape at n = 1e6 against the oracle: the circulant band of the test above (same offsets), k = 80,
+	full reorthogonalisation, P = 32 - an 81-slot ring, panels of 32, the generic passes (tiles == 0), the Gram sequence for the
+	steps with up to 8 ring columns handing over to the store-and-revisit sweeps from r = 9 on. Two probes against the oracle:
+	log within 1e-8 per probe, step(c) with the cut inside the dense spectrum within max(1e-8, 30x the oracle's own spread)."""
+	import time
+
+	from test_gpu_parity import oracle_spread
+
+	n, k, P = 10**6, 80, 32
+	A, lam = circulant_band(n)
+	cut = float(np.median(lam)) + 1e-3
+	op = eng.DeviceOperator(A)
+	plan = eng.LanczosPlan(op, P, k, k)
+	info = plan.describe()
+	assert info["tiles"] == 0 and info["panel_width"] == 32 and info["ring_slots"] == k + 1 and info["sequence"] == "fused_gram", info
+	rng = np.random.default_rng(45)
+	X = np.asfortranarray(np.floor(rng.random((n, P)) * 2) * 2 - 1)
+	plan.set_probes(X)
+	plan.run()
+	got = {"log": plan.quadrature("log"), "step": plan.quadrature("step", c=cut)}
+	plan.close()
+	op.close()
+	cols = [0, P - 1]
+	t0 = time.perf_counter()
+	ref, spread = oracle_spread(oracle, A, np.asfortranarray(X[:, cols]), k, k, funs=[("log", {}), ("step", {"c": cut})], seed=5)
+	t_oracle = time.perf_counter() - t0
+	err = {f: np.abs(got[f][cols] - ref[f]) / np.abs(ref[f]) for f in got}
+	bar = max(1e-8, 30.0 * spread["step"].max())
+	print(f"YARDSTICK E circulant_band(1e6) k=80 orth=80 P=32 ({info['sequence']}, sweeps from r=9): log {err['log'].max():.2e} (bar 1e-8, spread {spread['log'].max():.2e}); "
+	      f"step {err['step'].max():.2e} (spread {spread['step'].max():.2e}, bar {bar:.2e}); oracle leg {t_oracle:.1f} s")  # fmt: skip
+	assert np.all(err["log"] <= 1e-8), (err, spread)
+	assert np.all(err["step"] <= bar), (err, spread)

@@ -299,7 +299,7 @@ def test_parallel_rademacher_fill_is_the_same_stream(monkeypatch):
 	assert set(np.unique(outs[1])) == {-1.0, 1.0}
 
 
-def test_bench_starts_its_own_ranks(capfd):
+def test_bench_starts_its_own_ranks(capfd, tmp_path):
 	"""`python bench.py --gpus N` without a launcher: the parent starts N child ranks with RANK / LOCAL_RANK / WORLD_SIZE /
 	MASTER_* set, relays rank 0's stdout only, and returns the worst exit code (one process per GPU). The
 	children here are stubs - no torch, no GPU."""
@@ -310,7 +310,22 @@ def test_bench_starts_its_own_ranks(capfd):
 	out, err = capfd.readouterr()
 	assert rc == 0 and out == "{line 0 0 3 127.0.0.1 True\n"  # rank 0's record and nothing else on stdout
 	assert "line 1 1 3" in err and "line 2 2 3" in err and "[lib] chatter" in err
-	rc = bench.spawn_ranks(2, ["5", "1"], cmd=[sys.executable, "-c", stub])  # rank 1 fails with 5
+	## rank 1 fails with 5 - once rank 0 has exited (a zombie its parent has not reaped yet), so that the parent sees [0, 5]
+	## and not a rank 0 it had to end itself because rank 1 happened to finish first
+	wait0 = stub.rsplit("; sys.exit", 1)[0] + """
+import time
+mark, t_end = sys.argv[3], time.time() + 60
+if r == 0:
+    open(mark + ".tmp", "w").write(str(os.getpid()))
+    os.replace(mark + ".tmp", mark)
+while r == 1 and not os.path.exists(mark) and time.time() < t_end:
+    time.sleep(0.01)
+stat = f"/proc/{open(mark).read()}/stat" if r == 1 else ""
+while r == 1 and time.time() < t_end and os.path.exists(stat) and open(stat).read().rsplit(")", 1)[1].split()[0] not in "ZX":
+    time.sleep(0.01)
+sys.exit(int(sys.argv[1]) if r == int(sys.argv[2]) else 0)
+"""
+	rc = bench.spawn_ranks(2, ["5", "1", str(tmp_path / "rank0")], cmd=[sys.executable, "-c", wait0])
 	out, err = capfd.readouterr()
 	assert rc == 5 and out.startswith("{line 0 0 2") and "exit codes [0, 5]" in err
 	## a rank that hangs is ended by the parent (its own child, by handle), the others' result is kept
@@ -355,3 +370,50 @@ def test_bench_options_of_a_plain_run():
 	assert "--full" in h and "--dump-outputs" in h and "--steps" in h
 	r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
 	assert r.returncode == 2 and "--steps" in r.stderr and r.stdout == ""
+
+
+@pytest.mark.parametrize("hasher", ["xxhash", "stdlib"])
+def test_operator_cache_follows_the_matrix_content(monkeypatch, hasher):
+	"""primate_amd.lanczos keeps device operators by the CONTENT of the sparse matrix (xxh3, or BLAKE2b without xxhash): an
+	in-place edit of A.data builds a new operator, the same content (another object, another format) reuses the live one,
+	and a closed operator is never handed out."""
+	import scipy.sparse as sp
+
+	from primate_amd import engine
+	from primate_amd import lanczos as L
+
+	if hasher == "stdlib":
+		monkeypatch.setitem(sys.modules, "xxhash", None)  # (import xxhash raises ImportError)
+	built = []
+
+	class StubOperator:
+		def __init__(self, A, dtype=None, ctx=None):
+			self._h, self.dtype = object(), np.dtype(dtype if dtype is not None else A.dtype)
+			built.append(self)
+
+		def close(self):
+			self._h = None
+
+	class StubContext:
+		device = 0
+
+	monkeypatch.setattr(engine, "DeviceOperator", StubOperator)
+	monkeypatch.setattr(engine, "default_context", lambda: StubContext())
+	monkeypatch.setattr(L, "_OPERATORS", None)
+	A = sp.random(60, 60, density=0.1, random_state=np.random.default_rng(3), format="csr")
+	A = (A + A.T).tocsr()
+	op = L._as_device_operator(A)
+	assert L._as_device_operator(A) is op and L._as_device_operator(A.copy()) is op and L._as_device_operator(A.tocsc()) is op
+	assert len(built) == 1
+	v5 = A.data[5]
+	A.data[5] += 1.0  # in place: same object, same structure
+	op2 = L._as_device_operator(A)
+	assert op2 is not op and len(built) == 2
+	C = A.tocsc()
+	C.data[0] *= 2.0
+	assert L._as_device_operator(C) not in (op, op2) and len(built) == 3
+	A.data[5] = v5  # back to the first content: the first operator is still alive
+	assert L._as_device_operator(A) is op and len(built) == 3
+	op.close()
+	op3 = L._as_device_operator(A)
+	assert op3 is not op and op3._h is not None and len(built) == 4
