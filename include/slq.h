@@ -192,6 +192,15 @@ int slq_plan_get_probes(slq_plan *plan, void *X, int64_t ldx);
 /* deg Lanczos steps for all probes (asynchronous on the context stream). Without keep_basis the
  * residual slot deg % S holds no defined value after the run: the last step need not store W_deg. */
 int slq_plan_run(slq_plan *plan, double rtol);
+/* Resumable form: runs steps [cur, upto), cur = the number of steps done since the probes were set or generated (0
+ * then). cur < upto <= deg, else SLQ_EINVAL; rtol must equal the one the run began with. The launches are those of
+ * slq_plan_run: slq_plan_run_steps(p, rtol, deg) on fresh probes IS slq_plan_run(p, rtol), and the Jacobi matrix after m
+ * steps is the one a plan of degree m, orth min(orth, m) produces. Between two stages (0 < cur < deg) the entries that
+ * mean "the finished run" (slq_plan_quadrature, slq_plan_fun_action*, slq_plan_get_basis, slq_diag_update,
+ * slq_density_update) return SLQ_EINVAL - use slq_plan_quadrature_at -, and slq_plan_get_tridiag returns the prefix
+ * (zeros beyond it). Plans with stale ring columns (the drop-in slq_lanczos_* path) are not resumable. */
+int slq_plan_run_steps(slq_plan *plan, double rtol, int upto);
+int slq_plan_steps_done(const slq_plan *plan, int *cur);
 /* alpha, beta: nprobes x (deg+1) row-major of the plan dtype; steps: nprobes ints. Any may be
  * NULL. Synchronises. */
 int slq_plan_get_tridiag(slq_plan *plan, void *alpha, void *beta, int32_t *steps);
@@ -201,6 +210,16 @@ int slq_plan_get_tridiag(slq_plan *plan, void *alpha, void *beta, int32_t *steps
  * Synchronises. */
 int slq_plan_quadrature(slq_plan *plan, int fun_id, const double *fun_params, double *quad,
                         double *nodes, double *weights);
+/* Quadrature of the first m <= cur steps. rule 0: the m-point Gauss rule (for m = deg after a full run: what
+ * slq_plan_quadrature returns, bit for bit). rule 1: the (m+1)-point Gauss-Radau rule with a prescribed node at
+ * `endpoint` <= lambda_min(A) (Golub 1973); with the Gauss rule it brackets v^T f(A) v for every f whose derivatives
+ * keep one sign (log, inverse, exp(-t x), powers). nodes / weights: nprobes x (m + rule) row-major doubles or NULL. A
+ * probe that stopped at or before step m has an exact Gauss rule: its Radau value is its Gauss value (returned as the
+ * Gauss rule behind a zero-weight node at the endpoint). An endpoint that is not below the smallest Ritz value of every
+ * probe is SLQ_EINVAL. stage (4 doubles or NULL) = {sum_i quad_i, sum_i quad_i^2, sum_i |quad_i - gauss_i| (0 for rule
+ * 0), nprobes}, reduced on the device in a fixed order (identical runs give identical bits). Synchronises. */
+int slq_plan_quadrature_at(slq_plan *plan, int m, int rule, double endpoint, int fun_id, const double *fun_params,
+                           double *quad, double *nodes, double *weights, double *stage);
 /* Lanczos basis of probe `probe` as a column-major n x deg host array (normalised columns;
  * columns past an early stop are zero). Requires keep_basis. */
 int slq_plan_get_basis(slq_plan *plan, int probe, void *Q, int64_t ldq);
@@ -216,6 +235,13 @@ int slq_plan_fun_action(slq_plan *plan, int fun_id, const double *fun_params, vo
 int slq_quadrature_batch(slq_context *ctx, int nb, int deg, const double *d, const double *e,
                          int fun_id, const double *fun_params, double *quad, double *nodes,
                          double *weights);
+
+/* Stand-alone Gauss-Radau rules of nb Jacobi matrices of size m (d, e as above; beta_m: nb doubles, the coupling of each
+ * matrix to its border = the norm of the Lanczos residual after m steps; beta_m[i] = 0: the Gauss rule behind a
+ * zero-weight node). nodes / weights: nb x (m+1) row-major doubles or NULL; quad[i] = sum_k f(nodes[i,k]) weights[i,k]. */
+int slq_quadrature_radau_batch(slq_context *ctx, int nb, int m, const double *d, const double *e, const double *beta_m,
+                               double endpoint, int fun_id, const double *fun_params, double *quad, double *nodes,
+                               double *weights);
 
 /* Full eigendecomposition of nb symmetric tridiagonals (eigh_tridiag / eigvalsh_tridiag,
  * src/primate/tridiag.py:25-62; what rayleigh_ritz and MatrixFunction._matvec call): d, e as above
@@ -328,6 +354,8 @@ int slq_plan_profile_read(slq_plan *plan, slq_profile *out, int reset);
  *   slq_debug_plan_poke_ring_flag  sets a plan's device word as an aborting workgroup would */
 int slq_debug_ring_flag_status(int flag);
 int slq_debug_plan_poke_ring_flag(slq_plan *plan, int value);
+/* test hook: mark a plan as holding nstale stale ring columns (what the drop-in entry does to its own plan) */
+int slq_debug_plan_mark_stale(slq_plan *plan, int nstale);
 
 /* ---- one-shot entries ---------------------------------------------------------------------------- */
 /* P probes in one call: the batched counterpart of the Python loop at

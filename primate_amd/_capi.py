@@ -71,6 +71,11 @@ _SIGNATURES = {
 	"slq_plan_generate_probes": (C.c_int, [_P, C.c_int, C.c_uint64, C.c_uint64]),
 	"slq_plan_get_probes": (C.c_int, [_P, _P, C.c_int64]),
 	"slq_plan_run": (C.c_int, [_P, C.c_double]),
+	"slq_plan_run_steps": (C.c_int, [_P, C.c_double, C.c_int]),
+	"slq_plan_steps_done": (C.c_int, [_P, C.POINTER(C.c_int)]),
+	"slq_plan_quadrature_at": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_int, _P, _P, _P, _P, _P]),
+	"slq_quadrature_radau_batch": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_double, C.c_int, _P, _P, _P, _P]),
+	"slq_debug_plan_mark_stale": (C.c_int, [_P, C.c_int]),
 	"slq_plan_get_tridiag": (C.c_int, [_P, _P, _P, _P]),
 	"slq_plan_quadrature": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
 	"slq_plan_get_basis": (C.c_int, [_P, C.c_int, _P, C.c_int64]),

@@ -27,6 +27,7 @@
 #include "slq_ring.hpp"  // (RingGeo constants: no kernel of it is instantiated here)
 #include "slq_build.hpp"  // an operator's derived data built on the device
 #include "slq_density.hpp"  // spectral density accumulator (slq_density_*)
+#include "slq_radau.hpp"    // prefix quadrature, Gauss-Radau rule, stage statistics (slq_plan_quadrature_at)
 
 using namespace slq;
 
@@ -216,9 +217,23 @@ struct slq_plan {
   std::vector<char> hbuf;  // host staging for callback operators
   size_t bytes;
   int nstale;                 // > 0: the reorthogonalisation also sees nstale preloaded vectors t = -1 .. -nstale
-  hipGraphExec_t graph_exec;  // the k-step launch sequence captured once per (plan, rtol, variant)
-  double graph_rtol;
-  unsigned graph_variant;
+  // the launch sequence of steps [j0, j1) captured once per (j0, j1, rtol, variant); the one-shot run is the entry (0, deg)
+  struct GraphEntry {
+    int j0, j1;
+    double rtol;
+    unsigned variant;
+    hipGraphExec_t exec;
+    bool xt_out;  // prev_xt after step j1 - 1
+  };
+  std::vector<GraphEntry> graphs;  // (at most kGraphCacheMax: the oldest entry leaves first)
+  // resumable runs (slq_plan_run_steps): steps done since the probes were set, the rtol the run began with, and the one
+  // piece of host state a step hands to the next - the previous update pass produced the cross term W_j.W_{j-1}
+  int cur = 0;
+  double run_rtol = 0.0;
+  bool prev_xt = false;
+  // slq_plan_quadrature_at (allocated by its first call): quad | gauss | stage[4] | nodes | weights (P x (deg + 1) each), two flag words
+  double *at_d = nullptr;
+  int *at_flags = nullptr;
   Switches sw;
   bool pipelined;             // dots/update passes run the pipelined row loop (slq_plan_create)
   int dense_ks;               // dense MFMA operator with big tiles: K split over this many workgroups per row tile (0: 16-row kernel)
@@ -2424,7 +2439,9 @@ extern "C" int slq_plan_destroy(slq_plan *p) {
   hipStreamSynchronize(p->ctx->stream);
   for (auto &ev : p->events) { hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
   for (auto &ev : p->pool) { hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
-  if (p->graph_exec) hipGraphExecDestroy(p->graph_exec);
+  for (auto &g : p->graphs) hipGraphExecDestroy(g.exec);
+  if (p->at_d) hipFree(p->at_d);
+  if (p->at_flags) hipFree(p->at_flags);
   if (p->ring) hipFree(p->ring);
   if (p->T) hipFree(p->T);
   if (p->T2) hipFree(p->T2);
@@ -2620,9 +2637,6 @@ extern "C" int slq_plan_create(slq_context *ctx, slq_operator *op, int nprobes, 
   p->st.deg = deg;
   p->nodes_d = p->quad_d + bp;
   p->weights_d = p->nodes_d + bp * (size_t)deg;
-  p->graph_exec = nullptr;
-  p->graph_rtol = 0.0;
-  p->graph_variant = 0;
   p->nstale = 0;
   {
     hipError_t ze = hipMemsetAsync(p->scal, 0, nscal * 8, ctx->stream);
@@ -2921,6 +2935,7 @@ static int init_from_probes(slq_plan *p, int sphere, bool unit_entries = false) 
   HIP_TRY(hipGetLastError());
   p->probes_ready = true;
   p->ran = false;
+  p->cur = 0;
   return SLQ_OK;
 }
 
@@ -3315,8 +3330,9 @@ static int launch_ring_gen(slq_plan *p, int pass, int rc, dim3 grid, hipStream_t
   return SLQ_OK;
 }
 
-// enqueue the deg-step launch sequence on the context stream (also run under stream capture)
-static int enqueue_run(slq_plan *p, double rtol, int fused_mode, bool nt) {
+// enqueue the launch sequence of steps [j0, j1) on the context stream (also run under stream capture). Between steps the whole
+// state of a run lives on the device; the host carries p->prev_xt, read here at j0 and left as step j1 - 1 sets it.
+static int enqueue_run(slq_plan *p, double rtol, int fused_mode, bool nt, int j0, int j1) {
   const bool fused = fused_mode != 0;
   hipStream_t st = p->ctx->stream;
   const int bp = p->bpad, deg = p->deg, S = p->S;
@@ -3324,16 +3340,18 @@ static int enqueue_run(slq_plan *p, double rtol, int fused_mode, bool nt) {
                                          : (double)std::numeric_limits<float>::epsilon();
   const double residual_tol = std::sqrt((double)p->n) * rtol;   // lanczos.h:110
   const double orth_tol = 2.0 * eps * std::sqrt((double)p->n);  // lanczos.h:53
-  // alpha and nu[1..] start from zero (the reference's fresh np.zeros buffers, lanczos.py:101-102)
-  HIP_TRY(hipMemsetAsync(p->st.alpha, 0, (size_t)(deg + 1) * bp * 8, st));
-  HIP_TRY(hipMemsetAsync(p->st.nu + bp, 0, (size_t)deg * bp * 8, st));
-  HIP_TRY(hipMemsetAsync(p->st.gram, 0, (size_t)2 * (kFusedMaxR + 1) * bp * 8, st));  // (the Gram rows of a previous run are never read - index guards - but need not be trusted to be)
+  if (j0 == 0) {
+    // alpha and nu[1..] start from zero (the reference's fresh np.zeros buffers, lanczos.py:101-102)
+    HIP_TRY(hipMemsetAsync(p->st.alpha, 0, (size_t)(deg + 1) * bp * 8, st));
+    HIP_TRY(hipMemsetAsync(p->st.nu + bp, 0, (size_t)deg * bp * 8, st));
+    HIP_TRY(hipMemsetAsync(p->st.gram, 0, (size_t)2 * (kFusedMaxR + 1) * bp * 8, st));  // (the Gram rows of a previous run are never read - index guards - but need not be trusted to be)
+  }
   const dim3 gA(p->nblkA, p->NP), gS(p->nblkS, p->NP), gU(p->nblkU, p->NP), gF((bp + 63) / 64);
   const dim3 gAf(p->nblkF, p->NP);
   const dim3 gT(p->nblkT, p->NP);
   const slq_operator *op = p->op;
-  bool prev_xt = false;  // the previous step's update pass produced the cross term W_{j}.W_{j-1}
-  for (int j = 0; j < deg; ++j) {
+  bool prev_xt = j0 > 0 && p->prev_xt;  // the previous step's update pass produced the cross term W_{j}.W_{j-1}
+  for (int j = j0; j < j1; ++j) {
     const int sc_ = j % S, sp_ = (j + S - 1) % S, sn_ = (j + 1) % S;
     const int first = (j == 0);
     // reorth columns: the last `orth` ring vectors; before step orth-1 only j+1 exist, unless the
@@ -3546,6 +3564,7 @@ static int enqueue_run(slq_plan *p, double rtol, int fused_mode, bool nt) {
     PROFILED(p, SLQ_K_FINALIZE,
              hipLaunchKernelGGL(k_fin_beta, gF, dim3(kFinThreads), 0, st, p->st, p->part, nblk_last, j, residual_tol, prev_xt ? 1 : 0));
   }
+  p->prev_xt = prev_xt;
   HIP_TRY(hipGetLastError());
   if (p->launch_error) {
     p->launch_error = false;
@@ -3554,9 +3573,34 @@ static int enqueue_run(slq_plan *p, double rtol, int fused_mode, bool nt) {
   return SLQ_OK;
 }
 
+static int run_range(slq_plan *p, double rtol, int j0, int j1);
+
 extern "C" int slq_plan_run(slq_plan *p, double rtol) {
   if (!p) return fail(SLQ_EINVAL, "plan is NULL");
   if (!p->probes_ready) return fail(SLQ_EINVAL, "slq_plan_run: set or generate probes first");
+  return run_range(p, rtol, 0, p->deg);
+}
+
+extern "C" int slq_plan_run_steps(slq_plan *p, double rtol, int upto) {
+  if (!p) return fail(SLQ_EINVAL, "plan is NULL");
+  if (p->nstale > 0) return fail(SLQ_EINVAL, "slq_plan_run_steps: a plan with stale ring columns is not resumable");
+  const bool fresh = p->probes_ready;  // (probes set or generated and not yet consumed: cur == 0)
+  if (!fresh && !(p->ran && p->cur > 0)) return fail(SLQ_EINVAL, "slq_plan_run_steps: set or generate probes first");
+  const int cur = fresh ? 0 : p->cur;
+  if (upto <= cur || upto > p->deg) return fail(SLQ_EINVAL, "slq_plan_run_steps: upto = %d must lie in (%d, %d] (steps done, the plan's deg)", upto, cur, p->deg);
+  if (!fresh && rtol != p->run_rtol) return fail(SLQ_EINVAL, "slq_plan_run_steps: rtol = %g differs from the %g this run began with", rtol, p->run_rtol);
+  return run_range(p, rtol, cur, upto);
+}
+
+extern "C" int slq_plan_steps_done(const slq_plan *p, int *cur) {
+  if (!p || !cur) return fail(SLQ_EINVAL, "plan/cur is NULL");
+  *cur = p->probes_ready ? 0 : (p->ran ? p->cur : 0);
+  return SLQ_OK;
+}
+
+constexpr size_t kGraphCacheMax = 16;
+
+static int run_range(slq_plan *p, double rtol, int j0, int j1) {
   HIP_TRY(hipSetDevice(p->ctx->device));
   hipStream_t st = p->ctx->stream;
   const int fused = p->sw.fused;
@@ -3567,37 +3611,66 @@ extern "C" int slq_plan_run(slq_plan *p, double rtol) {
   // operators (they synchronise with the host every step).
   const bool graph_ok = p->sw.graph && !p->prof && p->op->kind != OP_CALLBACK && p->op->kind != OP_DEVICE_CALLBACK;
   if (!graph_ok) {
-    SLQ_TRY(enqueue_run(p, rtol, fused, nt));
+    SLQ_TRY(enqueue_run(p, rtol, fused, nt, j0, j1));
   } else {
     const unsigned variant = p->sw.key() * 31u + (unsigned)p->nstale;  // every switch of the sequence + the stale-column count
-    if (!p->graph_exec || p->graph_rtol != rtol || p->graph_variant != variant) {
-      if (p->graph_exec) {
-        HIP_TRY(hipGraphExecDestroy(p->graph_exec));
-        p->graph_exec = nullptr;
+    size_t gi = 0;
+    for (; gi < p->graphs.size(); ++gi) {
+      const auto &g = p->graphs[gi];
+      if (g.j0 == j0 && g.j1 == j1 && g.rtol == rtol && g.variant == variant) break;
+    }
+    if (gi == p->graphs.size()) {
+      // a graph of the same steps for another rtol or variant is replaced (as the one-shot graph always was); a full cache
+      // gives up its oldest entry
+      for (size_t k = 0; k < p->graphs.size();) {
+        if (p->graphs[k].j0 == j0 && p->graphs[k].j1 == j1) {
+          HIP_TRY(hipGraphExecDestroy(p->graphs[k].exec));
+          p->graphs.erase(p->graphs.begin() + k);
+        } else {
+          ++k;
+        }
+      }
+      if (p->graphs.size() >= kGraphCacheMax) {
+        HIP_TRY(hipGraphExecDestroy(p->graphs.front().exec));
+        p->graphs.erase(p->graphs.begin());
       }
       hipGraph_t graph = nullptr;
+      const bool xt_in = p->prev_xt;
       HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      const int rc = enqueue_run(p, rtol, fused, nt);
+      const int rc = enqueue_run(p, rtol, fused, nt, j0, j1);
       hipError_t ce = hipStreamEndCapture(st, &graph);
       if (rc != SLQ_OK) {
         if (graph) hipGraphDestroy(graph);
+        p->prev_xt = xt_in;
         return rc;
       }
       if (ce != hipSuccess) return fail(SLQ_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-      ce = hipGraphInstantiate(&p->graph_exec, graph, nullptr, nullptr, 0);
+      hipGraphExec_t exec = nullptr;
+      ce = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
       hipGraphDestroy(graph);
       if (ce != hipSuccess) {
-        p->graph_exec = nullptr;
+        p->prev_xt = xt_in;
         return fail(SLQ_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(ce));
       }
-      p->graph_rtol = rtol;
-      p->graph_variant = variant;
+      p->graphs.push_back({j0, j1, rtol, variant, exec, p->prev_xt});
+      gi = p->graphs.size() - 1;
     }
-    HIP_TRY(hipGraphLaunch(p->graph_exec, st));
+    HIP_TRY(hipGraphLaunch(p->graphs[gi].exec, st));
+    p->prev_xt = p->graphs[gi].xt_out;
   }
   p->probes_ready = false;
   p->ran = true;
+  p->cur = j1;
+  p->run_rtol = rtol;
   p->rule_src = 0;
+  return SLQ_OK;
+}
+
+// the entries that mean "the finished run": not while a staged run stands between two stages
+static int need_finished_run(const slq_plan *p, const char *who) {
+  if (!p->ran) return fail(SLQ_EINVAL, "%s: no completed run", who);
+  if (p->cur < p->deg)
+    return fail(SLQ_EINVAL, "%s: the run stands at step %d of %d (slq_plan_run_steps); use slq_plan_quadrature_at for a prefix, or run to deg", who, p->cur, p->deg);
   return SLQ_OK;
 }
 
@@ -3636,7 +3709,7 @@ extern "C" int slq_plan_get_tridiag(slq_plan *p, void *alpha, void *beta, int32_
 extern "C" int slq_plan_quadrature(slq_plan *p, int fun_id, const double *fun_params, double *quad,
                                    double *nodes, double *weights) {
   if (!p) return fail(SLQ_EINVAL, "plan is NULL");
-  if (!p->ran) return fail(SLQ_EINVAL, "slq_plan_quadrature: no completed run");
+  SLQ_TRY(need_finished_run(p, "slq_plan_quadrature"));
   if (fun_id < SLQ_FUN_NONE || fun_id > SLQ_FUN_SOFTSIGN) return fail(SLQ_EINVAL, "Unknown function id %d.", fun_id);
   HIP_TRY(hipSetDevice(p->ctx->device));
   hipStream_t st = p->ctx->stream;
@@ -3674,10 +3747,71 @@ extern "C" int slq_plan_quadrature(slq_plan *p, int fun_id, const double *fun_pa
   return SLQ_OK;
 }
 
+// Quadrature of the first m steps of the run as it stands (m <= steps done): rule 0 the m-point Gauss rule - what a run
+// of degree m returns -, rule 1 the (m + 1)-point Gauss-Radau rule with a node at `endpoint` (slq_radau.hpp). The rule goes
+// to buffers of its own: the finished run's rule (nodes_d / weights_d, shared with slq_density_update) is not touched.
+extern "C" int slq_plan_quadrature_at(slq_plan *p, int m, int rule, double endpoint, int fun_id, const double *fun_params,
+                                      double *quad, double *nodes, double *weights, double *stage) {
+  if (!p) return fail(SLQ_EINVAL, "plan is NULL");
+  if (!p->ran || p->cur < 1) return fail(SLQ_EINVAL, "slq_plan_quadrature_at: no steps done");
+  if (m < 1 || m > p->cur) return fail(SLQ_EINVAL, "slq_plan_quadrature_at: m = %d must lie in [1, %d] (steps done)", m, p->cur);
+  if (rule != 0 && rule != 1) return fail(SLQ_EINVAL, "slq_plan_quadrature_at: rule %d (0 Gauss, 1 Gauss-Radau)", rule);
+  if (rule == 1 && !std::isfinite(endpoint)) return fail(SLQ_EINVAL, "slq_plan_quadrature_at: the Gauss-Radau rule needs a finite endpoint");
+  if (fun_id < SLQ_FUN_NONE || fun_id > SLQ_FUN_SOFTSIGN) return fail(SLQ_EINVAL, "Unknown function id %d.", fun_id);
+  HIP_TRY(hipSetDevice(p->ctx->device));
+  hipStream_t st = p->ctx->stream;
+  const int deg = p->deg, P = p->nprobes, kout = m + rule;
+  const size_t rule_sz = (size_t)P * (deg + 1);
+  if (!p->at_d) {
+    hipError_t e = hipMalloc((void **)&p->at_d, (2 * (size_t)P + 4 + 2 * rule_sz) * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&p->at_flags, 2 * sizeof(int));
+    if (e != hipSuccess) {
+      if (p->at_d) hipFree(p->at_d);
+      p->at_d = nullptr;
+      return fail(SLQ_ENOMEM, "slq_plan_quadrature_at: scratch: %s", hipGetErrorString(e));
+    }
+  }
+  double *quad_d = p->at_d, *gauss_d = quad_d + P, *stage_d = gauss_d + P, *nodes_d = stage_d + 4, *weights_d = nodes_d + rule_sz;
+  const double p0 = fun_params ? fun_params[0] : 0.0, p1 = fun_params ? fun_params[1] : 0.0;
+  const int lanes = quadrature_lanes(m + 1);
+  const size_t lds = (size_t)3 * (m + 1) * lanes * 8;
+  if (lds > 48 * 1024)
+    HIP_TRY(hipFuncSetAttribute((const void *)k_quadrature_at, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  HIP_TRY(hipMemsetAsync(p->at_flags, 0, 2 * sizeof(int), st));
+  const double residual_tol = std::sqrt((double)p->n) * p->run_rtol;  // (the stop rule of the run: lanczos.h:110)
+  PROFILED(p, SLQ_K_QUADRATURE,
+           hipLaunchKernelGGL(k_quadrature_at, dim3((P + lanes - 1) / lanes), dim3(64), lds, st, p->st, m, rule, endpoint, residual_tol, lanes,
+                              fun_id, p0, p1, quad_d, gauss_d, nodes_d, weights_d, p->at_flags));
+  if (stage)
+    hipLaunchKernelGGL(k_stage_reduce, dim3(1), dim3(kStageThreads), 0, st, P, (const double *)quad_d,
+                       rule ? (const double *)gauss_d : (const double *)nullptr, stage_d);
+  HIP_TRY(hipGetLastError());
+  int flags[2] = {0, 0}, ring_bad = 0;
+  HIP_TRY(hipMemcpyAsync(flags, p->at_flags, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&ring_bad, p->ring_fail_d, sizeof(int), hipMemcpyDeviceToHost, st));
+  if (quad) HIP_TRY(hipMemcpyAsync(quad, quad_d, (size_t)P * 8, hipMemcpyDeviceToHost, st));
+  if (nodes) HIP_TRY(hipMemcpyAsync(nodes, nodes_d, (size_t)P * kout * 8, hipMemcpyDeviceToHost, st));
+  if (weights) HIP_TRY(hipMemcpyAsync(weights, weights_d, (size_t)P * kout * 8, hipMemcpyDeviceToHost, st));
+  if (stage) HIP_TRY(hipMemcpyAsync(stage, stage_d, 4 * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  SLQ_TRY(ring_flag_status(ring_bad));
+  if (flags[1]) return fail(SLQ_EINVAL, "slq_plan_quadrature_at: endpoint = %g is not below the smallest Ritz value of every probe", endpoint);
+  if (flags[0]) return fail(SLQ_ENOTCONV, "tridiagonal QL did not converge for at least one probe");
+  return SLQ_OK;
+}
+
+// test hook: mark a plan as holding `nstale` stale ring columns, as the drop-in slq_lanczos_* entry does for its own plan
+// (tests/test_gpu_resume.py: such a plan is not resumable). Mark it back to 0 before any run.
+extern "C" int slq_debug_plan_mark_stale(slq_plan *p, int nstale) {
+  if (!p || nstale < 0) return fail(SLQ_EINVAL, "plan is NULL or nstale < 0");
+  p->nstale = nstale;
+  return SLQ_OK;
+}
+
 extern "C" int slq_plan_get_basis(slq_plan *p, int probe, void *Q, int64_t ldq) {
   if (!p || !Q) return fail(SLQ_EINVAL, "plan/Q is NULL");
   if (!p->keep_basis) return fail(SLQ_EINVAL, "plan was created without keep_basis");
-  if (!p->ran) return fail(SLQ_EINVAL, "no completed run");
+  SLQ_TRY(need_finished_run(p, "slq_plan_get_basis"));
   if (probe < 0 || probe >= p->nprobes || ldq < p->n) return fail(SLQ_EINVAL, "bad probe index or ldq");
   HIP_TRY(hipSetDevice(p->ctx->device));
   hipStream_t st = p->ctx->stream;
@@ -3727,7 +3861,7 @@ static int launch_reorth_update(slq_plan *p, int j, int r, int istart, bool axpy
 // Y = f(A) X on the device: result left in ring slot `deg` (panel layout)
 static int fun_action_device(slq_plan *p, int fun_id, const double *fun_params) {
   if (!p->keep_basis) return fail(SLQ_EINVAL, "plan was created without keep_basis");
-  if (!p->ran) return fail(SLQ_EINVAL, "no completed run");
+  SLQ_TRY(need_finished_run(p, "slq_plan_fun_action / slq_diag_update"));
   if (fun_id < SLQ_FUN_IDENTITY || fun_id > SLQ_FUN_SOFTSIGN) return fail(SLQ_EINVAL, "Unknown function id %d.", fun_id);
   HIP_TRY(hipSetDevice(p->ctx->device));
   hipStream_t st = p->ctx->stream;
@@ -3915,7 +4049,7 @@ extern "C" int slq_density_destroy(slq_density *d) {
 extern "C" int slq_density_update(slq_density *d, slq_plan *p) {
   if (!d || !p) return fail(SLQ_EINVAL, "slq_density_update: density/plan is NULL");
   if (d->ctx != p->ctx) return fail(SLQ_EINVAL, "slq_density_update: the plan belongs to another context");
-  if (!p->ran) return fail(SLQ_EINVAL, "slq_density_update: no completed run");
+  SLQ_TRY(need_finished_run(p, "slq_density_update"));
   HIP_TRY(hipSetDevice(p->ctx->device));
   hipStream_t st = p->ctx->stream;
   const int P = p->nprobes, deg = p->deg, G2 = d->G + 2;
@@ -4333,6 +4467,71 @@ extern "C" int slq_quadrature_batch(slq_context *ctx, int nb, int deg, const dou
   hipFree(buf);
   if (err != hipSuccess) rc = fail(SLQ_EHIP, "slq_quadrature_batch: %s", hipGetErrorString(err));
   else if (bad) rc = fail(SLQ_ENOTCONV, "tridiagonal QL did not converge for at least one rule");
+  return rc;
+}
+
+// Gauss-Radau rules of nb given Jacobi matrices (d, e as slq_quadrature_batch; beta_m[i]: the coupling of matrix i to its
+// border, the norm of the Lanczos residual after m steps): the stand-alone form of slq_plan_quadrature_at's rule 1.
+extern "C" int slq_quadrature_radau_batch(slq_context *ctx, int nb, int m, const double *d, const double *e, const double *beta_m,
+                                          double endpoint, int fun_id, const double *fun_params, double *quad, double *nodes,
+                                          double *weights) {
+  if (!ctx || !d || !e || !beta_m) return fail(SLQ_EINVAL, "ctx/d/e/beta_m is NULL");
+  if (nb <= 0 || m <= 0 || m >= kMaxDeg) return fail(SLQ_EINVAL, "bad batch size or degree (m < %d)", kMaxDeg);
+  if (!std::isfinite(endpoint)) return fail(SLQ_EINVAL, "slq_quadrature_radau_batch: the endpoint must be finite");
+  if (fun_id < SLQ_FUN_NONE || fun_id > SLQ_FUN_SOFTSIGN) return fail(SLQ_EINVAL, "Unknown function id %d.", fun_id);
+  const int lanes = quadrature_lanes(m + 1);
+  const size_t lds = (size_t)3 * (m + 1) * lanes * 8;
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int bp = (nb + 63) / 64 * 64;
+  StepState s;
+  memset(&s, 0, sizeof(s));
+  s.bpad = bp;
+  s.nprobes = nb;
+  s.deg = m;
+  double *buf = nullptr;
+  const size_t in = (size_t)nb * m, out = (size_t)nb * (m + 1);
+  const size_t total = (size_t)(2 * (m + 1) + 1) * bp + 2 * in + nb + 2 * (size_t)bp + 2 * out + (size_t)bp / 2 + 8;
+  HIP_TRY(hipMalloc((void **)&buf, total * 8));
+  double *q = buf;
+  s.alpha = q; q += (size_t)(m + 1) * bp;
+  s.nu = q; q += (size_t)(m + 1) * bp;
+  s.vnorm2 = q; q += bp;
+  double *dd = q; q += in;
+  double *de = q; q += in;
+  double *db = q; q += nb;
+  double *dq = q; q += bp;
+  double *dg = q; q += bp;
+  double *dn = q; q += out;
+  double *dw = q; q += out;
+  s.steps = (int *)q; q += bp / 2;  // (bp ints)
+  int *dflags = (int *)q;
+  int rc = SLQ_OK;
+  hipError_t err = hipMemcpyAsync(dd, d, in * 8, hipMemcpyHostToDevice, st);
+  if (err == hipSuccess) err = hipMemcpyAsync(de, e, in * 8, hipMemcpyHostToDevice, st);
+  if (err == hipSuccess) err = hipMemcpyAsync(db, beta_m, (size_t)nb * 8, hipMemcpyHostToDevice, st);
+  if (err == hipSuccess) err = hipMemsetAsync(dflags, 0, 2 * sizeof(int), st);
+  if (err == hipSuccess) {
+    k_load_tridiag<<<dim3((bp + 255) / 256), dim3(256), 0, st>>>(s, dd, de, nb);
+    k_load_residual<<<dim3((bp + 255) / 256), dim3(256), 0, st>>>(s, db, nb);
+    if (lds > 48 * 1024)
+      err = hipFuncSetAttribute((const void *)k_quadrature_at, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  }
+  if (err == hipSuccess) {
+    const double p0 = fun_params ? fun_params[0] : 0.0, p1 = fun_params ? fun_params[1] : 0.0;
+    k_quadrature_at<<<dim3((nb + lanes - 1) / lanes), dim3(64), lds, st>>>(s, m, 1, endpoint, 0.0, lanes, fun_id, p0, p1, dq, dg, dn, dw, dflags);
+    err = hipGetLastError();
+  }
+  int flags[2] = {0, 0};
+  if (err == hipSuccess) err = hipMemcpyAsync(flags, dflags, 2 * sizeof(int), hipMemcpyDeviceToHost, st);
+  if (err == hipSuccess && quad) err = hipMemcpyAsync(quad, dq, (size_t)nb * 8, hipMemcpyDeviceToHost, st);
+  if (err == hipSuccess && nodes) err = hipMemcpyAsync(nodes, dn, out * 8, hipMemcpyDeviceToHost, st);
+  if (err == hipSuccess && weights) err = hipMemcpyAsync(weights, dw, out * 8, hipMemcpyDeviceToHost, st);
+  if (err == hipSuccess) err = hipStreamSynchronize(st);
+  hipFree(buf);
+  if (err != hipSuccess) rc = fail(SLQ_EHIP, "slq_quadrature_radau_batch: %s", hipGetErrorString(err));
+  else if (flags[1]) rc = fail(SLQ_EINVAL, "slq_quadrature_radau_batch: endpoint = %g is not below the smallest eigenvalue of every matrix", endpoint);
+  else if (flags[0]) rc = fail(SLQ_ENOTCONV, "tridiagonal QL did not converge for at least one rule");
   return rc;
 }
 

@@ -2276,6 +2276,79 @@ __device__ __forceinline__ double apply_fun(int fun_id, double p0, double p1, do
   }
 }
 
+// The QL of every first-row rule (k_quadrature and the prefix / Gauss-Radau form, slq_radau.hpp): implicit shifts
+// (Wilkinson) on the k x k Jacobi matrix one lane holds in LDS columns d, e, z (stride `lanes`; e[i] couples i and
+// i + 1; z = e_1 on entry), carrying only the first row of the eigenvector matrix, then an insertion sort by node
+// (ascending, like LAPACK's output). Returns 1 if an eigenvalue did not converge in 60 sweeps.
+__device__ __forceinline__ int ql_first_row_sorted(double *d, double *e, double *z, int k, int lanes) {
+#define D(i) d[(i) * lanes]
+#define E(i) e[(i) * lanes]
+#define Z(i) z[(i) * lanes]
+  int bad = 0;
+  for (int l = 0; l < k; ++l) {
+    int iter = 0;
+    for (;;) {
+      int m = l;
+      for (; m < k - 1; ++m) {
+        const double dd = fabs(D(m)) + fabs(D(m + 1));
+        if (fabs(E(m)) <= 2.220446049250313e-16 * dd) break;
+      }
+      if (m == l) break;
+      if (iter++ >= 60) {
+        bad = 1;
+        break;
+      }
+      double g = (D(l + 1) - D(l)) / (2.0 * E(l));
+      double r = hypot(g, 1.0);
+      g = D(m) - D(l) + E(l) / (g + (g >= 0.0 ? fabs(r) : -fabs(r)));
+      double s = 1.0, c = 1.0, p = 0.0;
+      int i = m - 1;
+      bool underflow = false;
+      for (; i >= l; --i) {
+        double f = s * E(i);
+        const double b = c * E(i);
+        r = hypot(f, g);
+        E(i + 1) = r;
+        if (r == 0.0) {
+          D(i + 1) -= p;
+          E(m) = 0.0;
+          underflow = true;
+          break;
+        }
+        s = f / r;
+        c = g / r;
+        g = D(i + 1) - p;
+        r = (D(i) - g) * s + 2.0 * c * b;
+        p = s * r;
+        D(i + 1) = g + p;
+        g = c * r - b;
+        f = Z(i + 1);
+        Z(i + 1) = s * Z(i) + c * f;
+        Z(i) = c * Z(i) - s * f;
+      }
+      if (underflow) continue;
+      D(l) -= p;
+      E(l) = g;
+      E(m) = 0.0;
+    }
+  }
+  // insertion sort by node
+  for (int i = 1; i < k; ++i) {
+    const double dv = D(i), zv = Z(i);
+    int jj = i - 1;
+    for (; jj >= 0 && D(jj) > dv; --jj) {
+      D(jj + 1) = D(jj);
+      Z(jj + 1) = Z(jj);
+    }
+    D(jj + 1) = dv;
+    Z(jj + 1) = zv;
+  }
+  return bad;
+#undef D
+#undef E
+#undef Z
+}
+
 // One probe per lane; d, e, z live in LDS as [k][lanes] so a wave's accesses are conflict-free.
 // Implicit-shift QL (Wilkinson shift) carrying only the first row of the eigenvector matrix:
 // nodes = eigenvalues of T_k, weights = z^2 (Golub-Welsch; reference: integrate.py:61-64 via
@@ -2305,66 +2378,8 @@ __global__ __launch_bounds__(64) void k_quadrature(StepState st, int lanes, int 
     E(i) = (live && i + 1 < k) ? st.nu[(int64_t)(i + 1) * st.bpad + col] : 0.0;
     Z(i) = (i == 0) ? 1.0 : 0.0;
   }
-  int bad = 0;
   if (live) {
-    for (int l = 0; l < k; ++l) {
-      int iter = 0;
-      for (;;) {
-        int m = l;
-        for (; m < k - 1; ++m) {
-          const double dd = fabs(D(m)) + fabs(D(m + 1));
-          if (fabs(E(m)) <= 2.220446049250313e-16 * dd) break;
-        }
-        if (m == l) break;
-        if (iter++ >= 60) {
-          bad = 1;
-          break;
-        }
-        double g = (D(l + 1) - D(l)) / (2.0 * E(l));
-        double r = hypot(g, 1.0);
-        g = D(m) - D(l) + E(l) / (g + (g >= 0.0 ? fabs(r) : -fabs(r)));
-        double s = 1.0, c = 1.0, p = 0.0;
-        int i = m - 1;
-        bool underflow = false;
-        for (; i >= l; --i) {
-          double f = s * E(i);
-          const double b = c * E(i);
-          r = hypot(f, g);
-          E(i + 1) = r;
-          if (r == 0.0) {
-            D(i + 1) -= p;
-            E(m) = 0.0;
-            underflow = true;
-            break;
-          }
-          s = f / r;
-          c = g / r;
-          g = D(i + 1) - p;
-          r = (D(i) - g) * s + 2.0 * c * b;
-          p = s * r;
-          D(i + 1) = g + p;
-          g = c * r - b;
-          f = Z(i + 1);
-          Z(i + 1) = s * Z(i) + c * f;
-          Z(i) = c * Z(i) - s * f;
-        }
-        if (underflow) continue;
-        D(l) -= p;
-        E(l) = g;
-        E(m) = 0.0;
-      }
-    }
-    // insertion sort by node
-    for (int i = 1; i < k; ++i) {
-      const double dv = D(i), zv = Z(i);
-      int jj = i - 1;
-      for (; jj >= 0 && D(jj) > dv; --jj) {
-        D(jj + 1) = D(jj);
-        Z(jj + 1) = Z(jj);
-      }
-      D(jj + 1) = dv;
-      Z(jj + 1) = zv;
-    }
+    const int bad = ql_first_row_sorted(d, e, z, k, lanes);
     double s = 0.0;
     for (int i = 0; i < k; ++i) {
       const double th = D(i), tau = Z(i) * Z(i);

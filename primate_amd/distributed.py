@@ -30,6 +30,18 @@ def _collective_device(group, device: Optional[str]) -> str:
 	return f"cuda:{int(os.environ['LOCAL_RANK']) if 'LOCAL_RANK' in os.environ else torch.cuda.current_device()}"
 
 
+def _refuse_adaptive(*objs, **kwargs) -> None:
+	"""Every sharded entry promises a result that does not depend on the sharding. A Lanczos degree chosen from the
+	statistics of a rank's own probes (MatrixFunction(..., deg_max=...)) would break that, so such an operator is refused
+	before any device work - also when it arrives as the bound method of one (`sharded_hutch(M.quad_generated ...)`)."""
+	if kwargs.get("deg_max") is not None:
+		raise ValueError("the sharded entries take a fixed Lanczos degree: deg_max (adaptive degree) is not supported across ranks")
+	for o in objs:
+		o = getattr(o, "__self__", o)
+		if getattr(o, "_adaptive", None) is not None:
+			raise ValueError("the sharded entries take a fixed Lanczos degree: an adaptive MatrixFunction (deg_max=...) would make the result depend on the sharding")
+
+
 def shard_range(nprobes: int, rank: int, world: int) -> tuple:
 	"""Contiguous block [lo, hi) of global probe ids owned by `rank` (first ranks take the remainder)."""
 	base, rem = divmod(int(nprobes), int(world))
@@ -125,6 +137,7 @@ def sharded_hutch(evaluate, converge="default", batch: int = 32, group=None, ful
 	`hutch(..., full=True)` makes per batch (src/primate/trace.py:104-110) - and evaluates the criterion on it, so all
 	ranks stop at the same batch with the same estimate. `converge` / kwargs as in `hutch` (default: 200 samples or a
 	95 % confidence interval of half-width 1, trace.py:89-92)."""
+	_refuse_adaptive(evaluate)
 	import torch.distributed as dist
 
 	from .estimators import ConfidenceCriterion, CountCriterion, EstimatorResult, MeanEstimator, convergence_criterion
@@ -161,6 +174,7 @@ def sharded_hutch_device(op, nprobes: Optional[int] = None, deg: int = 20, orth:
 	    evaluated per global batch of `batch` probes on the merged estimator (`sharded_hutch`); returns what
 	    `hutch` returns (the estimate, or (estimate, EstimatorResult) with full=True). `converge_kwargs` are the
 	    criterion's arguments (count, confidence, atol, rtol, ...)."""
+	_refuse_adaptive(op)
 	import torch.distributed as dist
 
 	from .engine import LanczosPlan
@@ -198,6 +212,7 @@ def sharded_diag_device(op, nprobes: int, deg: int, orth: int = 3, fun="identity
 	Returns (numer / denom, numer, denom, count) — the Hutchinson diagonal estimate of the pooled probes.
 	(The reference's running mean of successive ratios, diagonal.py:79, is order-dependent and is only
 	reproduced by the single-process `primate_amd.diagonal.diag`.)"""
+	_refuse_adaptive(op)
 	import torch.distributed as dist
 
 	from .engine import DiagAccumulator, LanczosPlan
@@ -418,6 +433,7 @@ def sharded_xtrace(M, count: int, batch: int = 128, pdf: str = "sphere", seed: i
 	sketches="rows": the n x m sketches W, Q, Z are ROW-sharded instead (`_xtrace_row_sharded`: 1/world of the memory and of the
 	Gram-matrix work per rank, one m x m all-reduce per Gram matrix, all-to-alls instead of all-gathers) - for n m beyond one
 	GPU's HBM or blocks wide enough for the dense algebra to matter; needs the device probe stream."""
+	_refuse_adaptive(M)
 	import torch.distributed as dist
 
 	from .trace import xtrace
@@ -439,6 +455,7 @@ def sharded_spectral_density(A, nprobes: int = 256, bins: int = 200, interval=No
 	accumulates its ids on its own GPU, then ONE all-gather of (count, mean[G], M2[G], outside) per rank, folded in rank
 	order (`merge_statistics_vec`), gives every rank the same result. With more than one rank, `interval` and `seed` are
 	required (every rank must use the same grid and the same probe stream)."""
+	_refuse_adaptive(A, **kwargs)
 	import torch.distributed as dist
 
 	from .integrate import _density_accumulate, _density_args, _density_result

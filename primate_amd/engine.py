@@ -288,11 +288,51 @@ class LanczosPlan:
 		"""The current probes (as used: sphere draws have norm sqrt(n)) into columns [o0, o0 + nprobes) of `out`."""
 		check(_capi.lib().slq_plan_get_probes_dmat(self._h, out._h, int(o0)))
 
-	def run(self, rtol: float = 1e-8):
-		rc = _capi.lib().slq_plan_run(self._h, float(rtol))
+	def run(self, rtol: float = 1e-8, upto: Optional[int] = None):
+		"""All `deg` steps (slq_plan_run), or with `upto` the steps [steps_done, upto) of a resumable run
+		(slq_plan_run_steps): the same launches, the state stays on the device between the stages."""
+		if upto is None:
+			rc = _capi.lib().slq_plan_run(self._h, float(rtol))
+		else:
+			rc = _capi.lib().slq_plan_run_steps(self._h, float(rtol), int(upto))
 		if rc == _capi.SLQ_ECALLBACK and getattr(self.op, "error", None) is not None:
 			raise self.op.error
 		check(rc)
+
+	@property
+	def steps_done(self) -> int:
+		"""Lanczos steps done since the probes were set or generated."""
+		c = C.c_int()
+		check(_capi.lib().slq_plan_steps_done(self._h, C.byref(c)))
+		return int(c.value)
+
+	def quadrature_at(self, m: Optional[int] = None, fun="identity", rule: str = "gauss", endpoint: Optional[float] = None,
+					  return_rule: bool = False, return_stage: bool = False, **fun_kwargs):  # fmt: skip
+		"""Quadrature of the first `m` steps of the run as it stands (default: all steps done; slq_plan_quadrature_at).
+		rule "gauss": the m-point Gauss rule, what a run of degree m returns. rule "radau": the (m+1)-point Gauss-Radau
+		rule with a node at `endpoint` <= lambda_min(A), which brackets v^T f(A) v together with the Gauss value for f
+		whose derivatives keep one sign. Returns quad, then (nodes, weights) with return_rule, then with return_stage the
+		four doubles {sum quad, sum quad^2, sum |quad - gauss|, nprobes} reduced on the device."""
+		rid, endpoint = _rule_args(rule, endpoint)
+		fid, params = fun_spec(fun, **fun_kwargs)
+		if fid is None and return_stage:
+			raise ValueError("the stage statistics are reduced on the device: built-in function names only")
+		host_fun = fid is None
+		m = self.steps_done if m is None else int(m)
+		want_rule = return_rule or host_fun
+		k = m + rid
+		quad = np.zeros(self.nprobes)
+		nodes = np.zeros((self.nprobes, k)) if want_rule and k > 0 else None
+		weights = np.zeros((self.nprobes, k)) if want_rule and k > 0 else None
+		stage = np.zeros(4) if return_stage else None
+		check(_capi.lib().slq_plan_quadrature_at(self._h, m, rid, endpoint, 0 if host_fun else fid, ptr(params), ptr(quad), ptr(nodes),
+												 ptr(weights), ptr(stage)))  # fmt: skip
+		if host_fun:  # (as `quadrature`: the callable on the host over the nodes, ||v||^2 from the identity's value)
+			ident = np.sum(nodes * weights, axis=1)
+			vn2 = np.divide(quad, ident, out=np.zeros_like(quad), where=ident != 0)
+			quad = np.array([np.sum(fun(nodes[i]) * weights[i]) for i in range(self.nprobes)]) * vn2
+		out = (quad,) + ((nodes, weights) if return_rule else ()) + ((stage,) if return_stage else ())
+		return out[0] if len(out) == 1 else out
 
 	def tridiag(self) -> tuple:
 		"""(alpha, beta, steps): alpha/beta are (nprobes, deg+1) with beta[:, 0] = 0."""
@@ -370,6 +410,135 @@ class LanczosPlan:
 			pass
 
 
+RULE_IDS = {"gauss": 0, "radau": 1}
+## stage every DEG_STEP Lanczos steps unless told otherwise (the cost of a stage against a step)
+DEG_STEP = 5
+
+
+def _rule_args(rule, endpoint) -> tuple:
+	"""(rule id, endpoint) of `quadrature_at`, checked before any device work."""
+	if rule not in RULE_IDS:
+		raise ValueError(f"unknown quadrature rule '{rule}' (one of {', '.join(RULE_IDS)})")
+	if rule == "radau":
+		if endpoint is None:
+			raise ValueError("rule='radau' needs endpoint=a with a <= lambda_min(A)")
+		endpoint = float(endpoint)
+		if not np.isfinite(endpoint):
+			raise ValueError(f"endpoint must be finite, got {endpoint!r}")
+	return RULE_IDS[rule], (0.0 if rule == "gauss" or endpoint is None else float(endpoint))
+
+
+def _adaptive_args(deg_max, stages, deg_rtol, endpoint=None, deg_step=None, first=None) -> tuple:
+	"""Checks the arguments of the adaptive-degree drivers before any device work; returns (deg_max, stages, deg_rtol,
+	endpoint). stages=None: first (default: the step), first + step, ... up to deg_max, with deg_max appended if it is
+	not the last."""
+	if isinstance(deg_max, bool) or not isinstance(deg_max, (int, np.integer)) or deg_max < 1:
+		raise ValueError(f"deg_max must be an integer >= 1, got {deg_max!r}")
+	deg_max = int(deg_max)
+	if deg_rtol is None:
+		raise ValueError("an adaptive degree needs deg_rtol (it has no default)")
+	deg_rtol = float(deg_rtol)
+	if not (np.isfinite(deg_rtol) and deg_rtol > 0.0):
+		raise ValueError(f"deg_rtol must be > 0, got {deg_rtol!r}")
+	if endpoint is not None:
+		endpoint = float(endpoint)
+		if not np.isfinite(endpoint):
+			raise ValueError(f"endpoint must be finite, got {endpoint!r}")
+	if stages is None:
+		step = DEG_STEP if deg_step is None else deg_step
+		if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or step < 1:
+			raise ValueError(f"deg_step must be an integer >= 1, got {step!r}")
+		first = int(step) if first is None else int(first)
+		if not 1 <= first <= deg_max:
+			raise ValueError(f"the first stage {first} lies outside [1, deg_max = {deg_max}]")
+		stages = list(range(first, deg_max + 1, int(step)))
+		if stages[-1] != deg_max:
+			stages.append(deg_max)
+	else:
+		if deg_step is not None:
+			raise ValueError("give stages or deg_step, not both")
+		try:
+			given = list(stages)
+		except TypeError:
+			raise ValueError("stages must be a sequence of integers") from None
+		if not given or any(isinstance(m, bool) or not isinstance(m, (int, np.integer)) for m in given):
+			raise ValueError(f"stages must be a non-empty sequence of integers, got {stages!r}")
+		stages = [int(m) for m in given]
+		if any(m < 1 or m > deg_max for m in stages):
+			raise ValueError(f"every stage must lie in [1, deg_max = {deg_max}], got {stages}")
+		if any(b <= a for a, b in zip(stages[:-1], stages[1:])):
+			raise ValueError(f"stages must be strictly increasing, got {stages}")
+	return deg_max, stages, deg_rtol, endpoint
+
+
+def quad_adaptive(
+	op: DeviceOperator, X, deg_max: int, orth: int = 0, fun="identity", stages=None, deg_rtol: Optional[float] = None,
+	endpoint: Optional[float] = None, rtol: float = 1e-8, nprobes: Optional[int] = None, deg_step: Optional[int] = None,
+	plan: Optional[LanczosPlan] = None, **fun_kwargs,
+):  # fmt: skip
+	"""Lanczos quadrature with the degree chosen by the run itself: a resumable run of capacity `deg_max`, stopped
+	after the first stage that meets the rule below. X: the probes (n x P), or (pdf, seed, probe_offset) to draw
+	`nprobes` of them on the device. Returns (quad, deg_used, history).
+
+	Stopping rule, from four doubles per stage reduced on the device (S_k = the sum of the Gauss values of stage k):
+	without `endpoint`, the first stage k >= 1 with |S_k - S_{k-1}| <= deg_rtol |S_k|; with `endpoint` (a lower bound of
+	the spectrum), the first stage with sum_i |radau_i - gauss_i| <= deg_rtol |S_k| - the width of the Gauss / Gauss-Radau
+	bracket, an error bar of the quadrature for f whose derivatives keep one sign. If no stage meets it the run ends at
+	deg_max. quad: the Gauss values at the stopping stage - what a fixed deg = deg_used, orth = min(orth, deg_used) run
+	returns -; with `endpoint` an (P, 2) array, the Radau values beside them. history: [(m, stage)] for every stage
+	visited, stage = {sum, sum of squares, sum |quad - gauss|, nprobes} of the Gauss values, with `endpoint` a (2, 4)
+	array whose second row holds the same of the Radau values."""
+	deg_max, stages, deg_rtol, endpoint = _adaptive_args(deg_max, stages, deg_rtol, endpoint, deg_step)
+	fid, _ = fun_spec(fun, **fun_kwargs)
+	if fid is None:
+		raise ValueError("quad_adaptive takes built-in function names (the stage statistics are reduced on the device)")
+	dev = isinstance(X, tuple)
+	if dev:
+		if len(X) != 3 or X[0] not in _capi.PDF_IDS:
+			raise ValueError("device-drawn probes are given as (pdf, seed, probe_offset)")
+		if nprobes is None or int(nprobes) < 1:
+			raise ValueError("device-drawn probes need nprobes >= 1")
+	else:
+		X = np.asarray(X)
+		X = X.reshape(-1, 1) if X.ndim == 1 else X
+		if X.shape[0] != op.shape[0]:
+			raise ValueError(f"X has {X.shape[0]} rows, the operator has {op.shape[0]}")
+		nprobes = X.shape[1]
+	own = plan is None
+	if own:
+		plan = LanczosPlan(op, int(nprobes), deg_max, orth)
+	try:
+		if plan.deg < stages[-1]:
+			stages = [m for m in stages if m < plan.deg] + [plan.deg]  # (deg_max beyond n: the plan's capacity is n)
+		if dev:
+			plan.generate_probes(X[0], seed=int(X[1]), probe_offset=int(X[2]))
+		else:
+			plan.set_probes(X)
+		history, s_prev, used = [], None, stages[-1]
+		for k, m in enumerate(stages):
+			plan.run(rtol, upto=m)
+			_, st = plan.quadrature_at(m, fun, return_stage=True, **fun_kwargs)
+			s_k = st[0]
+			if endpoint is not None:
+				_, sr = plan.quadrature_at(m, fun, rule="radau", endpoint=endpoint, return_stage=True, **fun_kwargs)
+				history.append((m, np.stack([st, sr])))
+				met = sr[2] <= deg_rtol * abs(s_k)
+			else:
+				history.append((m, st))
+				met = k >= 1 and abs(s_k - s_prev) <= deg_rtol * abs(s_k)
+			s_prev = s_k
+			if met:
+				used = m
+				break
+		quad = plan.quadrature_at(used, fun, **fun_kwargs)
+		if endpoint is not None:
+			quad = np.stack([quad, plan.quadrature_at(used, fun, rule="radau", endpoint=endpoint, **fun_kwargs)], axis=1)
+	finally:
+		if own:
+			plan.close()
+	return quad, used, history
+
+
 def quad_batch(
 	op: DeviceOperator, X: Optional[np.ndarray], deg: int, orth: int = 0, fun="identity", rtol: float = 1e-8,
 	nprobes: Optional[int] = None, pdf: str = "rademacher", seed: int = 0, probe_offset: int = 0,
@@ -431,6 +600,29 @@ def quadrature_batch(d: np.ndarray, e: np.ndarray, fun=None, ctx: Optional[Conte
 	fid, params = (_capi.FUN_NONE, np.zeros(4)) if fun is None else fun_spec(fun, **fun_kwargs)
 	quad = np.zeros(nb)
 	check(_capi.lib().slq_quadrature_batch(ctx._h, nb, deg, ptr(d), ptr(e), fid, ptr(params), ptr(quad), ptr(nodes), ptr(weights)))
+	return (nodes, weights) if fun is None else (quad, nodes, weights)
+
+
+def quadrature_radau_batch(d: np.ndarray, e: np.ndarray, residual, endpoint: float, fun=None, ctx: Optional[Context] = None, **fun_kwargs):
+	"""Gauss-Radau rules with a node at `endpoint` of a batch of m x m Jacobi matrices on the device
+	(slq_quadrature_radau_batch). d, e: (nb, m) with e[:, 0] ignored; residual: beta_m per matrix, the coupling to the
+	border. Returns (nodes, weights), each (nb, m + 1), or with `fun` (quad, nodes, weights)."""
+	if endpoint is None or not np.isfinite(float(endpoint)):
+		raise ValueError("the Gauss-Radau rule needs a finite endpoint")
+	if residual is None:
+		raise ValueError("the Gauss-Radau rule needs residual = beta_m, the norm of the Lanczos residual after m steps")
+	d = np.ascontiguousarray(np.atleast_2d(d), dtype=np.float64)
+	e = np.ascontiguousarray(np.atleast_2d(e), dtype=np.float64)
+	if d.shape != e.shape:
+		raise ValueError("d and e must have the same shape")
+	nb, m = d.shape
+	residual = np.ascontiguousarray(np.broadcast_to(np.asarray(residual, dtype=np.float64).ravel(), (nb,)))
+	ctx = ctx or default_context()
+	nodes, weights = np.zeros((nb, m + 1)), np.zeros((nb, m + 1))
+	fid, params = (_capi.FUN_NONE, np.zeros(4)) if fun is None else fun_spec(fun, **fun_kwargs)
+	quad = np.zeros(nb)
+	check(_capi.lib().slq_quadrature_radau_batch(ctx._h, nb, m, ptr(d), ptr(e), ptr(residual), float(endpoint), fid, ptr(params), ptr(quad),
+												 ptr(nodes), ptr(weights)))  # fmt: skip
 	return (nodes, weights) if fun is None else (quad, nodes, weights)
 
 

@@ -19,10 +19,21 @@ def quadrature(
 	quad: str = "gw",
 	nodes: Optional[np.ndarray] = None,
 	weights: Optional[np.ndarray] = None,
+	endpoint: Optional[float] = None,
+	residual: Optional[float] = None,
 	**kwargs,
 ) -> tuple:
 	"""Nodes (ascending eigenvalues of T(d, e)) and weights (squared first eigenvector components)
-	of the degree-`deg` Gauss rule. `e` may have len(d) entries (e[0] = 0) or len(d) - 1."""
+	of the degree-`deg` Gauss rule. `e` may have len(d) entries (e[0] = 0) or len(d) - 1.
+	quad="radau": the (deg + 1)-point Gauss-Radau rule with a prescribed node at `endpoint` (a lower bound of the
+	spectrum); `residual` is beta_deg, the coupling of T to its border (the norm of the Lanczos residual after deg steps)."""
+	if quad == "radau":  # (checked before any device work)
+		if endpoint is None or not np.isfinite(float(endpoint)):
+			raise ValueError("quad='radau' needs a finite endpoint=a with a <= lambda_min")
+		if residual is None or not np.isfinite(float(residual)):
+			raise ValueError("quad='radau' needs residual=beta_deg, the norm of the Lanczos residual after deg steps")
+	elif endpoint is not None or residual is not None:
+		raise ValueError("endpoint and residual belong to quad='radau'")
 	d = np.asarray(d)
 	e = np.asarray(e)
 	deg = len(d) if deg is None else int(min(deg, len(d)))
@@ -38,10 +49,13 @@ def quadrature(
 		theta = theta[0].astype(d.dtype, copy=False)
 		tau = np.zeros(len(theta), dtype=theta.dtype)
 		tau[:deg] = engine.fttr_batch(theta[None, :], d[None, :], e[None, :], k=deg)[0]
+	elif quad == "radau":
+		theta, tau = engine.quadrature_radau_batch(d[:deg][None, :], e[:deg][None, :], [float(residual)], float(endpoint))
+		theta, tau = theta[0].astype(d.dtype, copy=False), tau[0].astype(d.dtype, copy=False)
 	else:
 		raise ValueError(f"Invalid quadrature method '{quad}' supplied")
 	if nodes is not None and weights is not None:
-		assert len(nodes) == deg and len(weights) == deg, "`nodes` and `weights` output arrays must be `deg` in length."
+		assert len(nodes) == len(theta) and len(weights) == len(theta), "`nodes` and `weights` output arrays must be `deg` in length (deg + 1 for quad='radau')."
 		np.copyto(nodes, theta)
 		np.copyto(weights, tau)
 	return theta, tau

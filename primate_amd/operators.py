@@ -57,14 +57,38 @@ class MatrixFunction(LinearOperator):
 	ring, exactly like the reference (and as slowly: one device run per probe). The default False is
 	the lock-step batched path, which starts every probe from a clean ring — what the reference's own
 	`_matvec` enforces (operators.py:116) and what its first probe always sees.
+
+	Adaptive degree (extra; `deg_max=None`, the default, changes nothing): with `deg_max`, `quad` / `quad_generated` -
+	and so `hutch(M)` - run a resumable Lanczos run of capacity deg_max in stages deg, deg + deg_step, ... (deg_step
+	defaults to engine.DEG_STEP) and stop at the first stage that meets `deg_rtol` (required: it has no default), by the
+	change of the batch sum between stages or, with `endpoint` <= lambda_min(A), by the width of the Gauss / Gauss-Radau
+	bracket (engine.quad_adaptive). The values are those of a fixed deg = `M.deg_used` run; `M.deg_used` and
+	`M.quad_bounds` (per-probe (lower, upper) of the bracket, None without endpoint) record the last call, `M.deg_history`
+	its stages and their statistics. Built-in
+	function names only. `_matvec` (f(A) v), `diag`, `xtrace`, `hutchpp` and `spectral_density` keep the fixed `deg`, and
+	the `distributed` entries refuse an adaptive MatrixFunction: a degree chosen per rank would make the result depend on
+	the sharding.
 	"""
 
 	def __init__(
 		self, A, fun: Union[str, Callable, None] = None, deg: int = 20, orth: int = 3, dtype: np.dtype = F64,
-		stale_ring: bool = False, **kwargs,
+		stale_ring: bool = False, deg_max: Optional[int] = None, deg_rtol: Optional[float] = None, deg_step: Optional[int] = None,
+		endpoint: Optional[float] = None, **kwargs,
 	) -> None:  # fmt: skip
 		assert is_linear_op(A), "Invalid operator `A`; must be dim=2 symmetric operator with defined matvec"
 		assert deg >= 2, "Degree must be >= 2"
+		self._adaptive = None
+		self.deg_used, self.quad_bounds, self.deg_history = None, None, None
+		if deg_max is not None:
+			if stale_ring:
+				raise ValueError("an adaptive degree needs the clean ring of the batched path (stale_ring=False)")
+			if not isinstance(fun, str):
+				raise ValueError("an adaptive degree takes built-in function names (the stage statistics are reduced on the device)")
+			n_cap = min(int(deg_max), A.shape[0]) if isinstance(deg_max, (int, np.integer)) and not isinstance(deg_max, bool) else deg_max
+			dm, stages, rt, ep = engine._adaptive_args(n_cap, None, deg_rtol, endpoint, deg_step, first=min(deg, A.shape[0]))
+			self._adaptive = dict(deg_max=dm, stages=stages, deg_rtol=rt, endpoint=ep)
+		elif deg_rtol is not None or deg_step is not None or endpoint is not None:
+			raise ValueError("deg_rtol, deg_step and endpoint belong to an adaptive degree: give deg_max")
 		self.shape = A.shape
 		self.dtype = np.dtype(dtype)
 		fun = (lambda x: x) if fun is None else fun
@@ -73,6 +97,7 @@ class MatrixFunction(LinearOperator):
 		self._deg = min(deg, A.shape[0])
 		self._rtol = 1e-8
 		self._orth = self._deg if orth < 0 or orth > self._deg else orth
+		self._orth_given = orth  # (the adaptive plan has capacity deg_max: out-of-range means ITS deg)
 		self._A = A
 		self._op = _as_device_operator(A, dtype=self.dtype)
 		self._plans: dict = {}
@@ -109,14 +134,31 @@ class MatrixFunction(LinearOperator):
 	def _adjoint(self):
 		return self
 
-	def _plan(self, nprobes: int, keep_basis: bool) -> engine.LanczosPlan:
-		key = (nprobes, keep_basis)
+	def _plan(self, nprobes: int, keep_basis: bool, adaptive: bool = False) -> engine.LanczosPlan:
+		key = (nprobes, keep_basis, adaptive)
 		if key not in self._plans:
 			## one cached plan per shape class; older ones are released to bound device memory
-			for k in [k for k in self._plans if k[1] == keep_basis]:
+			for k in [k for k in self._plans if k[1:] == key[1:]]:
 				self._plans.pop(k).close()
-			self._plans[key] = engine.LanczosPlan(self._op, nprobes, self._deg, self._orth, keep_basis=keep_basis)
+			deg = self._adaptive["deg_max"] if adaptive else self._deg
+			self._plans[key] = engine.LanczosPlan(self._op, nprobes, deg, self._orth_given if adaptive else self._orth, keep_basis=keep_basis)
 		return self._plans[key]
+
+	def _quad_adaptive(self, X, nprobes: int) -> np.ndarray:
+		"""`quad` through engine.quad_adaptive on a cached plan of capacity deg_max; records deg_used / quad_bounds."""
+		a = self._adaptive
+		if self._builtin is None:
+			raise ValueError("an adaptive degree takes built-in function names (the stage statistics are reduced on the device)")
+		name, kw = self._builtin
+		q, used, hist = engine.quad_adaptive(
+			self._op, X, a["deg_max"], self._orth_given, name, stages=a["stages"], deg_rtol=a["deg_rtol"], endpoint=a["endpoint"],
+			rtol=self._rtol, nprobes=nprobes, plan=self._plan(nprobes, False, adaptive=True), **kw,
+		)  # fmt: skip
+		self.deg_used, self.deg_history = used, hist
+		if a["endpoint"] is not None:
+			self.quad_bounds = (np.minimum(q[:, 0], q[:, 1]), np.maximum(q[:, 0], q[:, 1]))
+			q = np.ascontiguousarray(q[:, 0])
+		return q
 
 	def quad(self, x: np.ndarray) -> np.ndarray:
 		"""x^T f(A) x for every column of x by Lanczos quadrature (operators.py:126-151)."""
@@ -124,6 +166,8 @@ class MatrixFunction(LinearOperator):
 		x = np.atleast_2d(x).T if x.ndim == 1 else x
 		if self._stale_ring:
 			return self._quad_reference_ring(x)
+		if self._adaptive is not None:
+			return self._quad_adaptive(x, x.shape[1])
 		plan = self._plan(x.shape[1], False)
 		plan.set_probes(x)
 		plan.run(self._rtol)
@@ -140,6 +184,8 @@ class MatrixFunction(LinearOperator):
 		"""v_i^T f(A) v_i for `nprobes` probes DRAWN ON THE DEVICE (Philox stream of probe ids probe_offset..;
 		slq_plan_generate_probes): the throughput form of `quad`, with no n x nprobes host array at all."""
 		assert not self._stale_ring, "device-drawn probes start from a clean ring"
+		if self._adaptive is not None:
+			return self._quad_adaptive((pdf, int(seed), int(probe_offset)), int(nprobes))
 		plan = self._plan(int(nprobes), False)
 		plan.generate_probes(pdf, seed=int(seed), probe_offset=int(probe_offset))
 		plan.run(self._rtol)
