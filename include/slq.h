@@ -155,11 +155,32 @@ int slq_operator_matmat(slq_operator *op, const void *X, int64_t ldx, void *Y, i
  * resident (ncv = clip(orth, 2, deg), src/primate/lanczos.py:89). */
 int slq_plan_create(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth,
                     int keep_basis, slq_plan **out);
+/* A plan for f(A)v by TWO-PASS Lanczos (Borici 2000; Frommer & Simoncini 2008): no basis is kept. Its ring has
+ * the slots of a plan without keep_basis plus up to 8 more, so that one accumulation launch consumes up to 8 finished columns,
+ * and two panels lie outside the ring: a stash of the probes and the output. At most ring_slots + 10 panels in all,
+ * independent of deg. slq_plan_run is pass 1 (the launches of any run). slq_plan_fun_action, slq_plan_fun_action_dmat and
+ * slq_diag_update work as on a keep_basis plan, but EACH CALL COSTS ONE FULL RE-RUN: the coefficients come out of T, the probes
+ * come back from the stash, and the recurrence is replayed - bit for bit, its sums are taken in a fixed order - while
+ * g_t W_t is added into the output as the columns pass through the ring. Afterwards alpha, beta and steps hold the bits of
+ * pass 1: slq_plan_quadrature, slq_plan_get_tridiag, slq_density_update work before and after an action.
+ * slq_plan_get_basis and slq_plan_run_steps return SLQ_EINVAL on such a plan. Every probe call (slq_plan_set_probes,
+ * _set_probes_device, _generate_probes) also copies the probe panel into the stash, device to device (0.9 ms for a 2 GB panel) -
+ * also when only quadratures follow: a plan that never takes an action should be an ordinary one. */
+int slq_plan_create_recompute(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, slq_plan **out);
+/* mode: 0 ring only, 1 kept basis, 2 recompute; ring_slots: slots of the ring itself; acc_cols: ring columns one accumulation
+ * launch of a recompute plan consumes (0 for the other kinds). Any output may be NULL. */
+int slq_plan_basis_mode(const slq_plan *plan, int *mode, int *ring_slots, int *acc_cols);
+/* Byte accounting of a recompute plan's accumulation launches, which do not read a ring column whose coefficient is zero for
+ * every probe of a panel (probes past an early stop): columns read and columns offered, summed over launches and panels since
+ * the last reset (SLQ_ACC_SKIP=0: read == offered). Synchronises. */
+int slq_plan_action_columns(slq_plan *plan, uint64_t *read, uint64_t *offered, int reset);
 int slq_plan_destroy(slq_plan *plan);
 /* Device bytes this plan holds / would hold. */
 int slq_plan_workspace_bytes(const slq_plan *plan, size_t *bytes);
 int slq_plan_query_bytes(int dtype, int64_t n, int nprobes, int deg, int orth, int keep_basis,
                          size_t *bytes);
+/* ... of a recompute plan: ring, stash and output (host arithmetic only). Independent of deg once deg > 8. */
+int slq_plan_query_bytes_recompute(int dtype, int64_t n, int nprobes, int deg, int orth, size_t *bytes);
 /* What the plan decided (panel geometry and launch sequence): for byte models and records. */
 typedef struct {
   int panel_width;   /* PW: probes per panel row                                                        */
@@ -224,7 +245,8 @@ int slq_plan_quadrature_at(slq_plan *plan, int m, int rule, double endpoint, int
  * columns past an early stop are zero). Requires keep_basis. */
 int slq_plan_get_basis(slq_plan *plan, int probe, void *Q, int64_t ldq);
 /* Y[:, i] = f(A) x_i ~= ||x_i|| Q_i Y_i (f(theta_i) * Y_i[0,:])  (src/primate/operators.py:113-124);
- * column-major n x nprobes host output. Requires keep_basis and a completed run. */
+ * column-major n x nprobes host output. Requires a completed run on a keep_basis plan or on a recompute plan (there
+ * every call replays the run: slq_plan_create_recompute). */
 int slq_plan_fun_action(slq_plan *plan, int fun_id, const double *fun_params, void *Y,
                         int64_t ldy);
 
@@ -331,7 +353,8 @@ enum {
   SLQ_K_FINALIZE,    /* all per-step scalar kernels (partials -> alpha/beta/coefficients)           */
   SLQ_K_PROBES,      /* probe generation / layout                                                   */
   SLQ_K_QUADRATURE,  /* tridiagonal eigensolve + f reduction                                        */
-  SLQ_K_COMBINE,     /* f(A)x = sum_t g_t W_t over the kept basis (slq_plan_fun_action; not a recurrence sweep) */
+  SLQ_K_COMBINE,     /* f(A)x = sum_t g_t W_t over the kept basis (slq_plan_fun_action; not a recurrence sweep), and the
+                        accumulation launches of a recompute plan's replay (its passes count in their usual classes) */
   SLQ_K_COUNT
 };
 typedef struct {
@@ -373,6 +396,12 @@ int slq_quad_batch(slq_context *ctx, slq_operator *op, const void *X, int64_t ld
  * fun ids only. Columns are processed in as few lock-step batches as the free device memory allows. */
 int slq_fAv_batch(slq_context *ctx, slq_operator *op, const void *X, int64_t ldx, int nvec, int deg,
                   double rtol, int orth, int fun_id, const double *fun_params, void *Y, int64_t ldy);
+/* The same with the plan kind chosen: basis_mode 1 kept basis (what slq_fAv_batch does), 2 recompute plans (two passes per
+ * batch, a footprint independent of deg), 0 automatic: the kept basis when a plan for ALL nvec columns fits the free device
+ * memory (its bytes + 1 GiB <= free), otherwise recompute plans - for all columns when that fits, else halved batches.
+ * basis_used (or NULL) receives the kind taken. */
+int slq_fAv_batch_mode(slq_context *ctx, slq_operator *op, const void *X, int64_t ldx, int nvec, int deg, double rtol, int orth,
+                       int fun_id, const double *fun_params, int basis_mode, void *Y, int64_t ldy, int *basis_used);
 
 /* Single-vector drop-in for primate._lanczos.lanczos (src/primate/_lanczos.cpp:88-99), host
  * pointers, same in/out contract: v (n) is scratch and is clobbered; alpha, beta (deg+1) and

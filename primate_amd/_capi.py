@@ -63,6 +63,9 @@ _SIGNATURES = {
 	"slq_operator_shape": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
 	"slq_operator_matmat": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int]),
 	"slq_plan_create": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _PP]),
+	"slq_plan_create_recompute": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _PP]),
+	"slq_plan_basis_mode": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+	"slq_plan_query_bytes_recompute": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
 	"slq_plan_destroy": (C.c_int, [_P]),
 	"slq_plan_workspace_bytes": (C.c_int, [_P, C.POINTER(C.c_size_t)]),
 	"slq_plan_describe": (C.c_int, [_P, C.c_void_p]),
@@ -106,11 +109,13 @@ _SIGNATURES = {
 	"slq_density_update": (C.c_int, [_P, _P]),
 	"slq_density_get": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int64)]),
 	"slq_plan_profile_enable": (C.c_int, [_P, C.c_int]),
+	"slq_plan_action_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
 	"slq_plan_sweep_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
 	"slq_plan_profile_read": (C.c_int, [_P, C.POINTER(SlqProfile), C.c_int]),
 	"slq_quad_batch": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _P, _P, _P, _P]),
 	"slq_eigh_tridiag_batch": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),
 	"slq_fAv_batch": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _P, _P, C.c_int64]),
+	"slq_fAv_batch_mode": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int)]),
 	"slq_lanczos_f64": (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_int, _P, _P, _P, C.c_size_t]),
 	"slq_lanczos_f32": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, C.c_int, _P, _P, _P, C.c_size_t]),
 	"slq_debug_ring_flag_status": (C.c_int, [C.c_int]),

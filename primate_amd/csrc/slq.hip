@@ -28,6 +28,7 @@
 #include "slq_build.hpp"  // an operator's derived data built on the device
 #include "slq_density.hpp"  // spectral density accumulator (slq_density_*)
 #include "slq_radau.hpp"    // prefix quadrature, Gauss-Radau rule, stage statistics (slq_plan_quadrature_at)
+#include "slq_action.hpp"   // two-pass f(A)v: the accumulation of a recompute plan's replay (slq_plan_create_recompute)
 
 using namespace slq;
 
@@ -255,6 +256,19 @@ struct slq_plan {
   bool sweep_skip = true;     // the update sweep does not read ring columns whose coefficient is zero for every probe of the panel (SLQ_SWEEP_SKIP=0: reads them all)
   unsigned long long *sweep_cols_d = nullptr;  // {ring columns the update sweeps read, columns they were offered}, summed over launches and panels (slq_plan_sweep_columns)
   bool last_nostore = true;   // the update pass of a run's last step does not store W_deg (plans without a kept basis; SLQ_LAST_STORE=1 stores)
+  // two-pass f(A)v (slq_plan_create_recompute). basis_mode: 0 ring only, 1 kept basis, 2 recompute - the ring
+  // has acc_cols + 1 slots at least, and two panels lie behind it: slot v_slot the stash of the probes, slot y_slot the output
+  int basis_mode = 0;
+  int acc_cols = 0;           // finished ring columns one accumulation launch consumes (<= kAccCols)
+  int v_slot = 0, y_slot = 0; // where the action's probes and its output are (kept basis: slots 0 and deg)
+  double *acc_coef = nullptr; // [deg][bpad] coefficients g_t of the action (st.gamma is live during the replay)
+  bool stash_ready = false;   // the stash holds the probes of the last probe call ...
+  bool stash_unit = false;    // ... which were device-drawn Rademacher probes taken with the known-norm shortcut
+  bool acc_skip = true;       // the accumulation does not read columns whose coefficient is zero for every probe of the panel (SLQ_ACC_SKIP=0: reads them all)
+  hipGraphExec_t replay_exec = nullptr;  // the replay (deg steps + accumulation launches: a linear chain) captured for replay_rtol / replay_variant
+  double replay_rtol = 0.0;
+  unsigned replay_variant = 0;
+  bool replay_xt_out = false;
 };
 
 // SLQ_TILES: 0 none, 1 workgroup tiles landed behind barriers (k_csr_tile_pass), 2 tiles fed through a ring of LDS slots by
@@ -2380,6 +2394,11 @@ static int ring_slots(int deg, int orth, int keep_basis) {
   return std::max(orth + 1, 3);
 }
 
+// A recompute plan's ring: the quadrature plan's, widened until an accumulation launch finds acc finished columns beside the one
+// the step wrote (acc + 1 slots), acc = min(kAccCols, deg). At most kAccCols slots more, none when orth >= kAccCols.
+static int recompute_acc_cols(int deg) { return std::min(kAccCols, deg); }
+static int recompute_ring_slots(int deg, int orth) { return std::max(ring_slots(deg, orth, 0), recompute_acc_cols(deg) + 1); }
+
 static void grid_sizes(int n, int LPR, int NP, int num_cus, int *nblkA, int *nblkS, int *nblkU, bool pipelined) {
   const int RPW = 64 / LPR;
   const int rows_per_block = kWaves * RPW;
@@ -2433,6 +2452,35 @@ static int plan_bytes_on(const slq_operator *op, int nprobes, int deg, int orth,
   return SLQ_OK;
 }
 
+// The footprint of a recompute plan does not depend on deg once deg > kAccCols, so the query answers for any deg >= 1 (a plan
+// itself is still limited to kMaxDeg steps).
+extern "C" int slq_plan_query_bytes_recompute(int dtype, int64_t n, int nprobes, int deg, int orth, size_t *bytes) {
+  if (!bytes) return fail(SLQ_EINVAL, "bytes is NULL");
+  SLQ_TRY(check_dtype(dtype));
+  if (n <= 0 || nprobes <= 0) return fail(SLQ_EINVAL, "n and nprobes must be positive");
+  if (deg < 1) return fail(SLQ_EINVAL, "Number of steps must be positive!");
+  if (deg > n) deg = (int)n;
+  if (orth < 0 || orth > deg) orth = deg;
+  int LPR, PW, NP;
+  choose_geometry(dtype, nprobes, &LPR, &PW, &NP);
+  const size_t S = (size_t)recompute_ring_slots(deg, orth) + 2;  // + the stash of the probes and the output panel
+  *bytes = S * (size_t)NP * (size_t)n * PW * esize(dtype);
+  return SLQ_OK;
+}
+
+// plan_bytes_on for a plan kind (basis_mode 0 ring only, 1 kept basis, 2 recompute). The coefficient buffer of a recompute plan
+// (deg * bpad doubles: 1 MB at deg 512, 256 probes) is left out like the other scalar arrays: the callers keep 1 GiB of margin.
+static int plan_bytes_on_mode(const slq_operator *op, int nprobes, int deg, int orth, int mode, size_t *bytes) {
+  SLQ_TRY(plan_bytes_on(op, nprobes, deg, orth, mode == 1, bytes));
+  if (mode == 2) {
+    size_t ring0 = 0, ring2 = 0;
+    SLQ_TRY(slq_plan_query_bytes(op->dtype, op->n, nprobes, deg, orth, 0, &ring0));
+    SLQ_TRY(slq_plan_query_bytes_recompute(op->dtype, op->n, nprobes, deg, orth, &ring2));
+    *bytes += ring2 - ring0;
+  }
+  return SLQ_OK;
+}
+
 extern "C" int slq_plan_destroy(slq_plan *p) {
   if (!p) return SLQ_OK;
   hipSetDevice(p->ctx->device);
@@ -2440,6 +2488,8 @@ extern "C" int slq_plan_destroy(slq_plan *p) {
   for (auto &ev : p->events) { hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
   for (auto &ev : p->pool) { hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
   for (auto &g : p->graphs) hipGraphExecDestroy(g.exec);
+  if (p->replay_exec) hipGraphExecDestroy(p->replay_exec);
+  if (p->acc_coef) hipFree(p->acc_coef);
   if (p->at_d) hipFree(p->at_d);
   if (p->at_flags) hipFree(p->at_flags);
   if (p->ring) hipFree(p->ring);
@@ -2458,8 +2508,27 @@ extern "C" int slq_plan_destroy(slq_plan *p) {
 
 static int set_kernel_attributes(slq_plan *p);
 
+static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, int basis_mode, slq_plan **out);
+
 extern "C" int slq_plan_create(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth,
                                int keep_basis, slq_plan **out) {
+  return plan_create_mode(ctx, op, nprobes, deg, orth, keep_basis != 0 ? 1 : 0, out);
+}
+
+extern "C" int slq_plan_create_recompute(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, slq_plan **out) {
+  return plan_create_mode(ctx, op, nprobes, deg, orth, 2, out);
+}
+
+extern "C" int slq_plan_basis_mode(const slq_plan *p, int *mode, int *ring_slots_out, int *acc_cols) {
+  if (!p) return fail(SLQ_EINVAL, "plan is NULL");
+  if (mode) *mode = p->basis_mode;
+  if (ring_slots_out) *ring_slots_out = p->S;
+  if (acc_cols) *acc_cols = p->acc_cols;
+  return SLQ_OK;
+}
+
+static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, int basis_mode, slq_plan **out) {
+  const int keep_basis = basis_mode == 1;
   if (!ctx || !op || !out) return fail(SLQ_EINVAL, "ctx/op/out is NULL");
   *out = nullptr;
   if (op->ctx != ctx) return fail(SLQ_EINVAL, "operator belongs to another context");
@@ -2485,7 +2554,12 @@ extern "C" int slq_plan_create(slq_context *ctx, slq_operator *op, int nprobes, 
                    env_int("SLQ_FUSED_LDS_PAD", -1), env_int("SLQ_SPMM_LDS_PAD", 57344), env_int("SLQ_DEFER_AXPY", 1) != 0};
   choose_geometry(op->dtype, nprobes, &p->LPR, &p->PW, &p->NP);
   p->bpad = p->NP * p->PW;
-  p->S = ring_slots(deg, orth, p->keep_basis);
+  p->basis_mode = basis_mode;
+  p->S = basis_mode == 2 ? recompute_ring_slots(deg, orth) : ring_slots(deg, orth, p->keep_basis);
+  p->acc_cols = basis_mode == 2 ? recompute_acc_cols(deg) : 0;
+  p->v_slot = basis_mode == 2 ? p->S : 0;
+  p->y_slot = basis_mode == 2 ? p->S + 1 : deg;
+  p->acc_skip = env_int("SLQ_ACC_SKIP", 1) != 0;
   p->slot_stride = (int64_t)p->NP * p->n * p->PW;
   p->rmax = std::max(p->keep_basis ? deg : orth, 1);
   // Row loop of the dots/update passes (slq_kernels.hpp: k_csr_pass). Measured on configs[1] and on the 100^3 grid
@@ -2577,8 +2651,9 @@ extern "C" int slq_plan_create(slq_context *ctx, slq_operator *op, int nprobes, 
   memset(&p->acc, 0, sizeof(p->acc));
   memset(&p->st, 0, sizeof(p->st));
 
-  const size_t ring_bytes = (size_t)p->S * (size_t)p->slot_stride * p->esz;
+  const size_t ring_bytes = (size_t)(p->S + (basis_mode == 2 ? 2 : 0)) * (size_t)p->slot_stride * p->esz;  // (recompute: stash and output behind the ring)
   const size_t bp = p->bpad;
+  const size_t ncoef = basis_mode == 2 ? (size_t)deg * bp : 0;
   // alpha[deg+1], nu[orth margin for stale vectors t < 0 | deg+1], vnorm2, coefA[2], coefB, cross, gram[2][kFusedMaxR+1], gamma[rmax]
   const size_t nscal = ((size_t)(deg + 1) * 2 + (size_t)orth + 1 + 2 + 1 + 1 + 2 * (kFusedMaxR + 1) + (size_t)p->rmax) * bp;
   p->part_maxblk = std::max(std::max(std::max(std::max(p->nblkA, p->nblkF), p->nblkU), p->nblkS), p->nblkT);
@@ -2586,8 +2661,9 @@ extern "C" int slq_plan_create(slq_context *ctx, slq_operator *op, int nprobes, 
   hipError_t e = hipMalloc(&p->ring, ring_bytes);
   if (e == hipSuccess) e = hipMalloc((void **)&p->scal, nscal * 8);
   if (e == hipSuccess) e = hipMalloc((void **)&p->part, npart * 8);
-  if (e == hipSuccess) e = hipMalloc((void **)&p->sweep_cols_d, 2 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMemset(p->sweep_cols_d, 0, 2 * sizeof(unsigned long long));
+  if (e == hipSuccess && ncoef) e = hipMalloc((void **)&p->acc_coef, ncoef * 8);
+  if (e == hipSuccess) e = hipMalloc((void **)&p->sweep_cols_d, 4 * sizeof(unsigned long long));  // (words 2, 3: the accumulation launches of a recompute plan, slq_plan_action_columns)
+  if (e == hipSuccess) e = hipMemset(p->sweep_cols_d, 0, 4 * sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMalloc((void **)&p->st.active, bp * 2 * sizeof(int) + 16);
   if (e == hipSuccess) e = hipMalloc((void **)&p->quad_d, (bp + 2 * bp * (size_t)deg) * 8);
   // dense fp64 operator on the matrix cores with 32-row tiles: n/32 workgroups per panel rarely fill 256 CUs, so K is
@@ -2614,7 +2690,7 @@ extern "C" int slq_plan_create(slq_context *ctx, slq_operator *op, int nprobes, 
     return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP,
                 "plan workspace (%zu bytes of Lanczos panels): %s", ring_bytes, hipGetErrorString(e));
   }
-  p->bytes = ring_bytes + nscal * 8 + npart * 8 + (bp + 2 * bp * deg) * 8 + t_slabs * (size_t)p->slot_stride * p->esz + t2_bytes;
+  p->bytes = ring_bytes + ncoef * 8 + nscal * 8 + npart * 8 + (bp + 2 * bp * deg) * 8 + t_slabs * (size_t)p->slot_stride * p->esz + t2_bytes;
   double *s = p->scal;
   p->st.alpha = s; s += (size_t)(deg + 1) * bp;
   s += (size_t)orth * bp;  // nu rows for t = -orth .. -1 (zero unless the drop-in entry preloads stale columns)
@@ -2895,6 +2971,19 @@ extern "C" int slq_plan_sweep_columns(slq_plan *p, uint64_t *read, uint64_t *off
   return SLQ_OK;
 }
 
+// The same accounting for the accumulation launches of a recompute plan's replay (k_action_accumulate): ring columns read against columns offered.
+extern "C" int slq_plan_action_columns(slq_plan *p, uint64_t *read, uint64_t *offered, int reset) {
+  if (!p) return fail(SLQ_EINVAL, "plan is NULL");
+  HIP_TRY(hipSetDevice(p->ctx->device));
+  unsigned long long h[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(h, p->sweep_cols_d + 2, sizeof(h), hipMemcpyDeviceToHost, p->ctx->stream));
+  if (reset) HIP_TRY(hipMemsetAsync(p->sweep_cols_d + 2, 0, sizeof(h), p->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+  if (read) *read = h[0];
+  if (offered) *offered = h[1];
+  return SLQ_OK;
+}
+
 extern "C" int slq_plan_workspace_bytes(const slq_plan *plan, size_t *bytes) {
   if (!plan || !bytes) return fail(SLQ_EINVAL, "plan/bytes is NULL");
   *bytes = plan->bytes;
@@ -2920,8 +3009,15 @@ static int stage_chunk_cols(const slq_plan *p) {
 // ||v||^2 of slot 0 -> nu_0, activity, first coefficients
 // unit_entries: every entry of every probe is +-1 (Rademacher probes drawn by k_gen_probes): ||v||^2 = n is known, the norm sweep - one read of
 // the panel, 0.38 ms of configs[1]'s 55 - is skipped (r04; bitwise the same nu_0: the sweep's partial sums are exact integers)
-static int init_from_probes(slq_plan *p, int sphere, bool unit_entries = false) {
+// restoring: the probes were copied back from a recompute plan's stash (replay_action) - everything else is what the original probe call did
+static int init_from_probes(slq_plan *p, int sphere, bool unit_entries = false, bool restoring = false) {
   hipStream_t st = p->ctx->stream;
+  if (p->basis_mode == 2 && !restoring) {
+    // recompute plans: pass 2 starts from these probes again, and slq_diag_update needs v next to f(A)v
+    HIP_TRY(hipMemcpyAsync(slot_ptr(p, p->v_slot), slot_ptr(p, 0), (size_t)p->slot_stride * p->esz, hipMemcpyDeviceToDevice, st));
+    p->stash_unit = unit_entries;
+    p->stash_ready = true;
+  }
   dim3 g(p->nblkS, p->NP);
   if (!unit_entries)
     PROFILED(p, SLQ_K_AXPY_NORM,
@@ -3584,6 +3680,7 @@ extern "C" int slq_plan_run(slq_plan *p, double rtol) {
 extern "C" int slq_plan_run_steps(slq_plan *p, double rtol, int upto) {
   if (!p) return fail(SLQ_EINVAL, "plan is NULL");
   if (p->nstale > 0) return fail(SLQ_EINVAL, "slq_plan_run_steps: a plan with stale ring columns is not resumable");
+  if (p->basis_mode == 2) return fail(SLQ_EINVAL, "slq_plan_run_steps: a recompute plan runs in one piece (a staged two-pass run is not supported)");
   const bool fresh = p->probes_ready;  // (probes set or generated and not yet consumed: cur == 0)
   if (!fresh && !(p->ran && p->cur > 0)) return fail(SLQ_EINVAL, "slq_plan_run_steps: set or generate probes first");
   const int cur = fresh ? 0 : p->cur;
@@ -3858,9 +3955,92 @@ static int launch_reorth_update_range(slq_plan *p, int j, int istart, int r, boo
 
 static int launch_reorth_update(slq_plan *p, int j, int r, int istart, bool axpy, int klass) { return launch_reorth_update_range(p, j, istart, r, axpy, klass); }
 
-// Y = f(A) X on the device: result left in ring slot `deg` (panel layout)
+// ---- two-pass f(A)v: the replay of a recompute plan -------------------------------------------------
+static int launch_action_accumulate(slq_plan *p, int t0, int nc, bool init) {
+  hipStream_t st = p->ctx->stream;
+  const dim3 gS(p->nblkS, p->NP);
+  PROFILED(p, SLQ_K_COMBINE,
+           DISPATCH(p->dtype, p->LPR,
+                    (k_action_accumulate<F, L><<<gS, dim3(kBlock), 0, st>>>(p->n, (const F *)p->ring, p->slot_stride, p->S, t0, nc,
+                                                                          p->acc_coef + (size_t)t0 * p->bpad, p->bpad,
+                                                                          (F *)slot_ptr(p, p->y_slot), init ? 1 : 0, p->acc_skip ? 1 : 0, p->sweep_cols_d + 2))));
+  return SLQ_OK;
+}
+
+// the run's launch sequence again, in pieces of up to acc_cols steps, each followed by the accumulation of the columns it
+// finished: after step j the ring holds W_{j+2-S} .. W_{j+1}, and S >= acc_cols + 1 keeps the piece's oldest column resident
+static int enqueue_replay(slq_plan *p, double rtol) {
+  const int fused = p->sw.fused;
+  const bool nt = p->sw.nt != 0;
+  int c0 = 0;
+  for (int j = 0; j < p->deg; ++j) {
+    if (j - c0 + 1 < p->acc_cols && j != p->deg - 1) continue;
+    SLQ_TRY(enqueue_run(p, rtol, fused, nt, c0, j + 1));
+    SLQ_TRY(launch_action_accumulate(p, c0, j + 1 - c0, c0 == 0));
+    c0 = j + 1;
+  }
+  HIP_TRY(hipGetLastError());
+  return SLQ_OK;
+}
+
+// pass 2: probes back from the stash, the state the original probe call left (init_from_probes with its arguments), the replay.
+// Afterwards alpha, nu, steps hold the bits of pass 1 again and the output panel holds sum_t g_t W_t.
+static int replay_action(slq_plan *p) {
+  if (!p->stash_ready) return fail(SLQ_EINVAL, "internal: a recompute plan without stashed probes");
+  hipStream_t st = p->ctx->stream;
+  const double rtol = p->run_rtol;
+  HIP_TRY(hipMemcpyAsync(slot_ptr(p, 0), slot_ptr(p, p->v_slot), (size_t)p->slot_stride * p->esz, hipMemcpyDeviceToDevice, st));
+  SLQ_TRY(init_from_probes(p, p->pdf_sphere, p->stash_unit, true));
+  const bool graph_ok = p->sw.graph && !p->prof && p->op->kind != OP_CALLBACK && p->op->kind != OP_DEVICE_CALLBACK;
+  int rc = SLQ_OK;
+  if (!graph_ok) {
+    rc = enqueue_replay(p, rtol);
+  } else {
+    const unsigned variant = (p->sw.key() * 31u + (unsigned)p->nstale) * 31u + 2u;  // (never a key of run_range's cache: those graphs live in p->graphs)
+    if (p->replay_exec && (p->replay_rtol != rtol || p->replay_variant != variant)) {
+      HIP_TRY(hipGraphExecDestroy(p->replay_exec));
+      p->replay_exec = nullptr;
+    }
+    if (!p->replay_exec) {
+      hipGraph_t graph = nullptr;
+      HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+      rc = enqueue_replay(p, rtol);
+      hipError_t ce = hipStreamEndCapture(st, &graph);
+      if (rc != SLQ_OK) {
+        if (graph) hipGraphDestroy(graph);
+      } else if (ce != hipSuccess) {
+        rc = fail(SLQ_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
+      } else {
+        ce = hipGraphInstantiate(&p->replay_exec, graph, nullptr, nullptr, 0);
+        hipGraphDestroy(graph);
+        if (ce != hipSuccess) {
+          p->replay_exec = nullptr;
+          rc = fail(SLQ_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(ce));
+        }
+      }
+      if (rc == SLQ_OK) {
+        p->replay_rtol = rtol;
+        p->replay_variant = variant;
+        p->replay_xt_out = p->prev_xt;
+      }
+    }
+    if (rc == SLQ_OK) {
+      hipError_t le = hipGraphLaunch(p->replay_exec, st);
+      if (le != hipSuccess) rc = fail(SLQ_EHIP, "hipGraphLaunch: %s", hipGetErrorString(le));
+      p->prev_xt = p->replay_xt_out;
+    }
+  }
+  p->probes_ready = false;
+  if (rc != SLQ_OK) return rc;  // (ran stays false: the plan needs new probes and a run)
+  p->ran = true;
+  p->cur = p->deg;
+  return SLQ_OK;
+}
+
+// Y = f(A) X on the device: result left in panel y_slot (kept basis: ring slot `deg`; recompute: behind the ring)
 static int fun_action_device(slq_plan *p, int fun_id, const double *fun_params) {
-  if (!p->keep_basis) return fail(SLQ_EINVAL, "plan was created without keep_basis");
+  if (p->basis_mode == 0) return fail(SLQ_EINVAL, "plan was created without keep_basis");
+  const bool two_pass = p->basis_mode == 2;
   SLQ_TRY(need_finished_run(p, "slq_plan_fun_action / slq_diag_update"));
   if (fun_id < SLQ_FUN_IDENTITY || fun_id > SLQ_FUN_SOFTSIGN) return fail(SLQ_EINVAL, "Unknown function id %d.", fun_id);
   HIP_TRY(hipSetDevice(p->ctx->device));
@@ -3877,19 +4057,26 @@ static int fun_action_device(slq_plan *p, int fun_id, const double *fun_params) 
   if (lds > 48 * 1024)
     HIP_TRY(hipFuncSetAttribute((const void *)k_fun_coeffs<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIP_TRY(hipMemsetAsync(p->fail_d, 0, sizeof(int), st));
-  // gamma row deg-1-t = -g_t: the update kernel's "w -= gamma W" then accumulates +g_t W_t into a
-  // zeroed slot while walking t = deg-1 .. 0
-  HIP_TRY(hipMemsetAsync(p->st.gamma, 0, (size_t)deg * p->bpad * 8, st));
+  // kept basis: gamma row deg-1-t = -g_t: the update kernel's "w -= gamma W" then accumulates +g_t W_t into a
+  // zeroed slot while walking t = deg-1 .. 0. Recompute: row t = +g_t in a buffer of its own (st.gamma is live during the replay)
+  double *coef = two_pass ? p->acc_coef : p->st.gamma;
+  const double sign = two_pass ? 1.0 : -1.0;
+  const int reverse_rows = two_pass ? 0 : 1;
+  HIP_TRY(hipMemsetAsync(coef, 0, (size_t)deg * p->bpad * 8, st));
   if (zg) {
     PROFILED(p, SLQ_K_QUADRATURE,
-             (k_fun_coeffs<true><<<dim3(p->nprobes), dim3(64), lds, st>>>(p->st, fun_id, p0, p1, -1.0, 1, p->st.gamma, zscr, p->fail_d)));
+             (k_fun_coeffs<true><<<dim3(p->nprobes), dim3(64), lds, st>>>(p->st, fun_id, p0, p1, sign, reverse_rows, coef, zscr, p->fail_d)));
   } else {
     PROFILED(p, SLQ_K_QUADRATURE,
-             (k_fun_coeffs<false><<<dim3(p->nprobes), dim3(64), lds, st>>>(p->st, fun_id, p0, p1, -1.0, 1, p->st.gamma, nullptr, p->fail_d)));
+             (k_fun_coeffs<false><<<dim3(p->nprobes), dim3(64), lds, st>>>(p->st, fun_id, p0, p1, sign, reverse_rows, coef, nullptr, p->fail_d)));
   }
+  if (two_pass) {
+    SLQ_TRY(replay_action(p));
+  } else {
   // output accumulates in slot `deg` (the spare slot behind the basis; it held the last residual)
   HIP_TRY(hipMemsetAsync(slot_ptr(p, deg), 0, (size_t)p->slot_stride * p->esz, st));
   SLQ_TRY(launch_reorth_update(p, deg - 1, deg, 0, false, SLQ_K_COMBINE));  // (its own profile class: these bytes are not the recurrence's update sweep)
+  }
   HIP_TRY(hipGetLastError());
   int bad = 0;
   HIP_TRY(hipMemcpyAsync(&bad, p->fail_d, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -3902,7 +4089,7 @@ extern "C" int slq_plan_fun_action(slq_plan *p, int fun_id, const double *fun_pa
   if (!p || !Y) return fail(SLQ_EINVAL, "plan/Y is NULL");
   if (ldy < p->n) return fail(SLQ_EINVAL, "ldy < n");
   SLQ_TRY(fun_action_device(p, fun_id, fun_params));
-  return panel_to_host(p, p->deg, 0, p->nprobes, Y, ldy, nullptr);
+  return panel_to_host(p, p->y_slot, 0, p->nprobes, Y, ldy, nullptr);
 }
 
 // ---- diagonal estimator state (device-resident) ----------------------------------------------------
@@ -3948,10 +4135,10 @@ extern "C" int slq_diag_update(slq_diag *d, slq_plan *p, int fun_id, const doubl
   k_probe_scale<<<dim3((p->bpad + 255) / 256), dim3(256), 0, st>>>(p->st, p->st.coefB);
   const dim3 g((p->n + 63) / 64);
   if (p->dtype == SLQ_F64)
-    k_diag_accumulate<double><<<g, dim3(64), 0, st>>>(p->n, (const double *)slot_ptr(p, 0), (const double *)slot_ptr(p, p->deg),
+    k_diag_accumulate<double><<<g, dim3(64), 0, st>>>(p->n, (const double *)slot_ptr(p, p->v_slot), (const double *)slot_ptr(p, p->y_slot),
                                                       p->PW, p->nprobes, p->st.coefB, d->buf, d->buf + d->n, d->buf + 2 * d->n);
   else
-    k_diag_accumulate<float><<<g, dim3(64), 0, st>>>(p->n, (const float *)slot_ptr(p, 0), (const float *)slot_ptr(p, p->deg),
+    k_diag_accumulate<float><<<g, dim3(64), 0, st>>>(p->n, (const float *)slot_ptr(p, p->v_slot), (const float *)slot_ptr(p, p->y_slot),
                                                      p->PW, p->nprobes, p->st.coefB, d->buf, d->buf + d->n, d->buf + 2 * d->n);
   HIP_TRY(hipGetLastError());
   d->count += p->nprobes;
@@ -4276,7 +4463,7 @@ extern "C" int slq_plan_fun_action_dmat(slq_plan *p, int fun_id, const double *f
   SLQ_TRY(fun_action_device(p, fun_id, fun_params));
   hipStream_t st = p->ctx->stream;
   dim3 g((p->n + 63) / 64, (p->nprobes + 63) / 64);
-  hipLaunchKernelGGL(k_panel_to_cols<double>, g, dim3(256), 0, st, p->n, (const double *)slot_ptr(p, p->deg), 0, p->nprobes,
+  hipLaunchKernelGGL(k_panel_to_cols<double>, g, dim3(256), 0, st, p->n, (const double *)slot_ptr(p, p->y_slot), 0, p->nprobes,
                      OUT->d + (size_t)o0 * p->n, p->PW, (const double *)nullptr, p->op->perm_d);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
@@ -4608,18 +4795,32 @@ extern "C" int slq_quad_batch(slq_context *ctx, slq_operator *op, const void *X,
 
 extern "C" int slq_fAv_batch(slq_context *ctx, slq_operator *op, const void *X, int64_t ldx, int nvec, int deg,
                              double rtol, int orth, int fun_id, const double *fun_params, void *Y, int64_t ldy) {
+  return slq_fAv_batch_mode(ctx, op, X, ldx, nvec, deg, rtol, orth, fun_id, fun_params, 1, Y, ldy, nullptr);
+}
+
+extern "C" int slq_fAv_batch_mode(slq_context *ctx, slq_operator *op, const void *X, int64_t ldx, int nvec, int deg, double rtol, int orth,
+                                  int fun_id, const double *fun_params, int basis_mode, void *Y, int64_t ldy, int *basis_used) {
   if (!ctx || !op || !X || !Y) return fail(SLQ_EINVAL, "ctx/op/X/Y is NULL");
+  if (basis_mode < 0 || basis_mode > 2) return fail(SLQ_EINVAL, "basis_mode %d (0 automatic, 1 kept basis, 2 recompute)", basis_mode);
   if (nvec <= 0) return fail(SLQ_EINVAL, "nvec must be positive");
   if (ldx < op->n || ldy < op->n) return fail(SLQ_EINVAL, "ldx/ldy < n");
   int d = deg, o = orth;
   SLQ_TRY(normalise_params(op->n, &d, &o));
-  // the whole basis of every column is kept (deg + 1 panels): chunk the columns to the free device memory
+  // kept basis: the whole basis of every column is kept (deg + 1 panels): chunk the columns to the free device memory.
+  // Automatic: the kept basis when the WHOLE column count fits, otherwise recompute plans (whole count first, then halving).
   size_t free_b = 0, total_b = 0;
   SLQ_TRY(slq_context_meminfo(ctx, &free_b, &total_b));
+  int mode = basis_mode;
+  if (mode == 0) {
+    size_t need = 0;
+    SLQ_TRY(plan_bytes_on_mode(op, nvec, d, o, 1, &need));
+    mode = need + ((size_t)1 << 30) <= free_b ? 1 : 2;
+  }
+  if (basis_used) *basis_used = mode;
   int chunk = nvec;
   for (;;) {
     size_t need = 0;
-    SLQ_TRY(plan_bytes_on(op, chunk, d, o, 1, &need));
+    SLQ_TRY(plan_bytes_on_mode(op, chunk, d, o, mode, &need));
     if (need + ((size_t)1 << 30) <= free_b || chunk <= 8) break;
     chunk = (chunk + 1) / 2;
   }
@@ -4632,7 +4833,7 @@ extern "C" int slq_fAv_batch(slq_context *ctx, slq_operator *op, const void *X, 
     if (nc != plan_cols) {
       if (p) slq_plan_destroy(p);
       p = nullptr;
-      rc = slq_plan_create(ctx, op, nc, d, o, 1, &p);
+      rc = plan_create_mode(ctx, op, nc, d, o, mode, &p);
       plan_cols = nc;
       if (rc != SLQ_OK) break;
     }

@@ -30,6 +30,13 @@ def _collective_device(group, device: Optional[str]) -> str:
 	return f"cuda:{int(os.environ['LOCAL_RANK']) if 'LOCAL_RANK' in os.environ else torch.cuda.current_device()}"
 
 
+def _refuse_auto_basis(basis) -> None:
+	"""basis="auto" picks the plan kind from the free memory of a rank's own GPU: the bits of a sharded result would depend
+	on the sharding (and on who else is on a device), so the sharded entries take "keep" or "recompute" only."""
+	if basis == "auto":
+		raise ValueError("the sharded entries take basis='keep' or 'recompute': 'auto' would choose per rank")
+
+
 def _refuse_adaptive(*objs, **kwargs) -> None:
 	"""Every sharded entry promises a result that does not depend on the sharding. A Lanczos degree chosen from the
 	statistics of a rank's own probes (MatrixFunction(..., deg_max=...)) would break that, so such an operator is refused
@@ -205,14 +212,20 @@ def sharded_hutch_device(op, nprobes: Optional[int] = None, deg: int = 20, orth:
 	return allreduce_trace(q, group=group)
 
 
-def sharded_diag_device(op, nprobes: int, deg: int, orth: int = 3, fun="identity", pdf: str = "rademacher", seed: int = 0, rtol: float = 1e-8, batch: int = 256, group=None, **fun_kwargs):
+def sharded_diag_device(op, nprobes: int, deg: int, orth: int = 3, fun="identity", pdf: str = "rademacher", seed: int = 0, rtol: float = 1e-8, batch: int = 256, group=None, basis: str = "keep", **fun_kwargs):
 	"""diag f(A) with a fixed probe budget sharded over the ranks of `group` (BASELINE.json configs[3]):
 	every rank accumulates numer += f(A)v * v and denom += v * v on its own GPU for its probe ids, then
 	ONE all-reduce of the 2n-vector (numer, denom) combines them (16 MB at n = 2e6 fp32).
 	Returns (numer / denom, numer, denom, count) — the Hutchinson diagonal estimate of the pooled probes.
 	(The reference's running mean of successive ratios, diagonal.py:79, is order-dependent and is only
-	reproduced by the single-process `primate_amd.diagonal.diag`.)"""
+	reproduced by the single-process `primate_amd.diagonal.diag`.) basis: "keep" or "recompute" (engine.LanczosPlan)."""
 	_refuse_adaptive(op)
+	_refuse_auto_basis(basis)
+	from .engine import _basis_arg
+
+	basis = _basis_arg(False, basis)
+	if basis is None:
+		raise ValueError("basis must be 'keep' or 'recompute'")
 	import torch.distributed as dist
 
 	from .engine import DiagAccumulator, LanczosPlan
@@ -224,7 +237,7 @@ def sharded_diag_device(op, nprobes: int, deg: int, orth: int = 3, fun="identity
 	done = lo
 	while done < hi:
 		m = min(batch, hi - done)
-		plan = LanczosPlan(op, m, deg, orth, keep_basis=True)
+		plan = LanczosPlan(op, m, deg, orth, basis=basis)
 		plan.generate_probes(pdf, seed=seed, probe_offset=done)
 		plan.run(rtol)
 		acc.update(plan, fun, **fun_kwargs)
@@ -330,7 +343,7 @@ def _xtrace_row_sharded(M, count: int, batch: int, pdf: str, seed: int, group, f
 		if k not in own_plans:
 			if len(own_plans) >= 3:  # (full blocks: ns and nloc; the last, shorter block: two more - drop the oldest)
 				own_plans.pop(next(iter(own_plans))).close()
-			own_plans[k] = engine.LanczosPlan(M._op, k, M._deg, M._orth, keep_basis=True)
+			own_plans[k] = engine.LanczosPlan(M._op, k, M._deg, M._orth, basis=getattr(M, "_basis", "keep"))
 		return own_plans[k]
 
 	def apply_fun(src, c0: int, nloc: int):
@@ -434,6 +447,7 @@ def sharded_xtrace(M, count: int, batch: int = 128, pdf: str = "sphere", seed: i
 	Gram-matrix work per rank, one m x m all-reduce per Gram matrix, all-to-alls instead of all-gathers) - for n m beyond one
 	GPU's HBM or blocks wide enough for the dense algebra to matter; needs the device probe stream."""
 	_refuse_adaptive(M)
+	_refuse_auto_basis(getattr(M, "_basis", "keep"))
 	import torch.distributed as dist
 
 	from .trace import xtrace

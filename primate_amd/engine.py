@@ -234,19 +234,67 @@ class DeviceOperator:
 			pass
 
 
-class LanczosPlan:
-	"""Workspace + state of one batched lock-step Lanczos run over `nprobes` probes."""
+BASIS_MODES = {None: 0, "keep": 1, "recompute": 2}
 
-	def __init__(self, op: DeviceOperator, nprobes: int, deg: int, orth: int = 0, keep_basis: bool = False):
+
+def _basis_arg(keep_basis: bool = False, basis: Optional[str] = None, auto: bool = False) -> Optional[str]:
+	"""The plan kind behind (keep_basis, basis): None (ring only), "keep", "recompute", or - where `auto` admits it - "auto".
+	Checked before the library is touched."""
+	names = ("keep", "recompute") + (("auto",) if auto else ())
+	if basis is not None and (not isinstance(basis, str) or basis not in names):
+		raise ValueError(f"basis must be one of {names} (or None), not {basis!r}")
+	if keep_basis and basis not in (None, "keep"):
+		raise ValueError(f"keep_basis=True contradicts basis={basis!r}")
+	return "keep" if (keep_basis and basis is None) else basis
+
+
+def plan_query_bytes(dtype, n: int, nprobes: int, deg: int, orth: int = 0, basis: Optional[str] = None) -> int:
+	"""Device bytes of the Lanczos panels a plan of this shape would hold (host arithmetic, nothing is allocated): `basis` None
+	the ring of a quadrature plan, "keep" the deg + 1 slots of a kept basis, "recompute" ring + probe stash + output of a
+	two-pass plan (independent of deg)."""
+	basis = _basis_arg(False, basis)
+	b = C.c_size_t()
+	if basis == "recompute":
+		check(_capi.lib().slq_plan_query_bytes_recompute(_capi.dtype_id(dtype), int(n), int(nprobes), int(deg), int(orth), C.byref(b)))
+	else:
+		check(_capi.lib().slq_plan_query_bytes(_capi.dtype_id(dtype), int(n), int(nprobes), int(deg), int(orth), int(basis == "keep"), C.byref(b)))
+	return int(b.value)
+
+
+class LanczosPlan:
+	"""Workspace + state of one batched lock-step Lanczos run over `nprobes` probes.
+
+	`basis` (or the older `keep_basis=True`, which is `basis="keep"`) says what the f(A)v action runs on: "keep" retains all deg
+	Lanczos vectors (deg + 1 panels); "recompute" keeps none - `fun_action`, `fun_action_into` and `DiagAccumulator.update`
+	replay the run (two-pass Lanczos) and add g_t W_t into an output panel as the vectors pass through a short ring: a
+	footprint independent of deg, one more run per action call. None: a quadrature plan (no action)."""
+
+	def __init__(self, op: DeviceOperator, nprobes: int, deg: int, orth: int = 0, keep_basis: bool = False, basis: Optional[str] = None):
+		basis = _basis_arg(keep_basis, basis)
 		self.op = op
 		n = op.shape[0]
 		self.nprobes = int(nprobes)
 		self.deg = min(int(deg), n)
 		self.orth = self.deg if orth < 0 or orth > self.deg else int(orth)
-		self.keep_basis = bool(keep_basis)
+		self.keep_basis = basis == "keep"
+		self.basis_kind = basis
 		h = C.c_void_p()
-		check(_capi.lib().slq_plan_create(op.ctx._h, op._h, self.nprobes, int(deg), int(orth), int(keep_basis), C.byref(h)))
+		if basis == "recompute":
+			check(_capi.lib().slq_plan_create_recompute(op.ctx._h, op._h, self.nprobes, int(deg), int(orth), C.byref(h)))
+		else:
+			check(_capi.lib().slq_plan_create(op.ctx._h, op._h, self.nprobes, int(deg), int(orth), int(self.keep_basis), C.byref(h)))
 		self._h = h
+
+	@property
+	def basis_mode(self) -> int:
+		"""0 ring only, 1 kept basis, 2 recompute (slq_plan_basis_mode)."""
+		return self.basis_info()["mode"]
+
+	def basis_info(self) -> dict:
+		"""{mode, ring_slots, acc_cols}: acc_cols = ring columns one accumulation launch of a recompute plan consumes."""
+		m, s, a = C.c_int(), C.c_int(), C.c_int()
+		check(_capi.lib().slq_plan_basis_mode(self._h, C.byref(m), C.byref(s), C.byref(a)))
+		return {"mode": int(m.value), "ring_slots": int(s.value), "acc_cols": int(a.value)}
 
 	@property
 	def workspace_bytes(self) -> int:
@@ -365,7 +413,8 @@ class LanczosPlan:
 		return (quad, nodes, weights) if return_rule else quad
 
 	def fun_action(self, fun="identity", **fun_kwargs) -> np.ndarray:
-		"""Y[:, i] = f(A) x_i from the retained basis (needs keep_basis); built-in `fun` names only."""
+		"""Y[:, i] = f(A) x_i from the retained basis (basis="keep") or by replaying the run (basis="recompute": every call
+		costs one more run); built-in `fun` names only."""
 		fid, params = fun_spec(fun, **fun_kwargs)
 		assert fid is not None, "fun_action evaluates built-in function names on the device"
 		Y = np.zeros((self.op.shape[0], self.nprobes), dtype=self.op.dtype, order="F")
@@ -379,6 +428,8 @@ class LanczosPlan:
 		check(_capi.lib().slq_plan_fun_action_dmat(self._h, fid, ptr(params), out._h, int(o0)))
 
 	def basis(self, probe: int = 0) -> np.ndarray:
+		if getattr(self, "basis_kind", None) == "recompute":
+			raise ValueError("a recompute plan holds no basis: create the plan with basis='keep'")
 		Q = np.zeros((self.op.shape[0], self.deg), dtype=self.op.dtype, order="F")
 		check(_capi.lib().slq_plan_get_basis(self._h, int(probe), ptr(Q), Q.shape[0]))
 		return Q
@@ -396,6 +447,13 @@ class LanczosPlan:
 		sweep skips a column whose projection is below the reference's threshold for every probe of the panel (slq_plan_sweep_columns)."""
 		a, b = C.c_uint64(), C.c_uint64()
 		check(_capi.lib().slq_plan_sweep_columns(self._h, C.byref(a), C.byref(b), int(reset)))
+		return int(a.value), int(b.value)
+
+	def action_columns(self, reset: bool = True) -> tuple:
+		"""(read, offered): ring columns the accumulation launches of a recompute plan's replays read against the ones they were offered, summed
+		over launches and panels - a column whose coefficient is zero for every probe of a panel is skipped (slq_plan_action_columns)."""
+		a, b = C.c_uint64(), C.c_uint64()
+		check(_capi.lib().slq_plan_action_columns(self._h, C.byref(a), C.byref(b), int(reset)))
 		return int(a.value), int(b.value)
 
 	def close(self):
@@ -570,9 +628,15 @@ def quad_batch(
 	return (quad, nodes, weights) if return_rule else quad
 
 
-def fun_action_batch(op: DeviceOperator, X: np.ndarray, deg: int, orth: int = 0, fun="identity", rtol: float = 1e-8, **fun_kwargs) -> np.ndarray:
-	"""Y = f(A) X for all columns of X in one call (C-ABI slq_fAv_batch): the batched form of
-	`MatrixFunction._matvec` (src/primate/operators.py:102-124)."""
+def fun_action_batch(op: DeviceOperator, X: np.ndarray, deg: int, orth: int = 0, fun="identity", rtol: float = 1e-8, basis: str = "keep",
+					 return_basis: bool = False, **fun_kwargs) -> np.ndarray:  # fmt: skip
+	"""Y = f(A) X for all columns of X in one call (C-ABI slq_fAv_batch_mode): the batched form of
+	`MatrixFunction._matvec` (src/primate/operators.py:102-124). basis: "keep" (the full basis of every column, batches sized
+	to the free memory), "recompute" (two-pass plans: a footprint independent of deg, twice the runs) or "auto" (the kept
+	basis when all columns fit at once, else recompute). With return_basis also the kind taken."""
+	basis = _basis_arg(False, basis, auto=True)
+	if basis is None:
+		raise ValueError("basis must be 'keep', 'recompute' or 'auto'")
 	fid, params = fun_spec(fun, **fun_kwargs)
 	assert fid is not None, "fun_action_batch takes built-in function names"
 	X = np.asarray(X)
@@ -581,11 +645,13 @@ def fun_action_batch(op: DeviceOperator, X: np.ndarray, deg: int, orth: int = 0,
 	if X.shape[0] != n:
 		raise ValueError(f"X has {X.shape[0]} rows, the operator has {n}")
 	Y = np.zeros((n, X.shape[1]), dtype=op.dtype, order="F")
-	rc = _capi.lib().slq_fAv_batch(op.ctx._h, op._h, ptr(X), n, X.shape[1], int(deg), float(rtol), int(orth), fid, ptr(params), ptr(Y), n)
+	used = C.c_int(0)
+	rc = _capi.lib().slq_fAv_batch_mode(op.ctx._h, op._h, ptr(X), n, X.shape[1], int(deg), float(rtol), int(orth), fid, ptr(params),
+										{"auto": 0, "keep": 1, "recompute": 2}[basis], ptr(Y), n, C.byref(used))  # fmt: skip
 	if rc == _capi.SLQ_ECALLBACK and getattr(op, "error", None) is not None:
 		raise op.error
 	check(rc)
-	return Y
+	return (Y, {1: "keep", 2: "recompute"}[used.value]) if return_basis else Y
 
 
 def quadrature_batch(d: np.ndarray, e: np.ndarray, fun=None, ctx: Optional[Context] = None, **fun_kwargs):

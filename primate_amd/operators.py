@@ -68,15 +68,28 @@ class MatrixFunction(LinearOperator):
 	function names only. `_matvec` (f(A) v), `diag`, `xtrace`, `hutchpp` and `spectral_density` keep the fixed `deg`, and
 	the `distributed` entries refuse an adaptive MatrixFunction: a degree chosen per rank would make the result depend on
 	the sharding.
+
+	`basis` (extra, default "keep": nothing changes): what the f(A)v action - `_matvec` / `_matmat`, and through them `diag`,
+	`xdiag`, `xtrace`, `hutchpp` - runs on. "keep" retains the deg + 1 Lanczos panels; "recompute" is two-pass Lanczos
+	(engine.LanczosPlan): a footprint independent of deg for one more run per action; "auto" takes the kept basis when its
+	plan for the requested column count fits the free device memory (its bytes + 1 GiB) and recompute otherwise.
+	`M.basis_used` records what the last action ran on. A Python callable `fun` needs the basis on the host: "keep" (and
+	"auto", which then means "keep") only.
 	"""
 
 	def __init__(
 		self, A, fun: Union[str, Callable, None] = None, deg: int = 20, orth: int = 3, dtype: np.dtype = F64,
 		stale_ring: bool = False, deg_max: Optional[int] = None, deg_rtol: Optional[float] = None, deg_step: Optional[int] = None,
-		endpoint: Optional[float] = None, **kwargs,
+		endpoint: Optional[float] = None, basis: str = "keep", **kwargs,
 	) -> None:  # fmt: skip
 		assert is_linear_op(A), "Invalid operator `A`; must be dim=2 symmetric operator with defined matvec"
 		assert deg >= 2, "Degree must be >= 2"
+		self._basis = engine._basis_arg(False, basis, auto=True)
+		if self._basis is None:
+			raise ValueError("basis must be 'keep', 'recompute' or 'auto'")
+		if self._basis == "recompute" and fun is not None and not isinstance(fun, str):
+			raise ValueError("a callable `fun` combines the Lanczos basis on the host: basis='recompute' takes built-in function names")
+		self.basis_used = None
 		self._adaptive = None
 		self.deg_used, self.quad_bounds, self.deg_history = None, None, None
 		if deg_max is not None:
@@ -134,14 +147,34 @@ class MatrixFunction(LinearOperator):
 	def _adjoint(self):
 		return self
 
+	def _action_basis(self, nprobes: int) -> str:
+		"""The plan kind an action over `nprobes` columns runs on: the mode given, "auto" resolved by the memory rule of
+		slq_fAv_batch_mode (a callable `fun` needs the basis on the host: "keep")."""
+		basis = getattr(self, "_basis", "keep")
+		if basis != "auto":
+			return basis
+		if self._builtin is None:
+			return "keep"
+		for k, plan in self._plans.items():  # (a plan this size already exists: it fits)
+			if k[0] == nprobes and k[1] in ("keep", "recompute") and not k[2]:
+				return k[1]
+		for k in [k for k in self._plans if k[1] in ("keep", "recompute")]:  # (their memory is free for the choice)
+			self._plans.pop(k).close()
+		need = engine.plan_query_bytes(self.dtype, self.shape[0], nprobes, self._deg, self._orth, "keep")
+		free, _ = self._op.ctx.meminfo()
+		return "keep" if need + (1 << 30) <= free else "recompute"
+
 	def _plan(self, nprobes: int, keep_basis: bool, adaptive: bool = False) -> engine.LanczosPlan:
-		key = (nprobes, keep_basis, adaptive)
+		kind = self._action_basis(nprobes) if keep_basis else False
+		key = (nprobes, kind, adaptive)
+		if keep_basis:
+			self.basis_used = kind
 		if key not in self._plans:
 			## one cached plan per shape class; older ones are released to bound device memory
-			for k in [k for k in self._plans if k[1:] == key[1:]]:
+			for k in [k for k in self._plans if bool(k[1]) == bool(kind) and k[2] == adaptive]:
 				self._plans.pop(k).close()
 			deg = self._adaptive["deg_max"] if adaptive else self._deg
-			self._plans[key] = engine.LanczosPlan(self._op, nprobes, deg, self._orth_given if adaptive else self._orth, keep_basis=keep_basis)
+			self._plans[key] = engine.LanczosPlan(self._op, nprobes, deg, self._orth_given if adaptive else self._orth, basis=kind or None)
 		return self._plans[key]
 
 	def _quad_adaptive(self, X, nprobes: int) -> np.ndarray:
@@ -223,6 +256,8 @@ class MatrixFunction(LinearOperator):
 		if self._builtin is not None:
 			name, kw = self._builtin
 			return plan.fun_action(name, **kw)
+		if plan.basis_kind != "keep":
+			raise ValueError("a callable `fun` combines the Lanczos basis on the host: it needs basis='keep'")
 		## Python callable: it can only be evaluated on the host, so the k x k eigenvectors of every probe's T come
 		## back from the device eigensolver (one batched call) and the basis combination is done per probe
 		a, b, _ = plan.tridiag()
