@@ -366,6 +366,22 @@ int slq_plan_profile_enable(slq_plan *plan, int enable);
  * reference skips a projection per probe below its threshold, src/primate/include/lanczos.h:62 -: columns read / columns offered, summed over launches and panels
  * since the last reset. Synchronises. */
 int slq_plan_sweep_columns(slq_plan *plan, uint64_t *read, uint64_t *offered, int reset);
+/* The oldest column of a full three-column window (ring-fed Gram sequence, orth = 3) is read by the update pass only where its zero projection is not
+ * certified from the inner products the step already has (SLQ_OMEGA: 1 on, 0 every column read, 2 verify: every column read and the certificate checked
+ * against the measurement). out: columns offered, columns read, rescues (the missing entry measured by a dot of its own), verify-mode violations,
+ * read -> skip transitions; summed over steps and panels since the last reset; zeros for a plan that offers nothing. Synchronises. */
+int slq_plan_window_columns(slq_plan *plan, int64_t out[5], int reset);
+/* ... the plan's mode (0 where nothing is offered) and, from verify runs since the last reset of those counters: out[0] the largest one-step innovation
+ * |measured - predicted| in units of eps ||A||_inf, out[1] the smallest (tol - |measured|) / rho (inf: none seen), out[2], out[3] the constants c and kappa
+ * of the certificate, out[4] ||A||_inf. mode or out may be NULL. */
+int slq_plan_window_verify(slq_plan *plan, int *mode, double out[5]);
+/* Census of the last run of a ring-fed Gram plan created under SLQ_OMEGA=2: out[(j * 9 + i) * panels + panel] = probes of the panel with a non-zero
+ * projection coefficient at window position i of step j; len must be (deg + 1) * 9 * panels. */
+int slq_plan_window_census(slq_plan *plan, int32_t *out, int64_t len);
+/* The per-step flags of the last run: read[j * panels + panel] = 1 where the panel's update pass of step j read the oldest column, rescue[...] = 1 where its
+ * entry was measured by the rescue kernels; len must be (deg + 1) * panels. (slq_plan_window_verify, _census and _flags are diagnostic entries: the tests' and
+ * the verify mode's view of the recurrence, not part of what a driver needs.) */
+int slq_plan_window_flags(slq_plan *plan, int32_t *read, int32_t *rescue, int64_t len);
 int slq_plan_profile_read(slq_plan *plan, slq_profile *out, int reset);
 
 /* Failure reporting of the ring-fed tile pass (k_csr_ring_pass). Every wait inside that kernel is bounded; a workgroup

@@ -111,6 +111,10 @@ _SIGNATURES = {
 	"slq_plan_profile_enable": (C.c_int, [_P, C.c_int]),
 	"slq_plan_action_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
 	"slq_plan_sweep_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
+	"slq_plan_window_columns": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int]),
+	"slq_plan_window_verify": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+	"slq_plan_window_census": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int64]),
+	"slq_plan_window_flags": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]),
 	"slq_plan_profile_read": (C.c_int, [_P, C.POINTER(SlqProfile), C.c_int]),
 	"slq_quad_batch": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _P, _P, _P, _P]),
 	"slq_eigh_tridiag_batch": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),

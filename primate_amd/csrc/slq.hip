@@ -141,6 +141,7 @@ struct slq_operator {
   double rms_dist = -1.0;  // rms |i - j| over the stored nonzeros inside an XCD chunk (-1: unknown)
   int64_t nnz_u = 0;       // entries of the upper-triangle copy
   double far_per_row = 0.0;  // stored nonzeros per row with |i - j| > 4096 (0 when unknown: device-resident CSR)
+  double norm_inf = -1.0;    // largest absolute row sum of a CSR operator (-1: not taken yet; operator_norm_inf takes it once, on the device)
   // OP_GRAM (x -> A^T (A x), A is mrows x n): rowptr/colind/vals hold A, the *_t arrays its transpose (n rows)
   int64_t mrows = 0;
   int32_t *rowptr_t = nullptr, *colind_t = nullptr;
@@ -175,9 +176,12 @@ struct Switches {
   int fused_pad;   // SLQ_FUSED_LDS_PAD (-1: by row loop)
   int spmm_pad;    // SLQ_SPMM_LDS_PAD
   int defer_axpy;  // SLQ_DEFER_AXPY the block-CGS sweeps apply `w -= cB W_c` in the update sweep: the dots sweeps are read-only (r04; 0: first chunk stores)
+  int omega;       // SLQ_OMEGA     the oldest column of a full 3-column window is read only where its zero projection is not certified:
+                   //               1 on, 0 every column read (the sequence as it was), 2 verify (every column read, the certificate checked beside it)
+  int omega_trip, omega_rescue;  // SLQ_OMEGA_TRIP / SLQ_OMEGA_RESCUE (tests): the step at which every panel reads / takes the rescue (-1: none)
   unsigned key() const {
     unsigned k = 0;
-    for (int v : {fused, nt, graph, mgs, stored_u, merged, cross, tiles, ring_alpha, ring_rev, dense_mfma, dense_tile16, dense_lds, pipe, fused_pad, spmm_pad, defer_axpy})
+    for (int v : {fused, nt, graph, mgs, stored_u, merged, cross, tiles, ring_alpha, ring_rev, dense_mfma, dense_tile16, dense_lds, pipe, fused_pad, spmm_pad, defer_axpy, omega, omega_trip, omega_rescue})
       k = k * 1000003u + (unsigned)(v + 7);
     return k;
   }
@@ -255,6 +259,13 @@ struct slq_plan {
   bool launch_error = false;  // a launcher declined (mis-dispatch): the run is invalid (enqueue_run)
   bool sweep_skip = true;     // the update sweep does not read ring columns whose coefficient is zero for every probe of the panel (SLQ_SWEEP_SKIP=0: reads them all)
   unsigned long long *sweep_cols_d = nullptr;  // {ring columns the update sweeps read, columns they were offered}, summed over launches and panels (slq_plan_sweep_columns)
+  // the edge recurrence: state of the offered steps - D, rho, g3, Dm [bpad] each | read, rescue [deg + 1][NP] | counters
+  bool omega_on = false;      // the plan offers its full-window steps (ring-fed Gram sequence, orth == 3, SLQ_OMEGA != 0)
+  double *om_buf = nullptr;
+  int *om_flags = nullptr;
+  unsigned long long *om_cnt = nullptr;
+  int *om_census = nullptr;   // SLQ_OMEGA=2, any ring-fed Gram plan: non-zero gammas per step, window position and panel (slq_plan_window_census)
+  double om_norm = 0.0;       // ||A||_inf of the operator when the plan was created
   bool last_nostore = true;   // the update pass of a run's last step does not store W_deg (plans without a kept basis; SLQ_LAST_STORE=1 stores)
   // two-pass f(A)v (slq_plan_create_recompute). basis_mode: 0 ring only, 1 kept basis, 2 recompute - the ring
   // has acc_cols + 1 slots at least, and two panels lie behind it: slot v_slot the stash of the probes, slot y_slot the output
@@ -275,6 +286,10 @@ struct slq_plan {
 // loader waves (k_csr_ring_pass). Read when an operator is created (the rows are regrouped into the tiles) and when a plan
 // is created (whether its passes use them).
 constexpr int kTilesDefault = 2;
+// the edge recurrence's certificate: a step adds kOmegaC eps_F ||A||_inf to the noise radius (8x the largest
+// one-step innovation the verify mode has seen on the device, and not less than 1); a zero is certified below orth_tol / kOmegaKappa
+constexpr double kOmegaC = 3.5;
+constexpr double kOmegaKappa = 4.0;
 constexpr double kTileMaxColsPerRow = 4.5;      // tiles are kept when a tile row needs at most this many distinct panel rows
 constexpr double kTileAlphaColsPerRow = 2.6;    // upper-triangle tiles: the alpha-only pass takes the ring up to this many landed rows per row (r03: 7-point grids too)
 constexpr double kTileAlphaMergedColsPerRow = 2.6;  // ... and on the merged tiles of narrow panels up to this many (of the unmerged tiles)
@@ -2399,6 +2414,42 @@ static int ring_slots(int deg, int orth, int keep_basis) {
 static int recompute_acc_cols(int deg) { return std::min(kAccCols, deg); }
 static int recompute_ring_slots(int deg, int orth) { return std::max(ring_slots(deg, orth, 0), recompute_acc_cols(deg) + 1); }
 
+// ||A||_inf of a CSR operator: the scale of one Lanczos step's rounding (what the edge recurrence adds to its noise radius per
+// step). Taken once per operator, on the device, the first time a plan asks; affine operators change their values.
+namespace slq {
+template <typename F> __global__ void k_norm_inf(int n, const int32_t *__restrict__ rowptr, const F *__restrict__ vals, unsigned long long *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double s = 0.0;
+  for (int32_t q = rowptr[i]; q < rowptr[i + 1]; ++q) s += fabs((double)vals[q]);
+  atomicMax(out, (unsigned long long)__double_as_longlong(s));  // (bits of non-negative doubles order as integers)
+}
+}  // namespace slq
+static int operator_norm_inf(slq_operator *op, double *out) {
+  if (op->kind != OP_CSR || op->vals_b != nullptr) return fail(SLQ_EINVAL, "no fixed CSR values to take ||A||_inf of");
+  if (op->norm_inf < 0.0) {
+    unsigned long long *d = nullptr, h = 0;
+    hipStream_t st = op->ctx->stream;
+    HIP_TRY(hipMalloc((void **)&d, 8));
+    hipError_t e = hipMemsetAsync(d, 0, 8, st);
+    if (e == hipSuccess) {
+      const dim3 grid((unsigned)((op->n + 255) / 256));
+      if (op->dtype == SLQ_F64) k_norm_inf<double><<<grid, 256, 0, st>>>((int)op->n, op->rowptr, (const double *)op->vals, d);
+      else k_norm_inf<float><<<grid, 256, 0, st>>>((int)op->n, op->rowptr, (const float *)op->vals, d);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    hipFree(d);
+    if (e != hipSuccess) return fail(SLQ_EHIP, "||A||_inf: %s", hipGetErrorString(e));
+    double v;
+    memcpy(&v, &h, 8);
+    op->norm_inf = v;
+  }
+  *out = op->norm_inf;
+  return SLQ_OK;
+}
+
 static void grid_sizes(int n, int LPR, int NP, int num_cus, int *nblkA, int *nblkS, int *nblkU, bool pipelined) {
   const int RPW = 64 / LPR;
   const int rows_per_block = kWaves * RPW;
@@ -2499,6 +2550,10 @@ extern "C" int slq_plan_destroy(slq_plan *p) {
   if (p->scal) hipFree(p->scal);
   if (p->part) hipFree(p->part);
   if (p->sweep_cols_d) hipFree(p->sweep_cols_d);
+  if (p->om_buf) hipFree(p->om_buf);
+  if (p->om_flags) hipFree(p->om_flags);
+  if (p->om_cnt) hipFree(p->om_cnt);
+  if (p->om_census) hipFree(p->om_census);
   if (p->quad_d) hipFree(p->quad_d);
   if (p->st.active) hipFree(p->st.active);
   ctx_release(p->ctx);
@@ -2551,7 +2606,8 @@ static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int
   p->sw = Switches{env_int("SLQ_FUSED", 1), env_int("SLQ_NT", 1) != 0, env_int("SLQ_GRAPH", 1) != 0, env_int("SLQ_MGS", 0) != 0,
                    env_int("SLQ_STORED_U", 1) != 0, env_int("SLQ_MERGED", 1) != 0, env_int("SLQ_CROSS", 1) != 0,
                    tiles_mode() != 0, env_int("SLQ_RING_ALPHA", 2), env_int("SLQ_RING_REV", 1) != 0, env_int("SLQ_DENSE_MFMA", 1) != 0, env_int("SLQ_DENSE_TILE16", 0) != 0, env_int("SLQ_DENSE_LDS", 1) != 0, env_int("SLQ_PIPE", -1),
-                   env_int("SLQ_FUSED_LDS_PAD", -1), env_int("SLQ_SPMM_LDS_PAD", 57344), env_int("SLQ_DEFER_AXPY", 1) != 0};
+                   env_int("SLQ_FUSED_LDS_PAD", -1), env_int("SLQ_SPMM_LDS_PAD", 57344), env_int("SLQ_DEFER_AXPY", 1) != 0,
+                   std::max(0, std::min(2, env_int("SLQ_OMEGA", 1))), env_int("SLQ_OMEGA_TRIP", -1), env_int("SLQ_OMEGA_RESCUE", -1)};
   choose_geometry(op->dtype, nprobes, &p->LPR, &p->PW, &p->NP);
   p->bpad = p->NP * p->PW;
   p->basis_mode = basis_mode;
@@ -2664,6 +2720,20 @@ static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int
   if (e == hipSuccess && ncoef) e = hipMalloc((void **)&p->acc_coef, ncoef * 8);
   if (e == hipSuccess) e = hipMalloc((void **)&p->sweep_cols_d, 4 * sizeof(unsigned long long));  // (words 2, 3: the accumulation launches of a recompute plan, slq_plan_action_columns)
   if (e == hipSuccess) e = hipMemset(p->sweep_cols_d, 0, 4 * sizeof(unsigned long long));
+  // the edge recurrence: full windows of three columns on the ring-fed Gram sequence (r = 4 .. 8: not offered; the rescue needs the
+  // column that leaves the window still in the ring: orth + 1 slots at least)
+  // (k_fin_gram_rescue's early exit looks at the first and the last panel under a block of 64 columns: panels of 32 columns at least)
+  p->omega_on = p->gram && p->sw.omega != 0 && orth == 3 && p->S >= 4 && op->vals_b == nullptr && p->PW >= 32;
+  const size_t om_flag_words = (size_t)2 * (deg + 1) * p->NP;
+  if (e == hipSuccess && p->omega_on) e = hipMalloc((void **)&p->om_buf, 4 * bp * 8);
+  if (e == hipSuccess && p->omega_on) e = hipMalloc((void **)&p->om_flags, om_flag_words * sizeof(int));
+  if (e == hipSuccess && p->omega_on) e = hipMalloc((void **)&p->om_cnt, 8 * sizeof(unsigned long long));
+  if (e == hipSuccess && p->omega_on) e = hipMemset(p->om_buf, 0, 4 * bp * 8);
+  if (e == hipSuccess && p->omega_on) e = hipMemset(p->om_flags, 0, om_flag_words * sizeof(int));
+  if (e == hipSuccess && p->omega_on) e = hipMemset(p->om_cnt, 0, 8 * sizeof(unsigned long long));
+  const size_t census_words = (size_t)(deg + 1) * (kFusedMaxR + 1) * p->NP;
+  if (e == hipSuccess && p->gram && p->sw.omega == 2) e = hipMalloc((void **)&p->om_census, census_words * sizeof(int));
+  if (e == hipSuccess && p->om_census) e = hipMemset(p->om_census, 0, census_words * sizeof(int));
   if (e == hipSuccess) e = hipMalloc((void **)&p->st.active, bp * 2 * sizeof(int) + 16);
   if (e == hipSuccess) e = hipMalloc((void **)&p->quad_d, (bp + 2 * bp * (size_t)deg) * 8);
   // dense fp64 operator on the matrix cores with 32-row tiles: n/32 workgroups per panel rarely fill 256 CUs, so K is
@@ -2723,6 +2793,13 @@ static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int
   }
   {
     const int rc = set_kernel_attributes(p);
+    if (rc != SLQ_OK) {
+      slq_plan_destroy(p);
+      return rc;
+    }
+  }
+  if (p->omega_on) {
+    const int rc = operator_norm_inf(op, &p->om_norm);
     if (rc != SLQ_OK) {
       slq_plan_destroy(p);
       return rc;
@@ -2968,6 +3045,71 @@ extern "C" int slq_plan_sweep_columns(slq_plan *p, uint64_t *read, uint64_t *off
   HIP_TRY(hipStreamSynchronize(p->ctx->stream));
   if (read) *read = h[0];
   if (offered) *offered = h[1];
+  return SLQ_OK;
+}
+
+// The edge recurrence's accounting, summed over steps and panels since the last reset: oldest window columns
+// offered, read, rescues (the entry measured after all by a dot of its own), verify-mode violations, read -> skip transitions.
+// A plan that offers nothing reports zeros. Synchronises.
+extern "C" int slq_plan_window_columns(slq_plan *p, int64_t out[5], int reset) {
+  if (!p || !out) return fail(SLQ_EINVAL, "plan/out is NULL");
+  for (int k = 0; k < 5; ++k) out[k] = 0;
+  if (!p->omega_on) return SLQ_OK;
+  HIP_TRY(hipSetDevice(p->ctx->device));
+  unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(h, p->om_cnt, sizeof(h), hipMemcpyDeviceToHost, p->ctx->stream));
+  if (reset) HIP_TRY(hipMemsetAsync(p->om_cnt, 0, sizeof(h), p->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+  for (int k = 0; k < 5; ++k) out[k] = (int64_t)h[k];
+  return SLQ_OK;
+}
+
+// The flags of the last run (diagnostics, tests): read[j * panels + panel] / rescue[...] = 1 where the panel's update pass of step j read the window's
+// oldest column / where its entry was measured by the rescue kernels; rows of steps that were not offered are zero. len = (deg + 1) * panels.
+extern "C" int slq_plan_window_flags(slq_plan *p, int32_t *read, int32_t *rescue, int64_t len) {
+  if (!p || !read || !rescue) return fail(SLQ_EINVAL, "plan/read/rescue is NULL");
+  const int64_t words = (int64_t)(p->deg + 1) * p->NP;
+  if (len != words) return fail(SLQ_EINVAL, "flag buffers: %lld words expected", (long long)words);
+  memset(read, 0, (size_t)words * sizeof(int32_t));
+  memset(rescue, 0, (size_t)words * sizeof(int32_t));
+  if (!p->omega_on) return SLQ_OK;
+  HIP_TRY(hipSetDevice(p->ctx->device));
+  HIP_TRY(hipMemcpyAsync(read, p->om_flags, (size_t)words * sizeof(int), hipMemcpyDeviceToHost, p->ctx->stream));
+  HIP_TRY(hipMemcpyAsync(rescue, p->om_flags + words, (size_t)words * sizeof(int), hipMemcpyDeviceToHost, p->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+  return SLQ_OK;
+}
+
+// Verify-mode census of the last run (any ring-fed Gram plan created under SLQ_OMEGA=2): out[(j * 9 + i) * panels + panel] = probes of the
+// panel with a non-zero gamma at window position i of step j; len = (deg + 1) * 9 * panels words. Synchronises.
+extern "C" int slq_plan_window_census(slq_plan *p, int32_t *out, int64_t len) {
+  if (!p || !out) return fail(SLQ_EINVAL, "plan/out is NULL");
+  const int64_t words = (int64_t)(p->deg + 1) * (kFusedMaxR + 1) * p->NP;
+  if (!p->om_census) return fail(SLQ_EINVAL, "the plan keeps no census (ring-fed Gram sequence created under SLQ_OMEGA=2)");
+  if (len != words) return fail(SLQ_EINVAL, "census buffer: %lld words expected", (long long)words);
+  HIP_TRY(hipSetDevice(p->ctx->device));
+  HIP_TRY(hipMemcpyAsync(out, p->om_census, (size_t)words * sizeof(int), hipMemcpyDeviceToHost, p->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+  return SLQ_OK;
+}
+
+// ... its mode (0: nothing offered, 1: on, 2: verify) and, from verify runs since the last reset of the counters: out[0] the largest
+// one-step innovation |measured - predicted| in units of eps_F ||A||_inf, out[1] the smallest (tol - |measured|) / rho (inf: none seen),
+// out[2] the c and out[3] the kappa in use, out[4] ||A||_inf.
+extern "C" int slq_plan_window_verify(slq_plan *p, int *mode, double out[5]) {
+  if (!p) return fail(SLQ_EINVAL, "plan is NULL");
+  if (mode) *mode = p->omega_on ? p->sw.omega : 0;
+  if (!out) return SLQ_OK;
+  out[0] = 0.0, out[1] = std::numeric_limits<double>::infinity(), out[2] = kOmegaC, out[3] = kOmegaKappa, out[4] = p->om_norm;
+  if (!p->omega_on) return SLQ_OK;
+  HIP_TRY(hipSetDevice(p->ctx->device));
+  unsigned long long h[8];
+  HIP_TRY(hipMemcpyAsync(h, p->om_cnt, sizeof(h), hipMemcpyDeviceToHost, p->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+  double inv;
+  memcpy(&out[0], &h[kOmCntInnov], 8);
+  memcpy(&inv, &h[kOmCntMargin], 8);
+  if (inv > 0.0) out[1] = 1.0 / inv;
   return SLQ_OK;
 }
 
@@ -3388,7 +3530,7 @@ static unsigned long long *debug_times_buffer() { return nullptr; }
 #endif
 
 // one ring-fed pass through k_ring_pass (slq_ring.hpp: any panel width, up to 8 ring columns; nontemporal streams)
-static int launch_ring_gen(slq_plan *p, int pass, int rc, dim3 grid, hipStream_t st, int j, int xt) {
+static int launch_ring_gen(slq_plan *p, int pass, int rc, dim3 grid, hipStream_t st, int j, int xt, const int *wread = nullptr) {
   const bool upper = pass == PASS_ALPHA && p->rs_desc_u != nullptr && p->sw.ring_alpha == 2;
   RingArgs a;
   a.pass = pass;
@@ -3413,6 +3555,7 @@ static int launch_ring_gen(slq_plan *p, int pass, int rc, dim3 grid, hipStream_t
   const bool last_nostore = (pass == PASS_UPDATE || pass == PASS_UPDATEG) && j == p->deg - 1 && !p->keep_basis && p->last_nostore;
   a.xt = xt | (((pass == PASS_UPDATE || pass == PASS_UPDATEG) && p->sw.ring_rev) ? 4 : 0) | ((upper && p->rs_u_padded) ? 8 : 0) | (last_nostore ? 16 : 0);  // bit 3: padded rows
   a.fail = p->ring_fail_d;
+  a.wread = wread;
   a.dbg = pass == env_int("SLQ_DEBUG_PASS", PASS_ADOTS) ? debug_times_buffer() : nullptr;  // (diagnostic builds: the pass whose time line is stamped)
   const bool d = p->dtype == SLQ_F64;
   int rc_l = -1;
@@ -3441,7 +3584,14 @@ static int enqueue_run(slq_plan *p, double rtol, int fused_mode, bool nt, int j0
     HIP_TRY(hipMemsetAsync(p->st.alpha, 0, (size_t)(deg + 1) * bp * 8, st));
     HIP_TRY(hipMemsetAsync(p->st.nu + bp, 0, (size_t)deg * bp * 8, st));
     HIP_TRY(hipMemsetAsync(p->st.gram, 0, (size_t)2 * (kFusedMaxR + 1) * bp * 8, st));  // (the Gram rows of a previous run are never read - index guards - but need not be trusted to be)
+    if (p->omega_on) {  // the edge recurrence starts with the run (its counters are the caller's to reset: slq_plan_window_columns)
+      HIP_TRY(hipMemsetAsync(p->om_buf, 0, (size_t)4 * bp * 8, st));
+      HIP_TRY(hipMemsetAsync(p->om_flags, 0, (size_t)2 * (deg + 1) * p->NP * sizeof(int), st));
+    }
   }
+  if (j0 == 0 && p->om_census) HIP_TRY(hipMemsetAsync(p->om_census, 0, (size_t)(deg + 1) * (kFusedMaxR + 1) * p->NP * sizeof(int), st));
+  OmegaState om_off;
+  memset(&om_off, 0, sizeof(om_off));
   const dim3 gA(p->nblkA, p->NP), gS(p->nblkS, p->NP), gU(p->nblkU, p->NP), gF((bp + 63) / 64);
   const dim3 gAf(p->nblkF, p->NP);
   const dim3 gT(p->nblkT, p->NP);
@@ -3534,11 +3684,35 @@ static int enqueue_run(slq_plan *p, double rtol, int fused_mode, bool nt, int j0
       if (gram) {
         const int xa = j > 0 ? 1 : 0;  // (alpha_j's -beta q_j.q_{j-1} part is a Gram entry: the pass leaves W_p unread)
         PROFILED(p, SLQ_K_SPMM, { if (nt) CSR_PASS(PASS_ALPHA, 1, 1, 0, 0, ldsA, xa); else CSR_PASS(PASS_ALPHA, 0, 0, 0, 0, ldsA, xa); });
+        // a full window of three columns is offered to the edge recurrence (slq_kernels.hpp: OmegaState): its oldest column is read only
+        // where the panel's flag says so. The launch sequence does not depend on the flags: the two rescue kernels are always there.
+        OmegaState om = om_off;
+        om.census = p->om_census, om.PW = p->PW, om.NP = p->NP;
+        if (p->omega_on && r == 3 && p->orth == 3) {
+          om.mode = p->sw.omega;
+          om.est_prev = j >= 3 ? 1 : 0;  // (step 2 is the first with a full window)
+          om.force = (j == p->sw.omega_trip ? 1 : 0) | (j == p->sw.omega_rescue ? 2 : 0);
+          om.PW = p->PW, om.NP = p->NP;
+          om.D = p->om_buf, om.rho = p->om_buf + bp, om.g3 = p->om_buf + 2 * (size_t)bp, om.Dm = p->om_buf + 3 * (size_t)bp;
+          om.read = p->om_flags, om.rescue = p->om_flags + (size_t)(deg + 1) * p->NP;
+          om.cnt = p->om_cnt;
+          om.eps_norm = eps * p->om_norm;
+          om.theta = kOmegaC * om.eps_norm;
+          om.tol_k = orth_tol / kOmegaKappa;
+        }
+        const int nblk_a = alpha_tiled ? p->nblkT : p->nblkF;
         PROFILED(p, SLQ_K_FINALIZE,
-                 hipLaunchKernelGGL(k_fin_gram, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, st, p->st, p->part, alpha_tiled ? p->nblkT : p->nblkF, j, r, orth_tol));
-        PROFILED(p, SLQ_K_REORTH_UPD, SLQ_TRY(launch_ring_gen(p, PASS_UPDATEG, r, gT, st, j, 0)));
+                 hipLaunchKernelGGL(k_fin_gram, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, st, p->st, p->part, nblk_a, j, r, orth_tol, om));
+        if (om.mode == 1 && om.est_prev) {
+          double *part_r = p->part + (size_t)p->part_maxblk * bp;  // (behind the alpha partials, which the second pass does not need but the slab layout keeps)
+          PROFILED(p, SLQ_K_FINALIZE,
+                   DISPATCH(p->dtype, p->LPR, (k_omega_rescue_dot<F, L><<<gS, dim3(kBlock), 0, st>>>(p->n, (const F *)p->ring, p->slot_stride, S, j, r, om.rescue + (size_t)j * p->NP, part_r, bp))));
+          PROFILED(p, SLQ_K_FINALIZE,
+                   hipLaunchKernelGGL(k_fin_gram_rescue, dim3((bp + 63) / 64), dim3(kFinThreads), 0, st, p->st, part_r, p->nblkS, j, r, orth_tol, om));
+        }
+        PROFILED(p, SLQ_K_REORTH_UPD, SLQ_TRY(launch_ring_gen(p, PASS_UPDATEG, r, gT, st, j, 0, om.mode == 1 ? om.read + (size_t)j * p->NP : nullptr)));
         PROFILED(p, SLQ_K_FINALIZE,
-                 hipLaunchKernelGGL(k_fin_beta_gram, dim3((bp + 63) / 64, r + 1), dim3(kFinThreads), 0, st, p->st, p->part, p->nblkT, j, r, residual_tol));
+                 hipLaunchKernelGGL(k_fin_beta_gram, dim3((bp + 63) / 64, r + 1), dim3(kFinThreads), 0, st, p->st, p->part, p->nblkT, j, r, residual_tol, om));
         prev_xt = false;
         continue;
       }
@@ -3547,10 +3721,10 @@ static int enqueue_run(slq_plan *p, double rtol, int fused_mode, bool nt, int j0
         const int xa = j > 0 ? 1 : 0;
         PROFILED(p, SLQ_K_SPMM, { if (nt) CSR_PASS(PASS_ALPHA, 1, 1, 0, 0, ldsA, xa); else CSR_PASS(PASS_ALPHA, 0, 0, 0, 0, ldsA, xa); });
         PROFILED(p, SLQ_K_FINALIZE,
-                 hipLaunchKernelGGL(k_fin_gram, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, st, p->st, p->part, alpha_tiled ? p->nblkT : p->nblkF, j, r, orth_tol));
+                 hipLaunchKernelGGL(k_fin_gram, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, st, p->st, p->part, alpha_tiled ? p->nblkT : p->nblkF, j, r, orth_tol, om_off));
         PROFILED(p, SLQ_K_REORTH_UPD, DISPATCH(p->dtype, p->LPR, (launch_csr_updateg<F, L>(p, r, pipe_on, gU, lds0 + fused_pad, st, j))));
         PROFILED(p, SLQ_K_FINALIZE,
-                 hipLaunchKernelGGL(k_fin_beta_gram, dim3((bp + 63) / 64, r + 1), dim3(kFinThreads), 0, st, p->st, p->part, p->nblkU, j, r, residual_tol));
+                 hipLaunchKernelGGL(k_fin_beta_gram, dim3((bp + 63) / 64, r + 1), dim3(kFinThreads), 0, st, p->st, p->part, p->nblkU, j, r, residual_tol, om_off));
         prev_xt = false;
         continue;
       }

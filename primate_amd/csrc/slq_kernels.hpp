@@ -1817,6 +1817,29 @@ struct StepState {
   int bpad, nprobes, deg;
 };
 
+// The window's oldest column in the Gram sequence ("the edge recurrence"): what k_fin_gram / k_fin_beta_gram
+// keep per probe and per panel to certify gamma_{r-1} = 0 without a measured W_{j+1} . W_{j+1-r}. mode 0: the step is not
+// offered (every entry measured: the kernels compute what they always did); 1: the update pass reads the column only where
+// read[j][panel] is set; 2: verify - the column is read and the measured decisions are applied, the estimate runs beside them.
+struct OmegaState {
+  int mode;
+  int est_prev;    // step j - 1 was offered: read[j - 1] says whether Gram entry r of row j is an estimate
+  int force;       // bit 0: every panel reads at this step (SLQ_OMEGA_TRIP), bit 1: every panel takes the rescue (SLQ_OMEGA_RESCUE)
+  int PW, NP;
+  double *D;       // [bpad] W_{j+1} . W_t if step j applies no projection (the numerator d - cb g0 of the edge projection)
+  double *rho;     // [bpad] noise radius of D / nu_t (the scaling of sproj)
+  double *g3;      // [bpad] verify: the entry mode 1 would hold (estimate or measurement)
+  double *Dm;      // [bpad] verify: D from measured entries only (the one-step prediction)
+  int *read;       // [deg + 1][NP]
+  int *rescue;     // [deg + 1][NP]
+  int *census;     // null, or [deg + 1][kFusedMaxR + 1][NP]: probes with a non-zero gamma per step, window position and panel (SLQ_OMEGA=2, any Gram plan)
+  unsigned long long *cnt;  // offered, read, rescues, violations, read->skip transitions, max innovation (bits of a double, in eps ||A||_inf), max rho / (tol - |measured|) (bits), spare
+  double theta;    // c eps_F ||A||_inf: what one step adds to rho
+  double tol_k;    // orth_tol / kappa: the certificate's bar
+  double eps_norm; // eps_F ||A||_inf
+};
+constexpr int kOmCntOffered = 0, kOmCntRead = 1, kOmCntRescue = 2, kOmCntViol = 3, kOmCntTrans = 4, kOmCntInnov = 5, kOmCntMargin = 6;
+
 // Sum part[blk][col] over blk in a fixed order. Block = kFinThreads = 64 columns x kFinSlices
 // slices; each thread adds every kFinSlices-th partial (4 independent loads in flight), then the
 // slices are folded through LDS in slice order: bitwise reproducible.
@@ -1958,8 +1981,105 @@ __global__ __launch_bounds__(kFinThreads) void k_fin_adots(StepState st, const d
 // (DESIGN.md §4.6): alpha / beta and the quadrature agree with the oracle exactly as well as before - a window of
 // 2-8 columns behind a three-term step only ever removes rounding-level components, most of them below the
 // reference's own threshold (lanczos.h:53,62).
+// q_t . w of window position i (t = j - i) from the Gram rows, as derived above; *nut_out = nu_t. hi: the entry W_j . W_{t-1}
+// (Gram row j, entry i + 1) - passed in because the edge position may hold an estimate of it beside the measured one.
+__device__ __forceinline__ double gram_sproj(const StepState &st, int j, int i, int col, double cb, double hi, double *nut_out) {
+  constexpr int R1 = kFusedMaxR + 1;
+  const int64_t bp = st.bpad;
+  const double *Gc = st.gram + (int64_t)(j & 1) * R1 * bp + col;        // Gc[q * bp] = W_j . W_{j-q}
+  const double *Gp = st.gram + (int64_t)((j + 1) & 1) * R1 * bp + col;  // Gp[q * bp] = W_{j-1} . W_{j-1-q}
+  const double sc = st.coefA[col], cp = st.coefA[bp + col];
+  const int t = j - i;
+  const double nut = st.nu[(int64_t)t * bp + col];
+  *nut_out = nut;
+  const double g1 = Gc[(int64_t)(i - 1) * bp], g0 = Gc[(int64_t)i * bp];
+  const double alt = st.alpha[(int64_t)t * bp + col];
+  double s = g1 + (alt / nut) * g0;
+  if (t >= 1 && i + 1 <= kFusedMaxR) {
+    const double nutm = st.nu[(int64_t)(t - 1) * bp + col];
+    if (nutm > 0.0) s += (nut / nutm) * hi;  // (zero where the window did not reach W_{t-1}: never in range, see slq.hip)
+  }
+  // W_t . W_{j-1}: t = j - 1 is the squared norm nu_{j-1}^2 itself (W_0's row is never written: take nu everywhere)
+  const double nujm = st.nu[(int64_t)(j - 1) * bp + col];
+  const double wt_wjm = i == 1 ? nujm * nujm : Gp[(int64_t)(i - 1) * bp];
+  const double d = sc * (nut * s) - cp * wt_wjm;
+  return (d - cb * g0) / nut;
+}
+
+__device__ __forceinline__ void om_max_bits(unsigned long long *w, double x) { atomicMax(w, (unsigned long long)__double_as_longlong(x > 0.0 ? x : 0.0)); }
+
+// The edge position i = r - 1 of an offered step (OmegaState): gamma, the kept numerator and its radius, the panel's flags.
+// measured_only: the entry W_j . W_{t-1} in the Gram row is a measurement whatever read[j - 1] says (the rescue's second pass).
+__device__ __forceinline__ double omega_edge(const StepState &st, const OmegaState &om, int j, int i, int col, double cb, double orth_tol, bool measured_only) {
+  constexpr int R1 = kFusedMaxR + 1;
+  const int64_t bp = st.bpad;
+  const int panel = col / om.PW;
+  const int t = j - i;
+  const double ghi = st.gram[((int64_t)(j & 1) * R1 + (i + 1)) * bp + col];
+  const double nut0 = st.nu[(int64_t)t * bp + col];
+  if (!(st.active[col] && nut0 > 0.0)) {
+    om.D[col] = 0.0;
+    om.rho[col] = 0.0;
+    if (om.mode == 2) om.Dm[col] = 0.0;
+    return 0.0;
+  }
+  int *read_j = om.read + (int64_t)j * om.NP + panel, *resc_j = om.rescue + (int64_t)j * om.NP + panel;
+  const bool est_in = !measured_only && om.est_prev && t >= 1 && om.read[(int64_t)(j - 1) * om.NP + panel] == 0;
+  const double sc = st.coefA[col];
+  double nut;
+  const double sproj_m = gram_sproj(st, j, i, col, cb, ghi, &nut);  // (mode 1 with est_in: ghi is the estimate itself)
+  double gm = 0.0;
+  bool need_read = (om.force & 1) != 0;
+  if (om.mode == 1) {
+    const double rho = (est_in ? sc * nut * om.rho[col] : 0.0) + om.theta;
+    const bool cert = fabs(sproj_m) + rho <= om.tol_k;
+    // the next step's radius is about rho + theta: where that would no longer certify, the column is read now (one column read,
+    // gamma = 0 all the same) rather than measured then by a pass of its own
+    const bool soon = fabs(sproj_m) + rho + om.theta > om.tol_k;
+    om.D[col] = sproj_m * nut;
+    om.rho[col] = rho;
+    if (est_in) {
+      // a zero is certified, or the entry is measured after all (k_omega_rescue_dot, k_fin_gram_rescue): never a gamma from an estimate
+      if (!cert) atomicOr(resc_j, 1);
+      else need_read = need_read || soon;
+    } else {
+      if (fabs(sproj_m) > orth_tol) gm = sproj_m / nut;
+      need_read = need_read || gm != 0.0 || soon;
+    }
+    if ((om.force & 2) && t >= 1 && !measured_only) atomicOr(resc_j, 1);
+  } else {
+    // verify: the measured entry decides, exactly as with mode 0; the estimate and its radius run as mode 1 would run them
+    if (fabs(sproj_m) > orth_tol) gm = sproj_m / nut;
+    double rho = om.theta, sproj_e = sproj_m;
+    if (est_in) {
+      double nut2;
+      sproj_e = gram_sproj(st, j, i, col, cb, om.g3[col], &nut2);
+      rho = sc * nut * om.rho[col] + om.theta;
+      const double nutm = st.nu[(int64_t)(t - 1) * bp + col];
+      if (nutm > 0.0) om_max_bits(om.cnt + kOmCntInnov, fabs(ghi - om.Dm[col]) / nutm / om.eps_norm);
+      {  // the smallest (tol - |measured|) / rho, kept as the largest reciprocal (integer atomics on the bits of a non-negative double)
+        const double room = orth_tol - fabs(sproj_m);
+        om_max_bits(om.cnt + kOmCntMargin, room > 0.0 ? rho / room : __longlong_as_double(0x7ff0000000000000ll));
+      }
+      const bool says_zero = fabs(sproj_e) + rho <= om.tol_k;
+      if ((says_zero && fabs(sproj_m) > orth_tol) || fabs(sproj_e - sproj_m) > rho) atomicAdd(om.cnt + kOmCntViol, 1ull);
+      if (!says_zero) {  // mode 1 would measure here: go on from the measurement
+        atomicOr(resc_j, 1);
+        sproj_e = sproj_m;
+        rho = om.theta;
+      }
+    }
+    need_read = need_read || gm != 0.0 || fabs(sproj_e) + rho + om.theta > om.tol_k;
+    om.D[col] = sproj_e * nut;
+    om.rho[col] = rho;
+    om.Dm[col] = sproj_m * nut;
+  }
+  if (need_read) atomicOr(read_j, 1);
+  return gm;
+}
+
 // k_fin_gram: blockIdx.y = i as in k_fin_adots. part: alpha partials of the alpha-only pass.
-__global__ __launch_bounds__(kFinThreads) void k_fin_gram(StepState st, const double *__restrict__ part, int nblk, int j, int RC, double orth_tol) {
+__global__ __launch_bounds__(kFinThreads) void k_fin_gram(StepState st, const double *__restrict__ part, int nblk, int j, int RC, double orth_tol, OmegaState om) {
   __shared__ double red4[kFinThreads];
   const int i = blockIdx.y;
   const int col = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -1968,7 +2088,6 @@ __global__ __launch_bounds__(kFinThreads) void k_fin_gram(StepState st, const do
     constexpr int R1 = kFusedMaxR + 1;
     const int64_t bp = st.bpad;
     const double *Gc = st.gram + (int64_t)(j & 1) * R1 * bp + col;        // Gc[q * bp] = W_j . W_{j-q}
-    const double *Gp = st.gram + (int64_t)((j + 1) & 1) * R1 * bp + col;  // Gp[q * bp] = W_{j-1} . W_{j-1-q}
     const int act = st.active[col];
     const double nuj = st.nu[(int64_t)j * bp + col];
     const double sc = st.coefA[col], cp = st.coefA[bp + col];
@@ -1979,41 +2098,101 @@ __global__ __launch_bounds__(kFinThreads) void k_fin_gram(StepState st, const do
       if (act) st.alpha[(int64_t)j * bp + col] = a;
       st.coefB[col] = cb;
       st.gamma[col] = 0.0;
+    } else if (om.mode != 0 && i == RC - 1) {
+      const double gm = omega_edge(st, om, j, i, col, cb, orth_tol, false);
+      st.gamma[(int64_t)i * bp + col] = gm;
+      if (om.census && gm != 0.0) atomicAdd(om.census + ((int64_t)j * R1 + i) * om.NP + col / om.PW, 1);
     } else {
       const int t = j - i;
-      const double nut = st.nu[(int64_t)t * bp + col];
+      const double nut0 = st.nu[(int64_t)t * bp + col];
       double gm = 0.0;
-      if (act && nut > 0.0) {
-        const double g1 = Gc[(int64_t)(i - 1) * bp], g0 = Gc[(int64_t)i * bp];
-        const double alt = st.alpha[(int64_t)t * bp + col];
-        double s = g1 + (alt / nut) * g0;
-        if (t >= 1 && i + 1 <= kFusedMaxR) {
-          const double nutm = st.nu[(int64_t)(t - 1) * bp + col];
-          if (nutm > 0.0) s += (nut / nutm) * Gc[(int64_t)(i + 1) * bp];  // (zero where the window did not reach W_{t-1}: never in range, see slq.hip)
-        }
-        // W_t . W_{j-1}: t = j - 1 is the squared norm nu_{j-1}^2 itself (W_0's row is never written: take nu everywhere)
-        const double nujm = st.nu[(int64_t)(j - 1) * bp + col];
-        const double wt_wjm = i == 1 ? nujm * nujm : Gp[(int64_t)(i - 1) * bp];
-        const double d = sc * (nut * s) - cp * wt_wjm;
-        const double sproj = (d - cb * g0) / nut;
+      if (act && nut0 > 0.0) {
+        double nut;
+        const double sproj = gram_sproj(st, j, i, col, cb, i + 1 <= kFusedMaxR ? Gc[(int64_t)(i + 1) * bp] : 0.0, &nut);
         if (fabs(sproj) > orth_tol) gm = sproj / nut;
       }
       st.gamma[(int64_t)i * bp + col] = gm;
+      // an applied projection perturbs the entries the edge estimate assumes: the panel measures the edge this step
+      if (om.mode != 0 && gm != 0.0) atomicOr(om.read + (int64_t)j * om.NP + col / om.PW, 1);
+      if (om.census && gm != 0.0) atomicAdd(om.census + ((int64_t)j * R1 + i) * om.NP + col / om.PW, 1);
     }
+  }
+}
+
+// The rescue of an offered step (mode 1): where k_fin_gram could not certify the edge's zero from an estimate, W_j . W_{t-1}
+// is measured after all - W_{t-1} is still in the ring, its slot is the one this step's update pass overwrites. Both kernels
+// are in the launch sequence of every offered step and leave at once where no panel asks (the usual case).
+template <typename F, int LPR>
+__global__ __launch_bounds__(kBlock) void k_omega_rescue_dot(int n, const F *__restrict__ ring, int64_t slot_stride, int S, int j, int back,
+                                                             const int *__restrict__ rescue /* row j */, double *__restrict__ partD, int bpad) {
+  using VF = typename VecT<F>::type;
+  constexpr int V = Geo<F, LPR>::V, PW = Geo<F, LPR>::PW, RPW = Geo<F, LPR>::RPW;
+  __shared__ double red[kWaves * 64 * V];
+  const int panel = blockIdx.y;
+  if (rescue[panel] == 0) return;  // (uniform over the workgroup)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane / LPR, cl = lane % LPR;
+  const int64_t poff = (int64_t)panel * n * PW + cl * V;
+  const F *A = ring + (int64_t)ring_slot(j, S) * slot_stride + poff;
+  const F *B = ring + (int64_t)ring_slot(j - back, S) * slot_stride + poff;
+  VF acc = (VF)(F)0;
+  const int stride = gridDim.x * kWaves * RPW;
+  for (int row = (blockIdx.x * kWaves + wave) * RPW + g; row < n; row += stride) {
+    const int64_t ro = (int64_t)row * PW;
+    acc += *(const VF *)(A + ro) * *(const VF *)(B + ro);
+  }
+  block_reduce_columns<F, LPR>(acc, red, partD + (int64_t)blockIdx.x * bpad + panel * PW);
+}
+
+// ... and the edge position again on the measured entry: today's rule, nothing estimated. partD: k_omega_rescue_dot's partials.
+__global__ __launch_bounds__(kFinThreads) void k_fin_gram_rescue(StepState st, const double *__restrict__ partD, int nblk, int j, int RC, double orth_tol, OmegaState om) {
+  __shared__ double red4[kFinThreads];
+  const int c0 = blockIdx.x * 64;
+  const int *resc_j = om.rescue + (int64_t)j * om.NP;
+  const int p_lo = min(c0 / om.PW, om.NP - 1), p_hi = min((c0 + 63) / om.PW, om.NP - 1);
+  if ((resc_j[p_lo] | resc_j[p_hi]) == 0) return;  // (uniform over the workgroup; a panel is at least 32 columns wide)
+  const int col = c0 + (threadIdx.x & 63);
+  const double m = sum_partials(partD, nblk, st.bpad, col, red4);
+  if ((threadIdx.x >> 6) == 0 && col < st.bpad && resc_j[min(col / om.PW, om.NP - 1)] != 0) {
+    constexpr int R1 = kFusedMaxR + 1;
+    st.gram[((int64_t)(j & 1) * R1 + RC) * st.bpad + col] = m;
+    st.gamma[(int64_t)(RC - 1) * st.bpad + col] = omega_edge(st, om, j, RC - 1, col, st.coefB[col], orth_tol, true);
   }
 }
 
 // After the update pass of step j in the Gram sequence: blockIdx.y = 0 does k_fin_beta's job (beta_{j+1}, stop rule, next
 // sc / cp) and stores ||W_{j+1}||^2 as entry 0 of the new Gram row; blockIdx.y = q >= 1 stores W_{j+1} . W_{j+1-q}
 // (slab q of the pass's partials; the grid has RC + 1 rows of blocks). The next step reads entries 0 .. RC only.
+// An offered step (OmegaState): where the panel's pass left the oldest column unread, entry RC of the new row is the kept
+// numerator of this step's edge projection instead of the pass's (zero) sum; the step's flags are counted.
 __global__ __launch_bounds__(kFinThreads) void k_fin_beta_gram(StepState st, const double *__restrict__ part, int nblk, int j, int RC,
-                                                       double residual_tol) {
+                                                       double residual_tol, OmegaState om) {
   __shared__ double red4[kFinThreads];
   constexpr int R1 = kFusedMaxR + 1;
   const int q = blockIdx.y;
   const int col = blockIdx.x * 64 + (threadIdx.x & 63);
   double s = 0.0;
   if (q <= RC) s = sum_partials(part + (int64_t)q * nblk * st.bpad, nblk, st.bpad, col, red4);
+  if (om.mode != 0 && q == RC) {
+    const int *read_j = om.read + (int64_t)j * om.NP;
+    if ((threadIdx.x >> 6) == 0 && col < st.bpad) {
+      const bool skipped = read_j[min(col / om.PW, om.NP - 1)] == 0;
+      if (om.mode == 2) om.g3[col] = skipped ? om.D[col] : s;
+      else if (skipped) s = om.D[col];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      unsigned long long rd = 0, rs = 0, tr = 0;
+      for (int pn = 0; pn < om.NP; ++pn) {
+        rd += read_j[pn] != 0;
+        rs += om.rescue[(int64_t)j * om.NP + pn] != 0;
+        tr += om.est_prev && om.read[(int64_t)(j - 1) * om.NP + pn] != 0 && read_j[pn] == 0;
+      }
+      atomicAdd(om.cnt + kOmCntOffered, (unsigned long long)om.NP);
+      atomicAdd(om.cnt + kOmCntRead, om.mode == 2 ? (unsigned long long)om.NP : rd);
+      atomicAdd(om.cnt + kOmCntRescue, rs);
+      atomicAdd(om.cnt + kOmCntTrans, tr);
+    }
+  }
   if ((threadIdx.x >> 6) == 0 && col < st.bpad) {
     st.gram[((int64_t)((j + 1) & 1) * R1 + q) * st.bpad + col] = s;
     if (q == 0) {

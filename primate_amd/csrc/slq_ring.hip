@@ -22,7 +22,7 @@ template <int PASS, int RC> constexpr int waves_of() { return RC <= kRingMaxR ? 
 template <int PASS, int RC, int GEO = 0> void launch(const RingArgs &a) {
   constexpr int W = waves_of<PASS, RC>();
   k_ring_pass<F, PASS, 1, RC, L, W, GEO><<<a.grid, dim3(W * 64), RingGeo<L, W, GEO>::kLdsBytes, a.st>>>(
-      a.n, a.desc, a.rec, a.xr, (F *)a.ring, a.slot_stride, a.S, a.j, a.coefA, a.coefB, a.gamma, a.part, a.bpad, a.xt, a.fail, a.dbg);
+      a.n, a.desc, a.rec, a.xr, (F *)a.ring, a.slot_stride, a.S, a.j, a.coefA, a.coefB, a.gamma, a.part, a.bpad, a.xt, a.fail, a.dbg, a.wread);
 }
 template <int PASS, int RC, int GEO = 0> hipError_t prepare() {
   constexpr int W = waves_of<PASS, RC>();

@@ -80,7 +80,8 @@ template <typename F, int PASS, int NTP, int RC, int LPR, int WAVES, int GEO = 0
 __global__ __launch_bounds__(WAVES * 64) void k_ring_pass(
     int n, const int32_t *__restrict__ tile_desc, const char *__restrict__ tile_rec, TileRanges xr, F *ring, int64_t slot_stride, int S, int j,
     const double *__restrict__ coefA, const double *__restrict__ coefB, const double *__restrict__ gamma, double *__restrict__ part,
-    int bpad, int xt, int *__restrict__ fail, unsigned long long *dbg_base /* diagnostic builds (-DSLQ_DEBUG_TIMES) only */) {
+    int bpad, int xt, int *__restrict__ fail, unsigned long long *dbg_base /* diagnostic builds (-DSLQ_DEBUG_TIMES) only */,
+    const int *__restrict__ wread /* PASS_UPDATEG, RC = 3: null, or per panel whether the window's oldest column is read */) {
   using VF = typename VecT<F>::type;
   using RG = RingGeo<LPR, WAVES, GEO>;
   constexpr int R = RG::R, V = Geo<F, LPR>::V, PW = Geo<F, LPR>::PW;
@@ -111,6 +112,13 @@ __global__ __launch_bounds__(WAVES * 64) void k_ring_pass(
   const F *ux[NX];
 #pragma unroll
   for (int i = 0; i < NX; ++i) ux[i] = ring + (int64_t)ring_slot(j - 2 - i, S) * slot_stride + poff;
+  // The oldest column of a full window whose projection is certified zero for every probe of the panel (k_fin_gram) is not
+  // read: its rows stand as zeros, so w is what it would have been (gamma = 0) and the column's Gram sum is zero -
+  // k_fin_beta_gram writes the kept estimate there instead. One flag per panel: uniform over the workgroup.
+  bool rd_old = true;
+  if constexpr (PASS == PASS_UPDATEG && RC == 3) {  // (only full windows of three columns are offered: deeper windows compile to what they were)
+    if (wread != nullptr) rd_old = __builtin_amdgcn_readfirstlane(wread[panel]) != 0;
+  }
   if (threadIdx.x < 2 * NS + 1) flags[threadIdx.x] = 0;
   __syncthreads();
   lds_int *ready = flags, *done = flags + NS, *abort_f = flags + 2 * NS;
@@ -489,7 +497,14 @@ __global__ __launch_bounds__(WAVES * 64) void k_ring_pass(
         if (!first) xpn[i] = stream_load<NTP>((const VF *)(wp + ro));
         if (PASS != PASS_ALPHA && RC > 2) {
 #pragma unroll
-          for (int q = 0; q < NX; ++q) un[i][q] = stream_load<NTP>((const VF *)(ux[q] + ro));
+          for (int q = 0; q < NX; ++q) {
+            if constexpr (PASS == PASS_UPDATEG && RC == 3) {
+              if (q < NX - 1 || rd_old) un[i][q] = stream_load<NTP>((const VF *)(ux[q] + ro));
+              else un[i][q] = (VF)(F)0;
+            } else {
+              un[i][q] = stream_load<NTP>((const VF *)(ux[q] + ro));
+            }
+          }
         }
       }
     };

@@ -22,6 +22,7 @@ struct RingArgs {
   int bpad, xt;
   int *fail;
   unsigned long long *dbg;  // -DSLQ_DEBUG_TIMES builds: the stamp buffer (else null)
+  const int *wread;         // PASS_UPDATEG with three ring columns: per panel, whether the window's oldest column is read (null: always)
 };
 
 // launch: 0, or -1 when the object has no kernel for (pass, rc). prepare: raises the dynamic-LDS limit of all its kernels.

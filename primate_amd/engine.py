@@ -308,6 +308,9 @@ class LanczosPlan:
 		check(_capi.lib().slq_plan_describe(self._h, C.byref(info)))
 		d = {k: getattr(info, k) for k, _ in _capi.PlanInfo._fields_}
 		d["sequence"] = {0: "sweeps", 1: "fused", 2: "fused_stored_u", 4: "fused_gram"}[d["sequence"]]
+		mode = C.c_int()
+		check(_capi.lib().slq_plan_window_verify(self._h, C.byref(mode), None))
+		d["omega"] = int(mode.value)  # the window's oldest column is read only where needed (1), verify mode (2), not offered (0)
 		return d
 
 	def set_probes(self, X: np.ndarray):
@@ -448,6 +451,38 @@ class LanczosPlan:
 		a, b = C.c_uint64(), C.c_uint64()
 		check(_capi.lib().slq_plan_sweep_columns(self._h, C.byref(a), C.byref(b), int(reset)))
 		return int(a.value), int(b.value)
+
+	def window_columns(self, reset: bool = False) -> dict:
+		"""Accounting of the window's oldest column in the Gram sequence (slq_plan_window_columns), summed over steps and panels since the last
+		reset: columns offered and read, rescues, verify-mode violations, read -> skip transitions."""
+		out = (C.c_int64 * 5)()
+		check(_capi.lib().slq_plan_window_columns(self._h, out, int(reset)))
+		return dict(zip(("offered", "read", "rescues", "violations", "transitions"), (int(v) for v in out)))
+
+	def window_verify(self) -> dict:
+		"""What SLQ_OMEGA=2 runs have recorded since the counters' last reset (slq_plan_window_verify): the largest one-step innovation in units of
+		eps ||A||_inf, the smallest (tol - |measured|) / rho, and the certificate's constants."""
+		out = (C.c_double * 5)()
+		check(_capi.lib().slq_plan_window_verify(self._h, None, out))
+		return dict(zip(("innovation", "margin", "c", "kappa", "norm_inf"), (float(v) for v in out)))
+
+	def window_flags(self) -> tuple:
+		"""(read, rescue), each [deg + 1, panels]: where the update pass of step j read the window's oldest column, and where its entry was
+		measured by the rescue kernels, in the last run (slq_plan_window_flags; zero rows for steps that were not offered)."""
+		panels = self.describe()["panels"]
+		rd = np.zeros((self.deg + 1, panels), dtype=np.int32)
+		rs = np.zeros((self.deg + 1, panels), dtype=np.int32)
+		i32 = C.POINTER(C.c_int32)
+		check(_capi.lib().slq_plan_window_flags(self._h, rd.ctypes.data_as(i32), rs.ctypes.data_as(i32), rd.size))
+		return rd, rs
+
+	def window_census(self) -> np.ndarray:
+		"""[deg + 1, 9, panels] probes with a non-zero projection coefficient per step, window position and panel in the last run
+		(plans of the ring-fed Gram sequence created under SLQ_OMEGA=2; slq_plan_window_census)."""
+		panels = self.describe()["panels"]
+		out = np.zeros((self.deg + 1, 9, panels), dtype=np.int32)
+		check(_capi.lib().slq_plan_window_census(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), out.size))
+		return out
 
 	def action_columns(self, reset: bool = True) -> tuple:
 		"""(read, offered): ring columns the accumulation launches of a recompute plan's replays read against the ones they were offered, summed

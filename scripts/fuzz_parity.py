@@ -1,9 +1,12 @@
 """Randomised parity sweep on the GPU box: random SPD graphs / grids, every panel geometry, orth 0..deg,
 both dtypes, against the CPU oracle on identical probes. Prints one line per failure and a summary.
-usage: python scripts/fuzz_parity.py [seconds] [seed] [tiles]
+usage: python scripts/fuzz_parity.py [seconds] [seed] [tiles] [omega [cases]]
 `tiles`: operators big enough for workgroup tiles (n 4,100-45,000, SLQ_TILES=2 forced), panels of 16, 32 and 64 lanes per
 row (17-300 probes: k_ring_pass on merged tiles and k_csr_ring_pass), orth up to k (the 8-wave form for 4..8 ring columns) -
-the ring-fed tile kernels with ragged tile counts, short last (merged) tiles, empty and long rows."""
+the ring-fed tile kernels with ragged tile counts, short last (merged) tiles, empty and long rows.
+`omega` (with `tiles`): the edge recurrence of the Gram sequence on the same operators at orth = 3, device only -
+every case runs under SLQ_OMEGA=2 (verify: zero violations is the condition, and the results are bitwise those of SLQ_OMEGA=0) and
+under the default (bitwise SLQ_OMEGA=0 where no rescue happened, else alpha / beta within 1e-10 / 3e-4 of it); stops after `cases` cases."""
 import os, sys, time
 from pathlib import Path
 import numpy as np, scipy.sparse as sp
@@ -17,9 +20,47 @@ oracle.build()
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 TILES = len(sys.argv) > 3 and sys.argv[3] == "tiles"
+OMEGA = TILES and len(sys.argv) > 4 and sys.argv[4] == "omega"
+OMEGA_CASES = int(sys.argv[5]) if len(sys.argv) > 5 else 10000
 if TILES:
 	os.environ["SLQ_TILES"] = "2"
 tiled_cases = 0
+om = {"offered": 0, "read": 0, "rescues": 0, "violations": 0, "transitions": 0, "innovation": 0.0, "margin": float("inf"), "plans_offering": 0, "plans_checked": 0, "with_rescue": 0}
+
+
+def omega_case(Ad, X, deg):
+	"""One operator at orth = 3 under SLQ_OMEGA = 2, 0 and the default; returns whether the case failed."""
+	op = eng.DeviceOperator(Ad)
+	res = {}
+	for mode in ("2", "0", "1"):
+		os.environ["SLQ_OMEGA"] = mode
+		pl = eng.LanczosPlan(op, X.shape[1], deg, 3)
+		pl.set_probes(X)
+		pl.run()
+		res[mode] = (*pl.tridiag(), pl.quadrature("exp", t=-0.1), pl.window_columns(), pl.window_verify(), pl.describe()["omega"])
+		pl.close()
+	del os.environ["SLQ_OMEGA"]
+	op.close()
+	same = lambda a, b: all(np.array_equal(x, y) for x, y in zip(a[:4], b[:4]))
+	v, off, on = res["2"], res["0"], res["1"]
+	bad = not same(v, off) or v[4]["violations"] != 0
+	if on[4]["rescues"] == 0:
+		bad = bad or not same(on, off)
+	else:
+		tol = 1e-10 if Ad.dtype == np.float64 else 3e-4
+		bad = bad or any(np.max(np.abs(x - y)) > tol * max(np.max(np.abs(y)), 1e-300) for x, y in zip(on[:2], off[:2]))
+		om["with_rescue"] += 1
+	for k in ("offered", "read", "rescues", "transitions"):
+		om[k] += on[4][k]
+	om["violations"] += v[4]["violations"]
+	om["innovation"] = max(om["innovation"], v[5]["innovation"])
+	om["margin"] = min(om["margin"], v[5]["margin"])
+	om["plans_offering"] += on[6] == 1
+	om["plans_checked"] += v[5]["innovation"] > 0.0  # (the verify run carried an estimate over a skipped step and compared it with the measurement)
+	if bad:
+		print(f"FAIL omega n={Ad.shape[0]} nnz={Ad.nnz} dtype={Ad.dtype} P={X.shape[1]} deg={deg}: verify {v[4]} {v[5]} default {on[4]}", flush=True)
+	return bad
+
 
 def random_spd(n, deg, rng):
 	m = int(n * deg / 2)
@@ -66,6 +107,21 @@ while time.time() - t0 < budget:
 	fun, kw = [("log", {}), ("exp", {"t": -0.1}), ("identity", {}), ("sqrt", {}), ("inv", {})][int(rng.integers(0, 5))]
 	Ad = A.astype(dtype)
 	X = np.asfortranarray((np.floor(rng.random((n, P)) * 2) * 2 - 1 if rng.random() < 0.5 else rng.standard_normal((n, P))).astype(dtype))
+	if OMEGA:
+		## (an operator's host analysis costs more than its runs: six draws of panel width, degree and probes per operator)
+		for _ in range(6):
+			fails += omega_case(Ad, X, deg)
+			cases += 1
+			if cases % 500 == 0 or cases == OMEGA_CASES:
+				print(f"... {cases} cases, {fails} failures, {time.time() - t0:.0f} s: {om}", flush=True)
+			if cases >= OMEGA_CASES:
+				break
+			P = int(rng.choice([17, 20, 32, 33, 40, 64, 65, 128, 129, 200, 257])) if dtype == np.float64 else int(rng.choice([33, 40, 64, 65, 100, 128, 129, 256, 257, 300]))
+			deg = int(rng.integers(1, min(n, 150 if rng.random() < 0.25 else 20) + 1))
+			X = np.asfortranarray((np.floor(rng.random((n, P)) * 2) * 2 - 1 if rng.random() < 0.5 else rng.standard_normal((n, P))).astype(dtype))
+		if cases >= OMEGA_CASES:
+			break
+		continue
 	## near-breakdown runs (beta -> 0: small grids with repeated eigenvalues) amplify rounding by 1/beta in ANY
 	## implementation, and a zero Ritz value makes sqrt/log/inv a coin toss: compare only well-posed runs
 	al, be, Qr = np.zeros(deg + 1, dtype), np.zeros(deg + 1, dtype), np.zeros((n, max(orth, 2)), dtype, order="F")
@@ -142,6 +198,11 @@ while time.time() - t0 < budget:
 		print(f"FAIL kind={kind} n={n} nnz={A.nnz} dtype={dtype.__name__} P={P} deg={deg} orth={orth} fun={fun} err={err}", flush=True)
 	if cases % 50 == 0:
 		print(f"... {cases} cases, {fails} failures, worst fp64 rel err {worst:.2e}, {time.time() - t0:.0f} s", flush=True)
+if OMEGA:
+	print(f"omega: {cases} cases (deg <= 150, orth = 3), {fails} failures, {om['violations']} violations; {om['plans_offering']} plans offered their windows, {om['plans_checked']} compared an estimate with a measurement in verify mode (the others are too small to skip: tol / kappa below three theta): "
+	      f"{om['read']} of {om['offered']} columns read, {om['rescues']} rescues in {om['with_rescue']} cases, {om['transitions']} read -> skip transitions; "
+	      f"largest innovation {om['innovation']:.4f} eps ||A||_inf, smallest margin {om['margin']:.3f}")
+	sys.exit(1 if fails or om["violations"] else 0)
 if TILES:
 	print(f"{tiled_cases} of the {cases} cases ran on ring-fed tiles")
 print(f"done: {cases} cases, {fails} failures ({illposed_skipped} mismatches confined to near-breakdown probes, {sensitive_skipped} within 10x the oracle's own 1-ulp sensitivity and "
