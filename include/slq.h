@@ -371,6 +371,11 @@ int slq_plan_sweep_columns(slq_plan *plan, uint64_t *read, uint64_t *offered, in
  * against the measurement). out: columns offered, columns read, rescues (the missing entry measured by a dot of its own), verify-mode violations,
  * read -> skip transitions; summed over steps and panels since the last reset; zeros for a plan that offers nothing. Synchronises. */
 int slq_plan_window_columns(slq_plan *plan, int64_t out[5], int reset);
+/* Which kernel computes the product of a plan on a dense operator, and over how many K slabs (a diagnostic entry: what the plan will launch, from the
+ * panel width, the operator's leading dimension and the SLQ_DENSE_* switches read when it was created). kernel: 0 the operator is not dense,
+ * 1 k_dense_panel, 2 k_dense_mfma_3term, 3 k_dense_mfma_tile, 4 k_dense_mfma_lds, 5 k_dense_mfma32_lds; ksplit: workgroups (slabs) the K range is
+ * split over, 0 for the kernels without slabs. kernel or ksplit may be NULL. */
+int slq_plan_dense_path(slq_plan *plan, int *kernel, int *ksplit);
 /* ... the plan's mode (0 where nothing is offered) and, from verify runs since the last reset of those counters: out[0] the largest one-step innovation
  * |measured - predicted| in units of eps ||A||_inf, out[1] the smallest (tol - |measured|) / rho (inf: none seen), out[2], out[3] the constants c and kappa
  * of the certificate, out[4] ||A||_inf. mode or out may be NULL. */

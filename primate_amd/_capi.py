@@ -112,6 +112,7 @@ _SIGNATURES = {
 	"slq_plan_action_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
 	"slq_plan_sweep_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
 	"slq_plan_window_columns": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int]),
+	"slq_plan_dense_path": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 	"slq_plan_window_verify": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
 	"slq_plan_window_census": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int64]),
 	"slq_plan_window_flags": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]),

@@ -3295,13 +3295,37 @@ extern "C" int slq_plan_get_probes(slq_plan *p, void *X, int64_t ldx) {
 }
 
 
+// Which kernel computes a plan's dense product (the ids of slq_plan_dense_path): the one decision behind launch_dense_mfma,
+// apply_operator_unfused and the step loop. 0: not a dense operator.
+enum { DENSE_K_NONE = 0, DENSE_K_PANEL = 1, DENSE_K_3TERM = 2, DENSE_K_TILE = 3, DENSE_K_LDS = 4, DENSE_K_LDS32 = 5 };
+static int dense_kernel_of(const slq_plan *p) {
+  const slq_operator *op = p->op;
+  if (op->kind != OP_DENSE) return DENSE_K_NONE;
+  if (!p->sw.dense_mfma || (p->dtype != SLQ_F64 && p->dense_ks <= 0)) return DENSE_K_PANEL;  // the VALU kernel (SLQ_DENSE_MFMA=0)
+  if (p->dense_ks <= 0) return DENSE_K_3TERM;  // 16-column panels, SLQ_DENSE_TILE16=1: the 16-row kernel with its fused epilogue
+  if (p->dtype == SLQ_F32) return DENSE_K_LDS32;
+  // operands staged in LDS once per workgroup: 16-byte aligned row pairs (lda even) and panels of 64+ columns (32-column
+  // panels keep the register form: their 256-row block does not fit static LDS)
+  return p->sw.dense_lds && op->lda % 2 == 0 && p->PW >= 64 ? DENSE_K_LDS : DENSE_K_TILE;
+}
+
+// Which kernel computes this plan's dense product, and over how many K slabs (diagnostics, tests): kernel 0 not dense, 1 k_dense_panel,
+// 2 k_dense_mfma_3term, 3 k_dense_mfma_tile, 4 k_dense_mfma_lds, 5 k_dense_mfma32_lds; ksplit = dense_ks (0: no slabs). A pure function of the plan.
+extern "C" int slq_plan_dense_path(slq_plan *p, int *kernel, int *ksplit) {
+  if (!p) return fail(SLQ_EINVAL, "plan is NULL");
+  if (kernel) *kernel = dense_kernel_of(p);
+  if (ksplit) *ksplit = p->dense_ks;
+  return SLQ_OK;
+}
+
 // dense operator on MFMA (fp64, and fp32 through k_dense_mfma32_lds): Wn = sc*(A Wc) - cp*Wp with alpha partials (plain = 0), or Wn = A Wc
 static int launch_dense_mfma(slq_plan *p, const void *Wc, const void *Wp, void *Wn, int first, int plain, int *nblk_out) {
   const slq_operator *op = p->op;
   hipStream_t st = p->ctx->stream;
   // panels of 32+ columns: big tiles, K split over workgroups, epilogue by k_3term_slabs (k_dense_mfma_tile);
   // 16-column panels: the 16-row kernel with its fused epilogue. SLQ_DENSE_TILE16=1 forces the latter (A/B runs).
-  if (p->dense_ks > 0 && p->dtype == SLQ_F32) {
+  const int kernel = dense_kernel_of(p);
+  if (kernel == DENSE_K_LDS32) {
     const int ks = p->dense_ks;
     float *raw = (float *)p->T + p->slot_stride;  // slabs 1..ks of T (slab 0 is the unfused product)
     const dim3 g((p->n + kDense32BM - 1) / kDense32BM, p->NP, ks);
@@ -3315,15 +3339,14 @@ static int launch_dense_mfma(slq_plan *p, const void *Wc, const void *Wp, void *
     if (nblk_out) *nblk_out = p->nblkS;
     return SLQ_OK;
   }
-  if (p->dense_ks > 0) {
+  if (kernel == DENSE_K_LDS || kernel == DENSE_K_TILE) {
     const int ks = p->dense_ks;
     double *raw = (double *)p->T + p->slot_stride;  // slabs 1..ks of T (slab 0 is the unfused product)
     const int ncg = p->PW >= 64 ? 2 : 1;
     const int rw = 32 * (kWaves / ncg);
     const dim3 g((p->n + rw - 1) / rw, p->NP, ks);
-    const bool lds_form = p->sw.dense_lds && (op->lda % 2 == 0);  // operands staged in LDS once per workgroup (16-byte aligned row pairs)
     for (int col0 = 0; col0 < p->PW; col0 += 32 * ncg) {  // PW = 128: two 64-column halves, A streamed twice
-      if (lds_form && ncg == 2)  // (panels of 64+ columns; 32-column panels keep the register form: their 256-row block does not fit static LDS)
+      if (kernel == DENSE_K_LDS)
         k_dense_mfma_lds<2><<<g, dim3(kBlock), 0, st>>>(p->n, (const double *)op->vals, op->lda, (const double *)Wc, p->PW, col0, raw, p->slot_stride);
       else if (ncg == 2)
         k_dense_mfma_tile<2><<<g, dim3(kBlock), 0, st>>>(p->n, (const double *)op->vals, op->lda, (const double *)Wc, p->PW, col0, raw, p->slot_stride);
@@ -3363,7 +3386,7 @@ static int launch_dense_mfma(slq_plan *p, const void *Wc, const void *Wp, void *
 static int apply_operator_unfused(slq_plan *p, int slot_c) {
   hipStream_t st = p->ctx->stream;
   slq_operator *op = p->op;
-  if (op->kind == OP_DENSE && p->sw.dense_mfma && (p->dtype == SLQ_F64 || p->dense_ks > 0)) {
+  if (dense_kernel_of(p) >= DENSE_K_3TERM) {
     PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_dense_mfma(p, slot_ptr(p, slot_c), nullptr, p->T, 1, 1, nullptr)));
     return SLQ_OK;
   }
@@ -3784,7 +3807,7 @@ static int enqueue_run(slq_plan *p, double rtol, int fused_mode, bool nt, int j0
 #undef SPMM_LAUNCH
       PROFILED(p, SLQ_K_FINALIZE,
                hipLaunchKernelGGL(k_fin_alpha, gF, dim3(kFinThreads), 0, st, p->st, p->part, p->nblkA, j, 0));
-    } else if (op->kind == OP_DENSE && p->sw.dense_mfma && (p->dtype == SLQ_F64 || p->dense_ks > 0)) {
+    } else if (dense_kernel_of(p) >= DENSE_K_3TERM) {
       int nb = 0;
       PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_dense_mfma(p, slot_ptr(p, sc_), slot_ptr(p, sp_), slot_ptr(p, sn_), first, 0, &nb)));
       PROFILED(p, SLQ_K_FINALIZE,

@@ -311,6 +311,10 @@ class LanczosPlan:
 		mode = C.c_int()
 		check(_capi.lib().slq_plan_window_verify(self._h, C.byref(mode), None))
 		d["omega"] = int(mode.value)  # the window's oldest column is read only where needed (1), verify mode (2), not offered (0)
+		kernel, ksplit = C.c_int(), C.c_int()
+		check(_capi.lib().slq_plan_dense_path(self._h, C.byref(kernel), C.byref(ksplit)))
+		## dense operators: 1 k_dense_panel, 2 k_dense_mfma_3term, 3 k_dense_mfma_tile, 4 k_dense_mfma_lds, 5 k_dense_mfma32_lds (0: not dense); K slabs
+		d["dense_kernel"], d["dense_ksplit"] = int(kernel.value), int(ksplit.value)
 		return d
 
 	def set_probes(self, X: np.ndarray):

@@ -6,7 +6,12 @@ row (17-300 probes: k_ring_pass on merged tiles and k_csr_ring_pass), orth up to
 the ring-fed tile kernels with ragged tile counts, short last (merged) tiles, empty and long rows.
 `omega` (with `tiles`): the edge recurrence of the Gram sequence on the same operators at orth = 3, device only -
 every case runs under SLQ_OMEGA=2 (verify: zero violations is the condition, and the results are bitwise those of SLQ_OMEGA=0) and
-under the default (bitwise SLQ_OMEGA=0 where no rescue happened, else alpha / beta within 1e-10 / 3e-4 of it); stops after `cases` cases."""
+under the default (bitwise SLQ_OMEGA=0 where no rescue happened, else alpha / beta within 1e-10 / 3e-4 of it); stops after `cases` cases.
+usage: python scripts/fuzz_parity.py [seconds] [seed] dense [cases]
+`dense`: the dense operator's product kernels (tests/test_gpu_dense.py draws from the same lists): n in [1, 600], P in [1, 300], a dtype and one
+variant of the SLQ_DENSE_* switches per case; the kernel the plan reports must be the expected one, the product of integer operands must equal
+the exact one bit for bit (a non-symmetric A, C- or F-ordered), and a Lanczos run on B B^T / n + I (k = min(12, n), orth 0 or 3, Rademacher probes)
+must give the oracle's log quadrature for every column and its alpha / beta on six columns within 1e-10 (fp64) / 3e-4 (fp32)."""
 import os, sys, time
 from pathlib import Path
 import numpy as np, scipy.sparse as sp
@@ -60,6 +65,91 @@ def omega_case(Ad, X, deg):
 	if bad:
 		print(f"FAIL omega n={Ad.shape[0]} nnz={Ad.nnz} dtype={Ad.dtype} P={X.shape[1]} deg={deg}: verify {v[4]} {v[5]} default {on[4]}", flush=True)
 	return bad
+
+
+def dense_sweep(budget, rng, max_cases):
+	"""The `dense` mode; returns the exit status."""
+	from test_gpu_dense import F32, F64, SWITCHES, V32, V64, KERNEL_NAMES, expected_path
+
+	t0 = time.time(); cases = fails = skipped = 0
+	seen = {}
+	worst = {"float64": 0.0, "float32": 0.0}
+	while time.time() - t0 < budget and cases < max_cases:
+		dtype = F64 if rng.random() < 0.7 else F32
+		variant = (V64 if dtype == F64 else V32)[int(rng.integers(0, len(V64 if dtype == F64 else V32)))]
+		n, P = int(rng.integers(1, 601)), int(rng.integers(1, 301))
+		orth = int(rng.choice([0, 3]))
+		for k in SWITCHES:
+			os.environ.pop(k, None)
+		os.environ.update(variant)
+		what = f"n={n} P={P} dtype={np.dtype(dtype).name} variant={variant} orth={orth}"
+		try:
+			want_k, want_ks = expected_path(dtype, variant, n, P)
+			## (a) integer operands: every partial sum is an exact float (below 2^53 / 2^24), so the BLAS product in fp64 is the exact one too
+			lim = 1000 if dtype == F64 else 64
+			A = rng.integers(-lim, lim + 1, (n, n)).astype(dtype)
+			X = rng.integers(-lim, lim + 1, (n, P)).astype(dtype)
+			op = eng.DeviceOperator(np.asfortranarray(A) if rng.random() < 0.5 else np.ascontiguousarray(A))
+			pl = eng.LanczosPlan(op, P, 1, 0)
+			d = pl.describe()
+			pl.close()
+			Y = op.matmat(X)
+			op.close()
+			bad = d["dense_kernel"] != want_k or (d["dense_ksplit"] != want_ks if want_ks is not None else not 1 <= d["dense_ksplit"] <= 16)
+			if bad:
+				print(f"FAIL dense path {what}: kernel {d['dense_kernel']} ksplit {d['dense_ksplit']}, expected {want_k} / {want_ks}", flush=True)
+			exact = A.astype(np.float64) @ X.astype(np.float64)
+			if not np.array_equal(Y, exact):
+				w = np.argwhere(Y != exact)
+				print(f"FAIL dense exact {what} kernel={want_k}: {len(w)} entries differ, rows {w[:, 0].min()}..{w[:, 0].max()}, columns {w[:, 1].min()}..{w[:, 1].max()}", flush=True)
+				bad = True
+			## (c) the fused epilogue and the alpha partials through Lanczos
+			B = rng.standard_normal((n, n))
+			S = B @ B.T / n + np.eye(n)
+			S = np.asfortranarray(((S + S.T) / 2).astype(dtype))
+			V = np.asfortranarray((np.floor(rng.random((n, P)) * 2) * 2 - 1).astype(dtype))
+			deg = min(12, n)
+			bar = 1e-10 if dtype == F64 else 3e-4
+			op = eng.DeviceOperator(S)
+			pl = eng.LanczosPlan(op, P, deg, orth)
+			bad = bad or pl.describe()["dense_kernel"] != want_k
+			pl.set_probes(V)
+			pl.run()
+			a, b, st = pl.tridiag()
+			q = pl.quadrature("log")
+			pl.close()
+			op.close()
+			ref = oracle.quad_batch(S, V, deg, orth, fun="log", fresh_q=True, nthreads=16)
+			err = 0.0
+			for c in sorted({0, P // 2, P - 1, min(P - 1, 63), min(P - 1, 64), min(P - 1, 128)}):
+				al, be, Q = np.zeros(deg + 1, dtype), np.zeros(deg + 1, dtype), np.zeros((n, max(orth, 2)), dtype, order="F")
+				steps = oracle.lanczos(S, V[:, c].copy(), deg, 1e-8, min(orth, deg), al, be, Q)
+				if steps < deg or (deg > 1 and np.min(np.abs(be[1:deg])) < 1e-3 * np.max(np.abs(be[1:deg]))):
+					skipped += 1  # (near breakdown: 1 / beta amplifies any implementation's rounding, as in the sparse sweep)
+					continue
+				scale = float(np.max(np.abs(al[:deg])))
+				err = max(err, float(np.max(np.abs(a[c, :deg] - al[:deg])) / scale), float(np.max(np.abs(b[c, :deg] - be[:deg])) / scale), abs(float(q[c] / ref[c]) - 1.0))
+				bad = bad or st[c] != steps
+			if not err <= bar:
+				print(f"FAIL dense lanczos {what} kernel={want_k}: error {err:.3e} above {bar:g}", flush=True)
+				bad = True
+			worst[np.dtype(dtype).name] = max(worst[np.dtype(dtype).name], err)
+			seen[want_k] = seen.get(want_k, 0) + 1
+		except Exception as e:  # noqa: BLE001
+			print(f"FAIL dense {what}: {e!r}", flush=True)
+			bad = True
+		cases += 1
+		fails += bool(bad)
+		if cases % 250 == 0:
+			print(f"... {cases} cases, {fails} failures, {time.time() - t0:.0f} s", flush=True)
+	per = ", ".join(f"{KERNEL_NAMES[k]} {c}" for k, c in sorted(seen.items()))
+	print(f"dense: {cases} cases in {time.time() - t0:.0f} s, {fails} failures ({skipped} near-breakdown columns not compared); cases per kernel: {per}; "
+	      f"worst alpha / beta / log-quadrature error fp64 {worst['float64']:.2e} (bar 1e-10), fp32 {worst['float32']:.2e} (bar 3e-4)")
+	return 1 if fails else 0
+
+
+if len(sys.argv) > 3 and sys.argv[3] == "dense":
+	sys.exit(dense_sweep(budget, rng, int(sys.argv[4]) if len(sys.argv) > 4 else 1 << 30))
 
 
 def random_spd(n, deg, rng):

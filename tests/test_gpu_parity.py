@@ -272,7 +272,7 @@ def test_operator_products(eng):
 	A32 = A.astype(np.float32)
 	np.testing.assert_allclose(eng.DeviceOperator(A32).matmat(X.astype(np.float32)), ref, rtol=2e-5, atol=2e-5)
 	## a dense operator's product is A X for WHATEVER is given (eigen_operators.h:24-30), also a non-symmetric array, on
-	## the fp64 matrix-core kernel and on the fp32 column-walking one
+	## the fp64 and the fp32 matrix-core kernels (the column-walking k_dense_panel runs under SLQ_DENSE_MFMA=0 only: tests/test_gpu_dense.py)
 	G = rng.standard_normal((301, 301))
 	Xg = np.asfortranarray(rng.standard_normal((301, 21)))
 	np.testing.assert_allclose(eng.DeviceOperator(G).matmat(Xg), G @ Xg, rtol=1e-11, atol=1e-11)

@@ -30,6 +30,23 @@ def test_library_exports_every_declared_symbol():
 	assert L.slq_version() == 100
 
 
+def test_dense_path_entry_point_and_its_single_decision():
+	"""slq_plan_dense_path (which dense kernel a plan launches: tests/test_gpu_dense.py asserts it on every item) is declared, bound and
+	exported, LanczosPlan.describe() reports it, and the launch code takes the decision from the same helper as the accessor."""
+	from primate_amd import _capi
+
+	hdr = (ROOT / "include" / "slq.h").read_text()
+	assert "slq_plan_dense_path" in _capi.EXPORTED_SYMBOLS and re.search(r"\bint slq_plan_dense_path\(slq_plan \*plan, int \*kernel, int \*ksplit\);", hdr)
+	assert hasattr(_capi.lib(), "slq_plan_dense_path")
+	assert _capi._SIGNATURES["slq_plan_dense_path"][1][1:] == [_capi.C.POINTER(_capi.C.c_int)] * 2
+	eng = (ROOT / "primate_amd" / "engine.py").read_text()
+	assert 'd["dense_kernel"], d["dense_ksplit"]' in eng
+	src = (ROOT / "primate_amd" / "csrc" / "slq.hip").read_text()
+	## the accessor, launch_dense_mfma, apply_operator_unfused and the step loop all ask dense_kernel_of; nothing else re-derives the choice
+	assert len(re.findall(r"\bdense_kernel_of\(p\)", src)) >= 4
+	assert not re.search(r"\blds_form\b", src) and len(re.findall(r"sw\.dense_lds", src)) == 1 and len(re.findall(r"sw\.dense_tile16", src)) == 1
+
+
 def test_ring_pass_bail_out_is_reported_not_swallowed():
 	"""The ring-fed tile pass bounds every wait; a workgroup that gives up raises a device word, and the accessors turn
 	it into SLQ_EHIP through ONE translation (slq.hip: ring_flag_status). That translation needs no device: a clear flag
