@@ -400,6 +400,11 @@ int slq_debug_ring_flag_status(int flag);
 int slq_debug_plan_poke_ring_flag(slq_plan *plan, int value);
 /* test hook: mark a plan as holding nstale stale ring columns (what the drop-in entry does to its own plan) */
 int slq_debug_plan_mark_stale(slq_plan *plan, int nstale);
+/* What step j of a run launches, as the library decides it, without a device (csrc/slq_sequence.hpp: step_shape). facts: the
+ * 27 facts of a plan and its operator in the order of seq::facts_from_array (facts[2]: the operator's tiles, 0 none / 1 landed
+ * behind barriers / 2 ring-fed); out: the 18 values of seq::shape_to_array, then what slq_plan_describe reports as
+ * `sequence` for such a plan. No HIP call. */
+int slq_debug_step_shape(const int *facts, int nfacts, int j, int prev_xt, int *out, int nout);
 
 /* ---- one-shot entries ---------------------------------------------------------------------------- */
 /* P probes in one call: the batched counterpart of the Python loop at

@@ -29,6 +29,8 @@
 #include "slq_density.hpp"  // spectral density accumulator (slq_density_*)
 #include "slq_radau.hpp"    // prefix quadrature, Gauss-Radau rule, stage statistics (slq_plan_quadrature_at)
 #include "slq_action.hpp"   // two-pass f(A)v: the accumulation of a recompute plan's replay (slq_plan_create_recompute)
+#include "slq_switches.hpp"  // the table of run-time switches, OperatorSwitches, PlanSwitches
+#include "slq_sequence.hpp"  // what a step launches, as a value (step_shape)
 
 using namespace slq;
 
@@ -148,43 +150,12 @@ struct slq_operator {
   // affine CSR operator A + t B (slq_csr_affine_create): values of A and B on the union pattern (vals = va + t vb)
   void *vals_a = nullptr, *vals_b = nullptr;
   void *vals_t = nullptr;    // OP_DENSE, non-symmetric input only (also the values of A^T for OP_GRAM): the transpose, for the kernel that walks A by columns (null: A == A^T)
+  OperatorSwitches sw;       // the switches as they were when the operator was created (slq_switches.hpp)
 };
 
 struct ProfEvent {
   hipEvent_t a, b;
   int kind;
-};
-
-// Every run-time switch of the launch sequence, read from the environment ONCE, when the plan is
-// created: a plan never changes its behaviour afterwards, and key() is part of what identifies its captured hipGraph.
-struct Switches {
-  int fused;       // SLQ_FUSED     1: recompute-SpMM passes where they pay, 0: store-and-revisit sweeps, 2: passes always
-  int nt;          // SLQ_NT        nontemporal hints on streamed-once rows
-  int graph;       // SLQ_GRAPH     capture the k-step launch sequence into a hipGraph
-  int mgs;         // SLQ_MGS       exact modified-Gram-Schmidt order
-  int stored_u;    // SLQ_STORED_U  non-local operators: merged pass stores u, update pass reads it back
-  int merged;      // SLQ_MERGED    alpha from the merged alpha+dots pass
-  int cross;       // SLQ_CROSS     q_c.q_p from the update pass's cross term
-  int tiles;       // SLQ_TILES     fused passes on the operator's LDS workgroup tiles (when it has them)
-  int ring_alpha;  // SLQ_RING_ALPHA the alpha-only pass of a tiled symmetric operator: 2 ring over the upper-triangle stream, 1 ring over
-                   //               the full rows, 0 the generic upper-triangle pass
-  int ring_rev;    // SLQ_RING_REV  the ring-fed update pass sweeps panels and tiles in reverse (it starts where the dots pass ended)
-  int dense_mfma;  // SLQ_DENSE_MFMA dense operator on the matrix cores (fp64 and fp32)
-  int dense_tile16;  // SLQ_DENSE_TILE16 keep the 16-row dense kernel also for wide panels (A/B runs)
-  int dense_lds;     // SLQ_DENSE_LDS  fp64 dense product with the operands staged in LDS (k_dense_mfma_lds; 0: k_dense_mfma_tile)
-  int pipe;        // SLQ_PIPE      pipelined row loop in the dots/update passes (-1: by operator, slq_plan_create)
-  int fused_pad;   // SLQ_FUSED_LDS_PAD (-1: by row loop)
-  int spmm_pad;    // SLQ_SPMM_LDS_PAD
-  int defer_axpy;  // SLQ_DEFER_AXPY the block-CGS sweeps apply `w -= cB W_c` in the update sweep: the dots sweeps are read-only (r04; 0: first chunk stores)
-  int omega;       // SLQ_OMEGA     the oldest column of a full 3-column window is read only where its zero projection is not certified:
-                   //               1 on, 0 every column read (the sequence as it was), 2 verify (every column read, the certificate checked beside it)
-  int omega_trip, omega_rescue;  // SLQ_OMEGA_TRIP / SLQ_OMEGA_RESCUE (tests): the step at which every panel reads / takes the rescue (-1: none)
-  unsigned key() const {
-    unsigned k = 0;
-    for (int v : {fused, nt, graph, mgs, stored_u, merged, cross, tiles, ring_alpha, ring_rev, dense_mfma, dense_tile16, dense_lds, pipe, fused_pad, spmm_pad, defer_axpy, omega, omega_trip, omega_rescue})
-      k = k * 1000003u + (unsigned)(v + 7);
-    return k;
-  }
 };
 
 struct slq_plan {
@@ -222,7 +193,9 @@ struct slq_plan {
   std::vector<char> hbuf;  // host staging for callback operators
   size_t bytes;
   int nstale;                 // > 0: the reorthogonalisation also sees nstale preloaded vectors t = -1 .. -nstale
-  // the launch sequence of steps [j0, j1) captured once per (j0, j1, rtol, variant); the one-shot run is the entry (0, deg)
+  // the launch sequence of steps [j0, j1) captured once per (j0, j1, rtol, variant); the one-shot run is the entry (0, deg).
+  // Everything else the sequence depends on is fixed when the plan is created (PlanSwitches), so variant is what can change
+  // under a live plan: the number of stale ring columns (slq_debug_plan_mark_stale).
   struct GraphEntry {
     int j0, j1;
     double rtol;
@@ -239,7 +212,7 @@ struct slq_plan {
   // slq_plan_quadrature_at (allocated by its first call): quad | gauss | stage[4] | nodes | weights (P x (deg + 1) each), two flag words
   double *at_d = nullptr;
   int *at_flags = nullptr;
-  Switches sw;
+  PlanSwitches sw;            // the switches as they were when the plan was created (slq_switches.hpp)
   bool pipelined;             // dots/update passes run the pipelined row loop (slq_plan_create)
   int dense_ks;               // dense MFMA operator with big tiles: K split over this many workgroups per row tile (0: 16-row kernel)
   // ring-fed tile passes (k_csr_ring_pass / k_ring_pass): ringR = panel rows per wave instruction of the tile stream the plan
@@ -278,14 +251,16 @@ struct slq_plan {
   bool acc_skip = true;       // the accumulation does not read columns whose coefficient is zero for every probe of the panel (SLQ_ACC_SKIP=0: reads them all)
   hipGraphExec_t replay_exec = nullptr;  // the replay (deg steps + accumulation launches: a linear chain) captured for replay_rtol / replay_variant
   double replay_rtol = 0.0;
-  unsigned replay_variant = 0;
+  unsigned replay_variant = 0;  // (nstale, as GraphEntry::variant)
   bool replay_xt_out = false;
 };
 
 // SLQ_TILES: 0 none, 1 workgroup tiles landed behind barriers (k_csr_tile_pass), 2 tiles fed through a ring of LDS slots by
 // loader waves (k_csr_ring_pass). Read when an operator is created (the rows are regrouped into the tiles) and when a plan
 // is created (whether its passes use them).
-constexpr int kTilesDefault = 2;
+static_assert(OperatorSwitches{}.tiles == 2 && OperatorSwitches{}.tile_rows == kTileRows && OperatorSwitches{}.tile_cols == kTileCols, "slq_switches.hpp: tile defaults");
+static_assert(seq::kMaxFusedR == kFusedMaxR && seq::kMaxRingR == kRingMaxR, "slq_sequence.hpp: the constants of slq_common.hpp");
+static_assert(PlanSwitches{}.debug_pass == PASS_ADOTS, "slq_switches.hpp: SLQ_DEBUG_PASS");
 // the edge recurrence's certificate: a step adds kOmegaC eps_F ||A||_inf to the noise radius (8x the largest
 // one-step innovation the verify mode has seen on the device, and not less than 1); a zero is certified below orth_tol / kOmegaKappa
 constexpr double kOmegaC = 3.5;
@@ -293,21 +268,17 @@ constexpr double kOmegaKappa = 4.0;
 constexpr double kTileMaxColsPerRow = 4.5;      // tiles are kept when a tile row needs at most this many distinct panel rows
 constexpr double kTileAlphaColsPerRow = 2.6;    // upper-triangle tiles: the alpha-only pass takes the ring up to this many landed rows per row (r03: 7-point grids too)
 constexpr double kTileAlphaMergedColsPerRow = 2.6;  // ... and on the merged tiles of narrow panels up to this many (of the unmerged tiles)
+static_assert(PlanSwitches{}.ring_alpha_max_x100 == (int)(100 * kTileAlphaColsPerRow), "slq_switches.hpp: SLQ_RING_ALPHA_MAX_X100");
 constexpr double kTileLevelRows = 320.0;        // level sets the tile sweep's base order should not exceed (csr_create_impl)
 
-static int env_int(const char *name, int dflt) {
-  const char *s = getenv(name);
-  return (s && *s) ? atoi(s) : dflt;
-}
-static int tiles_mode() { return env_int("SLQ_TILES", kTilesDefault); }
 
 // Host-side work of an operator's creation (row orders, clusters, tile lists, streams) is cut into independent pieces -
 // XCD chunks, tile ranges, row ranges - and run on a few threads: fn(piece, begin, end) over [0, count). Results never depend
 // on the number of threads (every piece writes its own slots or its own buffer, joined in piece order). SLQ_HOST_THREADS
-// overrides the default of min(16, hardware threads). Exceptions do not leave a worker: the first failure is reported.
+// overrides the default of min(16, hardware threads); it is the one switch read where it is used. Exceptions do not leave a worker: the first failure is reported.
 static int host_threads() {
   const int hw = (int)std::thread::hardware_concurrency();
-  return std::max(1, std::min(64, env_int("SLQ_HOST_THREADS", std::max(1, std::min(16, hw)))));
+  return std::max(1, std::min(64, or_auto(read_host_threads(), std::max(1, std::min(16, hw)))));
 }
 template <typename Fn> static bool parallel_pieces(int pieces, int64_t count, Fn fn) {
   pieces = (int)std::max<int64_t>(1, std::min<int64_t>(pieces, count));
@@ -335,7 +306,8 @@ template <typename Fn> static bool parallel_pieces(int pieces, int64_t count, Fn
 
 // wall time of the phases of an operator's creation, printed under SLQ_DEBUG (scripts/time_create.py)
 struct PhaseClock {
-  bool on = env_int("SLQ_DEBUG", 0) != 0;
+  bool on;
+  explicit PhaseClock(const OperatorSwitches &sw) : on(sw.debug != 0) {}
   std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now(), t0 = t;
   void total(const char *what) {
     if (on) fprintf(stderr, "[slq] create: %-34s %7.1f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
@@ -626,11 +598,11 @@ static void xcd_rcm_permutation(int64_t n, const int32_t *rowptr, const int32_t 
 // every chunk. Returns false when a single row already needs more than kTileCols indices (no tiling for this operator).
 // *lines_total (if not null): the sum over the clusters of their distinct indices (rows and columns) - the panel rows a sweep of the tiles lands.
 static bool build_clusters(int64_t n, const int32_t *rowptr, const int32_t *colind, const int32_t *order_in, const int32_t *inv_in,
-                           std::vector<int32_t> &order_out, std::vector<int32_t> &tile_row, int32_t xcd_tile[9], int64_t *lines_total = nullptr) {
+                           std::vector<int32_t> &order_out, std::vector<int32_t> &tile_row, int32_t xcd_tile[9], const OperatorSwitches &osw, int64_t *lines_total = nullptr) {
   const int64_t chunk = (n + 7) / 8;
-  const bool ringed = tiles_mode() == 2;  // tiles of the ring-fed kernel (k_csr_ring_pass): smaller, fixed caps
-  const int tmax = ringed ? kRingTileRows : std::max(1, std::min(env_int("SLQ_TILE_ROWS", kTileRows), 64));
-  const int dcap = ringed ? kRingTileCols : std::max(8, std::min(env_int("SLQ_TILE_COLS", kTileCols), kTileCols));
+  const bool ringed = osw.tiles == 2;  // tiles of the ring-fed kernel (k_csr_ring_pass): smaller, fixed caps
+  const int tmax = ringed ? kRingTileRows : std::max(1, std::min(osw.tile_rows, 64));
+  const int dcap = ringed ? kRingTileCols : std::max(8, std::min(osw.tile_cols, kTileCols));
   const int nzcap = ringed ? kRingTileNnz : std::numeric_limits<int>::max();  // the ring kernel's tile record is bounded
   // The chunks are independent (a cluster never leaves its chunk): one worker each, with its own order, its own tile
   // boundaries (counted from the chunk's first row) and its own stamp array; `assigned` is shared, but a worker reads and
@@ -791,13 +763,13 @@ static double sample_tile_quality(int64_t n, const int32_t *rowptr, const int32_
 // says otherwise), per nonzero the position of its column in that list, per row the position of the row itself.
 static void build_tile_meta(int64_t n, const int32_t *rowptr, const int32_t *colind, const std::vector<int32_t> &tile_row,
                             std::vector<int32_t> &tile_ptr, std::vector<int32_t> &tile_cols, std::vector<int32_t> &lcol,
-                            std::vector<int32_t> &self_idx, int *max_cols) {
+                            std::vector<int32_t> &self_idx, int *max_cols, const OperatorSwitches &osw) {
   const size_t ntiles = tile_row.size() - 1;
   tile_ptr.assign(ntiles + 1, 0);
   tile_cols.clear();
   lcol.assign((size_t)rowptr[n] + kCsrPad, 0);
   self_idx.assign((size_t)n, 0);
-  const int line_order = env_int("SLQ_RING_ORDER", 0);
+  const int line_order = osw.ring_order;
   const int pieces = host_threads();
   std::vector<std::vector<int32_t>> local((size_t)pieces);  // every piece's lists, in tile order
   std::vector<int> mx_piece((size_t)pieces, 0);
@@ -1227,7 +1199,8 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
   if (!rowptr || (nnz > 0 && (!colind || (!vals && !dev.va)))) return fail(SLQ_EINVAL, "CSR arrays are NULL");
   if (rowptr[0] != 0 || rowptr[n] != nnz)
     return fail(SLQ_EINVAL, "rowptr[0] must be 0 and rowptr[n] must equal nnz");
-  PhaseClock clk;
+  const OperatorSwitches osw = read_operator_switches();  // (the one read of this creation: everything below, and the operator, keep these values)
+  PhaseClock clk(osw);
   std::vector<char> vals_back;  // the values of a device-resident CSR, fetched when the host needs them
   auto need_host_vals = [&]() -> hipError_t {
     if (vals || nnz == 0) return hipSuccess;
@@ -1257,6 +1230,7 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
   if (!op) return fail(SLQ_ENOMEM, "host allocation failed");
   ctx_retain(ctx);
   *op = slq_operator{ctx, OP_CSR, dtype, n, nnz, nullptr, nullptr, nullptr, 0, true, nullptr, nullptr, nullptr, nullptr, TileMeta{}};
+  op->sw = osw;
   // whatever way this function is left without handing `op` out - an error return below or an exception of the host-side
   // analysis - the operator and what it owns on the device go with it (declared before the upload queue: that one joins first)
   struct OpGuard {
@@ -1276,7 +1250,7 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
   // 126^3: 8486) whose natural-order halo no longer fits any cache level it is 9-12 % FASTER. Automatic
   // mode therefore reorders only when the rms index distance exceeds 2048 rows AND the permutation cuts
   // it to 60 % or less (random graphs gain nothing and are left alone).
-  const int reorder_mode = plain ? 0 : env_int("SLQ_REORDER", -1);
+  const int reorder_mode = plain ? 0 : osw.reorder;
   // rms index distance of the nonzeros whose two ends lie in the same XCD chunk (links that cross
   // chunks are served by another XCD's L2 whatever the order inside the chunks)
   const int64_t rchunk = (n + 7) / 8;
@@ -1305,38 +1279,38 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
     for (int t = 0; t < pieces; ++t) a += acc[(size_t)t], c += cnt[(size_t)t];  // (piece order: the same value whatever the timing)
     return std::sqrt(a / (double)std::max<int64_t>(c, 1));
   };
-  // Workgroup tiles (SLQ_TILES, tiles_mode()): the rows are regrouped into compact clusters = the tiles of k_csr_tile_pass /
+  // Workgroup tiles (SLQ_TILES): the rows are regrouped into compact clusters = the tiles of k_csr_tile_pass /
   // k_csr_ring_pass, on top of a base order. Kept only if the tiles actually share rows: at most kTileMaxColsPerRow distinct
   // panel rows per tile row (5-point grid: 2.1, 7-point grid: 3.9 with the ring kernel's 36-row images, random graph: 10+).
   // Unasked (SLQ_TILES unset) only operators of 65536 rows and more are tried - below that a pass is launch-bound anyway.
-  const int tmode = plain ? 0 : tiles_mode();
-  const bool tiles_forced = getenv("SLQ_TILES") != nullptr;
+  const int tmode = plain ? 0 : osw.tiles;
+  const bool tiles_forced = osw.tiles_forced;
   bool try_tiles = tmode != 0 && nnz > 0 && n >= (tiles_forced ? 4096 : 65536);
   if (try_tiles) {
     // (a sample cluster grows on the caller's numbering, the real ones on the reordered chunk: 4.3 against 3.9 on a 7-point grid,
     // 2.3 against 2.1 on a 5-point one, 12-16 on the operators this is meant to turn away. 25 % of margin keeps it a filter for
     // those only)
     const bool ringed = tmode == 2;
-    const double q = sample_tile_quality(n, rowptr, colind, ringed ? kRingTileRows : std::max(1, std::min(env_int("SLQ_TILE_ROWS", kTileRows), 64)),
-                                         ringed ? kRingTileCols : std::max(8, std::min(env_int("SLQ_TILE_COLS", kTileCols), kTileCols)),
+    const double q = sample_tile_quality(n, rowptr, colind, ringed ? kRingTileRows : std::max(1, std::min(osw.tile_rows, 64)),
+                                         ringed ? kRingTileCols : std::max(8, std::min(osw.tile_cols, kTileCols)),
                                          ringed ? kRingTileNnz : std::numeric_limits<int>::max());
-    if (env_int("SLQ_DEBUG", 0) != 0) fprintf(stderr, "[slq] tiles: sample of 256 clusters: %.2f distinct panel rows per row\n", q);
+    if (osw.debug != 0) fprintf(stderr, "[slq] tiles: sample of 256 clusters: %.2f distinct panel rows per row\n", q);
     if (q > 1.25 * kTileMaxColsPerRow) try_tiles = false;
   }
   clk.lap("tile sample");
   // SLQ_DEVICE_BUILD (r04, slq_build.hpp): 1 (default) - an operator that gets ring-sized tiles has its stored CSR, upper triangle and
   // tile streams built on the device from the caller's CSR, which starts its way up now, while the host orders and clusters the rows;
   // 0 - everything on the host, as before; 2 - both, compared array by array (tests)
-  const int dev_mode = (plain || host_build) ? 0 : env_int("SLQ_DEVICE_BUILD", 1);
+  const int dev_mode = (plain || host_build) ? 0 : osw.device_build;
   DevBuf o_rp, o_ci, o_va;       // the caller's CSR on the device (scratch of the build)
   UploadQueue early(ctx->device);  // (declared after what it fills: joined first)
   bool early_started = false;
   const int32_t *src_rp = nullptr, *src_ci = nullptr;  // where the device-side build reads the caller's CSR
   const void *src_va = nullptr;
-  if (dev_mode != 0 && try_tiles && tmode == 2 && reorder_mode != 0 && env_int("SLQ_RING_ORDER", 0) == 0 && dev.va) {
+  if (dev_mode != 0 && try_tiles && tmode == 2 && reorder_mode != 0 && osw.ring_order == 0 && dev.va) {
     src_rp = dev.rp, src_ci = dev.ci, src_va = dev.va;  // in place (slq_csr_create_device)
     early_started = true;
-  } else if (dev_mode != 0 && try_tiles && tmode == 2 && reorder_mode != 0 && env_int("SLQ_RING_ORDER", 0) == 0) {
+  } else if (dev_mode != 0 && try_tiles && tmode == 2 && reorder_mode != 0 && osw.ring_order == 0) {
     hipError_t ee = o_rp.alloc((size_t)(n + 1) * 4);
     if (ee == hipSuccess) ee = o_ci.alloc((size_t)nnz * 4);
     if (ee == hipSuccess) ee = o_va.alloc((size_t)nnz * esize(dtype));
@@ -1357,10 +1331,10 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
       for (int64_t i = 0; i < n; ++i) inv0[(size_t)(*base)[(size_t)i]] = (int32_t)i;
     }
     int64_t dsum = 0;  // distinct indices (rows and columns) summed over the tiles: the clusters count them as they grow
-    if (!build_clusters(n, rowptr, colind, base ? base->data() : nullptr, base ? inv0.data() : nullptr, order, tile_row, xcd_tile, &dsum)) return false;
+    if (!build_clusters(n, rowptr, colind, base ? base->data() : nullptr, base ? inv0.data() : nullptr, order, tile_row, xcd_tile, osw, &dsum)) return false;
     clk.lap("  clusters");
     const double per_row = (double)dsum / (double)n;
-    if (env_int("SLQ_DEBUG", 0) != 0)
+    if (osw.debug != 0)
       fprintf(stderr, "[slq] tiles: %zu clusters, %.2f rows each, %.2f distinct panel rows per row (limit %.1f)\n", tile_row.size() - 1,
               (double)n / (double)(tile_row.size() - 1), per_row, tile_limit);
     return per_row <= tile_limit;
@@ -1372,7 +1346,7 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
     return true;
   };
   std::vector<int32_t> rcm_perm;  // the in-chunk Cuthill-McKee order, computed at most once
-  const int sub_env = env_int("SLQ_RCM_SUB", 0);  // 0: 1 piece, except for the tile sweep below
+  const int sub_env = osw.rcm_sub;  // 0: 1 piece, except for the tile sweep below
   auto rcm_order = [&]() -> const std::vector<int32_t> & {
     if (rcm_perm.empty()) xcd_rcm_permutation(n, rowptr, colind, rcm_perm, std::max(1, sub_env), nullptr);
     return rcm_perm;
@@ -1394,7 +1368,7 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
         if (k == 4) level1 = rcm_perm;
         xcd_rcm_permutation(n, rowptr, colind, rcm_perm, k, &w, k > 1 ? &level1 : nullptr);
         clk.lap("  Cuthill-McKee in the chunks");
-        if (env_int("SLQ_DEBUG", 0) != 0) fprintf(stderr, "[slq] tiles: %d piece(s) per chunk: level sets of %.0f rows on average\n", k, w);
+        if (osw.debug != 0) fprintf(stderr, "[slq] tiles: %d piece(s) per chunk: level sets of %.0f rows on average\n", k, w);
         if (w <= kTileLevelRows) break;
       }
     }
@@ -1453,7 +1427,7 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
       if (rr != SLQ_OK) return rr;
       const int diff = operators_differ(op, ref);
       slq_operator_destroy(ref);
-      if (diff) return fail(SLQ_EHIP, "SLQ_DEVICE_BUILD=2: the device-built operator differs from the host-built one (item %d)", diff);
+      if (diff) return fail(SLQ_EHIP, "the device-built operator differs from the host-built one (SLQ_DEVICE_BUILD=2, item %d)", diff);
     }
     clk.total("all of slq_csr_create");
     guard.op = nullptr;
@@ -1542,7 +1516,7 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
     for (int64_t f : farp) far += f;
     op->far_per_row = (double)far / (double)n;
   }
-  if (env_int("SLQ_DEBUG", 0) != 0)
+  if (osw.debug != 0)
     fprintf(stderr, "[slq] csr n=%lld nnz=%lld reordered=%d rms in-chunk |i-j| = %.1f, far gathers per row %.2f\n", (long long)n,
             (long long)nnz, op->perm_h ? 1 : 0, op->rms_dist, op->far_per_row);
   clk.lap("far count");
@@ -1551,7 +1525,7 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
   // panel rows. Built only when the stored CSR is EXACTLY symmetric (pattern and values, sorted rows
   // without duplicates); anything else keeps the full rows. SLQ_SYM_ALPHA=0 disables it.
   bool sym = false;
-  if (!plain && env_int("SLQ_SYM_ALPHA", 1) != 0 && nnz > 0) {
+  if (!plain && osw.sym_alpha != 0 && nnz > 0) {
     sym = dtype == SLQ_F64 ? build_symmetric_upper<double>(n, rowptr, colind, (const double *)vals, urp, uci, uva)
                                 : build_symmetric_upper<float>(n, rowptr, colind, (const float *)vals, urp, uci, uva);
     if (sym) {
@@ -1570,11 +1544,11 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
   // workgroup tiles (SLQ_TILES): lists of the stored CSR, uploaded next to it
   if (have_tiles) {
     int mx = 0;
-    build_tile_meta(n, rowptr, colind, tile_row, tp, tc, lc, si, &mx);
+    build_tile_meta(n, rowptr, colind, tile_row, tp, tc, lc, si, &mx, osw);
     clk.lap("  tile lists");
     int32_t *d_tr = nullptr, *d_tp = nullptr, *d_tc = nullptr, *d_lc = nullptr, *d_si = nullptr;
     // (the per-nonzero lists are read by k_csr_tile_pass only: ring-sized tiles carry them inside their records instead)
-    const bool lists_on_device = tiles_mode() != 2;
+    const bool lists_on_device = osw.tiles != 2;
     hipError_t te = hipMalloc((void **)&d_tr, tile_row.size() * 4);
     if (te == hipSuccess) te = hipMalloc((void **)&d_tp, tp.size() * 4);
     if (te == hipSuccess && lists_on_device) te = hipMalloc((void **)&d_tc, tc.size() * 4);
@@ -1596,7 +1570,7 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
     }
     for (int x = 0; x < 9; ++x) op->tiles.xcd_tile[x] = xcd_tile[x];
     op->tiles.max_cols = mx;
-    op->tiles_ringed = tiles_mode() == 2;
+    op->tiles_ringed = osw.tiles == 2;
     if (op->tiles_ringed) op->merged_lock = new (std::nothrow) std::mutex();
     if (te == hipSuccess && op->tiles_ringed) {
       if (dtype == SLQ_F64) build_ring_stream<double>(1, rowptr, (const double *)vals, tile_row, tp, tc, lc, si, desc, rec);
@@ -1614,29 +1588,29 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
         std::vector<int32_t> tile_row_u;
         // (not where the base tiles are as tall as a tile gets - a 5-point grid's 13.9 of 14 rows: nothing to join, 10-20 ms of host time saved)
         const bool tall_already = (double)n / (double)(tile_row.size() - 1) > 0.8 * kRingTileRows;
-        if (env_int("SLQ_RING_UPPER_REGROUP", 1) != 0 && !tall_already) {
+        if (osw.ring_upper_regroup != 0 && !tall_already) {
           regroup_upper_tiles(urp.data(), uci.data(), tile_row, xcd_tile, tile_row_u, op->xcd_tile_u);
         } else {
           tile_row_u = tile_row;
           for (int x = 0; x < 9; ++x) op->xcd_tile_u[x] = xcd_tile[x];
         }
-        if (env_int("SLQ_DEBUG", 0) != 0)
+        if (osw.debug != 0)
           fprintf(stderr, "[slq] tiles: upper-triangle stream on %zu tiles of %.2f rows (base: %zu of %.2f)\n", tile_row_u.size() - 1, (double)n / (double)(tile_row_u.size() - 1),
                   tile_row.size() - 1, (double)n / (double)(tile_row.size() - 1));
-        build_tile_meta(n, urp.data(), uci.data(), tile_row_u, tpu, tcu, lcu, siu, &mxu);
+        build_tile_meta(n, urp.data(), uci.data(), tile_row_u, tpu, tcu, lcu, siu, &mxu, osw);
         clk.lap("  upper tile lists");
         // Worth it while the tiles land at most kTileAlphaColsPerRow panel rows per row (r03, scalar-descriptor loaders and the
         // padded-row consumer of slq_ring.hpp: 5-point grid, 1.5 rows per row: 0.40 against 0.51 ms for the generic pass; 7-point
         // grid, 2.5: 0.66 against 0.81 ms)
         const double upper_per_row = (double)(tcu.size() - kCsrPad) / (double)n;
-        if (env_int("SLQ_DEBUG", 0) != 0) fprintf(stderr, "[slq] tiles: upper triangle: %.2f distinct panel rows per row, longest list %d (full rows: %d)\n", upper_per_row, mxu, mx);
+        if (osw.debug != 0) fprintf(stderr, "[slq] tiles: upper triangle: %.2f distinct panel rows per row, longest list %d (full rows: %d)\n", upper_per_row, mxu, mx);
         op->tile_max_lines_u = mxu;
         op->upper_per_row = upper_per_row;
         // (built up to kTileAlphaMergedColsPerRow: wide panels take it up to kTileAlphaColsPerRow, slq_plan_create; the merged
         // tiles of narrow panels share more of their halo and gain from it on 7-point grids too - 100^3, 64 probes: alpha pass
         // 0.25 against 0.35 ms for the generic upper-triangle pass)
         if (upper_per_row <= kTileAlphaMergedColsPerRow) {
-          bool pad = env_int("SLQ_RING_PAD_ROWS", 1) != 0;
+          bool pad = osw.ring_pad_rows != 0;
           if (dtype == SLQ_F64) build_ring_stream<double>(1, urp.data(), (const double *)uva.data(), tile_row_u, tpu, tcu, lcu, siu, desc_u, rec_u, &pad);
           else build_ring_stream<float>(1, urp.data(), (const float *)uva.data(), tile_row_u, tpu, tcu, lcu, siu, desc_u, rec_u, &pad);
           op->tile_u_padded = pad;
@@ -1679,9 +1653,10 @@ static int csr_finish_on_device(slq_context *ctx, slq_operator *op, int dtype, i
     const int32_t o = perm[(size_t)i];
     rp2[(size_t)i + 1] = rp2[(size_t)i] + (rowptr0[o + 1] - rowptr0[o]);
   }
-  const bool want_sym = env_int("SLQ_SYM_ALPHA", 1) != 0;
+  const OperatorSwitches &osw = op->sw;
+  const bool want_sym = osw.sym_alpha != 0;
   const bool tall_already = (double)n / (double)ntiles > 0.8 * kRingTileRows;
-  const bool regroup = want_sym && env_int("SLQ_RING_UPPER_REGROUP", 1) != 0 && !tall_already;
+  const bool regroup = want_sym && osw.ring_upper_regroup != 0 && !tall_already;
   std::vector<int32_t> tile_row_u;
   int32_t xcd_u[9];
   for (int x = 0; x < 9; ++x) xcd_u[x] = xcd_tile[x];
@@ -1775,7 +1750,7 @@ static int csr_finish_on_device(slq_context *ctx, slq_operator *op, int dtype, i
     if (dtype == SLQ_F64) slqb::k_upper_fill<double><<<grow, brow, 0, st>>>((int)n, op->rowptr, op->colind, (const double *)op->vals, op->rowptr_u, op->colind_u, (double *)op->vals_u);
     else slqb::k_upper_fill<float><<<grow, brow, 0, st>>>((int)n, op->rowptr, op->colind, (const float *)op->vals, op->rowptr_u, op->colind_u, (float *)op->vals_u);
   }
-  if (env_int("SLQ_DEBUG", 0) != 0)
+  if (osw.debug != 0)
     fprintf(stderr, "[slq] csr n=%lld nnz=%lld reordered=1 rms in-chunk |i-j| = %.1f, far gathers per row %.2f (built on the device)\n", (long long)n, (long long)nnz,
             op->rms_dist, op->far_per_row);
   clk.lap("  device: stored CSR, upper triangle");
@@ -1797,19 +1772,19 @@ static int csr_finish_on_device(slq_context *ctx, slq_operator *op, int dtype, i
     if (!regroup) tile_row_u = tile_row;
     for (int x = 0; x < 9; ++x) op->xcd_tile_u[x] = xcd_u[x];
     const int ntu = (int)tile_row_u.size() - 1;
-    if (env_int("SLQ_DEBUG", 0) != 0)
+    if (osw.debug != 0)
       fprintf(stderr, "[slq] tiles: upper-triangle stream on %d tiles of %.2f rows (base: %d of %.2f)\n", ntu, (double)n / (double)ntu, ntiles, (double)n / (double)ntiles);
     DevBuf d_tru;
     e = d_tru.alloc(tile_row_u.size() * 4);
     if (e == hipSuccess) e = hipMemcpy(d_tru.p, tile_row_u.data(), tile_row_u.size() * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess) return hip_fail("upper-triangle tiles", e);
     DeviceStream us;
-    rc = device_build_stream(ctx, dtype, 1, n, op->rowptr_u, op->colind_u, op->vals_u, d_tru.as<int32_t>(), ntu, env_int("SLQ_RING_PAD_ROWS", 1) != 0,
+    rc = device_build_stream(ctx, dtype, 1, n, op->rowptr_u, op->colind_u, op->vals_u, d_tru.as<int32_t>(), ntu, osw.ring_pad_rows != 0,
                              kTileAlphaMergedColsPerRow, false, us);
     if (rc < 0) return rc;
     op->tile_max_lines_u = us.max_lines;
     op->upper_per_row = (double)us.sum_lines / (double)n;
-    if (env_int("SLQ_DEBUG", 0) != 0)
+    if (osw.debug != 0)
       fprintf(stderr, "[slq] tiles: upper triangle: %.2f distinct panel rows per row, longest list %d (full rows: %d)\n", op->upper_per_row, us.max_lines, full.max_lines);
     if (rc == 0) {
       op->tile_desc_u = us.desc, op->tile_rec_u = us.rec;
@@ -1913,6 +1888,7 @@ extern "C" int slq_csr_gram_create(slq_context *ctx, int dtype, int64_t mrows, i
   if (!op) return fail(SLQ_ENOMEM, "host allocation failed");
   ctx_retain(ctx);
   *op = slq_operator{ctx, OP_GRAM, dtype, ncols, nnz, nullptr, nullptr, nullptr, 0, true, nullptr, nullptr, nullptr, nullptr, TileMeta{}};
+  op->sw = read_operator_switches();
   op->mrows = mrows;
   const size_t es = esize(dtype);
   // transpose on the host (counting sort by column; rows of A^T come out with ascending indices)
@@ -2043,6 +2019,7 @@ extern "C" int slq_dense_create(slq_context *ctx, int dtype, int64_t n, const vo
   if (!op) return fail(SLQ_ENOMEM, "host allocation failed");
   ctx_retain(ctx);
   *op = slq_operator{ctx, OP_DENSE, dtype, n, n * n, nullptr, nullptr, nullptr, n, true, nullptr, nullptr, nullptr, nullptr, TileMeta{}};
+  op->sw = read_operator_switches();
   const size_t es = esize(dtype);
   // Y = A X for whatever is given (eigen_operators.h:24-30 does not ask for symmetry either). k_dense_mfma_3term reads
   // A(row, k) and is right for any A; k_dense_panel walks row `row` of A as the contiguous COLUMN `row`, which is A^T:
@@ -2095,6 +2072,7 @@ extern "C" int slq_callback_create(slq_context *ctx, int dtype, int64_t n, slq_m
   if (!op) return fail(SLQ_ENOMEM, "host allocation failed");
   ctx_retain(ctx);
   *op = slq_operator{ctx, OP_CALLBACK, dtype, n, 0, nullptr, nullptr, nullptr, 0, false, fn, user, nullptr, nullptr, TileMeta{}};
+  op->sw = read_operator_switches();
   *out = op;
   return SLQ_OK;
 }
@@ -2110,6 +2088,7 @@ extern "C" int slq_device_callback_create(slq_context *ctx, int dtype, int64_t n
   if (!op) return fail(SLQ_ENOMEM, "host allocation failed");
   ctx_retain(ctx);
   *op = slq_operator{ctx, OP_DEVICE_CALLBACK, dtype, n, 0, nullptr, nullptr, nullptr, 0, false, nullptr, user, nullptr, nullptr, TileMeta{}};
+  op->sw = read_operator_switches();
   op->dev_fn = fn;
   *out = op;
   return SLQ_OK;
@@ -2202,7 +2181,7 @@ static bool ensure_ring_stream(slq_operator *op, int R) {
         RawBuf<int32_t> desc;
         RawBuf<char> rec;
         int mx = 0;
-        build_tile_meta(n, rowptr, colind, mrow, tp, tc, lc, si, &mx);
+        build_tile_meta(n, rowptr, colind, mrow, tp, tc, lc, si, &mx, op->sw);
         *max_lines = mx;
         if (mx > kRingTileCols * R) return false;  // (cannot happen: a union of R lists of <= 36)
         if (op->dtype == SLQ_F64) build_ring_stream<double>(R, rowptr, (const double *)vals, mrow, tp, tc, lc, si, desc, rec, pad);
@@ -2216,7 +2195,7 @@ static bool ensure_ring_stream(slq_operator *op, int R) {
       bool ok = upload(rp.data(), ci.data(), va.data(), &mm.desc, &mm.rec, &mm.max_lines, nullptr, sizes);
       if (ok && op->tile_desc_u && op->rowptr_u) {
         const size_t nu = (size_t)op->nnz_u;
-        bool upad = env_int("SLQ_RING_PAD_ROWS", 1) != 0;
+        bool upad = op->sw.ring_pad_rows != 0;
         std::vector<int32_t> urp((size_t)n + 1), uci(nu);
         std::vector<char> uva(nu * es);
         ok = hipMemcpy(urp.data(), op->rowptr_u, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost) == hipSuccess &&
@@ -2242,7 +2221,7 @@ static bool ensure_ring_stream(slq_operator *op, int R) {
       dsz[0] = f.desc_bytes, dsz[1] = f.rec_bytes;
       if (op->tile_desc_u && op->rowptr_u) {
         DeviceStream g;
-        if (device_build_stream(op->ctx, op->dtype, R, n, op->rowptr_u, op->colind_u, op->vals_u, d_mrow.as<int32_t>(), nm, env_int("SLQ_RING_PAD_ROWS", 1) != 0, 0.0, false, g) != 0) {
+        if (device_build_stream(op->ctx, op->dtype, R, n, op->rowptr_u, op->colind_u, op->vals_u, d_mrow.as<int32_t>(), nm, op->sw.ring_pad_rows != 0, 0.0, false, g) != 0) {
           drop(mm);
           return false;
         }
@@ -2251,7 +2230,7 @@ static bool ensure_ring_stream(slq_operator *op, int R) {
       }
       return true;
     };
-    const int dev_mode = env_int("SLQ_RING_ORDER", 0) != 0 ? 0 : env_int("SLQ_DEVICE_BUILD", 1);
+    const int dev_mode = op->sw.ring_order != 0 ? 0 : op->sw.device_build;  // (as the operator was built)
     size_t hsz[4] = {0, 0, 0, 0};
     if (dev_mode == 0) return build_host(m, hsz);
     if (!build_device(m)) return false;
@@ -2293,11 +2272,11 @@ extern "C" int slq_operator_shape(const slq_operator *op, int64_t *nrows, int64_
 // ---------------------------------------------------------------------------------------------------
 // geometry + dispatch
 // ---------------------------------------------------------------------------------------------------
-static void choose_geometry(int dtype, int nprobes, int *LPR, int *PW, int *NP) {
+static void choose_geometry(const PlanSwitches &sw, int dtype, int nprobes, int *LPR, int *PW, int *NP) {
   const int V = dtype == SLQ_F64 ? 2 : 4;
   int lpr = 8;
   while (lpr < 64 && lpr * V < nprobes) lpr *= 2;
-  const int forced = env_int("SLQ_LPR", 0);
+  const int forced = sw.lpr;
   if (forced == 8 || forced == 16 || forced == 32 || forced == 64) lpr = forced;
   *LPR = lpr;
   *PW = lpr * V;
@@ -2450,14 +2429,14 @@ static int operator_norm_inf(slq_operator *op, double *out) {
   return SLQ_OK;
 }
 
-static void grid_sizes(int n, int LPR, int NP, int num_cus, int *nblkA, int *nblkS, int *nblkU, bool pipelined) {
+static void grid_sizes(const PlanSwitches &sw, int n, int LPR, int NP, int num_cus, int *nblkA, int *nblkS, int *nblkU, bool pipelined) {
   const int RPW = 64 / LPR;
   const int rows_per_block = kWaves * RPW;
   // Tunables: resident workgroups (kBlock threads) per CU, summed over the panels of a launch.
   // Defaults from the MI355X sweeps: in-place read-modify-write sweeps peak at
   // ~2 workgroups per CU (more concurrent writers lose 5-10 %); the SpMM likes 4-8.
-  const int per_cu_a = std::max(1, env_int("SLQ_BLOCKS_PER_CU_SPMM", env_int("SLQ_BLOCKS_PER_CU", 4)));
-  const int per_cu_s = std::max(1, env_int("SLQ_BLOCKS_PER_CU_STREAM", env_int("SLQ_BLOCKS_PER_CU", 2)));
+  const int per_cu_a = std::max(1, or_auto(sw.blocks_per_cu_spmm, or_auto(sw.blocks_per_cu, 4)));
+  const int per_cu_s = std::max(1, or_auto(sw.blocks_per_cu_stream, or_auto(sw.blocks_per_cu, 2)));
   // sweep A: a multiple of 8 blocks (XCD-aware chunking), no more than the rows can feed
   const int chunk = (n + 7) / 8;
   int per_xcd = std::min(std::max(8, num_cus * per_cu_a / NP) / 8, (chunk + rows_per_block - 1) / rows_per_block);
@@ -2467,7 +2446,7 @@ static void grid_sizes(int n, int LPR, int NP, int num_cus, int *nblkA, int *nbl
   // per panel. More rows in flight evict each other's gather halo
   // (dots pass, r = 3, per 30 launches: 36.3 ms at 2 resident, 41.3 at 3), and a grid that is not a multiple
   // of what is resident leaves a ragged last round. Panels run one after the other (panel-major dispatch).
-  const int per_cu_u = std::max(1, env_int("SLQ_BLOCKS_PER_CU_FUSED", pipelined ? 1 : 2));  // per panel; 1 with the pipelined row loop
+  const int per_cu_u = std::max(1, or_auto(sw.blocks_per_cu_fused, pipelined ? 1 : 2));  // per panel; 1 with the pipelined row loop
   int per_xcd_u = std::min(std::max(8, num_cus * per_cu_u) / 8, (chunk + rows_per_block - 1) / rows_per_block);
   *nblkU = 8 * std::max(per_xcd_u, 1);
   int s = std::min(std::max(1, num_cus * per_cu_s / NP), (n + rows_per_block - 1) / rows_per_block);
@@ -2481,7 +2460,7 @@ extern "C" int slq_plan_query_bytes(int dtype, int64_t n, int nprobes, int deg, 
   if (n <= 0 || nprobes <= 0) return fail(SLQ_EINVAL, "n and nprobes must be positive");
   SLQ_TRY(normalise_params(n, &deg, &orth));
   int LPR, PW, NP;
-  choose_geometry(dtype, nprobes, &LPR, &PW, &NP);
+  choose_geometry(read_plan_switches(), dtype, nprobes, &LPR, &PW, &NP);
   const size_t S = ring_slots(deg, orth, keep_basis);
   *bytes = S * (size_t)NP * (size_t)n * PW * esize(dtype);
   return SLQ_OK;
@@ -2493,7 +2472,7 @@ extern "C" int slq_plan_query_bytes(int dtype, int64_t n, int nprobes, int deg, 
 static int plan_bytes_on(const slq_operator *op, int nprobes, int deg, int orth, int keep_basis, size_t *bytes) {
   SLQ_TRY(slq_plan_query_bytes(op->dtype, op->n, nprobes, deg, orth, keep_basis, bytes));
   int LPR, PW, NP;
-  choose_geometry(op->dtype, nprobes, &LPR, &PW, &NP);
+  choose_geometry(read_plan_switches(), op->dtype, nprobes, &LPR, &PW, &NP);
   const size_t panel = (size_t)NP * PW * esize(op->dtype);
   if (op->kind != OP_CSR) {
     const bool big_tiles = op->kind == OP_DENSE && (op->dtype == SLQ_F32 || PW >= 32);  // K-split slabs of the MFMA dense kernels (<= 16)
@@ -2513,7 +2492,7 @@ extern "C" int slq_plan_query_bytes_recompute(int dtype, int64_t n, int nprobes,
   if (deg > n) deg = (int)n;
   if (orth < 0 || orth > deg) orth = deg;
   int LPR, PW, NP;
-  choose_geometry(dtype, nprobes, &LPR, &PW, &NP);
+  choose_geometry(read_plan_switches(), dtype, nprobes, &LPR, &PW, &NP);
   const size_t S = (size_t)recompute_ring_slots(deg, orth) + 2;  // + the stash of the probes and the output panel
   *bytes = S * (size_t)NP * (size_t)n * PW * esize(dtype);
   return SLQ_OK;
@@ -2564,6 +2543,7 @@ extern "C" int slq_plan_destroy(slq_plan *p) {
 static int set_kernel_attributes(slq_plan *p);
 
 static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, int basis_mode, slq_plan **out);
+static seq::SequenceFacts sequence_facts(const slq_plan *p);
 
 extern "C" int slq_plan_create(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth,
                                int keep_basis, slq_plan **out) {
@@ -2603,19 +2583,15 @@ static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int
   p->orth = orth;
   p->keep_basis = keep_basis != 0;
   p->esz = esize(op->dtype);
-  p->sw = Switches{env_int("SLQ_FUSED", 1), env_int("SLQ_NT", 1) != 0, env_int("SLQ_GRAPH", 1) != 0, env_int("SLQ_MGS", 0) != 0,
-                   env_int("SLQ_STORED_U", 1) != 0, env_int("SLQ_MERGED", 1) != 0, env_int("SLQ_CROSS", 1) != 0,
-                   tiles_mode() != 0, env_int("SLQ_RING_ALPHA", 2), env_int("SLQ_RING_REV", 1) != 0, env_int("SLQ_DENSE_MFMA", 1) != 0, env_int("SLQ_DENSE_TILE16", 0) != 0, env_int("SLQ_DENSE_LDS", 1) != 0, env_int("SLQ_PIPE", -1),
-                   env_int("SLQ_FUSED_LDS_PAD", -1), env_int("SLQ_SPMM_LDS_PAD", 57344), env_int("SLQ_DEFER_AXPY", 1) != 0,
-                   std::max(0, std::min(2, env_int("SLQ_OMEGA", 1))), env_int("SLQ_OMEGA_TRIP", -1), env_int("SLQ_OMEGA_RESCUE", -1)};
-  choose_geometry(op->dtype, nprobes, &p->LPR, &p->PW, &p->NP);
+  p->sw = read_plan_switches();  // (the one read of this plan: nothing below, and nothing the plan does later, looks at the environment)
+  choose_geometry(p->sw, op->dtype, nprobes, &p->LPR, &p->PW, &p->NP);
   p->bpad = p->NP * p->PW;
   p->basis_mode = basis_mode;
   p->S = basis_mode == 2 ? recompute_ring_slots(deg, orth) : ring_slots(deg, orth, p->keep_basis);
   p->acc_cols = basis_mode == 2 ? recompute_acc_cols(deg) : 0;
   p->v_slot = basis_mode == 2 ? p->S : 0;
   p->y_slot = basis_mode == 2 ? p->S + 1 : deg;
-  p->acc_skip = env_int("SLQ_ACC_SKIP", 1) != 0;
+  p->acc_skip = p->sw.acc_skip != 0;
   p->slot_stride = (int64_t)p->NP * p->n * p->PW;
   p->rmax = std::max(p->keep_basis ? deg : orth, 1);
   // Row loop of the dots/update passes (slq_kernels.hpp: k_csr_pass). Measured on configs[1] and on the 100^3 grid
@@ -2624,7 +2600,7 @@ static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int
   // 101.0 ms): what bounds both is the traffic a CU's vector-memory pipe has in flight, and the pipelined loop puts
   // the same bytes in flight with half the waves.
   p->pipelined = op->kind == OP_CSR && p->LPR == 64 && (p->sw.pipe >= 0 ? p->sw.pipe != 0 : (double)op->nnz / (double)std::max<int64_t>(op->n, 1) > 5.5);
-  grid_sizes(p->n, p->LPR, p->NP, ctx->num_cus, &p->nblkA, &p->nblkS, &p->nblkU, p->pipelined);
+  grid_sizes(p->sw, p->n, p->LPR, p->NP, ctx->num_cus, &p->nblkA, &p->nblkS, &p->nblkU, p->pipelined);
   {
     // Fused alpha pass: one read sweep plus the gathers. Two regimes, told apart by the
     // gathers per row of the matrix the pass walks (upper triangle when the operator is symmetric):
@@ -2636,20 +2612,19 @@ static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int
     //    from the XCD's L2: 2 resident per CU (LDS padding), 2 per CU *per panel*, panel after panel.
     const double gathers = op->kind != OP_CSR ? 0.0 : (double)(op->rowptr_u ? op->nnz_u : op->nnz) / (double)std::max<int64_t>(op->n, 1);
     const int local = op->kind == OP_CSR && gathers <= 3.2;
-    const int per_cu_env = env_int("SLQ_BLOCKS_PER_CU_ALPHA", 0);  // total over the panels
+    const int per_cu_env = p->sw.blocks_per_cu_alpha;  // total over the panels
     const int rows_per_block = kWaves * (64 / p->LPR);
     const int chunk = (p->n + 7) / 8;
     const int per_panel = per_cu_env > 0 ? std::max(8, ctx->num_cus * per_cu_env / p->NP)
                                          : (local ? std::max(8, ctx->num_cus * 4 / p->NP) : ctx->num_cus * 2);
     const int per_xcd = std::min(per_panel / 8, (chunk + rows_per_block - 1) / rows_per_block);
     p->nblkF = 8 * std::max(per_xcd, 1);
-    p->alpha_pad = (size_t)env_int("SLQ_ALPHA_LDS_PAD", (per_cu_env > 0 || local) ? 0 : 65536);
+    p->alpha_pad = (size_t)or_auto(p->sw.alpha_lds_pad, (per_cu_env > 0 || local) ? 0 : 65536);
   }
   {
     // which tile stream, if any (plan_tiled): wide panels take the tiles as clustered; panels of 32 / 16 lanes per row the
     // merged tiles of the narrow-panel ring kernel (built on first use; nontemporal streams only - the one form instantiated)
     p->ringR = 0;
-    p->ring_gen = p->ring_deep = p->gram = false;
     p->rs_desc = p->rs_desc_u = nullptr;
     p->rs_rec = p->rs_rec_u = nullptr;
     p->rs_u_padded = false;
@@ -2660,43 +2635,40 @@ static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int
         p->ringR = 1;
         if (op->tiles_ringed) {
           p->rs_desc = op->tile_desc, p->rs_rec = op->tile_rec;
-          if (op->tile_desc_u && op->upper_per_row <= (double)env_int("SLQ_RING_ALPHA_MAX_X100", (int)(100 * kTileAlphaColsPerRow)) / 100.0)
+          if (op->tile_desc_u && op->upper_per_row <= (double)p->sw.ring_alpha_max_x100 / 100.0)  // (default: kTileAlphaColsPerRow)
             p->rs_desc_u = op->tile_desc_u, p->rs_rec_u = op->tile_rec_u, p->rs_u_padded = op->tile_u_padded;
-          p->ring_gen = p->sw.nt && env_int("SLQ_RING_GEN", 1) != 0;
-          p->ring_deep = p->sw.nt && env_int("SLQ_RING_DEEP", 1) != 0;
         }
-      } else if ((p->LPR == 32 || p->LPR == 16) && op->tiles_ringed && p->sw.nt && env_int("SLQ_RING_NARROW", 1) != 0 &&
+      } else if ((p->LPR == 32 || p->LPR == 16) && op->tiles_ringed && p->sw.nt && p->sw.ring_narrow != 0 &&
                  ensure_ring_stream(op, 64 / p->LPR)) {
         const slq_operator::MergedStream &m = op->merged[p->LPR == 32 ? 0 : 1];
         p->ringR = 64 / p->LPR;
-        p->ring_gen = true;
-        p->ring_deep = env_int("SLQ_RING_DEEP", 1) != 0;
         p->rs_desc = m.desc, p->rs_rec = m.rec, p->rs_desc_u = m.desc_u, p->rs_rec_u = m.rec_u, p->rs_u_padded = m.u_padded;
         for (int x = 0; x < 9; ++x) p->rs_xcd[x] = m.xcd_tile[x], p->rs_xcd_u[x] = m.xcd_tile[x];  // (merged streams: one partition for both)
       }
       // alpha-only pass: LDS-DMA loaders everywhere since their r03 rewrite (merged tiles: a lane reads its lines' sources straight
       // out of the staged descriptor - 100^3, 64 probes 0.230 -> 0.187 ms against the register-staged loaders that had been the
       // faster form there, configs[1] 0.129 -> 0.113). SLQ_RING_STAGED=1 takes the loaders through registers (GEO 1) again.
-      p->ring_staged = env_int("SLQ_RING_STAGED", 0) != 0;
-      // the Gram sequence needs every step of the window on k_ring_pass (PASS_UPDATEG), i.e. the deep form too
-      // (and an EXACTLY symmetric operator: the sequence rewrites W_t . (A W_j) as (A W_t) . W_j - §4.6 - while the reference's recurrence never
-      // looks at symmetry, lanczos.h:127-136; rowptr_u is the record of that check. r04: r03 took the sequence on any tiled operator)
-      p->gram = p->ring_gen && p->ring_deep && p->sw.merged && !p->sw.mgs && op->rowptr_u != nullptr && env_int("SLQ_GRAM", 1) != 0;
+      p->ring_staged = p->sw.ring_staged != 0;
     }
   }
-  // the Gram sequence on the generic passes (no tiles, or a plan whose panels the tiles do not serve): the dots pass - a third to a half of every
+  // which form of the ring-fed passes, and which steps take the Gram sequence (derive_plan_flags, slq_sequence.hpp). The Gram sequence
+  // needs an EXACTLY symmetric operator: it rewrites W_t . (A W_j) as (A W_t) . W_j - §4.6 - while the reference's recurrence never looks
+  // at symmetry, lanczos.h:127-136; rowptr_u is the record of that check (r04: r03 took the sequence on any tiled operator).
+  // The Gram sequence on the generic passes (no tiles, or a plan whose panels the tiles do not serve): the dots pass - a third to a half of every
   // step's bytes - is gone there as well. Not for operators whose gathers are the cost (random graphs keep the stored-u sequence: it gathers once,
-  // the Gram sequence twice) - enqueue_run decides that per step exactly as before.
-  p->last_nostore = env_int("SLQ_LAST_STORE", 0) == 0;
-  p->sweep_skip = env_int("SLQ_SWEEP_SKIP", 1) != 0;
-  p->gram_csr = op->kind == OP_CSR && p->ringR == 0 && op->rowptr_u != nullptr && p->sw.merged && !p->sw.mgs && p->sw.nt && env_int("SLQ_GRAM", 1) != 0 && env_int("SLQ_GRAM_CSR", 1) != 0;
+  // the Gram sequence twice) - step_shape decides that per step.
+  {
+    const seq::SequenceFacts f = sequence_facts(p);  // (the derived flags depend on nothing that is set further down)
+    p->ring_gen = f.ring_gen, p->ring_deep = f.ring_deep, p->gram = f.gram, p->gram_csr = f.gram_csr, p->last_nostore = f.last_nostore;
+  }
+  p->sweep_skip = p->sw.sweep_skip != 0;
   {
     // tiled passes: as many workgroups resident per CU as their LDS images admit (2 x 72 KiB by default), the same number
     // per CU and panel in the grid, panel after panel
     const int img_kib = op->tiles.tile_ptr ? (op->tiles.max_cols + 16) * (SLQ_TILE_DB ? 2 : 1) : 160;
-    const int per_cu_t = op->tiles_ringed ? 1 : std::max(1, env_int("SLQ_BLOCKS_PER_CU_TILED", std::max(1, std::min(4, 160 / std::max(img_kib, 1)))));
+    const int per_cu_t = op->tiles_ringed ? 1 : std::max(1, or_auto(p->sw.blocks_per_cu_tiled, std::max(1, std::min(4, 160 / std::max(img_kib, 1)))));
     int per_xcd_t = std::max(1, ctx->num_cus * per_cu_t / 8);
-    per_xcd_t = std::max(1, std::min(per_xcd_t, env_int("SLQ_TILED_WGS_PER_XCD", per_xcd_t)));  // (experiments: fewer CUs sweeping a chunk)
+    per_xcd_t = std::max(1, std::min(per_xcd_t, or_auto(p->sw.tiled_wgs_per_xcd, per_xcd_t)));  // (experiments: fewer CUs sweeping a chunk)
     if (op->tiles.tile_ptr) {
       int mn = 1 << 30;
       for (int x = 0; x < 8; ++x) mn = std::min(mn, std::max(1, p->rs_xcd[x + 1] - p->rs_xcd[x]));
@@ -2745,7 +2717,7 @@ static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int
     const int rw = dense32 ? kDense32BM : 32 * (kWaves / (p->PW >= 64 ? 2 : 1));
     const double wgs = (double)((p->n + rw - 1) / rw) * p->NP;
     double best = 1e30;
-    const int forced = env_int("SLQ_DENSE_KSPLIT", 0);
+    const int forced = p->sw.dense_ksplit;
     for (int ks = 1; ks <= 16; ++ks) {
       const double cost = std::ceil(wgs * ks / ctx->num_cus) / ks + 0.005 * ks;
       if ((forced > 0 && ks == forced) || (forced <= 0 && cost < best - 1e-12)) { best = cost; p->dense_ks = ks; }
@@ -3011,21 +2983,13 @@ extern "C" int slq_debug_plan_poke_ring_flag(slq_plan *p, int value) {
   return SLQ_OK;
 }
 
-// which launch sequence the steps with r <= kFusedMaxR take (enqueue_run): 0 sweeps, 1 recompute passes, 2 stored u
-static int plan_sequence(const slq_plan *p) {
-  const slq_operator *op = p->op;
-  if (op->kind != OP_CSR || p->sw.fused == 0 || p->sw.mgs || p->nstale > 0) return 0;
-  if (p->sw.fused == 2 || op->far_per_row <= 4.0) return (((p->gram && plan_tiled(p)) || p->gram_csr) && p->orth >= 1) ? 4 : 1;
-  return (p->orth >= 1 && p->sw.stored_u && p->sw.merged && !plan_tiled(p)) ? 2 : 0;
-}
-
 extern "C" int slq_plan_describe(const slq_plan *p, slq_plan_info *out) {
   if (!p || !out) return fail(SLQ_EINVAL, "plan/out is NULL");
   memset(out, 0, sizeof(*out));  // (and the retired trailing field stays 0: include/slq.h)
   out->panel_width = p->PW;
   out->panels = p->NP;
   out->ring_slots = p->S;
-  out->sequence = plan_sequence(p);
+  out->sequence = seq::plan_sequence_of(sequence_facts(p));
   out->pipelined = p->pipelined ? 1 : 0;
   out->reordered = p->op->perm_d ? 1 : 0;
   out->upper_alpha = p->op->rowptr_u ? 1 : 0;
@@ -3205,7 +3169,7 @@ extern "C" int slq_plan_set_probes(slq_plan *p, const void *X, int64_t ldx) {
   // into one of two pinned buffers (32 MiB chunks) and sent from there; the copy of chunk i + 1 overlaps the transfer
   // and the transposition kernel of chunk i. SLQ_PINNED_UPLOAD=0 keeps the direct copy.
   const size_t col_bytes = (size_t)p->n * p->esz;
-  const bool pinned = env_int("SLQ_PINNED_UPLOAD", 1) != 0 && (size_t)p->nprobes * col_bytes >= ((size_t)4 << 20);
+  const bool pinned = p->sw.pinned_upload != 0 && (size_t)p->nprobes * col_bytes >= ((size_t)4 << 20);
   int cc = stage_chunk_cols(p);
   if (pinned) cc = (int)std::max<size_t>(1, std::min<size_t>((size_t)cc, ((size_t)32 << 20) / col_bytes));
   const bool use_pin = pinned && ensure_pinned(ctx, (size_t)cc * col_bytes);
@@ -3263,7 +3227,7 @@ extern "C" int slq_plan_generate_probes(slq_plan *p, int pdf, uint64_t seed, uin
                     (k_gen_probes<F, L><<<g, dim3(256), 0, st>>>(p->n,
                                         (F *)slot_ptr(p, 0), pdf, seed, probe_offset, p->nprobes, p->op->inv_perm_d))));
   p->pdf_sphere = (pdf == SLQ_PDF_SPHERE);
-  return init_from_probes(p, p->pdf_sphere, pdf == 0 && env_int("SLQ_KNOWN_NORM", 1) != 0);
+  return init_from_probes(p, p->pdf_sphere, pdf == 0 && p->sw.known_norm != 0);
 }
 
 // copy columns [c0, c0+nc) of `slot` to a host column-major array, optional per-column scale
@@ -3315,6 +3279,32 @@ extern "C" int slq_plan_dense_path(slq_plan *p, int *kernel, int *ksplit) {
   if (!p) return fail(SLQ_EINVAL, "plan is NULL");
   if (kernel) *kernel = dense_kernel_of(p);
   if (ksplit) *ksplit = p->dense_ks;
+  return SLQ_OK;
+}
+
+// the facts of a plan and its operator that decide what a step launches (slq_sequence.hpp)
+static seq::SequenceFacts sequence_facts(const slq_plan *p) {
+  const slq_operator *op = p->op;
+  seq::SequenceFacts f;
+  f.csr = op->kind == OP_CSR, f.far_le4 = op->far_per_row <= 4.0, f.tiles_ringed = op->tiles_ringed, f.upper = op->rowptr_u != nullptr;
+  f.ringR = p->ringR, f.rs_desc_u = p->rs_desc_u != nullptr, f.rs_u_padded = p->rs_u_padded;
+  f.deg = p->deg, f.orth = p->orth, f.nstale = p->nstale, f.basis_mode = p->basis_mode;
+  f.dense_class = dense_kernel_of(p), f.pipelined = p->pipelined, f.omega_on = p->omega_on;
+  const PlanSwitches &sw = p->sw;
+  f.fused = sw.fused, f.merged = sw.merged, f.mgs = sw.mgs, f.stored_u = sw.stored_u, f.nt = sw.nt, f.cross = sw.cross, f.sw_gram = sw.gram;
+  f.sw_gram_csr = sw.gram_csr, f.sw_ring_gen = sw.ring_gen, f.sw_ring_deep = sw.ring_deep, f.last_store = sw.last_store;
+  f.ring_alpha = sw.ring_alpha, f.ring_rev = sw.ring_rev;
+  seq::derive_plan_flags(f);
+  return f;
+}
+
+// step_shape() of slq_sequence.hpp on facts given as an array (the order of seq::facts_from_array), the answer as an array (the
+// order of seq::shape_to_array, then plan_sequence_of): no HIP call, so that a CPU test enumerates the decision
+extern "C" int slq_debug_step_shape(const int *facts, int nfacts, int j, int prev_xt, int *out, int nout) {
+  if (!facts || !out || nfacts != seq::kNumFacts || nout != seq::kNumShape + 1) return fail(SLQ_EINVAL, "slq_debug_step_shape: %d facts in, %d values out", seq::kNumFacts, seq::kNumShape + 1);
+  const seq::SequenceFacts f = seq::facts_from_array(facts);
+  seq::shape_to_array(seq::step_shape(f, j, prev_xt != 0), out);
+  out[seq::kNumShape] = seq::plan_sequence_of(f);
   return SLQ_OK;
 }
 
@@ -3469,17 +3459,17 @@ static int quadrature_lanes(int deg) {
 }
 
 // the generic update pass of the Gram sequence (k_csr_pass<PASS_UPDATEG>, nontemporal streams), r = 1 .. kFusedMaxR ring columns
-template <typename F, int L, int RC> static inline void launch_csr_updateg_rc(slq_plan *p, bool pipe_on, dim3 grid, size_t lds, hipStream_t st, int j);
-template <typename F, int L> static inline void launch_csr_updateg(slq_plan *p, int r, bool pipe_on, dim3 grid, size_t lds, hipStream_t st, int j) {
+template <typename F, int L, int RC> static inline void launch_csr_updateg_rc(slq_plan *p, bool pipe_on, dim3 grid, size_t lds, hipStream_t st, int j, int xt);
+template <typename F, int L> static inline void launch_csr_updateg(slq_plan *p, int r, bool pipe_on, dim3 grid, size_t lds, hipStream_t st, int j, int xt) {
   switch (r) {
-    case 1: launch_csr_updateg_rc<F, L, 1>(p, pipe_on, grid, lds, st, j); break;
-    case 2: launch_csr_updateg_rc<F, L, 2>(p, pipe_on, grid, lds, st, j); break;
-    case 3: launch_csr_updateg_rc<F, L, 3>(p, pipe_on, grid, lds, st, j); break;
-    case 4: launch_csr_updateg_rc<F, L, 4>(p, pipe_on, grid, lds, st, j); break;
-    case 5: launch_csr_updateg_rc<F, L, 5>(p, pipe_on, grid, lds, st, j); break;
-    case 6: launch_csr_updateg_rc<F, L, 6>(p, pipe_on, grid, lds, st, j); break;
-    case 7: launch_csr_updateg_rc<F, L, 7>(p, pipe_on, grid, lds, st, j); break;
-    default: launch_csr_updateg_rc<F, L, 8>(p, pipe_on, grid, lds, st, j); break;
+    case 1: launch_csr_updateg_rc<F, L, 1>(p, pipe_on, grid, lds, st, j, xt); break;
+    case 2: launch_csr_updateg_rc<F, L, 2>(p, pipe_on, grid, lds, st, j, xt); break;
+    case 3: launch_csr_updateg_rc<F, L, 3>(p, pipe_on, grid, lds, st, j, xt); break;
+    case 4: launch_csr_updateg_rc<F, L, 4>(p, pipe_on, grid, lds, st, j, xt); break;
+    case 5: launch_csr_updateg_rc<F, L, 5>(p, pipe_on, grid, lds, st, j, xt); break;
+    case 6: launch_csr_updateg_rc<F, L, 6>(p, pipe_on, grid, lds, st, j, xt); break;
+    case 7: launch_csr_updateg_rc<F, L, 7>(p, pipe_on, grid, lds, st, j, xt); break;
+    default: launch_csr_updateg_rc<F, L, 8>(p, pipe_on, grid, lds, st, j, xt); break;
   }
 }
 
@@ -3507,16 +3497,16 @@ static inline void launch_csr_pass(bool pipe_on, dim3 grid, size_t lds, hipStrea
   k_csr_pass<F, L, PASS, LP, RC, 0><<<grid, dim3(kBlock), lds, st>>>(args...);
 }
 
-template <typename F, int L, int RC> static inline void launch_csr_updateg_rc(slq_plan *p, bool pipe_on, dim3 grid, size_t lds, hipStream_t st, int j) {
+template <typename F, int L, int RC> static inline void launch_csr_updateg_rc(slq_plan *p, bool pipe_on, dim3 grid, size_t lds, hipStream_t st, int j, int xt) {
   const slq_operator *op = p->op;
-  const int xt = (j == p->deg - 1 && !p->keep_basis && p->last_nostore) ? 16 : 0;  // (the run's last step: W_deg is not stored)
   launch_csr_pass<F, L, PASS_UPDATEG, 1, RC>(pipe_on, grid, lds, st, p->n, op->rowptr, op->colind, (const F *)op->vals, (F *)p->ring, p->slot_stride, p->S, j, p->st.coefA,
                                              p->st.coefB, p->st.gamma, p->part, p->bpad, xt);
 }
 
-// the same pass on workgroup tiles (wide panels only; slq_kernels.hpp: k_csr_tile_pass)
+// the same pass on workgroup tiles (wide panels only; slq_kernels.hpp: k_csr_tile_pass). xt is the kernel's complete word
+// (step_shape); upper: the alpha-only pass reads the upper-triangle stream
 template <typename F, int L, int PASS, int LP, int RC>
-static inline void launch_tile_pass(slq_plan *p, dim3 grid, size_t lds, hipStream_t st, int j, int xt) {
+static inline void launch_tile_pass(slq_plan *p, dim3 grid, size_t lds, hipStream_t st, int j, int xt, bool upper) {
   if constexpr (L == 64 && (PASS == PASS_ALPHA || PASS == PASS_ADOTS || PASS == PASS_UPDATE || PASS == PASS_SPMM)) {
     const slq_operator *op = p->op;
     TileRanges xr;
@@ -3525,16 +3515,14 @@ static inline void launch_tile_pass(slq_plan *p, dim3 grid, size_t lds, hipStrea
       if (op->tiles_ringed) {
         // the ring-fed variant: flag words and descriptor staging + kRingSlots slots; 16 waves per workgroup
         const size_t lds_ring = kRingHeadBytes + (size_t)kRingSlots * (kRingTileCols * 1024 + kRingMetaBytes);
-        const bool upper = PASS == PASS_ALPHA && p->rs_desc_u != nullptr && p->sw.ring_alpha == 2;
         if (upper)
           for (int x = 0; x < 9; ++x) xr.first[x] = p->rs_xcd_u[x];
         k_csr_ring_pass<F, PASS, LP, RC><<<grid, dim3(kRingBlock), lds_ring, st>>>(p->n, upper ? p->rs_desc_u : op->tile_desc, upper ? p->rs_rec_u : op->tile_rec, xr, (F *)p->ring, p->slot_stride, p->S, j, p->st.coefA,
-                                                                               p->st.coefB, p->st.gamma, p->part, p->bpad,
-                                                                               xt | ((PASS == PASS_UPDATE && p->sw.ring_rev) ? 4 : 0), p->ring_fail_d);
+                                                                               p->st.coefB, p->st.gamma, p->part, p->bpad, xt, p->ring_fail_d);
         return;
       }
     }
-    if (op->tiles_ringed) {  // never reached (enqueue_run sends ring-sized tiles to the ring-fed kernels or the generic passes)
+    if (op->tiles_ringed) {  // never reached (step_shape sends ring-sized tiles to the ring-fed kernels or the generic passes)
       p->launch_error = true;  // (no launch: enqueue_run turns this into SLQ_EINVAL instead of handing out numbers of a pass that never ran)
       return;
     }
@@ -3552,9 +3540,9 @@ static unsigned long long *debug_times_buffer() { return g_dbg_host_handle; }
 static unsigned long long *debug_times_buffer() { return nullptr; }
 #endif
 
-// one ring-fed pass through k_ring_pass (slq_ring.hpp: any panel width, up to 8 ring columns; nontemporal streams)
-static int launch_ring_gen(slq_plan *p, int pass, int rc, dim3 grid, hipStream_t st, int j, int xt, const int *wread = nullptr) {
-  const bool upper = pass == PASS_ALPHA && p->rs_desc_u != nullptr && p->sw.ring_alpha == 2;
+// one ring-fed pass through k_ring_pass (slq_ring.hpp: any panel width, up to 8 ring columns; nontemporal streams). xt is the
+// kernel's complete word (step_shape); upper: the alpha-only pass reads the upper-triangle stream
+static int launch_ring_gen(slq_plan *p, int pass, int rc, dim3 grid, hipStream_t st, int j, int xt, bool upper, const int *wread = nullptr) {
   RingArgs a;
   a.pass = pass;
   a.rc = rc;
@@ -3574,12 +3562,10 @@ static int launch_ring_gen(slq_plan *p, int pass, int rc, dim3 grid, hipStream_t
   a.gamma = p->st.gamma;
   a.part = p->part;
   a.bpad = p->bpad;
-  // bit 4: the LAST step of a run whose basis is not kept stores nothing - W_deg is never read (lanczos.h:139-142 takes its norm and breaks); SLQ_LAST_STORE=1 keeps the store
-  const bool last_nostore = (pass == PASS_UPDATE || pass == PASS_UPDATEG) && j == p->deg - 1 && !p->keep_basis && p->last_nostore;
-  a.xt = xt | (((pass == PASS_UPDATE || pass == PASS_UPDATEG) && p->sw.ring_rev) ? 4 : 0) | ((upper && p->rs_u_padded) ? 8 : 0) | (last_nostore ? 16 : 0);  // bit 3: padded rows
+  a.xt = xt;
   a.fail = p->ring_fail_d;
   a.wread = wread;
-  a.dbg = pass == env_int("SLQ_DEBUG_PASS", PASS_ADOTS) ? debug_times_buffer() : nullptr;  // (diagnostic builds: the pass whose time line is stamped)
+  a.dbg = pass == p->sw.debug_pass ? debug_times_buffer() : nullptr;  // (diagnostic builds: the pass whose time line is stamped)
   const bool d = p->dtype == SLQ_F64;
   int rc_l = -1;
   switch (p->LPR) {
@@ -3592,16 +3578,258 @@ static int launch_ring_gen(slq_plan *p, int pass, int rc, dim3 grid, hipStream_t
   return SLQ_OK;
 }
 
+// what the launches of one enqueue_run share: grids, tolerances, the LDS sizes of the fused passes
+struct RunFrame {
+  slq_plan *p;
+  hipStream_t st;
+  bool nt;
+  double eps, residual_tol, orth_tol;
+  dim3 gA, gS, gU, gF, gAf, gT;
+  size_t lds0;  // the fused passes' static part
+  OmegaState om_off;
+  int blocks(int blk) const {
+    switch (blk) {
+      case seq::BLK_A: return p->nblkA;
+      case seq::BLK_U: return p->nblkU;
+      case seq::BLK_T: return p->nblkT;
+      case seq::BLK_F: return p->nblkF;
+      default: return p->nblkS;
+    }
+  }
+  // alpha pass: grid and residency cap (nblkF, alpha_pad) are chosen in slq_plan_create
+  size_t lds_alpha(const seq::StepShape &s) const { return lds0 + (s.alpha_tiled ? 0 : p->alpha_pad); }
+  // dots/update passes: 64 KiB of LDS padding pins residency at 2 workgroups per CU whatever the variant's
+  // register count (62-96 VGPRs would admit 3 for some). Their grid is 2 per CU *per panel*: blocks are
+  // dispatched panel-major, so panel 0 fills the chip, panel 1 follows as its workgroups retire, and an
+  // XCD's L2 holds one panel's gather halo at a time (both panels side by side fetch 9.2/10.8 GB per
+  // dots/update launch instead of 6.5/8.6 GB).
+  // (the pipelined row loop runs ONE resident workgroup per CU: 96 KiB of padding)
+  size_t lds_fused(const seq::StepShape &s) const {
+    return lds0 + (s.tiled ? 0 : (size_t)(p->sw.fused_pad >= 0 ? p->sw.fused_pad : (p->pipelined ? 98304 : 65536)));
+  }
+  // wide panels (one row per wave) of an operator with barrier tiles: the tile's distinct panel rows are staged once in LDS
+  size_t lds_tile(const seq::StepShape &s) const {
+    return lds0 + (s.tiled ? (size_t)(SLQ_TILE_DB ? 2 : 1) * p->op->tiles.max_cols * p->PW * p->esz : 0);
+  }
+};
+
+// one fused pass of step j as the shape says: k_ring_pass, the tile kernels or the generic k_csr_pass (the macros are the
+// template dispatch over PASS, load policy and ring columns, nothing else)
+#define CSR_PASS_RC(PASS, LP, RCT)                                                                   \
+  do {                                                                                               \
+    if (tl && s.gen)                                                                                 \
+      SLQ_TRY(launch_ring_gen(p, PASS, RCT, c.gT, c.st, j, xt, upper));                              \
+    else if (tl)                                                                                     \
+      DISPATCH(p->dtype, p->LPR, (launch_tile_pass<F, L, PASS, LP, RCT>(p, c.gT, c.lds_tile(s), c.st, j, xt, upper))); \
+    else                                                                                             \
+      DISPATCH(p->dtype, p->LPR,                                                                     \
+               (launch_csr_pass<F, L, PASS, LP, RCT>(s.pipe_on != 0, (PASS == PASS_ALPHA ? c.gAf : c.gU), lds, c.st, p->n, \
+                   half ? op->rowptr_u : op->rowptr, half ? op->colind_u : op->colind,               \
+                   (const F *)(half ? op->vals_u : op->vals), (F *)p->ring, p->slot_stride, p->S, j, \
+                   p->st.coefA, p->st.coefB, p->st.gamma, p->part, p->bpad, xt)));                   \
+  } while (0)
+#define CSR_PASS(PASS, LP)                                                                           \
+  switch (PASS == PASS_ALPHA ? 0 : rc) {                                                             \
+    case 0: CSR_PASS_RC(PASS, LP, ((PASS == PASS_DOTS || PASS == PASS_ADOTS) ? 1 : 0)); break;       \
+    case 1: CSR_PASS_RC(PASS, LP, (PASS == PASS_ALPHA ? 0 : 1)); break;                              \
+    case 2: CSR_PASS_RC(PASS, LP, (PASS == PASS_ALPHA ? 0 : 2)); break;                              \
+    case 3: CSR_PASS_RC(PASS, LP, (PASS == PASS_ALPHA ? 0 : 3)); break;                              \
+    case 4: CSR_PASS_RC(PASS, LP, (PASS == PASS_ALPHA ? 0 : 4)); break;                              \
+    case 5: CSR_PASS_RC(PASS, LP, (PASS == PASS_ALPHA ? 0 : 5)); break;                              \
+    case 6: CSR_PASS_RC(PASS, LP, (PASS == PASS_ALPHA ? 0 : 6)); break;                              \
+    case 7: CSR_PASS_RC(PASS, LP, (PASS == PASS_ALPHA ? 0 : 7)); break;                              \
+    default: CSR_PASS_RC(PASS, LP, (PASS == PASS_ALPHA ? 0 : 8)); break;                             \
+  }
+template <int PASS> static int launch_fused_pass(const RunFrame &c, const seq::StepShape &s, int j, int rc, size_t lds, int xt) {
+  slq_plan *p = c.p;
+  const slq_operator *op = p->op;
+  const bool tl = PASS == PASS_ALPHA ? s.alpha_tiled : s.tiled;
+  const bool half = PASS == PASS_ALPHA && s.half;
+  const bool upper = PASS == PASS_ALPHA && s.alpha_upper;
+  if (c.nt) CSR_PASS(PASS, 1) else CSR_PASS(PASS, 0)
+  return SLQ_OK;
+}
+#undef CSR_PASS
+#undef CSR_PASS_RC
+
+// Gram sequence on ring-fed plans (r >= 1): alpha-only pass, projections from the Gram rows of the last two update passes
+// (k_fin_gram), update pass that also takes the new vector against every ring column it reads (slq_kernels.hpp)
+static int launch_gram_ring(const RunFrame &c, const seq::StepShape &s, int j) {
+  slq_plan *p = c.p;
+  hipStream_t st = c.st;
+  const int bp = p->bpad, r = s.r, S = p->S;
+  PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_fused_pass<PASS_ALPHA>(c, s, j, 0, c.lds_alpha(s), s.xt_alpha)));
+  // a full window of three columns is offered to the edge recurrence (slq_kernels.hpp: OmegaState): its oldest column is read only
+  // where the panel's flag says so. The launch sequence does not depend on the flags: the two rescue kernels are always there.
+  OmegaState om = c.om_off;
+  om.census = p->om_census, om.PW = p->PW, om.NP = p->NP;
+  if (s.omega) {
+    om.mode = p->sw.omega;
+    om.est_prev = s.est_prev;
+    om.force = (j == p->sw.omega_trip ? 1 : 0) | (j == p->sw.omega_rescue ? 2 : 0);
+    om.D = p->om_buf, om.rho = p->om_buf + bp, om.g3 = p->om_buf + 2 * (size_t)bp, om.Dm = p->om_buf + 3 * (size_t)bp;
+    om.read = p->om_flags, om.rescue = p->om_flags + (size_t)(p->deg + 1) * p->NP;
+    om.cnt = p->om_cnt;
+    om.eps_norm = c.eps * p->om_norm;
+    om.theta = kOmegaC * om.eps_norm;
+    om.tol_k = c.orth_tol / kOmegaKappa;
+  }
+  PROFILED(p, SLQ_K_FINALIZE,
+           hipLaunchKernelGGL(k_fin_gram, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, st, p->st, p->part, c.blocks(s.blk_alpha), j, r, c.orth_tol, om));
+  if (om.mode == 1 && om.est_prev) {
+    double *part_r = p->part + (size_t)p->part_maxblk * bp;  // (behind the alpha partials, which the second pass does not need but the slab layout keeps)
+    PROFILED(p, SLQ_K_FINALIZE,
+             DISPATCH(p->dtype, p->LPR, (k_omega_rescue_dot<F, L><<<c.gS, dim3(kBlock), 0, st>>>(p->n, (const F *)p->ring, p->slot_stride, S, j, r, om.rescue + (size_t)j * p->NP, part_r, bp))));
+    PROFILED(p, SLQ_K_FINALIZE,
+             hipLaunchKernelGGL(k_fin_gram_rescue, dim3((bp + 63) / 64), dim3(kFinThreads), 0, st, p->st, part_r, p->nblkS, j, r, c.orth_tol, om));
+  }
+  PROFILED(p, SLQ_K_REORTH_UPD, SLQ_TRY(launch_ring_gen(p, PASS_UPDATEG, r, c.gT, st, j, s.xt_update, false, om.mode == 1 ? om.read + (size_t)j * p->NP : nullptr)));
+  PROFILED(p, SLQ_K_FINALIZE,
+           hipLaunchKernelGGL(k_fin_beta_gram, dim3((bp + 63) / 64, r + 1), dim3(kFinThreads), 0, st, p->st, p->part, c.blocks(s.blk_beta), j, r, c.residual_tol, om));
+  return SLQ_OK;
+}
+
+// the same sequence on the generic passes (k_csr_pass<PASS_UPDATEG>; r04): alpha-only pass over the upper triangle, projections from Gram rows
+static int launch_gram_csr(const RunFrame &c, const seq::StepShape &s, int j) {
+  slq_plan *p = c.p;
+  hipStream_t st = c.st;
+  const int bp = p->bpad, r = s.r;
+  PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_fused_pass<PASS_ALPHA>(c, s, j, 0, c.lds_alpha(s), s.xt_alpha)));
+  PROFILED(p, SLQ_K_FINALIZE,
+           hipLaunchKernelGGL(k_fin_gram, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, st, p->st, p->part, c.blocks(s.blk_alpha), j, r, c.orth_tol, c.om_off));
+  PROFILED(p, SLQ_K_REORTH_UPD, DISPATCH(p->dtype, p->LPR, (launch_csr_updateg<F, L>(p, r, s.pipe_on != 0, c.gU, c.lds_fused(s), st, j, s.xt_update))));
+  PROFILED(p, SLQ_K_FINALIZE,
+           hipLaunchKernelGGL(k_fin_beta_gram, dim3((bp + 63) / 64, r + 1), dim3(kFinThreads), 0, st, p->st, p->part, c.blocks(s.blk_beta), j, r, c.residual_tol, c.om_off));
+  return SLQ_OK;
+}
+
+// fused passes, r >= 1: alpha comes out of the dots pass (PASS_ADOTS: two gather passes per step instead of three); the
+// stored-u sequence is this one with the bits that make the first pass store u and the second read it back
+static int launch_merged(const RunFrame &c, const seq::StepShape &s, int j) {
+  slq_plan *p = c.p;
+  const int bp = p->bpad, r = s.r;
+  PROFILED(p, SLQ_K_REORTH_DOT, SLQ_TRY(launch_fused_pass<PASS_ADOTS>(c, s, j, r, c.lds_fused(s), s.xt_dots)));
+  PROFILED(p, SLQ_K_FINALIZE,
+           hipLaunchKernelGGL(k_fin_adots, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, c.st, p->st, p->part, c.blocks(s.blk_dots), j, r, c.orth_tol));
+  PROFILED(p, SLQ_K_REORTH_UPD, SLQ_TRY(launch_fused_pass<PASS_UPDATE>(c, s, j, r, c.lds_fused(s), s.xt_update)));
+  return SLQ_OK;
+}
+
+// fused passes with the alpha pass on its own (r == 0, or SLQ_MERGED=0): alpha, dots (r > 0), update
+static int launch_separate(const RunFrame &c, const seq::StepShape &s, int j) {
+  slq_plan *p = c.p;
+  const int bp = p->bpad, r = s.r;
+  PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_fused_pass<PASS_ALPHA>(c, s, j, 0, c.lds_alpha(s), s.xt_alpha)));
+  PROFILED(p, SLQ_K_FINALIZE,
+           hipLaunchKernelGGL(k_fin_alpha, c.gF, dim3(kFinThreads), 0, c.st, p->st, p->part, c.blocks(s.blk_alpha), j, s.xt_alpha & 1));
+  if (r > 0) {
+    PROFILED(p, SLQ_K_REORTH_DOT, SLQ_TRY(launch_fused_pass<PASS_DOTS>(c, s, j, r, c.lds_fused(s), s.xt_dots)));
+    PROFILED(p, SLQ_K_FINALIZE,
+             hipLaunchKernelGGL(k_fin_gamma, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, c.st, p->st, p->part, c.blocks(s.blk_dots), j, 0, c.orth_tol));
+  }
+  PROFILED(p, (r == 0 ? SLQ_K_AXPY_NORM : SLQ_K_REORTH_UPD), SLQ_TRY(launch_fused_pass<PASS_UPDATE>(c, s, j, r, c.lds_fused(s), s.xt_update)));
+  return SLQ_OK;
+}
+
+// the sweeps' first launch: W_n = A W_c - (three-term part) with the alpha partials, by the kernel of the operator's kind
+static int launch_sweep_product(const RunFrame &c, const seq::StepShape &s, int j) {
+  slq_plan *p = c.p;
+  const slq_operator *op = p->op;
+  hipStream_t st = c.st;
+  const int bp = p->bpad, S = p->S;
+  const int sc_ = j % S, sp_ = (j + S - 1) % S, sn_ = (j + 1) % S;
+  const int first = (j == 0);
+  int nblk = c.blocks(s.blk_alpha);
+  switch (s.product) {
+    case seq::PRODUCT_RING:
+      // the sweeps' SpMM + three-term step on the ring-fed tiles (k_csr_ring_pass<PASS_SPMM>): same result slot, same alpha partials
+      PROFILED(p, SLQ_K_SPMM, {
+        if (s.gen) SLQ_TRY(launch_ring_gen(p, PASS_SPMM, 0, c.gT, st, j, 0, false));
+        else if (c.nt) DISPATCH(p->dtype, p->LPR, (launch_tile_pass<F, L, PASS_SPMM, 1, 0>(p, c.gT, 0, st, j, 0, false)));
+        else DISPATCH(p->dtype, p->LPR, (launch_tile_pass<F, L, PASS_SPMM, 0, 0>(p, c.gT, 0, st, j, 0, false)));
+      });
+      break;
+    case seq::PRODUCT_CSR: {
+      const size_t spmm_pad = (size_t)p->sw.spmm_pad;  // dynamic LDS only to cap residency at 2 per CU (panel after panel: 38.8 -> 34.7 ms per 26 launches at orth 30)
+#define SPMM_LAUNCH(LP, SP)                                                                          \
+  DISPATCH(p->dtype, p->LPR,                                                                         \
+           (k_spmm_3term<F, L, LP, SP><<<c.gA, dim3(kBlock), spmm_pad, st>>>(                        \
+               p->n, op->rowptr, op->colind, (const F *)op->vals, (const F *)slot_ptr(p, sc_),       \
+               (const F *)slot_ptr(p, sp_), (F *)slot_ptr(p, sn_), p->st.coefA, p->part, bp, first)))
+      PROFILED(p, SLQ_K_SPMM, {
+        switch (c.nt ? 11 : 0) {  // tens digit: load policy, units: store policy
+          case 1: SPMM_LAUNCH(0, 1); break;
+          case 2: SPMM_LAUNCH(0, 2); break;
+          case 10: SPMM_LAUNCH(1, 0); break;
+          case 11: SPMM_LAUNCH(1, 1); break;
+          case 12: SPMM_LAUNCH(1, 2); break;
+          default: SPMM_LAUNCH(0, 0); break;
+        }
+      });
+#undef SPMM_LAUNCH
+      break;
+    }
+    case seq::PRODUCT_DENSE:
+      PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_dense_mfma(p, slot_ptr(p, sc_), slot_ptr(p, sp_), slot_ptr(p, sn_), first, 0, &nblk)));
+      break;
+    default:
+      SLQ_TRY(apply_operator_unfused(p, sc_));
+      PROFILED(p, SLQ_K_AXPY_NORM,
+               DISPATCH(p->dtype, p->LPR,
+                        (k_3term<F, L><<<c.gS, dim3(kBlock), 0, st>>>(p->n, (const F *)p->T, (const F *)slot_ptr(p, sc_), (const F *)slot_ptr(p, sp_),
+                                                                      (F *)slot_ptr(p, sn_), p->st.coefA, p->part, bp, first))));
+      break;
+  }
+  PROFILED(p, SLQ_K_FINALIZE, hipLaunchKernelGGL(k_fin_alpha, c.gF, dim3(kFinThreads), 0, st, p->st, p->part, nblk, j, 0));
+  return SLQ_OK;
+}
+
+// store-and-revisit sweeps: the product, then the reorthogonalisation against the r ring columns in the order the shape names
+static int launch_sweeps(const RunFrame &c, const seq::StepShape &s, int j) {
+  slq_plan *p = c.p;
+  hipStream_t st = c.st;
+  const int bp = p->bpad, S = p->S, r = s.r;
+  SLQ_TRY(launch_sweep_product(c, s, j));
+  if (s.seq == seq::SEQ_SWEEPS_PLAIN) {
+    PROFILED(p, SLQ_K_AXPY_NORM,
+             DISPATCH(p->dtype, p->LPR,
+                      (k_axpy_norm<F, L, 0><<<c.gS, dim3(kBlock), 0, st>>>(p->n, (F *)slot_ptr(p, (j + 1) % S), (const F *)slot_ptr(p, j % S), p->st.coefB, p->part, bp))));
+  } else if (s.seq == seq::SEQ_SWEEPS_MGS) {
+    for (int i = 0; i < r; ++i) {
+      PROFILED(p, SLQ_K_REORTH_DOT,
+               DISPATCH(p->dtype, p->LPR,
+                        (k_reorth_dot<F, L><<<c.gS, dim3(kBlock), 0, st>>>(p->n, (F *)p->ring, p->slot_stride, S, j, i, 1, (int)(i == 0), p->st.coefB, p->part, bp))));
+      PROFILED(p, SLQ_K_FINALIZE,
+               hipLaunchKernelGGL(k_fin_gamma, dim3((bp + 63) / 64, 1), dim3(kFinThreads), 0, st, p->st, p->part, p->nblkS, j, i, c.orth_tol));
+      SLQ_TRY(launch_reorth_update_range(p, j, i, i + 1));
+    }
+  } else {
+    for (int i0 = 0; i0 < r; i0 += kReorthChunk) {  // reorth columns per dots launch
+      const int rc = std::min(kReorthChunk, r - i0);
+      PROFILED(p, SLQ_K_REORTH_DOT, DISPATCH(p->dtype, p->LPR, (launch_reorth_dot<F, L>(p, c.gS, st, j, i0, rc))));
+      PROFILED(p, SLQ_K_FINALIZE,
+               hipLaunchKernelGGL(k_fin_gamma, dim3((bp + 63) / 64, rc), dim3(kFinThreads), 0, st, p->st, p->part, p->nblkS, j, i0, c.orth_tol));
+    }
+    SLQ_TRY(launch_reorth_update(p, j, r, 0, p->sw.defer_axpy));
+  }
+  return SLQ_OK;
+}
+
 // enqueue the launch sequence of steps [j0, j1) on the context stream (also run under stream capture). Between steps the whole
 // state of a run lives on the device; the host carries p->prev_xt, read here at j0 and left as step j1 - 1 sets it.
-static int enqueue_run(slq_plan *p, double rtol, int fused_mode, bool nt, int j0, int j1) {
-  const bool fused = fused_mode != 0;
+// What a step launches is step_shape's answer (slq_sequence.hpp); the functions above launch it and decide nothing.
+static int enqueue_run(slq_plan *p, double rtol, int j0, int j1) {
   hipStream_t st = p->ctx->stream;
-  const int bp = p->bpad, deg = p->deg, S = p->S;
-  const double eps = p->dtype == SLQ_F64 ? std::numeric_limits<double>::epsilon()
-                                         : (double)std::numeric_limits<float>::epsilon();
-  const double residual_tol = std::sqrt((double)p->n) * rtol;   // lanczos.h:110
-  const double orth_tol = 2.0 * eps * std::sqrt((double)p->n);  // lanczos.h:53
+  const int bp = p->bpad, deg = p->deg;
+  RunFrame c;
+  c.p = p, c.st = st, c.nt = p->sw.nt != 0;
+  c.eps = p->dtype == SLQ_F64 ? std::numeric_limits<double>::epsilon() : (double)std::numeric_limits<float>::epsilon();
+  c.residual_tol = std::sqrt((double)p->n) * rtol;   // lanczos.h:110
+  c.orth_tol = 2.0 * c.eps * std::sqrt((double)p->n);  // lanczos.h:53
+  c.gA = dim3(p->nblkA, p->NP), c.gS = dim3(p->nblkS, p->NP), c.gU = dim3(p->nblkU, p->NP), c.gF = dim3((bp + 63) / 64);
+  c.gAf = dim3(p->nblkF, p->NP), c.gT = dim3(p->nblkT, p->NP);
+  c.lds0 = sizeof(double) * kWaves * 64 * (p->dtype == SLQ_F64 ? 2 : 4);
+  memset(&c.om_off, 0, sizeof(c.om_off));
   if (j0 == 0) {
     // alpha and nu[1..] start from zero (the reference's fresh np.zeros buffers, lanczos.py:101-102)
     HIP_TRY(hipMemsetAsync(p->st.alpha, 0, (size_t)(deg + 1) * bp * 8, st));
@@ -3613,249 +3841,21 @@ static int enqueue_run(slq_plan *p, double rtol, int fused_mode, bool nt, int j0
     }
   }
   if (j0 == 0 && p->om_census) HIP_TRY(hipMemsetAsync(p->om_census, 0, (size_t)(deg + 1) * (kFusedMaxR + 1) * p->NP * sizeof(int), st));
-  OmegaState om_off;
-  memset(&om_off, 0, sizeof(om_off));
-  const dim3 gA(p->nblkA, p->NP), gS(p->nblkS, p->NP), gU(p->nblkU, p->NP), gF((bp + 63) / 64);
-  const dim3 gAf(p->nblkF, p->NP);
-  const dim3 gT(p->nblkT, p->NP);
-  const slq_operator *op = p->op;
+  const seq::SequenceFacts facts = sequence_facts(p);
   bool prev_xt = j0 > 0 && p->prev_xt;  // the previous step's update pass produced the cross term W_{j}.W_{j-1}
   for (int j = j0; j < j1; ++j) {
-    const int sc_ = j % S, sp_ = (j + S - 1) % S, sn_ = (j + 1) % S;
-    const int first = (j == 0);
-    // reorth columns: the last `orth` ring vectors; before step orth-1 only j+1 exist, unless the
-    // drop-in entry preloaded the caller's stale ring columns as vectors t < 0 (lanczos_single)
-    const int r = p->orth > 0 ? std::min(j + 1 + p->nstale, p->orth) : 0;
-    int nblk_last = p->nblkS;
-    // exact modified Gram-Schmidt order (one ring column at a time, each dot taken on the updated w):
-    // used when stale ring columns take part, whose projections are NOT small, so block-CGS and the
-    // reference's MGS would differ at second order (1e-6..1e-5 measured with 18 stale vectors)
-    const bool mgs = p->nstale > 0 || p->sw.mgs;
-    // Recomputing the SpMM in every pass pays while the gathers are served from cache. A row whose
-    // neighbours are scattered over the whole vector (random graph, 16 per row) pays an HBM row fetch per
-    // gather and per pass: there the sweeps that gather once and store are 1.3-1.55x faster (configs[2]:
-    // 0.59 -> 0.38 s at orth 3), while grids keep the passes even in natural 3-D order (2 far gathers per row:
-    // 135 vs 178 ms). SLQ_FUSED=2 forces the passes.
-    const bool gathers_cached = fused_mode == 2 || op->far_per_row <= 4.0;
-    // ... with r >= 1 the merged pass can store u for the update pass to read back (SLQ_STORED_U, default on):
-    // one gather pass per step, 7 reads + 2 writes instead of the sweeps' 9 reads + 3 writes
-    const bool stored_u = op->kind == OP_CSR && fused && !gathers_cached && r >= 1 && r <= kFusedMaxR && !mgs &&
-                          p->sw.stored_u && p->sw.merged && !plan_tiled(p);
-    if (op->kind == OP_CSR && fused && (gathers_cached || stored_u) && r <= kFusedMaxR && !mgs) {
-      // ---- fused passes: recompute the SpMM, write once (slq_kernels.hpp: k_csr_pass) ----
-      const int V = p->dtype == SLQ_F64 ? 2 : 4;
-      const size_t lds0 = sizeof(double) * kWaves * 64 * V;
-      // wide panels (one row per wave) of an operator with workgroup tiles (SLQ_TILES): the tile's distinct panel rows are
-      // staged once in LDS (k_csr_tile_pass); everything else about the sequence is the same
-      // (ring-sized tiles serve up to kRingMaxR ring columns; steps with more take the generic passes, on the same row order)
-      const bool tiled = plan_tiled(p) && !stored_u && (!op->tiles_ringed || r <= kRingMaxR || p->ring_deep);
-      const bool gen = tiled && op->tiles_ringed && (p->ring_gen || r > kRingMaxR);  // k_ring_pass rather than k_csr_ring_pass
-      const size_t lds_tile = tiled ? (size_t)(SLQ_TILE_DB ? 2 : 1) * op->tiles.max_cols * p->PW * p->esz : 0;  // the tile image(s)
-      // the alpha-only pass of a symmetric operator stays on the upper triangle (half the gathers) rather than the ring
-      // the alpha-only pass of a symmetric operator: ring-fed over the upper-triangle stream where the operator has one
-      // (SLQ_RING_ALPHA=2, default; else the generic upper-triangle pass), ring-fed over the full rows (1), generic (0)
-      const bool alpha_tiled = tiled && !(op->tiles_ringed && op->rowptr_u != nullptr &&
-                                          (p->sw.ring_alpha == 0 || (p->sw.ring_alpha == 2 && p->rs_desc_u == nullptr)));
-#define CSR_PASS_RC(PASS, LP, RCT, LDS, XT)                                                          \
-  do {                                                                                               \
-    if (tl && gen)                                                                                   \
-      SLQ_TRY(launch_ring_gen(p, PASS, RCT, gT, st, j, XT));                                         \
-    else if (tl)                                                                                     \
-      DISPATCH(p->dtype, p->LPR, (launch_tile_pass<F, L, PASS, LP, RCT>(p, gT, lds0 + lds_tile, st, j, XT))); \
-    else                                                                                             \
-      DISPATCH(p->dtype, p->LPR,                                                                     \
-               (launch_csr_pass<F, L, PASS, LP, RCT>(pipe_on, (PASS == PASS_ALPHA ? gAf : gU), LDS, st, p->n, \
-                   half ? op->rowptr_u : op->rowptr, half ? op->colind_u : op->colind,               \
-                   (const F *)(half ? op->vals_u : op->vals), (F *)p->ring, p->slot_stride, S, j,    \
-                   p->st.coefA, p->st.coefB, p->st.gamma, p->part, bp, XT)));                        \
-  } while (0)
-#define CSR_PASS(PASS, LP, SP, I0, RC, LDS, XT)                                                        \
-  do {                                                                                               \
-    const bool tl = PASS == PASS_ALPHA ? alpha_tiled : tiled;                                        \
-    const bool half = !tl && PASS == PASS_ALPHA && op->rowptr_u != nullptr;                          \
-    switch (PASS == PASS_ALPHA ? 0 : (RC)) {                                                         \
-      case 0: CSR_PASS_RC(PASS, LP, ((PASS == PASS_DOTS || PASS == PASS_ADOTS) ? 1 : 0), LDS, XT); break; \
-      case 1: CSR_PASS_RC(PASS, LP, (PASS == PASS_ALPHA ? 0 : 1), LDS, XT); break;                   \
-      case 2: CSR_PASS_RC(PASS, LP, (PASS == PASS_ALPHA ? 0 : 2), LDS, XT); break;                   \
-      case 3: CSR_PASS_RC(PASS, LP, (PASS == PASS_ALPHA ? 0 : 3), LDS, XT); break;                   \
-      case 4: CSR_PASS_RC(PASS, LP, (PASS == PASS_ALPHA ? 0 : 4), LDS, XT); break;                   \
-      case 5: CSR_PASS_RC(PASS, LP, (PASS == PASS_ALPHA ? 0 : 5), LDS, XT); break;                   \
-      case 6: CSR_PASS_RC(PASS, LP, (PASS == PASS_ALPHA ? 0 : 6), LDS, XT); break;                   \
-      case 7: CSR_PASS_RC(PASS, LP, (PASS == PASS_ALPHA ? 0 : 7), LDS, XT); break;                   \
-      default: CSR_PASS_RC(PASS, LP, (PASS == PASS_ALPHA ? 0 : 8), LDS, XT); break;                  \
-    }                                                                                                \
-  } while (0)
-      // alpha pass: grid and residency cap (nblkF, alpha_pad) are chosen in slq_plan_create
-      const size_t ldsA = lds0 + (alpha_tiled ? 0 : p->alpha_pad);
-      // dots/update passes: 64 KiB of LDS padding pins residency at 2 workgroups per CU whatever the variant's
-      // register count (62-96 VGPRs would admit 3 for some). Their grid is 2 per CU *per panel*: blocks are
-      // dispatched panel-major, so panel 0 fills the chip, panel 1 follows as its workgroups retire, and an
-      // XCD's L2 holds one panel's gather halo at a time (both panels side by side fetch 9.2/10.8 GB per
-      // dots/update launch instead of 6.5/8.6 GB).
-      // (the pipelined row loop runs ONE resident workgroup per CU: 96 KiB of padding)
-      const size_t fused_pad = tiled ? 0 : (size_t)(p->sw.fused_pad >= 0 ? p->sw.fused_pad : (p->pipelined ? 98304 : 65536));
-      const bool pipe_on = p->pipelined && !tiled;
-      // r >= 1: alpha comes out of the dots pass (PASS_ADOTS: two gather passes per step instead of three)
-      const bool merged = r > 0 && (tiled || p->sw.merged);  // (the tiled kernels have the merged form only)
-      // cross term: the update pass of the previous step left W_c.W_p behind, so the alpha pass skips W_p
-      const int xt_a = (prev_xt && j > 0) ? 1 : 0;
-      const int su = stored_u ? 2 : 0;
-      const int xt_u = ((!merged && p->sw.cross) ? 1 : 0) | su;
-      // Gram sequence (ring-fed plans, r >= 1): alpha-only pass, projections from the Gram rows of the last two update passes
-      // (k_fin_gram), update pass that also takes the new vector against every ring column it reads (slq_kernels.hpp)
-      const bool gram = gen && p->gram && r >= 1 && p->nstale == 0;
-      if (gram) {
-        const int xa = j > 0 ? 1 : 0;  // (alpha_j's -beta q_j.q_{j-1} part is a Gram entry: the pass leaves W_p unread)
-        PROFILED(p, SLQ_K_SPMM, { if (nt) CSR_PASS(PASS_ALPHA, 1, 1, 0, 0, ldsA, xa); else CSR_PASS(PASS_ALPHA, 0, 0, 0, 0, ldsA, xa); });
-        // a full window of three columns is offered to the edge recurrence (slq_kernels.hpp: OmegaState): its oldest column is read only
-        // where the panel's flag says so. The launch sequence does not depend on the flags: the two rescue kernels are always there.
-        OmegaState om = om_off;
-        om.census = p->om_census, om.PW = p->PW, om.NP = p->NP;
-        if (p->omega_on && r == 3 && p->orth == 3) {
-          om.mode = p->sw.omega;
-          om.est_prev = j >= 3 ? 1 : 0;  // (step 2 is the first with a full window)
-          om.force = (j == p->sw.omega_trip ? 1 : 0) | (j == p->sw.omega_rescue ? 2 : 0);
-          om.PW = p->PW, om.NP = p->NP;
-          om.D = p->om_buf, om.rho = p->om_buf + bp, om.g3 = p->om_buf + 2 * (size_t)bp, om.Dm = p->om_buf + 3 * (size_t)bp;
-          om.read = p->om_flags, om.rescue = p->om_flags + (size_t)(deg + 1) * p->NP;
-          om.cnt = p->om_cnt;
-          om.eps_norm = eps * p->om_norm;
-          om.theta = kOmegaC * om.eps_norm;
-          om.tol_k = orth_tol / kOmegaKappa;
-        }
-        const int nblk_a = alpha_tiled ? p->nblkT : p->nblkF;
-        PROFILED(p, SLQ_K_FINALIZE,
-                 hipLaunchKernelGGL(k_fin_gram, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, st, p->st, p->part, nblk_a, j, r, orth_tol, om));
-        if (om.mode == 1 && om.est_prev) {
-          double *part_r = p->part + (size_t)p->part_maxblk * bp;  // (behind the alpha partials, which the second pass does not need but the slab layout keeps)
-          PROFILED(p, SLQ_K_FINALIZE,
-                   DISPATCH(p->dtype, p->LPR, (k_omega_rescue_dot<F, L><<<gS, dim3(kBlock), 0, st>>>(p->n, (const F *)p->ring, p->slot_stride, S, j, r, om.rescue + (size_t)j * p->NP, part_r, bp))));
-          PROFILED(p, SLQ_K_FINALIZE,
-                   hipLaunchKernelGGL(k_fin_gram_rescue, dim3((bp + 63) / 64), dim3(kFinThreads), 0, st, p->st, part_r, p->nblkS, j, r, orth_tol, om));
-        }
-        PROFILED(p, SLQ_K_REORTH_UPD, SLQ_TRY(launch_ring_gen(p, PASS_UPDATEG, r, gT, st, j, 0, om.mode == 1 ? om.read + (size_t)j * p->NP : nullptr)));
-        PROFILED(p, SLQ_K_FINALIZE,
-                 hipLaunchKernelGGL(k_fin_beta_gram, dim3((bp + 63) / 64, r + 1), dim3(kFinThreads), 0, st, p->st, p->part, p->nblkT, j, r, residual_tol, om));
-        prev_xt = false;
-        continue;
-      }
-      // the same sequence on the generic passes (k_csr_pass<PASS_UPDATEG>; r04): alpha-only pass over the upper triangle, projections from Gram rows
-      if (p->gram_csr && !tiled && gathers_cached && !stored_u && r >= 1 && p->nstale == 0) {
-        const int xa = j > 0 ? 1 : 0;
-        PROFILED(p, SLQ_K_SPMM, { if (nt) CSR_PASS(PASS_ALPHA, 1, 1, 0, 0, ldsA, xa); else CSR_PASS(PASS_ALPHA, 0, 0, 0, 0, ldsA, xa); });
-        PROFILED(p, SLQ_K_FINALIZE,
-                 hipLaunchKernelGGL(k_fin_gram, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, st, p->st, p->part, alpha_tiled ? p->nblkT : p->nblkF, j, r, orth_tol, om_off));
-        PROFILED(p, SLQ_K_REORTH_UPD, DISPATCH(p->dtype, p->LPR, (launch_csr_updateg<F, L>(p, r, pipe_on, gU, lds0 + fused_pad, st, j))));
-        PROFILED(p, SLQ_K_FINALIZE,
-                 hipLaunchKernelGGL(k_fin_beta_gram, dim3((bp + 63) / 64, r + 1), dim3(kFinThreads), 0, st, p->st, p->part, p->nblkU, j, r, residual_tol, om_off));
-        prev_xt = false;
-        continue;
-      }
-      if (merged) {
-        PROFILED(p, SLQ_K_REORTH_DOT, { if (nt) CSR_PASS(PASS_ADOTS, 1, 1, 0, r, lds0 + fused_pad, su); else CSR_PASS(PASS_ADOTS, 0, 0, 0, r, lds0 + fused_pad, su); });
-        PROFILED(p, SLQ_K_FINALIZE,
-                 hipLaunchKernelGGL(k_fin_adots, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, st, p->st, p->part, tiled ? p->nblkT : p->nblkU, j, r, orth_tol));
-      } else {
-      PROFILED(p, SLQ_K_SPMM, { if (nt) CSR_PASS(PASS_ALPHA, 1, 1, 0, 0, ldsA, xt_a); else CSR_PASS(PASS_ALPHA, 0, 0, 0, 0, ldsA, xt_a); });
-      PROFILED(p, SLQ_K_FINALIZE,
-               hipLaunchKernelGGL(k_fin_alpha, gF, dim3(kFinThreads), 0, st, p->st, p->part, alpha_tiled ? p->nblkT : p->nblkF, j, xt_a));
-      if (r > 0) {
-        PROFILED(p, SLQ_K_REORTH_DOT, { if (nt) CSR_PASS(PASS_DOTS, 1, 1, 0, r, lds0 + fused_pad, 0); else CSR_PASS(PASS_DOTS, 0, 0, 0, r, lds0 + fused_pad, 0); });
-        PROFILED(p, SLQ_K_FINALIZE,
-                 hipLaunchKernelGGL(k_fin_gamma, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, st, p->st,
-                                    p->part, tiled ? p->nblkT : p->nblkU, j, 0, orth_tol));
-      }
-      }
-      const size_t ldsU = lds0 + fused_pad;
-      // (generic passes: the run's last step does not store W_deg; the ring-fed ones add the bit themselves, launch_ring_gen; the older tiled kernels store)
-      const int xt_uu = xt_u | ((!tiled && j == deg - 1 && !p->keep_basis && p->last_nostore && !stored_u) ? 16 : 0);
-      PROFILED(p, (r == 0 ? SLQ_K_AXPY_NORM : SLQ_K_REORTH_UPD),
-               { if (nt) CSR_PASS(PASS_UPDATE, 1, 1, 0, r, ldsU, xt_uu); else CSR_PASS(PASS_UPDATE, 0, 0, 0, r, ldsU, xt_uu); });
-#undef CSR_PASS
-#undef CSR_PASS_RC
-      nblk_last = tiled ? p->nblkT : p->nblkU;
-      prev_xt = (xt_u & 1) != 0;
-    } else {
-    prev_xt = false;
-    if (op->kind == OP_CSR && plan_tiled(p) && op->tiles_ringed) {
-      // the sweeps' SpMM + three-term step on the ring-fed tiles (k_csr_ring_pass<PASS_SPMM>): same result slot, same alpha partials
-      PROFILED(p, SLQ_K_SPMM, {
-        if (p->ring_gen) SLQ_TRY(launch_ring_gen(p, PASS_SPMM, 0, gT, st, j, 0));
-        else if (nt) DISPATCH(p->dtype, p->LPR, (launch_tile_pass<F, L, PASS_SPMM, 1, 0>(p, gT, 0, st, j, 0)));
-        else DISPATCH(p->dtype, p->LPR, (launch_tile_pass<F, L, PASS_SPMM, 0, 0>(p, gT, 0, st, j, 0)));
-      });
-      PROFILED(p, SLQ_K_FINALIZE,
-               hipLaunchKernelGGL(k_fin_alpha, gF, dim3(kFinThreads), 0, st, p->st, p->part, p->nblkT, j, 0));
-    } else if (op->kind == OP_CSR) {
-      const int pol = nt ? 11 : 0;  // tens digit: load policy, units: store policy
-      const size_t spmm_pad = (size_t)p->sw.spmm_pad;  // dynamic LDS only to cap residency at 2 per CU (panel after panel: 38.8 -> 34.7 ms per 26 launches at orth 30)
-#define SPMM_LAUNCH(LP, SP)                                                                          \
-  DISPATCH(p->dtype, p->LPR,                                                                         \
-           (k_spmm_3term<F, L, LP, SP><<<gA, dim3(kBlock), spmm_pad, st>>>(                          \
-               p->n, op->rowptr, op->colind, (const F *)op->vals, (const F *)slot_ptr(p, sc_),       \
-               (const F *)slot_ptr(p, sp_), (F *)slot_ptr(p, sn_), p->st.coefA, p->part, bp, first)))
-      PROFILED(p, SLQ_K_SPMM, {
-        switch (pol) {
-          case 1: SPMM_LAUNCH(0, 1); break;
-          case 2: SPMM_LAUNCH(0, 2); break;
-          case 10: SPMM_LAUNCH(1, 0); break;
-          case 11: SPMM_LAUNCH(1, 1); break;
-          case 12: SPMM_LAUNCH(1, 2); break;
-          default: SPMM_LAUNCH(0, 0); break;
-        }
-      });
-#undef SPMM_LAUNCH
-      PROFILED(p, SLQ_K_FINALIZE,
-               hipLaunchKernelGGL(k_fin_alpha, gF, dim3(kFinThreads), 0, st, p->st, p->part, p->nblkA, j, 0));
-    } else if (dense_kernel_of(p) >= DENSE_K_3TERM) {
-      int nb = 0;
-      PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_dense_mfma(p, slot_ptr(p, sc_), slot_ptr(p, sp_), slot_ptr(p, sn_), first, 0, &nb)));
-      PROFILED(p, SLQ_K_FINALIZE,
-               hipLaunchKernelGGL(k_fin_alpha, gF, dim3(kFinThreads), 0, st, p->st, p->part, nb, j, 0));
-    } else {
-      SLQ_TRY(apply_operator_unfused(p, sc_));
-      PROFILED(p, SLQ_K_AXPY_NORM,
-               DISPATCH(p->dtype, p->LPR,
-                        (k_3term<F, L><<<gS, dim3(kBlock), 0, st>>>(p->n,
-                                            (const F *)p->T, (const F *)slot_ptr(p, sc_),
-                                            (const F *)slot_ptr(p, sp_), (F *)slot_ptr(p, sn_),
-                                            p->st.coefA, p->part, bp, first))));
-      PROFILED(p, SLQ_K_FINALIZE,
-               hipLaunchKernelGGL(k_fin_alpha, gF, dim3(kFinThreads), 0, st, p->st, p->part, p->nblkS, j, 0));
+    const seq::StepShape s = seq::step_shape(facts, j, prev_xt);
+    prev_xt = s.prev_xt != 0;
+    switch (s.seq) {
+      case seq::SEQ_GRAM_RING: SLQ_TRY(launch_gram_ring(c, s, j)); continue;  // (k_fin_beta_gram has closed the step)
+      case seq::SEQ_GRAM_CSR: SLQ_TRY(launch_gram_csr(c, s, j)); continue;
+      case seq::SEQ_MERGED:
+      case seq::SEQ_STORED_U: SLQ_TRY(launch_merged(c, s, j)); break;
+      case seq::SEQ_SEPARATE: SLQ_TRY(launch_separate(c, s, j)); break;
+      default: SLQ_TRY(launch_sweeps(c, s, j)); break;
     }
-    if (r == 0) {
-      PROFILED(p, SLQ_K_AXPY_NORM,
-               DISPATCH(p->dtype, p->LPR,
-                        (k_axpy_norm<F, L, 0><<<gS, dim3(kBlock), 0, st>>>(p->n,
-                                            (F *)slot_ptr(p, sn_), (const F *)slot_ptr(p, sc_),
-                                            p->st.coefB, p->part, bp))));
-    } else if (mgs) {
-      for (int i = 0; i < r; ++i) {
-        PROFILED(p, SLQ_K_REORTH_DOT,
-                 DISPATCH(p->dtype, p->LPR,
-                          (k_reorth_dot<F, L><<<gS, dim3(kBlock), 0, st>>>(p->n,
-                                              (F *)p->ring, p->slot_stride, S, j, i, 1, (int)(i == 0),
-                                              p->st.coefB, p->part, bp))));
-        PROFILED(p, SLQ_K_FINALIZE,
-                 hipLaunchKernelGGL(k_fin_gamma, dim3((bp + 63) / 64, 1), dim3(kFinThreads), 0, st, p->st,
-                                    p->part, p->nblkS, j, i, orth_tol));
-        SLQ_TRY(launch_reorth_update_range(p, j, i, i + 1));
-      }
-    } else {
-      for (int i0 = 0; i0 < r; i0 += kReorthChunk) {  // reorth columns per dots launch
-        const int rc = std::min(kReorthChunk, r - i0);
-        PROFILED(p, SLQ_K_REORTH_DOT,
-                 DISPATCH(p->dtype, p->LPR,
-                          (launch_reorth_dot<F, L>(p, gS, st, j, i0, rc))));
-        PROFILED(p, SLQ_K_FINALIZE,
-                 hipLaunchKernelGGL(k_fin_gamma, dim3((bp + 63) / 64, rc), dim3(kFinThreads), 0, st, p->st,
-                                    p->part, p->nblkS, j, i0, orth_tol));
-      }
-      SLQ_TRY(launch_reorth_update(p, j, r, 0, p->sw.defer_axpy));
-    }
-    }  // !fused
     PROFILED(p, SLQ_K_FINALIZE,
-             hipLaunchKernelGGL(k_fin_beta, gF, dim3(kFinThreads), 0, st, p->st, p->part, nblk_last, j, residual_tol, prev_xt ? 1 : 0));
+             hipLaunchKernelGGL(k_fin_beta, c.gF, dim3(kFinThreads), 0, st, p->st, p->part, c.blocks(s.blk_beta), j, c.residual_tol, prev_xt ? 1 : 0));
   }
   p->prev_xt = prev_xt;
   HIP_TRY(hipGetLastError());
@@ -3897,17 +3897,15 @@ constexpr size_t kGraphCacheMax = 16;
 static int run_range(slq_plan *p, double rtol, int j0, int j1) {
   HIP_TRY(hipSetDevice(p->ctx->device));
   hipStream_t st = p->ctx->stream;
-  const int fused = p->sw.fused;
-  const bool nt = p->sw.nt != 0;
   // The launch sequence of a run (7 launches per Lanczos step, ~210 for k = 30) depends only on
   // the plan, so it is captured into a hipGraph once and replayed: launch-bound for small n,
   // a few per cent for n = 1e6. Not used while per-kernel events are recorded, nor for host-callback
   // operators (they synchronise with the host every step).
   const bool graph_ok = p->sw.graph && !p->prof && p->op->kind != OP_CALLBACK && p->op->kind != OP_DEVICE_CALLBACK;
   if (!graph_ok) {
-    SLQ_TRY(enqueue_run(p, rtol, fused, nt, j0, j1));
+    SLQ_TRY(enqueue_run(p, rtol, j0, j1));
   } else {
-    const unsigned variant = p->sw.key() * 31u + (unsigned)p->nstale;  // every switch of the sequence + the stale-column count
+    const unsigned variant = (unsigned)p->nstale;
     size_t gi = 0;
     for (; gi < p->graphs.size(); ++gi) {
       const auto &g = p->graphs[gi];
@@ -3931,7 +3929,7 @@ static int run_range(slq_plan *p, double rtol, int j0, int j1) {
       hipGraph_t graph = nullptr;
       const bool xt_in = p->prev_xt;
       HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      const int rc = enqueue_run(p, rtol, fused, nt, j0, j1);
+      const int rc = enqueue_run(p, rtol, j0, j1);
       hipError_t ce = hipStreamEndCapture(st, &graph);
       if (rc != SLQ_OK) {
         if (graph) hipGraphDestroy(graph);
@@ -4167,12 +4165,10 @@ static int launch_action_accumulate(slq_plan *p, int t0, int nc, bool init) {
 // the run's launch sequence again, in pieces of up to acc_cols steps, each followed by the accumulation of the columns it
 // finished: after step j the ring holds W_{j+2-S} .. W_{j+1}, and S >= acc_cols + 1 keeps the piece's oldest column resident
 static int enqueue_replay(slq_plan *p, double rtol) {
-  const int fused = p->sw.fused;
-  const bool nt = p->sw.nt != 0;
   int c0 = 0;
   for (int j = 0; j < p->deg; ++j) {
     if (j - c0 + 1 < p->acc_cols && j != p->deg - 1) continue;
-    SLQ_TRY(enqueue_run(p, rtol, fused, nt, c0, j + 1));
+    SLQ_TRY(enqueue_run(p, rtol, c0, j + 1));
     SLQ_TRY(launch_action_accumulate(p, c0, j + 1 - c0, c0 == 0));
     c0 = j + 1;
   }
@@ -4193,7 +4189,7 @@ static int replay_action(slq_plan *p) {
   if (!graph_ok) {
     rc = enqueue_replay(p, rtol);
   } else {
-    const unsigned variant = (p->sw.key() * 31u + (unsigned)p->nstale) * 31u + 2u;  // (never a key of run_range's cache: those graphs live in p->graphs)
+    const unsigned variant = (unsigned)p->nstale;  // (the replay has a cache of its own: replay_exec)
     if (p->replay_exec && (p->replay_rtol != rtol || p->replay_variant != variant)) {
       HIP_TRY(hipGraphExecDestroy(p->replay_exec));
       p->replay_exec = nullptr;

@@ -84,6 +84,42 @@ def test_product_never_imports_the_oracle():
 			assert "import oracle" not in txt and "from oracle" not in txt and "slq_oracle" not in txt, p
 
 
+def test_switches_are_read_in_one_place():
+	"""csrc/slq_switches.hpp holds the one table of SLQ_* switches: no other file of csrc/ names one as a string, getenv has one
+	caller (env_int), and the hash of the plan's switches that once stood in its graph key is gone."""
+	import re
+
+	csrc = ROOT / "primate_amd" / "csrc"
+	getenv_sites = []
+	for p in sorted(csrc.iterdir()):
+		if p.suffix not in {".hip", ".hpp", ".h"}:
+			continue
+		txt = p.read_text()
+		getenv_sites += [(p.name, m.start()) for m in re.finditer(r"\bgetenv\s*\(", txt)]
+		if p.name != "slq_switches.hpp":
+			assert '"SLQ_' not in txt, p
+		assert not re.search(r"\bkey\s*\(\s*\)", txt), p
+	assert len(getenv_sites) == 1 and getenv_sites[0][0] == "slq_switches.hpp", getenv_sites
+	table = (csrc / "slq_switches.hpp").read_text()
+	fn = table[table.index("inline int env_int(") :]
+	assert "getenv(" in fn[: fn.index("\n}\n")]  # ... and that one site is inside env_int
+	names = re.findall(r'"(SLQ_[A-Z0-9_]+)"', table)
+	assert len(names) == len(set(names)) == 54, len(names)  # one line per switch
+	## DESIGN.md §5.4 lists exactly the table's names
+	design = (ROOT / "DESIGN.md").read_text()
+	sec = design[design.index("### 5.4") :]
+	sec = sec[: sec.index("\n## ", 1) if "\n## " in sec[1:] else len(sec)]
+	listed = set()
+	for line in sec.splitlines():
+		if line.startswith("| `SLQ_"):
+			cell = line.split("|")[1]
+			for m in re.finditer(r"`(SLQ_[A-Z0-9_]+)(\[[^\]]*\])?`", cell):
+				listed.add(m.group(1))
+				if m.group(2):
+					listed.update(m.group(1) + suf for suf in m.group(2).strip("[]").split("/") if suf)
+	assert listed == set(names), (sorted(listed - set(names)), sorted(set(names) - listed))
+
+
 def test_function_registry_matches_golden(golden):
 	from primate_amd.engine import fun_spec
 	from primate_amd.special import _BUILTIN_MATRIX_FUNCTIONS, builtin_spec, param_callable
