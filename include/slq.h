@@ -77,7 +77,8 @@ enum {
 enum { SLQ_PDF_RADEMACHER = 0, SLQ_PDF_NORMAL = 1, SLQ_PDF_SPHERE = 2 };
 
 /* Spectral density kernels (slq_density_create): K(x, theta) of the smoothed per-probe measure. */
-enum { SLQ_DENSITY_GAUSSIAN = 0, SLQ_DENSITY_LORENTZIAN = 1, SLQ_DENSITY_HISTOGRAM = 2, SLQ_DENSITY_CDF = 3 };
+enum { SLQ_DENSITY_GAUSSIAN = 0, SLQ_DENSITY_LORENTZIAN = 1, SLQ_DENSITY_HISTOGRAM = 2, SLQ_DENSITY_CDF = 3,
+       SLQ_DENSITY_CHEBYSHEV = 4 /* from Chebyshev moments (slq_density_update_moments): no smoothing kernel, bw ignored */ };
 
 typedef struct slq_context slq_context;   /* one per (process, GPU): device id + HIP stream      */
 typedef struct slq_operator slq_operator; /* a symmetric linear operator resident on that GPU    */
@@ -343,6 +344,37 @@ int slq_density_update(slq_density *d, slq_plan *plan);
 int slq_density_get(slq_density *d, double *mean, double *m2, double *outside, int64_t *count);
 int slq_density_destroy(slq_density *d);
 
+/* ---- Chebyshev moments: the kernel polynomial method (Weisse, Wellein, Alvermann, Fehske, Rev. Mod. Phys. 2006; the other
+ * method of Lin, Saad, Yang 2016) -------------------------------------------------------------------------------------
+ * mu_k = v^T T_k(A~) v with A~ = (A - center) / halfwidth, for every probe of a batch, by the recurrence
+ *   w_0 = v, w_1 = A~ v, w_{j+1} = 2 A~ w_j - w_{j-1}
+ * and the doubling identities mu_{2j+2} = 2 ||w_{j+1}||^2 - mu_0, mu_{2j+1} = 2 w_{j+1}.w_j - mu_1: nsteps steps give the
+ * 2 nsteps + 1 moments mu_0 .. mu_{2 nsteps}, the polynomial degree per product of a Gauss rule. A step is ONE update pass of
+ * the orth-0 Lanczos step with constant coefficients (no alpha pass, no orthogonality, no eigensolve) and one scalar kernel,
+ * so nsteps is bounded by 16384, not by the Lanczos cap of 512.
+ * slq_plan_create_chebyshev: a plan of orth-0 geometry (two ring slots) that holds the moments on the device. The probe
+ *   entries, slq_plan_describe, _workspace_bytes, _profile_* and _destroy work on it unchanged; every Lanczos entry
+ *   (slq_plan_run, _run_steps, _get_tridiag, _quadrature*, _get_basis, _fun_action*, slq_diag_update, slq_density_update)
+ *   returns SLQ_EINVAL, as the entries below do on any other plan.
+ * slq_plan_run_chebyshev: enqueues the nsteps steps on the context stream (asynchronous; it consumes the probes like
+ *   slq_plan_run). [center - halfwidth, center + halfwidth] must contain the spectrum: where it does not, T_k grows and
+ *   |mu_k| > (1 + outside_tol) mu_0 raises the probe's `outside` flag (outside_tol <= 0: the default, 1e-3).
+ * slq_plan_get_moments: mu row-major nprobes x (2 nsteps + 1), outside nprobes ints (or NULL). Synchronises. The numbers are
+ *   returned (finite or not) whatever the flags say.
+ * slq_plan_moment_sum: quad_i = sum_{k < ncoef} coef_k mu_ik, k ascending, ncoef <= 2 nsteps + 1 - with the Chebyshev
+ *   coefficients of f on the interval, v_i^T f(A) v_i. quad: nprobes doubles or NULL; stage: the four doubles of
+ *   slq_plan_quadrature_at {sum quad, sum quad^2, 0, nprobes} or NULL. SLQ_EINVAL, naming the bounds, if a flag is up.
+ * slq_density_update_moments (kind SLQ_DENSITY_CHEBYSHEV only; slq_density_update returns SLQ_EINVAL on that kind): folds
+ *   rho_p(x_g) = [g_0 mu_0 + 2 sum_{k>=1} g_k mu_k T_k(x~_g)] / (pi h sqrt(1 - x~_g^2)), x~ = (x - center) / h,
+ *   over the first nweights moments with damping factors damp (NULL: all ones; Jackson factors make rho >= 0) into the
+ *   accumulator; the integral over the interval is mu_0 = ||v||^2 (the eigenvalue-count normalisation of the other kinds).
+ *   Every grid point must lie strictly inside (center - h, center + h). The two `outside` columns are 0. */
+int slq_plan_create_chebyshev(slq_context *ctx, slq_operator *op, int nprobes, int nsteps, slq_plan **out);
+int slq_plan_run_chebyshev(slq_plan *plan, double center, double halfwidth, double outside_tol);
+int slq_plan_get_moments(slq_plan *plan, double *mu, int *outside);
+int slq_plan_moment_sum(slq_plan *plan, int ncoef, const double *coef, double *quad, double *stage);
+int slq_density_update_moments(slq_density *d, slq_plan *plan, int nweights, const double *damp);
+
 /* Per-kernel device time accumulated by HIP events on the context stream (for bench.py's
  * roofline line). enable != 0 turns event recording on for subsequent slq_plan_run calls. */
 enum {
@@ -405,6 +437,10 @@ int slq_debug_plan_mark_stale(slq_plan *plan, int nstale);
  * behind barriers / 2 ring-fed); out: the 18 values of seq::shape_to_array, then what slq_plan_describe reports as
  * `sequence` for such a plan. No HIP call. */
 int slq_debug_step_shape(const int *facts, int nfacts, int j, int prev_xt, int *out, int nout);
+/* The same for step j of a Chebyshev run of facts[7] (deg) steps (seq::cheb_step_shape, derived from step_shape's answer at
+ * orth = 0): out receives the 9 values of seq::cheb_shape_to_array - sweeps, tiled, gen, pipe_on, the update pass's xt word,
+ * the sweeps' product kernel and its grid, the grid behind the partials, alpha_pass (always 0). No HIP call. */
+int slq_debug_cheb_step_shape(const int *facts, int nfacts, int j, int *out, int nout);
 
 /* ---- one-shot entries ---------------------------------------------------------------------------- */
 /* P probes in one call: the batched counterpart of the Python loop at

@@ -23,7 +23,7 @@ FUN_IDS = {
 	"softsign": 8,
 }  # fmt: skip
 PDF_IDS = {"rademacher": 0, "signs": 0, "normal": 1, "gaussian": 1, "sphere": 2}
-DENSITY_KINDS = {"gaussian": 0, "lorentzian": 1, "histogram": 2, "cdf": 3}
+DENSITY_KINDS = {"gaussian": 0, "lorentzian": 1, "histogram": 2, "cdf": 3, "chebyshev": 4}
 KERNEL_CLASSES = ["spmm_3term", "axpy_norm", "reorth_dot", "reorth_update", "finalize", "probes", "quadrature", "fun_combine"]
 
 MATVEC_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
@@ -126,6 +126,12 @@ _SIGNATURES = {
 	"slq_debug_ring_flag_status": (C.c_int, [C.c_int]),
 	"slq_debug_plan_poke_ring_flag": (C.c_int, [_P, C.c_int]),
 	"slq_debug_step_shape": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
+	"slq_debug_cheb_step_shape": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
+	"slq_plan_create_chebyshev": (C.c_int, [_P, _P, C.c_int, C.c_int, _PP]),
+	"slq_plan_run_chebyshev": (C.c_int, [_P, C.c_double, C.c_double, C.c_double]),
+	"slq_plan_get_moments": (C.c_int, [_P, _P, _P]),
+	"slq_plan_moment_sum": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+	"slq_density_update_moments": (C.c_int, [_P, _P, C.c_int, _P]),
 }  # fmt: skip
 DEVICE_MATMAT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p)
 class PlanInfo(C.Structure):

@@ -31,6 +31,7 @@
 #include "slq_action.hpp"   // two-pass f(A)v: the accumulation of a recompute plan's replay (slq_plan_create_recompute)
 #include "slq_switches.hpp"  // the table of run-time switches, OperatorSwitches, PlanSwitches
 #include "slq_sequence.hpp"  // what a step launches, as a value (step_shape)
+#include "slq_cheb.hpp"      // Chebyshev moments: the kernels of slq_plan_run_chebyshev, _moment_sum, slq_density_update_moments
 
 using namespace slq;
 
@@ -253,7 +254,25 @@ struct slq_plan {
   double replay_rtol = 0.0;
   unsigned replay_variant = 0;  // (nstale, as GraphEntry::variant)
   bool replay_xt_out = false;
+  // Chebyshev plan (slq_plan_create_chebyshev): deg is its number of steps, the geometry that of an orth-0 plan;
+  // alpha / nu keep one row (nu_0), and there is no QL workspace
+  bool cheb = false;
+  bool cheb_ran = false;           // a Chebyshev run has been enqueued since the plan was created (its moments are those of the last run)
+  double cheb_c = 0.0, cheb_h = 0.0;  // centre and half-width of the last run
+  double *cheb_mu = nullptr;       // [2 deg + 1][bpad] moments
+  int *cheb_out = nullptr;         // [bpad] outside flags
+  double *cheb_coef = nullptr;     // [2 deg + 1] coefficients of slq_plan_moment_sum / damping factors of a density update | stage[4]
 };
+
+// the entries of a Lanczos run are not for Chebyshev plans, and the other way round
+static int need_lanczos(const slq_plan *p, const char *who) {
+  if (p->cheb) return fail(SLQ_EINVAL, "%s: a Chebyshev plan has no Lanczos run (slq_plan_run_chebyshev, _get_moments, _moment_sum)", who);
+  return SLQ_OK;
+}
+static int need_chebyshev(const slq_plan *p, const char *who) {
+  if (!p->cheb) return fail(SLQ_EINVAL, "%s: not a Chebyshev plan (slq_plan_create_chebyshev)", who);
+  return SLQ_OK;
+}
 
 // SLQ_TILES: 0 none, 1 workgroup tiles landed behind barriers (k_csr_tile_pass), 2 tiles fed through a ring of LDS slots by
 // loader waves (k_csr_ring_pass). Read when an operator is created (the rows are regrouped into the tiles) and when a plan
@@ -2520,6 +2539,9 @@ extern "C" int slq_plan_destroy(slq_plan *p) {
   for (auto &g : p->graphs) hipGraphExecDestroy(g.exec);
   if (p->replay_exec) hipGraphExecDestroy(p->replay_exec);
   if (p->acc_coef) hipFree(p->acc_coef);
+  if (p->cheb_mu) hipFree(p->cheb_mu);
+  if (p->cheb_out) hipFree(p->cheb_out);
+  if (p->cheb_coef) hipFree(p->cheb_coef);
   if (p->at_d) hipFree(p->at_d);
   if (p->at_flags) hipFree(p->at_flags);
   if (p->ring) hipFree(p->ring);
@@ -2542,7 +2564,7 @@ extern "C" int slq_plan_destroy(slq_plan *p) {
 
 static int set_kernel_attributes(slq_plan *p);
 
-static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, int basis_mode, slq_plan **out);
+static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, int basis_mode, slq_plan **out, bool cheb = false);
 static seq::SequenceFacts sequence_facts(const slq_plan *p);
 
 extern "C" int slq_plan_create(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth,
@@ -2562,17 +2584,21 @@ extern "C" int slq_plan_basis_mode(const slq_plan *p, int *mode, int *ring_slots
   return SLQ_OK;
 }
 
-static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, int basis_mode, slq_plan **out) {
+static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, int basis_mode, slq_plan **out, bool cheb) {
   const int keep_basis = basis_mode == 1;
   if (!ctx || !op || !out) return fail(SLQ_EINVAL, "ctx/op/out is NULL");
   *out = nullptr;
   if (op->ctx != ctx) return fail(SLQ_EINVAL, "operator belongs to another context");
   if (nprobes <= 0) return fail(SLQ_EINVAL, "nprobes must be positive");
-  SLQ_TRY(normalise_params(op->n, &deg, &orth));
+  // a Chebyshev plan: deg steps of the orth-0 geometry, bounded by kMaxChebSteps (neither by n nor by kMaxDeg: nothing is orthogonalised or diagonalised)
+  if (cheb && (deg < 1 || deg > kMaxChebSteps)) return fail(SLQ_EINVAL, "slq_plan_create_chebyshev: nsteps = %d must lie in [1, %d]", deg, kMaxChebSteps);
+  if (!cheb) SLQ_TRY(normalise_params(op->n, &deg, &orth));
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->dead) return fail(SLQ_EINVAL, "the context has been destroyed");
   slq_plan *p = new (std::nothrow) slq_plan();
   if (!p) return fail(SLQ_ENOMEM, "host allocation failed");
+  p->cheb = cheb;
+  const int hist = cheb ? 0 : deg;  // rows of alpha / nu beyond row 0, columns of the stored Gauss rule
   p->ctx = ctx;
   ctx_retain(ctx);
   p->op = op;
@@ -2683,7 +2709,7 @@ static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int
   const size_t bp = p->bpad;
   const size_t ncoef = basis_mode == 2 ? (size_t)deg * bp : 0;
   // alpha[deg+1], nu[orth margin for stale vectors t < 0 | deg+1], vnorm2, coefA[2], coefB, cross, gram[2][kFusedMaxR+1], gamma[rmax]
-  const size_t nscal = ((size_t)(deg + 1) * 2 + (size_t)orth + 1 + 2 + 1 + 1 + 2 * (kFusedMaxR + 1) + (size_t)p->rmax) * bp;
+  const size_t nscal = ((size_t)(hist + 1) * 2 + (size_t)orth + 1 + 2 + 1 + 1 + 2 * (kFusedMaxR + 1) + (size_t)p->rmax) * bp;
   p->part_maxblk = std::max(std::max(std::max(std::max(p->nblkA, p->nblkF), p->nblkU), p->nblkS), p->nblkT);
   const size_t npart = (size_t)kReorthChunk * p->part_maxblk * bp;
   hipError_t e = hipMalloc(&p->ring, ring_bytes);
@@ -2704,10 +2730,16 @@ static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int
   if (e == hipSuccess && p->omega_on) e = hipMemset(p->om_flags, 0, om_flag_words * sizeof(int));
   if (e == hipSuccess && p->omega_on) e = hipMemset(p->om_cnt, 0, 8 * sizeof(unsigned long long));
   const size_t census_words = (size_t)(deg + 1) * (kFusedMaxR + 1) * p->NP;
-  if (e == hipSuccess && p->gram && p->sw.omega == 2) e = hipMalloc((void **)&p->om_census, census_words * sizeof(int));
+  if (e == hipSuccess && p->gram && p->sw.omega == 2 && !cheb) e = hipMalloc((void **)&p->om_census, census_words * sizeof(int));
   if (e == hipSuccess && p->om_census) e = hipMemset(p->om_census, 0, census_words * sizeof(int));
   if (e == hipSuccess) e = hipMalloc((void **)&p->st.active, bp * 2 * sizeof(int) + 16);
-  if (e == hipSuccess) e = hipMalloc((void **)&p->quad_d, (bp + 2 * bp * (size_t)deg) * 8);
+  if (e == hipSuccess) e = hipMalloc((void **)&p->quad_d, (bp + 2 * bp * (size_t)hist) * 8);
+  const size_t nmom = cheb ? (size_t)(2 * deg + 1) : 0;  // moments per probe (256 probes, 16384 steps: 67 MB)
+  if (e == hipSuccess && cheb) e = hipMalloc((void **)&p->cheb_mu, nmom * bp * 8);
+  if (e == hipSuccess && cheb) e = hipMalloc((void **)&p->cheb_out, bp * sizeof(int));
+  if (e == hipSuccess && cheb) e = hipMalloc((void **)&p->cheb_coef, (nmom + 4) * 8);
+  if (e == hipSuccess && cheb) e = hipMemset(p->cheb_mu, 0, nmom * bp * 8);
+  if (e == hipSuccess && cheb) e = hipMemset(p->cheb_out, 0, bp * sizeof(int));
   // dense fp64 operator on the matrix cores with 32-row tiles: n/32 workgroups per panel rarely fill 256 CUs, so K is
   // also split over dense_ks workgroups whose raw products land in dense_ks slabs behind T. ks minimises the number
   // of workgroup rounds times the work per workgroup, plus a small cost per slab.
@@ -2732,11 +2764,11 @@ static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int
     return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP,
                 "plan workspace (%zu bytes of Lanczos panels): %s", ring_bytes, hipGetErrorString(e));
   }
-  p->bytes = ring_bytes + ncoef * 8 + nscal * 8 + npart * 8 + (bp + 2 * bp * deg) * 8 + t_slabs * (size_t)p->slot_stride * p->esz + t2_bytes;
+  p->bytes = ring_bytes + ncoef * 8 + nscal * 8 + npart * 8 + (bp + 2 * bp * hist) * 8 + t_slabs * (size_t)p->slot_stride * p->esz + t2_bytes + nmom * bp * 8;
   double *s = p->scal;
-  p->st.alpha = s; s += (size_t)(deg + 1) * bp;
+  p->st.alpha = s; s += (size_t)(hist + 1) * bp;
   s += (size_t)orth * bp;  // nu rows for t = -orth .. -1 (zero unless the drop-in entry preloads stale columns)
-  p->st.nu = s; s += (size_t)(deg + 1) * bp;
+  p->st.nu = s; s += (size_t)(hist + 1) * bp;
   p->st.vnorm2 = s; s += bp;
   p->st.coefA = s; s += 2 * bp;
   p->st.coefB = s; s += bp;
@@ -2754,7 +2786,7 @@ static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int
   p->st.nprobes = nprobes;
   p->st.deg = deg;
   p->nodes_d = p->quad_d + bp;
-  p->weights_d = p->nodes_d + bp * (size_t)deg;
+  p->weights_d = p->nodes_d + bp * (size_t)hist;
   p->nstale = 0;
   {
     hipError_t ze = hipMemsetAsync(p->scal, 0, nscal * 8, ctx->stream);
@@ -3731,8 +3763,10 @@ static int launch_separate(const RunFrame &c, const seq::StepShape &s, int j) {
   return SLQ_OK;
 }
 
-// the sweeps' first launch: W_n = A W_c - (three-term part) with the alpha partials, by the kernel of the operator's kind
-static int launch_sweep_product(const RunFrame &c, const seq::StepShape &s, int j) {
+// the sweeps' first launch: W_n = A W_c - (three-term part) with the alpha partials, by the kernel of the operator's kind.
+// cheb: a Chebyshev step - no k_fin_alpha (nothing reads the alpha partials), and the unfused product's epilogue is
+// k_cheb_3term, which closes the step's vector work; after the other products the caller runs k_cheb_axpy
+static int launch_sweep_product(const RunFrame &c, const seq::StepShape &s, int j, bool cheb = false) {
   slq_plan *p = c.p;
   const slq_operator *op = p->op;
   hipStream_t st = c.st;
@@ -3774,12 +3808,19 @@ static int launch_sweep_product(const RunFrame &c, const seq::StepShape &s, int 
       break;
     default:
       SLQ_TRY(apply_operator_unfused(p, sc_));
+      if (cheb)
+        PROFILED(p, SLQ_K_AXPY_NORM,
+                 DISPATCH(p->dtype, p->LPR,
+                          (k_cheb_3term<F, L><<<c.gS, dim3(kBlock), 0, st>>>(p->n, (const F *)p->T, (const F *)slot_ptr(p, sc_), (const F *)slot_ptr(p, sp_),
+                                                                             (F *)slot_ptr(p, sn_), p->st.coefA, p->st.coefB, p->part, bp, first))));
+      else
       PROFILED(p, SLQ_K_AXPY_NORM,
                DISPATCH(p->dtype, p->LPR,
                         (k_3term<F, L><<<c.gS, dim3(kBlock), 0, st>>>(p->n, (const F *)p->T, (const F *)slot_ptr(p, sc_), (const F *)slot_ptr(p, sp_),
                                                                       (F *)slot_ptr(p, sn_), p->st.coefA, p->part, bp, first))));
       break;
   }
+  if (cheb) return SLQ_OK;
   PROFILED(p, SLQ_K_FINALIZE, hipLaunchKernelGGL(k_fin_alpha, c.gF, dim3(kFinThreads), 0, st, p->st, p->part, nblk, j, 0));
   return SLQ_OK;
 }
@@ -3818,11 +3859,10 @@ static int launch_sweeps(const RunFrame &c, const seq::StepShape &s, int j) {
 // enqueue the launch sequence of steps [j0, j1) on the context stream (also run under stream capture). Between steps the whole
 // state of a run lives on the device; the host carries p->prev_xt, read here at j0 and left as step j1 - 1 sets it.
 // What a step launches is step_shape's answer (slq_sequence.hpp); the functions above launch it and decide nothing.
-static int enqueue_run(slq_plan *p, double rtol, int j0, int j1) {
-  hipStream_t st = p->ctx->stream;
-  const int bp = p->bpad, deg = p->deg;
+static RunFrame run_frame(slq_plan *p, double rtol) {
+  const int bp = p->bpad;
   RunFrame c;
-  c.p = p, c.st = st, c.nt = p->sw.nt != 0;
+  c.p = p, c.st = p->ctx->stream, c.nt = p->sw.nt != 0;
   c.eps = p->dtype == SLQ_F64 ? std::numeric_limits<double>::epsilon() : (double)std::numeric_limits<float>::epsilon();
   c.residual_tol = std::sqrt((double)p->n) * rtol;   // lanczos.h:110
   c.orth_tol = 2.0 * c.eps * std::sqrt((double)p->n);  // lanczos.h:53
@@ -3830,6 +3870,13 @@ static int enqueue_run(slq_plan *p, double rtol, int j0, int j1) {
   c.gAf = dim3(p->nblkF, p->NP), c.gT = dim3(p->nblkT, p->NP);
   c.lds0 = sizeof(double) * kWaves * 64 * (p->dtype == SLQ_F64 ? 2 : 4);
   memset(&c.om_off, 0, sizeof(c.om_off));
+  return c;
+}
+
+static int enqueue_run(slq_plan *p, double rtol, int j0, int j1) {
+  hipStream_t st = p->ctx->stream;
+  const int bp = p->bpad, deg = p->deg;
+  const RunFrame c = run_frame(p, rtol);
   if (j0 == 0) {
     // alpha and nu[1..] start from zero (the reference's fresh np.zeros buffers, lanczos.py:101-102)
     HIP_TRY(hipMemsetAsync(p->st.alpha, 0, (size_t)(deg + 1) * bp * 8, st));
@@ -3866,16 +3913,147 @@ static int enqueue_run(slq_plan *p, double rtol, int j0, int j1) {
   return SLQ_OK;
 }
 
+// ---- Chebyshev moments (kernels in slq_cheb.hpp) ------------------------------------------------------
+extern "C" int slq_plan_create_chebyshev(slq_context *ctx, slq_operator *op, int nprobes, int nsteps, slq_plan **out) {
+  return plan_create_mode(ctx, op, nprobes, nsteps, 0, 0, out, true);
+}
+
+extern "C" int slq_debug_cheb_step_shape(const int *facts, int nfacts, int j, int *out, int nout) {
+  if (!facts || !out || nfacts != seq::kNumFacts || nout != seq::kNumChebShape) return fail(SLQ_EINVAL, "slq_debug_cheb_step_shape: %d facts in, %d values out", seq::kNumFacts, seq::kNumChebShape);
+  seq::cheb_shape_to_array(seq::cheb_step_shape(seq::facts_from_array(facts), j), out);
+  return SLQ_OK;
+}
+
+// Step j is the update pass cheb_step_shape names (or the product kernel and k_cheb_axpy where the plan takes sweeps) and one
+// k_fin_cheb: a strict subset of the orth-0 Lanczos step's launches. Enqueued directly on the context stream.
+extern "C" int slq_plan_run_chebyshev(slq_plan *p, double center, double halfwidth, double outside_tol) {
+  if (!p) return fail(SLQ_EINVAL, "plan is NULL");
+  SLQ_TRY(need_chebyshev(p, "slq_plan_run_chebyshev"));
+  if (!p->probes_ready) return fail(SLQ_EINVAL, "slq_plan_run_chebyshev: set or generate probes first");
+  if (!std::isfinite(center) || !std::isfinite(halfwidth) || !(halfwidth > 0.0))
+    return fail(SLQ_EINVAL, "slq_plan_run_chebyshev: center = %g, halfwidth = %g (finite, halfwidth > 0)", center, halfwidth);
+  HIP_TRY(hipSetDevice(p->ctx->device));
+  hipStream_t st = p->ctx->stream;
+  const int bp = p->bpad, S = p->S;
+  const RunFrame c = run_frame(p, 0.0);
+  const double tol = outside_tol > 0.0 ? outside_tol : kChebOutsideTol;
+  const double inv_h = 1.0 / halfwidth, c_over_h = center / halfwidth;
+  const int sphere = p->pdf_sphere ? 1 : 0;
+  const seq::SequenceFacts facts = sequence_facts(p);
+  // mu_0: the probes' norm sweep once more (one read of the panel per run), reduced with the error terms carried (k_fin_cheb)
+  PROFILED(p, SLQ_K_AXPY_NORM,
+           DISPATCH(p->dtype, p->LPR,
+                    (k_axpy_norm<F, L, 1><<<c.gS, dim3(kBlock), 0, st>>>(p->n, (F *)slot_ptr(p, 0), (const F *)nullptr, (const double *)nullptr, p->part, bp))));
+  PROFILED(p, SLQ_K_FINALIZE,
+           hipLaunchKernelGGL(k_fin_cheb, c.gF, dim3(kFinThreads), 0, st, p->st, p->part, p->nblkS, -1, p->cheb_mu, p->cheb_out, inv_h, c_over_h, tol, sphere));
+  for (int j = 0; j < p->deg; ++j) {
+    const seq::ChebStepShape s = seq::cheb_step_shape(facts, j);
+    seq::StepShape l;  // (what the launchers of the Lanczos step read of a shape)
+    l.tiled = s.tiled, l.gen = s.gen, l.pipe_on = s.pipe_on, l.product = s.product, l.blk_alpha = s.blk_product;
+    int nblk = c.blocks(s.blk);
+    if (!s.sweeps) {
+      PROFILED(p, SLQ_K_AXPY_NORM, SLQ_TRY(launch_fused_pass<PASS_UPDATE>(c, l, j, 0, c.lds_fused(l), s.xt_update)));
+    } else {
+      SLQ_TRY(launch_sweep_product(c, l, j, true));
+      if (s.product != seq::PRODUCT_UNFUSED)
+        PROFILED(p, SLQ_K_AXPY_NORM,
+                 DISPATCH(p->dtype, p->LPR,
+                          (k_cheb_axpy<F, L><<<c.gS, dim3(kBlock), 0, st>>>(p->n, (F *)slot_ptr(p, (j + 1) % S), (const F *)slot_ptr(p, j % S), p->st.coefB, p->part, bp))));
+      nblk = p->nblkS;
+    }
+    PROFILED(p, SLQ_K_FINALIZE,
+             hipLaunchKernelGGL(k_fin_cheb, c.gF, dim3(kFinThreads), 0, st, p->st, p->part, nblk, j, p->cheb_mu, p->cheb_out, inv_h, c_over_h, tol, sphere));
+  }
+  HIP_TRY(hipGetLastError());
+  p->probes_ready = false;
+  p->cheb_ran = true;
+  p->cheb_c = center, p->cheb_h = halfwidth;
+  if (p->launch_error) {
+    p->launch_error = false;
+    p->cheb_ran = false;
+    return fail(SLQ_EINVAL, "internal: a pass of the launch sequence had no kernel for this plan's tiles");
+  }
+  return SLQ_OK;
+}
+
+// the outside flags and the ring bail-out word of the last Chebyshev run (synchronises); *raised = probes whose flag is up
+static int cheb_flags(slq_plan *p, std::vector<int> &flags, int *raised) {
+  hipStream_t st = p->ctx->stream;
+  flags.assign((size_t)p->nprobes, 0);
+  int ring_bad = 0;
+  HIP_TRY(hipMemcpyAsync(flags.data(), p->cheb_out, (size_t)p->nprobes * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&ring_bad, p->ring_fail_d, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  SLQ_TRY(ring_flag_status(ring_bad));
+  *raised = 0;
+  for (int f : flags) *raised += f != 0;
+  return SLQ_OK;
+}
+static int cheb_outside_error(const slq_plan *p, const char *who, int raised) {
+  return fail(SLQ_EINVAL, "%s: %d of %d probes saw a moment above mu_0: the spectrum is not inside the bounds [%.17g, %.17g] of the run", who, raised,
+              p->nprobes, p->cheb_c - p->cheb_h, p->cheb_c + p->cheb_h);
+}
+
+extern "C" int slq_plan_get_moments(slq_plan *p, double *mu, int *outside) {
+  if (!p) return fail(SLQ_EINVAL, "plan is NULL");
+  SLQ_TRY(need_chebyshev(p, "slq_plan_get_moments"));
+  if (!p->cheb_ran) return fail(SLQ_EINVAL, "slq_plan_get_moments: no completed run");
+  HIP_TRY(hipSetDevice(p->ctx->device));
+  hipStream_t st = p->ctx->stream;
+  const int bp = p->bpad, P = p->nprobes;
+  const size_t K = (size_t)2 * p->deg + 1;
+  std::vector<double> h;
+  if (mu) {
+    h.resize(K * bp);
+    HIP_TRY(hipMemcpyAsync(h.data(), p->cheb_mu, h.size() * 8, hipMemcpyDeviceToHost, st));
+  }
+  std::vector<int> flags;
+  int raised = 0;
+  SLQ_TRY(cheb_flags(p, flags, &raised));
+  if (mu)
+    for (int i = 0; i < P; ++i)
+      for (size_t k = 0; k < K; ++k) mu[(size_t)i * K + k] = h[k * bp + i];
+  if (outside) memcpy(outside, flags.data(), (size_t)P * sizeof(int));
+  return SLQ_OK;
+}
+
+extern "C" int slq_plan_moment_sum(slq_plan *p, int ncoef, const double *coef, double *quad, double *stage) {
+  if (!p || !coef) return fail(SLQ_EINVAL, "plan/coef is NULL");
+  SLQ_TRY(need_chebyshev(p, "slq_plan_moment_sum"));
+  if (!p->cheb_ran) return fail(SLQ_EINVAL, "slq_plan_moment_sum: no completed run");
+  const int K = 2 * p->deg + 1, P = p->nprobes;
+  if (ncoef < 1 || ncoef > K) return fail(SLQ_EINVAL, "slq_plan_moment_sum: ncoef = %d must lie in [1, %d] (2 nsteps + 1 moments)", ncoef, K);
+  HIP_TRY(hipSetDevice(p->ctx->device));
+  hipStream_t st = p->ctx->stream;
+  std::vector<int> flags;
+  int raised = 0;
+  SLQ_TRY(cheb_flags(p, flags, &raised));
+  if (raised) return cheb_outside_error(p, "slq_plan_moment_sum", raised);
+  double *stage_d = p->cheb_coef + K;
+  HIP_TRY(hipMemcpyAsync(p->cheb_coef, coef, (size_t)ncoef * 8, hipMemcpyHostToDevice, st));
+  PROFILED(p, SLQ_K_QUADRATURE,
+           hipLaunchKernelGGL(k_moment_sum, dim3((P + 63) / 64), dim3(64), 0, st, P, p->bpad, ncoef, (const double *)p->cheb_coef, (const double *)p->cheb_mu, p->quad_d));
+  if (stage)
+    hipLaunchKernelGGL(k_stage_reduce, dim3(1), dim3(kStageThreads), 0, st, P, (const double *)p->quad_d, (const double *)nullptr, stage_d);
+  HIP_TRY(hipGetLastError());
+  if (quad) HIP_TRY(hipMemcpyAsync(quad, p->quad_d, (size_t)P * 8, hipMemcpyDeviceToHost, st));
+  if (stage) HIP_TRY(hipMemcpyAsync(stage, stage_d, 4 * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return SLQ_OK;
+}
+
 static int run_range(slq_plan *p, double rtol, int j0, int j1);
 
 extern "C" int slq_plan_run(slq_plan *p, double rtol) {
   if (!p) return fail(SLQ_EINVAL, "plan is NULL");
+  SLQ_TRY(need_lanczos(p, "slq_plan_run"));
   if (!p->probes_ready) return fail(SLQ_EINVAL, "slq_plan_run: set or generate probes first");
   return run_range(p, rtol, 0, p->deg);
 }
 
 extern "C" int slq_plan_run_steps(slq_plan *p, double rtol, int upto) {
   if (!p) return fail(SLQ_EINVAL, "plan is NULL");
+  SLQ_TRY(need_lanczos(p, "slq_plan_run_steps"));
   if (p->nstale > 0) return fail(SLQ_EINVAL, "slq_plan_run_steps: a plan with stale ring columns is not resumable");
   if (p->basis_mode == 2) return fail(SLQ_EINVAL, "slq_plan_run_steps: a recompute plan runs in one piece (a staged two-pass run is not supported)");
   const bool fresh = p->probes_ready;  // (probes set or generated and not yet consumed: cur == 0)
@@ -3968,6 +4146,7 @@ static int need_finished_run(const slq_plan *p, const char *who) {
 
 extern "C" int slq_plan_get_tridiag(slq_plan *p, void *alpha, void *beta, int32_t *steps) {
   if (!p) return fail(SLQ_EINVAL, "plan is NULL");
+  SLQ_TRY(need_lanczos(p, "slq_plan_get_tridiag"));
   if (!p->ran) return fail(SLQ_EINVAL, "slq_plan_get_tridiag: no completed run");
   HIP_TRY(hipSetDevice(p->ctx->device));
   hipStream_t st = p->ctx->stream;
@@ -4001,6 +4180,7 @@ extern "C" int slq_plan_get_tridiag(slq_plan *p, void *alpha, void *beta, int32_
 extern "C" int slq_plan_quadrature(slq_plan *p, int fun_id, const double *fun_params, double *quad,
                                    double *nodes, double *weights) {
   if (!p) return fail(SLQ_EINVAL, "plan is NULL");
+  SLQ_TRY(need_lanczos(p, "slq_plan_quadrature"));
   SLQ_TRY(need_finished_run(p, "slq_plan_quadrature"));
   if (fun_id < SLQ_FUN_NONE || fun_id > SLQ_FUN_SOFTSIGN) return fail(SLQ_EINVAL, "Unknown function id %d.", fun_id);
   HIP_TRY(hipSetDevice(p->ctx->device));
@@ -4045,6 +4225,7 @@ extern "C" int slq_plan_quadrature(slq_plan *p, int fun_id, const double *fun_pa
 extern "C" int slq_plan_quadrature_at(slq_plan *p, int m, int rule, double endpoint, int fun_id, const double *fun_params,
                                       double *quad, double *nodes, double *weights, double *stage) {
   if (!p) return fail(SLQ_EINVAL, "plan is NULL");
+  SLQ_TRY(need_lanczos(p, "slq_plan_quadrature_at"));
   if (!p->ran || p->cur < 1) return fail(SLQ_EINVAL, "slq_plan_quadrature_at: no steps done");
   if (m < 1 || m > p->cur) return fail(SLQ_EINVAL, "slq_plan_quadrature_at: m = %d must lie in [1, %d] (steps done)", m, p->cur);
   if (rule != 0 && rule != 1) return fail(SLQ_EINVAL, "slq_plan_quadrature_at: rule %d (0 Gauss, 1 Gauss-Radau)", rule);
@@ -4096,12 +4277,14 @@ extern "C" int slq_plan_quadrature_at(slq_plan *p, int m, int rule, double endpo
 // (tests/test_gpu_resume.py: such a plan is not resumable). Mark it back to 0 before any run.
 extern "C" int slq_debug_plan_mark_stale(slq_plan *p, int nstale) {
   if (!p || nstale < 0) return fail(SLQ_EINVAL, "plan is NULL or nstale < 0");
+  SLQ_TRY(need_lanczos(p, "slq_debug_plan_mark_stale"));
   p->nstale = nstale;
   return SLQ_OK;
 }
 
 extern "C" int slq_plan_get_basis(slq_plan *p, int probe, void *Q, int64_t ldq) {
   if (!p || !Q) return fail(SLQ_EINVAL, "plan/Q is NULL");
+  SLQ_TRY(need_lanczos(p, "slq_plan_get_basis"));
   if (!p->keep_basis) return fail(SLQ_EINVAL, "plan was created without keep_basis");
   SLQ_TRY(need_finished_run(p, "slq_plan_get_basis"));
   if (probe < 0 || probe >= p->nprobes || ldq < p->n) return fail(SLQ_EINVAL, "bad probe index or ldq");
@@ -4232,6 +4415,7 @@ static int replay_action(slq_plan *p) {
 
 // Y = f(A) X on the device: result left in panel y_slot (kept basis: ring slot `deg`; recompute: behind the ring)
 static int fun_action_device(slq_plan *p, int fun_id, const double *fun_params) {
+  SLQ_TRY(need_lanczos(p, "slq_plan_fun_action / slq_diag_update"));
   if (p->basis_mode == 0) return fail(SLQ_EINVAL, "plan was created without keep_basis");
   const bool two_pass = p->basis_mode == 2;
   SLQ_TRY(need_finished_run(p, "slq_plan_fun_action / slq_diag_update"));
@@ -4319,6 +4503,7 @@ extern "C" int slq_diag_destroy(slq_diag *d) {
 
 extern "C" int slq_diag_update(slq_diag *d, slq_plan *p, int fun_id, const double *fun_params) {
   if (!d || !p) return fail(SLQ_EINVAL, "diag/plan is NULL");
+  SLQ_TRY(need_lanczos(p, "slq_diag_update"));
   if (d->n != p->n || d->ctx != p->ctx) return fail(SLQ_EINVAL, "diag accumulator does not match the plan");
   if (d->op && d->op != p->op) return fail(SLQ_EINVAL, "diag accumulator was started with another operator");
   d->op = p->op;
@@ -4373,12 +4558,13 @@ struct slq_density {
   int *flags;        // [0] QL non-convergence, [1] ring bail-out word of a plan
   double *phi;       // P x (G + 2) scratch of the per-probe values
   int64_t phi_cap;   // probes the scratch holds
+  std::vector<double> grid_h;  // SLQ_DENSITY_CHEBYSHEV: the grid on the host (checked against the bounds of every run folded in)
 };
 
 extern "C" int slq_density_create(slq_context *ctx, int kind, int ngrid, const double *grid, double bw, slq_density **out) {
   if (!ctx || !out || !grid) return fail(SLQ_EINVAL, "slq_density_create: NULL argument");
   *out = nullptr;
-  if (kind < SLQ_DENSITY_GAUSSIAN || kind > SLQ_DENSITY_CDF) return fail(SLQ_EINVAL, "slq_density_create: unknown kind %d", kind);
+  if (kind < SLQ_DENSITY_GAUSSIAN || kind > SLQ_DENSITY_CHEBYSHEV) return fail(SLQ_EINVAL, "slq_density_create: unknown kind %d", kind);
   if (ngrid < 1) return fail(SLQ_EINVAL, "slq_density_create: ngrid = %d < 1", ngrid);
   const int npts = ngrid + (kind == SLQ_DENSITY_HISTOGRAM ? 1 : 0);
   for (int i = 0; i < npts; ++i) {
@@ -4395,6 +4581,7 @@ extern "C" int slq_density_create(slq_context *ctx, int kind, int ngrid, const d
   if (kind == SLQ_DENSITY_GAUSSIAN) { d->c0 = 1.0 / (2.0 * bw * bw); d->c1 = 1.0 / (bw * std::sqrt(2.0 * M_PI)); }
   if (kind == SLQ_DENSITY_LORENTZIAN) { d->c0 = bw * bw; d->c1 = bw / M_PI; }
   d->grid = d->stat = d->phi = nullptr; d->flags = nullptr; d->phi_cap = 0;
+  if (kind == SLQ_DENSITY_CHEBYSHEV) d->grid_h.assign(grid, grid + ngrid);
   const size_t G2 = (size_t)ngrid + 2;
   hipError_t e = hipMalloc((void **)&d->grid, (size_t)npts * 8);
   if (e == hipSuccess) e = hipMalloc((void **)&d->stat, 2 * G2 * 8 + 2 * sizeof(int));
@@ -4426,24 +4613,67 @@ extern "C" int slq_density_destroy(slq_density *d) {
   return SLQ_OK;
 }
 
+// the P x (G + 2) scratch of an update
+static int density_scratch(slq_density *d, int P, hipStream_t st) {
+  const int G2 = d->G + 2;
+  if (d->phi_cap >= P) return SLQ_OK;
+  if (d->phi) {
+    HIP_TRY(hipStreamSynchronize(st));  // (the old scratch may still be read by the previous update)
+    hipFree(d->phi);
+    d->phi = nullptr;
+    d->phi_cap = 0;
+  }
+  hipError_t e = hipMalloc((void **)&d->phi, (size_t)P * G2 * 8);
+  if (e != hipSuccess) return fail(SLQ_ENOMEM, "density scratch (%zu bytes): %s", (size_t)P * G2 * 8, hipGetErrorString(e));
+  d->phi_cap = P;
+  return SLQ_OK;
+}
+
+// The density of the kernel polynomial method from the moments of a plan's last Chebyshev run (k_cheb_density_eval), folded by
+// the same k_density_fold as every other kind. Synchronises once (the outside flags of the run decide whether it may be folded).
+extern "C" int slq_density_update_moments(slq_density *d, slq_plan *p, int nweights, const double *damp) {
+  if (!d || !p) return fail(SLQ_EINVAL, "slq_density_update_moments: density/plan is NULL");
+  if (d->ctx != p->ctx) return fail(SLQ_EINVAL, "slq_density_update_moments: the plan belongs to another context");
+  if (d->kind != SLQ_DENSITY_CHEBYSHEV) return fail(SLQ_EINVAL, "slq_density_update_moments: the accumulator's kind is %d, not SLQ_DENSITY_CHEBYSHEV", d->kind);
+  SLQ_TRY(need_chebyshev(p, "slq_density_update_moments"));
+  if (!p->cheb_ran) return fail(SLQ_EINVAL, "slq_density_update_moments: no completed run");
+  const int K = 2 * p->deg + 1, P = p->nprobes, G2 = d->G + 2;
+  if (nweights < 1 || nweights > K) return fail(SLQ_EINVAL, "slq_density_update_moments: nweights = %d must lie in [1, %d] (2 nsteps + 1 moments)", nweights, K);
+  const double lo = p->cheb_c - p->cheb_h, hi = p->cheb_c + p->cheb_h;
+  for (int g = 0; g < d->G; ++g)
+    if (!(d->grid_h[g] > lo && d->grid_h[g] < hi))
+      return fail(SLQ_EINVAL, "slq_density_update_moments: grid[%d] = %.17g is not strictly inside the bounds (%.17g, %.17g) of the run", g, d->grid_h[g], lo, hi);
+  HIP_TRY(hipSetDevice(p->ctx->device));
+  hipStream_t st = p->ctx->stream;
+  if (damp) HIP_TRY(hipMemcpyAsync(p->cheb_coef, damp, (size_t)nweights * 8, hipMemcpyHostToDevice, st));  // (ahead of the synchronisation below: the caller's array may go away on return)
+  std::vector<int> flags;
+  int raised = 0;
+  SLQ_TRY(cheb_flags(p, flags, &raised));
+  if (raised) return cheb_outside_error(p, "slq_density_update_moments", raised);
+  SLQ_TRY(density_scratch(d, P, st));
+  const int nbg = (G2 + kDensEvalThreads - 1) / kDensEvalThreads;
+  PROFILED(p, SLQ_K_QUADRATURE,
+           hipLaunchKernelGGL(k_cheb_density_eval, dim3((unsigned)((int64_t)P * nbg)), dim3(kDensEvalThreads), 0, st, d->G, nweights, p->bpad,
+                              (const double *)p->cheb_mu, damp ? (const double *)p->cheb_coef : (const double *)nullptr, (const double *)d->grid,
+                              p->cheb_c, p->cheb_h, nbg, d->phi));
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_density_fold, dim3((G2 + 63) / 64), dim3(64 * kDensFoldWaves), 0, st, P, G2, d->count, d->phi, d->stat, d->stat + G2,
+                     (const int *)nullptr, 0, (const int *)p->ring_fail_d, d->flags);
+  HIP_TRY(hipGetLastError());
+  d->count += P;
+  return SLQ_OK;
+}
+
 extern "C" int slq_density_update(slq_density *d, slq_plan *p) {
   if (!d || !p) return fail(SLQ_EINVAL, "slq_density_update: density/plan is NULL");
   if (d->ctx != p->ctx) return fail(SLQ_EINVAL, "slq_density_update: the plan belongs to another context");
+  SLQ_TRY(need_lanczos(p, "slq_density_update"));
+  if (d->kind == SLQ_DENSITY_CHEBYSHEV) return fail(SLQ_EINVAL, "slq_density_update: a Chebyshev density is updated from moments (slq_density_update_moments)");
   SLQ_TRY(need_finished_run(p, "slq_density_update"));
   HIP_TRY(hipSetDevice(p->ctx->device));
   hipStream_t st = p->ctx->stream;
   const int P = p->nprobes, deg = p->deg, G2 = d->G + 2;
-  if (d->phi_cap < P) {
-    if (d->phi) {
-      HIP_TRY(hipStreamSynchronize(st));  // (the old scratch may still be read by the previous update)
-      hipFree(d->phi);
-      d->phi = nullptr;
-      d->phi_cap = 0;
-    }
-    hipError_t e = hipMalloc((void **)&d->phi, (size_t)P * G2 * 8);
-    if (e != hipSuccess) return fail(SLQ_ENOMEM, "density scratch (%zu bytes): %s", (size_t)P * G2 * 8, hipGetErrorString(e));
-    d->phi_cap = P;
-  }
+  SLQ_TRY(density_scratch(d, P, st));
   // the Gauss rule of this run: once per run, whoever asks first (slq_plan_quadrature or a density update)
   int *rule_fail = p->fail_d + 2;
   if (p->rule_src == 0) {

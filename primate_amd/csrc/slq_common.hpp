@@ -56,6 +56,10 @@ constexpr int kBlock = 512;          // threads per workgroup for the sweep kern
 constexpr int kWaves = kBlock / 64;
 constexpr int kReorthChunk = 16;     // reorth columns whose dot accumulators live in registers
 constexpr int kMaxDeg = 512;
+constexpr int kMaxChebSteps = 16384;  // steps of a Chebyshev plan (2 * steps + 1 moments per probe; slq_cheb.hpp)
+// |mu_k| > (1 + tol) mu_0 raises a probe's `outside` flag (k_fin_cheb): the default tol. Inside the bounds |mu_k| <= mu_0 up to
+// rounding; DESIGN.md §4.12 records the largest excess seen per dtype, which this sits 100x above at least.
+constexpr double kChebOutsideTol = 1e-3;
 constexpr int kFusedMaxR = 8;        // fused recompute passes handle up to this many reorth columns
 #ifndef SLQ_UPD_UR
 #define SLQ_UPD_UR 2

@@ -181,5 +181,44 @@ inline int plan_sequence_of(const SequenceFacts &f) {
   }
 }
 
+// ---- Chebyshev runs (slq_cheb.hpp) ----------------------------------------------------------------
+// A Chebyshev step w_{j+1} = 2 A~ w_j - w_{j-1} IS the update pass of the orth-0 Lanczos step with constant coefficients:
+// no alpha pass, no dots pass. What it launches is therefore read off step_shape's answer for the same facts at orth = 0 (deg =
+// the number of Chebyshev steps), so that a plan takes the same kernels for both kinds of run.
+struct ChebStepShape {
+  int sweeps = 1;          // 1: product kernel, then k_cheb_axpy (k_cheb_3term after an unfused product); 0: one fused update pass
+  int tiled = 0;           // the update pass runs on the plan's tiles
+  int gen = 0;             // ... through k_ring_pass (fused), or the sweeps' ring product through it
+  int pipe_on = 0;         // pipelined row loop in the generic update pass
+  int xt_update = 1;       // complete xt word of the update pass: bit 0 cross term (always), bit 2 reverse sweep, bit 4 (16) stores nothing
+  int product = PRODUCT_UNFUSED;  // sweeps: which kernel forms A W_j
+  int blk_product = BLK_S; // sweeps: the grid of the product kernel (its alpha partials are not read)
+  int blk = BLK_S;         // the grid behind the norm and cross partials k_fin_cheb reduces
+  int alpha_pass = 0;      // always 0: a Chebyshev step has no alpha pass
+};
+constexpr int kNumChebShape = 9;
+
+inline void cheb_shape_to_array(const ChebStepShape &s, int *out) {
+  const int v[kNumChebShape] = {s.sweeps, s.tiled, s.gen, s.pipe_on, s.xt_update, s.product, s.blk_product, s.blk, s.alpha_pass};
+  for (int i = 0; i < kNumChebShape; ++i) out[i] = v[i];
+}
+
+inline ChebStepShape cheb_step_shape(const SequenceFacts &facts, int j) {
+  SequenceFacts f = facts;
+  f.orth = 0, f.nstale = 0;
+  const StepShape l = step_shape(f, j, false);
+  ChebStepShape s;
+  if (l.seq == SEQ_SWEEPS_PLAIN) {
+    s.sweeps = 1, s.gen = l.gen, s.product = l.product, s.blk_product = l.blk_alpha;
+    s.blk = BLK_S;  // (k_cheb_axpy / k_cheb_3term run on the streaming grid, as k_axpy_norm does)
+    s.xt_update = 1;
+    return s;
+  }
+  // (orth = 0 leaves SEQ_SEPARATE only: r = 0 rules out the merged, stored-u and Gram sequences)
+  s.sweeps = 0, s.tiled = l.tiled, s.gen = l.gen, s.pipe_on = l.pipe_on, s.blk = l.blk_beta;
+  s.xt_update = l.xt_update | 1;  // the cross term is a moment: always reduced, whatever SLQ_CROSS says
+  return s;
+}
+
 }  // namespace seq
 }  // namespace slq

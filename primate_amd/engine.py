@@ -512,6 +512,54 @@ RULE_IDS = {"gauss": 0, "radau": 1}
 DEG_STEP = 5
 
 
+class ChebyshevPlan(LanczosPlan):
+	"""Workspace + state of one batched Chebyshev run (the kernel polynomial method; slq_plan_create_chebyshev): `nsteps`
+	steps w_{j+1} = 2 A~ w_j - w_{j-1}, A~ = (A - c) / h, give the moments mu_k = v^T T_k(A~) v for k = 0 .. 2 nsteps per
+	probe. No orthogonality, no eigensolve, no cap at 512 steps (nsteps <= 16384). The probe methods, `describe`,
+	`workspace_bytes`, `profile_*` and `close` are LanczosPlan's; its Lanczos entries raise ValueError on such a plan."""
+
+	def __init__(self, op: DeviceOperator, nprobes: int, nsteps: int):
+		self.op = op
+		self.nprobes = int(nprobes)
+		self.nsteps = int(nsteps)
+		self.nmoments = 2 * self.nsteps + 1
+		self.deg, self.orth, self.keep_basis, self.basis_kind = self.nsteps, 0, False, None
+		self.bounds = None
+		h = C.c_void_p()
+		check(_capi.lib().slq_plan_create_chebyshev(op.ctx._h, op._h, self.nprobes, self.nsteps, C.byref(h)))
+		self._h = h
+
+	def run(self, bounds, outside_tol: float = 0.0):
+		"""Enqueue the nsteps steps for the probes set or generated last. bounds = (a, b) must contain the spectrum:
+		where it does not, the probe's `outside` flag goes up (|mu_k| > (1 + outside_tol) mu_0; 0: the library's default)."""
+		a, b = (float(v) for v in bounds)
+		if not (np.isfinite(a) and np.isfinite(b) and a < b):
+			raise ValueError(f"bounds must be finite with a < b, got {bounds!r}")
+		rc = _capi.lib().slq_plan_run_chebyshev(self._h, 0.5 * (a + b), 0.5 * (b - a), float(outside_tol))
+		if rc == _capi.SLQ_ECALLBACK and getattr(self.op, "error", None) is not None:
+			raise self.op.error
+		check(rc)
+		self.bounds = (a, b)
+
+	def moments(self, return_outside: bool = False):
+		"""mu (nprobes, 2 nsteps + 1) of the last run, and with return_outside the per-probe flags (slq_plan_get_moments)."""
+		mu = np.zeros((self.nprobes, self.nmoments))
+		out = np.zeros(self.nprobes, dtype=np.int32)
+		check(_capi.lib().slq_plan_get_moments(self._h, ptr(mu), ptr(out)))
+		return (mu, out) if return_outside else mu
+
+	def moment_sum(self, coef: np.ndarray, return_stage: bool = False):
+		"""quad[i] = sum_k coef[k] mu[i, k], reduced on the device (slq_plan_moment_sum): with the Chebyshev coefficients of f
+		on the bounds of the run (chebyshev.chebyshev_coefficients), v_i^T f(A) v_i. ValueError if an `outside` flag is up."""
+		coef = np.ascontiguousarray(coef, dtype=np.float64).ravel()
+		if not 1 <= coef.size <= self.nmoments:
+			raise ValueError(f"{coef.size} coefficients for {self.nmoments} moments")
+		quad = np.zeros(self.nprobes)
+		stage = np.zeros(4) if return_stage else None
+		check(_capi.lib().slq_plan_moment_sum(self._h, int(coef.size), ptr(coef), ptr(quad), ptr(stage)))
+		return (quad, stage) if return_stage else quad
+
+
 def _rule_args(rule, endpoint) -> tuple:
 	"""(rule id, endpoint) of `quadrature_at`, checked before any device work."""
 	if rule not in RULE_IDS:
@@ -796,8 +844,9 @@ class DiagAccumulator:
 class DensityAccumulator:
 	"""Device-resident (count, mean, M2) of a spectral density estimate over a fixed grid (slq_density_*): every
 	`update(plan)` folds the per-probe values ||v||^2 sum_k tau_k K(x_g, theta_k) of a completed run, in probe order.
-	kind: "gaussian" | "lorentzian" (G points, bandwidth bw > 0), "histogram" (G bins: G + 1 edges) or "cdf"
-	(G thresholds)."""
+	kind: "gaussian" | "lorentzian" (G points, bandwidth bw > 0), "histogram" (G bins: G + 1 edges), "cdf"
+	(G thresholds) or "chebyshev" (G points strictly inside the bounds of the runs folded in; bw ignored): the density of
+	the kernel polynomial method from the moments of a ChebyshevPlan."""
 
 	def __init__(self, kind: str, grid: np.ndarray, bw: float = 0.0, ctx: Optional[Context] = None):
 		if kind not in _capi.DENSITY_KINDS:
@@ -810,8 +859,21 @@ class DensityAccumulator:
 		check(_capi.lib().slq_density_create(self.ctx._h, _capi.DENSITY_KINDS[kind], int(self.ngrid), ptr(self.grid), float(bw), C.byref(h)))
 		self._h = h
 
-	def update(self, plan: LanczosPlan):
-		"""Asynchronous on the context stream; the QL of the run is shared with `plan.quadrature`."""
+	def update(self, plan: LanczosPlan, damping=None, nweights: Optional[int] = None):
+		"""Asynchronous on the context stream; the QL of the run is shared with `plan.quadrature`.
+		kind "chebyshev": `plan` is a ChebyshevPlan; the first `nweights` moments (default: all, or len(damping)) are folded
+		with the damping factors `damping` (None: all ones; chebyshev.damping_factors) - slq_density_update_moments."""
+		if self.kind == "chebyshev":
+			if not isinstance(plan, ChebyshevPlan):
+				raise ValueError("a 'chebyshev' density is updated from a ChebyshevPlan")
+			g = None if damping is None else np.ascontiguousarray(damping, dtype=np.float64).ravel()
+			k = int(nweights) if nweights is not None else (plan.nmoments if g is None else g.size)
+			if g is not None and g.size < k:
+				raise ValueError(f"{g.size} damping factors for {k} moments")
+			check(_capi.lib().slq_density_update_moments(self._h, plan._h, k, ptr(g)))
+			return
+		if damping is not None or nweights is not None:
+			raise ValueError("damping and nweights belong to the 'chebyshev' kind")
 		check(_capi.lib().slq_density_update(self._h, plan._h))
 
 	def get(self) -> tuple:

@@ -168,7 +168,8 @@ def _density_result(kernel, mean, m2, outside, cnt, grid, interval, bw, full: bo
 
 def spectral_density(
 	A, bins: int = 200, interval: Optional[tuple] = None, bw: Optional[float] = None, kernel: str = "gaussian", deg: int = 20, orth: int = 3,
-	nprobes: int = 256, batch: int = 256, pdf: str = "rademacher", seed=None, full: bool = False, **kwargs,
+	nprobes: int = 256, batch: int = 256, pdf: str = "rademacher", seed=None, full: bool = False, method: str = "lanczos",
+	damping: Optional[str] = "jackson", **kwargs,
 ):  # fmt: skip
 	"""Spectral density of A by stochastic Lanczos quadrature (Lin, Saad, Yang, SIAM Review 2016), accumulated on the GPU.
 
@@ -184,7 +185,22 @@ def spectral_density(
 	is then fixed. bw=None: (b - a) / deg, the mean spacing of deg nodes over the interval.
 	pdf: host draws are the columns `hutch` draws for the same seed (the `isotropic` stream); "device:<name>" draws
 	Philox probe ids 0, 1, 2, ... on the GPU. full=True also returns `info`: stderr per point, nprobes, interval, bw
-	and outside = the mean node mass (below, above) the grid (in eigenvalue counts)."""
+	and outside = the mean node mass (below, above) the grid (in eigenvalue counts).
+	method="kpm": the kernel polynomial method instead (chebyshev.py) - `deg` is then the polynomial degree (deg + 1 Chebyshev
+	moments from ceil(deg / 2) steps, up to 32768: no Lanczos cap, no reorthogonalisation, resolution ~ (b - a) / deg), `damping`
+	("jackson": a positive kernel, "lanczos", "none") replaces kernel / bw, which must be left at their defaults, and
+	interval=None means the spectral bounds (chebyshev.spectral_bounds), sampled at the midpoints of `bins` cells.
+	A is then the operator itself (kwargs: dtype=...)."""
+	if method not in ("lanczos", "kpm"):
+		raise ValueError(f"unknown method '{method}' (one of lanczos, kpm)")
+	if method == "kpm":
+		if kernel != "gaussian" or bw is not None:
+			raise ValueError("method='kpm' smooths by `damping`: leave kernel and bw at their defaults")
+		bins, interval, _ = _density_args("gaussian", bins, interval, None, nprobes, batch, pdf)
+		from .chebyshev import kpm_density
+
+		mean, m2, outside, cnt, grid, bounds = kpm_density(A, bins, interval, deg, damping, int(nprobes), int(batch), pdf, seed, **kwargs)
+		return _density_result("chebyshev", mean, m2, outside, cnt, grid, bounds, None, full)
 	bins, interval, bw = _density_args(kernel, bins, interval, bw, nprobes, batch, pdf)
 	from .operators import MatrixFunction
 
