@@ -441,6 +441,14 @@ int slq_debug_step_shape(const int *facts, int nfacts, int j, int prev_xt, int *
  * orth = 0): out receives the 9 values of seq::cheb_shape_to_array - sweeps, tiled, gen, pipe_on, the update pass's xt word,
  * the sweeps' product kernel and its grid, the grid behind the partials, alpha_pass (always 0). No HIP call. */
 int slq_debug_cheb_step_shape(const int *facts, int nfacts, int j, int *out, int nout);
+/* The layout a CSR operator over this pattern would be created with, as the library decides it, without a device
+ * (csrc/slq_layout.hpp: layout_prefilter + decide_layout; the operator switches are read from the environment as a creation
+ * reads them). plain != 0: the affine operator's kind (caller's order, no tiles). perm_out [n]: stored row i = caller row
+ * perm_out[i], written only for a reordered operator; tile_row_out [ntiles + 1 <= ntile_cap]: first stored row of every tile,
+ * written only with tiles; xcd_tile_out [9]: the tile range of every XCD chunk; info_out [4]: have_tiles, ntiles, reordered,
+ * rms in-chunk |i - j| of the stored nonzeros. No HIP call. */
+int slq_debug_csr_layout(int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colind, int plain, int32_t *perm_out,
+                         int32_t *tile_row_out, int64_t ntile_cap, int32_t *xcd_tile_out, double *info_out);
 
 /* ---- one-shot entries ---------------------------------------------------------------------------- */
 /* P probes in one call: the batched counterpart of the Python loop at

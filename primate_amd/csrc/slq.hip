@@ -31,6 +31,7 @@
 #include "slq_action.hpp"   // two-pass f(A)v: the accumulation of a recompute plan's replay (slq_plan_create_recompute)
 #include "slq_switches.hpp"  // the table of run-time switches, OperatorSwitches, PlanSwitches
 #include "slq_sequence.hpp"  // what a step launches, as a value (step_shape)
+#include "slq_layout.hpp"    // an operator's layout as a value and the host analysis behind it (layout_prefilter, decide_layout)
 #include "slq_cheb.hpp"      // Chebyshev moments: the kernels of slq_plan_run_chebyshev, _moment_sum, slq_density_update_moments
 
 using namespace slq;
@@ -284,74 +285,7 @@ static_assert(PlanSwitches{}.debug_pass == PASS_ADOTS, "slq_switches.hpp: SLQ_DE
 // one-step innovation the verify mode has seen on the device, and not less than 1); a zero is certified below orth_tol / kOmegaKappa
 constexpr double kOmegaC = 3.5;
 constexpr double kOmegaKappa = 4.0;
-constexpr double kTileMaxColsPerRow = 4.5;      // tiles are kept when a tile row needs at most this many distinct panel rows
-constexpr double kTileAlphaColsPerRow = 2.6;    // upper-triangle tiles: the alpha-only pass takes the ring up to this many landed rows per row (r03: 7-point grids too)
-constexpr double kTileAlphaMergedColsPerRow = 2.6;  // ... and on the merged tiles of narrow panels up to this many (of the unmerged tiles)
 static_assert(PlanSwitches{}.ring_alpha_max_x100 == (int)(100 * kTileAlphaColsPerRow), "slq_switches.hpp: SLQ_RING_ALPHA_MAX_X100");
-constexpr double kTileLevelRows = 320.0;        // level sets the tile sweep's base order should not exceed (csr_create_impl)
-
-
-// Host-side work of an operator's creation (row orders, clusters, tile lists, streams) is cut into independent pieces -
-// XCD chunks, tile ranges, row ranges - and run on a few threads: fn(piece, begin, end) over [0, count). Results never depend
-// on the number of threads (every piece writes its own slots or its own buffer, joined in piece order). SLQ_HOST_THREADS
-// overrides the default of min(16, hardware threads); it is the one switch read where it is used. Exceptions do not leave a worker: the first failure is reported.
-static int host_threads() {
-  const int hw = (int)std::thread::hardware_concurrency();
-  return std::max(1, std::min(64, or_auto(read_host_threads(), std::max(1, std::min(16, hw)))));
-}
-template <typename Fn> static bool parallel_pieces(int pieces, int64_t count, Fn fn) {
-  pieces = (int)std::max<int64_t>(1, std::min<int64_t>(pieces, count));
-  const int64_t per = (count + pieces - 1) / pieces;
-  if (pieces == 1) {
-    try { fn(0, (int64_t)0, count); } catch (...) { return false; }
-    return true;
-  }
-  std::vector<char> ok((size_t)pieces, 1);
-  std::vector<std::thread> th;
-  th.reserve((size_t)pieces);
-  for (int t = 0; t < pieces; ++t) {
-    const int64_t b = std::min(count, t * per), e = std::min(count, b + per);
-    try {
-      th.emplace_back([&, t, b, e]() {
-        try { fn(t, b, e); } catch (...) { ok[(size_t)t] = 0; }
-      });
-    } catch (...) {  // no thread to be had: do the piece here
-      try { fn(t, b, e); } catch (...) { ok[(size_t)t] = 0; }
-    }
-  }
-  for (auto &x : th) x.join();
-  return std::all_of(ok.begin(), ok.end(), [](char c) { return c != 0; });
-}
-
-// wall time of the phases of an operator's creation, printed under SLQ_DEBUG (scripts/time_create.py)
-struct PhaseClock {
-  bool on;
-  explicit PhaseClock(const OperatorSwitches &sw) : on(sw.debug != 0) {}
-  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now(), t0 = t;
-  void total(const char *what) {
-    if (on) fprintf(stderr, "[slq] create: %-34s %7.1f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  }
-  void lap(const char *what) {
-    if (!on) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[slq] create: %-34s %7.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
-    t = now;
-  }
-};
-
-// Uninitialised host storage for the big arrays of an operator's creation (a std::vector zero-fills them on one thread,
-// 20 ms per 100 MB, and every page is then touched a second time); whoever fills it writes every byte it will read.
-template <typename T> struct RawBuf {
-  std::unique_ptr<T[]> p;
-  size_t n = 0;
-  void alloc(size_t count) {
-    p.reset(new T[count]);  // (default-initialised: no fill for arithmetic T)
-    n = count;
-  }
-  T *data() { return p.get(); }
-  const T *data() const { return p.get(); }
-  size_t size() const { return n; }
-};
 
 // Host-to-device copies of an operator's arrays, run by helper threads while the caller builds the next arrays: a copy from
 // pageable memory blocks its caller at ~10 GB/s, 40 of the 160 ms a 10^6-row operator took to create. Every source must
@@ -478,577 +412,6 @@ static int check_dtype(int dtype) {
 }
 
 
-// ---------------------------------------------------------------------------------------------------
-// XCD-aware row reordering (speed only; results are permutation-invariant up to rounding)
-// ---------------------------------------------------------------------------------------------------
-// k_spmm_3term / k_csr_pass give XCD x the contiguous row range [x*n/8, (x+1)*n/8) and sweep it
-// with all of the XCD's waves in lock-step, so a gathered panel row stays useful only while the
-// sweep front is within the matrix bandwidth of it. With 1 KiB panel rows and a 4 MiB L2 the
-// natural order of a 1000 x 1000 grid (bandwidth 1000 -> 2 MiB of halo) no longer fits beside the
-// rows in flight: the alpha pass fetched 6.5 GB per launch against 4.2 GB algorithmic
-// (profiles/r01b_pmc_per_kernel.csv). Reverse Cuthill-McKee INSIDE each XCD's chunk shrinks the
-// bandwidth to the chunk's short dimension (125 for that grid; build/rcm_test in round 1). perm[new] = old.
-// MEASURED RESULT: slower, see slq_csr_create. The L2 behaviour of this kernel is not explained by
-// the reuse-distance model above (fewer resident workgroups also fetch MORE, not less).
-// sub: second-level pieces per chunk (below). avg_level: if not null, receives the mean size of the breadth-first level sets of
-// the final order - what a tile sweep has to keep in L2 between a row and its neighbours in the next level.
-// first_level: the order a call with sub = 1 returned for this matrix (null: computed here) - the sweep over sub = 4, 16, 64 of
-// csr_create_body does the chunks' own Cuthill-McKee once (r04: it was redone per attempt, 12 ms of a 100^3 operator's creation).
-static void xcd_rcm_permutation(int64_t n, const int32_t *rowptr, const int32_t *colind, std::vector<int32_t> &perm, int sub,
-                                double *avg_level, const std::vector<int32_t> *first_level = nullptr) {
-  perm.resize((size_t)n);
-  const int64_t chunk = (n + 7) / 8;
-  // The eight chunks are independent: one worker each. deg / part / seen are indexed by node and a worker touches the
-  // entries of its own chunk only (a neighbour's entry is read only after its index has been found inside the chunk).
-  std::vector<int32_t> deg((size_t)n), part((size_t)n, -1);
-  std::vector<char> seen((size_t)n, 0);
-  sub = std::max(1, sub);
-  int64_t levels_x[8] = {0, 0, 0, 0, 0, 0, 0, 0}, levelled_x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  auto do_chunk = [&](int x) {
-    const int64_t lo = x * chunk, hi = std::min<int64_t>(n, lo + chunk);
-    if (lo >= hi) return;
-    int64_t levels = 0, levelled = 0;  // of the committed searches since the last reset
-    std::vector<int32_t> nbrs, order, members, first, piece, second;
-    auto inside = [&](int32_t v, int32_t id) { return v >= lo && v < hi && part[(size_t)v] == id; };
-    // Reverse Cuthill-McKee of the subgraph induced by `members` (all with part[v] == id), appended to `out`.
-    auto rcm = [&](const std::vector<int32_t> &mem, int32_t id, std::vector<int32_t> &out) {
-      for (int32_t v : mem) {
-        int d = 0;
-        for (int32_t p = rowptr[v]; p < rowptr[v + 1]; ++p) d += (colind[p] != v && inside(colind[p], id));
-        deg[(size_t)v] = d;
-      }
-      order.clear();
-      // candidates in increasing degree: starting points of the components
-      std::vector<int32_t> cand(mem);
-      std::stable_sort(cand.begin(), cand.end(), [&](int32_t a, int32_t b) { return deg[(size_t)a] < deg[(size_t)b]; });
-      auto bfs = [&](int32_t start, bool commit, int32_t *last_min) {
-        // breadth-first numbering with neighbours in increasing degree (Cuthill-McKee)
-        const size_t base = order.size();
-        order.push_back(start);
-        seen[(size_t)start] = 1;
-        size_t head = base, level_begin = base;
-        while (head < order.size()) {
-          const size_t level_end = order.size();
-          level_begin = head;
-          if (commit) {
-            ++levels;
-            levelled += (int64_t)(level_end - head);
-          }
-          for (; head < level_end; ++head) {
-            const int32_t u = order[head];
-            nbrs.clear();
-            for (int32_t p = rowptr[u]; p < rowptr[u + 1]; ++p) {
-              const int32_t v = colind[p];
-              if (inside(v, id) && !seen[(size_t)v]) {
-                seen[(size_t)v] = 1;
-                nbrs.push_back(v);
-              }
-            }
-            std::sort(nbrs.begin(), nbrs.end(), [&](int32_t a, int32_t b) { return deg[(size_t)a] < deg[(size_t)b] || (deg[(size_t)a] == deg[(size_t)b] && a < b); });
-            order.insert(order.end(), nbrs.begin(), nbrs.end());
-          }
-        }
-        // min-degree node of the last level: a pseudo-peripheral candidate
-        int32_t far = order[level_begin];
-        for (size_t q = level_begin; q < order.size(); ++q)
-          if (deg[(size_t)order[q]] < deg[(size_t)far]) far = order[q];
-        if (last_min) *last_min = far;
-        if (!commit) {
-          for (size_t q = base; q < order.size(); ++q) seen[(size_t)order[q]] = 0;
-          order.resize(base);
-        }
-      };
-      for (int32_t c : cand) {
-        if (seen[(size_t)c]) continue;
-        int32_t far = c;
-        bfs(c, false, &far);      // one pseudo-peripheral refinement
-        bfs(far, true, nullptr);
-      }
-      for (int32_t v : mem) seen[(size_t)v] = 0;
-      out.insert(out.end(), order.rbegin(), order.rend());  // reversed (RCM)
-    };
-    if (first_level && sub > 1) {
-      first.assign(first_level->begin() + lo, first_level->begin() + hi);
-    } else {
-      members.resize((size_t)(hi - lo));
-      for (int64_t i = lo; i < hi; ++i) {
-        members[(size_t)(i - lo)] = (int32_t)i;
-        part[(size_t)i] = x;
-      }
-      rcm(members, x, first);
-    }
-    // Second level (SLQ_RCM_SUB = K > 1): the chunk's RCM order is cut into K consecutive pieces of equal size - runs of
-    // BFS levels, i.e. slices ACROSS the chunk's longest direction - and each piece is reordered on its own. A piece is
-    // short along the old sweep direction, so its own Cuthill-McKee levels run along another one and are K times
-    // smaller: the gather halo an XCD's L2 has to hold shrinks accordingly, at the price of the edges cut between pieces.
-    if (sub > 1 && (int64_t)first.size() >= 64 * sub) {
-      levels = levelled = 0;
-      const size_t len = (first.size() + sub - 1) / sub;
-      for (int k = 0; k < sub; ++k) {
-        const size_t b0 = std::min(first.size(), k * len), b1 = std::min(first.size(), b0 + len);
-        piece.assign(first.begin() + b0, first.begin() + b1);
-        const int32_t id = 8 + x * sub + k;
-        for (int32_t v : piece) part[(size_t)v] = id;
-        rcm(piece, id, second);
-      }
-      first.swap(second);
-    }
-    levels_x[x] = levels;
-    levelled_x[x] = levelled;
-    for (int64_t q = 0; q < hi - lo; ++q) perm[(size_t)(lo + q)] = first[(size_t)q];
-  };
-  if (host_threads() > 1) {
-    if (!parallel_pieces(8, 8, [&](int, int64_t x0, int64_t x1) { for (int64_t x = x0; x < x1; ++x) do_chunk((int)x); })) throw std::bad_alloc();
-  } else {
-    for (int x = 0; x < 8; ++x) do_chunk(x);
-  }
-  int64_t levels_all = 0, levelled_all = 0;
-  for (int x = 0; x < 8; ++x) levels_all += levels_x[x], levelled_all += levelled_x[x];
-  if (avg_level) *avg_level = levels_all > 0 ? (double)levelled_all / (double)levels_all : 0.0;
-}
-
-
-// Workgroup tiles for k_csr_tile_pass (SLQ_TILES). The rows of every XCD chunk are regrouped into compact clusters:
-// seeds are taken in the chunk's current order (natural or Cuthill-McKee), a cluster grows breadth-first by the
-// unassigned in-chunk neighbour with the most links into it (ties: first discovered), up to kTileRows rows and as long
-// as its rows and columns together stay within kTileCols distinct indices. Clusters follow one another in seed order,
-// so the sweep of the chunk keeps its locality. order_in: stored row -> caller row; inv_in: caller row -> stored row
-// (null: identity). order_out: the new stored order; tile_row: first stored row of every tile; xcd_tile: tile range of
-// every chunk. Returns false when a single row already needs more than kTileCols indices (no tiling for this operator).
-// *lines_total (if not null): the sum over the clusters of their distinct indices (rows and columns) - the panel rows a sweep of the tiles lands.
-static bool build_clusters(int64_t n, const int32_t *rowptr, const int32_t *colind, const int32_t *order_in, const int32_t *inv_in,
-                           std::vector<int32_t> &order_out, std::vector<int32_t> &tile_row, int32_t xcd_tile[9], const OperatorSwitches &osw, int64_t *lines_total = nullptr) {
-  const int64_t chunk = (n + 7) / 8;
-  const bool ringed = osw.tiles == 2;  // tiles of the ring-fed kernel (k_csr_ring_pass): smaller, fixed caps
-  const int tmax = ringed ? kRingTileRows : std::max(1, std::min(osw.tile_rows, 64));
-  const int dcap = ringed ? kRingTileCols : std::max(8, std::min(osw.tile_cols, kTileCols));
-  const int nzcap = ringed ? kRingTileNnz : std::numeric_limits<int>::max();  // the ring kernel's tile record is bounded
-  // The chunks are independent (a cluster never leaves its chunk): one worker each, with its own order, its own tile
-  // boundaries (counted from the chunk's first row) and its own stamp array; `assigned` is shared, but a worker reads and
-  // writes the entries of its own chunk's rows only.
-  // (r03: every chunk is clustered as kClusterPieces independent halves of its order - a fixed split, so the tiles do not
-  // depend on the number of host threads - because the greedy growth is sequential and was 25-50 ms of an operator's creation
-  // with one worker per chunk; a cluster never crosses the middle of a chunk either: one short tile per 60,000 rows.)
-  constexpr int kClusterPieces = 2, NX = 8 * kClusterPieces;
-  std::vector<char> assigned((size_t)n, 0);
-  std::vector<int32_t> order_x[NX], rows_x[NX];  // per piece: the new order, and the row count of every cluster
-  int64_t lines_x[NX] = {};
-  char failed[NX] = {};
-  auto do_chunk = [&](int x) {
-    const int64_t clo = (x / kClusterPieces) * chunk, chi = std::min<int64_t>(n, clo + chunk);
-    if (clo >= chi) return;
-    const int64_t plen = (chi - clo + kClusterPieces - 1) / kClusterPieces;
-    const int64_t lo = clo + (x % kClusterPieces) * plen, hi = std::min<int64_t>(chi, lo + plen);
-    if (lo >= hi) return;
-    std::vector<int32_t> stamp((size_t)n, -1);
-    struct Cand { int32_t node, cnt, disc; };
-    std::vector<Cand> cand;
-    // where a node of this piece sits in `cand` while it is a candidate of the current cluster (r04: the list was searched linearly for every
-    // neighbour of every added row - 20 of the 35 ms this took on a 100^3 grid); indexed by position in the piece
-    std::vector<int32_t> slot_of((size_t)(hi - lo), -1);
-    std::vector<int32_t> &order = order_x[x];
-    order.reserve((size_t)(hi - lo));
-    int32_t cid = 0;
-    auto in_chunk = [&](int32_t v) {
-      const int64_t b = inv_in ? inv_in[v] : v;
-      return b >= lo && b < hi;
-    };
-    for (int64_t b = lo; b < hi; ++b) {
-      const int32_t seed = order_in ? order_in[b] : (int32_t)b;
-      if (assigned[(size_t)seed]) continue;
-      int D = 0, ndisc = 0, nz = 0;
-      cand.clear();
-      const size_t first_member = order.size();
-      auto new_cols = [&](int32_t v) {
-        int c = stamp[(size_t)v] != cid;
-        for (int32_t p = rowptr[v]; p < rowptr[v + 1]; ++p) c += (stamp[(size_t)colind[p]] != cid && colind[p] != v);
-        return c;
-      };
-      auto add = [&](int32_t v) {
-        assigned[(size_t)v] = 1;
-        order.push_back(v);
-        nz += rowptr[v + 1] - rowptr[v];
-        if (stamp[(size_t)v] != cid) { stamp[(size_t)v] = cid; ++D; }
-        for (int32_t p = rowptr[v]; p < rowptr[v + 1]; ++p) {
-          const int32_t c = colind[p];
-          if (stamp[(size_t)c] != cid) { stamp[(size_t)c] = cid; ++D; }
-          if (c != v && in_chunk(c) && !assigned[(size_t)c]) {
-            int32_t &slot = slot_of[(size_t)((inv_in ? inv_in[c] : c) - lo)];
-            if (slot >= 0) ++cand[(size_t)slot].cnt;
-            else slot = (int32_t)cand.size(), cand.push_back(Cand{c, 1, ndisc++});
-          }
-        }
-      };
-      if (new_cols(seed) > dcap || rowptr[seed + 1] - rowptr[seed] > nzcap) { failed[x] = 1; return; }
-      add(seed);
-      while ((int)(order.size() - first_member) < tmax && !cand.empty()) {
-        size_t best = 0;
-        for (size_t q = 1; q < cand.size(); ++q)
-          if (cand[q].cnt > cand[best].cnt || (cand[q].cnt == cand[best].cnt && cand[q].disc < cand[best].disc)) best = q;
-        const int32_t v = cand[best].node;
-        slot_of[(size_t)((inv_in ? inv_in[v] : v) - lo)] = -1;
-        cand[best] = cand.back();
-        cand.pop_back();
-        if (best < cand.size()) slot_of[(size_t)((inv_in ? inv_in[cand[best].node] : cand[best].node) - lo)] = (int32_t)best;
-        if (assigned[(size_t)v]) continue;
-        if (D + new_cols(v) > dcap || nz + rowptr[v + 1] - rowptr[v] > nzcap) continue;  // would not fit: leave it for a later cluster
-        add(v);
-      }
-      for (const Cand &k : cand) slot_of[(size_t)((inv_in ? inv_in[k.node] : k.node) - lo)] = -1;  // (what the cluster leaves behind)
-      lines_x[x] += D;
-      rows_x[x].push_back((int32_t)(order.size() - first_member));
-      ++cid;
-    }
-  };
-  if (host_threads() > 1) {
-    if (!parallel_pieces(NX, NX, [&](int, int64_t x0, int64_t x1) { for (int64_t x = x0; x < x1; ++x) do_chunk((int)x); })) return false;
-  } else {
-    for (int x = 0; x < NX; ++x) do_chunk(x);
-  }
-  order_out.clear();
-  order_out.reserve((size_t)n);
-  tile_row.assign(1, 0);
-  for (int x = 0; x < NX; ++x) {
-    if (failed[x]) return false;
-    if (x % kClusterPieces == 0) xcd_tile[x / kClusterPieces] = (int32_t)tile_row.size() - 1;
-    order_out.insert(order_out.end(), order_x[x].begin(), order_x[x].end());
-    for (int32_t r : rows_x[x]) tile_row.push_back(tile_row.back() + r);
-  }
-  xcd_tile[8] = (int32_t)tile_row.size() - 1;
-  for (int x = 7; x >= 0; --x) xcd_tile[x] = std::min(xcd_tile[x], xcd_tile[x + 1]);
-  if (lines_total) {
-    *lines_total = 0;
-    for (int x = 0; x < NX; ++x) *lines_total += lines_x[x];
-  }
-  return (int64_t)order_out.size() == n;
-}
-
-// A cheap look before the expensive one: grow one cluster from each of 256 evenly spaced seeds with build_clusters' rule (most
-// links first, same caps) on the caller's numbering, and return the distinct panel rows per tile row of that sample. Operators
-// whose rows share nothing (random graphs, bands with scattered far entries) show it here, in microseconds, and are spared the
-// reorderings and the full clustering (tens of seconds at n = 10^7).
-static double sample_tile_quality(int64_t n, const int32_t *rowptr, const int32_t *colind, int tmax, int dcap, int nzcap) {
-  const int64_t chunk = (n + 7) / 8;
-  int64_t rows = 0, cols = 0;
-  std::vector<int32_t> members, seen;
-  struct Cand { int32_t node, cnt; };
-  std::vector<Cand> cand;
-  for (int sidx = 0; sidx < 256; ++sidx) {
-    const int32_t seed = (int32_t)(((int64_t)sidx * n) / 256);
-    const int64_t lo = (seed / chunk) * chunk, hi = std::min<int64_t>(n, lo + chunk);
-    members.clear();
-    seen.clear();
-    cand.clear();
-    int nz = 0;
-    auto is_in = [](const std::vector<int32_t> &v, int32_t x) { return std::find(v.begin(), v.end(), x) != v.end(); };
-    auto new_cols = [&](int32_t v) {
-      int c = !is_in(seen, v);
-      for (int32_t p = rowptr[v]; p < rowptr[v + 1]; ++p) c += (colind[p] != v && !is_in(seen, colind[p]));
-      return c;
-    };
-    auto add = [&](int32_t v) {
-      members.push_back(v);
-      nz += rowptr[v + 1] - rowptr[v];
-      if (!is_in(seen, v)) seen.push_back(v);
-      for (int32_t p = rowptr[v]; p < rowptr[v + 1]; ++p) {
-        const int32_t c = colind[p];
-        if (!is_in(seen, c)) seen.push_back(c);
-        if (c != v && c >= lo && c < hi && !is_in(members, c)) {
-          bool found = false;
-          for (auto &k : cand) if (k.node == c) { ++k.cnt; found = true; break; }
-          if (!found) cand.push_back(Cand{c, 1});
-        }
-      }
-    };
-    if (new_cols(seed) > dcap || rowptr[seed + 1] - rowptr[seed] > nzcap) return 1e9;
-    add(seed);
-    while ((int)members.size() < tmax && !cand.empty()) {
-      size_t best = 0;
-      for (size_t q = 1; q < cand.size(); ++q) if (cand[q].cnt > cand[best].cnt) best = q;
-      const int32_t v = cand[best].node;
-      cand[best] = cand.back();
-      cand.pop_back();
-      if (is_in(members, v)) continue;
-      if ((int)seen.size() + new_cols(v) > dcap || nz + rowptr[v + 1] - rowptr[v] > nzcap) continue;
-      add(v);
-    }
-    rows += (int64_t)members.size();
-    cols += (int64_t)seen.size();
-  }
-  return rows > 0 ? (double)cols / (double)rows : 1e9;
-}
-
-// Tile lists of the STORED CSR: per tile the distinct indices of its rows and their columns (ascending unless SLQ_RING_ORDER
-// says otherwise), per nonzero the position of its column in that list, per row the position of the row itself.
-static void build_tile_meta(int64_t n, const int32_t *rowptr, const int32_t *colind, const std::vector<int32_t> &tile_row,
-                            std::vector<int32_t> &tile_ptr, std::vector<int32_t> &tile_cols, std::vector<int32_t> &lcol,
-                            std::vector<int32_t> &self_idx, int *max_cols, const OperatorSwitches &osw) {
-  const size_t ntiles = tile_row.size() - 1;
-  tile_ptr.assign(ntiles + 1, 0);
-  tile_cols.clear();
-  lcol.assign((size_t)rowptr[n] + kCsrPad, 0);
-  self_idx.assign((size_t)n, 0);
-  const int line_order = osw.ring_order;
-  const int pieces = host_threads();
-  std::vector<std::vector<int32_t>> local((size_t)pieces);  // every piece's lists, in tile order
-  std::vector<int> mx_piece((size_t)pieces, 0);
-  const bool ok = parallel_pieces(pieces, (int64_t)ntiles, [&](int piece, int64_t t0, int64_t t1) {
-    std::vector<int32_t> u, pos, ordered;
-    std::vector<int32_t> &mine = local[(size_t)piece];
-    int mx = 0;
-    for (int64_t t = t0; t < t1; ++t) {
-      const int64_t r0 = tile_row[(size_t)t], r1 = tile_row[(size_t)t + 1];
-      u.clear();
-      for (int64_t r = r0; r < r1; ++r) {
-        u.push_back((int32_t)r);
-        for (int32_t p = rowptr[r]; p < rowptr[r + 1]; ++p) u.push_back(colind[p]);
-      }
-      std::sort(u.begin(), u.end());
-      u.erase(std::unique(u.begin(), u.end()), u.end());
-      mx = std::max(mx, (int)u.size());
-      // position of every distinct index in the tile's list = the order its panel rows are landed in. Ascending by default;
-      // line_order 1: the tile's own rows first, then the rows below them, then the rows above (experiments, SLQ_RING_ORDER)
-      pos.resize(u.size());
-      if (line_order == 0) {
-        for (size_t q = 0; q < u.size(); ++q) pos[q] = (int32_t)q;
-      } else {
-        const size_t lo = (size_t)(std::lower_bound(u.begin(), u.end(), (int32_t)r0) - u.begin());
-        const size_t own = (size_t)(r1 - r0);
-        for (size_t q = 0; q < u.size(); ++q) pos[q] = (int32_t)(q < lo ? own + q : (q < lo + own ? q - lo : q));
-      }
-      ordered.resize(u.size());
-      for (size_t q = 0; q < u.size(); ++q) ordered[(size_t)pos[q]] = u[q];
-      for (int64_t r = r0; r < r1; ++r) {
-        self_idx[(size_t)r] = pos[(size_t)(std::lower_bound(u.begin(), u.end(), (int32_t)r) - u.begin())];
-        for (int32_t p = rowptr[r]; p < rowptr[r + 1]; ++p)
-          lcol[(size_t)p] = pos[(size_t)(std::lower_bound(u.begin(), u.end(), colind[p]) - u.begin())];
-      }
-      mine.insert(mine.end(), ordered.begin(), ordered.end());
-      tile_ptr[(size_t)t + 1] = (int32_t)ordered.size();  // (the list's length for now; offsets below)
-    }
-    mx_piece[(size_t)piece] = mx;
-  });
-  if (!ok) throw std::bad_alloc();
-  for (size_t t = 0; t < ntiles; ++t) tile_ptr[t + 1] += tile_ptr[t];
-  tile_cols.reserve((size_t)tile_ptr[ntiles] + kCsrPad);
-  for (auto &v : local) tile_cols.insert(tile_cols.end(), v.begin(), v.end());
-  tile_cols.insert(tile_cols.end(), kCsrPad, 0);
-  *max_cols = *std::max_element(mx_piece.begin(), mx_piece.end());
-}
-
-// What the ring-fed passes read (SLQ_TILES=2; layouts in slq_kernels.hpp / slq_ring.hpp): per tile a descriptor of R blocks
-// of 64 words and a record of its CSR in the tile's own numbering, every record at a 16-byte boundary of one blob that ends
-// in a spare record's worth of zeros (a record is fetched in whole KiB). R = 1: the tiles as clustered (k_csr_ring_pass and
-// k_ring_pass<LPR = 64>); R = 2, 4: tiles of R merged base tiles for panels of 64 / R lanes per row - block b of the
-// descriptor lists the lines b, R + b, 2R + b, ... (the lines lane group b lands), the last one repeated to the end of its DMA.
-template <typename F>
-static void build_ring_stream(int R, const int32_t *rowptr, const F *vals, const std::vector<int32_t> &tile_row, const std::vector<int32_t> &tile_ptr,
-                              const std::vector<int32_t> &tile_cols, const std::vector<int32_t> &lcol, const std::vector<int32_t> &self_idx,
-                              RawBuf<int32_t> &desc, RawBuf<char> &rec, bool *pad_rows = nullptr) {
-  const size_t ntiles = tile_row.size() - 1;
-  const size_t dw = (size_t)64 * R, head_bytes = (size_t)kRecHeadBytes * R;
-  const int valoff_w = 16 * R - 1, self_w = 16 * R;
-  desc.alloc(ntiles * dw);  // (zeroed tile by tile below, by the thread that fills the tile)
-  // *pad_rows (the alpha-only pass's upper-triangle streams): every row's entries padded to a multiple of four, at least four, with
-  // {the row's own line, 0} - its consumer then reads a row's entries four at a time with aligned 16-byte LDS reads and
-  // without a single per-entry condition (slq_ring.hpp: do_alpha_padded). Given up (*pad_rows = false) if some tile's record
-  // would outgrow its slot.
-  bool pad = pad_rows && *pad_rows;
-  auto padded = [](int32_t cnt) { return std::max<int32_t>(4, (cnt + 3) / 4 * 4); };
-  if (pad) {
-    for (size_t t = 0; t < ntiles && pad; ++t) {
-      size_t e = 0;
-      for (int32_t r = tile_row[t]; r < tile_row[t + 1]; ++r) e += (size_t)padded(rowptr[r + 1] - rowptr[r]);
-      if (head_bytes + e * (4 + sizeof(F)) > (size_t)((kRingRecStride * R + 1023) / 1024 * 1024)) pad = false;
-    }
-  }
-  if (pad_rows) *pad_rows = pad;
-  // where every record starts (its size follows from the tile's entry count alone), then the tiles in parallel
-  std::vector<size_t> off(ntiles + 1, 0);
-  for (size_t t = 0; t < ntiles; ++t) {
-    const int32_t r0 = tile_row[t];
-    size_t nz = (size_t)(rowptr[tile_row[t + 1]] - rowptr[r0]);
-    if (pad) {
-      nz = 0;
-      for (int32_t r = r0; r < tile_row[t + 1]; ++r) nz += (size_t)padded(rowptr[r + 1] - rowptr[r]);
-    }
-    const size_t nzp = (nz + 3) / 4 * 4;
-    off[t + 1] = off[t] + (head_bytes + nzp * 4 + nzp * sizeof(F) + 15) / 16 * 16;
-  }
-  rec.alloc(off[ntiles] + (size_t)kRingMetaBytes * R);
-  memset(rec.data() + off[ntiles], 0, (size_t)kRingMetaBytes * R);  // the spare record behind the last one
-  const bool ok = parallel_pieces(host_threads(), (int64_t)ntiles, [&](int, int64_t t0, int64_t t1) {
-    for (int64_t tt = t0; tt < t1; ++tt) {
-      const size_t t = (size_t)tt;
-      const int32_t r0 = tile_row[t], rows = tile_row[t + 1] - r0, p0 = rowptr[r0];
-      int32_t nz = rowptr[r0 + rows] - p0;
-      if (pad) {
-        nz = 0;
-        for (int32_t i = 0; i < rows; ++i) nz += padded(rowptr[r0 + i + 1] - rowptr[r0 + i]);
-      }
-      const int32_t D = tile_ptr[t + 1] - tile_ptr[t];
-      const size_t nzp = ((size_t)nz + 3) / 4 * 4, valoff = head_bytes + nzp * 4, bytes = off[t + 1] - off[t];
-      memset(rec.data() + off[t], 0, bytes);
-      memset(desc.data() + t * dw, 0, dw * 4);
-      int32_t *head = (int32_t *)(rec.data() + off[t]);
-      head[valoff_w] = (int32_t)valoff;
-      for (int32_t i = 0; i < rows; ++i) head[self_w + i] = self_idx[(size_t)(r0 + i)];
-      if (!pad) {
-        for (int32_t i = 0; i <= rows; ++i) head[i] = rowptr[r0 + i] - p0;
-        memcpy(rec.data() + off[t] + head_bytes, lcol.data() + p0, (size_t)nz * 4);
-        memcpy(rec.data() + off[t] + valoff, vals + p0, (size_t)nz * sizeof(F));
-      } else {
-        int32_t *lc_out = (int32_t *)(rec.data() + off[t] + head_bytes);
-        F *va_out = (F *)(rec.data() + off[t] + valoff);
-        int32_t w = 0;
-        for (int32_t i = 0; i < rows; ++i) {
-          const int32_t q0 = rowptr[r0 + i], cnt = rowptr[r0 + i + 1] - q0, pc = padded(cnt);
-          head[i] = w;
-          for (int32_t q = 0; q < pc; ++q) {
-            lc_out[w + q] = q < cnt ? lcol[(size_t)(q0 + q)] : self_idx[(size_t)(r0 + i)];
-            va_out[w + q] = q < cnt ? vals[q0 + q] : (F)0;
-          }
-          w += pc;
-        }
-        head[rows] = w;
-      }
-      int32_t *d = desc.data() + t * dw;
-      d[kDescCols] = D;
-      d[kDescRecOff] = (int32_t)(off[t] / 16);
-      d[kDescRecChunks] = (int32_t)((bytes + 1023) / 1024);
-      d[kDescRow0] = r0;
-      d[kDescRows] = rows;
-      const int32_t nd = (D + R - 1) / R;
-      if (R == 1) {  // (de-interleaved: even lines, then odd ones - slq_common.hpp: ring1_list_pos)
-        for (int32_t c = 0; c < D; ++c) d[kDescList + ring1_list_pos(c)] = tile_cols[(size_t)tile_ptr[t] + c];
-      } else {
-        for (int32_t c = 0; c < nd * R; ++c) d[(size_t)(c % R) * 64 + kDescList + c / R] = tile_cols[(size_t)tile_ptr[t] + std::min(c, D - 1)];
-      }
-    }
-  });
-  if (!ok) throw std::bad_alloc();
-}
-
-// Tiles of the upper-triangle stream (the alpha-only pass, r04). That pass lands 31-32 GB/s per CU by LDS-DMA whatever the operator (configs[1]: 1.64 KiB per row,
-// 0.40 ms; 100^3: 2.65 KiB per row, 0.65 ms) - the DMA path's own cadence - so what shortens it is fewer landed lines per row. The base tiles are cut to what a slot
-// holds of FULL rows; over the upper triangle the same rows need two thirds of the lines, so consecutive base tiles of a chunk - neighbours in the sweep, which share
-// halo - are joined while the run keeps to kRingTileRows rows, kRingTileCols distinct lines (rows and upper columns) and kRingTileNnz padded entries: 100^3, 118,940 ->
-// 107,848 tiles, alpha pass 0.652 -> 0.607 ms. (Cutting the chunk's rows anew, row by row, to the same caps gives 12.9-row tiles that straddle cluster boundaries and
-// land MORE lines per row, 2.65 against 2.47: 0.82 ms. Not kept.) Tiles stay contiguous row ranges of one XCD chunk; kernel and stream format do not change.
-// each_upper(r, consider): calls consider(c) for every column c >= r of stored row r and returns how many there were (the upper
-// triangle's CSR, or - before that exists - the caller's CSR seen through the permutation: the columns' order does not matter)
-template <typename EachUpper>
-static void regroup_upper_tiles_impl(EachUpper each_upper, const std::vector<int32_t> &tile_row, const int32_t xcd_tile[9],
-                                     std::vector<int32_t> &tile_row_u, int32_t xcd_tile_u[9]) {
-  auto padded = [](int32_t cnt) { return std::max<int32_t>(4, (cnt + 3) / 4 * 4); };
-  // every chunk on its own (in parallel): consecutive base tiles - neighbours in the sweep - joined while the run keeps to the caps
-  std::vector<int32_t> cuts[8];
-  const bool ok = parallel_pieces(8, 8, [&](int, int64_t x0, int64_t x1) {
-    for (int64_t x = x0; x < x1; ++x) {
-      std::vector<int32_t> &out = cuts[x];
-      if (xcd_tile[x] >= xcd_tile[x + 1]) continue;
-      // membership by stamps (r04: the lists were searched linearly - 25 ms of a 100^3 operator's creation): in_run[c - base] == run: c is a line of
-      // the current run; in_tile[c - base] == stamp: c was counted for the base tile under consideration. Every column of a chunk's rows is >= base.
-      const int32_t base = tile_row[(size_t)xcd_tile[x]], n_all = tile_row.back();
-      std::vector<int32_t> in_run((size_t)(n_all - base), -1), in_tile((size_t)(n_all - base), -1);
-      int32_t run = 0, stamp = 0;
-      int nl = 0, rows = 0, nz = 0;
-      for (int32_t t = xcd_tile[x]; t < xcd_tile[x + 1]; ++t) {
-        const int32_t r0 = tile_row[(size_t)t], r1 = tile_row[(size_t)t + 1];
-        // what this base tile lists - its rows and their upper columns, each once - and how much of that the run does not list yet
-        int32_t all[kRingTileCols + 16];
-        int na = 0, nf = 0;
-        int32_t pz = 0;
-        auto consider = [&](int32_t c) {
-          const size_t k = (size_t)(c - base);
-          if (in_tile[k] == stamp) return;
-          in_tile[k] = stamp;
-          if (na < kRingTileCols + 16) all[na++] = c, nf += in_run[k] != run;
-        };
-        for (int32_t r = r0; r < r1; ++r) {
-          consider(r);
-          pz += padded(each_upper(r, consider));
-        }
-        ++stamp;
-        if (rows > 0 && (rows + (r1 - r0) > kRingTileRows || nl + nf > kRingTileCols || nz + pz > kRingTileNnz)) {
-          nl = rows = nz = 0;  // cut: this base tile opens the next run (its own lines: everything it lists)
-          ++run;
-        }
-        if (rows == 0) out.push_back(r0);
-        for (int q = 0; q < na && nl < 2 * kRingTileCols + 16; ++q) {
-          int32_t &m = in_run[(size_t)(all[q] - base)];
-          if (m != run) m = run, ++nl;
-        }
-        rows += r1 - r0;
-        nz += pz;
-      }
-    }
-  });
-  if (!ok) throw std::bad_alloc();
-  tile_row_u.clear();
-  for (int x = 0; x < 8; ++x) {
-    xcd_tile_u[x] = (int32_t)tile_row_u.size();
-    tile_row_u.insert(tile_row_u.end(), cuts[x].begin(), cuts[x].end());
-  }
-  xcd_tile_u[8] = (int32_t)tile_row_u.size();
-  tile_row_u.push_back(tile_row.back());
-}
-static void regroup_upper_tiles(const int32_t *urp, const int32_t *uci, const std::vector<int32_t> &tile_row, const int32_t xcd_tile[9],
-                                std::vector<int32_t> &tile_row_u, int32_t xcd_tile_u[9]) {
-  regroup_upper_tiles_impl(
-      [&](int32_t r, auto &consider) {
-        for (int32_t q = urp[r]; q < urp[r + 1]; ++q) consider(uci[q]);
-        return urp[r + 1] - urp[r];
-      },
-      tile_row, xcd_tile, tile_row_u, xcd_tile_u);
-}
-
-// If the CSR (rows sorted, no duplicates) is exactly symmetric, emit its upper triangle with the strict
-// upper entries doubled and return true. Row ranges in parallel: every off-diagonal entry (i, j) looks its mirror (j, i)
-// up by bisection in row j (rows are sorted - checked on the way) and compares the values; the upper entries are then
-// counted per row, placed by a prefix sum and written, again by row ranges.
-template <typename F>
-static bool build_symmetric_upper(int64_t n, const int32_t *rowptr, const int32_t *colind, const F *vals,
-                                  std::vector<int32_t> &urp, std::vector<int32_t> &uci, std::vector<char> &uva) {
-  urp.assign((size_t)n + 1, 0);
-  const int pieces = host_threads();
-  std::vector<char> bad((size_t)pieces, 0);
-  if (!parallel_pieces(pieces, n, [&](int piece, int64_t i0, int64_t i1) {
-        for (int64_t i = i0; i < i1 && !bad[(size_t)piece]; ++i) {
-          int32_t up = 0;
-          for (int32_t q = rowptr[i]; q < rowptr[i + 1]; ++q) {
-            const int32_t j = colind[q];
-            if (q > rowptr[i] && colind[q - 1] >= j) { bad[(size_t)piece] = 1; break; }  // unsorted or duplicate
-            up += j >= i;
-            if (j == i) continue;
-            const int32_t *lo = colind + rowptr[j], *hi = colind + rowptr[j + 1];
-            const int32_t *m = std::lower_bound(lo, hi, (int32_t)i);
-            if (m == hi || *m != (int32_t)i || !(vals[m - colind] == vals[q])) { bad[(size_t)piece] = 1; break; }
-          }
-          urp[(size_t)i + 1] = up;
-        }
-      }))
-    return false;
-  if (std::any_of(bad.begin(), bad.end(), [](char c) { return c != 0; })) return false;
-  for (int64_t i = 0; i < n; ++i) urp[(size_t)i + 1] += urp[(size_t)i];
-  const size_t nu = (size_t)urp[(size_t)n];
-  uci.resize(nu);
-  uva.resize(nu * sizeof(F));
-  F *uv = (F *)uva.data();
-  return parallel_pieces(pieces, n, [&](int, int64_t i0, int64_t i1) {
-    for (int64_t i = i0; i < i1; ++i) {
-      size_t w = (size_t)urp[(size_t)i];
-      for (int32_t q = rowptr[i]; q < rowptr[i + 1]; ++q) {
-        const int32_t j = colind[q];
-        if (j < i) continue;
-        uci[w] = j;
-        uv[w] = j == i ? vals[q] : (F)2 * vals[q];
-        ++w;
-      }
-    }
-  });
-}
-
 // ---- derived data built on the device (slq_build.hpp) ----
 struct DevBuf {  // device scratch of a build, freed when the build is left
   void *p = nullptr;
@@ -1168,32 +531,24 @@ static int device_build_stream(slq_context *ctx, int dtype, int R, int64_t n, co
   out.tile_ptr = keep_tile_ptr ? (int32_t *)tptr.take() : nullptr;
   return 0;
 }
+// the same bytes on the device and on the host / twice on the device (null pointers: equal when both are) - what SLQ_DEVICE_BUILD=2 compares
 static bool device_equals_host(const void *dev, const void *host, size_t bytes) {
   std::vector<char> tmp(bytes);
   if (hipMemcpy(tmp.data(), dev, bytes, hipMemcpyDeviceToHost) != hipSuccess) return false;
   return memcmp(tmp.data(), host, bytes) == 0;
 }
-
-// plain != 0: rows stay in the caller's order and no derived copy (upper triangle, tiles) is built - for operators whose
-// values change after creation (the affine operator)
-// dev_*: the same CSR already on the device (slq_csr_create_device): the device-side build reads it in place, and `vals` may then be null
-// (the values come back to the host only if the host has to build the operator after all)
-struct DeviceCsr { const int32_t *rp = nullptr, *ci = nullptr; const void *va = nullptr; };
-static int csr_create_impl(slq_context *ctx, int dtype, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colind,
-                           const void *vals, slq_operator **out, int plain, int host_build = 0, DeviceCsr dev = DeviceCsr());
-
-extern "C" int slq_csr_create(slq_context *ctx, int dtype, int64_t n, int64_t nnz,
-                              const int32_t *rowptr, const int32_t *colind, const void *vals,
-                              slq_operator **out) {
-  return csr_create_impl(ctx, dtype, n, nnz, rowptr, colind, vals, out, 0);
+static bool device_equals_device(const void *x, const void *y, size_t bytes) {
+  if (!x || !y) return x == y;
+  std::vector<char> hx(bytes);
+  return hipMemcpy(hx.data(), x, bytes, hipMemcpyDeviceToHost) == hipSuccess && device_equals_host(y, hx.data(), bytes);
 }
 
-static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colind,
-                           const void *vals, slq_operator **out, int plain, int host_build, DeviceCsr dev);
-static int csr_create_impl(slq_context *ctx, int dtype, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colind,
-                           const void *vals, slq_operator **out, int plain, int host_build, DeviceCsr dev) {
-  try {  // (host-side allocations of the analysis: no C++ exception crosses the C boundary)
-    return csr_create_body(ctx, dtype, n, nnz, rowptr, colind, vals, out, plain, host_build, dev);
+// No C++ exception crosses the C boundary: every slq_*_create whose body allocates on the host runs it through here, and
+// holds the operator it is building in an OpGuard - however the body is left without handing the operator out (an error
+// return, an exception of the host-side analysis), the operator and what it owns on the device go with it.
+template <typename Body> static int create_guarded(slq_operator **out, Body body) {
+  try {
+    return body();
   } catch (const std::bad_alloc &) {
     if (out) *out = nullptr;
     return fail(SLQ_ENOMEM, "host allocation failed while analysing the operator");
@@ -1202,265 +557,74 @@ static int csr_create_impl(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
     return fail(SLQ_EHIP, "operator analysis failed: %s", e.what());
   }
 }
+struct OpGuard {  // (declare it BEFORE an upload queue that fills the operator's arrays: that one joins first)
+  slq_operator *op;
+  ~OpGuard() {
+    if (op) slq_operator_destroy(op);
+  }
+  slq_operator *release() {
+    slq_operator *o = op;
+    op = nullptr;
+    return o;
+  }
+};
+// colind/vals of a stored CSR carry kCsrPad spare entries: the batched row gather (slq_kernels.hpp: gather_row_uniform)
+// loads indices and values 8 at a time and may read (never use) up to 7 entries past a row's end. The pad is cleared on `st`.
+static hipError_t alloc_padded_csr(int32_t **colind, void **vals, size_t nnz, size_t es, hipStream_t st) {
+  hipError_t e = hipMalloc((void **)colind, (nnz + kCsrPad) * 4);
+  if (e == hipSuccess) e = hipMalloc(vals, (nnz + kCsrPad) * es);
+  if (e == hipSuccess) e = hipMemsetAsync(*colind + nnz, 0, kCsrPad * 4, st);
+  if (e == hipSuccess) e = hipMemsetAsync((char *)*vals + nnz * es, 0, kCsrPad * es, st);
+  return e;
+}
 
-static int csr_finish_on_device(slq_context *ctx, slq_operator *op, int dtype, int64_t n, int64_t nnz, const int32_t *rowptr0, const int32_t *colind0,
-                                const int32_t *o_rp, const int32_t *o_ci, const void *o_va, UploadQueue &early, const std::vector<int32_t> &tile_row,
-                                const int32_t xcd_tile[9], PhaseClock &clk);
-static int operators_differ(const slq_operator *a, const slq_operator *b);
+// plain != 0: rows stay in the caller's order and no derived copy (upper triangle, tiles) is built - for operators whose
+// values change after creation (the affine operator)
+// dev: the same CSR already on the device (slq_csr_create_device): the device-side build reads it in place, and `vals` may then be null
+// (the values come back to the host only if the host has to build the operator after all)
+struct DeviceCsr { const int32_t *rp = nullptr, *ci = nullptr; const void *va = nullptr; };
 static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colind,
-                           const void *vals, slq_operator **out, int plain, int host_build, DeviceCsr dev) {
-  if (!ctx || !out) return fail(SLQ_EINVAL, "ctx/out is NULL");
-  *out = nullptr;
-  SLQ_TRY(check_dtype(dtype));
-  if (n <= 0 || n >= (int64_t)1 << 31 || nnz < 0 || nnz >= (int64_t)1 << 31)
-    return fail(SLQ_EINVAL, "CSR shape out of range for int32 indices (n=%lld, nnz=%lld)",
-                (long long)n, (long long)nnz);
-  if (!rowptr || (nnz > 0 && (!colind || (!vals && !dev.va)))) return fail(SLQ_EINVAL, "CSR arrays are NULL");
-  if (rowptr[0] != 0 || rowptr[n] != nnz)
-    return fail(SLQ_EINVAL, "rowptr[0] must be 0 and rowptr[n] must equal nnz");
-  const OperatorSwitches osw = read_operator_switches();  // (the one read of this creation: everything below, and the operator, keep these values)
-  PhaseClock clk(osw);
-  std::vector<char> vals_back;  // the values of a device-resident CSR, fetched when the host needs them
-  auto need_host_vals = [&]() -> hipError_t {
-    if (vals || nnz == 0) return hipSuccess;
-    vals_back.resize((size_t)nnz * esize(dtype));
-    const hipError_t he = hipMemcpy(vals_back.data(), dev.va, vals_back.size(), hipMemcpyDeviceToHost);
-    vals = vals_back.data();
-    return he;
-  };
-  for (int64_t i = 0; i < n; ++i)
-    if (rowptr[i + 1] < rowptr[i]) return fail(SLQ_EINVAL, "rowptr is not non-decreasing at %lld", (long long)i);
-  {
-    // every column index inside [0, n): ranges of the array in parallel, the first offender (lowest position) reported
-    const int pieces = host_threads();
-    std::vector<int64_t> bad((size_t)pieces, -1);
-    if (!parallel_pieces(pieces, nnz, [&](int piece, int64_t p0, int64_t p1) {
-          for (int64_t p = p0; p < p1; ++p)
-            if (colind[p] < 0 || colind[p] >= n) { bad[(size_t)piece] = p; break; }
-        }))
-      return fail(SLQ_ENOMEM, "host worker failed while validating the column indices");
-    for (int64_t b : bad)
-      if (b >= 0) return fail(SLQ_EINVAL, "column index %d out of range at position %lld", colind[b], (long long)b);
-  }
-  HIP_TRY(hipSetDevice(ctx->device));
-  clk.lap("validation");
-  if (ctx->dead) return fail(SLQ_EINVAL, "the context has been destroyed");
-  slq_operator *op = new (std::nothrow) slq_operator();
-  if (!op) return fail(SLQ_ENOMEM, "host allocation failed");
-  ctx_retain(ctx);
-  *op = slq_operator{ctx, OP_CSR, dtype, n, nnz, nullptr, nullptr, nullptr, 0, true, nullptr, nullptr, nullptr, nullptr, TileMeta{}};
-  op->sw = osw;
-  // whatever way this function is left without handing `op` out - an error return below or an exception of the host-side
-  // analysis - the operator and what it owns on the device go with it (declared before the upload queue: that one joins first)
-  struct OpGuard {
-    slq_operator *op;
-    ~OpGuard() {
-      if (op) slq_operator_destroy(op);
-    }
-  } guard{op};
+                           const void *vals, slq_operator **out, int plain, int host_build, DeviceCsr dev);
+static int csr_create_impl(slq_context *ctx, int dtype, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colind,
+                           const void *vals, slq_operator **out, int plain, int host_build = 0, DeviceCsr dev = DeviceCsr()) {
+  return create_guarded(out, [&]() { return csr_create_body(ctx, dtype, n, nnz, rowptr, colind, vals, out, plain, host_build, dev); });
+}
+
+extern "C" int slq_csr_create(slq_context *ctx, int dtype, int64_t n, int64_t nnz,
+                              const int32_t *rowptr, const int32_t *colind, const void *vals,
+                              slq_operator **out) {
+  return csr_create_impl(ctx, dtype, n, nnz, rowptr, colind, vals, out, 0);
+}
+
+// what both storage builders print under SLQ_DEBUG
+static void debug_stored_csr(const slq_operator *op, const char *how) {
+  if (op->sw.debug != 0)
+    fprintf(stderr, "[slq] csr n=%lld nnz=%lld reordered=%d rms in-chunk |i-j| = %.1f, far gathers per row %.2f%s\n", (long long)op->n,
+            (long long)op->nnz, op->perm_h ? 1 : 0, op->rms_dist, op->far_per_row, how);
+}
+static void debug_upper_tiles(const slq_operator *op, size_t ntu, size_t ntiles) {
+  if (op->sw.debug != 0)
+    fprintf(stderr, "[slq] tiles: upper-triangle stream on %zu tiles of %.2f rows (base: %zu of %.2f)\n", ntu, (double)op->n / (double)ntu, ntiles,
+            (double)op->n / (double)ntiles);
+}
+static void debug_upper_lists(const slq_operator *op) {
+  if (op->sw.debug != 0)
+    fprintf(stderr, "[slq] tiles: upper triangle: %.2f distinct panel rows per row, longest list %d (full rows: %d)\n", op->upper_per_row, op->tile_max_lines_u,
+            op->tiles.max_cols);
+}
+
+// An operator's storage built on the host from its layout: the permuted CSR, the far-gather count, the upper triangle, the tile
+// lists and both tile streams. Every array goes to the device through `up` while the next one is being built; the buffers it
+// reads are declared before it (L lives in the caller) and nothing returns without up.wait() (its destructor, at the latest).
+static int build_storage_host(slq_context *ctx, slq_operator *op, const CsrView &A, const void *vals, const OperatorLayout &L, int plain, PhaseClock &clk) {
+  const int64_t n = A.n, nnz = A.nnz;
+  const int32_t *rowptr = A.rowptr, *colind = A.colind;
+  const int dtype = op->dtype;
   const size_t es = esize(dtype);
-  // optional XCD-aware reordering: A' = P A P^T stored, vectors live in the permuted row space
-  std::vector<int32_t> rp2;
-  RawBuf<int32_t> ci2;
+  const OperatorSwitches &osw = op->sw;
+  const std::vector<int32_t> &tile_row = L.tile_row;
+  RawBuf<int32_t> ci2;                            // the stored CSR of a reordered operator: A' = P A P^T, vectors live in the permuted row space
   RawBuf<char> va2;
-  // SLQ_REORDER: 0 never, 1 operators with n >= 65536, 2 always, unset = automatic. Measured (DESIGN.md
-  // §5.3): on the 2-D grid of configs[1] (rms |i-j| of the nonzeros = 632 rows) it RAISED the alpha pass's
-  // fetch traffic from 6.5 to 8.9 GB and the step time by 10 %; on 3-D grids (100^3: rms |i-j| = 5345,
-  // 126^3: 8486) whose natural-order halo no longer fits any cache level it is 9-12 % FASTER. Automatic
-  // mode therefore reorders only when the rms index distance exceeds 2048 rows AND the permutation cuts
-  // it to 60 % or less (random graphs gain nothing and are left alone).
-  const int reorder_mode = plain ? 0 : osw.reorder;
-  // rms index distance of the nonzeros whose two ends lie in the same XCD chunk (links that cross
-  // chunks are served by another XCD's L2 whatever the order inside the chunks)
-  const int64_t rchunk = (n + 7) / 8;
-  auto mean_dist = [&](const std::vector<int32_t> *inv) {
-    const int pieces = 8;  // (a fixed partition: the sum does not depend on how many threads ran it)
-    std::vector<double> acc((size_t)pieces, 0.0);
-    std::vector<int64_t> cnt((size_t)pieces, 0);
-    if (!parallel_pieces(pieces, n, [&](int piece, int64_t i0, int64_t i1) {
-      double a = 0.0;
-      int64_t c = 0;
-      for (int64_t i = i0; i < i1; ++i) {
-        const int64_t ii = inv ? (*inv)[(size_t)i] : i;
-        for (int32_t q = rowptr[i]; q < rowptr[i + 1]; ++q) {
-          if (colind[q] / rchunk != i / rchunk) continue;
-          const int64_t jj = inv ? (*inv)[(size_t)colind[q]] : colind[q];
-          const double dd = (double)(ii > jj ? ii - jj : jj - ii);
-          a += dd * dd;
-          ++c;
-        }
-      }
-      acc[(size_t)piece] = a;
-      cnt[(size_t)piece] = c;
-    })) throw std::bad_alloc();
-    double a = 0.0;
-    int64_t c = 0;
-    for (int t = 0; t < pieces; ++t) a += acc[(size_t)t], c += cnt[(size_t)t];  // (piece order: the same value whatever the timing)
-    return std::sqrt(a / (double)std::max<int64_t>(c, 1));
-  };
-  // Workgroup tiles (SLQ_TILES): the rows are regrouped into compact clusters = the tiles of k_csr_tile_pass /
-  // k_csr_ring_pass, on top of a base order. Kept only if the tiles actually share rows: at most kTileMaxColsPerRow distinct
-  // panel rows per tile row (5-point grid: 2.1, 7-point grid: 3.9 with the ring kernel's 36-row images, random graph: 10+).
-  // Unasked (SLQ_TILES unset) only operators of 65536 rows and more are tried - below that a pass is launch-bound anyway.
-  const int tmode = plain ? 0 : osw.tiles;
-  const bool tiles_forced = osw.tiles_forced;
-  bool try_tiles = tmode != 0 && nnz > 0 && n >= (tiles_forced ? 4096 : 65536);
-  if (try_tiles) {
-    // (a sample cluster grows on the caller's numbering, the real ones on the reordered chunk: 4.3 against 3.9 on a 7-point grid,
-    // 2.3 against 2.1 on a 5-point one, 12-16 on the operators this is meant to turn away. 25 % of margin keeps it a filter for
-    // those only)
-    const bool ringed = tmode == 2;
-    const double q = sample_tile_quality(n, rowptr, colind, ringed ? kRingTileRows : std::max(1, std::min(osw.tile_rows, 64)),
-                                         ringed ? kRingTileCols : std::max(8, std::min(osw.tile_cols, kTileCols)),
-                                         ringed ? kRingTileNnz : std::numeric_limits<int>::max());
-    if (osw.debug != 0) fprintf(stderr, "[slq] tiles: sample of 256 clusters: %.2f distinct panel rows per row\n", q);
-    if (q > 1.25 * kTileMaxColsPerRow) try_tiles = false;
-  }
-  clk.lap("tile sample");
-  // SLQ_DEVICE_BUILD (r04, slq_build.hpp): 1 (default) - an operator that gets ring-sized tiles has its stored CSR, upper triangle and
-  // tile streams built on the device from the caller's CSR, which starts its way up now, while the host orders and clusters the rows;
-  // 0 - everything on the host, as before; 2 - both, compared array by array (tests)
-  const int dev_mode = (plain || host_build) ? 0 : osw.device_build;
-  DevBuf o_rp, o_ci, o_va;       // the caller's CSR on the device (scratch of the build)
-  UploadQueue early(ctx->device);  // (declared after what it fills: joined first)
-  bool early_started = false;
-  const int32_t *src_rp = nullptr, *src_ci = nullptr;  // where the device-side build reads the caller's CSR
-  const void *src_va = nullptr;
-  if (dev_mode != 0 && try_tiles && tmode == 2 && reorder_mode != 0 && osw.ring_order == 0 && dev.va) {
-    src_rp = dev.rp, src_ci = dev.ci, src_va = dev.va;  // in place (slq_csr_create_device)
-    early_started = true;
-  } else if (dev_mode != 0 && try_tiles && tmode == 2 && reorder_mode != 0 && osw.ring_order == 0) {
-    hipError_t ee = o_rp.alloc((size_t)(n + 1) * 4);
-    if (ee == hipSuccess) ee = o_ci.alloc((size_t)nnz * 4);
-    if (ee == hipSuccess) ee = o_va.alloc((size_t)nnz * esize(dtype));
-    if (ee != hipSuccess) return fail(ee == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "CSR upload: %s", hipGetErrorString(ee));
-    early.push({{o_rp.p, rowptr, (size_t)(n + 1) * 4}, {o_ci.p, colind, (size_t)nnz * 4}, {o_va.p, vals, (size_t)nnz * esize(dtype)}});
-    early_started = true;
-    src_rp = o_rp.as<int32_t>(), src_ci = o_ci.as<int32_t>(), src_va = o_va.p;
-  }
-  const double tile_limit = kTileMaxColsPerRow;
-  std::vector<int32_t> tile_row;
-  int32_t xcd_tile[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  bool have_tiles = false;
-  // clusters on top of `base` (stored row -> caller row; null: the caller's order); on success `order` is the new order
-  auto cluster_tiles = [&](const std::vector<int32_t> *base, std::vector<int32_t> &order) -> bool {
-    std::vector<int32_t> inv0;
-    if (base) {
-      inv0.resize((size_t)n);
-      for (int64_t i = 0; i < n; ++i) inv0[(size_t)(*base)[(size_t)i]] = (int32_t)i;
-    }
-    int64_t dsum = 0;  // distinct indices (rows and columns) summed over the tiles: the clusters count them as they grow
-    if (!build_clusters(n, rowptr, colind, base ? base->data() : nullptr, base ? inv0.data() : nullptr, order, tile_row, xcd_tile, osw, &dsum)) return false;
-    clk.lap("  clusters");
-    const double per_row = (double)dsum / (double)n;
-    if (osw.debug != 0)
-      fprintf(stderr, "[slq] tiles: %zu clusters, %.2f rows each, %.2f distinct panel rows per row (limit %.1f)\n", tile_row.size() - 1,
-              (double)n / (double)(tile_row.size() - 1), per_row, tile_limit);
-    return per_row <= tile_limit;
-  };
-  auto adopt = [&](std::vector<int32_t> &order) -> bool {
-    if (!op->perm_h) op->perm_h = new (std::nothrow) std::vector<int32_t>();
-    if (!op->perm_h) return false;
-    op->perm_h->swap(order);
-    return true;
-  };
-  std::vector<int32_t> rcm_perm;  // the in-chunk Cuthill-McKee order, computed at most once
-  const int sub_env = osw.rcm_sub;  // 0: 1 piece, except for the tile sweep below
-  auto rcm_order = [&]() -> const std::vector<int32_t> & {
-    if (rcm_perm.empty()) xcd_rcm_permutation(n, rowptr, colind, rcm_perm, std::max(1, sub_env), nullptr);
-    return rcm_perm;
-  };
-  // Ring-fed tiles sweep a chunk tile after tile, 32 CUs abreast, and re-read a neighbour tile's rows from L2 only if the
-  // neighbour is at most a few dozen tiles away: the BASE order must have short level sets, whatever the index distances
-  // are. On the 2-D grid of configs[1] in its natural order (grid rows of 1000 = 270 tiles) every vertical neighbour was
-  // fetched again (7.5 GB per dots pass against 6.3 algorithmic); on the in-chunk Cuthill-McKee order (levels of <= 125
-  // nodes = 34 tiles) the pass fetches 6.37 GB. So mode 2 clusters the Cuthill-McKee order unless SLQ_REORDER=0 forbids it.
-  // ... and level sets no longer than about one round of the sweep (32 CUs x 10 rows): a 12.5-plane slab of a 100^3 grid has
-  // level sets of 590 rows on average - its tiles then fetch 8.7 GB per dots pass against 6.1 algorithmic - so the chunk's
-  // order is cut into 4, 16, 64 runs of levels, each reordered on its own (xcd_rcm_permutation), until they are: 16 pieces
-  // there (level sets of ~200 rows, 7.5 GB). SLQ_RCM_SUB fixes the number of pieces.
-  if (try_tiles && tmode == 2 && reorder_mode != 0) {
-    if (sub_env <= 0) {
-      double w = 0.0;
-      std::vector<int32_t> level1;  // the chunks' own order (k = 1), which every finer attempt starts from
-      for (int k = 1; k <= 64; k *= 4) {
-        if (k == 4) level1 = rcm_perm;
-        xcd_rcm_permutation(n, rowptr, colind, rcm_perm, k, &w, k > 1 ? &level1 : nullptr);
-        clk.lap("  Cuthill-McKee in the chunks");
-        if (osw.debug != 0) fprintf(stderr, "[slq] tiles: %d piece(s) per chunk: level sets of %.0f rows on average\n", k, w);
-        if (w <= kTileLevelRows) break;
-      }
-    }
-    std::vector<int32_t> order;
-    if (cluster_tiles(&rcm_order(), order)) {
-      have_tiles = true;
-      if (!adopt(order)) { return fail(SLQ_ENOMEM, "host allocation failed"); }
-    } else if (sub_env <= 0) {
-      rcm_perm.clear();  // declined: the generic passes keep their own (one-piece) order, decided below
-    }
-  }
-  clk.lap("base order + clusters");
-  bool want = false;
-  if (nnz > 0 && !have_tiles) {
-    if (reorder_mode == 2) want = true;
-    else if (reorder_mode == 1) want = n >= 65536;
-    else if (reorder_mode < 0) want = n >= 65536 && mean_dist(nullptr) > 2048.0;
-  }
-  if (want) {
-    op->perm_h = new (std::nothrow) std::vector<int32_t>();
-    if (!op->perm_h) { return fail(SLQ_ENOMEM, "host allocation failed"); }
-    std::vector<int32_t> &perm = *op->perm_h;
-    perm = rcm_order();
-    std::vector<int32_t> inv((size_t)n);
-    for (int64_t i = 0; i < n; ++i) inv[(size_t)perm[(size_t)i]] = (int32_t)i;
-    const double d_new = mean_dist(&inv);
-    if (reorder_mode < 0 && d_new > 0.6 * mean_dist(nullptr)) {
-      delete op->perm_h;  // no locality to gain: keep the caller's order
-      op->perm_h = nullptr;
-    } else {
-      op->rms_dist = d_new;
-    }
-  }
-  // tiles on top of whatever order was chosen above: mode 1, and mode 2 when SLQ_REORDER=0 kept it from its own base order
-  if (try_tiles && !have_tiles && (tmode == 1 || reorder_mode == 0)) {
-    std::vector<int32_t> order;
-    if (cluster_tiles(op->perm_h, order)) {
-      have_tiles = true;
-      if (!adopt(order)) { return fail(SLQ_ENOMEM, "host allocation failed"); }
-    }
-  }
-  if (have_tiles) {
-    std::vector<int32_t> inv((size_t)n);
-    for (int64_t i = 0; i < n; ++i) inv[(size_t)(*op->perm_h)[(size_t)i]] = (int32_t)i;
-    op->rms_dist = mean_dist(&inv);
-  }
-  if (op->rms_dist < 0.0 && nnz > 0) op->rms_dist = mean_dist(nullptr);
-  clk.lap("reorder decision");
-  if (early_started && have_tiles && op->perm_h) {
-    const int rc = csr_finish_on_device(ctx, op, dtype, n, nnz, rowptr, colind, src_rp, src_ci, src_va, early, tile_row, xcd_tile, clk);
-    if (rc != SLQ_OK) return rc;
-    if (dev_mode == 2) {  // the same operator built on the host: every array must be the same
-      if (need_host_vals() != hipSuccess) return fail(SLQ_EHIP, "CSR values: copy back failed");
-      slq_operator *ref = nullptr;
-      const int rr = csr_create_impl(ctx, dtype, n, nnz, rowptr, colind, vals, &ref, plain, 1);
-      if (rr != SLQ_OK) return rr;
-      const int diff = operators_differ(op, ref);
-      slq_operator_destroy(ref);
-      if (diff) return fail(SLQ_EHIP, "the device-built operator differs from the host-built one (SLQ_DEVICE_BUILD=2, item %d)", diff);
-    }
-    clk.total("all of slq_csr_create");
-    guard.op = nullptr;
-    *out = op;
-    return SLQ_OK;
-  }
-  if (early_started) {  // no tiles after all: the host path below uploads what it builds
-    early.wait();
-    o_rp.release(), o_ci.release(), o_va.release();
-  }
-  if (need_host_vals() != hipSuccess) return fail(SLQ_EHIP, "CSR values: copy back failed");
-  // From here on every array goes to the device through `up` while the next one is being built; the buffers it reads are
-  // declared before it and nothing returns without up.wait() (its destructor, at the latest).
-  std::vector<int32_t> inv_keep;                  // stored row of every caller row (reordered operators)
   std::vector<int32_t> urp, uci;                  // the upper triangle (stored order), also the source of the alpha-only tile stream
   std::vector<char> uva;
   std::vector<int32_t> tp, tc, lc, si, tpu, tcu, lcu, siu;
@@ -1473,22 +637,13 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
     return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : code, "%s: %s", what, hipGetErrorString(e));
   };
   if (op->perm_h) {
-    std::vector<int32_t> &perm = *op->perm_h;
-    inv_keep.resize((size_t)n);
-    std::vector<int32_t> &inv = inv_keep;
-    for (int64_t i = 0; i < n; ++i) inv[(size_t)perm[(size_t)i]] = (int32_t)i;
+    const std::vector<int32_t> &perm = *op->perm_h, &inv = L.inv, &rp2 = L.rowptr_stored;
     hipError_t pe = hipMalloc((void **)&op->perm_d, (size_t)n * 4);
     if (pe == hipSuccess) pe = hipMalloc((void **)&op->inv_perm_d, (size_t)n * 4);
     if (pe != hipSuccess) return bail(SLQ_EHIP, "permutation upload", pe);
     up.push({{op->perm_d, perm.data(), (size_t)n * 4}, {op->inv_perm_d, inv.data(), (size_t)n * 4}});
-    rp2.resize((size_t)n + 1);
     ci2.alloc((size_t)nnz);
     va2.alloc((size_t)nnz * es);
-    rp2[0] = 0;
-    for (int64_t i = 0; i < n; ++i) {
-      const int32_t o = perm[(size_t)i];
-      rp2[(size_t)i + 1] = rp2[(size_t)i] + (rowptr[o + 1] - rowptr[o]);
-    }
     const bool pok = parallel_pieces(host_threads(), n, [&](int, int64_t i0, int64_t i1) {
       std::vector<std::pair<int32_t, int32_t>> rowbuf;
       for (int64_t i = i0; i < i1; ++i) {
@@ -1512,13 +667,8 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
     vals = va2.data();
   }
   clk.lap("permuted CSR");
-  // colind/vals carry kCsrPad spare entries: the batched row gather (slq_kernels.hpp: gather_row_uniform)
-  // loads indices and values 8 at a time and may read (never use) up to 7 entries past a row's end
   hipError_t e = hipMalloc((void **)&op->rowptr, (size_t)(n + 1) * 4);
-  if (e == hipSuccess) e = hipMalloc((void **)&op->colind, ((size_t)nnz + kCsrPad) * 4);
-  if (e == hipSuccess) e = hipMalloc(&op->vals, ((size_t)nnz + kCsrPad) * es);
-  if (e == hipSuccess) e = hipMemsetAsync(op->colind + nnz, 0, kCsrPad * 4, ctx->stream);
-  if (e == hipSuccess) e = hipMemsetAsync((char *)op->vals + (size_t)nnz * es, 0, kCsrPad * es, ctx->stream);
+  if (e == hipSuccess) e = alloc_padded_csr(&op->colind, &op->vals, (size_t)nnz, es, ctx->stream);
   if (e != hipSuccess) return bail(SLQ_EHIP, "CSR upload", e);
   up.push({{op->rowptr, rowptr, (size_t)(n + 1) * 4}, {op->colind, colind, (size_t)nnz * 4}, {op->vals, vals, (size_t)nnz * es}});
   {
@@ -1535,9 +685,7 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
     for (int64_t f : farp) far += f;
     op->far_per_row = (double)far / (double)n;
   }
-  if (osw.debug != 0)
-    fprintf(stderr, "[slq] csr n=%lld nnz=%lld reordered=%d rms in-chunk |i-j| = %.1f, far gathers per row %.2f\n", (long long)n,
-            (long long)nnz, op->perm_h ? 1 : 0, op->rms_dist, op->far_per_row);
+  debug_stored_csr(op, "");
   clk.lap("far count");
   // Symmetric operators (what Lanczos assumes; the reference never checks): the alpha pass only needs the
   // scalar q^T A q, so it can run on the upper triangle with doubled off-diagonals and gather half the
@@ -1551,17 +699,14 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
       const size_t nu = uci.size();
       op->nnz_u = (int64_t)nu;
       hipError_t ue = hipMalloc((void **)&op->rowptr_u, (size_t)(n + 1) * 4);
-      if (ue == hipSuccess) ue = hipMalloc((void **)&op->colind_u, (nu + kCsrPad) * 4);
-      if (ue == hipSuccess) ue = hipMalloc(&op->vals_u, (nu + kCsrPad) * es);
-      if (ue == hipSuccess) ue = hipMemsetAsync(op->colind_u + nu, 0, kCsrPad * 4, ctx->stream);
-      if (ue == hipSuccess) ue = hipMemsetAsync((char *)op->vals_u + nu * es, 0, kCsrPad * es, ctx->stream);
+      if (ue == hipSuccess) ue = alloc_padded_csr(&op->colind_u, &op->vals_u, nu, es, ctx->stream);
       if (ue != hipSuccess) return bail(SLQ_EHIP, "upper-triangle upload", ue);
       up.push({{op->rowptr_u, urp.data(), (size_t)(n + 1) * 4}, {op->colind_u, uci.data(), nu * 4}, {op->vals_u, uva.data(), nu * es}});
     }
   }
   clk.lap("upper triangle");
   // workgroup tiles (SLQ_TILES): lists of the stored CSR, uploaded next to it
-  if (have_tiles) {
+  if (L.have_tiles) {
     int mx = 0;
     build_tile_meta(n, rowptr, colind, tile_row, tp, tc, lc, si, &mx, osw);
     clk.lap("  tile lists");
@@ -1587,7 +732,7 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
       }
       up.push(std::move(jobs));
     }
-    for (int x = 0; x < 9; ++x) op->tiles.xcd_tile[x] = xcd_tile[x];
+    for (int x = 0; x < 9; ++x) op->tiles.xcd_tile[x] = L.xcd_tile[x];
     op->tiles.max_cols = mx;
     op->tiles_ringed = osw.tiles == 2;
     if (op->tiles_ringed) op->merged_lock = new (std::nothrow) std::mutex();
@@ -1605,30 +750,25 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
         int mxu = 0;
         // (its own, longer tiles: runs of the base tiles - the pass pays per tile, regroup_upper_tiles; SLQ_RING_UPPER_REGROUP=0 keeps the base tiles)
         std::vector<int32_t> tile_row_u;
-        // (not where the base tiles are as tall as a tile gets - a 5-point grid's 13.9 of 14 rows: nothing to join, 10-20 ms of host time saved)
-        const bool tall_already = (double)n / (double)(tile_row.size() - 1) > 0.8 * kRingTileRows;
-        if (osw.ring_upper_regroup != 0 && !tall_already) {
-          regroup_upper_tiles(urp.data(), uci.data(), tile_row, xcd_tile, tile_row_u, op->xcd_tile_u);
+        if (regroup_upper_wanted(osw, n, tile_row.size() - 1)) {
+          regroup_upper_tiles(urp.data(), uci.data(), tile_row, L.xcd_tile, tile_row_u, op->xcd_tile_u);
         } else {
           tile_row_u = tile_row;
-          for (int x = 0; x < 9; ++x) op->xcd_tile_u[x] = xcd_tile[x];
+          for (int x = 0; x < 9; ++x) op->xcd_tile_u[x] = L.xcd_tile[x];
         }
-        if (osw.debug != 0)
-          fprintf(stderr, "[slq] tiles: upper-triangle stream on %zu tiles of %.2f rows (base: %zu of %.2f)\n", tile_row_u.size() - 1, (double)n / (double)(tile_row_u.size() - 1),
-                  tile_row.size() - 1, (double)n / (double)(tile_row.size() - 1));
+        debug_upper_tiles(op, tile_row_u.size() - 1, tile_row.size() - 1);
         build_tile_meta(n, urp.data(), uci.data(), tile_row_u, tpu, tcu, lcu, siu, &mxu, osw);
         clk.lap("  upper tile lists");
         // Worth it while the tiles land at most kTileAlphaColsPerRow panel rows per row (r03, scalar-descriptor loaders and the
         // padded-row consumer of slq_ring.hpp: 5-point grid, 1.5 rows per row: 0.40 against 0.51 ms for the generic pass; 7-point
         // grid, 2.5: 0.66 against 0.81 ms)
-        const double upper_per_row = (double)(tcu.size() - kCsrPad) / (double)n;
-        if (osw.debug != 0) fprintf(stderr, "[slq] tiles: upper triangle: %.2f distinct panel rows per row, longest list %d (full rows: %d)\n", upper_per_row, mxu, mx);
         op->tile_max_lines_u = mxu;
-        op->upper_per_row = upper_per_row;
+        op->upper_per_row = (double)(tcu.size() - kCsrPad) / (double)n;
+        debug_upper_lists(op);
         // (built up to kTileAlphaMergedColsPerRow: wide panels take it up to kTileAlphaColsPerRow, slq_plan_create; the merged
         // tiles of narrow panels share more of their halo and gain from it on 7-point grids too - 100^3, 64 probes: alpha pass
         // 0.25 against 0.35 ms for the generic upper-triangle pass)
-        if (upper_per_row <= kTileAlphaMergedColsPerRow) {
+        if (op->upper_per_row <= kTileAlphaMergedColsPerRow) {
           bool pad = osw.ring_pad_rows != 0;
           if (dtype == SLQ_F64) build_ring_stream<double>(1, urp.data(), (const double *)uva.data(), tile_row_u, tpu, tcu, lcu, siu, desc_u, rec_u, &pad);
           else build_ring_stream<float>(1, urp.data(), (const float *)uva.data(), tile_row_u, tpu, tcu, lcu, siu, desc_u, rec_u, &pad);
@@ -1647,52 +787,30 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) return bail(SLQ_EHIP, "operator upload", e);
   clk.lap("uploads drained");
-  clk.total("all of slq_csr_create");
-  guard.op = nullptr;
-  *out = op;
   return SLQ_OK;
 }
 
-// The second half of slq_csr_create for operators with ring-sized tiles (SLQ_DEVICE_BUILD, slq_build.hpp): given the order and the
-// tiles (host), everything stored with the operator is built on the device from the caller's CSR (o_rp, o_ci, o_va: on their way up
-// through `early`): the permuted CSR, the far-gather count, the symmetry check and the upper triangle, both tile streams. The one
-// sequential piece left - the runs of base tiles the upper-triangle stream's tiles are made of (regroup_upper_tiles) - runs on a host
-// thread meanwhile, on the caller's CSR seen through the permutation.
-static int csr_finish_on_device(slq_context *ctx, slq_operator *op, int dtype, int64_t n, int64_t nnz, const int32_t *rowptr0, const int32_t *colind0,
-                                const int32_t *o_rp, const int32_t *o_ci, const void *o_va, UploadQueue &early, const std::vector<int32_t> &tile_row,
-                                const int32_t xcd_tile[9], PhaseClock &clk) {
+// The same storage for operators with ring-sized tiles, built on the device (SLQ_DEVICE_BUILD, slq_build.hpp) from the caller's CSR
+// (src: on its way up through `early`, or the caller's own device arrays): the permuted CSR, the far-gather count, the symmetry check and
+// the upper triangle, both tile streams. The one sequential piece left - the runs of base tiles the upper-triangle stream's tiles are
+// made of (regroup_upper_tiles_permuted) - runs on a host thread meanwhile, on the caller's CSR seen through the permutation.
+static int build_storage_device(slq_context *ctx, slq_operator *op, const CsrView &A, const DeviceCsr &src, UploadQueue &early, const OperatorLayout &L, PhaseClock &clk) {
   hipStream_t st = ctx->stream;
+  const int64_t n = A.n, nnz = A.nnz;
+  const int dtype = op->dtype;
   const size_t es = esize(dtype);
-  const std::vector<int32_t> &perm = *op->perm_h;
+  const std::vector<int32_t> &perm = *op->perm_h, &tile_row = L.tile_row;
   const int ntiles = (int)tile_row.size() - 1;
-  std::vector<int32_t> inv((size_t)n), rp2((size_t)n + 1);
-  for (int64_t i = 0; i < n; ++i) inv[(size_t)perm[(size_t)i]] = (int32_t)i;
-  rp2[0] = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    const int32_t o = perm[(size_t)i];
-    rp2[(size_t)i + 1] = rp2[(size_t)i] + (rowptr0[o + 1] - rowptr0[o]);
-  }
   const OperatorSwitches &osw = op->sw;
   const bool want_sym = osw.sym_alpha != 0;
-  const bool tall_already = (double)n / (double)ntiles > 0.8 * kRingTileRows;
-  const bool regroup = want_sym && osw.ring_upper_regroup != 0 && !tall_already;
+  const bool regroup = want_sym && regroup_upper_wanted(osw, n, (size_t)ntiles);
   std::vector<int32_t> tile_row_u;
   int32_t xcd_u[9];
-  for (int x = 0; x < 9; ++x) xcd_u[x] = xcd_tile[x];
+  for (int x = 0; x < 9; ++x) xcd_u[x] = L.xcd_tile[x];
   std::atomic<int> rg_failed{0};
   auto do_regroup = [&]() {
     try {
-      regroup_upper_tiles_impl(
-          [&](int32_t r, auto &consider) {
-            const int32_t o = perm[(size_t)r];
-            int32_t cnt = 0;
-            for (int32_t q = rowptr0[o]; q < rowptr0[o + 1]; ++q) {
-              const int32_t c = inv[(size_t)colind0[q]];
-              if (c >= r) consider(c), ++cnt;
-            }
-            return cnt;
-          },
-          tile_row, xcd_tile, tile_row_u, xcd_u);
+      regroup_upper_tiles_permuted(A.rowptr, A.colind, perm, L.inv, tile_row, L.xcd_tile, tile_row_u, xcd_u);
     } catch (...) {
       rg_failed = 1;
     }
@@ -1716,22 +834,19 @@ static int csr_finish_on_device(slq_context *ctx, slq_operator *op, int dtype, i
   hipError_t e = hipMalloc((void **)&op->perm_d, (size_t)n * 4);
   if (e == hipSuccess) e = hipMalloc((void **)&op->inv_perm_d, (size_t)n * 4);
   if (e == hipSuccess) e = hipMalloc((void **)&op->rowptr, (size_t)(n + 1) * 4);
-  if (e == hipSuccess) e = hipMalloc((void **)&op->colind, ((size_t)nnz + kCsrPad) * 4);
-  if (e == hipSuccess) e = hipMalloc(&op->vals, ((size_t)nnz + kCsrPad) * es);
+  if (e == hipSuccess) e = alloc_padded_csr(&op->colind, &op->vals, (size_t)nnz, es, st);
   if (e == hipSuccess) e = hipMalloc((void **)&d_tr, tile_row.size() * 4);
   op->tiles.tile_row = d_tr;
   if (e == hipSuccess) e = hipMemcpy(op->perm_d, perm.data(), (size_t)n * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(op->inv_perm_d, inv.data(), (size_t)n * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(op->rowptr, rp2.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(op->inv_perm_d, L.inv.data(), (size_t)n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(op->rowptr, L.rowptr_stored.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_tr, tile_row.data(), tile_row.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemsetAsync(op->colind + nnz, 0, kCsrPad * 4, st);
-  if (e == hipSuccess) e = hipMemsetAsync((char *)op->vals + (size_t)nnz * es, 0, kCsrPad * es, st);
   if (e == hipSuccess) e = early.wait();
   if (e != hipSuccess) return hip_fail("CSR upload", e);
   clk.lap("  order, tile boundaries and the caller's CSR on the device");
   const dim3 grow((unsigned)((n + 255) / 256)), brow(256);
-  if (dtype == SLQ_F64) slqb::k_permute_csr<double><<<grow, brow, 0, st>>>((int)n, o_rp, o_ci, (const double *)o_va, op->perm_d, op->inv_perm_d, op->rowptr, op->colind, (double *)op->vals);
-  else slqb::k_permute_csr<float><<<grow, brow, 0, st>>>((int)n, o_rp, o_ci, (const float *)o_va, op->perm_d, op->inv_perm_d, op->rowptr, op->colind, (float *)op->vals);
+  if (dtype == SLQ_F64) slqb::k_permute_csr<double><<<grow, brow, 0, st>>>((int)n, src.rp, src.ci, (const double *)src.va, op->perm_d, op->inv_perm_d, op->rowptr, op->colind, (double *)op->vals);
+  else slqb::k_permute_csr<float><<<grow, brow, 0, st>>>((int)n, src.rp, src.ci, (const float *)src.va, op->perm_d, op->inv_perm_d, op->rowptr, op->colind, (float *)op->vals);
   DevBuf misc;  // [0..1] far gathers (u64), [2] "not symmetric"
   e = misc.alloc(16);
   if (e == hipSuccess) e = hipMemsetAsync(misc.p, 0, 16, st);
@@ -1761,17 +876,12 @@ static int csr_finish_on_device(slq_context *ctx, slq_operator *op, int dtype, i
     if (e == hipSuccess) e = hipMemcpy(&nu32, op->rowptr_u + n, 4, hipMemcpyDeviceToHost);
     const size_t nu = (size_t)nu32;
     op->nnz_u = (int64_t)nu;
-    if (e == hipSuccess) e = hipMalloc((void **)&op->colind_u, (nu + kCsrPad) * 4);
-    if (e == hipSuccess) e = hipMalloc(&op->vals_u, (nu + kCsrPad) * es);
-    if (e == hipSuccess) e = hipMemsetAsync(op->colind_u + nu, 0, kCsrPad * 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync((char *)op->vals_u + nu * es, 0, kCsrPad * es, st);
+    if (e == hipSuccess) e = alloc_padded_csr(&op->colind_u, &op->vals_u, nu, es, st);
     if (e != hipSuccess) return hip_fail("upper triangle", e);
     if (dtype == SLQ_F64) slqb::k_upper_fill<double><<<grow, brow, 0, st>>>((int)n, op->rowptr, op->colind, (const double *)op->vals, op->rowptr_u, op->colind_u, (double *)op->vals_u);
     else slqb::k_upper_fill<float><<<grow, brow, 0, st>>>((int)n, op->rowptr, op->colind, (const float *)op->vals, op->rowptr_u, op->colind_u, (float *)op->vals_u);
   }
-  if (osw.debug != 0)
-    fprintf(stderr, "[slq] csr n=%lld nnz=%lld reordered=1 rms in-chunk |i-j| = %.1f, far gathers per row %.2f (built on the device)\n", (long long)n, (long long)nnz,
-            op->rms_dist, op->far_per_row);
+  debug_stored_csr(op, " (built on the device)");
   clk.lap("  device: stored CSR, upper triangle");
   // the tiles' stream over the full rows
   DeviceStream full;
@@ -1781,7 +891,7 @@ static int csr_finish_on_device(slq_context *ctx, slq_operator *op, int dtype, i
   op->tile_desc_bytes = full.desc_bytes, op->tile_rec_bytes = full.rec_bytes;
   op->tiles.tile_ptr = full.tile_ptr;
   op->tiles.max_cols = full.max_lines;
-  for (int x = 0; x < 9; ++x) op->tiles.xcd_tile[x] = xcd_tile[x];
+  for (int x = 0; x < 9; ++x) op->tiles.xcd_tile[x] = L.xcd_tile[x];
   op->tiles_ringed = true;
   op->merged_lock = new (std::nothrow) std::mutex();
   clk.lap("  device: tile stream");
@@ -1791,8 +901,7 @@ static int csr_finish_on_device(slq_context *ctx, slq_operator *op, int dtype, i
     if (!regroup) tile_row_u = tile_row;
     for (int x = 0; x < 9; ++x) op->xcd_tile_u[x] = xcd_u[x];
     const int ntu = (int)tile_row_u.size() - 1;
-    if (osw.debug != 0)
-      fprintf(stderr, "[slq] tiles: upper-triangle stream on %d tiles of %.2f rows (base: %d of %.2f)\n", ntu, (double)n / (double)ntu, ntiles, (double)n / (double)ntiles);
+    debug_upper_tiles(op, (size_t)ntu, (size_t)ntiles);
     DevBuf d_tru;
     e = d_tru.alloc(tile_row_u.size() * 4);
     if (e == hipSuccess) e = hipMemcpy(d_tru.p, tile_row_u.data(), tile_row_u.size() * 4, hipMemcpyHostToDevice);
@@ -1803,8 +912,7 @@ static int csr_finish_on_device(slq_context *ctx, slq_operator *op, int dtype, i
     if (rc < 0) return rc;
     op->tile_max_lines_u = us.max_lines;
     op->upper_per_row = (double)us.sum_lines / (double)n;
-    if (osw.debug != 0)
-      fprintf(stderr, "[slq] tiles: upper triangle: %.2f distinct panel rows per row, longest list %d (full rows: %d)\n", op->upper_per_row, us.max_lines, full.max_lines);
+    debug_upper_lists(op);
     if (rc == 0) {
       op->tile_desc_u = us.desc, op->tile_rec_u = us.rec;
       op->tile_desc_u_bytes = us.desc_bytes, op->tile_rec_u_bytes = us.rec_bytes;
@@ -1817,15 +925,107 @@ static int csr_finish_on_device(slq_context *ctx, slq_operator *op, int dtype, i
   return SLQ_OK;
 }
 
+// a square CSR pattern the library can store: int32 shape, row pointer from 0 to nnz and non-decreasing, every column inside [0, n)
+static int validate_csr(int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colind) {
+  if (n <= 0 || n >= (int64_t)1 << 31 || nnz < 0 || nnz >= (int64_t)1 << 31)
+    return fail(SLQ_EINVAL, "CSR shape out of range for int32 indices (n=%lld, nnz=%lld)",
+                (long long)n, (long long)nnz);
+  if (!rowptr || (nnz > 0 && !colind)) return fail(SLQ_EINVAL, "CSR arrays are NULL");
+  if (rowptr[0] != 0 || rowptr[n] != nnz)
+    return fail(SLQ_EINVAL, "rowptr[0] must be 0 and rowptr[n] must equal nnz");
+  for (int64_t i = 0; i < n; ++i)
+    if (rowptr[i + 1] < rowptr[i]) return fail(SLQ_EINVAL, "rowptr is not non-decreasing at %lld", (long long)i);
+  // every column index inside [0, n): ranges of the array in parallel, the first offender (lowest position) reported
+  const int pieces = host_threads();
+  std::vector<int64_t> bad((size_t)pieces, -1);
+  if (!parallel_pieces(pieces, nnz, [&](int piece, int64_t p0, int64_t p1) {
+        for (int64_t p = p0; p < p1; ++p)
+          if (colind[p] < 0 || colind[p] >= n) { bad[(size_t)piece] = p; break; }
+      }))
+    return fail(SLQ_ENOMEM, "host worker failed while validating the column indices");
+  for (int64_t b : bad)
+    if (b >= 0) return fail(SLQ_EINVAL, "column index %d out of range at position %lld", colind[b], (long long)b);
+  return SLQ_OK;
+}
+
+static int operators_differ(const slq_operator *a, const slq_operator *b);
+// A CSR operator's creation, phase by phase: validate, layout_prefilter, start the early upload, decide_layout (slq_layout.hpp),
+// then one of the two storage builders, which consume the same OperatorLayout.
+static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colind,
+                           const void *vals, slq_operator **out, int plain, int host_build, DeviceCsr dev) {
+  if (!ctx || !out) return fail(SLQ_EINVAL, "ctx/out is NULL");
+  *out = nullptr;
+  SLQ_TRY(check_dtype(dtype));
+  const OperatorSwitches osw = read_operator_switches();  // (the one read of this creation: everything below, and the operator, keep these values)
+  PhaseClock clk(osw);
+  SLQ_TRY(validate_csr(n, nnz, rowptr, colind));
+  if (nnz > 0 && !vals && !dev.va) return fail(SLQ_EINVAL, "CSR arrays are NULL");
+  HIP_TRY(hipSetDevice(ctx->device));
+  clk.lap("validation");
+  if (ctx->dead) return fail(SLQ_EINVAL, "the context has been destroyed");
+  slq_operator *op = new (std::nothrow) slq_operator();
+  if (!op) return fail(SLQ_ENOMEM, "host allocation failed");
+  ctx_retain(ctx);
+  *op = slq_operator{ctx, OP_CSR, dtype, n, nnz, nullptr, nullptr, nullptr, 0, true, nullptr, nullptr, nullptr, nullptr, TileMeta{}};
+  op->sw = osw;
+  OpGuard guard{op};
+  const CsrView A{n, nnz, rowptr, colind};
+  const LayoutPrefilter pre = layout_prefilter(A, osw, plain != 0);
+  clk.lap("tile sample");
+  // SLQ_DEVICE_BUILD (r04, slq_build.hpp): 1 (default) - an operator that gets ring-sized tiles has its stored CSR, upper triangle and
+  // tile streams built on the device from the caller's CSR, which starts its way up now, while the host orders and clusters the rows;
+  // 0 - everything on the host, as before; 2 - both, compared array by array (tests)
+  const int dev_mode = (plain || host_build) ? 0 : osw.device_build;
+  const bool early_started = dev_mode != 0 && pre.try_tiles && pre.tmode == 2 && pre.reorder_mode != 0 && osw.ring_order == 0;
+  DevBuf o_rp, o_ci, o_va;         // the caller's CSR on the device (scratch of the build)
+  UploadQueue early(ctx->device);  // (declared after what it fills: joined first)
+  DeviceCsr src = dev;             // where the device-side build reads the caller's CSR: in place (slq_csr_create_device), or
+  if (early_started && !dev.va) {  // ... from the scratch the early upload fills
+    hipError_t ee = o_rp.alloc((size_t)(n + 1) * 4);
+    if (ee == hipSuccess) ee = o_ci.alloc((size_t)nnz * 4);
+    if (ee == hipSuccess) ee = o_va.alloc((size_t)nnz * esize(dtype));
+    if (ee != hipSuccess) return fail(ee == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "CSR upload: %s", hipGetErrorString(ee));
+    early.push({{o_rp.p, rowptr, (size_t)(n + 1) * 4}, {o_ci.p, colind, (size_t)nnz * 4}, {o_va.p, vals, (size_t)nnz * esize(dtype)}});
+    src.rp = o_rp.as<int32_t>(), src.ci = o_ci.as<int32_t>(), src.va = o_va.p;
+  }
+  OperatorLayout L = decide_layout(A, osw, pre, &clk);
+  op->rms_dist = L.rms_dist;
+  if (!L.perm.empty()) op->perm_h = new std::vector<int32_t>(std::move(L.perm));  // (the operator keeps the order; the builders read it there)
+  std::vector<char> vals_back;  // the values of a device-resident CSR, fetched when the host needs them
+  auto need_host_vals = [&]() -> hipError_t {
+    if (vals || nnz == 0) return hipSuccess;
+    vals_back.resize((size_t)nnz * esize(dtype));
+    const hipError_t he = hipMemcpy(vals_back.data(), dev.va, vals_back.size(), hipMemcpyDeviceToHost);
+    vals = vals_back.data();
+    return he;
+  };
+  if (early_started && L.have_tiles) {
+    SLQ_TRY(build_storage_device(ctx, op, A, src, early, L, clk));
+    if (dev_mode == 2) {  // the same operator built on the host: every array must be the same
+      if (need_host_vals() != hipSuccess) return fail(SLQ_EHIP, "CSR values: copy back failed");
+      slq_operator *ref = nullptr;
+      SLQ_TRY(csr_create_impl(ctx, dtype, n, nnz, rowptr, colind, vals, &ref, plain, 1));
+      const int diff = operators_differ(op, ref);
+      slq_operator_destroy(ref);
+      if (diff) return fail(SLQ_EHIP, "the device-built operator differs from the host-built one (SLQ_DEVICE_BUILD=2, item %d)", diff);
+    }
+  } else {
+    if (early_started) {  // no tiles after all: the host builder uploads what it builds
+      early.wait();
+      o_rp.release(), o_ci.release(), o_va.release();
+    }
+    if (need_host_vals() != hipSuccess) return fail(SLQ_EHIP, "CSR values: copy back failed");
+    SLQ_TRY(build_storage_host(ctx, op, A, vals, L, plain, clk));
+  }
+  clk.total("all of slq_csr_create");
+  *out = guard.release();
+  return SLQ_OK;
+}
+
 // SLQ_DEVICE_BUILD=2: 0 when everything two operators over the same matrix keep is the same, else the number of the first item that is not
 static int operators_differ(const slq_operator *a, const slq_operator *b) {
   const size_t es = esize(a->dtype);
-  auto same = [](const void *x, const void *y, size_t bytes) {
-    if (!x || !y) return x == y;
-    std::vector<char> hx(bytes), hy(bytes);
-    if (hipMemcpy(hx.data(), x, bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hy.data(), y, bytes, hipMemcpyDeviceToHost) != hipSuccess) return false;
-    return memcmp(hx.data(), hy.data(), bytes) == 0;
-  };
+  auto same = device_equals_device;
   const size_t n = (size_t)a->n, nnz = (size_t)a->nnz;
   if (a->n != b->n || a->nnz != b->nnz || a->nnz_u != b->nnz_u || a->dtype != b->dtype) return 1;
   if (!a->perm_h || !b->perm_h || *a->perm_h != *b->perm_h) return 2;
@@ -1859,9 +1059,8 @@ static int operators_differ(const slq_operator *a, const slq_operator *b) {
   return 0;
 }
 
-extern "C" int slq_csr_create_device(slq_context *ctx, int dtype, int64_t n, int64_t nnz,
-                                     const int32_t *d_rowptr, const int32_t *d_colind,
-                                     const void *d_vals, slq_operator **out) {
+static int csr_create_device_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colind,
+                                  const void *d_vals, slq_operator **out) {
   if (!ctx || !out) return fail(SLQ_EINVAL, "ctx/out is NULL");
   *out = nullptr;
   SLQ_TRY(check_dtype(dtype));
@@ -1874,22 +1073,21 @@ extern "C" int slq_csr_create_device(slq_context *ctx, int dtype, int64_t n, int
   // tiles are decided on the host, from the index arrays (4 bytes per nonzero come back, once); what the operator stores is then built
   // on the device straight from the caller's arrays (slq_build.hpp) - the values come back only for operators without ring tiles, whose
   // storage the host builds. The caller's arrays are not referenced after the call.
-  std::vector<int32_t> rp, ci;
-  try {
-    rp.resize((size_t)n + 1);
-    ci.resize((size_t)nnz);
-  } catch (const std::bad_alloc &) {
-    return fail(SLQ_ENOMEM, "host allocation failed");
-  }
+  std::vector<int32_t> rp((size_t)n + 1), ci((size_t)nnz);
   HIP_TRY(hipMemcpy(rp.data(), d_rowptr, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost));
   if (nnz) HIP_TRY(hipMemcpy(ci.data(), d_colind, (size_t)nnz * 4, hipMemcpyDeviceToHost));
   DeviceCsr dev;
   dev.rp = d_rowptr, dev.ci = d_colind, dev.va = d_vals;
   return csr_create_impl(ctx, dtype, n, nnz, rp.data(), ci.data(), nullptr, out, 0, 0, dev);
 }
+extern "C" int slq_csr_create_device(slq_context *ctx, int dtype, int64_t n, int64_t nnz,
+                                     const int32_t *d_rowptr, const int32_t *d_colind,
+                                     const void *d_vals, slq_operator **out) {
+  return create_guarded(out, [&]() { return csr_create_device_body(ctx, dtype, n, nnz, d_rowptr, d_colind, d_vals, out); });
+}
 
-extern "C" int slq_csr_gram_create(slq_context *ctx, int dtype, int64_t mrows, int64_t ncols, int64_t nnz, const int32_t *rowptr,
-                                   const int32_t *colind, const void *vals, slq_operator **out) {
+static int csr_gram_create_body(slq_context *ctx, int dtype, int64_t mrows, int64_t ncols, int64_t nnz, const int32_t *rowptr,
+                                const int32_t *colind, const void *vals, slq_operator **out) {
   if (!ctx || !out) return fail(SLQ_EINVAL, "ctx/out is NULL");
   *out = nullptr;
   SLQ_TRY(check_dtype(dtype));
@@ -1909,6 +1107,7 @@ extern "C" int slq_csr_gram_create(slq_context *ctx, int dtype, int64_t mrows, i
   *op = slq_operator{ctx, OP_GRAM, dtype, ncols, nnz, nullptr, nullptr, nullptr, 0, true, nullptr, nullptr, nullptr, nullptr, TileMeta{}};
   op->sw = read_operator_switches();
   op->mrows = mrows;
+  OpGuard guard{op};
   const size_t es = esize(dtype);
   // transpose on the host (counting sort by column; rows of A^T come out with ascending indices)
   std::vector<int32_t> tp((size_t)ncols + 1, 0), tc((size_t)nnz);
@@ -1925,11 +1124,9 @@ extern "C" int slq_csr_gram_create(slq_context *ctx, int dtype, int64_t mrows, i
       }
   }
   hipError_t e = hipMalloc((void **)&op->rowptr, (size_t)(mrows + 1) * 4);
-  if (e == hipSuccess) e = hipMalloc((void **)&op->colind, ((size_t)nnz + kCsrPad) * 4);
-  if (e == hipSuccess) e = hipMalloc(&op->vals, ((size_t)nnz + kCsrPad) * es);
+  if (e == hipSuccess) e = alloc_padded_csr(&op->colind, &op->vals, (size_t)nnz, es, ctx->stream);
   if (e == hipSuccess) e = hipMalloc((void **)&op->rowptr_t, (size_t)(ncols + 1) * 4);
-  if (e == hipSuccess) e = hipMalloc((void **)&op->colind_t, ((size_t)nnz + kCsrPad) * 4);
-  if (e == hipSuccess) e = hipMalloc(&op->vals_t, ((size_t)nnz + kCsrPad) * es);
+  if (e == hipSuccess) e = alloc_padded_csr(&op->colind_t, &op->vals_t, (size_t)nnz, es, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(op->rowptr, rowptr, (size_t)(mrows + 1) * 4, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess && nnz) e = hipMemcpyAsync(op->colind, colind, (size_t)nnz * 4, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess && nnz) e = hipMemcpyAsync(op->vals, vals, (size_t)nnz * es, hipMemcpyHostToDevice, ctx->stream);
@@ -1937,20 +1134,21 @@ extern "C" int slq_csr_gram_create(slq_context *ctx, int dtype, int64_t mrows, i
   if (e == hipSuccess && nnz) e = hipMemcpyAsync(op->colind_t, tc.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess && nnz) e = hipMemcpyAsync(op->vals_t, tv.data(), (size_t)nnz * es, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    slq_operator_destroy(op);
-    return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "Gram operator upload: %s", hipGetErrorString(e));
-  }
-  *out = op;
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "Gram operator upload: %s", hipGetErrorString(e));
+  *out = guard.release();
   return SLQ_OK;
+}
+extern "C" int slq_csr_gram_create(slq_context *ctx, int dtype, int64_t mrows, int64_t ncols, int64_t nnz, const int32_t *rowptr,
+                                   const int32_t *colind, const void *vals, slq_operator **out) {
+  return create_guarded(out, [&]() { return csr_gram_create_body(ctx, dtype, mrows, ncols, nnz, rowptr, colind, vals, out); });
 }
 
 // Affine sparse operator A + t B (eigen_operators.h:106-137, SparseEigenAffineOperator): both n x n CSR. The operator is an
 // ordinary CSR operator on the UNION pattern - every fused pass applies - whose values are va + t vb, recomputed on the
 // device by slq_operator_set_parameter (t = 0 at creation, like the reference's _param).
-extern "C" int slq_csr_affine_create(slq_context *ctx, int dtype, int64_t n, int64_t nnz_a, const int32_t *rp_a, const int32_t *ci_a,
-                                     const void *va, int64_t nnz_b, const int32_t *rp_b, const int32_t *ci_b, const void *vb,
-                                     slq_operator **out) {
+static int csr_affine_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz_a, const int32_t *rp_a, const int32_t *ci_a,
+                                  const void *va, int64_t nnz_b, const int32_t *rp_b, const int32_t *ci_b, const void *vb,
+                                  slq_operator **out) {
   if (!ctx || !out) return fail(SLQ_EINVAL, "ctx/out is NULL");
   *out = nullptr;
   SLQ_TRY(check_dtype(dtype));
@@ -1966,7 +1164,6 @@ extern "C" int slq_csr_affine_create(slq_context *ctx, int dtype, int64_t n, int
   std::vector<char> ua, ub;
   std::vector<std::pair<int32_t, int>> a_row, b_row;
   const char zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  try {
   rp.assign((size_t)n + 1, 0);
   ci.reserve((size_t)std::max(nnz_a, nnz_b));
   for (int64_t i = 0; i < n; ++i) {
@@ -1990,26 +1187,26 @@ extern "C" int slq_csr_affine_create(slq_context *ctx, int dtype, int64_t n, int
     if (ci.size() >= ((size_t)1 << 31)) return fail(SLQ_EINVAL, "the union pattern exceeds int32 indices");
     rp[(size_t)i + 1] = (int32_t)ci.size();
   }
-  } catch (const std::bad_alloc &) {  // no C++ exception crosses the C boundary
-    return fail(SLQ_ENOMEM, "host allocation failed");
-  }
   const int64_t nnz = (int64_t)ci.size();
   // the union pattern with A's values is an ordinary CSR operator; keep its rows as given (no reordering, no upper-triangle
   // alpha pass: both would have to follow every parameter change)
   slq_operator *op = nullptr;
   const int rc = csr_create_impl(ctx, dtype, n, nnz, rp.data(), ci.data(), ua.data(), &op, 1);
   if (rc != SLQ_OK) return rc;
+  OpGuard guard{op};
   hipError_t e = hipMalloc(&op->vals_a, std::max<size_t>((size_t)nnz * es, 8));
   if (e == hipSuccess) e = hipMalloc(&op->vals_b, std::max<size_t>((size_t)nnz * es, 8));
   if (e == hipSuccess && nnz) e = hipMemcpyAsync(op->vals_a, ua.data(), (size_t)nnz * es, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess && nnz) e = hipMemcpyAsync(op->vals_b, ub.data(), (size_t)nnz * es, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    slq_operator_destroy(op);
-    return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "affine operator upload: %s", hipGetErrorString(e));
-  }
-  *out = op;
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "affine operator upload: %s", hipGetErrorString(e));
+  *out = guard.release();
   return SLQ_OK;
+}
+extern "C" int slq_csr_affine_create(slq_context *ctx, int dtype, int64_t n, int64_t nnz_a, const int32_t *rp_a, const int32_t *ci_a,
+                                     const void *va, int64_t nnz_b, const int32_t *rp_b, const int32_t *ci_b, const void *vb,
+                                     slq_operator **out) {
+  return create_guarded(out, [&]() { return csr_affine_create_body(ctx, dtype, n, nnz_a, rp_a, ci_a, va, nnz_b, rp_b, ci_b, vb, out); });
 }
 
 // t of an affine operator A + t B (SparseEigenAffineOperator::set_parameter, eigen_operators.h:134-136)
@@ -2026,8 +1223,7 @@ extern "C" int slq_operator_set_parameter(slq_operator *op, double t) {
   return SLQ_OK;
 }
 
-extern "C" int slq_dense_create(slq_context *ctx, int dtype, int64_t n, const void *A, int64_t lda,
-                                slq_operator **out) {
+static int dense_create_body(slq_context *ctx, int dtype, int64_t n, const void *A, int64_t lda, slq_operator **out) {
   if (!ctx || !out) return fail(SLQ_EINVAL, "ctx/out is NULL");
   *out = nullptr;
   SLQ_TRY(check_dtype(dtype));
@@ -2039,6 +1235,7 @@ extern "C" int slq_dense_create(slq_context *ctx, int dtype, int64_t n, const vo
   ctx_retain(ctx);
   *op = slq_operator{ctx, OP_DENSE, dtype, n, n * n, nullptr, nullptr, nullptr, n, true, nullptr, nullptr, nullptr, nullptr, TileMeta{}};
   op->sw = read_operator_switches();
+  OpGuard guard{op};
   const size_t es = esize(dtype);
   // Y = A X for whatever is given (eigen_operators.h:24-30 does not ask for symmetry either). k_dense_mfma_3term reads
   // A(row, k) and is right for any A; k_dense_panel walks row `row` of A as the contiguous COLUMN `row`, which is A^T:
@@ -2056,13 +1253,7 @@ extern "C" int slq_dense_create(slq_context *ctx, int dtype, int64_t n, const vo
     e = hipMemcpy2DAsync(op->vals, (size_t)n * es, A, (size_t)lda * es, (size_t)n * es, (size_t)n,
                          hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess && !symmetric) {
-    std::vector<char> T;
-    try {
-      T.resize((size_t)n * n * es);
-    } catch (const std::bad_alloc &) {
-      slq_operator_destroy(op);
-      return fail(SLQ_ENOMEM, "host allocation failed");
-    }
+    std::vector<char> T((size_t)n * n * es);
     for (int64_t j = 0; j < n; ++j)
       for (int64_t i = 0; i < n; ++i)
         memcpy(T.data() + ((size_t)j * n + i) * es, (const char *)A + ((size_t)i * lda + j) * es, es);  // T(i,j) = A(j,i)
@@ -2071,12 +1262,13 @@ extern "C" int slq_dense_create(slq_context *ctx, int dtype, int64_t n, const vo
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    slq_operator_destroy(op);
-    return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "dense upload: %s", hipGetErrorString(e));
-  }
-  *out = op;
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "dense upload: %s", hipGetErrorString(e));
+  *out = guard.release();
   return SLQ_OK;
+}
+extern "C" int slq_dense_create(slq_context *ctx, int dtype, int64_t n, const void *A, int64_t lda,
+                                slq_operator **out) {
+  return create_guarded(out, [&]() { return dense_create_body(ctx, dtype, n, A, lda, out); });
 }
 
 extern "C" int slq_callback_create(slq_context *ctx, int dtype, int64_t n, slq_matvec_fn fn,
@@ -2256,12 +1448,7 @@ static bool ensure_ring_stream(slq_operator *op, int R) {
     if (dev_mode == 2) {  // both, compared
       slq_operator::MergedStream h;
       bool same = build_host(h, hsz);
-      auto eq = [](const void *x, const void *y, size_t bytes) {
-        if (!x || !y) return x == y;
-        std::vector<char> hx(bytes), hy(bytes);
-        return hipMemcpy(hx.data(), x, bytes, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(hy.data(), y, bytes, hipMemcpyDeviceToHost) == hipSuccess &&
-               memcmp(hx.data(), hy.data(), bytes) == 0;
-      };
+      auto eq = device_equals_device;
       for (int q = 0; q < 4 && same; ++q) same = hsz[q] == dsz[q];
       same = same && h.max_lines == m.max_lines && h.max_lines_u == m.max_lines_u && h.u_padded == m.u_padded;
       same = same && eq(h.desc, m.desc, dsz[0]) && eq(h.rec, m.rec, dsz[1]) && eq(h.desc_u, m.desc_u, dsz[2]) && eq(h.rec_u, m.rec_u, dsz[3]);
@@ -3328,6 +2515,26 @@ static seq::SequenceFacts sequence_facts(const slq_plan *p) {
   f.ring_alpha = sw.ring_alpha, f.ring_rev = sw.ring_rev;
   seq::derive_plan_flags(f);
   return f;
+}
+
+// The layout a CSR operator would get (include/slq.h): the decision of csr_create_body - the switches read as a creation reads
+// them, layout_prefilter + decide_layout - without its device half. No HIP call.
+extern "C" int slq_debug_csr_layout(int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colind, int plain, int32_t *perm_out,
+                                    int32_t *tile_row_out, int64_t ntile_cap, int32_t *xcd_tile_out, double *info_out) {
+  if (!perm_out || !tile_row_out || !xcd_tile_out || !info_out) return fail(SLQ_EINVAL, "slq_debug_csr_layout: an output is NULL");
+  return create_guarded(nullptr, [&]() {
+    SLQ_TRY(validate_csr(n, nnz, rowptr, colind));
+    const OperatorSwitches osw = read_operator_switches();
+    const CsrView A{n, nnz, rowptr, colind};
+    const OperatorLayout L = decide_layout(A, osw, layout_prefilter(A, osw, plain != 0), nullptr);
+    const int64_t ntiles = L.have_tiles ? (int64_t)L.tile_row.size() - 1 : 0;
+    if ((int64_t)L.tile_row.size() > ntile_cap) return fail(SLQ_EINVAL, "slq_debug_csr_layout: %zu tile boundaries, room for %lld", L.tile_row.size(), (long long)ntile_cap);
+    std::copy(L.perm.begin(), L.perm.end(), perm_out);
+    std::copy(L.tile_row.begin(), L.tile_row.end(), tile_row_out);
+    std::copy(L.xcd_tile, L.xcd_tile + 9, xcd_tile_out);
+    info_out[0] = L.have_tiles ? 1.0 : 0.0, info_out[1] = (double)ntiles, info_out[2] = L.perm.empty() ? 0.0 : 1.0, info_out[3] = L.rms_dist;
+    return (int)SLQ_OK;
+  });
 }
 
 // step_shape() of slq_sequence.hpp on facts given as an array (the order of seq::facts_from_array), the answer as an array (the

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "slq_format.hpp"  // the stored formats' constants (plain C++: the host analysis of slq_layout.hpp shares them)
+
 namespace slq {
 
 
@@ -116,12 +118,6 @@ struct TileRanges {
 #ifndef SLQ_RING_WAVES
 #define SLQ_RING_WAVES 16
 #endif
-#ifndef SLQ_RING_ROWS
-#define SLQ_RING_ROWS 14
-#endif
-#ifndef SLQ_RING_COLS
-#define SLQ_RING_COLS 36
-#endif
 constexpr int kRingWaves = SLQ_RING_WAVES;  // a consumer's work per row is a chain of LDS latencies: many consumer waves hide it
 constexpr int kRingBlock = kRingWaves * 64;
 constexpr int kRingChunk = SLQ_RING_CHUNK;  // nonzeros of a row gathered per batch (power of two)
@@ -129,23 +125,10 @@ constexpr int kRingLoaders = SLQ_RING_LOADERS;
 constexpr int kRingGroups = SLQ_RING_GROUPS;  // consumer groups taking the tiles in turn: a wave's prefetch runs kRingGroups tiles ahead
 constexpr int kRingSlots = SLQ_RING_SLOTS;
 constexpr int kRingLag = SLQ_RING_LAG;        // a loader's tiles in flight
-constexpr int kRingTileRows = SLQ_RING_ROWS;  // two rows per consumer wave of a group
-constexpr int kRingTileCols = SLQ_RING_COLS;  // distinct panel rows per tile at most
-constexpr int kRingTileNnz = 112;             // nonzeros per tile at most: 128 B of header + 112 x (4 + 8) B fit 1.5 KiB (slq_ring.hpp: R merged tiles per slot)
-constexpr int kRingMetaBytes = 2048;          // 4 slots x (36 + 2) KiB + kRingHeadBytes = 156 KiB
 constexpr int kRingHeadBytes = 4096;          // flag words + the loaders' descriptor staging
 constexpr int kRingSpinMax = 1 << 20;         // ~0.1 s of polling
 constexpr int kRingMaxR = 3;                  // ring columns per step served (more: 128 VGPRs at 16 waves do not hold the sums)
-// descriptor words (tile_desc[t * 64 + ...])
-constexpr int kDescCols = 0, kDescRecOff = 1, kDescRecChunks = 2, kDescRow0 = 3, kDescRows = 4, kDescList = 8;
-// The line list of an R = 1 descriptor is stored de-interleaved (r03): line d at word kDescList + ring1_list_pos(d), i.e. the
-// even lines first, then the odd ones - the lines of each of TWO loader waves are then consecutive words, which a loader
-// fetches with two wide scalar loads instead of eighteen single ones (slq_ring.hpp). Merged tiles (R > 1) keep line d at d.
-constexpr int kRing1ListHalf = (kRingTileCols + 1) / 2;
-__host__ __device__ inline int ring1_list_pos(int d) { return (d & 1) * kRing1ListHalf + (d >> 1); }
-// record words: [0 .. rows] row offsets into the record's own nonzeros, [15] byte offset of the values,
-// [16 .. 16 + rows) line of each row's own panel row, then from byte 128 the column lines (int32) and the values (F)
-constexpr int kRecValOff = 15, kRecSelf = 16, kRecHeadBytes = 128;
+// (tile caps, descriptor and record words: slq_format.hpp)
 static_assert((kRingWaves - kRingLoaders) % kRingGroups == 0 && kRingSlots % kRingGroups == 0, "every slot is served by one consumer group");
 static_assert(kRingLag < kRingSlots && kRingLoaders < kRingWaves && kRingLoaders <= 3 && kRingTileRows < kRecValOff && kRecSelf + kRingTileRows <= 32 && kRingTileCols <= 64 - kDescList, "ring geometry");
 static_assert(kRingWaves <= 16 && (size_t)kRingSlots * (kRingTileCols * 1024 + kRingMetaBytes) + kRingHeadBytes <= 160 * 1024, "ring slots must fit the LDS");

@@ -37,7 +37,6 @@ __device__ unsigned long long *g_dbg_times = nullptr;
 // end; they are never dereferenced. The CSR arrays carry kCsrPad spare entries for that
 // (slq.hip: slq_csr_create pads every array it uploads).
 // Summation order is p0, p0+1, ...: bitwise the same as a scalar loop over the row.
-constexpr int kCsrPad = 8;
 // 8 consecutive CSR entries as ONE scalar load each (s_load_dwordx8 / x16 need dword alignment only)
 typedef int32_t csr_i8 __attribute__((ext_vector_type(8), aligned(4)));
 typedef float csr_f8 __attribute__((ext_vector_type(8), aligned(4)));
@@ -544,8 +543,6 @@ __global__ __launch_bounds__(kBlock) void k_csr_pass(
 #ifndef SLQ_TILE_DB
 #define SLQ_TILE_DB 0
 #endif
-constexpr int kTileRows = 24;  // rows per tile at most (3 per wave)
-constexpr int kTileCols = 72;  // distinct panel rows per tile at most: 72 KiB of LDS image
 
 template <typename F, int PASS, int NTP, int RC>
 __global__ __launch_bounds__(kBlock) void k_csr_tile_pass(

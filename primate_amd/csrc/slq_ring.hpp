@@ -34,7 +34,6 @@ namespace slq {
 #define SLQ_RINGN_PRIO 0     // s_setprio of the loader waves (0: none)
 #endif
 constexpr int kRingNLoaders = SLQ_RINGN_LOADERS;
-constexpr int kRingRecStride = 1536;  // bytes of record per base tile: 128 B of header + kRingTileNnz x (4 + 8)
 
 // GEO 0: the tile's lines and record land by LDS-DMA (loader waves issue global_load_lds and count them with vmcnt).
 // GEO 1 ("staged"): the loader waves bring them through their REGISTERS instead (global_load_dwordx4, ds_write_b128) - for the

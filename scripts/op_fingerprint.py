@@ -1,7 +1,8 @@
 """Fingerprint of what an operator's creation decides (order, tiles, streams) through what it produces: sha256 of alpha, beta and the
 quadrature values of one seeded 256 x 30 run per operator. Two libraries that print the same lines build the same operators
 (r04: used to show that the device-side build, the stamp-based regrouping and the cached first-level Cuthill-McKee leave every result
-bitwise unchanged).   PRIMATE_AMD_LIBSLQ=<other library> python scripts/op_fingerprint.py"""
+bitwise unchanged; later: that slq_layout.hpp does - the cases then cover the host builder, barrier tiles, a forced reorder without tiles, a
+random graph, creation from device arrays, an affine and a Gram operator).   PRIMATE_AMD_LIBSLQ=<other library> python scripts/op_fingerprint.py"""
 import hashlib, sys, time
 from pathlib import Path
 import numpy as np
@@ -10,15 +11,59 @@ sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))
 from conftest import laplacian_2d, laplacian_3d
 from primate_amd import engine as eng
 
-cases = [("lap2d_1000", laplacian_2d(1000), 256, 3), ("lap2d_1000", laplacian_2d(1000), 64, 3), ("lap3d_100", laplacian_3d(100), 256, 3), ("lap3d_100", laplacian_3d(100), 64, 6),
-         ("lap3d_100", laplacian_3d(100), 32, 0), ("lap3d_80_f32", laplacian_3d(80, np.float32), 256, 3)]
+def random_graph(n=500000, deg=16, seed=1234):  # (the pattern of scripts/time_create.py's random graph plus a dominant diagonal: no tiles, automatic reorder declined)
+	import scipy.sparse as sp
+	rng = np.random.default_rng(seed)
+	m = int(n * deg / 2)
+	i, j = rng.integers(0, n, m), rng.integers(0, n, m)
+	keep = i != j
+	W = sp.coo_matrix((np.ones(keep.sum()), (i[keep], j[keep])), shape=(n, n)).tocsr()
+	W = ((W + W.T) > 0).astype(np.float64).tocsr()
+	W = (W + sp.identity(n) * (deg * 4.0)).tocsr()  # (diagonally dominant: log is defined)
+	W.sort_indices()
+	return W
+
+def on_device(A):  # slq_csr_create_device: the operator from arrays that already live on the GPU
+	import torch
+	return torch.sparse_csr_tensor(torch.from_numpy(A.indptr.astype(np.int64)), torch.from_numpy(A.indices.astype(np.int64)), torch.from_numpy(A.data), size=A.shape).to("cuda")
+
+def affine():
+	from primate_amd.operators import AffineOperator
+	import scipy.sparse as sp
+	A = laplacian_2d(300)
+	return AffineOperator(A, sp.diags(np.linspace(0.5, 1.5, A.shape[0])).tocsr(), t=0.75)
+
+def gram():
+	from primate_amd.operators import GramOperator
+	import scipy.sparse as sp
+	rng = np.random.default_rng(9)
+	m = 650000
+	B = sp.coo_matrix((rng.uniform(0.5, 1.5, m), (rng.integers(0, 120000, m), rng.integers(0, 90000, m))), shape=(120000, 90000)) + sp.eye(120000, 90000) * 3.0
+	return GramOperator(B.tocsr())
+
+# (label, matrix or builder, switches the operator is created under, probes, orth)
+cases = [("lap2d_1000", lambda: laplacian_2d(1000), {}, 256, 3), ("lap2d_1000", None, {}, 64, 3), ("lap3d_100", lambda: laplacian_3d(100), {}, 256, 3), ("lap3d_100", None, {}, 64, 6),
+         ("lap3d_100", None, {}, 32, 0), ("lap3d_80_f32", lambda: laplacian_3d(80, np.float32), {}, 256, 3),
+         ## the creation paths beyond the default one
+         ("lap2d_1000 host build", lambda: laplacian_2d(1000), {"SLQ_DEVICE_BUILD": "0"}, 256, 3), ("lap2d_1000 host build", None, {}, 64, 3),
+         ("lap2d_1000 tiles 1", lambda: laplacian_2d(1000), {"SLQ_TILES": "1"}, 256, 3),
+         ("lap3d_100 reorder 2, no tiles", lambda: laplacian_3d(100), {"SLQ_REORDER": "2", "SLQ_TILES": "0"}, 256, 3),
+         ("random graph n=5e5", random_graph, {}, 64, 3),
+         ("lap3d_100 from device arrays", lambda: on_device(laplacian_3d(100)), {}, 256, 3), ("lap3d_100 from device arrays", None, {}, 64, 6),
+         ("affine lap2d_300 + 0.75 D", affine, {}, 64, 3), ("gram 120000 x 90000", gram, {}, 64, 3)]
+import os
 ops = {}
-for name, A, P, orth in cases:
+for name, make, env, P, orth in cases:
+	env = ops[name][1] if name in ops else env  # (an operator and its plans are created under the same switches)
+	saved = {k: os.environ.get(k) for k in env}
+	os.environ.update(env)
 	if name not in ops:
 		t = time.perf_counter()
-		ops[name] = eng.DeviceOperator(A)
+		ops[name] = (eng.DeviceOperator(make()), env)
 		print(f"{name}: created in {time.perf_counter() - t:.3f} s", flush=True)
-	plan = eng.LanczosPlan(ops[name], P, 30, orth)
+	plan = eng.LanczosPlan(ops[name][0], P, 30, orth)
+	for k, v in saved.items():
+		os.environ.pop(k) if v is None else os.environ.__setitem__(k, v)
 	plan.generate_probes("rademacher", seed=77)
 	plan.run()
 	q = plan.quadrature("log")
