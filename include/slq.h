@@ -169,7 +169,8 @@ int slq_plan_create(slq_context *ctx, slq_operator *op, int nprobes, int deg, in
  * also when only quadratures follow: a plan that never takes an action should be an ordinary one. */
 int slq_plan_create_recompute(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, slq_plan **out);
 /* mode: 0 ring only, 1 kept basis, 2 recompute; ring_slots: slots of the ring itself; acc_cols: ring columns one accumulation
- * launch of a recompute plan consumes (0 for the other kinds). Any output may be NULL. */
+ * launch of a recompute plan or of a Chebyshev action plan (mode 0; slq_plan_create_chebyshev_action) consumes (0 for the
+ * other kinds). Any output may be NULL. */
 int slq_plan_basis_mode(const slq_plan *plan, int *mode, int *ring_slots, int *acc_cols);
 /* Byte accounting of a recompute plan's accumulation launches, which do not read a ring column whose coefficient is zero for
  * every probe of a panel (probes past an early stop): columns read and columns offered, summed over launches and panels since
@@ -375,6 +376,35 @@ int slq_plan_get_moments(slq_plan *plan, double *mu, int *outside);
 int slq_plan_moment_sum(slq_plan *plan, int ncoef, const double *coef, double *quad, double *stage);
 int slq_density_update_moments(slq_density *d, slq_plan *plan, int nweights, const double *damp);
 
+/* ---- The Chebyshev action Y = p(A) X, p(x) = sum_{k <= nsteps} c_k T_k((x - center) / halfwidth) ----------
+ * The same polynomial for every column: exactly linear in X and symmetric, one run, no replay, nsteps up to 16384, and the
+ * moments and `outside` flags of that run besides. Y = sum_k c_k w_k is summed while the w_k pass through the ring, by one
+ * accumulation launch per 16 finished columns (slq_plan_basis_mode's acc_cols).
+ * slq_plan_create_chebyshev_action (beside slq_plan_create_chebyshev, which is unchanged: two ring slots, no store in the last
+ *   step): a Chebyshev plan whose ring has min(acc_cols, nsteps + 1) slots (2 at least), with ONE output panel behind it -
+ *   AT MOST acc_cols + 1 = 17 PANELS in all, whatever nsteps is (the recompute plan's contract: ring_slots + 10). The probes
+ *   are ring column 0: no stash. Every step stores its vector. Every Chebyshev entry works on it - slq_plan_run_chebyshev,
+ *   _get_moments, _moment_sum, slq_density_update_moments give the bits a plain plan gives -, so one plan serves the quadratic
+ *   forms and the action; every Lanczos entry returns SLQ_EINVAL as on any Chebyshev plan.
+ * slq_plan_chebyshev_action (beside slq_plan_fun_action): runs the nsteps steps of slq_plan_run_chebyshev with the
+ *   accumulation launches in between (class SLQ_K_COMBINE), then copies the output panel to the column-major n x nprobes Y
+ *   (ldy >= n). coef: ncoef = nsteps + 1 finite doubles, rounded to the plan's dtype once on the device; a column whose
+ *   coefficient is exactly 0.0 is not read (SLQ_ACC_SKIP=0 reads it: the same bits). It consumes the probes and leaves the
+ *   moments and flags as a plain run does. Synchronises.
+ * slq_plan_chebyshev_action_dmat (beside slq_plan_fun_action_dmat): the same into OUT[:, o0 : o0 + nprobes] (fp64 plans).
+ * SLQ_EINVAL, the message naming the cause, and Y / OUT not written: not an action plan (a plain Chebyshev plan, a Lanczos
+ *   plan); probes not ready; ncoef != nsteps + 1; a non-finite coefficient; ldy < n; an `outside` flag up after the run (the
+ *   message of slq_plan_moment_sum, naming the bounds); and probes that the last probe call DREW ON THE DEVICE FROM THE SPHERE
+ *   (slq_plan_generate_probes, SLQ_PDF_SPHERE): their panel holds the normal draw g while the probe is sqrt(n) g / ||g|| - the
+ *   moments carry that ratio, the vectors of the ring do not. Draw them on the host and use slq_plan_set_probes.
+ * slq_plan_action_columns reports these launches too: whole ring columns read against columns offered (nsteps + 1 per
+ *   action), counted once per launch on the host - the mask is the host's and the same for every panel. */
+int slq_plan_create_chebyshev_action(slq_context *ctx, slq_operator *op, int nprobes, int nsteps, slq_plan **out);
+int slq_plan_chebyshev_action(slq_plan *plan, double center, double halfwidth, double outside_tol, int ncoef, const double *coef,
+                              void *Y, int64_t ldy);
+int slq_plan_chebyshev_action_dmat(slq_plan *plan, double center, double halfwidth, double outside_tol, int ncoef, const double *coef,
+                                   slq_dmat *OUT, int o0);
+
 /* Per-kernel device time accumulated by HIP events on the context stream (for bench.py's
  * roofline line). enable != 0 turns event recording on for subsequent slq_plan_run calls. */
 enum {
@@ -386,7 +416,8 @@ enum {
   SLQ_K_PROBES,      /* probe generation / layout                                                   */
   SLQ_K_QUADRATURE,  /* tridiagonal eigensolve + f reduction                                        */
   SLQ_K_COMBINE,     /* f(A)x = sum_t g_t W_t over the kept basis (slq_plan_fun_action; not a recurrence sweep), and the
-                        accumulation launches of a recompute plan's replay (its passes count in their usual classes) */
+                        accumulation launches of a recompute plan's replay and of a Chebyshev action (their passes count in
+                        their usual classes) */
   SLQ_K_COUNT
 };
 typedef struct {
@@ -441,6 +472,10 @@ int slq_debug_step_shape(const int *facts, int nfacts, int j, int prev_xt, int *
  * orth = 0): out receives the 9 values of seq::cheb_shape_to_array - sweeps, tiled, gen, pipe_on, the update pass's xt word,
  * the sweeps' product kernel and its grid, the grid behind the partials, alpha_pass (always 0). No HIP call. */
 int slq_debug_cheb_step_shape(const int *facts, int nfacts, int j, int *out, int nout);
+/* The accumulation launches of an action of nsteps steps (csrc/slq_sequence.hpp: cheb_action_schedule), in launch order: piece
+ * i consumes the ring columns t0[i] .. t0[i] + nc[i] - 1 (t0, nc: the first cap pieces are written; either may be NULL);
+ * *npieces their number, *ring_slots the ring of such a plan, *acc_cols the columns a launch consumes at most. No HIP call. */
+int slq_debug_cheb_action_schedule(int nsteps, int *t0, int *nc, int cap, int *npieces, int *ring_slots, int *acc_cols);
 /* The layout a CSR operator over this pattern would be created with, as the library decides it, without a device
  * (csrc/slq_layout.hpp: layout_prefilter + decide_layout; the operator switches are read from the environment as a creation
  * reads them). plain != 0: the affine operator's kind (caller's order, no tiles). perm_out [n]: stored row i = caller row

@@ -133,6 +133,10 @@ _SIGNATURES = {
 	"slq_plan_get_moments": (C.c_int, [_P, _P, _P]),
 	"slq_plan_moment_sum": (C.c_int, [_P, C.c_int, _P, _P, _P]),
 	"slq_density_update_moments": (C.c_int, [_P, _P, C.c_int, _P]),
+	"slq_plan_create_chebyshev_action": (C.c_int, [_P, _P, C.c_int, C.c_int, _PP]),
+	"slq_plan_chebyshev_action": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, C.c_int, _P, _P, C.c_int64]),
+	"slq_plan_chebyshev_action_dmat": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, C.c_int, _P, _P, C.c_int]),
+	"slq_debug_cheb_action_schedule": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }  # fmt: skip
 DEVICE_MATMAT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p)
 class PlanInfo(C.Structure):

@@ -1,10 +1,13 @@
 """The kernel polynomial method (Weisse, Wellein, Alvermann, Fehske, Rev. Mod. Phys. 78, 2006; Lin, Saad, Yang, SIAM Review 2016):
 traces v^T f(A) v and spectral densities from the Chebyshev moments mu_k = v^T T_k(A~) v, A~ = (A - c) / h, of a batch of
 probes (engine.ChebyshevPlan: one update pass of the orth-0 Lanczos step per two moments, no orthogonality, no eigensolve,
-no cap at 512 steps).
+no cap at 512 steps), and the action f(A) X ~= sum_k c_k T_k(A~) X of the same expansion: one fixed polynomial for every
+column, so `ChebyshevFunction @ X` is exactly linear and symmetric (what hutchpp and xtrace assume), at any degree up to
+16384 and in memory that does not depend on the degree.
 
-What runs where: the moments, their sums against coefficients and the density on a grid are libslq kernels; the Chebyshev
-coefficients of f, the damping factors and the spectral bounds are small host computations.
+What runs where: the recurrence, the moments, their sums against coefficients, the sum of the action and the density on a
+grid are libslq kernels; the Chebyshev coefficients of f, the damping factors and the spectral bounds are small host
+computations.
 """
 
 from __future__ import annotations
@@ -158,15 +161,19 @@ def _steps_of(deg: int) -> int:
 
 
 class ChebyshevFunction(LinearOperator):
-	"""v -> v^T f(A) v by a degree-`deg` Chebyshev expansion of f on `bounds` (the kernel polynomial method): `quad(x)` and
-	`quad_generated(...)` as MatrixFunction has them, so `hutch(ChebyshevFunction(A, "log", deg=80))` estimates a trace with
-	`trace.py` as it is. ceil(deg / 2) steps run; the moments 0 .. deg are summed against the (damped) coefficients of f.
+	"""p(A), the degree-`deg` Chebyshev expansion of f on `bounds`, as a linear operator (the kernel polynomial method).
+	`M @ x` / `M @ X` is sum_k c_k T_k(A~) X: `deg` steps of the recurrence in ONE run, the same polynomial for every column -
+	exactly linear and symmetric, so `hutchpp(M)`, `xtrace(M)` and `diag(M)` work on it as on a matrix -, in device memory that
+	does not depend on deg (the action: deg <= 16384); the columns go in batches of `batch`.
+	`quad(x)` and `quad_generated(...)` as MatrixFunction has them, so `hutch(ChebyshevFunction(A, "log", deg=80))` estimates a
+	trace with `trace.py` as it is: there ceil(deg / 2) steps run and the moments 0 .. deg are summed against the (damped)
+	coefficients of f.
 	fun: a built-in name (kwargs: its parameters) or a callable on arrays. bounds=None: `spectral_bounds(A)`; an `outside`
-	flag then doubles the margin and runs again, BOUNDS_RETRIES times at most. With bounds given, the flag raises ValueError.
-	The action f(A) v itself is not provided (`_matvec` raises)."""
+	flag then doubles the margin and runs again, BOUNDS_RETRIES times at most. With bounds given, the flag raises ValueError."""
 
 	def __init__(self, A, fun: Union[str, Callable, None] = None, deg: int = 40, bounds: Optional[tuple] = None, damping: Optional[str] = "none",
-				 dtype=np.float64, bounds_method: str = "auto", margin: float = 0.01, **kwargs):  # fmt: skip
+				 dtype=np.float64, bounds_method: str = "auto", margin: float = 0.01, batch: int = 128, **kwargs):  # fmt: skip
+		self._batch = _check_count("batch", batch)
 		if not is_linear_op(A):
 			raise ValueError("Invalid operator `A`; must be a square symmetric operator with a product")
 		self._deg = _check_count("deg", deg)
@@ -192,6 +199,7 @@ class ChebyshevFunction(LinearOperator):
 		self.bounds = self._given
 		self._coef = None
 		self._plans: dict = {}
+		self._action_plans: dict = {}
 
 	@property
 	def degree(self) -> int:
@@ -201,7 +209,51 @@ class ChebyshevFunction(LinearOperator):
 		return self
 
 	def _matvec(self, x):
-		raise NotImplementedError("ChebyshevFunction evaluates quadratic forms v^T f(A) v; f(A) v by Chebyshev expansion is not provided")
+		x = np.asarray(x)
+		return self._matmat(x.reshape(-1, 1)).reshape(x.shape)
+
+	def _matmat(self, X):
+		"""p(A) X in batches of `batch` columns, every batch one run of deg steps (engine.ChebyshevPlan.action)."""
+		X = np.asarray(X)
+		if X.ndim != 2 or X.shape[0] != self.shape[1]:
+			raise ValueError(f"dimension mismatch: {X.shape} against {self.shape}")
+		Xd = X.astype(self.dtype, copy=False)
+		Y = np.empty((self.shape[0], X.shape[1]), dtype=self.dtype, order="F")
+		for c0 in range(0, X.shape[1], self._batch):
+			Y[:, c0 : c0 + self._batch] = self._action(Xd[:, c0 : c0 + self._batch])
+		return Y
+
+	def _action_plan(self, nprobes: int) -> engine.ChebyshevPlan:
+		if self._deg > 16384:
+			raise ValueError(f"deg = {self._deg}: the action runs deg steps, at most 16384 (quad runs ceil(deg / 2))")
+		if nprobes not in self._action_plans:
+			for k in list(self._action_plans):  # (one cached action plan beside the cached quad plan)
+				self._action_plans.pop(k).close()
+			self._action_plans[nprobes] = engine.ChebyshevPlan(self._op, nprobes, self._deg, action=True)
+		return self._action_plans[nprobes]
+
+	def _action(self, X: np.ndarray) -> np.ndarray:
+		"""The bounds logic of `_quad` around one action run."""
+		plan = self._action_plan(X.shape[1])
+		if self._coef is None:
+			self._set_bounds()
+		for attempt in range(BOUNDS_RETRIES + 1):
+			plan.set_probes(X)
+			try:
+				return plan.action(self.bounds, self._coef)
+			except ValueError:
+				if plan.bounds != self.bounds:  # (refused before the run)
+					raise
+				_, flags = plan.moments(return_outside=True)
+				if not flags.any():
+					raise
+				if self._given is not None:
+					raise ValueError(f"the spectrum of A is not inside bounds = {self.bounds}: {int(flags.sum())} of {X.shape[1]} columns saw a moment above mu_0") from None
+				if attempt == BOUNDS_RETRIES:
+					raise ValueError(f"the spectrum of A is not inside the automatic bounds {self.bounds} after {BOUNDS_RETRIES} widenings: give bounds=") from None
+				self._extra = max(2.0 * self._extra, 2.0 * self._margin)
+				self._set_bounds()
+		raise AssertionError("unreachable")
 
 	def _set_bounds(self):
 		if self._given is None:
@@ -251,6 +303,8 @@ class ChebyshevFunction(LinearOperator):
 	def close(self):
 		for k in list(self._plans):
 			self._plans.pop(k).close()
+		for k in list(self._action_plans):
+			self._action_plans.pop(k).close()
 
 
 def _probe_stream(pdf: str, seed, n: int, dtype):

@@ -263,6 +263,10 @@ struct slq_plan {
   double *cheb_mu = nullptr;       // [2 deg + 1][bpad] moments
   int *cheb_out = nullptr;         // [bpad] outside flags
   double *cheb_coef = nullptr;     // [2 deg + 1] coefficients of slq_plan_moment_sum / damping factors of a density update | stage[4]
+  // action plan (slq_plan_create_chebyshev_action): a ring of cheb_action_ring_slots slots, the output panel
+  // y_slot behind it, every step stores (the fact last_store = 1), acc_cols = kChebAccCols
+  bool cheb_action = false;
+  uint64_t cheb_cols_read = 0, cheb_cols_offered = 0;  // ring columns its accumulation launches read / were offered (the mask is the host's)
 };
 
 // the entries of a Lanczos run are not for Chebyshev plans, and the other way round
@@ -1751,7 +1755,8 @@ extern "C" int slq_plan_destroy(slq_plan *p) {
 
 static int set_kernel_attributes(slq_plan *p);
 
-static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, int basis_mode, slq_plan **out, bool cheb = false);
+static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, int basis_mode, slq_plan **out, bool cheb = false,
+                            bool cheb_action = false);
 static seq::SequenceFacts sequence_facts(const slq_plan *p);
 
 extern "C" int slq_plan_create(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth,
@@ -1771,7 +1776,7 @@ extern "C" int slq_plan_basis_mode(const slq_plan *p, int *mode, int *ring_slots
   return SLQ_OK;
 }
 
-static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, int basis_mode, slq_plan **out, bool cheb) {
+static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, int basis_mode, slq_plan **out, bool cheb, bool cheb_action) {
   const int keep_basis = basis_mode == 1;
   if (!ctx || !op || !out) return fail(SLQ_EINVAL, "ctx/op/out is NULL");
   *out = nullptr;
@@ -1785,6 +1790,7 @@ static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int
   slq_plan *p = new (std::nothrow) slq_plan();
   if (!p) return fail(SLQ_ENOMEM, "host allocation failed");
   p->cheb = cheb;
+  p->cheb_action = cheb && cheb_action;
   const int hist = cheb ? 0 : deg;  // rows of alpha / nu beyond row 0, columns of the stored Gauss rule
   p->ctx = ctx;
   ctx_retain(ctx);
@@ -1805,6 +1811,11 @@ static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int
   p->v_slot = basis_mode == 2 ? p->S : 0;
   p->y_slot = basis_mode == 2 ? p->S + 1 : deg;
   p->acc_skip = p->sw.acc_skip != 0;
+  if (p->cheb_action) {
+    p->S = seq::cheb_action_ring_slots(deg, kChebAccCols);
+    p->acc_cols = kChebAccCols;
+    p->y_slot = p->S;  // (the output panel behind the ring; the probes are ring column 0: no stash)
+  }
   p->slot_stride = (int64_t)p->NP * p->n * p->PW;
   p->rmax = std::max(p->keep_basis ? deg : orth, 1);
   // Row loop of the dots/update passes (slq_kernels.hpp: k_csr_pass). Measured on configs[1] and on the 100^3 grid
@@ -1892,7 +1903,8 @@ static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int
   memset(&p->acc, 0, sizeof(p->acc));
   memset(&p->st, 0, sizeof(p->st));
 
-  const size_t ring_bytes = (size_t)(p->S + (basis_mode == 2 ? 2 : 0)) * (size_t)p->slot_stride * p->esz;  // (recompute: stash and output behind the ring)
+  // (recompute: stash and output behind the ring; Chebyshev action: the output)
+  const size_t ring_bytes = (size_t)(p->S + (basis_mode == 2 ? 2 : (p->cheb_action ? 1 : 0))) * (size_t)p->slot_stride * p->esz;
   const size_t bp = p->bpad;
   const size_t ncoef = basis_mode == 2 ? (size_t)deg * bp : 0;
   // alpha[deg+1], nu[orth margin for stale vectors t < 0 | deg+1], vnorm2, coefA[2], coefB, cross, gram[2][kFusedMaxR+1], gamma[rmax]
@@ -2300,6 +2312,14 @@ extern "C" int slq_plan_window_verify(slq_plan *p, int *mode, double out[5]) {
 extern "C" int slq_plan_action_columns(slq_plan *p, uint64_t *read, uint64_t *offered, int reset) {
   if (!p) return fail(SLQ_EINVAL, "plan is NULL");
   HIP_TRY(hipSetDevice(p->ctx->device));
+  if (p->cheb_action) {
+    // k_cheb_accumulate takes its mask from the host, the same for every panel: whole ring columns, counted once per launch
+    if (read) *read = p->cheb_cols_read;
+    if (offered) *offered = p->cheb_cols_offered;
+    if (reset) p->cheb_cols_read = p->cheb_cols_offered = 0;
+    HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+    return SLQ_OK;
+  }
   unsigned long long h[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(h, p->sweep_cols_d + 2, sizeof(h), hipMemcpyDeviceToHost, p->ctx->stream));
   if (reset) HIP_TRY(hipMemsetAsync(p->sweep_cols_d + 2, 0, sizeof(h), p->ctx->stream));
@@ -2511,7 +2531,8 @@ static seq::SequenceFacts sequence_facts(const slq_plan *p) {
   f.dense_class = dense_kernel_of(p), f.pipelined = p->pipelined, f.omega_on = p->omega_on;
   const PlanSwitches &sw = p->sw;
   f.fused = sw.fused, f.merged = sw.merged, f.mgs = sw.mgs, f.stored_u = sw.stored_u, f.nt = sw.nt, f.cross = sw.cross, f.sw_gram = sw.gram;
-  f.sw_gram_csr = sw.gram_csr, f.sw_ring_gen = sw.ring_gen, f.sw_ring_deep = sw.ring_deep, f.last_store = sw.last_store;
+  f.sw_gram_csr = sw.gram_csr, f.sw_ring_gen = sw.ring_gen, f.sw_ring_deep = sw.ring_deep;
+  f.last_store = (sw.last_store || p->cheb_action) ? 1 : 0;  // (an action reads w_nsteps: the last step stores it)
   f.ring_alpha = sw.ring_alpha, f.ring_rev = sw.ring_rev;
   seq::derive_plan_flags(f);
   return f;
@@ -3131,14 +3152,40 @@ extern "C" int slq_debug_cheb_step_shape(const int *facts, int nfacts, int j, in
   return SLQ_OK;
 }
 
+extern "C" int slq_debug_cheb_action_schedule(int nsteps, int *t0, int *nc, int cap, int *npieces, int *ring_slots_out, int *acc_cols) {
+  if (nsteps < 1 || nsteps > kMaxChebSteps || cap < 0 || !npieces)
+    return fail(SLQ_EINVAL, "slq_debug_cheb_action_schedule: nsteps = %d must lie in [1, %d], cap >= 0, npieces not NULL", nsteps, kMaxChebSteps);
+  *npieces = seq::cheb_action_schedule(nsteps, kChebAccCols, t0, nc, nullptr, cap);
+  if (ring_slots_out) *ring_slots_out = seq::cheb_action_ring_slots(nsteps, kChebAccCols);
+  if (acc_cols) *acc_cols = kChebAccCols;
+  return SLQ_OK;
+}
+
+// One accumulation launch of an action: columns t0 .. t0 + nc - 1 of the ring into the output panel, the coefficients in
+// cheb_coef (device), the live-column mask from their host copy.
+static int launch_cheb_accumulate(slq_plan *p, int t0, int nc, const double *coef_h) {
+  hipStream_t st = p->ctx->stream;
+  const dim3 gS(p->nblkS, p->NP);
+  unsigned live = 0;
+  for (int i = 0; i < nc; ++i)
+    if (!p->acc_skip || coef_h[t0 + i] != 0.0) live |= 1u << i;
+  p->cheb_cols_read += (uint64_t)__builtin_popcount(live);
+  p->cheb_cols_offered += (uint64_t)nc;
+  PROFILED(p, SLQ_K_COMBINE,
+           DISPATCH(p->dtype, p->LPR,
+                    (k_cheb_accumulate<F, L><<<gS, dim3(kBlock), 0, st>>>(p->n, (const F *)p->ring, p->slot_stride, p->S, t0, nc, live,
+                                                                        (const double *)p->cheb_coef, (F *)slot_ptr(p, p->y_slot), t0 == 0 ? 1 : 0))));
+  return SLQ_OK;
+}
+
 // Step j is the update pass cheb_step_shape names (or the product kernel and k_cheb_axpy where the plan takes sweeps) and one
 // k_fin_cheb: a strict subset of the orth-0 Lanczos step's launches. Enqueued directly on the context stream.
-extern "C" int slq_plan_run_chebyshev(slq_plan *p, double center, double halfwidth, double outside_tol) {
-  if (!p) return fail(SLQ_EINVAL, "plan is NULL");
-  SLQ_TRY(need_chebyshev(p, "slq_plan_run_chebyshev"));
-  if (!p->probes_ready) return fail(SLQ_EINVAL, "slq_plan_run_chebyshev: set or generate probes first");
+// action_coef: null, or the host copy of the nsteps + 1 coefficients of an action (already in cheb_coef): the accumulation
+// launches of seq::cheb_action_piece_after go between the steps.
+static int cheb_run(slq_plan *p, const char *who, double center, double halfwidth, double outside_tol, const double *action_coef) {
+  if (!p->probes_ready) return fail(SLQ_EINVAL, "%s: set or generate probes first", who);
   if (!std::isfinite(center) || !std::isfinite(halfwidth) || !(halfwidth > 0.0))
-    return fail(SLQ_EINVAL, "slq_plan_run_chebyshev: center = %g, halfwidth = %g (finite, halfwidth > 0)", center, halfwidth);
+    return fail(SLQ_EINVAL, "%s: center = %g, halfwidth = %g (finite, halfwidth > 0)", who, center, halfwidth);
   HIP_TRY(hipSetDevice(p->ctx->device));
   hipStream_t st = p->ctx->stream;
   const int bp = p->bpad, S = p->S;
@@ -3153,6 +3200,7 @@ extern "C" int slq_plan_run_chebyshev(slq_plan *p, double center, double halfwid
                     (k_axpy_norm<F, L, 1><<<c.gS, dim3(kBlock), 0, st>>>(p->n, (F *)slot_ptr(p, 0), (const F *)nullptr, (const double *)nullptr, p->part, bp))));
   PROFILED(p, SLQ_K_FINALIZE,
            hipLaunchKernelGGL(k_fin_cheb, c.gF, dim3(kFinThreads), 0, st, p->st, p->part, p->nblkS, -1, p->cheb_mu, p->cheb_out, inv_h, c_over_h, tol, sphere));
+  int c0 = 0;  // the oldest unconsumed column of an action
   for (int j = 0; j < p->deg; ++j) {
     const seq::ChebStepShape s = seq::cheb_step_shape(facts, j);
     seq::StepShape l;  // (what the launchers of the Lanczos step read of a shape)
@@ -3170,6 +3218,11 @@ extern "C" int slq_plan_run_chebyshev(slq_plan *p, double center, double halfwid
     }
     PROFILED(p, SLQ_K_FINALIZE,
              hipLaunchKernelGGL(k_fin_cheb, c.gF, dim3(kFinThreads), 0, st, p->st, p->part, nblk, j, p->cheb_mu, p->cheb_out, inv_h, c_over_h, tol, sphere));
+    if (action_coef) {
+      const int m = seq::cheb_action_piece_after(p->deg, p->acc_cols, j, c0);
+      if (m) SLQ_TRY(launch_cheb_accumulate(p, c0, m, action_coef));
+      c0 += m;
+    }
   }
   HIP_TRY(hipGetLastError());
   p->probes_ready = false;
@@ -3181,6 +3234,12 @@ extern "C" int slq_plan_run_chebyshev(slq_plan *p, double center, double halfwid
     return fail(SLQ_EINVAL, "internal: a pass of the launch sequence had no kernel for this plan's tiles");
   }
   return SLQ_OK;
+}
+
+extern "C" int slq_plan_run_chebyshev(slq_plan *p, double center, double halfwidth, double outside_tol) {
+  if (!p) return fail(SLQ_EINVAL, "plan is NULL");
+  SLQ_TRY(need_chebyshev(p, "slq_plan_run_chebyshev"));
+  return cheb_run(p, "slq_plan_run_chebyshev", center, halfwidth, outside_tol, nullptr);
 }
 
 // the outside flags and the ring bail-out word of the last Chebyshev run (synchronises); *raised = probes whose flag is up
@@ -3199,6 +3258,42 @@ static int cheb_flags(slq_plan *p, std::vector<int> &flags, int *raised) {
 static int cheb_outside_error(const slq_plan *p, const char *who, int raised) {
   return fail(SLQ_EINVAL, "%s: %d of %d probes saw a moment above mu_0: the spectrum is not inside the bounds [%.17g, %.17g] of the run", who, raised,
               p->nprobes, p->cheb_c - p->cheb_h, p->cheb_c + p->cheb_h);
+}
+
+// ---- the Chebyshev action Y = sum_k c_k T_k(A~) X ---------------------------------------------------
+extern "C" int slq_plan_create_chebyshev_action(slq_context *ctx, slq_operator *op, int nprobes, int nsteps, slq_plan **out) {
+  return plan_create_mode(ctx, op, nprobes, nsteps, 0, 0, out, true, true);
+}
+
+// the run with its accumulation launches; on SLQ_OK the output panel y_slot holds the action and no `outside` flag is up
+static int cheb_action_device(slq_plan *p, const char *who, double center, double halfwidth, double outside_tol, int ncoef, const double *coef) {
+  SLQ_TRY(need_chebyshev(p, who));
+  if (!p->cheb_action) return fail(SLQ_EINVAL, "%s: not an action plan (slq_plan_create_chebyshev_action)", who);
+  if (!p->probes_ready) return fail(SLQ_EINVAL, "%s: set or generate probes first", who);
+  if (ncoef != p->deg + 1) return fail(SLQ_EINVAL, "%s: ncoef = %d, a plan of %d steps takes %d coefficients", who, ncoef, p->deg, p->deg + 1);
+  if (!coef) return fail(SLQ_EINVAL, "%s: coef is NULL", who);
+  for (int k = 0; k < ncoef; ++k)
+    if (!std::isfinite(coef[k])) return fail(SLQ_EINVAL, "%s: coefficient %d is not finite", who, k);
+  // sphere probes drawn on the device are sqrt(n) g / ||g|| while the panel holds g (k_fin_init): the moments carry the ratio,
+  // the vectors of the ring do not
+  if (p->pdf_sphere)
+    return fail(SLQ_EINVAL, "%s: the probes are sphere probes drawn on the device, whose panel holds the normal draw g, not the probe: set them with slq_plan_set_probes", who);
+  HIP_TRY(hipSetDevice(p->ctx->device));
+  HIP_TRY(hipMemcpyAsync(p->cheb_coef, coef, (size_t)ncoef * 8, hipMemcpyHostToDevice, p->ctx->stream));
+  SLQ_TRY(cheb_run(p, who, center, halfwidth, outside_tol, coef));
+  std::vector<int> flags;
+  int raised = 0;
+  SLQ_TRY(cheb_flags(p, flags, &raised));  // (synchronises)
+  if (raised) return cheb_outside_error(p, who, raised);
+  return SLQ_OK;
+}
+
+extern "C" int slq_plan_chebyshev_action(slq_plan *p, double center, double halfwidth, double outside_tol, int ncoef, const double *coef, void *Y,
+                                         int64_t ldy) {
+  if (!p || !Y) return fail(SLQ_EINVAL, "plan/Y is NULL");
+  if (ldy < p->n) return fail(SLQ_EINVAL, "slq_plan_chebyshev_action: ldy < n");
+  SLQ_TRY(cheb_action_device(p, "slq_plan_chebyshev_action", center, halfwidth, outside_tol, ncoef, coef));
+  return panel_to_host(p, p->y_slot, 0, p->nprobes, Y, ldy, nullptr);
 }
 
 extern "C" int slq_plan_get_moments(slq_plan *p, double *mu, int *outside) {
@@ -4091,6 +4186,22 @@ extern "C" int slq_plan_fun_action_dmat(slq_plan *p, int fun_id, const double *f
   SLQ_TRY(dmat_range(OUT, o0, p->nprobes, "slq_plan_fun_action_dmat"));
   if (p->dtype != SLQ_F64 || OUT->n != p->n || OUT->ctx != p->ctx) return fail(SLQ_EINVAL, "plan and matrix do not match (fp64, same n, same context)");
   SLQ_TRY(fun_action_device(p, fun_id, fun_params));
+  hipStream_t st = p->ctx->stream;
+  dim3 g((p->n + 63) / 64, (p->nprobes + 63) / 64);
+  hipLaunchKernelGGL(k_panel_to_cols<double>, g, dim3(256), 0, st, p->n, (const double *)slot_ptr(p, p->y_slot), 0, p->nprobes,
+                     OUT->d + (size_t)o0 * p->n, p->PW, (const double *)nullptr, p->op->perm_d);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  return SLQ_OK;
+}
+
+// the Chebyshev action of an action plan, written to OUT[:, o0 : o0 + nprobes] (fp64 plans)
+extern "C" int slq_plan_chebyshev_action_dmat(slq_plan *p, double center, double halfwidth, double outside_tol, int ncoef, const double *coef,
+                                              slq_dmat *OUT, int o0) {
+  if (!p) return fail(SLQ_EINVAL, "plan is NULL");
+  SLQ_TRY(dmat_range(OUT, o0, p->nprobes, "slq_plan_chebyshev_action_dmat"));
+  if (p->dtype != SLQ_F64 || OUT->n != p->n || OUT->ctx != p->ctx) return fail(SLQ_EINVAL, "plan and matrix do not match (fp64, same n, same context)");
+  SLQ_TRY(cheb_action_device(p, "slq_plan_chebyshev_action_dmat", center, halfwidth, outside_tol, ncoef, coef));
   hipStream_t st = p->ctx->stream;
   dim3 g((p->n + 63) / 64, (p->nprobes + 63) / 64);
   hipLaunchKernelGGL(k_panel_to_cols<double>, g, dim3(256), 0, st, p->n, (const double *)slot_ptr(p, p->y_slot), 0, p->nprobes,

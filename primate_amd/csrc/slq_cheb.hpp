@@ -8,9 +8,12 @@
 // W_p unread; later sc = 2/h, cB = 2c/h, cp = 1), which stores w over W_p and reduces ||w||^2 and w.W_c already
 // (k_csr_pass / k_csr_ring_pass / k_ring_pass with xt bit 0). Plans that take the sweeps run their product kernel and then
 // k_cheb_axpy (k_cheb_3term after an unfused product). No float atomics; every sum in a fixed order.
+// The action Y = sum_k c_k w_k (slq_plan_chebyshev_action) adds k_cheb_accumulate, launched between the steps
+// of the same run while the w_k are still in the ring.
 #pragma once
 
 #include "slq_kernels.hpp"
+#include "slq_action.hpp"   // (acc_fma: k_cheb_accumulate adds its columns as k_action_accumulate does)
 #include "slq_density.hpp"  // (kDensEvalThreads: k_cheb_density_eval fills the scratch k_density_fold folds)
 
 namespace slq {
@@ -150,6 +153,73 @@ __global__ __launch_bounds__(kBlock) void k_cheb_3term(int n, const F *T, const 
   }
   block_reduce_columns<F, LPR>(nacc, red, part + (int64_t)blockIdx.x * bpad + panel * PW);
   block_reduce_columns<F, LPR>(xacc, red, part + ((int64_t)gridDim.x + blockIdx.x) * bpad + panel * PW);
+}
+
+// a wave-uniform value into scalar registers (fp32: the conversion from the double leaves it in a vector register)
+__device__ __forceinline__ float wave_uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ __forceinline__ double wave_uniform(double v) { return lane_bcast(v, 0) /* (no lane is off in the prologue) */; }
+// acc_fma with the coefficient as a SCALAR operand. fp32: left to itself the compiler pairs the four fmas of a column into
+// two v_pk_fma_f32, which want the coefficient duplicated into a VGPR pair per column - 140 VGPRs at 16 columns, one resident
+// workgroup per CU; v_fma_f32 is the instruction __builtin_fmaf compiles to, so the bits are the same.
+__device__ __forceinline__ float acc_fma_scalar(float c, float x, float y) {
+  asm("v_fma_f32 %0, %1, %2, %0" : "+v"(y) : "s"(c), "v"(x));
+  return y;
+}
+__device__ __forceinline__ double acc_fma_scalar(double c, double x, double y) { return acc_fma(c, x, y); }
+
+// Y[row, :] (+)= sum_{i < nc} c_{t0+i} W_{t0+i}[row, :] for nc <= kChebAccCols finished ring columns (w_t in slot t mod S), t
+// ascending, one fma per column: the same bits whatever the grid. k_action_accumulate with ONE polynomial for every probe:
+// coef: the [nsteps + 1] coefficients as doubles, read at wave-uniform indices - scalar loads, scalar registers - and rounded
+//   to F once here; no lane holds a coefficient (k_action_accumulate: 8 x V VGPRs of them), which is what admits 16 columns;
+// live: bit i set iff column t0 + i is read - computed on the host (c_{t0+i} != 0.0, or every bit under SLQ_ACC_SKIP=0): a
+//   column whose bit is off is not read (0 * x adds nothing for finite x: bitwise neutral). Bits i >= nc are never set;
+// init != 0: Y is written, not read (the first launch of a run).
+// Every live column load of a row group is issued before the first fma; one row group per wave and iteration.
+template <typename F, int LPR>
+__global__ __launch_bounds__(kBlock) void k_cheb_accumulate(int n, const F *__restrict__ ring, int64_t slot_stride, int S, int t0, int nc,
+                                                            unsigned live, const double *__restrict__ coef, F *__restrict__ Y, int init) {
+  using VF = typename VecT<F>::type;
+  constexpr int V = Geo<F, LPR>::V, PW = Geo<F, LPR>::PW, RPW = Geo<F, LPR>::RPW;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane / LPR, cl = lane % LPR;
+  // Addresses are a wave-uniform 64-bit base (column, panel, the workgroup's first row: scalar registers) plus ONE small
+  // per-lane byte offset shared by every column - with a 64-bit address per column and lane the compiler keeps 16 of them
+  // in vector registers (fp64, 64 lanes per row: 111 VGPRs against 76).
+  const unsigned lrow = (unsigned)(wave * RPW + g);
+  const unsigned vbyte = (lrow * PW + cl * V) * (unsigned)sizeof(F);  // < kWaves * 64 * V * sizeof(F) = 8 KiB
+  const int64_t pbase = (int64_t)blockIdx.y * n * PW;
+  live &= (1u << nc) - 1u;
+  // (branch-free: a column past nc takes column t0 again and is never live - the prologue stays straight-line code)
+  F c[kChebAccCols];
+  const char *U[kChebAccCols];
+#pragma unroll
+  for (int i = 0; i < kChebAccCols; ++i) {
+    const int t = t0 + (i < nc ? i : 0);
+    c[i] = wave_uniform((F)coef[t]);
+    U[i] = (const char *)(ring + (int64_t)ring_slot(t, S) * slot_stride + pbase);
+  }
+  char *Yp = (char *)(Y + pbase);
+  const int stride = gridDim.x * kWaves * RPW;
+#pragma unroll 1
+  for (int rb = blockIdx.x * kWaves * RPW; rb < n; rb += stride) {  // (the workgroup's first row: wave-uniform)
+    const int64_t ro = (int64_t)rb * PW * (int64_t)sizeof(F);
+    if (rb + (int)lrow < n) {
+      VF y = init ? (VF)(F)0 : stream_load<SLQ_SWEEP_LDW>((const VF *)(Yp + ro + vbyte));
+      // every live column load of the row group is issued before the first use
+      VF x[kChebAccCols];
+#pragma unroll
+      for (int i = 0; i < kChebAccCols; ++i)
+        if ((live >> i) & 1u) x[i] = *(const VF *)(U[i] + ro + vbyte);
+#pragma unroll
+      for (int i = 0; i < kChebAccCols; ++i) {
+        if ((live >> i) & 1u) {
+#pragma unroll
+          for (int v = 0; v < V; ++v) y[v] = acc_fma_scalar(c[i], x[i][v], y[v]);
+        }
+      }
+      stream_store<SLQ_SWEEP_ST>((VF *)(Yp + ro + vbyte), y);
+    }
+  }
 }
 
 // quad[p] = sum_{k < ncoef} coef[k] mu[k][p], k ascending: one lane per probe.

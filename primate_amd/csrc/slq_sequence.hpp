@@ -220,5 +220,39 @@ inline ChebStepShape cheb_step_shape(const SequenceFacts &facts, int j) {
   return s;
 }
 
+// ---- the action of a Chebyshev run (k_cheb_accumulate) ---------------------------------------------
+// Y = sum_{k <= nsteps} c_k w_k is summed while the w_k pass through the ring: w_t lives in slot t mod S, step j reads w_j and
+// w_{j-1} and writes w_{j+1}, a FINISHED vector (unlike the Lanczos residual), and w_0 - the probes - is column 0 of the first
+// piece: no stash panel. An accumulation launch is issued after step j when `acc` columns c0 .. j+1 are unconsumed, or after
+// the last step, and consumes them all. Step j + 1 then writes slot (j + 2) mod S, which must hold a consumed column and neither
+// w_{j+1} nor w_j: before that step at most acc - 1 columns c0 .. j+1 are unconsumed, so S = acc slots suffice (with acc - 1
+// the step that finishes the acc-th unconsumed column would overwrite column c0), and a run of fewer than acc columns keeps
+// them all: S = nsteps + 1. An action plan's steps are cheb_step_shape's with the fact last_store = 1: w_nsteps is read.
+inline int cheb_action_ring_slots(int nsteps, int acc) { return std::max(2, std::min(acc, nsteps + 1)); }
+
+// the piece issued after step j, given that columns c0 .. j+1 are unconsumed: its number of columns, 0 for none
+inline int cheb_action_piece_after(int nsteps, int acc, int j, int c0) {
+  const int unconsumed = j + 2 - c0;
+  return (unconsumed >= acc || j == nsteps - 1) ? unconsumed : 0;
+}
+
+// every piece of a run in launch order: t0[i], nc[i] (the first cap of them; either may be null), after[i] the step it follows.
+// Returns the number of pieces.
+inline int cheb_action_schedule(int nsteps, int acc, int *t0, int *nc, int *after, int cap) {
+  int np = 0, c0 = 0;
+  for (int j = 0; j < nsteps; ++j) {
+    const int m = cheb_action_piece_after(nsteps, acc, j, c0);
+    if (!m) continue;
+    if (np < cap) {
+      if (t0) t0[np] = c0;
+      if (nc) nc[np] = m;
+      if (after) after[np] = j;
+    }
+    ++np;
+    c0 += m;
+  }
+  return np;
+}
+
 }  // namespace seq
 }  // namespace slq

@@ -4,7 +4,8 @@
 (`converge="count"`) runs entirely on the device: f(A)v for a batch of probes from the retained
 Lanczos basis, then the numer/denom/running-mean accumulation (`slq_diag_update`). Everything else
 (plain matrices, adaptive stopping rules, callbacks) follows the reference loop on the host with the
-operator product delegated to `A @ v`.
+operator product delegated to `A @ v`; over a `ChebyshevFunction` with a fixed probe budget the same loop takes its
+products `batch` probes per device run.
 
 `xdiag(A, m)` is the exchangeable estimator, re-derived here as an average of leave-one-out estimates (`_exchangeable_diagonal`) and pinned by the
 reference's own output (tests/golden: `xdiag_m40`).
@@ -80,6 +81,19 @@ def diag(
 
 	numer, denom = np.zeros(N, dtype=f_dtype), np.zeros(N, dtype=f_dtype)
 	result = EstimatorResult(estimator, converge)
+	from .chebyshev import ChebyshevFunction
+
+	if isinstance(A, ChebyshevFunction) and isinstance(converge, CountCriterion) and callback is None:
+		## a fixed budget over a Chebyshev action: `batch` probes per device run (A @ V is one run per A's own batch) instead of
+		## one - the loop's probe stream, drawn one by one, and its per-sample running estimate, folded cumulatively on the host
+		while not converge(estimator):
+			m = min(int(batch), converge.count - len(estimator))
+			V = np.column_stack([pdf_fn(size=N).astype(f_dtype, copy=False).reshape(N, -1) for _ in range(m)])
+			U = np.asarray(A @ V)
+			for i in range(m):
+				numer += U[:, i] * V[:, i]
+				denom += np.square(V[:, i])
+				estimator.update(np.atleast_2d(numer / denom))
 	while not converge(estimator):
 		v = pdf_fn(size=N).astype(f_dtype, copy=False)
 		u = np.asarray(A @ v).ravel()

@@ -516,9 +516,12 @@ class ChebyshevPlan(LanczosPlan):
 	"""Workspace + state of one batched Chebyshev run (the kernel polynomial method; slq_plan_create_chebyshev): `nsteps`
 	steps w_{j+1} = 2 A~ w_j - w_{j-1}, A~ = (A - c) / h, give the moments mu_k = v^T T_k(A~) v for k = 0 .. 2 nsteps per
 	probe. No orthogonality, no eigensolve, no cap at 512 steps (nsteps <= 16384). The probe methods, `describe`,
-	`workspace_bytes`, `profile_*` and `close` are LanczosPlan's; its Lanczos entries raise ValueError on such a plan."""
+	`workspace_bytes`, `profile_*` and `close` are LanczosPlan's; its Lanczos entries raise ValueError on such a plan.
+	action=True (slq_plan_create_chebyshev_action): the plan also evaluates Y = sum_{k <= nsteps} c_k T_k(A~) X - `action`,
+	`action_into` - on a ring of `acc_cols` slots with one output panel behind it, whatever nsteps is; `run`, `moments` and
+	`moment_sum` work on it as on a plain plan and give the same bits."""
 
-	def __init__(self, op: DeviceOperator, nprobes: int, nsteps: int):
+	def __init__(self, op: DeviceOperator, nprobes: int, nsteps: int, action: bool = False):
 		self.op = op
 		self.nprobes = int(nprobes)
 		self.nsteps = int(nsteps)
@@ -526,8 +529,57 @@ class ChebyshevPlan(LanczosPlan):
 		self.deg, self.orth, self.keep_basis, self.basis_kind = self.nsteps, 0, False, None
 		self.bounds = None
 		h = C.c_void_p()
-		check(_capi.lib().slq_plan_create_chebyshev(op.ctx._h, op._h, self.nprobes, self.nsteps, C.byref(h)))
+		self.is_action = bool(action)
+		create = _capi.lib().slq_plan_create_chebyshev_action if self.is_action else _capi.lib().slq_plan_create_chebyshev
+		check(create(op.ctx._h, op._h, self.nprobes, self.nsteps, C.byref(h)))
 		self._h = h
+
+	def describe(self) -> dict:
+		"""LanczosPlan.describe() and `acc_cols`: ring columns one accumulation launch of an action plan consumes (0: a plain plan);
+		`ring_slots` is 2 for a plain plan and min(acc_cols, nsteps + 1) for an action plan."""
+		d = super().describe()
+		d["acc_cols"] = self.basis_info()["acc_cols"]
+		return d
+
+	def _action_args(self, bounds, coef) -> tuple:
+		if not self.is_action:
+			raise ValueError("not an action plan: create it with ChebyshevPlan(op, nprobes, nsteps, action=True)")
+		try:
+			a, b = (float(v) for v in bounds)
+		except (TypeError, ValueError):
+			raise ValueError(f"bounds must be a pair (a, b), got {bounds!r}") from None
+		if not (np.isfinite(a) and np.isfinite(b) and a < b):
+			raise ValueError(f"bounds must be finite with a < b, got {bounds!r}")
+		coef = np.ascontiguousarray(coef, dtype=np.float64).ravel()
+		if coef.size != self.nsteps + 1:
+			raise ValueError(f"{coef.size} coefficients for a plan of {self.nsteps} steps: it takes {self.nsteps + 1} (c_0 .. c_nsteps)")
+		if not np.all(np.isfinite(coef)):
+			raise ValueError("the coefficients must be finite")
+		return a, b, coef
+
+	def _action_rc(self, rc: int, a: float, b: float):
+		if rc == _capi.SLQ_ECALLBACK and getattr(self.op, "error", None) is not None:
+			raise self.op.error
+		if rc == _capi.SLQ_OK or "not inside the bounds" in _capi.lib().slq_last_error().decode(errors="replace"):
+			self.bounds = (a, b)  # (the run took place: the moments and flags are those of these bounds)
+		check(rc)
+
+	def action(self, bounds, coef, outside_tol: float = 0.0) -> np.ndarray:
+		"""Y (n, nprobes), Fortran-ordered: sum_k coef[k] T_k(A~) x_i for the probes set last (slq_plan_chebyshev_action), with
+		coef = c_0 .. c_nsteps - the Chebyshev coefficients of f on `bounds` (chebyshev.chebyshev_coefficients) give f(A) x_i.
+		One run of nsteps steps; the moments and flags of that run are left behind (`moments`, `moment_sum`). ValueError if the
+		bounds miss part of the spectrum (an `outside` flag), and for device-drawn sphere probes."""
+		a, b, coef = self._action_args(bounds, coef)
+		Y = np.zeros((self.op.shape[0], self.nprobes), dtype=self.op.dtype, order="F")
+		rc = _capi.lib().slq_plan_chebyshev_action(self._h, 0.5 * (a + b), 0.5 * (b - a), float(outside_tol), int(coef.size), ptr(coef), ptr(Y), Y.shape[0])
+		self._action_rc(rc, a, b)
+		return Y
+
+	def action_into(self, bounds, coef, out: "DeviceMatrix", o0: int, outside_tol: float = 0.0):
+		"""The same, written straight into columns [o0, o0 + nprobes) of a DeviceMatrix (fp64 plans; slq_plan_chebyshev_action_dmat)."""
+		a, b, coef = self._action_args(bounds, coef)
+		rc = _capi.lib().slq_plan_chebyshev_action_dmat(self._h, 0.5 * (a + b), 0.5 * (b - a), float(outside_tol), int(coef.size), ptr(coef), out._h, int(o0))
+		self._action_rc(rc, a, b)
 
 	def run(self, bounds, outside_tol: float = 0.0):
 		"""Enqueue the nsteps steps for the probes set or generated last. bounds = (a, b) must contain the spectrum:
