@@ -484,6 +484,13 @@ int slq_debug_cheb_action_schedule(int nsteps, int *t0, int *nc, int cap, int *n
  * rms in-chunk |i - j| of the stored nonzeros. No HIP call. */
 int slq_debug_csr_layout(int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colind, int plain, int32_t *perm_out,
                          int32_t *tile_row_out, int64_t ntile_cap, int32_t *xcd_tile_out, double *info_out);
+/* What creating a plan decides (csrc/slq_plan_shape.hpp: plan_shape), without a device: the facts of operator, context and
+ * request as an array in the order of plan_facts_to_array (kNumPlanFacts values), the shape - geometry, grids, tile stream,
+ * sequence flags, the table of the plan's device allocations {id, bytes, zeroed, counted} and the offsets inside its two
+ * carved blocks - in the order of plan_shape_to_array (kNumPlanShape values). The plan switches are read from the environment
+ * as a creation reads them. No HIP call. slq_debug_plan_shape_of returns the facts and the shape a live plan was created from. */
+int slq_debug_plan_shape(const double *facts, int nfacts, double *out, int nout);
+int slq_debug_plan_shape_of(const slq_plan *plan, double *facts_out, int nfacts, double *shape_out, int nout);
 
 /* ---- one-shot entries ---------------------------------------------------------------------------- */
 /* P probes in one call: the batched counterpart of the Python loop at

@@ -128,6 +128,8 @@ _SIGNATURES = {
 	"slq_debug_step_shape": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
 	"slq_debug_cheb_step_shape": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
 	"slq_debug_csr_layout": (C.c_int, [C.c_int64, C.c_int64, _P, _P, C.c_int, _P, _P, C.c_int64, _P, _P]),
+	"slq_debug_plan_shape": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int]),
+	"slq_debug_plan_shape_of": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int]),
 	"slq_plan_create_chebyshev": (C.c_int, [_P, _P, C.c_int, C.c_int, _PP]),
 	"slq_plan_run_chebyshev": (C.c_int, [_P, C.c_double, C.c_double, C.c_double]),
 	"slq_plan_get_moments": (C.c_int, [_P, _P, _P]),

@@ -20,6 +20,7 @@
 #include <system_error>
 #include <thread>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "slq_kernels.hpp"
@@ -32,6 +33,7 @@
 #include "slq_switches.hpp"  // the table of run-time switches, OperatorSwitches, PlanSwitches
 #include "slq_sequence.hpp"  // what a step launches, as a value (step_shape)
 #include "slq_layout.hpp"    // an operator's layout as a value and the host analysis behind it (layout_prefilter, decide_layout)
+#include "slq_plan_shape.hpp"  // what creating a plan decides, as a value (plan_shape)
 #include "slq_cheb.hpp"      // Chebyshev moments: the kernels of slq_plan_run_chebyshev, _moment_sum, slq_density_update_moments
 
 using namespace slq;
@@ -100,7 +102,8 @@ static void ctx_release(slq_context *ctx) {
   if (--ctx->refs == 0 && ctx->dead) ctx_free(ctx);
 }
 
-enum { OP_CSR = 0, OP_DENSE = 1, OP_CALLBACK = 2, OP_DEVICE_CALLBACK = 3, OP_GRAM = 4 };
+// (OP_CSR .. OP_GRAM, the kinds of an operator: slq_plan_shape.hpp)
+static_assert(kF32 == SLQ_F32 && kF64 == SLQ_F64, "slq_plan_shape.hpp: the dtype codes of include/slq.h");
 
 struct slq_operator {
   slq_context *ctx;
@@ -193,7 +196,6 @@ struct slq_plan {
   std::vector<ProfEvent> pool;
   slq_profile acc;
   std::vector<char> hbuf;  // host staging for callback operators
-  size_t bytes;
   int nstale;                 // > 0: the reorthogonalisation also sees nstale preloaded vectors t = -1 .. -nstale
   // the launch sequence of steps [j0, j1) captured once per (j0, j1, rtol, variant); the one-shot run is the entry (0, deg).
   // Everything else the sequence depends on is fixed when the plan is created (PlanSwitches), so variant is what can change
@@ -266,6 +268,11 @@ struct slq_plan {
   // action plan (slq_plan_create_chebyshev_action): a ring of cheb_action_ring_slots slots, the output panel
   // y_slot behind it, every step stores (the fact last_store = 1), acc_cols = kChebAccCols
   bool cheb_action = false;
+  // what the plan was created from and what creation decided (slq_plan_shape.hpp; the fields above that repeat shape values are
+  // what the launchers read), and the device allocations of the shape's workspace table, by region
+  PlanFacts facts;
+  PlanShape shape;
+  void *ws[kNumRegions] = {};
   uint64_t cheb_cols_read = 0, cheb_cols_offered = 0;  // ring columns its accumulation launches read / were offered (the mask is the host's)
 };
 
@@ -1482,17 +1489,6 @@ extern "C" int slq_operator_shape(const slq_operator *op, int64_t *nrows, int64_
 // ---------------------------------------------------------------------------------------------------
 // geometry + dispatch
 // ---------------------------------------------------------------------------------------------------
-static void choose_geometry(const PlanSwitches &sw, int dtype, int nprobes, int *LPR, int *PW, int *NP) {
-  const int V = dtype == SLQ_F64 ? 2 : 4;
-  int lpr = 8;
-  while (lpr < 64 && lpr * V < nprobes) lpr *= 2;
-  const int forced = sw.lpr;
-  if (forced == 8 || forced == 16 || forced == 32 || forced == 64) lpr = forced;
-  *LPR = lpr;
-  *PW = lpr * V;
-  *NP = (nprobes + *PW - 1) / *PW;
-}
-
 template <int L> using LprTag = std::integral_constant<int, L>;
 // calls fn(F{}, LprTag<L>{}) for the runtime (dtype, lanes-per-row) pair
 template <typename Fn> static inline void dispatch(int dtype, int lpr, Fn &&fn) {
@@ -1592,17 +1588,6 @@ static int normalise_params(int64_t n, int *deg, int *orth) {
   return SLQ_OK;
 }
 
-static int ring_slots(int deg, int orth, int keep_basis) {
-  if (keep_basis) return deg + 1;
-  if (orth == 0) return 2;
-  return std::max(orth + 1, 3);
-}
-
-// A recompute plan's ring: the quadrature plan's, widened until an accumulation launch finds acc finished columns beside the one
-// the step wrote (acc + 1 slots), acc = min(kAccCols, deg). At most kAccCols slots more, none when orth >= kAccCols.
-static int recompute_acc_cols(int deg) { return std::min(kAccCols, deg); }
-static int recompute_ring_slots(int deg, int orth) { return std::max(ring_slots(deg, orth, 0), recompute_acc_cols(deg) + 1); }
-
 // ||A||_inf of a CSR operator: the scale of one Lanczos step's rounding (what the edge recurrence adds to its noise radius per
 // step). Taken once per operator, on the device, the first time a plan asks; affine operators change their values.
 namespace slq {
@@ -1639,86 +1624,74 @@ static int operator_norm_inf(slq_operator *op, double *out) {
   return SLQ_OK;
 }
 
-static void grid_sizes(const PlanSwitches &sw, int n, int LPR, int NP, int num_cus, int *nblkA, int *nblkS, int *nblkU, bool pipelined) {
-  const int RPW = 64 / LPR;
-  const int rows_per_block = kWaves * RPW;
-  // Tunables: resident workgroups (kBlock threads) per CU, summed over the panels of a launch.
-  // Defaults from the MI355X sweeps: in-place read-modify-write sweeps peak at
-  // ~2 workgroups per CU (more concurrent writers lose 5-10 %); the SpMM likes 4-8.
-  const int per_cu_a = std::max(1, or_auto(sw.blocks_per_cu_spmm, or_auto(sw.blocks_per_cu, 4)));
-  const int per_cu_s = std::max(1, or_auto(sw.blocks_per_cu_stream, or_auto(sw.blocks_per_cu, 2)));
-  // sweep A: a multiple of 8 blocks (XCD-aware chunking), no more than the rows can feed
-  const int chunk = (n + 7) / 8;
-  int per_xcd = std::min(std::max(8, num_cus * per_cu_a / NP) / 8, (chunk + rows_per_block - 1) / rows_per_block);
-  per_xcd = std::max(per_xcd, 1);
-  *nblkA = 8 * per_xcd;
-  // fused dots/update passes: 2 workgroups resident per CU (LDS padding, enqueue_run) and a grid of 2 per CU
-  // per panel. More rows in flight evict each other's gather halo
-  // (dots pass, r = 3, per 30 launches: 36.3 ms at 2 resident, 41.3 at 3), and a grid that is not a multiple
-  // of what is resident leaves a ragged last round. Panels run one after the other (panel-major dispatch).
-  const int per_cu_u = std::max(1, or_auto(sw.blocks_per_cu_fused, pipelined ? 1 : 2));  // per panel; 1 with the pipelined row loop
-  int per_xcd_u = std::min(std::max(8, num_cus * per_cu_u) / 8, (chunk + rows_per_block - 1) / rows_per_block);
-  *nblkU = 8 * std::max(per_xcd_u, 1);
-  int s = std::min(std::max(1, num_cus * per_cu_s / NP), (n + rows_per_block - 1) / rows_per_block);
-  *nblkS = std::max(s, 1);
+// The facts of a plan of `kind` on `op` (slq_plan_shape.hpp). No device work: the merged streams are reported as they are now
+// (plan_create_mode builds the one its plan wants first).
+static PlanFacts plan_facts_of(const slq_operator *op, int nprobes, int deg, int orth, PlanKind kind) {
+  PlanFacts f;
+  f.kind = op->kind, f.dtype = op->dtype, f.n = op->n, f.nnz = op->nnz, f.nnz_u = op->nnz_u, f.upper = op->rowptr_u != nullptr;
+  f.mrows = op->mrows, f.lda = op->lda;
+  f.has_tiles = op->tiles.tile_ptr != nullptr, f.tiles_ringed = op->tiles_ringed, f.tiles_max_cols = op->tiles.max_cols;
+  f.upper_per_row = op->upper_per_row, f.upper_stream = op->tile_desc_u != nullptr, f.upper_padded = op->tile_u_padded;
+  f.far_per_row = op->far_per_row, f.affine = op->vals_b != nullptr;
+  std::copy(op->tiles.xcd_tile, op->tiles.xcd_tile + 9, f.xcd_tile);
+  std::copy(op->xcd_tile_u, op->xcd_tile_u + 9, f.xcd_tile_u);
+  {
+    std::unique_lock<std::mutex> guard;
+    if (op->merged_lock) guard = std::unique_lock<std::mutex>(*op->merged_lock);  // (another plan's creation may be building one)
+    for (int i = 0; i < 2; ++i) {
+      const slq_operator::MergedStream &m = op->merged[i];
+      f.merged[i].available = m.desc != nullptr, f.merged[i].upper = m.desc_u != nullptr, f.merged[i].u_padded = m.u_padded;
+      std::copy(m.xcd_tile, m.xcd_tile + 9, f.merged[i].xcd_tile);
+    }
+  }
+  f.num_cus = op->ctx->num_cus;
+  f.nprobes = nprobes, f.deg = deg, f.orth = orth, f.plan = kind;
+  return f;
+}
+
+static int check_query(int dtype, int64_t n, int nprobes, size_t *bytes) {
+  if (!bytes) return fail(SLQ_EINVAL, "bytes is NULL");
+  SLQ_TRY(check_dtype(dtype));
+  if (n <= 0 || nprobes <= 0) return fail(SLQ_EINVAL, "n and nprobes must be positive");
+  return SLQ_OK;
+}
+// the ring region of the shape of a plan that exists only as (dtype, n, nprobes, deg, orth, kind): the region depends on nothing else
+static size_t query_ring_bytes(int dtype, int64_t n, int nprobes, int deg, int orth, PlanKind kind) {
+  PlanFacts f;
+  f.dtype = dtype, f.n = n, f.nprobes = nprobes, f.deg = deg, f.orth = orth, f.plan = kind;
+  return plan_shape(f, read_plan_switches()).ws[WS_RING].bytes;
 }
 
 extern "C" int slq_plan_query_bytes(int dtype, int64_t n, int nprobes, int deg, int orth,
                                     int keep_basis, size_t *bytes) {
-  if (!bytes) return fail(SLQ_EINVAL, "bytes is NULL");
-  SLQ_TRY(check_dtype(dtype));
-  if (n <= 0 || nprobes <= 0) return fail(SLQ_EINVAL, "n and nprobes must be positive");
+  SLQ_TRY(check_query(dtype, n, nprobes, bytes));
   SLQ_TRY(normalise_params(n, &deg, &orth));
-  int LPR, PW, NP;
-  choose_geometry(read_plan_switches(), dtype, nprobes, &LPR, &PW, &NP);
-  const size_t S = ring_slots(deg, orth, keep_basis);
-  *bytes = S * (size_t)NP * (size_t)n * PW * esize(dtype);
-  return SLQ_OK;
-}
-
-// What a plan on `op` allocates: the ring (slq_plan_query_bytes) plus the product panels of operators that are not applied
-// row by row inside the passes - T (dense / callback / Gram: one panel; the fp64 dense MFMA kernel with big tiles adds up to
-// 16 split-K slabs) and T2 (Gram: the m-row intermediate). The one-shot entries size their probe chunks from this.
-static int plan_bytes_on(const slq_operator *op, int nprobes, int deg, int orth, int keep_basis, size_t *bytes) {
-  SLQ_TRY(slq_plan_query_bytes(op->dtype, op->n, nprobes, deg, orth, keep_basis, bytes));
-  int LPR, PW, NP;
-  choose_geometry(read_plan_switches(), op->dtype, nprobes, &LPR, &PW, &NP);
-  const size_t panel = (size_t)NP * PW * esize(op->dtype);
-  if (op->kind != OP_CSR) {
-    const bool big_tiles = op->kind == OP_DENSE && (op->dtype == SLQ_F32 || PW >= 32);  // K-split slabs of the MFMA dense kernels (<= 16)
-    *bytes += (size_t)(1 + (big_tiles ? 16 : 0)) * panel * (size_t)op->n;
-  }
-  if (op->kind == OP_GRAM) *bytes += panel * (size_t)op->mrows;
+  *bytes = query_ring_bytes(dtype, n, nprobes, deg, orth, keep_basis ? PlanKind::KeepBasis : PlanKind::Ring);
   return SLQ_OK;
 }
 
 // The footprint of a recompute plan does not depend on deg once deg > kAccCols, so the query answers for any deg >= 1 (a plan
 // itself is still limited to kMaxDeg steps).
 extern "C" int slq_plan_query_bytes_recompute(int dtype, int64_t n, int nprobes, int deg, int orth, size_t *bytes) {
-  if (!bytes) return fail(SLQ_EINVAL, "bytes is NULL");
-  SLQ_TRY(check_dtype(dtype));
-  if (n <= 0 || nprobes <= 0) return fail(SLQ_EINVAL, "n and nprobes must be positive");
+  SLQ_TRY(check_query(dtype, n, nprobes, bytes));
   if (deg < 1) return fail(SLQ_EINVAL, "Number of steps must be positive!");
   if (deg > n) deg = (int)n;
   if (orth < 0 || orth > deg) orth = deg;
-  int LPR, PW, NP;
-  choose_geometry(read_plan_switches(), dtype, nprobes, &LPR, &PW, &NP);
-  const size_t S = (size_t)recompute_ring_slots(deg, orth) + 2;  // + the stash of the probes and the output panel
-  *bytes = S * (size_t)NP * (size_t)n * PW * esize(dtype);
+  *bytes = query_ring_bytes(dtype, n, nprobes, deg, orth, PlanKind::Recompute);  // (with the stash of the probes and the output panel)
   return SLQ_OK;
 }
 
-// plan_bytes_on for a plan kind (basis_mode 0 ring only, 1 kept basis, 2 recompute). The coefficient buffer of a recompute plan
-// (deg * bpad doubles: 1 MB at deg 512, 256 probes) is left out like the other scalar arrays: the callers keep 1 GiB of margin.
+// What a plan of a kind (basis_mode 0 ring only, 1 kept basis, 2 recompute) on `op` allocates, for the one-shot entries, which
+// size their probe chunks from it: plan_estimate_bytes (slq_plan_shape.hpp) - a bound, not the exact footprint.
 static int plan_bytes_on_mode(const slq_operator *op, int nprobes, int deg, int orth, int mode, size_t *bytes) {
-  SLQ_TRY(plan_bytes_on(op, nprobes, deg, orth, mode == 1, bytes));
-  if (mode == 2) {
-    size_t ring0 = 0, ring2 = 0;
-    SLQ_TRY(slq_plan_query_bytes(op->dtype, op->n, nprobes, deg, orth, 0, &ring0));
-    SLQ_TRY(slq_plan_query_bytes_recompute(op->dtype, op->n, nprobes, deg, orth, &ring2));
-    *bytes += ring2 - ring0;
-  }
+  SLQ_TRY(check_query(op->dtype, op->n, nprobes, bytes));
+  SLQ_TRY(normalise_params(op->n, &deg, &orth));
+  const PlanFacts f = plan_facts_of(op, nprobes, deg, orth, mode == 2 ? PlanKind::Recompute : (mode == 1 ? PlanKind::KeepBasis : PlanKind::Ring));
+  *bytes = plan_estimate_bytes(plan_shape(f, read_plan_switches()), f);
   return SLQ_OK;
+}
+static int plan_bytes_on(const slq_operator *op, int nprobes, int deg, int orth, int keep_basis, size_t *bytes) {
+  return plan_bytes_on_mode(op, nprobes, deg, orth, keep_basis ? 1 : 0, bytes);
 }
 
 extern "C" int slq_plan_destroy(slq_plan *p) {
@@ -1729,43 +1702,30 @@ extern "C" int slq_plan_destroy(slq_plan *p) {
   for (auto &ev : p->pool) { hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
   for (auto &g : p->graphs) hipGraphExecDestroy(g.exec);
   if (p->replay_exec) hipGraphExecDestroy(p->replay_exec);
-  if (p->acc_coef) hipFree(p->acc_coef);
-  if (p->cheb_mu) hipFree(p->cheb_mu);
-  if (p->cheb_out) hipFree(p->cheb_out);
-  if (p->cheb_coef) hipFree(p->cheb_coef);
+  // what later calls allocated on demand
   if (p->at_d) hipFree(p->at_d);
   if (p->at_flags) hipFree(p->at_flags);
-  if (p->ring) hipFree(p->ring);
-  if (p->T) hipFree(p->T);
-  if (p->T2) hipFree(p->T2);
   if (p->stage) hipFree(p->stage);
-  if (p->scal) hipFree(p->scal);
-  if (p->part) hipFree(p->part);
-  if (p->sweep_cols_d) hipFree(p->sweep_cols_d);
-  if (p->om_buf) hipFree(p->om_buf);
-  if (p->om_flags) hipFree(p->om_flags);
-  if (p->om_cnt) hipFree(p->om_cnt);
-  if (p->om_census) hipFree(p->om_census);
-  if (p->quad_d) hipFree(p->quad_d);
-  if (p->st.active) hipFree(p->st.active);
+  // the workspace table (plan_materialise)
+  for (void *q : p->ws)
+    if (q) hipFree(q);
   ctx_release(p->ctx);
   delete p;
   return SLQ_OK;
 }
 
 static int set_kernel_attributes(slq_plan *p);
-
-static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, int basis_mode, slq_plan **out, bool cheb = false,
-                            bool cheb_action = false);
 static seq::SequenceFacts sequence_facts(const slq_plan *p);
+
+static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, PlanKind kind, slq_plan **out);
 
 extern "C" int slq_plan_create(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth,
                                int keep_basis, slq_plan **out) {
-  return plan_create_mode(ctx, op, nprobes, deg, orth, keep_basis != 0 ? 1 : 0, out);
+  return plan_create_mode(ctx, op, nprobes, deg, orth, keep_basis != 0 ? PlanKind::KeepBasis : PlanKind::Ring, out);
 }
 
 extern "C" int slq_plan_create_recompute(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, slq_plan **out) {
-  return plan_create_mode(ctx, op, nprobes, deg, orth, 2, out);
+  return plan_create_mode(ctx, op, nprobes, deg, orth, PlanKind::Recompute, out);
 }
 
 extern "C" int slq_plan_basis_mode(const slq_plan *p, int *mode, int *ring_slots_out, int *acc_cols) {
@@ -1776,392 +1736,187 @@ extern "C" int slq_plan_basis_mode(const slq_plan *p, int *mode, int *ring_slots
   return SLQ_OK;
 }
 
-static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, int basis_mode, slq_plan **out, bool cheb, bool cheb_action) {
-  const int keep_basis = basis_mode == 1;
+// the plan's fields that repeat its shape (what the launchers read), and the tile stream the shape chose as pointers
+static void plan_adopt_shape(slq_plan *p) {
+  const PlanFacts &f = p->facts;
+  const PlanShape &sh = p->shape;
+  const slq_operator *op = p->op;
+  p->cheb = is_cheb(f.plan);
+  p->cheb_action = f.plan == PlanKind::ChebyshevAction;
+  p->basis_mode = basis_mode_of(f.plan);
+  p->keep_basis = f.plan == PlanKind::KeepBasis;
+  p->dtype = op->dtype, p->n = (int)op->n, p->nprobes = f.nprobes, p->deg = f.deg, p->orth = f.orth;
+  p->esz = esize(op->dtype);
+  p->LPR = sh.LPR, p->PW = sh.PW, p->NP = sh.NP, p->bpad = sh.bpad, p->S = sh.S;
+  p->acc_cols = sh.acc_cols, p->v_slot = sh.v_slot, p->y_slot = sh.y_slot;
+  p->slot_stride = sh.slot_stride, p->rmax = sh.rmax;
+  p->pipelined = sh.pipelined != 0;
+  p->nblkA = sh.nblkA, p->nblkS = sh.nblkS, p->nblkU = sh.nblkU, p->nblkF = sh.nblkF, p->nblkT = sh.nblkT;
+  p->alpha_pad = sh.alpha_pad, p->part_maxblk = sh.part_maxblk, p->dense_ks = sh.dense_ks;
+  p->ringR = sh.ringR, p->rs_u_padded = sh.rs_u_padded != 0, p->ring_staged = sh.ring_staged != 0;
+  std::copy(sh.rs_xcd, sh.rs_xcd + 9, p->rs_xcd);
+  std::copy(sh.rs_xcd_u, sh.rs_xcd_u + 9, p->rs_xcd_u);
+  p->rs_desc = p->rs_desc_u = nullptr;
+  p->rs_rec = p->rs_rec_u = nullptr;
+  if (sh.stream == STREAM_BASE) {
+    p->rs_desc = op->tile_desc, p->rs_rec = op->tile_rec;
+    if (sh.rs_upper) p->rs_desc_u = op->tile_desc_u, p->rs_rec_u = op->tile_rec_u;
+  } else if (sh.stream != STREAM_NONE) {
+    const slq_operator::MergedStream &m = op->merged[sh.stream - STREAM_MERGED2];
+    p->rs_desc = m.desc, p->rs_rec = m.rec, p->rs_desc_u = m.desc_u, p->rs_rec_u = m.rec_u;
+  }
+  p->ring_gen = sh.seq.ring_gen, p->ring_deep = sh.seq.ring_deep, p->gram = sh.seq.gram, p->gram_csr = sh.seq.gram_csr, p->last_nostore = sh.seq.last_nostore;
+  p->omega_on = sh.omega_on != 0;
+  p->acc_skip = p->sw.acc_skip != 0;
+  p->sweep_skip = p->sw.sweep_skip != 0;
+  p->nstale = 0;
+}
+
+// allocates the shape's workspace table, clears what it marks, sets the kernel attributes and takes the operator's norm. On
+// failure the plan is left for slq_plan_destroy, which frees whatever the table had allocated.
+static int plan_materialise(slq_plan *p) {
+  const PlanShape &sh = p->shape;
+  hipError_t e = hipSuccess;
+  for (const Region &r : sh.ws) {
+    if (e != hipSuccess || !r.bytes) continue;
+    e = hipMalloc(&p->ws[r.id], r.bytes);
+    if (e == hipSuccess && r.zeroed == 1) e = hipMemset(p->ws[r.id], 0, r.bytes);
+  }
+  if (e != hipSuccess)
+    return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "plan workspace (%zu bytes of Lanczos panels): %s", sh.ws[WS_RING].bytes, hipGetErrorString(e));
+  p->ring = p->ws[WS_RING], p->scal = (double *)p->ws[WS_SCAL], p->part = (double *)p->ws[WS_PART], p->acc_coef = (double *)p->ws[WS_ACC_COEF];
+  p->sweep_cols_d = (unsigned long long *)p->ws[WS_SWEEP_COLS];
+  p->om_buf = (double *)p->ws[WS_OM_BUF], p->om_flags = (int *)p->ws[WS_OM_FLAGS], p->om_cnt = (unsigned long long *)p->ws[WS_OM_CNT];
+  p->om_census = (int *)p->ws[WS_OM_CENSUS];
+  p->quad_d = (double *)p->ws[WS_QUAD];
+  p->cheb_mu = (double *)p->ws[WS_CHEB_MU], p->cheb_out = (int *)p->ws[WS_CHEB_OUT], p->cheb_coef = (double *)p->ws[WS_CHEB_COEF];
+  p->T = p->ws[WS_T], p->T2 = p->ws[WS_T2];
+  const ScalOffsets &so = sh.scal;
+  double *const s = p->scal;
+  p->st.alpha = s + so.alpha, p->st.nu = s + so.nu, p->st.vnorm2 = s + so.vnorm2, p->st.coefA = s + so.coefA, p->st.coefB = s + so.coefB;
+  p->st.cross = s + so.cross, p->st.gram = s + so.gram, p->st.gamma = s + so.gamma;
+  p->st.active = (int *)p->ws[WS_ACTIVE];
+  p->st.steps = p->st.active + sh.active.steps;
+  p->fail_d = p->st.active + sh.active.fail;
+  p->ring_fail_d = p->st.active + sh.active.ring_fail;  // raised by k_csr_ring_pass when a bounded spin ran out (never cleared: the plan is dead)
+  if (hipMemset(p->ring_fail_d, 0, 2 * sizeof(int)) != hipSuccess) return fail(SLQ_EHIP, "hipMemset failed");  // (and fail_d[2]: the QL status of a density update)
+  p->st.bpad = p->bpad;
+  p->st.nprobes = p->nprobes;
+  p->st.deg = p->deg;
+  p->nodes_d = p->quad_d + sh.bpad;
+  p->weights_d = p->nodes_d + (size_t)sh.bpad * (size_t)sh.hist;
+  for (const Region &r : sh.ws) {
+    if (r.zeroed != 2 || !r.bytes) continue;
+    const hipError_t ze = hipMemsetAsync(p->ws[r.id], 0, r.bytes, p->ctx->stream);
+    if (ze != hipSuccess) return fail(SLQ_EHIP, "workspace clear: %s", hipGetErrorString(ze));
+  }
+  SLQ_TRY(set_kernel_attributes(p));
+  if (p->omega_on) SLQ_TRY(operator_norm_inf(p->op, &p->om_norm));
+  return SLQ_OK;
+}
+
+static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, PlanKind kind, slq_plan **out) {
   if (!ctx || !op || !out) return fail(SLQ_EINVAL, "ctx/op/out is NULL");
   *out = nullptr;
   if (op->ctx != ctx) return fail(SLQ_EINVAL, "operator belongs to another context");
   if (nprobes <= 0) return fail(SLQ_EINVAL, "nprobes must be positive");
   // a Chebyshev plan: deg steps of the orth-0 geometry, bounded by kMaxChebSteps (neither by n nor by kMaxDeg: nothing is orthogonalised or diagonalised)
-  if (cheb && (deg < 1 || deg > kMaxChebSteps)) return fail(SLQ_EINVAL, "slq_plan_create_chebyshev: nsteps = %d must lie in [1, %d]", deg, kMaxChebSteps);
-  if (!cheb) SLQ_TRY(normalise_params(op->n, &deg, &orth));
+  if (is_cheb(kind) && (deg < 1 || deg > kMaxChebSteps)) return fail(SLQ_EINVAL, "slq_plan_create_chebyshev: nsteps = %d must lie in [1, %d]", deg, kMaxChebSteps);
+  if (!is_cheb(kind)) SLQ_TRY(normalise_params(op->n, &deg, &orth));
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->dead) return fail(SLQ_EINVAL, "the context has been destroyed");
   slq_plan *p = new (std::nothrow) slq_plan();
   if (!p) return fail(SLQ_ENOMEM, "host allocation failed");
-  p->cheb = cheb;
-  p->cheb_action = cheb && cheb_action;
-  const int hist = cheb ? 0 : deg;  // rows of alpha / nu beyond row 0, columns of the stored Gauss rule
   p->ctx = ctx;
   ctx_retain(ctx);
   p->op = op;
-  p->dtype = op->dtype;
-  p->n = (int)op->n;
-  p->nprobes = nprobes;
-  p->deg = deg;
-  p->orth = orth;
-  p->keep_basis = keep_basis != 0;
-  p->esz = esize(op->dtype);
   p->sw = read_plan_switches();  // (the one read of this plan: nothing below, and nothing the plan does later, looks at the environment)
-  choose_geometry(p->sw, op->dtype, nprobes, &p->LPR, &p->PW, &p->NP);
-  p->bpad = p->NP * p->PW;
-  p->basis_mode = basis_mode;
-  p->S = basis_mode == 2 ? recompute_ring_slots(deg, orth) : ring_slots(deg, orth, p->keep_basis);
-  p->acc_cols = basis_mode == 2 ? recompute_acc_cols(deg) : 0;
-  p->v_slot = basis_mode == 2 ? p->S : 0;
-  p->y_slot = basis_mode == 2 ? p->S + 1 : deg;
-  p->acc_skip = p->sw.acc_skip != 0;
-  if (p->cheb_action) {
-    p->S = seq::cheb_action_ring_slots(deg, kChebAccCols);
-    p->acc_cols = kChebAccCols;
-    p->y_slot = p->S;  // (the output panel behind the ring; the probes are ring column 0: no stash)
-  }
-  p->slot_stride = (int64_t)p->NP * p->n * p->PW;
-  p->rmax = std::max(p->keep_basis ? deg : orth, 1);
-  // Row loop of the dots/update passes (slq_kernels.hpp: k_csr_pass). Measured on configs[1] and on the 100^3 grid
-  // (DESIGN.md §5.3): rows of up to 5 nonzeros are fastest with the plain loop at 2 resident workgroups per CU (82.9
-  // against 91.7 ms per step), 7-point rows with the pipelined loop at ONE resident workgroup per CU (93.7 against
-  // 101.0 ms): what bounds both is the traffic a CU's vector-memory pipe has in flight, and the pipelined loop puts
-  // the same bytes in flight with half the waves.
-  p->pipelined = op->kind == OP_CSR && p->LPR == 64 && (p->sw.pipe >= 0 ? p->sw.pipe != 0 : (double)op->nnz / (double)std::max<int64_t>(op->n, 1) > 5.5);
-  grid_sizes(p->sw, p->n, p->LPR, p->NP, ctx->num_cus, &p->nblkA, &p->nblkS, &p->nblkU, p->pipelined);
-  {
-    // Fused alpha pass: one read sweep plus the gathers. Two regimes, told apart by the
-    // gathers per row of the matrix the pass walks (upper triangle when the operator is symmetric):
-    //  * <= 3 (5-point stencil, upper triangle): each wave has too few loads in flight, the pass is bound by
-    //    the rowptr -> colind -> gather latency chain: 4 workgroups per CU in total, panels side by side
-    //    (configs[1]: 0.88 ms at 2 per CU, 0.51 at 4; one panel at a time with 4 resident 0.61);
-    //  * more (full 5-point rows: 0.92 ms at 2 per CU vs 0.96 at 4; 7-point upper triangle: 0.67 vs 0.83;
-    //    random graphs): the waves carry enough loads and extra rows in flight only evict each other's halo
-    //    from the XCD's L2: 2 resident per CU (LDS padding), 2 per CU *per panel*, panel after panel.
-    const double gathers = op->kind != OP_CSR ? 0.0 : (double)(op->rowptr_u ? op->nnz_u : op->nnz) / (double)std::max<int64_t>(op->n, 1);
-    const int local = op->kind == OP_CSR && gathers <= 3.2;
-    const int per_cu_env = p->sw.blocks_per_cu_alpha;  // total over the panels
-    const int rows_per_block = kWaves * (64 / p->LPR);
-    const int chunk = (p->n + 7) / 8;
-    const int per_panel = per_cu_env > 0 ? std::max(8, ctx->num_cus * per_cu_env / p->NP)
-                                         : (local ? std::max(8, ctx->num_cus * 4 / p->NP) : ctx->num_cus * 2);
-    const int per_xcd = std::min(per_panel / 8, (chunk + rows_per_block - 1) / rows_per_block);
-    p->nblkF = 8 * std::max(per_xcd, 1);
-    p->alpha_pad = (size_t)or_auto(p->sw.alpha_lds_pad, (per_cu_env > 0 || local) ? 0 : 65536);
-  }
-  {
-    // which tile stream, if any (plan_tiled): wide panels take the tiles as clustered; panels of 32 / 16 lanes per row the
-    // merged tiles of the narrow-panel ring kernel (built on first use; nontemporal streams only - the one form instantiated)
-    p->ringR = 0;
-    p->rs_desc = p->rs_desc_u = nullptr;
-    p->rs_rec = p->rs_rec_u = nullptr;
-    p->rs_u_padded = false;
-    p->ring_staged = false;
-    for (int x = 0; x < 9; ++x) p->rs_xcd[x] = op->tiles.xcd_tile[x], p->rs_xcd_u[x] = op->xcd_tile_u[x];
-    if (op->kind == OP_CSR && op->tiles.tile_ptr && p->sw.tiles) {
-      if (p->LPR == 64) {
-        p->ringR = 1;
-        if (op->tiles_ringed) {
-          p->rs_desc = op->tile_desc, p->rs_rec = op->tile_rec;
-          if (op->tile_desc_u && op->upper_per_row <= (double)p->sw.ring_alpha_max_x100 / 100.0)  // (default: kTileAlphaColsPerRow)
-            p->rs_desc_u = op->tile_desc_u, p->rs_rec_u = op->tile_rec_u, p->rs_u_padded = op->tile_u_padded;
-        }
-      } else if ((p->LPR == 32 || p->LPR == 16) && op->tiles_ringed && p->sw.nt && p->sw.ring_narrow != 0 &&
-                 ensure_ring_stream(op, 64 / p->LPR)) {
-        const slq_operator::MergedStream &m = op->merged[p->LPR == 32 ? 0 : 1];
-        p->ringR = 64 / p->LPR;
-        p->rs_desc = m.desc, p->rs_rec = m.rec, p->rs_desc_u = m.desc_u, p->rs_rec_u = m.rec_u, p->rs_u_padded = m.u_padded;
-        for (int x = 0; x < 9; ++x) p->rs_xcd[x] = m.xcd_tile[x], p->rs_xcd_u[x] = m.xcd_tile[x];  // (merged streams: one partition for both)
-      }
-      // alpha-only pass: LDS-DMA loaders everywhere since their r03 rewrite (merged tiles: a lane reads its lines' sources straight
-      // out of the staged descriptor - 100^3, 64 probes 0.230 -> 0.187 ms against the register-staged loaders that had been the
-      // faster form there, configs[1] 0.129 -> 0.113). SLQ_RING_STAGED=1 takes the loaders through registers (GEO 1) again.
-      p->ring_staged = p->sw.ring_staged != 0;
-    }
-  }
-  // which form of the ring-fed passes, and which steps take the Gram sequence (derive_plan_flags, slq_sequence.hpp). The Gram sequence
-  // needs an EXACTLY symmetric operator: it rewrites W_t . (A W_j) as (A W_t) . W_j - §4.6 - while the reference's recurrence never looks
-  // at symmetry, lanczos.h:127-136; rowptr_u is the record of that check (r04: r03 took the sequence on any tiled operator).
-  // The Gram sequence on the generic passes (no tiles, or a plan whose panels the tiles do not serve): the dots pass - a third to a half of every
-  // step's bytes - is gone there as well. Not for operators whose gathers are the cost (random graphs keep the stored-u sequence: it gathers once,
-  // the Gram sequence twice) - step_shape decides that per step.
-  {
-    const seq::SequenceFacts f = sequence_facts(p);  // (the derived flags depend on nothing that is set further down)
-    p->ring_gen = f.ring_gen, p->ring_deep = f.ring_deep, p->gram = f.gram, p->gram_csr = f.gram_csr, p->last_nostore = f.last_nostore;
-  }
-  p->sweep_skip = p->sw.sweep_skip != 0;
-  {
-    // tiled passes: as many workgroups resident per CU as their LDS images admit (2 x 72 KiB by default), the same number
-    // per CU and panel in the grid, panel after panel
-    const int img_kib = op->tiles.tile_ptr ? (op->tiles.max_cols + 16) * (SLQ_TILE_DB ? 2 : 1) : 160;
-    const int per_cu_t = op->tiles_ringed ? 1 : std::max(1, or_auto(p->sw.blocks_per_cu_tiled, std::max(1, std::min(4, 160 / std::max(img_kib, 1)))));
-    int per_xcd_t = std::max(1, ctx->num_cus * per_cu_t / 8);
-    per_xcd_t = std::max(1, std::min(per_xcd_t, or_auto(p->sw.tiled_wgs_per_xcd, per_xcd_t)));  // (experiments: fewer CUs sweeping a chunk)
-    if (op->tiles.tile_ptr) {
-      int mn = 1 << 30;
-      for (int x = 0; x < 8; ++x) mn = std::min(mn, std::max(1, p->rs_xcd[x + 1] - p->rs_xcd[x]));
-      per_xcd_t = std::min(per_xcd_t, mn);
-    }
-    p->nblkT = 8 * per_xcd_t;
-  }
-  memset(&p->acc, 0, sizeof(p->acc));
-  memset(&p->st, 0, sizeof(p->st));
-
-  // (recompute: stash and output behind the ring; Chebyshev action: the output)
-  const size_t ring_bytes = (size_t)(p->S + (basis_mode == 2 ? 2 : (p->cheb_action ? 1 : 0))) * (size_t)p->slot_stride * p->esz;
-  const size_t bp = p->bpad;
-  const size_t ncoef = basis_mode == 2 ? (size_t)deg * bp : 0;
-  // alpha[deg+1], nu[orth margin for stale vectors t < 0 | deg+1], vnorm2, coefA[2], coefB, cross, gram[2][kFusedMaxR+1], gamma[rmax]
-  const size_t nscal = ((size_t)(hist + 1) * 2 + (size_t)orth + 1 + 2 + 1 + 1 + 2 * (kFusedMaxR + 1) + (size_t)p->rmax) * bp;
-  p->part_maxblk = std::max(std::max(std::max(std::max(p->nblkA, p->nblkF), p->nblkU), p->nblkS), p->nblkT);
-  const size_t npart = (size_t)kReorthChunk * p->part_maxblk * bp;
-  hipError_t e = hipMalloc(&p->ring, ring_bytes);
-  if (e == hipSuccess) e = hipMalloc((void **)&p->scal, nscal * 8);
-  if (e == hipSuccess) e = hipMalloc((void **)&p->part, npart * 8);
-  if (e == hipSuccess && ncoef) e = hipMalloc((void **)&p->acc_coef, ncoef * 8);
-  if (e == hipSuccess) e = hipMalloc((void **)&p->sweep_cols_d, 4 * sizeof(unsigned long long));  // (words 2, 3: the accumulation launches of a recompute plan, slq_plan_action_columns)
-  if (e == hipSuccess) e = hipMemset(p->sweep_cols_d, 0, 4 * sizeof(unsigned long long));
-  // the edge recurrence: full windows of three columns on the ring-fed Gram sequence (r = 4 .. 8: not offered; the rescue needs the
-  // column that leaves the window still in the ring: orth + 1 slots at least)
-  // (k_fin_gram_rescue's early exit looks at the first and the last panel under a block of 64 columns: panels of 32 columns at least)
-  p->omega_on = p->gram && p->sw.omega != 0 && orth == 3 && p->S >= 4 && op->vals_b == nullptr && p->PW >= 32;
-  const size_t om_flag_words = (size_t)2 * (deg + 1) * p->NP;
-  if (e == hipSuccess && p->omega_on) e = hipMalloc((void **)&p->om_buf, 4 * bp * 8);
-  if (e == hipSuccess && p->omega_on) e = hipMalloc((void **)&p->om_flags, om_flag_words * sizeof(int));
-  if (e == hipSuccess && p->omega_on) e = hipMalloc((void **)&p->om_cnt, 8 * sizeof(unsigned long long));
-  if (e == hipSuccess && p->omega_on) e = hipMemset(p->om_buf, 0, 4 * bp * 8);
-  if (e == hipSuccess && p->omega_on) e = hipMemset(p->om_flags, 0, om_flag_words * sizeof(int));
-  if (e == hipSuccess && p->omega_on) e = hipMemset(p->om_cnt, 0, 8 * sizeof(unsigned long long));
-  const size_t census_words = (size_t)(deg + 1) * (kFusedMaxR + 1) * p->NP;
-  if (e == hipSuccess && p->gram && p->sw.omega == 2 && !cheb) e = hipMalloc((void **)&p->om_census, census_words * sizeof(int));
-  if (e == hipSuccess && p->om_census) e = hipMemset(p->om_census, 0, census_words * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc((void **)&p->st.active, bp * 2 * sizeof(int) + 16);
-  if (e == hipSuccess) e = hipMalloc((void **)&p->quad_d, (bp + 2 * bp * (size_t)hist) * 8);
-  const size_t nmom = cheb ? (size_t)(2 * deg + 1) : 0;  // moments per probe (256 probes, 16384 steps: 67 MB)
-  if (e == hipSuccess && cheb) e = hipMalloc((void **)&p->cheb_mu, nmom * bp * 8);
-  if (e == hipSuccess && cheb) e = hipMalloc((void **)&p->cheb_out, bp * sizeof(int));
-  if (e == hipSuccess && cheb) e = hipMalloc((void **)&p->cheb_coef, (nmom + 4) * 8);
-  if (e == hipSuccess && cheb) e = hipMemset(p->cheb_mu, 0, nmom * bp * 8);
-  if (e == hipSuccess && cheb) e = hipMemset(p->cheb_out, 0, bp * sizeof(int));
-  // dense fp64 operator on the matrix cores with 32-row tiles: n/32 workgroups per panel rarely fill 256 CUs, so K is
-  // also split over dense_ks workgroups whose raw products land in dense_ks slabs behind T. ks minimises the number
-  // of workgroup rounds times the work per workgroup, plus a small cost per slab.
-  p->dense_ks = 0;  // 0: the 16-row kernel with its fused epilogue
-  const bool dense32 = op->kind == OP_DENSE && p->dtype == SLQ_F32 && p->sw.dense_mfma;  // fp32: k_dense_mfma32_lds, 256-row tiles, every panel width
-  if (dense32 || (op->kind == OP_DENSE && p->dtype == SLQ_F64 && p->sw.dense_mfma && p->PW >= 32 && !p->sw.dense_tile16)) {
-    const int rw = dense32 ? kDense32BM : 32 * (kWaves / (p->PW >= 64 ? 2 : 1));
-    const double wgs = (double)((p->n + rw - 1) / rw) * p->NP;
-    double best = 1e30;
-    const int forced = p->sw.dense_ksplit;
-    for (int ks = 1; ks <= 16; ++ks) {
-      const double cost = std::ceil(wgs * ks / ctx->num_cus) / ks + 0.005 * ks;
-      if ((forced > 0 && ks == forced) || (forced <= 0 && cost < best - 1e-12)) { best = cost; p->dense_ks = ks; }
-    }
-  }
-  const size_t t_slabs = op->kind == OP_CSR ? 0 : (size_t)(1 + p->dense_ks);
-  if (e == hipSuccess && t_slabs) e = hipMalloc(&p->T, t_slabs * (size_t)p->slot_stride * p->esz);
-  const size_t t2_bytes = op->kind == OP_GRAM ? (size_t)p->NP * (size_t)op->mrows * p->PW * p->esz : 0;
-  if (e == hipSuccess && t2_bytes) e = hipMalloc(&p->T2, t2_bytes);
-  if (e != hipSuccess) {
+  // the merged tiles of narrow panels are built on first use - device work, so before the facts are taken
+  if (const int R = wants_merged_stream(plan_facts_of(op, nprobes, deg, orth, kind), p->sw)) ensure_ring_stream(op, R);
+  p->facts = plan_facts_of(op, nprobes, deg, orth, kind);
+  p->shape = plan_shape(p->facts, p->sw);
+  plan_adopt_shape(p);
+  const int rc = plan_materialise(p);
+  if (rc != SLQ_OK) {
     slq_plan_destroy(p);
-    return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP,
-                "plan workspace (%zu bytes of Lanczos panels): %s", ring_bytes, hipGetErrorString(e));
-  }
-  p->bytes = ring_bytes + ncoef * 8 + nscal * 8 + npart * 8 + (bp + 2 * bp * hist) * 8 + t_slabs * (size_t)p->slot_stride * p->esz + t2_bytes + nmom * bp * 8;
-  double *s = p->scal;
-  p->st.alpha = s; s += (size_t)(hist + 1) * bp;
-  s += (size_t)orth * bp;  // nu rows for t = -orth .. -1 (zero unless the drop-in entry preloads stale columns)
-  p->st.nu = s; s += (size_t)(hist + 1) * bp;
-  p->st.vnorm2 = s; s += bp;
-  p->st.coefA = s; s += 2 * bp;
-  p->st.coefB = s; s += bp;
-  p->st.cross = s; s += bp;
-  p->st.gram = s; s += (size_t)2 * (kFusedMaxR + 1) * bp;
-  p->st.gamma = s;
-  p->st.steps = p->st.active + bp;
-  p->fail_d = p->st.steps + bp;
-  p->ring_fail_d = p->fail_d + 1;  // raised by k_csr_ring_pass when a bounded spin ran out (never cleared: the plan is dead)
-  if (hipMemset(p->ring_fail_d, 0, 2 * sizeof(int)) != hipSuccess) {  // (and fail_d[2]: the QL status of a density update)
-    slq_plan_destroy(p);
-    return fail(SLQ_EHIP, "hipMemset failed");
-  }
-  p->st.bpad = p->bpad;
-  p->st.nprobes = nprobes;
-  p->st.deg = deg;
-  p->nodes_d = p->quad_d + bp;
-  p->weights_d = p->nodes_d + bp * (size_t)hist;
-  p->nstale = 0;
-  {
-    hipError_t ze = hipMemsetAsync(p->scal, 0, nscal * 8, ctx->stream);
-    if (ze != hipSuccess) {
-      slq_plan_destroy(p);
-      return fail(SLQ_EHIP, "workspace clear: %s", hipGetErrorString(ze));
-    }
-  }
-  {
-    const int rc = set_kernel_attributes(p);
-    if (rc != SLQ_OK) {
-      slq_plan_destroy(p);
-      return rc;
-    }
-  }
-  if (p->omega_on) {
-    const int rc = operator_norm_inf(op, &p->om_norm);
-    if (rc != SLQ_OK) {
-      slq_plan_destroy(p);
-      return rc;
-    }
+    return rc;
   }
   *out = p;
   return SLQ_OK;
 }
 
-// Kernels that may be launched with more than the default 64 KiB of dynamic LDS (gamma staging):
-// raise their limit once, outside any stream capture.
+// plan_shape() of slq_plan_shape.hpp on facts given as an array (the order of plan_facts_to_array), the answer as an array (the
+// order of plan_shape_to_array, workspace table included), under the switches as a creation would read them now: no HIP call, so
+// that a CPU test enumerates the decision
+extern "C" int slq_debug_plan_shape(const double *facts, int nfacts, double *out, int nout) {
+  if (!facts || !out || nfacts != kNumPlanFacts || nout != kNumPlanShape)
+    return fail(SLQ_EINVAL, "slq_debug_plan_shape: %d facts in, %d values out", kNumPlanFacts, kNumPlanShape);
+  const PlanFacts f = plan_facts_from_array(facts);
+  if (f.kind < OP_CSR || f.kind > OP_GRAM || (f.dtype != kF32 && f.dtype != kF64) || (int)f.plan < 0 || (int)f.plan > (int)PlanKind::ChebyshevAction)
+    return fail(SLQ_EINVAL, "slq_debug_plan_shape: operator kind, dtype or plan kind out of range");
+  if (f.n <= 0 || f.nprobes <= 0 || f.deg < 1 || f.orth < 0 || f.num_cus <= 0) return fail(SLQ_EINVAL, "slq_debug_plan_shape: n, nprobes, deg, num_cus must be positive");
+  plan_shape_to_array(plan_shape(f, read_plan_switches()), out);
+  return SLQ_OK;
+}
+// the facts and the shape a live plan was created from, in the same orders
+extern "C" int slq_debug_plan_shape_of(const slq_plan *p, double *facts_out, int nfacts, double *shape_out, int nout) {
+  if (!p || !facts_out || !shape_out || nfacts != kNumPlanFacts || nout != kNumPlanShape)
+    return fail(SLQ_EINVAL, "slq_debug_plan_shape_of: plan, %d facts out, %d values out", kNumPlanFacts, kNumPlanShape);
+  plan_facts_to_array(p->facts, facts_out);
+  plan_shape_to_array(p->shape, shape_out);
+  return SLQ_OK;
+}
+
+// Kernels that may be launched with more than the default 64 KiB of dynamic LDS (gamma staging): raise their limit once,
+// outside any stream capture. Taking a kernel's address instantiates it, so these enumerations are also part of what decides
+// which kernels the library contains: every (pass, load policy, ring columns, pipelined) combination a launcher can name.
+template <int... I, typename Fn> static inline void for_each_int(std::integer_sequence<int, I...>, Fn &&fn) {
+  (fn(std::integral_constant<int, I>{}), ...);
+}
+// fn(kernel) for every k_csr_pass<F, L, PASS, NTP, RC, PIPE> of the library: ALPHA has no ring columns, DOTS / ADOTS / UPDATEG
+// at least one, UPDATEG the nontemporal form only; the pipelined row loop exists for 64 lanes per row, and not for ALPHA
+template <typename F, int L, typename Fn> static inline void for_each_csr_pass(Fn &&fn) {
+  for_each_int(std::integer_sequence<int, PASS_ALPHA, PASS_DOTS, PASS_ADOTS, PASS_UPDATE, PASS_UPDATEG>{}, [&](auto pass) {
+    for_each_int(std::make_integer_sequence<int, 2>{}, [&](auto ntp) {
+      for_each_int(std::make_integer_sequence<int, kFusedMaxR + 1>{}, [&](auto rc) {
+        for_each_int(std::make_integer_sequence<int, 2>{}, [&](auto pipe) {
+          constexpr int P = decltype(pass)::value, NTP = decltype(ntp)::value, RC = decltype(rc)::value, PIPE = decltype(pipe)::value;
+          constexpr bool rc_ok = P == PASS_ALPHA ? RC == 0 : (P == PASS_UPDATE || RC >= 1);
+          if constexpr (rc_ok && (P != PASS_UPDATEG || NTP == 1) && (PIPE == 0 || (L == 64 && P != PASS_ALPHA)))
+            fn((const void *)k_csr_pass<F, L, P, NTP, RC, PIPE>);
+        });
+      });
+    });
+  });
+}
+// ... and for every k_csr_tile_pass (MAXRC = kFusedMaxR) / k_csr_ring_pass (MAXRC = kRingMaxR, and the SPMM pass): ALPHA,
+// UPDATE (and SPMM) without ring columns, ADOTS and UPDATE with 1 .. MAXRC
+template <typename F, bool RING, typename Fn> static inline void for_each_tiled_pass(Fn &&fn) {
+  constexpr int MAXRC = RING ? kRingMaxR : kFusedMaxR;
+  for_each_int(std::integer_sequence<int, PASS_ALPHA, PASS_UPDATE, PASS_SPMM, PASS_ADOTS>{}, [&](auto pass) {
+    for_each_int(std::make_integer_sequence<int, 2>{}, [&](auto ntp) {
+      for_each_int(std::make_integer_sequence<int, MAXRC + 1>{}, [&](auto rc) {
+        constexpr int P = decltype(pass)::value, NTP = decltype(ntp)::value, RC = decltype(rc)::value;
+        constexpr bool rc_ok = P == PASS_UPDATE || (P == PASS_ADOTS ? RC >= 1 : RC == 0);
+        if constexpr (rc_ok && (P != PASS_SPMM || RING)) {
+          if constexpr (RING) fn((const void *)k_csr_ring_pass<F, P, NTP, RC>);
+          else fn((const void *)k_csr_tile_pass<F, P, NTP, RC>);
+        }
+      });
+    });
+  });
+}
 template <typename F, int L> static hipError_t raise_lds_limits() {
-  hipError_t e = hipFuncSetAttribute((const void *)k_reorth_update<F, L>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  // fused passes: LDS padding caps their residency (SLQ_ALPHA_LDS_PAD experiments; dots/update: 2 per CU)
-  std::vector<const void *> fused_fns = {
-      (const void *)k_csr_pass<F, L, PASS_ALPHA, 0, 0, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ALPHA, 1, 0, 0>,
-      (const void *)k_csr_pass<F, L, PASS_DOTS, 0, 1, 0>,
-      (const void *)k_csr_pass<F, L, PASS_DOTS, 1, 1, 0>,
-      (const void *)k_csr_pass<F, L, PASS_DOTS, 0, 2, 0>,
-      (const void *)k_csr_pass<F, L, PASS_DOTS, 1, 2, 0>,
-      (const void *)k_csr_pass<F, L, PASS_DOTS, 0, 3, 0>,
-      (const void *)k_csr_pass<F, L, PASS_DOTS, 1, 3, 0>,
-      (const void *)k_csr_pass<F, L, PASS_DOTS, 0, 4, 0>,
-      (const void *)k_csr_pass<F, L, PASS_DOTS, 1, 4, 0>,
-      (const void *)k_csr_pass<F, L, PASS_DOTS, 0, 5, 0>,
-      (const void *)k_csr_pass<F, L, PASS_DOTS, 1, 5, 0>,
-      (const void *)k_csr_pass<F, L, PASS_DOTS, 0, 6, 0>,
-      (const void *)k_csr_pass<F, L, PASS_DOTS, 1, 6, 0>,
-      (const void *)k_csr_pass<F, L, PASS_DOTS, 0, 7, 0>,
-      (const void *)k_csr_pass<F, L, PASS_DOTS, 1, 7, 0>,
-      (const void *)k_csr_pass<F, L, PASS_DOTS, 0, 8, 0>,
-      (const void *)k_csr_pass<F, L, PASS_DOTS, 1, 8, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ADOTS, 0, 1, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ADOTS, 1, 1, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ADOTS, 0, 2, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ADOTS, 1, 2, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ADOTS, 0, 3, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ADOTS, 1, 3, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ADOTS, 0, 4, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ADOTS, 1, 4, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ADOTS, 0, 5, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ADOTS, 1, 5, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ADOTS, 0, 6, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ADOTS, 1, 6, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ADOTS, 0, 7, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ADOTS, 1, 7, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ADOTS, 0, 8, 0>,
-      (const void *)k_csr_pass<F, L, PASS_ADOTS, 1, 8, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 0, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 0, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 1, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 1, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 2, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 2, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 3, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 3, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 4, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 4, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 5, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 5, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 6, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 6, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 7, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 7, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 8, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 8, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATEG, 1, 1, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATEG, 1, 2, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATEG, 1, 3, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATEG, 1, 4, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATEG, 1, 5, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATEG, 1, 6, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATEG, 1, 7, 0>,
-      (const void *)k_csr_pass<F, L, PASS_UPDATEG, 1, 8, 0>};
-  if constexpr (L == 64) {
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATEG, 1, 1, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATEG, 1, 2, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATEG, 1, 3, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATEG, 1, 4, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATEG, 1, 5, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATEG, 1, 6, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATEG, 1, 7, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATEG, 1, 8, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_DOTS, 0, 1, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_DOTS, 1, 1, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_DOTS, 0, 2, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_DOTS, 1, 2, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_DOTS, 0, 3, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_DOTS, 1, 3, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_DOTS, 0, 4, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_DOTS, 1, 4, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_DOTS, 0, 5, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_DOTS, 1, 5, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_DOTS, 0, 6, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_DOTS, 1, 6, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_DOTS, 0, 7, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_DOTS, 1, 7, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_DOTS, 0, 8, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_DOTS, 1, 8, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_ADOTS, 0, 1, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_ADOTS, 1, 1, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_ADOTS, 0, 2, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_ADOTS, 1, 2, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_ADOTS, 0, 3, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_ADOTS, 1, 3, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_ADOTS, 0, 4, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_ADOTS, 1, 4, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_ADOTS, 0, 5, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_ADOTS, 1, 5, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_ADOTS, 0, 6, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_ADOTS, 1, 6, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_ADOTS, 0, 7, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_ADOTS, 1, 7, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_ADOTS, 0, 8, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_ADOTS, 1, 8, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 0, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 0, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 1, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 1, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 2, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 2, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 3, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 3, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 4, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 4, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 5, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 5, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 6, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 6, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 7, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 7, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 0, 8, 1>);
-    fused_fns.push_back((const void *)k_csr_pass<F, L, PASS_UPDATE, 1, 8, 1>);
-  }
-  for (const void *fn : fused_fns)
+  hipError_t e = hipSuccess;
+  auto raise = [&e](const void *fn) {
     if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  };
+  raise((const void *)k_reorth_update<F, L>);
+  // fused passes: LDS padding caps their residency (SLQ_ALPHA_LDS_PAD experiments; dots/update: 2 per CU)
+  for_each_csr_pass<F, L>(raise);
   if constexpr (L == 64) {
-    std::vector<const void *> tiled_fns = {
-        (const void *)k_csr_tile_pass<F, PASS_ALPHA, 0, 0>, (const void *)k_csr_tile_pass<F, PASS_ALPHA, 1, 0>,
-        (const void *)k_csr_tile_pass<F, PASS_UPDATE, 0, 0>, (const void *)k_csr_tile_pass<F, PASS_UPDATE, 1, 0>,
-#define TILE_RC(R)                                                                                              \
-  (const void *)k_csr_tile_pass<F, PASS_ADOTS, 0, R>, (const void *)k_csr_tile_pass<F, PASS_ADOTS, 1, R>,       \
-      (const void *)k_csr_tile_pass<F, PASS_UPDATE, 0, R>, (const void *)k_csr_tile_pass<F, PASS_UPDATE, 1, R>
-        TILE_RC(1), TILE_RC(2), TILE_RC(3), TILE_RC(4), TILE_RC(5), TILE_RC(6), TILE_RC(7), TILE_RC(8)};
-#undef TILE_RC
-    for (const void *fn : tiled_fns)
-      if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    std::vector<const void *> ring_fns = {
-        (const void *)k_csr_ring_pass<F, PASS_ALPHA, 0, 0>, (const void *)k_csr_ring_pass<F, PASS_ALPHA, 1, 0>,
-        (const void *)k_csr_ring_pass<F, PASS_UPDATE, 0, 0>, (const void *)k_csr_ring_pass<F, PASS_UPDATE, 1, 0>,
-        (const void *)k_csr_ring_pass<F, PASS_SPMM, 0, 0>, (const void *)k_csr_ring_pass<F, PASS_SPMM, 1, 0>,
-#define RING_RC(R)                                                                                              \
-  (const void *)k_csr_ring_pass<F, PASS_ADOTS, 0, R>, (const void *)k_csr_ring_pass<F, PASS_ADOTS, 1, R>,       \
-      (const void *)k_csr_ring_pass<F, PASS_UPDATE, 0, R>, (const void *)k_csr_ring_pass<F, PASS_UPDATE, 1, R>
-        RING_RC(1), RING_RC(2), RING_RC(3)};
-#undef RING_RC
-    for (const void *fn : ring_fns)
-      if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    for_each_tiled_pass<F, false>(raise);
+    for_each_tiled_pass<F, true>(raise);
   }
   return e;
 }
@@ -2331,7 +2086,7 @@ extern "C" int slq_plan_action_columns(slq_plan *p, uint64_t *read, uint64_t *of
 
 extern "C" int slq_plan_workspace_bytes(const slq_plan *plan, size_t *bytes) {
   if (!plan || !bytes) return fail(SLQ_EINVAL, "plan/bytes is NULL");
-  *bytes = plan->bytes;
+  *bytes = plan_workspace_bytes(plan->shape);
   return SLQ_OK;
 }
 
@@ -2498,19 +2253,8 @@ extern "C" int slq_plan_get_probes(slq_plan *p, void *X, int64_t ldx) {
 }
 
 
-// Which kernel computes a plan's dense product (the ids of slq_plan_dense_path): the one decision behind launch_dense_mfma,
-// apply_operator_unfused and the step loop. 0: not a dense operator.
-enum { DENSE_K_NONE = 0, DENSE_K_PANEL = 1, DENSE_K_3TERM = 2, DENSE_K_TILE = 3, DENSE_K_LDS = 4, DENSE_K_LDS32 = 5 };
-static int dense_kernel_of(const slq_plan *p) {
-  const slq_operator *op = p->op;
-  if (op->kind != OP_DENSE) return DENSE_K_NONE;
-  if (!p->sw.dense_mfma || (p->dtype != SLQ_F64 && p->dense_ks <= 0)) return DENSE_K_PANEL;  // the VALU kernel (SLQ_DENSE_MFMA=0)
-  if (p->dense_ks <= 0) return DENSE_K_3TERM;  // 16-column panels, SLQ_DENSE_TILE16=1: the 16-row kernel with its fused epilogue
-  if (p->dtype == SLQ_F32) return DENSE_K_LDS32;
-  // operands staged in LDS once per workgroup: 16-byte aligned row pairs (lda even) and panels of 64+ columns (32-column
-  // panels keep the register form: their 256-row block does not fit static LDS)
-  return p->sw.dense_lds && op->lda % 2 == 0 && p->PW >= 64 ? DENSE_K_LDS : DENSE_K_TILE;
-}
+// Which kernel computes a plan's dense product (DENSE_K_*, the ids of slq_plan_dense_path): decided with the plan's shape
+static int dense_kernel_of(const slq_plan *p) { return p->shape.dense_class; }
 
 // Which kernel computes this plan's dense product, and over how many K slabs (diagnostics, tests): kernel 0 not dense, 1 k_dense_panel,
 // 2 k_dense_mfma_3term, 3 k_dense_mfma_tile, 4 k_dense_mfma_lds, 5 k_dense_mfma32_lds; ksplit = dense_ks (0: no slabs). A pure function of the plan.
@@ -2523,18 +2267,8 @@ extern "C" int slq_plan_dense_path(slq_plan *p, int *kernel, int *ksplit) {
 
 // the facts of a plan and its operator that decide what a step launches (slq_sequence.hpp)
 static seq::SequenceFacts sequence_facts(const slq_plan *p) {
-  const slq_operator *op = p->op;
-  seq::SequenceFacts f;
-  f.csr = op->kind == OP_CSR, f.far_le4 = op->far_per_row <= 4.0, f.tiles_ringed = op->tiles_ringed, f.upper = op->rowptr_u != nullptr;
-  f.ringR = p->ringR, f.rs_desc_u = p->rs_desc_u != nullptr, f.rs_u_padded = p->rs_u_padded;
-  f.deg = p->deg, f.orth = p->orth, f.nstale = p->nstale, f.basis_mode = p->basis_mode;
-  f.dense_class = dense_kernel_of(p), f.pipelined = p->pipelined, f.omega_on = p->omega_on;
-  const PlanSwitches &sw = p->sw;
-  f.fused = sw.fused, f.merged = sw.merged, f.mgs = sw.mgs, f.stored_u = sw.stored_u, f.nt = sw.nt, f.cross = sw.cross, f.sw_gram = sw.gram;
-  f.sw_gram_csr = sw.gram_csr, f.sw_ring_gen = sw.ring_gen, f.sw_ring_deep = sw.ring_deep;
-  f.last_store = (sw.last_store || p->cheb_action) ? 1 : 0;  // (an action reads w_nsteps: the last step stores it)
-  f.ring_alpha = sw.ring_alpha, f.ring_rev = sw.ring_rev;
-  seq::derive_plan_flags(f);
+  seq::SequenceFacts f = p->shape.seq;
+  f.nstale = p->nstale;  // (the one fact that changes under a live plan; the derived flags do not depend on it)
   return f;
 }
 
@@ -2611,7 +2345,7 @@ static int launch_dense_mfma(slq_plan *p, const void *Wc, const void *Wp, void *
     if (nblk_out) *nblk_out = p->nblkS;
     return SLQ_OK;
   }
-  const size_t part_rows = (size_t)kReorthChunk * std::max(std::max(std::max(std::max(p->nblkA, p->nblkF), p->nblkU), p->nblkS), p->nblkT);
+  const size_t part_rows = (size_t)kReorthChunk * p->part_maxblk;
   const int nblk = (p->n + 15) / 16;
   if ((size_t)nblk > part_rows) return fail(SLQ_EINVAL, "dense operator too large for the partials buffer");
   const dim3 g(nblk, p->NP);
@@ -3143,7 +2877,7 @@ static int enqueue_run(slq_plan *p, double rtol, int j0, int j1) {
 
 // ---- Chebyshev moments (kernels in slq_cheb.hpp) ------------------------------------------------------
 extern "C" int slq_plan_create_chebyshev(slq_context *ctx, slq_operator *op, int nprobes, int nsteps, slq_plan **out) {
-  return plan_create_mode(ctx, op, nprobes, nsteps, 0, 0, out, true);
+  return plan_create_mode(ctx, op, nprobes, nsteps, 0, PlanKind::Chebyshev, out);
 }
 
 extern "C" int slq_debug_cheb_step_shape(const int *facts, int nfacts, int j, int *out, int nout) {
@@ -3262,7 +2996,7 @@ static int cheb_outside_error(const slq_plan *p, const char *who, int raised) {
 
 // ---- the Chebyshev action Y = sum_k c_k T_k(A~) X ---------------------------------------------------
 extern "C" int slq_plan_create_chebyshev_action(slq_context *ctx, slq_operator *op, int nprobes, int nsteps, slq_plan **out) {
-  return plan_create_mode(ctx, op, nprobes, nsteps, 0, 0, out, true, true);
+  return plan_create_mode(ctx, op, nprobes, nsteps, 0, PlanKind::ChebyshevAction, out);
 }
 
 // the run with its accumulation launches; on SLQ_OK the output panel y_slot holds the action and no `outside` flag is up
@@ -4574,7 +4308,7 @@ extern "C" int slq_fAv_batch_mode(slq_context *ctx, slq_operator *op, const void
     if (nc != plan_cols) {
       if (p) slq_plan_destroy(p);
       p = nullptr;
-      rc = plan_create_mode(ctx, op, nc, d, o, mode, &p);
+      rc = plan_create_mode(ctx, op, nc, d, o, mode == 2 ? PlanKind::Recompute : PlanKind::KeepBasis, &p);
       plan_cols = nc;
       if (rc != SLQ_OK) break;
     }

@@ -12,7 +12,7 @@
 
 namespace slq {
 
-constexpr int kAccCols = 8;  // ring columns one accumulation launch consumes at most (their coefficients live in registers)
+// (kAccCols - ring columns one accumulation launch consumes at most: slq_format.hpp)
 
 __device__ __forceinline__ double acc_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ __forceinline__ float acc_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }

@@ -54,22 +54,10 @@ template <int POLICY> __device__ __forceinline__ void stream_store(
 #ifndef SLQ_SWEEP_LDW
 #define SLQ_SWEEP_LDW 0  // load flavour of the row that is stored again
 #endif
-constexpr int kBlock = 512;          // threads per workgroup for the sweep kernels (8 waves)
-constexpr int kWaves = kBlock / 64;
-constexpr int kReorthChunk = 16;     // reorth columns whose dot accumulators live in registers
-constexpr int kMaxDeg = 512;
-constexpr int kMaxChebSteps = 16384;  // steps of a Chebyshev plan (2 * steps + 1 moments per probe; slq_cheb.hpp)
+// (kBlock, kWaves, kReorthChunk, kMaxDeg, kMaxChebSteps, kChebAccCols, kFusedMaxR: slq_format.hpp - a plan's shape is decided from them without a device)
 // |mu_k| > (1 + tol) mu_0 raises a probe's `outside` flag (k_fin_cheb): the default tol. Inside the bounds |mu_k| <= mu_0 up to
 // rounding; DESIGN.md §4.12 records the largest excess seen per dtype, which this sits 100x above at least.
 constexpr double kChebOutsideTol = 1e-3;
-#ifndef SLQ_CHEB_ACC_COLS
-#define SLQ_CHEB_ACC_COLS 16  // A/B builds (scripts/bench_cheb_action.py); the choice: DESIGN.md §4.13
-#endif
-// Finished ring columns one accumulation launch of a Chebyshev action plan consumes (k_cheb_accumulate; the plan's ring has as
-// many slots): a launch moves (cols + 2) / cols panel passes per column. Bounded by the kernel's loads in flight: 4 VGPRs each.
-constexpr int kChebAccCols = SLQ_CHEB_ACC_COLS;
-static_assert(kChebAccCols >= 8 && kChebAccCols <= 16, "the live-column mask and the resident-workgroup budget of k_cheb_accumulate");
-constexpr int kFusedMaxR = 8;        // fused recompute passes handle up to this many reorth columns
 #ifndef SLQ_UPD_UR
 #define SLQ_UPD_UR 2
 #endif         // upper bound on the Krylov degree (LDS sizing of the QL kernel)

@@ -41,4 +41,24 @@ inline int ring1_list_pos(int d) { return (d & 1) * kRing1ListHalf + (d >> 1); }
 // [16 .. 16 + rows) line of each row's own panel row, then from byte 128 the column lines (int32) and the values (F)
 constexpr int kRecValOff = 15, kRecSelf = 16, kRecHeadBytes = 128;
 
+// ---- the constants a plan's shape is decided from (slq_plan_shape.hpp, which runs without a device), shared with the kernels ----
+constexpr int kBlock = 512;          // threads per workgroup for the sweep kernels (8 waves)
+constexpr int kWaves = kBlock / 64;
+constexpr int kReorthChunk = 16;     // reorth columns whose dot accumulators live in registers
+constexpr int kMaxDeg = 512;
+constexpr int kMaxChebSteps = 16384;  // steps of a Chebyshev plan (2 * steps + 1 moments per probe; slq_cheb.hpp)
+#ifndef SLQ_CHEB_ACC_COLS
+#define SLQ_CHEB_ACC_COLS 16  // A/B builds (scripts/bench_cheb_action.py); the choice: DESIGN.md §4.13
+#endif
+// Finished ring columns one accumulation launch of a Chebyshev action plan consumes (k_cheb_accumulate; the plan's ring has as
+// many slots): a launch moves (cols + 2) / cols panel passes per column. Bounded by the kernel's loads in flight: 4 VGPRs each.
+constexpr int kChebAccCols = SLQ_CHEB_ACC_COLS;
+static_assert(kChebAccCols >= 8 && kChebAccCols <= 16, "the live-column mask and the resident-workgroup budget of k_cheb_accumulate");
+constexpr int kFusedMaxR = 8;        // fused recompute passes handle up to this many reorth columns
+constexpr int kAccCols = 8;  // ring columns one accumulation launch consumes at most (their coefficients live in registers; slq_action.hpp)
+constexpr int kDense32BM = 256, kDense32BN = 64, kDense32BK = 16, kDense32Pad = 32;  // k_dense_mfma32_lds: a workgroup's rows, columns, K stage, LDS row pad
+#ifndef SLQ_TILE_DB
+#define SLQ_TILE_DB 0  // k_csr_tile_pass: two tile images per workgroup
+#endif
+
 }  // namespace slq

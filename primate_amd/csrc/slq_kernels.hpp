@@ -540,9 +540,7 @@ __global__ __launch_bounds__(kBlock) void k_csr_pass(
 // of its column in its tile's list (it replaces colind in the CSR stream); `self_idx` the position of each row itself.
 // One panel row per wave instruction, i.e. LPR = 64 panels only. One workgroup per CU with TWO images (2 x 72 KiB):
 // the next tile is staged while the current one is computed. The arithmetic per row is that of k_csr_pass, products summed in CSR order.
-#ifndef SLQ_TILE_DB
-#define SLQ_TILE_DB 0
-#endif
+// (SLQ_TILE_DB, two images per workgroup: its default is in slq_format.hpp)
 
 template <typename F, int PASS, int NTP, int RC>
 __global__ __launch_bounds__(kBlock) void k_csr_tile_pass(
@@ -1432,7 +1430,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_mfma_lds(int n, const double *
 // order by k_3term_slabs. a_vec = 1 when A's columns are 16-byte aligned (lda % 4 == 0): 16-byte loads; else element loads.
 typedef float f4v_t __attribute__((ext_vector_type(4)));
 typedef float f2v_t __attribute__((ext_vector_type(2)));
-constexpr int kDense32BM = 256, kDense32BN = 64, kDense32BK = 16, kDense32Pad = 32;
+// (kDense32BM = 256, kDense32BN = 64, kDense32BK = 16, kDense32Pad = 32: slq_format.hpp)
 __global__ __launch_bounds__(kBlock) void k_dense_mfma32_lds(int n, const float *__restrict__ A, int64_t lda, int a_vec, const float *__restrict__ X, int ldw,
                                                              int col0, float *__restrict__ raw, int64_t raw_stride) {
   constexpr int BM = kDense32BM, BN = kDense32BN, BK = kDense32BK, LDS_A = BM + kDense32Pad;

@@ -24,7 +24,7 @@ def test_symbols_are_declared_exported_and_bound():
 		assert re.search(rf"\bint {s}\(", hdr), f"{s} is not declared in slq.h"
 		assert s in _capi.EXPORTED_SYMBOLS, f"{s} is not bound in _capi"
 		assert hasattr(L, s), f"{s} is not exported by libslq"
-	m = re.search(r"#define SLQ_CHEB_ACC_COLS (\d+)", (ROOT / "primate_amd" / "csrc" / "slq_common.hpp").read_text())
+	m = re.search(r"#define SLQ_CHEB_ACC_COLS (\d+)", (ROOT / "primate_amd" / "csrc" / "slq_format.hpp").read_text())
 	assert m and 8 <= int(m.group(1)) <= 16
 	from primate_amd import chebyshev, engine
 

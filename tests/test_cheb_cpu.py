@@ -25,7 +25,7 @@ def test_symbols_are_declared_exported_and_bound():
 		assert s in _capi.EXPORTED_SYMBOLS, f"{s} is not bound in _capi"
 		assert hasattr(L, s), f"{s} is not exported by libslq"
 	assert re.search(r"SLQ_DENSITY_CHEBYSHEV\s*=\s*4\b", hdr) and _capi.DENSITY_KINDS["chebyshev"] == 4
-	assert re.search(r"constexpr int kMaxChebSteps = 16384;", (ROOT / "primate_amd" / "csrc" / "slq_common.hpp").read_text())
+	assert re.search(r"constexpr int kMaxChebSteps = 16384;", (ROOT / "primate_amd" / "csrc" / "slq_format.hpp").read_text())
 	from primate_amd import chebyshev, engine
 
 	for name in ("run", "moments", "moment_sum", "describe", "set_probes", "set_probes_device", "generate_probes", "get_probes", "close"):

@@ -42,9 +42,12 @@ def test_dense_path_entry_point_and_its_single_decision():
 	eng = (ROOT / "primate_amd" / "engine.py").read_text()
 	assert 'd["dense_kernel"], d["dense_ksplit"]' in eng
 	src = (ROOT / "primate_amd" / "csrc" / "slq.hip").read_text()
-	## the accessor, launch_dense_mfma, apply_operator_unfused and the step loop all ask dense_kernel_of; nothing else re-derives the choice
-	assert len(re.findall(r"\bdense_kernel_of\(p\)", src)) >= 4
-	assert not re.search(r"\blds_form\b", src) and len(re.findall(r"sw\.dense_lds", src)) == 1 and len(re.findall(r"sw\.dense_tile16", src)) == 1
+	shape = (ROOT / "primate_amd" / "csrc" / "slq_plan_shape.hpp").read_text()
+	## the accessor, launch_dense_mfma and apply_operator_unfused ask dense_kernel_of, which answers with the class plan_shape() decided - the one
+	## the step loop's facts carry; nothing else re-derives the choice
+	assert len(re.findall(r"\bdense_kernel_of\(p\)", src)) >= 3 and "return p->shape.dense_class;" in src and "q.dense_class = s.dense_class" in shape
+	both = src + shape
+	assert not re.search(r"\blds_form\b", both) and len(re.findall(r"sw\.dense_lds", both)) == 1 and len(re.findall(r"sw\.dense_tile16", both)) == 1
 
 
 def test_ring_pass_bail_out_is_reported_not_swallowed():
