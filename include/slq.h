@@ -86,6 +86,7 @@ typedef struct slq_plan slq_plan;         /* workspace + state of one batched La
 typedef struct slq_diag slq_diag;         /* device-resident accumulators of the diagonal estimator */
 typedef struct slq_dmat slq_dmat;         /* column-major n x m fp64 matrix resident on the device  */
 typedef struct slq_density slq_density;   /* device-resident statistics of a spectral density estimate */
+typedef struct slq_sddmm slq_sddmm;       /* device-resident values on a CSR pattern, caller's order */
 
 /* Host-callback operator: y = A x on HOST memory (the fallback for arbitrary Python
  * LinearOperators; mirrors PyLinearOperator::matvec, src/primate/include/pylinop.h:32-40).
@@ -404,6 +405,44 @@ int slq_plan_chebyshev_action(slq_plan *plan, double center, double halfwidth, d
                               void *Y, int64_t ldy);
 int slq_plan_chebyshev_action_dmat(slq_plan *plan, double center, double halfwidth, double outside_tol, int ncoef, const double *coef,
                                    slq_dmat *OUT, int o0);
+
+/* ---- The sampled dense-dense product on a CSR pattern (SDDMM) ----------------------------------------------
+ * For symmetric A, d tr f(A) / dA = f'(A), and its Hutchinson estimate on the stored nonzeros e = (row, col) is
+ *   G[e] = (1/N) sum_i (f'(A) v_i)[row(e)] v_i[col(e)]
+ * - both factors are columns of a slq_dmat already (slq_plan_fun_action_dmat or slq_plan_chebyshev_action_dmat, and
+ * slq_plan_get_probes_dmat). A slq_sddmm holds one double per stored nonzero on the device and folds such products in.
+ * slq_sddmm_create: the pattern is ANY CSR over n rows and n columns, given as host arrays (copied). It is kept in the caller's
+ *   order - never reordered, sorted or deduplicated; a duplicate entry gets its own (equal) value - and it is independent of any
+ *   slq_operator: a dense or plugin operator can have a gradient on a pattern of the user's choice. It is validated on the host:
+ *   rowptr[0] == 0, rowptr non-decreasing, rowptr[n] == nnz, 0 <= colind < n; SLQ_EINVAL names the first offending row. nnz == 0
+ *   is legal (no update launches anything). The values start at 0.
+ * slq_sddmm_create_device: the same from arrays on the context's GPU: they are read back once, validated, and the validated
+ *   copy is what the kernel reads (as slq_csr_create_device reads its index arrays); the caller's arrays are not referenced
+ *   after the call.
+ * slq_sddmm_update: vals[e] = beta * vals[e] + alpha * sum_{j < m} W[row(e), w0 + j] * Z[col(e), z0 + j]; with symmetric != 0
+ *   the summand is 0.5 * (W[r, .] Z[c, .] + Z[r, .] W[c, .]) - the symmetric part, what a symmetric A can see of its gradient.
+ *   beta == 0 does not read the old values. Asynchronous on the context stream; count += m. Every stored nonzero is owned by
+ *   one lane (one lane of a wave of its own for a row of more than 64 nonzeros) that sums j ascending: no float atomics, and
+ *   identical calls give identical bits. W may be Z. SLQ_EINVAL, the values untouched: a column range outside its matrix, a
+ *   matrix that has not n rows, an object of another context, a non-finite alpha or beta.
+ * slq_sddmm_get: the nnz values in the caller's order and the columns folded in so far (either may be NULL). Synchronises.
+ * slq_sddmm_ptr: the device address of the values, for zero-copy consumers (valid until slq_sddmm_destroy; order reads after
+ *   the context stream). slq_sddmm_reset: values and count back to 0 (asynchronous). */
+int slq_sddmm_create(slq_context *ctx, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colind, slq_sddmm **out);
+int slq_sddmm_create_device(slq_context *ctx, int64_t n, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colind, slq_sddmm **out);
+int slq_sddmm_update(slq_sddmm *s, slq_dmat *W, int w0, slq_dmat *Z, int z0, int m, double alpha, double beta, int symmetric);
+int slq_sddmm_get(slq_sddmm *s, double *vals, int64_t *count);
+int slq_sddmm_ptr(slq_sddmm *s, void **d_vals);
+int slq_sddmm_reset(slq_sddmm *s);
+int slq_sddmm_destroy(slq_sddmm *s);
+/* The work items an update over this pattern launches, one wave each, as the library cuts them, without a device
+ * (csrc/slq_sddmm.hpp: sddmm_schedule). Item i owns the stored nonzeros [e0[i], e1[i]) of the rows row0[i] .. row0[i] + nrows[i]
+ * - 1; kind[i] = 0: at most 64 consecutive rows of at most 64 nonzeros, one lane per row; 1: one longer row, the lanes over
+ * its nonzeros. The first cap items are written (any array may be NULL); *nitems their number; info (4 values or NULL):
+ * workgroups, long rows, the long-row threshold, waves per workgroup. rowptr: n + 1 non-decreasing offsets from 0, else
+ * SLQ_EINVAL. No HIP call. */
+int slq_debug_sddmm_schedule(int64_t n, const int32_t *rowptr, int32_t *row0, int32_t *nrows, int32_t *kind, int64_t *e0, int64_t *e1,
+                             int64_t cap, int64_t *nitems, int64_t *info);
 
 /* Per-kernel device time accumulated by HIP events on the context stream (for bench.py's
  * roofline line). enable != 0 turns event recording on for subsequent slq_plan_run calls. */

@@ -108,6 +108,14 @@ _SIGNATURES = {
 	"slq_density_destroy": (C.c_int, [_P]),
 	"slq_density_update": (C.c_int, [_P, _P]),
 	"slq_density_get": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int64)]),
+	"slq_sddmm_create": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _PP]),
+	"slq_sddmm_create_device": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _PP]),
+	"slq_sddmm_update": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]),
+	"slq_sddmm_get": (C.c_int, [_P, _P, C.POINTER(C.c_int64)]),
+	"slq_sddmm_ptr": (C.c_int, [_P, _PP]),
+	"slq_sddmm_reset": (C.c_int, [_P]),
+	"slq_sddmm_destroy": (C.c_int, [_P]),
+	"slq_debug_sddmm_schedule": (C.c_int, [C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64), _P]),
 	"slq_plan_profile_enable": (C.c_int, [_P, C.c_int]),
 	"slq_plan_action_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
 	"slq_plan_sweep_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),

@@ -1,0 +1,69 @@
+"""tr f(A) as a differentiable torch function of the values of a sparse-CSR tensor on the GPU:
+
+    loss = trace_fun(A_csr, "log", deg=30, count=256, seed=0)   # ~ log det A
+    loss.backward()                                              # A_csr.values().grad ~ (A^-1) on the pattern
+
+`forward` is one `primate_amd.grad.trace_grad` call with `pattern=A_csr` and probes drawn on the device: the value and the
+gradient come out of the same runs, and the gradient stays in HBM (a clone of the accumulator's values). `backward` scales it.
+The operator is rebuilt on every call - its values changed, which is the point.
+"""
+
+from __future__ import annotations
+
+import torch
+
+from . import engine
+from .grad import trace_grad
+
+METHODS = ("lanczos", "chebyshev")
+
+
+class _TraceFun(torch.autograd.Function):
+	@staticmethod
+	def forward(ctx, values, A_csr, opts):
+		from .chebyshev import ChebyshevFunction
+		from .operators import MatrixFunction
+
+		## a tensor of its own: no operator cached on the caller's tensor survives a change of its values
+		A = torch.sparse_csr_tensor(A_csr.crow_indices(), A_csr.col_indices(), values.detach().to(torch.float64), size=tuple(A_csr.shape))
+		o = dict(opts)
+		method, fun, deg, count, seed = (o.pop(k) for k in ("method", "fun", "deg", "count", "seed"))
+		tg = {k: o.pop(k) for k in ("batch", "pdf", "symmetric", "dfun") if k in o}
+		tg.setdefault("pdf", "device:rademacher")
+		M = (MatrixFunction if method == "lanczos" else ChebyshevFunction)(A, fun, deg=deg, **o)
+		try:
+			est, grad, info = trace_grad(M, count=count, seed=seed, pattern=A, keep_device=True, **tg)
+		finally:
+			if hasattr(M, "close"):
+				M.close()
+		acc = info.get("accumulator")
+		if acc is not None:
+			try:
+				G = torch.as_tensor(acc.cuda_array(), device=values.device).clone()
+			finally:
+				acc.close()
+		else:  # (an exact gradient: it never was on the device)
+			G = torch.from_numpy(grad).to(values.device)
+		ctx.save_for_backward(G.to(values.dtype))
+		return values.new_tensor(est)
+
+	@staticmethod
+	def backward(ctx, grad_output):
+		(G,) = ctx.saved_tensors
+		return grad_output * G, None, None
+
+
+def trace_fun(A_csr, fun="log", deg: int = 30, count: int = 256, seed: int = 0, method: str = "lanczos", **kw):
+	"""The Girard-Hutchinson estimate of tr f(A) as a 0-d tensor on A's device, differentiable with respect to `A_csr.values()`:
+	the gradient is the estimate of f'(A) on A's own pattern from the same `count` probes (primate_amd.grad.trace_grad).
+	A_csr: a symmetric fp64 torch sparse-CSR tensor on the GPU. method: "lanczos" (MatrixFunction: fun in log, exp, identity) or
+	"chebyshev" (ChebyshevFunction; `dfun=` for a callable). kw: batch, pdf (default "device:rademacher"), symmetric, dfun go to
+	trace_grad, everything else to the operator (orth=, t=, bounds=, damping=, ...). The same seed gives the same bits."""
+	if not engine._is_torch_csr(A_csr):
+		raise ValueError("trace_fun takes a torch sparse-CSR tensor")
+	if method not in METHODS:
+		raise ValueError(f"unknown method '{method}' (one of {', '.join(METHODS)})")
+	if not A_csr.is_cuda:
+		raise ValueError("a torch sparse-CSR operator must live on the GPU")
+	opts = dict(kw, method=method, fun=fun, deg=int(deg), count=int(count), seed=int(seed))
+	return _TraceFun.apply(A_csr.values(), A_csr, opts)

@@ -35,6 +35,7 @@
 #include "slq_layout.hpp"    // an operator's layout as a value and the host analysis behind it (layout_prefilter, decide_layout)
 #include "slq_plan_shape.hpp"  // what creating a plan decides, as a value (plan_shape)
 #include "slq_cheb.hpp"      // Chebyshev moments: the kernels of slq_plan_run_chebyshev, _moment_sum, slq_density_update_moments
+#include "slq_sddmm.hpp"     // sampled dense-dense product on a CSR pattern: schedule (sddmm_schedule) and kernel of slq_sddmm_*
 
 using namespace slq;
 
@@ -3960,6 +3961,160 @@ extern "C" int slq_plan_get_probes_dmat(slq_plan *p, slq_dmat *OUT, int o0) {
                      OUT->d + (size_t)o0 * p->n, p->PW, (const double *)p->st.coefB, p->op->perm_d);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
+  return SLQ_OK;
+}
+
+// ---- sampled dense-dense product on a CSR pattern (device-resident values; schedule and kernel in slq_sddmm.hpp) -------------
+struct slq_sddmm {
+  slq_context *ctx;
+  int64_t n, nnz, count, nitems, grid;
+  int32_t *rowptr, *colind;  // the caller's pattern as validated on the host (never the caller's own device arrays)
+  SddmmItem *items;
+  double *vals;
+};
+
+static int sddmm_create_body(slq_context *ctx, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colind, slq_sddmm **out, const char *what) {
+  const int64_t bad = sddmm_first_bad_row(n, nnz, rowptr, colind);
+  if (bad >= 0)
+    return fail(SLQ_EINVAL, "%s: not a CSR pattern over %lld rows at row %lld (rowptr[0] == 0, rowptr non-decreasing, rowptr[n] == nnz = %lld, 0 <= colind < n)",
+                what, (long long)n, (long long)bad, (long long)nnz);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->dead) return fail(SLQ_EINVAL, "%s: the context has been destroyed", what);
+  const SddmmSchedule S = sddmm_schedule(n, rowptr);
+  slq_sddmm *s = new (std::nothrow) slq_sddmm();
+  if (!s) return fail(SLQ_ENOMEM, "host allocation failed");
+  *s = slq_sddmm{ctx, n, nnz, 0, (int64_t)S.items.size(), S.grid, nullptr, nullptr, nullptr, nullptr};
+  hipStream_t st = ctx->stream;
+  hipError_t e = hipMalloc((void **)&s->rowptr, ((size_t)n + 1) * 4);
+  if (e == hipSuccess) e = hipMalloc((void **)&s->colind, std::max<size_t>((size_t)nnz, 1) * 4);
+  if (e == hipSuccess) e = hipMalloc((void **)&s->vals, std::max<size_t>((size_t)nnz, 1) * 8);
+  if (e == hipSuccess) e = hipMalloc((void **)&s->items, std::max<size_t>(S.items.size(), 1) * sizeof(SddmmItem));
+  if (e == hipSuccess) e = hipMemcpyAsync(s->rowptr, rowptr, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && nnz) e = hipMemcpyAsync(s->colind, colind, (size_t)nnz * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && !S.items.empty()) e = hipMemcpyAsync(s->items, S.items.data(), S.items.size() * sizeof(SddmmItem), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(s->vals, 0, std::max<size_t>((size_t)nnz, 1) * 8, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // (the host arrays are the caller's, or locals of this call)
+  if (e != hipSuccess) {
+    for (void *p : {(void *)s->rowptr, (void *)s->colind, (void *)s->vals, (void *)s->items})
+      if (p) hipFree(p);
+    delete s;  // (not yet retained)
+    return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "%s: %s", what, hipGetErrorString(e));
+  }
+  ctx_retain(ctx);
+  *out = s;
+  return SLQ_OK;
+}
+
+static int sddmm_shape_check(slq_context *ctx, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colind, slq_sddmm **out, const char *what) {
+  if (!ctx || !out) return fail(SLQ_EINVAL, "%s: ctx/out is NULL", what);
+  *out = nullptr;
+  if (n <= 0 || n >= (int64_t)1 << 31 || nnz < 0 || nnz >= (int64_t)1 << 31) return fail(SLQ_EINVAL, "%s: pattern shape out of range for int32 indices", what);
+  if (!rowptr || (nnz > 0 && !colind)) return fail(SLQ_EINVAL, "%s: pattern arrays are NULL", what);
+  return SLQ_OK;
+}
+
+extern "C" int slq_sddmm_create(slq_context *ctx, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colind, slq_sddmm **out) {
+  SLQ_TRY(sddmm_shape_check(ctx, n, nnz, rowptr, colind, out, "slq_sddmm_create"));
+  try {
+    return sddmm_create_body(ctx, n, nnz, rowptr, colind, out, "slq_sddmm_create");
+  } catch (const std::bad_alloc &) {
+    return fail(SLQ_ENOMEM, "slq_sddmm_create: host allocation failed");
+  }
+}
+
+extern "C" int slq_sddmm_create_device(slq_context *ctx, int64_t n, int64_t nnz, const int32_t *d_rowptr, const int32_t *d_colind, slq_sddmm **out) {
+  SLQ_TRY(sddmm_shape_check(ctx, n, nnz, d_rowptr, d_colind, out, "slq_sddmm_create_device"));
+  try {
+    // the index arrays come back once (4 bytes per nonzero); what the kernel reads is the validated copy, not the caller's arrays
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<int32_t> rp((size_t)n + 1), ci((size_t)nnz);
+    HIP_TRY(hipMemcpy(rp.data(), d_rowptr, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost));
+    if (nnz) HIP_TRY(hipMemcpy(ci.data(), d_colind, (size_t)nnz * 4, hipMemcpyDeviceToHost));
+    return sddmm_create_body(ctx, n, nnz, rp.data(), ci.data(), out, "slq_sddmm_create_device");
+  } catch (const std::bad_alloc &) {
+    return fail(SLQ_ENOMEM, "slq_sddmm_create_device: host allocation failed");
+  }
+}
+
+extern "C" int slq_sddmm_destroy(slq_sddmm *s) {
+  if (!s) return SLQ_OK;
+  hipSetDevice(s->ctx->device);
+  hipStreamSynchronize(s->ctx->stream);
+  for (void *p : {(void *)s->rowptr, (void *)s->colind, (void *)s->vals, (void *)s->items})
+    if (p) hipFree(p);
+  ctx_release(s->ctx);
+  delete s;
+  return SLQ_OK;
+}
+
+extern "C" int slq_sddmm_update(slq_sddmm *s, slq_dmat *W, int w0, slq_dmat *Z, int z0, int m, double alpha, double beta, int symmetric) {
+  if (!s) return fail(SLQ_EINVAL, "slq_sddmm_update: accumulator is NULL");
+  SLQ_TRY(dmat_range(W, w0, m, "slq_sddmm_update(W)"));
+  SLQ_TRY(dmat_range(Z, z0, m, "slq_sddmm_update(Z)"));
+  if (W->n != s->n || Z->n != s->n)
+    return fail(SLQ_EINVAL, "slq_sddmm_update: the pattern has %lld rows, W %lld, Z %lld", (long long)s->n, (long long)W->n, (long long)Z->n);
+  if (W->ctx != s->ctx || Z->ctx != s->ctx) return fail(SLQ_EINVAL, "slq_sddmm_update: a matrix belongs to another context");
+  if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(SLQ_EINVAL, "slq_sddmm_update: alpha = %g, beta = %g must be finite", alpha, beta);
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  if (s->nitems > 0) {
+    const double *w = W->d + (size_t)w0 * s->n, *z = Z->d + (size_t)z0 * s->n;
+    const dim3 g((unsigned)s->grid), b(64 * kSddmmWaves);
+    if (symmetric)
+      k_sddmm<true><<<g, b, 0, s->ctx->stream>>>(s->nitems, s->items, s->rowptr, s->colind, s->n, w, z, m, 0.5 * alpha, beta, s->vals);
+    else
+      k_sddmm<false><<<g, b, 0, s->ctx->stream>>>(s->nitems, s->items, s->rowptr, s->colind, s->n, w, z, m, alpha, beta, s->vals);
+    HIP_TRY(hipGetLastError());
+  }
+  s->count += m;
+  return SLQ_OK;
+}
+
+extern "C" int slq_sddmm_get(slq_sddmm *s, double *vals, int64_t *count) {
+  if (!s) return fail(SLQ_EINVAL, "slq_sddmm_get: accumulator is NULL");
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  if (vals && s->nnz) HIP_TRY(hipMemcpyAsync(vals, s->vals, (size_t)s->nnz * 8, hipMemcpyDeviceToHost, s->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+  if (count) *count = s->count;
+  return SLQ_OK;
+}
+
+extern "C" int slq_sddmm_ptr(slq_sddmm *s, void **d_vals) {
+  if (!s || !d_vals) return fail(SLQ_EINVAL, "slq_sddmm_ptr: NULL argument");
+  *d_vals = s->vals;
+  return SLQ_OK;
+}
+
+extern "C" int slq_sddmm_reset(slq_sddmm *s) {
+  if (!s) return fail(SLQ_EINVAL, "slq_sddmm_reset: accumulator is NULL");
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  HIP_TRY(hipMemsetAsync(s->vals, 0, std::max<size_t>((size_t)s->nnz, 1) * 8, s->ctx->stream));
+  s->count = 0;
+  return SLQ_OK;
+}
+
+extern "C" int slq_debug_sddmm_schedule(int64_t n, const int32_t *rowptr, int32_t *row0, int32_t *nrows, int32_t *kind, int64_t *e0, int64_t *e1, int64_t cap,
+                                        int64_t *nitems, int64_t *info) {
+  if (!rowptr || !nitems || n <= 0 || n >= (int64_t)1 << 31 || cap < 0) return fail(SLQ_EINVAL, "slq_debug_sddmm_schedule: rowptr, nitems, 0 < n < 2^31, cap >= 0");
+  if (rowptr[0] != 0) return fail(SLQ_EINVAL, "slq_debug_sddmm_schedule: rowptr[0] = %d, not 0", rowptr[0]);
+  for (int64_t i = 0; i < n; ++i)
+    if (rowptr[i + 1] < rowptr[i]) return fail(SLQ_EINVAL, "slq_debug_sddmm_schedule: rowptr is not non-decreasing at row %lld", (long long)i);
+  try {
+    const SddmmSchedule S = sddmm_schedule(n, rowptr);
+    *nitems = (int64_t)S.items.size();
+    for (int64_t i = 0; i < std::min<int64_t>(cap, *nitems); ++i) {
+      const SddmmItem &it = S.items[(size_t)i];
+      int64_t a, b;
+      sddmm_item_range(it, rowptr, &a, &b);
+      if (row0) row0[i] = it.row0;
+      if (nrows) nrows[i] = it.nrows ? it.nrows : 1;
+      if (kind) kind[i] = it.nrows ? 0 : 1;
+      if (e0) e0[i] = a;
+      if (e1) e1[i] = b;
+    }
+    if (info) { info[0] = S.grid; info[1] = S.nlong; info[2] = kSddmmLongRow; info[3] = kSddmmWaves; }
+  } catch (const std::bad_alloc &) {
+    return fail(SLQ_ENOMEM, "slq_debug_sddmm_schedule: host allocation failed");
+  }
   return SLQ_OK;
 }
 

@@ -947,6 +947,97 @@ class DensityAccumulator:
 			pass
 
 
+def _is_torch_csr(A) -> bool:
+	return type(A).__module__.split(".")[0] == "torch" and str(getattr(A, "layout", "")) == "torch.sparse_csr"
+
+
+def sddmm_schedule(indptr) -> dict:
+	"""The work items an SddmmAccumulator over this row-pointer array launches, one wave each (slq_debug_sddmm_schedule: no
+	device is touched): row0, nrows, kind (0: one lane per row, 1: one long row over the lanes), e0, e1 (the stored nonzeros
+	[e0, e1) the item owns), and grid, nlong, long_row, waves."""
+	rp = np.ascontiguousarray(indptr, dtype=np.int32).ravel()
+	n = rp.size - 1
+	L = _capi.lib()
+	nitems, info = C.c_int64(), np.zeros(4, dtype=np.int64)
+	check(L.slq_debug_sddmm_schedule(n, ptr(rp), None, None, None, None, None, 0, C.byref(nitems), ptr(info)))
+	k = nitems.value
+	row0, nrows, kind = (np.zeros(k, dtype=np.int32) for _ in range(3))
+	e0, e1 = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int64)
+	check(L.slq_debug_sddmm_schedule(n, ptr(rp), ptr(row0), ptr(nrows), ptr(kind), ptr(e0), ptr(e1), k, C.byref(nitems), ptr(info)))
+	return dict(row0=row0, nrows=nrows, kind=kind, e0=e0, e1=e1, grid=int(info[0]), nlong=int(info[1]), long_row=int(info[2]), waves=int(info[3]))
+
+
+class SddmmAccumulator:
+	"""Device-resident values on a CSR pattern (slq_sddmm_*): every `update` folds alpha * sum_j W[row(e), w0 + j] Z[col(e), z0 + j]
+	into the value of every stored nonzero e. pattern: a SciPy sparse matrix (its `indptr` / `indices` as given - not sorted, not
+	deduplicated; any other format is converted to CSR first) or a torch sparse-CSR tensor on the context's GPU. Only the pattern
+	is read; the values come out aligned with `pattern.data` / `pattern.values()`, entry for entry."""
+
+	def __init__(self, pattern, ctx: Optional[Context] = None):
+		import scipy.sparse as sp
+
+		if not (_is_torch_csr(pattern) or sp.issparse(pattern)):
+			raise ValueError("pattern must be a SciPy sparse matrix or a torch sparse-CSR tensor on the GPU")
+		self.ctx = ctx or default_context()
+		L = _capi.lib()
+		h = C.c_void_p()
+		if _is_torch_csr(pattern):
+			import torch
+
+			if not pattern.is_cuda:
+				raise ValueError("a torch sparse-CSR pattern must live on the GPU (use scipy.sparse for host matrices)")
+			if pattern.device.index != self.ctx.device:
+				raise ValueError(f"the pattern is on {pattern.device}, the context on GPU {self.ctx.device}")
+			if pattern.shape[0] != pattern.shape[1]:
+				raise ValueError(f"the pattern must be square, got {tuple(pattern.shape)}")
+			crow = pattern.crow_indices().to(torch.int32).contiguous()
+			col = pattern.col_indices().to(torch.int32).contiguous()
+			torch.cuda.synchronize(pattern.device)
+			self.n, self.nnz = int(pattern.shape[0]), int(col.numel())
+			check(L.slq_sddmm_create_device(self.ctx._h, self.n, self.nnz, C.c_void_p(crow.data_ptr()), C.c_void_p(col.data_ptr()), C.byref(h)))
+		elif sp.issparse(pattern):
+			M = pattern if pattern.format == "csr" else sp.csr_matrix(pattern)
+			if M.shape[0] != M.shape[1]:
+				raise ValueError(f"the pattern must be square, got {M.shape}")
+			rowptr = np.ascontiguousarray(M.indptr, dtype=np.int32)
+			colind = np.ascontiguousarray(M.indices, dtype=np.int32)
+			self.n, self.nnz = int(M.shape[0]), int(colind.size)
+			check(L.slq_sddmm_create(self.ctx._h, self.n, self.nnz, ptr(rowptr), ptr(colind), C.byref(h)))
+		self._h = h
+
+	def update(self, W: "DeviceMatrix", w0: int, Z: "DeviceMatrix", z0: int, m: int, alpha: float = 1.0, beta: float = 1.0, symmetric: bool = False):
+		"""vals = beta * vals + alpha * (the sampled product over columns [w0, w0 + m) of W and [z0, z0 + m) of Z); symmetric: its
+		symmetric part. Asynchronous on the context stream."""
+		check(_capi.lib().slq_sddmm_update(self._h, W._h, int(w0), Z._h, int(z0), int(m), float(alpha), float(beta), 1 if symmetric else 0))
+
+	def get(self) -> tuple:
+		"""(vals, count): the nnz values in the pattern's order, the columns folded in."""
+		vals = np.zeros(self.nnz)
+		cnt = C.c_int64()
+		check(_capi.lib().slq_sddmm_get(self._h, ptr(vals) if self.nnz else None, C.byref(cnt)))
+		return vals, cnt.value
+
+	def cuda_array(self):
+		"""The values as a flat object with `__cuda_array_interface__` (zero-copy; it keeps the accumulator alive)."""
+		p = C.c_void_p()
+		check(_capi.lib().slq_sddmm_ptr(self._h, C.byref(p)))
+		return _CudaArrayView(p.value, self.nnz, self)
+
+	def reset(self):
+		check(_capi.lib().slq_sddmm_reset(self._h))
+
+	def close(self):
+		if getattr(self, "_h", None):
+			_capi.lib().slq_sddmm_destroy(self._h)
+			self._h = None
+
+	def __del__(self):
+		try:
+			self.close()
+		except Exception:  # noqa: BLE001
+			pass
+
+
 class _CudaArrayView:
 	"""Flat fp64 device array described by the CUDA array interface (v2); keeps its owner alive."""
 
