@@ -133,6 +133,41 @@ int slq_csr_affine_create(slq_context *ctx, int dtype, int64_t n, int64_t nnz_a,
                           const void *vals_a, int64_t nnz_b, const int32_t *rowptr_b, const int32_t *colind_b, const void *vals_b,
                           slq_operator **out);
 int slq_operator_set_parameter(slq_operator *op, double t);
+/* Matrix-free kernel operator: for n points x_i in d dimensions (row-major n x d, leading dimension ldp >= d,
+ * in the operator's dtype), lengthscales l (nls = 1: a scalar that broadcasts, or nls = d: one per dimension), outputscale s
+ * and noise sigma2,
+ *   z_i = (x_i - mean(x)) / l     rounded to the operator's dtype: the operator is DEFINED on these z
+ *   r2_ij = max(0, |z_i|^2 + |z_j|^2 - 2 z_i.z_j), r2_ii = 0 exactly
+ *   A = s phi(r2) + sigma2 I,  phi = exp(-r2/2) (SLQ_KERNEL_RBF), exp(-r) (MATERN12), (1 + sqrt3 r) exp(-sqrt3 r) (MATERN32),
+ *                                    (1 + sqrt5 r + 5 r2 / 3) exp(-sqrt5 r) (MATERN52), r = sqrt(r2).
+ * mean(x) is taken once, at creation: per dimension the sum over the points in row order in double, divided by n. The matrix is
+ * never formed: a product evaluates 16 x 16 tiles of it on the matrix cores and the VALU and feeds them to the product with the
+ * probe panel out of registers; the operator holds the points, z and |z|^2: O(n d) words (slq_operator_shape reports nnz = n d).
+ * The operator is sequenced like a device callback - direct projections, no Gram rows - and its plans replay captured graphs.
+ * SLQ_EINVAL names the first bad value: n, d (1 <= d <= 64), ldp, the profile, nls, a lengthscale that is not positive and
+ * finite, s likewise, sigma2 < 0 or not finite, the first point (row, coordinate) that is not finite.
+ * slq_kernel_create_device: the points are on the context's GPU (they are read back once, for these checks and the mean, and
+ *   copied; the caller's array is not referenced after the call).
+ * slq_kernel_set_parameters: new l, s, sigma2. It recomputes z, |z|^2 and the two scalars IN PLACE on the context stream: no
+ *   allocation, no upload of points, asynchronous. The product kernel reads all of them from device memory, so a plan created
+ *   before the call - and the graphs it has captured - computes with the new values from its next run on.
+ * slq_kernel_get_parameters: d, the profile, the d lengthscales (nls == d; NULL: not wanted), s, sigma2 as last set.
+ * slq_operator_set_parameter (the t of an affine operator) refuses a kernel operator. */
+enum { SLQ_KERNEL_RBF = 0, SLQ_KERNEL_MATERN12 = 1, SLQ_KERNEL_MATERN32 = 2, SLQ_KERNEL_MATERN52 = 3 };
+int slq_kernel_create(slq_context *ctx, int dtype, int64_t n, int d, const void *points, int64_t ldp, int profile,
+                      const double *lengthscales, int nls, double outputscale, double noise, slq_operator **out);
+int slq_kernel_create_device(slq_context *ctx, int dtype, int64_t n, int d, const void *d_points, int64_t ldp, int profile,
+                             const double *lengthscales, int nls, double outputscale, double noise, slq_operator **out);
+int slq_kernel_set_parameters(slq_operator *op, const double *lengthscales, int nls, double outputscale, double noise);
+int slq_kernel_get_parameters(const slq_operator *op, int *d, int *profile, double *lengthscales, int nls, double *outputscale, double *noise);
+/* Diagnostics (tests). slq_debug_kernel_points: what the product kernel reads, as it is on the device now - z transposed
+ * (dpad x npad; dpad = d rounded up to a multiple of 4, npad = n rounded up to a multiple of 16, zeros beyond d and n), |z|^2
+ * (npad) and {s, sigma2}, in the operator's dtype; any may be NULL. slq_debug_kernel_schedule: the schedule of one product for a
+ * plan of `panels` panels of `panel_width` columns on `num_cus` compute units, without a device: out[0] rows per workgroup,
+ * out[1] row blocks, out[2] 16-column tiles per workgroup, out[3] column chunks, out[4] j slabs, out[5 ..] the slabs + 1 bounds
+ * of the slabs in [0, n] (then -1); nout >= 22. */
+int slq_debug_kernel_points(slq_operator *op, void *zt, void *nrm, void *params);
+int slq_debug_kernel_schedule(int64_t n, int panel_width, int panels, int num_cus, int64_t *out, int nout);
 /* Dense symmetric n x n, column-major with leading dimension lda (host array, copied). */
 int slq_dense_create(slq_context *ctx, int dtype, int64_t n, const void *A, int64_t lda,
                      slq_operator **out);
@@ -476,7 +511,8 @@ int slq_plan_window_columns(slq_plan *plan, int64_t out[5], int reset);
 /* Which kernel computes the product of a plan on a dense operator, and over how many K slabs (a diagnostic entry: what the plan will launch, from the
  * panel width, the operator's leading dimension and the SLQ_DENSE_* switches read when it was created). kernel: 0 the operator is not dense,
  * 1 k_dense_panel, 2 k_dense_mfma_3term, 3 k_dense_mfma_tile, 4 k_dense_mfma_lds, 5 k_dense_mfma32_lds; ksplit: workgroups (slabs) the K range is
- * split over, 0 for the kernels without slabs. kernel or ksplit may be NULL. */
+ * split over, 0 for the kernels without slabs. A plan on a kernel operator (slq_kernel_create) answers kernel 0 and, in ksplit, the j slabs of its
+ * product (0: one slab, written straight into the product panel). kernel or ksplit may be NULL. */
 int slq_plan_dense_path(slq_plan *plan, int *kernel, int *ksplit);
 /* ... the plan's mode (0 where nothing is offered) and, from verify runs since the last reset of those counters: out[0] the largest one-step innovation
  * |measured - predicted| in units of eps ||A||_inf, out[1] the smallest (tol - |measured|) / rho (inf: none seen), out[2], out[3] the constants c and kappa

@@ -24,6 +24,7 @@ FUN_IDS = {
 }  # fmt: skip
 PDF_IDS = {"rademacher": 0, "signs": 0, "normal": 1, "gaussian": 1, "sphere": 2}
 DENSITY_KINDS = {"gaussian": 0, "lorentzian": 1, "histogram": 2, "cdf": 3, "chebyshev": 4}
+KERNEL_PROFILES = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3}
 KERNEL_CLASSES = ["spmm_3term", "axpy_norm", "reorth_dot", "reorth_update", "finalize", "probes", "quadrature", "fun_combine"]
 
 MATVEC_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
@@ -58,6 +59,12 @@ _SIGNATURES = {
 	"slq_csr_affine_create": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, _PP]),
 	"slq_operator_set_parameter": (C.c_int, [_P, C.c_double]),
 	"slq_dense_create": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int64, _PP]),
+	"slq_kernel_create": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int, C.c_double, C.c_double, _PP]),
+	"slq_kernel_create_device": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int, C.c_double, C.c_double, _PP]),
+	"slq_kernel_set_parameters": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double]),
+	"slq_kernel_get_parameters": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), _P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+	"slq_debug_kernel_points": (C.c_int, [_P, _P, _P, _P]),
+	"slq_debug_kernel_schedule": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int]),
 	"slq_callback_create": (C.c_int, [_P, C.c_int, C.c_int64, MATVEC_FN, _P, _PP]),
 	"slq_operator_destroy": (C.c_int, [_P]),
 	"slq_operator_shape": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),

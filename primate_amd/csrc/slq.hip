@@ -36,6 +36,7 @@
 #include "slq_plan_shape.hpp"  // what creating a plan decides, as a value (plan_shape)
 #include "slq_cheb.hpp"      // Chebyshev moments: the kernels of slq_plan_run_chebyshev, _moment_sum, slq_density_update_moments
 #include "slq_sddmm.hpp"     // sampled dense-dense product on a CSR pattern: schedule (sddmm_schedule) and kernel of slq_sddmm_*
+#include "slq_kernelop.hpp"  // matrix-free kernel operator (slq_kernel_*): validation, schedule, k_kernel_rescale, k_kernel_panel
 
 using namespace slq;
 
@@ -103,7 +104,7 @@ static void ctx_release(slq_context *ctx) {
   if (--ctx->refs == 0 && ctx->dead) ctx_free(ctx);
 }
 
-// (OP_CSR .. OP_GRAM, the kinds of an operator: slq_plan_shape.hpp)
+// (OP_CSR .. OP_KERNEL, the kinds of an operator: slq_plan_shape.hpp)
 static_assert(kF32 == SLQ_F32 && kF64 == SLQ_F64, "slq_plan_shape.hpp: the dtype codes of include/slq.h");
 
 struct slq_operator {
@@ -157,6 +158,13 @@ struct slq_operator {
   void *vals_a = nullptr, *vals_b = nullptr;
   void *vals_t = nullptr;    // OP_DENSE, non-symmetric input only (also the values of A^T for OP_GRAM): the transpose, for the kernel that walks A by columns (null: A == A^T)
   OperatorSwitches sw;       // the switches as they were when the operator was created (slq_switches.hpp)
+  // OP_KERNEL (slq_kernelop.hpp): the raw points (n x d), z transposed (dpad x npad) and |z|^2 (npad), s and sigma2 in two device
+  // words - all at addresses that never change, so that a captured graph sees a hyperparameter change. nnz reports n d.
+  int k_d = 0, k_dpad = 0, k_profile = 0;
+  int64_t k_npad = 0;
+  void *k_raw = nullptr, *k_zt = nullptr, *k_nrm = nullptr, *k_params = nullptr;  // (one allocation, k_raw its base)
+  KernelScale *k_scale = nullptr;  // host: the centre of the points and the lengthscales per dimension
+  double k_s = 1.0, k_noise = 0.0;
 };
 
 struct ProfEvent {
@@ -1224,6 +1232,7 @@ extern "C" int slq_csr_affine_create(slq_context *ctx, int dtype, int64_t n, int
 // t of an affine operator A + t B (SparseEigenAffineOperator::set_parameter, eigen_operators.h:134-136)
 extern "C" int slq_operator_set_parameter(slq_operator *op, double t) {
   if (!op) return fail(SLQ_EINVAL, "op is NULL");
+  if (op->kind == OP_KERNEL) return fail(SLQ_EINVAL, "a kernel operator has no parameter t: its hyperparameters are set by slq_kernel_set_parameters");
   if (!op->vals_a || !op->vals_b) return fail(SLQ_EINVAL, "not an affine operator");
   HIP_TRY(hipSetDevice(op->ctx->device));
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (op->nnz + 255) / 256));
@@ -1317,6 +1326,137 @@ extern "C" int slq_device_callback_create(slq_context *ctx, int dtype, int64_t n
   return SLQ_OK;
 }
 
+// ---- matrix-free kernel operator (slq_kernelop.hpp) ----
+// z, |z|^2, s and sigma2 from the raw points and the operator's host record, on the library's stream (no allocation, no upload)
+static int kernel_rescale(slq_operator *op) {
+  const int n = (int)op->n, npad = (int)op->k_npad;
+  const dim3 g((unsigned)((npad + 255) / 256));
+  if (op->dtype == SLQ_F64)
+    k_kernel_rescale<double><<<g, dim3(256), 0, op->ctx->stream>>>(n, npad, op->k_d, op->k_dpad, (const double *)op->k_raw, *op->k_scale, (double *)op->k_zt,
+                                                                  (double *)op->k_nrm, (double *)op->k_params, op->k_s, op->k_noise);
+  else
+    k_kernel_rescale<float><<<g, dim3(256), 0, op->ctx->stream>>>(n, npad, op->k_d, op->k_dpad, (const float *)op->k_raw, *op->k_scale, (float *)op->k_zt,
+                                                                 (float *)op->k_nrm, (float *)op->k_params, op->k_s, op->k_noise);
+  HIP_TRY(hipGetLastError());
+  return SLQ_OK;
+}
+static int kernel_bad(const KernelBad &b) {
+  char msg[256];
+  kernel_bad_message(b, msg, sizeof msg);
+  return fail(SLQ_EINVAL, "%s", msg);
+}
+static void kernel_set_scale(slq_operator *op, const double *ls, int nls, double s, double noise) {
+  for (int k = 0; k < kKernelMaxDim; ++k) op->k_scale->ls[k] = k < op->k_d ? ls[nls == 1 ? 0 : k] : 1.0;
+  op->k_s = s, op->k_noise = noise;
+}
+static int kernel_create_body(slq_context *ctx, int dtype, int64_t n, int d, const void *points, int64_t ldp, int profile, const double *ls,
+                              int nls, double s, double noise, bool on_device, slq_operator **out) {
+  if (!ctx || !out) return fail(SLQ_EINVAL, "ctx/out is NULL");
+  *out = nullptr;
+  if (!points || !ls) return fail(SLQ_EINVAL, "kernel operator: points/lengthscales is NULL");
+  SLQ_TRY(check_dtype(dtype));
+  KernelBad bad = dtype == SLQ_F64 ? kernel_validate<double>(n, d, on_device ? nullptr : (const double *)points, ldp, profile, ls, nls, s, noise)
+                                   : kernel_validate<float>(n, d, on_device ? nullptr : (const float *)points, ldp, profile, ls, nls, s, noise);
+  if (bad.what != KERNEL_OK) return kernel_bad(bad);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->dead) return fail(SLQ_EINVAL, "the context has been destroyed");
+  const size_t es = esize(dtype);
+  // points on the device: a packed host copy for the checks and the centre (n d words, once per operator)
+  std::vector<char> host;
+  const void *hp = points;
+  int64_t hld = ldp;
+  if (on_device) {
+    host.resize((size_t)n * d * es);
+    HIP_TRY(hipMemcpy2D(host.data(), (size_t)d * es, points, (size_t)ldp * es, (size_t)d * es, (size_t)n, hipMemcpyDeviceToHost));
+    hp = host.data(), hld = d;
+    bad = dtype == SLQ_F64 ? kernel_validate<double>(n, d, (const double *)hp, hld, profile, ls, nls, s, noise)
+                           : kernel_validate<float>(n, d, (const float *)hp, hld, profile, ls, nls, s, noise);
+    if (bad.what != KERNEL_OK) return kernel_bad(bad);
+  }
+  slq_operator *op = new (std::nothrow) slq_operator();
+  if (!op) return fail(SLQ_ENOMEM, "host allocation failed");
+  ctx_retain(ctx);
+  *op = slq_operator{ctx, OP_KERNEL, dtype, n, n * d, nullptr, nullptr, nullptr, 0, false, nullptr, nullptr, nullptr, nullptr, TileMeta{}};
+  op->sw = read_operator_switches();
+  OpGuard guard{op};
+  op->k_d = d, op->k_dpad = kernel_dpad(d), op->k_npad = kernel_npad(n), op->k_profile = profile;
+  op->k_scale = new KernelScale();
+  for (int k = 0; k < kKernelMaxDim; ++k) op->k_scale->mean[k] = 0.0;
+  if (dtype == SLQ_F64) kernel_column_means<double>(n, d, (const double *)hp, hld, op->k_scale->mean);
+  else kernel_column_means<float>(n, d, (const float *)hp, hld, op->k_scale->mean);
+  for (int k = 0; k < d; ++k)
+    if (!std::isfinite(op->k_scale->mean[k])) return fail(SLQ_EINVAL, "kernel operator: the mean of coordinate %d overflows", k);
+  kernel_set_scale(op, ls, nls, s, noise);
+  // one allocation: raw points | z transposed | |z|^2 | {s, sigma2}, each on a 256-byte boundary
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t b_raw = up((size_t)n * d * es), b_zt = up((size_t)op->k_dpad * (size_t)op->k_npad * es), b_nrm = up((size_t)op->k_npad * es);
+  hipError_t e = hipMalloc(&op->k_raw, b_raw + b_zt + b_nrm + 256);
+  if (e == hipSuccess) {
+    op->k_zt = (char *)op->k_raw + b_raw;
+    op->k_nrm = (char *)op->k_zt + b_zt;
+    op->k_params = (char *)op->k_nrm + b_nrm;
+  }
+  if (e == hipSuccess)
+    e = hipMemcpy2DAsync(op->k_raw, (size_t)d * es, hp, (size_t)hld * es, (size_t)d * es, (size_t)n, hipMemcpyHostToDevice, ctx->stream);
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "kernel operator upload: %s", hipGetErrorString(e));
+  SLQ_TRY(kernel_rescale(op));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  *out = guard.release();
+  return SLQ_OK;
+}
+extern "C" int slq_kernel_create(slq_context *ctx, int dtype, int64_t n, int d, const void *points, int64_t ldp, int profile,
+                                 const double *lengthscales, int nls, double outputscale, double noise, slq_operator **out) {
+  return create_guarded(out, [&]() { return kernel_create_body(ctx, dtype, n, d, points, ldp, profile, lengthscales, nls, outputscale, noise, false, out); });
+}
+extern "C" int slq_kernel_create_device(slq_context *ctx, int dtype, int64_t n, int d, const void *d_points, int64_t ldp, int profile,
+                                        const double *lengthscales, int nls, double outputscale, double noise, slq_operator **out) {
+  return create_guarded(out, [&]() { return kernel_create_body(ctx, dtype, n, d, d_points, ldp, profile, lengthscales, nls, outputscale, noise, true, out); });
+}
+extern "C" int slq_kernel_set_parameters(slq_operator *op, const double *lengthscales, int nls, double outputscale, double noise) {
+  if (!op) return fail(SLQ_EINVAL, "op is NULL");
+  if (op->kind != OP_KERNEL) return fail(SLQ_EINVAL, "slq_kernel_set_parameters: not a kernel operator");
+  const KernelBad bad = kernel_validate_parameters(op->k_d, lengthscales, nls, outputscale, noise);
+  if (bad.what != KERNEL_OK) return kernel_bad(bad);
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  kernel_set_scale(op, lengthscales, nls, outputscale, noise);
+  return kernel_rescale(op);
+}
+extern "C" int slq_kernel_get_parameters(const slq_operator *op, int *d, int *profile, double *lengthscales, int nls, double *outputscale, double *noise) {
+  if (!op) return fail(SLQ_EINVAL, "op is NULL");
+  if (op->kind != OP_KERNEL) return fail(SLQ_EINVAL, "slq_kernel_get_parameters: not a kernel operator");
+  if (lengthscales && nls != op->k_d) return fail(SLQ_EINVAL, "slq_kernel_get_parameters: room for %d lengthscales, the operator has d = %d", nls, op->k_d);
+  if (d) *d = op->k_d;
+  if (profile) *profile = op->k_profile;
+  if (lengthscales) std::copy(op->k_scale->ls, op->k_scale->ls + op->k_d, lengthscales);
+  if (outputscale) *outputscale = op->k_s;
+  if (noise) *noise = op->k_noise;
+  return SLQ_OK;
+}
+// what the product kernel reads, as it is on the device now: z transposed (dpad x npad, dpad = d rounded up to 4, npad = n rounded
+// up to 16), |z|^2 (npad) and {s, sigma2}, in the operator's dtype (tests)
+extern "C" int slq_debug_kernel_points(slq_operator *op, void *zt, void *nrm, void *params) {
+  if (!op) return fail(SLQ_EINVAL, "op is NULL");
+  if (op->kind != OP_KERNEL) return fail(SLQ_EINVAL, "slq_debug_kernel_points: not a kernel operator");
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  HIP_TRY(hipStreamSynchronize(op->ctx->stream));
+  const size_t es = esize(op->dtype);
+  if (zt) HIP_TRY(hipMemcpy(zt, op->k_zt, (size_t)op->k_dpad * (size_t)op->k_npad * es, hipMemcpyDeviceToHost));
+  if (nrm) HIP_TRY(hipMemcpy(nrm, op->k_nrm, (size_t)op->k_npad * es, hipMemcpyDeviceToHost));
+  if (params) HIP_TRY(hipMemcpy(params, op->k_params, 2 * es, hipMemcpyDeviceToHost));
+  return SLQ_OK;
+}
+// kernel_schedule() of slq_kernelop.hpp as an array: rows per block, row blocks, 16-column tiles per workgroup, column chunks, slabs,
+// then slab_begin[0 .. slabs]. No HIP call.
+extern "C" int slq_debug_kernel_schedule(int64_t n, int panel_width, int panels, int num_cus, int64_t *out, int nout) {
+  if (!out || nout < 5 + kKernelMaxSlabs + 1) return fail(SLQ_EINVAL, "slq_debug_kernel_schedule: room for %d values", 5 + kKernelMaxSlabs + 1);
+  if (n <= 0 || panel_width < 16 || (panel_width & (panel_width - 1)) || panels <= 0 || num_cus <= 0)
+    return fail(SLQ_EINVAL, "slq_debug_kernel_schedule: n, panels, num_cus positive, panel_width a power of two >= 16");
+  const KernelSchedule S = kernel_schedule(n, panel_width, panels, num_cus);
+  out[0] = S.rows_per_block, out[1] = S.nrow_blocks, out[2] = S.col_blocks, out[3] = S.ncol_chunks, out[4] = S.nslabs;
+  for (int z = 0; z <= kKernelMaxSlabs; ++z) out[5 + z] = z <= S.nslabs ? S.slab_begin[z] : -1;
+  return SLQ_OK;
+}
+
 extern "C" int slq_operator_destroy(slq_operator *op) {
   if (!op) return SLQ_OK;
   if (op->owns) {
@@ -1325,6 +1465,8 @@ extern "C" int slq_operator_destroy(slq_operator *op) {
     if (op->colind) hipFree(op->colind);
     if (op->vals) hipFree(op->vals);
   }
+  if (op->k_raw) hipFree(op->k_raw);  // (z, |z|^2 and the scalars lie behind the points in the same allocation)
+  delete op->k_scale;
   if (op->vals_t) hipFree(op->vals_t);
   if (op->rowptr_t) hipFree(op->rowptr_t);
   if (op->colind_t) hipFree(op->colind_t);
@@ -1853,6 +1995,8 @@ extern "C" int slq_debug_plan_shape(const double *facts, int nfacts, double *out
   if (!facts || !out || nfacts != kNumPlanFacts || nout != kNumPlanShape)
     return fail(SLQ_EINVAL, "slq_debug_plan_shape: %d facts in, %d values out", kNumPlanFacts, kNumPlanShape);
   const PlanFacts f = plan_facts_from_array(facts);
+  // (OP_KERNEL is not taken here: its shape is that of a callback operator plus the j slabs of slq_debug_kernel_schedule, and a live
+  // plan answers through slq_debug_plan_shape_of)
   if (f.kind < OP_CSR || f.kind > OP_GRAM || (f.dtype != kF32 && f.dtype != kF64) || (int)f.plan < 0 || (int)f.plan > (int)PlanKind::ChebyshevAction)
     return fail(SLQ_EINVAL, "slq_debug_plan_shape: operator kind, dtype or plan kind out of range");
   if (f.n <= 0 || f.nprobes <= 0 || f.deg < 1 || f.orth < 0 || f.num_cus <= 0) return fail(SLQ_EINVAL, "slq_debug_plan_shape: n, nprobes, deg, num_cus must be positive");
@@ -2367,10 +2511,37 @@ static int launch_dense_mfma(slq_plan *p, const void *Wc, const void *Wp, void *
   return SLQ_OK;
 }
 
+// kernel operator: T = A W_c by k_kernel_panel (slq_kernelop.hpp). One slab: straight into T; a j split (small n): slab z into
+// T + (1 + z) slots, summed in slab order into T by k_3term_slabs (plain) - the slabs the plan's shape allocated (dense_ks)
+static int launch_kernel_product(slq_plan *p, const void *Wc) {
+  const slq_operator *op = p->op;
+  hipStream_t st = p->ctx->stream;
+  const KernelSchedule S = kernel_schedule(p->n, p->PW, p->NP, p->ctx->num_cus);
+  if ((S.nslabs > 1 ? S.nslabs : 0) != p->dense_ks) return fail(SLQ_EINVAL, "kernel operator: the plan holds %d slabs, the schedule asks for %d", p->dense_ks, S.nslabs);
+  int log2pw = 0;
+  while ((1 << log2pw) < p->PW) ++log2pw;
+  char *raw = (char *)p->T + (S.nslabs > 1 ? (size_t)p->slot_stride * p->esz : 0);
+  const KernelPanelArgs a{p->n, (int)op->k_npad, op->k_dpad / 4, op->k_zt, op->k_nrm, op->k_params, Wc, log2pw, p->NP * p->PW, raw, p->slot_stride};
+  const bool ok = p->dtype == SLQ_F64 ? kernel_panel_launch<double>(op->k_profile, S, a, st) : kernel_panel_launch<float>(op->k_profile, S, a, st);
+  if (!ok) return fail(SLQ_EINVAL, "kernel operator: no product kernel for profile %d with %d column tiles", op->k_profile, S.col_blocks);
+  if (S.nslabs > 1) {
+    const dim3 gS(p->nblkS, p->NP);
+    DISPATCH(p->dtype, p->LPR,
+             (k_3term_slabs<F, L><<<gS, dim3(kBlock), 0, st>>>(p->n, (const F *)raw, S.nslabs, p->slot_stride, (const F *)Wc, (const F *)nullptr, (F *)p->T,
+                                                             p->st.coefA, p->part, p->bpad, 1, 1)));
+  }
+  HIP_TRY(hipGetLastError());
+  return SLQ_OK;
+}
+
 // T = A * (slot c), unscaled, for operators without a fused kernel
 static int apply_operator_unfused(slq_plan *p, int slot_c) {
   hipStream_t st = p->ctx->stream;
   slq_operator *op = p->op;
+  if (op->kind == OP_KERNEL) {
+    PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_kernel_product(p, slot_ptr(p, slot_c))));
+    return SLQ_OK;
+  }
   if (dense_kernel_of(p) >= DENSE_K_3TERM) {
     PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_dense_mfma(p, slot_ptr(p, slot_c), nullptr, p->T, 1, 1, nullptr)));
     return SLQ_OK;

@@ -13,12 +13,13 @@
 #include <cmath>
 
 #include "slq_format.hpp"
+#include "slq_kernelop.hpp"
 #include "slq_sequence.hpp"
 #include "slq_switches.hpp"
 
 namespace slq {
 
-enum { OP_CSR = 0, OP_DENSE = 1, OP_CALLBACK = 2, OP_DEVICE_CALLBACK = 3, OP_GRAM = 4 };
+enum { OP_CSR = 0, OP_DENSE = 1, OP_CALLBACK = 2, OP_DEVICE_CALLBACK = 3, OP_GRAM = 4, OP_KERNEL = 5 };
 constexpr int kF32 = 0, kF64 = 1;  // == SLQ_F32, SLQ_F64 (include/slq.h; slq.hip asserts the equality)
 
 // Ring: the window of the last orth vectors. KeepBasis: every vector. Recompute: the ring widened for the accumulation launches
@@ -355,7 +356,12 @@ inline PlanShape plan_shape(const PlanFacts &f, const PlanSwitches &sw) {
       if ((forced > 0 && ks == forced) || (forced <= 0 && cost < best - 1e-12)) { best = cost; s.dense_ks = ks; }
     }
   }
-  s.t_slabs_bound = f.kind == OP_CSR ? 0 : 1 + ((f.kind == OP_DENSE && (f.dtype == kF32 || s.PW >= 32)) ? 16 : 0);
+  // kernel operator (slq_kernelop.hpp): the j slabs of its product take the same place behind T (dense_ks slabs; 0: one slab, straight into T)
+  if (f.kind == OP_KERNEL) {
+    const int slabs = kernel_schedule(f.n, s.PW, s.NP, f.num_cus).nslabs;
+    s.dense_ks = slabs > 1 ? slabs : 0;
+  }
+  s.t_slabs_bound = f.kind == OP_CSR ? 0 : 1 + (((f.kind == OP_DENSE && (f.dtype == kF32 || s.PW >= 32)) || f.kind == OP_KERNEL) ? 16 : 0);
   // the one decision behind launch_dense_mfma, apply_operator_unfused and the step loop
   if (f.kind != OP_DENSE) s.dense_class = DENSE_K_NONE;
   else if (!sw.dense_mfma || (f.dtype != kF64 && s.dense_ks <= 0)) s.dense_class = DENSE_K_PANEL;  // the VALU kernel (SLQ_DENSE_MFMA=0)

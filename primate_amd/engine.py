@@ -171,6 +171,30 @@ class DeviceOperator:
 			import weakref
 
 			A._device_ops.append(weakref.ref(self))
+		elif getattr(A, "_slq_kind", None) == "kernel":
+			## matrix-free kernel operator (primate_amd.operators.KernelOperator): slq_kernel_create, or slq_kernel_create_device for
+			## points that are a torch tensor on this context's GPU; the hyperparameters follow A.set_parameters
+			if self.dtype != np.dtype(A.dtype):
+				raise ValueError(f"the KernelOperator is {A.dtype}: its device operator cannot be {self.dtype} (the operator is defined on points rounded to its dtype)")
+			ls = np.ascontiguousarray(A.lengthscale, dtype=np.float64)
+			prof = _capi.KERNEL_PROFILES[A.kernel]
+			n, d = A.X.shape
+			Xd = getattr(A, "_X_device", None)
+			if Xd is not None:
+				import torch
+
+				if Xd.device.index != self.ctx.device:
+					raise ValueError(f"the points are on {Xd.device}, the context on GPU {self.ctx.device}")
+				Xt = Xd.detach().reshape(n, d).to(torch.float64 if self.dtype == np.float64 else torch.float32).contiguous()
+				torch.cuda.synchronize(Xd.device)
+				check(L.slq_kernel_create_device(self.ctx._h, dt, n, d, C.c_void_p(Xt.data_ptr()), d, prof, ptr(ls), ls.size, float(A.outputscale), float(A.noise), C.byref(h)))
+			else:
+				check(L.slq_kernel_create(self.ctx._h, dt, n, d, ptr(A.X), d, prof, ptr(ls), ls.size, float(A.outputscale), float(A.noise), C.byref(h)))
+			self.kind, self.nnz = "kernel", int(n * d)
+			A._device_ops = getattr(A, "_device_ops", [])
+			import weakref
+
+			A._device_ops.append(weakref.ref(self))
 		elif hasattr(A, "matmat_device"):
 			## GPU-resident plugin: A.matmat_device(X, Y, stream) receives two objects with
 			## `__cuda_array_interface__` (shape (ncols, n), C order = column-major n x ncols) and a stream handle
@@ -215,6 +239,22 @@ class DeviceOperator:
 	def set_parameter(self, t: float) -> None:
 		"""t of an affine operator A + t B (SparseEigenAffineOperator::set_parameter, eigen_operators.h:134-136)."""
 		check(_capi.lib().slq_operator_set_parameter(self._h, float(t)))
+
+	def set_kernel_parameters(self, lengthscale, outputscale: float, noise: float) -> None:
+		"""Hyperparameters of a kernel operator (slq_kernel_set_parameters): z, |z|^2 and the scalars are recomputed in place on the
+		context stream; live plans, and the graphs they captured, see the new values from their next run."""
+		ls = np.ascontiguousarray(np.atleast_1d(lengthscale), dtype=np.float64)
+		check(_capi.lib().slq_kernel_set_parameters(self._h, ptr(ls), ls.size, float(outputscale), float(noise)))
+
+	def kernel_parameters(self) -> dict:
+		"""What slq_kernel_get_parameters reports: d, kernel, the d lengthscales, outputscale, noise."""
+		L = _capi.lib()
+		d, prof, s, v = C.c_int(), C.c_int(), C.c_double(), C.c_double()
+		check(L.slq_kernel_get_parameters(self._h, C.byref(d), C.byref(prof), None, 0, C.byref(s), C.byref(v)))
+		ls = np.empty(d.value)
+		check(L.slq_kernel_get_parameters(self._h, None, None, ptr(ls), d.value, None, None))
+		name = {v_: k for k, v_ in _capi.KERNEL_PROFILES.items()}[prof.value]
+		return dict(d=d.value, kernel=name, lengthscale=ls, outputscale=s.value, noise=v.value)
 
 	def matmat(self, X: np.ndarray) -> np.ndarray:
 		X = np.asfortranarray(X.reshape(self.shape[1], -1), dtype=self.dtype)

@@ -147,6 +147,8 @@ def trace_grad(M, pdf: Union[str, None] = "rademacher", count: int = 256, batch:
 
 	if not isinstance(M, (MatrixFunction, ChebyshevFunction)):
 		raise ValueError("trace_grad takes a MatrixFunction or a ChebyshevFunction")
+	if getattr(getattr(M, "_A", None), "_slq_kind", None) == "kernel" or getattr(getattr(M, "_op", None), "kind", None) == "kernel":
+		raise ValueError("trace_grad: hyperparameter gradients of a KernelOperator are not built (they need a derivative-kernel product)")
 	if np.dtype(M.dtype) != np.float64:
 		raise ValueError("trace_grad is fp64 only (the device matrices are fp64): build M with dtype=np.float64")
 	count, batch = int(count), int(batch)

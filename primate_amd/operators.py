@@ -339,6 +339,145 @@ class AffineOperator(LinearOperator):
 		return self
 
 
+KERNEL_PROFILES = ("rbf", "matern12", "matern32", "matern52")
+KERNEL_MAX_DIM = 64
+
+
+def _kernel_profile(name: str, r2: np.ndarray) -> np.ndarray:
+	"""phi(r2) of the four stationary profiles (r = sqrt(r2))."""
+	if name == "rbf":
+		return np.exp(-0.5 * r2)
+	r = np.sqrt(r2)
+	if name == "matern12":
+		return np.exp(-r)
+	if name == "matern32":
+		a = np.sqrt(3.0) * r
+		return (1.0 + a) * np.exp(-a)
+	a = np.sqrt(5.0) * r
+	return (1.0 + a + (5.0 / 3.0) * r2) * np.exp(-a)
+
+
+class KernelOperator(LinearOperator):
+	"""The kernel matrix of n points in d dimensions, never formed: with z_i = (x_i - mean(x)) / lengthscale rounded to `dtype`
+	(the operator is DEFINED on these z), r2_ij = max(0, |z_i|^2 + |z_j|^2 - 2 z_i.z_j) (0 on the diagonal) and phi the profile
+	("rbf": exp(-r2/2); "matern12": exp(-r); "matern32": (1 + sqrt3 r) exp(-sqrt3 r); "matern52": (1 + sqrt5 r + 5 r2/3) exp(-sqrt5 r)),
+
+	    A = outputscale * phi(r2) + noise * I.
+
+	The operator of a Gaussian process: `hutch(MatrixFunction(KernelOperator(X, "rbf", lengthscale=0.3, noise=1e-2), fun="log"))` is
+	the log-determinant of its marginal likelihood. On the device (`slq_kernel_create`) a product evaluates tiles of A on the matrix
+	cores and consumes them out of registers: the operator holds O(n d) words, whatever n. `X`: an (n, d) NumPy array (or (n,) for
+	d = 1), or a torch tensor on the context's GPU (`slq_kernel_create_device`; the host methods below then work on a host copy).
+	`lengthscale`: a scalar or one per dimension. mean(x) is fixed at construction: per dimension the sum over the points in row
+	order in float64, divided by n. `set_parameters` changes lengthscale / outputscale / noise, also on operators already wrapped in
+	a `MatrixFunction` - live plans compute with the new values from their next run. The host `_matvec` / `_matmat` are blocked
+	NumPy in float64 from the definition: the plugin surface, and the model of the tests."""
+
+	_slq_kind = "kernel"
+
+	def __init__(self, X, kernel: str = "rbf", lengthscale=1.0, outputscale: float = 1.0, noise: float = 0.0, dtype=None):
+		self._X_device = None
+		if type(X).__module__.split(".")[0] == "torch":
+			if dtype is None:
+				dtype = {"torch.float64": np.float64, "torch.float32": np.float32}.get(str(X.dtype), np.float64)
+			if X.is_cuda:
+				self._X_device = X
+			X = X.detach().cpu().numpy()
+		X = np.asarray(X)
+		if dtype is None:
+			dtype = X.dtype if X.dtype in (np.float32, np.float64) else np.float64
+		self.dtype = np.dtype(dtype)
+		if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+			raise ValueError("Only 32- or 64-bit floats are supported.")
+		if X.ndim == 1:
+			X = X.reshape(-1, 1)
+		if X.ndim != 2 or X.shape[0] < 1:
+			raise ValueError(f"the points must be an (n, d) array, got shape {X.shape}")
+		n, d = X.shape
+		if not 1 <= d <= KERNEL_MAX_DIM:
+			raise ValueError(f"kernel operator: d = {d} dimensions (1 <= d <= {KERNEL_MAX_DIM})")
+		if not isinstance(kernel, str) or kernel not in KERNEL_PROFILES:
+			raise ValueError(f"kernel operator: unknown profile {kernel!r} (one of {', '.join(KERNEL_PROFILES)})")
+		self.X = np.ascontiguousarray(X, dtype=self.dtype)
+		bad = np.argwhere(~np.isfinite(self.X))
+		if bad.size:
+			i, k = (int(v) for v in bad[0])
+			raise ValueError(f"kernel operator: point {i}, coordinate {k} is {self.X[i, k]} (points must be finite)")
+		self.kernel = kernel
+		self.shape = (n, n)
+		## the centre: sequential float64 sums in row order (cumsum adds in order; np.sum is pairwise), as the library takes it
+		self.mean = np.cumsum(self.X, axis=0, dtype=np.float64)[-1] / np.float64(n)
+		self.lengthscale, self.outputscale, self.noise = self._check_parameters(lengthscale, outputscale, noise)
+		self._z = None
+
+	def _check_parameters(self, lengthscale, outputscale, noise):
+		d = self.X.shape[1]
+		ls = np.atleast_1d(np.asarray(lengthscale, dtype=np.float64)).ravel()
+		if ls.size not in (1, d):
+			raise ValueError(f"kernel operator: {ls.size} lengthscales (1 or d = {d})")
+		badl = np.flatnonzero(~(np.isfinite(ls) & (ls > 0)))
+		if badl.size:
+			raise ValueError(f"kernel operator: lengthscale[{int(badl[0])}] = {ls[badl[0]]} is not a positive finite number")
+		s, v = float(outputscale), float(noise)
+		if not (np.isfinite(s) and s > 0):
+			raise ValueError(f"kernel operator: outputscale = {s} is not a positive finite number")
+		if not (np.isfinite(v) and v >= 0):
+			raise ValueError(f"kernel operator: noise = {v} is not a finite number >= 0")
+		return ls.copy(), s, v
+
+	def set_parameters(self, lengthscale=None, outputscale=None, noise=None) -> None:
+		"""New hyperparameters (None: unchanged), forwarded to every live device operator built from this object."""
+		self.lengthscale, self.outputscale, self.noise = self._check_parameters(
+			self.lengthscale if lengthscale is None else lengthscale,
+			self.outputscale if outputscale is None else outputscale,
+			self.noise if noise is None else noise,
+		)
+		self._z = None
+		for ref in getattr(self, "_device_ops", []):
+			op = ref()
+			if op is not None and getattr(op, "_h", None):
+				op.set_kernel_parameters(self.lengthscale, self.outputscale, self.noise)
+
+	def scaled_points(self) -> np.ndarray:
+		"""z = (x - mean) / lengthscale, computed in float64 and rounded once to the operator's dtype: what the operator is defined on."""
+		if self._z is None:
+			ls = np.broadcast_to(self.lengthscale, (self.X.shape[1],))
+			self._z = ((self.X.astype(np.float64) - self.mean) / ls).astype(self.dtype)
+		return self._z
+
+	def rows(self, idx) -> np.ndarray:
+		"""Rows `idx` of A in float64, from the definition (norms plus dot product, clamped, exact zeros on the diagonal)."""
+		idx = np.asarray(idx, dtype=np.int64).ravel()
+		z = self.scaled_points().astype(np.float64)
+		nrm = np.einsum("ij,ij->i", z, z)
+		r2 = np.maximum(nrm[idx, None] + nrm[None, :] - 2.0 * (z[idx] @ z.T), 0.0)
+		r2[np.arange(idx.size), idx] = 0.0
+		K = self.outputscale * _kernel_profile(self.kernel, r2)
+		K[np.arange(idx.size), idx] += self.noise
+		return K
+
+	def _matmat(self, X: np.ndarray) -> np.ndarray:
+		X = np.asarray(X)
+		if X.ndim != 2 or X.shape[0] != self.shape[1]:
+			raise ValueError(f"dimension mismatch: the operator is {self.shape[0]} x {self.shape[1]}, the operand has {X.shape[0]} rows")
+		n = self.shape[0]
+		Y = np.empty((n, X.shape[1]), dtype=np.float64)
+		X64 = X.astype(np.float64, copy=False)
+		for i0 in range(0, n, 1024):
+			i1 = min(n, i0 + 1024)
+			Y[i0:i1] = self.rows(np.arange(i0, i1)) @ X64
+		return Y.astype(self.dtype, copy=False)
+
+	def _matvec(self, x: np.ndarray) -> np.ndarray:
+		x = np.asarray(x)
+		if x.size != self.shape[1]:
+			raise ValueError(f"dimension mismatch: the operator is {self.shape[0]} x {self.shape[1]}, the operand has {x.size} entries")
+		return self._matmat(x.reshape(-1, 1)).ravel()
+
+	def _adjoint(self):
+		return self
+
+
 class Toeplitz(LinearOperator):
 	"""Matrix-free symmetric-or-not Toeplitz operator with first column `c` and first row `r` (default r = c),
 	applied by circulant embedding and two FFTs of length 2n (src/primate/operators.py:165-183). A host-side
