@@ -168,6 +168,9 @@ int slq_kernel_get_parameters(const slq_operator *op, int *d, int *profile, doub
  * of the slabs in [0, n] (then -1); nout >= 22. */
 int slq_debug_kernel_points(slq_operator *op, void *zt, void *nrm, void *params);
 int slq_debug_kernel_schedule(int64_t n, int panel_width, int panels, int num_cus, int64_t *out, int nout);
+/* Bytes of device memory the process's operators (and the scratch of operator builds in flight) hold now: back where it was once
+ * every operator created since has been destroyed (tests). No HIP call. */
+int slq_debug_operator_device_bytes(int64_t *live);
 /* Dense symmetric n x n, column-major with leading dimension lda (host array, copied). */
 int slq_dense_create(slq_context *ctx, int dtype, int64_t n, const void *A, int64_t lda,
                      slq_operator **out);

@@ -65,6 +65,7 @@ _SIGNATURES = {
 	"slq_kernel_get_parameters": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), _P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 	"slq_debug_kernel_points": (C.c_int, [_P, _P, _P, _P]),
 	"slq_debug_kernel_schedule": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+	"slq_debug_operator_device_bytes": (C.c_int, [C.POINTER(C.c_int64)]),
 	"slq_callback_create": (C.c_int, [_P, C.c_int, C.c_int64, MATVEC_FN, _P, _PP]),
 	"slq_operator_destroy": (C.c_int, [_P]),
 	"slq_operator_shape": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),

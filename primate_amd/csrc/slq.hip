@@ -17,6 +17,7 @@
 #include <atomic>
 #include <mutex>
 #include <new>
+#include <string>
 #include <system_error>
 #include <thread>
 #include <type_traits>
@@ -37,6 +38,7 @@
 #include "slq_cheb.hpp"      // Chebyshev moments: the kernels of slq_plan_run_chebyshev, _moment_sum, slq_density_update_moments
 #include "slq_sddmm.hpp"     // sampled dense-dense product on a CSR pattern: schedule (sddmm_schedule) and kernel of slq_sddmm_*
 #include "slq_kernelop.hpp"  // matrix-free kernel operator (slq_kernel_*): validation, schedule, k_kernel_rescale, k_kernel_panel
+#include "slq_operator.hpp"  // the operator handle and the values it owns (DevBuf, CsrArrays, TileStream)
 
 using namespace slq;
 
@@ -107,65 +109,7 @@ static void ctx_release(slq_context *ctx) {
 // (OP_CSR .. OP_KERNEL, the kinds of an operator: slq_plan_shape.hpp)
 static_assert(kF32 == SLQ_F32 && kF64 == SLQ_F64, "slq_plan_shape.hpp: the dtype codes of include/slq.h");
 
-struct slq_operator {
-  slq_context *ctx;
-  int kind, dtype;
-  int64_t n, nnz;
-  int32_t *rowptr, *colind;
-  void *vals;   // CSR values or dense matrix (device)
-  int64_t lda;
-  bool owns;
-  slq_matvec_fn fn;
-  void *user;
-  int32_t *perm_d;               // device: stored row i = caller row perm[i]; null if not reordered
-  std::vector<int32_t> *perm_h;  // host copy (diag un-permutation)
-  TileMeta tiles;                // workgroup LDS tiles of the fused passes (tile_ptr == null: none; SLQ_TILES)
-  bool tiles_ringed = false;     // ... built to the caps of k_csr_ring_pass (SLQ_TILES=2), which reads these two:
-  int32_t *inv_perm_d = nullptr; // device: caller row r is stored row inv_perm[r] (null if not reordered)
-  int32_t *tile_desc = nullptr;  // 64 words per tile
-  char *tile_rec = nullptr;      // the tiles' CSR records
-  int32_t *tile_desc_u = nullptr;  // the same over the upper triangle (exactly symmetric operators): the alpha-only pass
-  char *tile_rec_u = nullptr;
-  int32_t xcd_tile_u[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // tile ranges of the upper-triangle stream, whose tiles are runs of the base tiles (regroup_upper_tiles, r04)
-  size_t tile_desc_bytes = 0, tile_rec_bytes = 0, tile_desc_u_bytes = 0, tile_rec_u_bytes = 0;  // (what SLQ_DEVICE_BUILD=2 compares)
-  int tile_max_lines_u = 0;        // longest line list of a tile in that stream (short lists: a ring geometry with one slot more)
-  bool tile_u_padded = false;      // ... with every row's entries padded to a multiple of four (build_ring_stream: pad_rows)
-  double upper_per_row = 0.0;      // distinct panel rows per row that stream lands (what decides whether the alpha-only pass takes it)
-  // narrow panels (slq_ring.hpp): R = 2, 4 consecutive tiles merged into one, built the first time a plan asks for them
-  // (ensure_ring_stream); [0] R = 2, [1] R = 4; *_u over the upper triangle where the operator has that stream
-  struct MergedStream {
-    bool u_padded = false;  // the upper stream's rows are padded to whole chunks (build_ring_stream: pad_rows)
-    int32_t *desc = nullptr, *desc_u = nullptr;
-    char *rec = nullptr, *rec_u = nullptr;
-    int32_t xcd_tile[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int max_lines = 0, max_lines_u = 0;  // longest line lists (full rows / upper triangle)
-    bool tried = false;
-  } merged[2];
-  std::mutex *merged_lock = nullptr;
-  // exactly symmetric CSR only: upper triangle (diagonal + 2x strict upper) for the alpha pass, whose
-  // q^T A q = sum_i q_i (a_ii q_i + 2 sum_{j>i} a_ij q_j) then gathers half the panel rows (null: none)
-  int32_t *rowptr_u = nullptr, *colind_u = nullptr;
-  void *vals_u = nullptr;
-  slq_matmat_device_fn dev_fn = nullptr;  // OP_DEVICE_CALLBACK: Y = A X on device buffers, enqueued on our stream
-  double rms_dist = -1.0;  // rms |i - j| over the stored nonzeros inside an XCD chunk (-1: unknown)
-  int64_t nnz_u = 0;       // entries of the upper-triangle copy
-  double far_per_row = 0.0;  // stored nonzeros per row with |i - j| > 4096 (0 when unknown: device-resident CSR)
-  double norm_inf = -1.0;    // largest absolute row sum of a CSR operator (-1: not taken yet; operator_norm_inf takes it once, on the device)
-  // OP_GRAM (x -> A^T (A x), A is mrows x n): rowptr/colind/vals hold A, the *_t arrays its transpose (n rows)
-  int64_t mrows = 0;
-  int32_t *rowptr_t = nullptr, *colind_t = nullptr;
-  // affine CSR operator A + t B (slq_csr_affine_create): values of A and B on the union pattern (vals = va + t vb)
-  void *vals_a = nullptr, *vals_b = nullptr;
-  void *vals_t = nullptr;    // OP_DENSE, non-symmetric input only (also the values of A^T for OP_GRAM): the transpose, for the kernel that walks A by columns (null: A == A^T)
-  OperatorSwitches sw;       // the switches as they were when the operator was created (slq_switches.hpp)
-  // OP_KERNEL (slq_kernelop.hpp): the raw points (n x d), z transposed (dpad x npad) and |z|^2 (npad), s and sigma2 in two device
-  // words - all at addresses that never change, so that a captured graph sees a hyperparameter change. nnz reports n d.
-  int k_d = 0, k_dpad = 0, k_profile = 0;
-  int64_t k_npad = 0;
-  void *k_raw = nullptr, *k_zt = nullptr, *k_nrm = nullptr, *k_params = nullptr;  // (one allocation, k_raw its base)
-  KernelScale *k_scale = nullptr;  // host: the centre of the points and the lengthscales per dimension
-  double k_s = 1.0, k_noise = 0.0;
-};
+// (slq_operator, the handle of an operator, and the values it owns - DevBuf, CsrArrays, TileStream: slq_operator.hpp)
 
 struct ProfEvent {
   hipEvent_t a, b;
@@ -235,12 +179,10 @@ struct slq_plan {
   bool ring_deep;             // steps with 4..8 ring columns run k_ring_pass with 8 waves (SLQ_RING_DEEP; else the generic passes)
   bool gram;                  // steps with 1..8 ring columns take their projections from Gram rows of the update passes (SLQ_GRAM)
   bool gram_csr;              // ... also where the plan's fused passes are the generic ones (k_csr_pass<PASS_UPDATEG>: narrow panels, small operators; SLQ_GRAM_CSR, r04)
-  const int32_t *rs_desc, *rs_desc_u;  // the stream the plan's ring-fed passes read (full rows / upper triangle or null)
-  const char *rs_rec, *rs_rec_u;
-  bool rs_u_padded;            // ... whose rows are padded to whole chunks of four entries (the alpha-only pass's branch-free consumer)
-  int32_t rs_xcd[9];
-  int32_t rs_xcd_u[9];         // ... and of the upper-triangle stream (its tiles are runs of the base tiles)
-  bool ring_staged;           // the alpha-only pass's loaders go through registers (SLQ_RING_STAGED; slq_ring.hpp: GEO 1)
+  // the operator's streams the plan's ring-fed passes read: full rows / upper triangle or null (their tile ranges and the upper
+  // stream's padding are the shape's: rs_xcd, rs_xcd_u, rs_u_padded)
+  const TileStream *rs_full = nullptr, *rs_upper = nullptr;
+  bool ring_staged;          // the alpha-only pass's loaders go through registers (SLQ_RING_STAGED; slq_ring.hpp: GEO 1)
   int part_maxblk = 0;        // blocks per slab of `part`
   bool launch_error = false;  // a launcher declined (mis-dispatch): the run is invalid (enqueue_run)
   bool sweep_skip = true;     // the update sweep does not read ring columns whose coefficient is zero for every probe of the panel (SLQ_SWEEP_SKIP=0: reads them all)
@@ -433,27 +375,6 @@ static int check_dtype(int dtype) {
 
 
 // ---- derived data built on the device (slq_build.hpp) ----
-struct DevBuf {  // device scratch of a build, freed when the build is left
-  void *p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) hipFree(p);
-    p = nullptr;
-  }
-  hipError_t alloc(size_t bytes) {
-    release();
-    return hipMalloc(&p, std::max<size_t>(bytes, 16));
-  }
-  template <typename T> T *as() const { return (T *)p; }
-  void *take() {
-    void *q = p;
-    p = nullptr;
-    return q;
-  }
-};
 // a[0, count) := its inclusive scan (the callers keep a zero in front of it: row pointers, record offsets)
 static hipError_t device_scan_inclusive(int32_t *a, int64_t count, hipStream_t st) {
   if (count <= 0) return hipSuccess;
@@ -468,22 +389,13 @@ static hipError_t device_scan_inclusive(int32_t *a, int64_t count, hipStream_t s
   if (e == hipSuccess) e = hipStreamSynchronize(st);  // (sums is freed on return)
   return e;
 }
-struct DeviceStream {  // what device_build_stream hands back (the caller owns desc, rec, tile_ptr)
-  int32_t *desc = nullptr;
-  char *rec = nullptr;
-  int32_t *tile_ptr = nullptr;  // [ntiles + 1] running sum of the lists' lengths (only if asked for)
-  size_t desc_bytes = 0, rec_bytes = 0;
-  int max_lines = 0;
-  int64_t sum_lines = 0;
-  bool padded = false;
-};
 // The descriptor / record stream of R-merged tiles `tile_row_d` (device, ntiles + 1) over the CSR (rp, ci, va) (device): what
 // build_tile_meta + build_ring_stream produce on the host, byte for byte. want_pad: rows padded to whole chunks of four entries
 // unless some record would outgrow its slot (out.padded tells). max_lines_per_row > 0: nothing is built (return 1) when the tiles
-// land more distinct panel rows per row than that; out.max_lines / out.sum_lines are set either way. 0: built; < 0: failed
-// (the SLQ status).
+// land more distinct panel rows per row than that; out.max_lines / *sum_lines are set either way. tile_ptr (optional): [ntiles + 1]
+// running sum of the lists' lengths. 0: built; < 0: failed (the SLQ status). out.xcd_tile is the caller's to set.
 static int device_build_stream(slq_context *ctx, int dtype, int R, int64_t n, const int32_t *rp, const int32_t *ci, const void *va, const int32_t *tile_row_d,
-                               int ntiles, bool want_pad, double max_lines_per_row, bool keep_tile_ptr, DeviceStream &out) {
+                               int ntiles, bool want_pad, double max_lines_per_row, TileStream &out, int64_t *sum_lines = nullptr, DevBuf *tile_ptr = nullptr) {
   hipStream_t st = ctx->stream;
   const int cap = kRingTileCols * R;
   const int es = (int)esize(dtype);
@@ -518,15 +430,16 @@ static int device_build_stream(slq_context *ctx, int dtype, int R, int64_t n, co
   if (e == hipSuccess) e = hipMemcpyAsync(&totals[1], u + ntiles, 4, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return fail(SLQ_EHIP, "tile stream offsets: %s", hipGetErrorString(e));
-  out.sum_lines = totals[0];
-  if (max_lines_per_row > 0.0 && (double)totals[0] / (double)n > max_lines_per_row) return 1;
-  DevBuf desc, rec, tptr;
-  out.desc_bytes = (size_t)ntiles * 64 * R * 4;
-  out.rec_bytes = (size_t)totals[1] * 16 + (size_t)kRingMetaBytes * R;
-  e = desc.alloc(out.desc_bytes);
-  if (e == hipSuccess) e = rec.alloc(out.rec_bytes);
-  if (e == hipSuccess && keep_tile_ptr) e = tptr.alloc(cnt * 4);
-  if (e == hipSuccess && keep_tile_ptr) e = hipMemcpyAsync(tptr.p, D, cnt * 4, hipMemcpyDeviceToDevice, st);
+  if (sum_lines) *sum_lines = totals[0];
+  if (max_lines_per_row > 0.0 && (double)totals[0] / (double)n > max_lines_per_row) {
+    out.padded = false;
+    return 1;
+  }
+  DevBuf &desc = out.desc, &rec = out.rec;
+  e = desc.alloc((size_t)ntiles * 64 * R * 4);
+  if (e == hipSuccess) e = rec.alloc((size_t)totals[1] * 16 + (size_t)kRingMetaBytes * R);
+  if (e == hipSuccess && tile_ptr) e = tile_ptr->alloc(cnt * 4);
+  if (e == hipSuccess && tile_ptr) e = hipMemcpyAsync(tile_ptr->p, D, cnt * 4, hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess) e = hipMemsetAsync(rec.as<char>() + (size_t)totals[1] * 16, 0, (size_t)kRingMetaBytes * R, st);  // the spare record behind the last one
   if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "tile stream: %s", hipGetErrorString(e));
   const dim3 gs((unsigned)((ntiles + 3) / 4));
@@ -546,9 +459,6 @@ static int device_build_stream(slq_context *ctx, int dtype, int R, int64_t n, co
   e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(st);  // (the scratch goes when this returns)
   if (e != hipSuccess) return fail(SLQ_EHIP, "tile stream: %s", hipGetErrorString(e));
-  out.desc = (int32_t *)desc.take();
-  out.rec = (char *)rec.take();
-  out.tile_ptr = keep_tile_ptr ? (int32_t *)tptr.take() : nullptr;
   return 0;
 }
 // the same bytes on the device and on the host / twice on the device (null pointers: equal when both are) - what SLQ_DEVICE_BUILD=2 compares
@@ -561,6 +471,15 @@ static bool device_equals_device(const void *x, const void *y, size_t bytes) {
   if (!x || !y) return x == y;
   std::vector<char> hx(bytes);
   return hipMemcpy(hx.data(), x, bytes, hipMemcpyDeviceToHost) == hipSuccess && device_equals_host(y, hx.data(), bytes);
+}
+static bool buffers_equal(const DevBuf &x, const DevBuf &y) { return x.bytes() == y.bytes() && device_equals_device(x.p, y.p, x.bytes()); }
+// 0 when two tile streams are the same, else what differs first: 1 one is built and the other is not, or their sizes, tile ranges,
+// longest lists or padding; 2 the descriptors; 3 the records
+static int streams_differ(const TileStream &a, const TileStream &b) {
+  if ((bool)a != (bool)b || a.desc.bytes() != b.desc.bytes() || a.rec.bytes() != b.rec.bytes()) return 1;
+  if (!std::equal(a.xcd_tile, a.xcd_tile + 9, b.xcd_tile) || a.max_lines != b.max_lines || a.padded != b.padded) return 1;
+  if (!buffers_equal(a.desc, b.desc)) return 2;
+  return buffers_equal(a.rec, b.rec) ? 0 : 3;
 }
 
 // No C++ exception crosses the C boundary: every slq_*_create whose body allocates on the host runs it through here, and
@@ -577,6 +496,22 @@ template <typename Body> static int create_guarded(slq_operator **out, Body body
     return fail(SLQ_EHIP, "operator analysis failed: %s", e.what());
   }
 }
+// What every slq_*_create begins with: the arguments every kind shares are checked, the context's device is made current, and a new
+// operator of `kind` holds the context and the switches as they are now (the one read of a creation). The caller puts it in an OpGuard.
+static int operator_new(slq_context *ctx, int kind, int dtype, int64_t n, int64_t nnz, slq_operator **out, slq_operator **op) {
+  if (!ctx || !out) return fail(SLQ_EINVAL, "ctx/out is NULL");
+  *out = nullptr;
+  SLQ_TRY(check_dtype(dtype));
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->dead) return fail(SLQ_EINVAL, "the context has been destroyed");
+  slq_operator *o = new (std::nothrow) slq_operator();
+  if (!o) return fail(SLQ_ENOMEM, "host allocation failed");
+  ctx_retain(ctx);
+  o->ctx = ctx, o->kind = kind, o->dtype = dtype, o->n = n, o->nnz = nnz;
+  o->sw = read_operator_switches();
+  *op = o;
+  return SLQ_OK;
+}
 struct OpGuard {  // (declare it BEFORE an upload queue that fills the operator's arrays: that one joins first)
   slq_operator *op;
   ~OpGuard() {
@@ -588,16 +523,6 @@ struct OpGuard {  // (declare it BEFORE an upload queue that fills the operator'
     return o;
   }
 };
-// colind/vals of a stored CSR carry kCsrPad spare entries: the batched row gather (slq_kernels.hpp: gather_row_uniform)
-// loads indices and values 8 at a time and may read (never use) up to 7 entries past a row's end. The pad is cleared on `st`.
-static hipError_t alloc_padded_csr(int32_t **colind, void **vals, size_t nnz, size_t es, hipStream_t st) {
-  hipError_t e = hipMalloc((void **)colind, (nnz + kCsrPad) * 4);
-  if (e == hipSuccess) e = hipMalloc(vals, (nnz + kCsrPad) * es);
-  if (e == hipSuccess) e = hipMemsetAsync(*colind + nnz, 0, kCsrPad * 4, st);
-  if (e == hipSuccess) e = hipMemsetAsync((char *)*vals + nnz * es, 0, kCsrPad * es, st);
-  return e;
-}
-
 // plain != 0: rows stay in the caller's order and no derived copy (upper triangle, tiles) is built - for operators whose
 // values change after creation (the affine operator)
 // dev: the same CSR already on the device (slq_csr_create_device): the device-side build reads it in place, and `vals` may then be null
@@ -620,7 +545,7 @@ extern "C" int slq_csr_create(slq_context *ctx, int dtype, int64_t n, int64_t nn
 static void debug_stored_csr(const slq_operator *op, const char *how) {
   if (op->sw.debug != 0)
     fprintf(stderr, "[slq] csr n=%lld nnz=%lld reordered=%d rms in-chunk |i-j| = %.1f, far gathers per row %.2f%s\n", (long long)op->n,
-            (long long)op->nnz, op->perm_h ? 1 : 0, op->rms_dist, op->far_per_row, how);
+            (long long)op->nnz, op->perm_h.empty() ? 0 : 1, op->rms_dist, op->far_per_row, how);
 }
 static void debug_upper_tiles(const slq_operator *op, size_t ntu, size_t ntiles) {
   if (op->sw.debug != 0)
@@ -629,8 +554,40 @@ static void debug_upper_tiles(const slq_operator *op, size_t ntu, size_t ntiles)
 }
 static void debug_upper_lists(const slq_operator *op) {
   if (op->sw.debug != 0)
-    fprintf(stderr, "[slq] tiles: upper triangle: %.2f distinct panel rows per row, longest list %d (full rows: %d)\n", op->upper_per_row, op->tile_max_lines_u,
-            op->tiles.max_cols);
+    fprintf(stderr, "[slq] tiles: upper triangle: %.2f distinct panel rows per row, longest list %d (full rows: %d)\n", op->upper_per_row,
+            op->streams[0].upper.max_lines, op->tiles.max_cols);
+}
+
+// The host side of one tile stream: the tiles' lists (build_tile_meta) and the stream made of them, which an upload reads - so it
+// outlives the wait for the queue the upload was pushed into (declare it BEFORE that queue).
+struct HostStream {
+  std::vector<int32_t> tp, tc, lc, si;
+  int max_cols = 0;
+  RawBuf<int32_t> desc;
+  RawBuf<char> rec;
+};
+struct HostCsr { const int32_t *rowptr, *colind; const void *vals; };
+// The stream of the R-merged tiles `tile_row` over a CSR on the host: lists, descriptors and records (build_tile_meta +
+// build_ring_stream), their device arrays in `out`, the upload pushed into `up`; h keeps the lists for whoever needs them. As with
+// device_build_stream, out.max_lines is set either way, want_pad asks for padded rows (out.padded tells), out.xcd_tile is the
+// caller's to set, and `out` stays empty when the tiles land more than max_lines_per_row (> 0) distinct panel rows per row - or
+// when a list outgrows the ring's cap.
+static hipError_t host_build_stream(const slq_operator *op, int R, const HostCsr &A, const std::vector<int32_t> &tile_row, bool want_pad, double max_lines_per_row,
+                                    HostStream &h, UploadQueue &up, TileStream &out, PhaseClock *clk = nullptr, const char *what = "") {
+  build_tile_meta(op->n, A.rowptr, A.colind, tile_row, h.tp, h.tc, h.lc, h.si, &h.max_cols, op->sw);
+  if (clk) clk->lap((std::string("  ") + what + "tile lists").c_str());
+  out.max_lines = h.max_cols;
+  if (h.max_cols > kRingTileCols * R) return hipSuccess;
+  if (max_lines_per_row > 0.0 && (double)(h.tc.size() - kCsrPad) / (double)op->n > max_lines_per_row) return hipSuccess;
+  bool pad = want_pad;
+  if (op->dtype == SLQ_F64) build_ring_stream<double>(R, A.rowptr, (const double *)A.vals, tile_row, h.tp, h.tc, h.lc, h.si, h.desc, h.rec, &pad);
+  else build_ring_stream<float>(R, A.rowptr, (const float *)A.vals, tile_row, h.tp, h.tc, h.lc, h.si, h.desc, h.rec, &pad);
+  out.padded = pad;
+  if (clk) clk->lap((std::string("  ") + what + "tile stream").c_str());
+  hipError_t e = out.desc.alloc(h.desc.size() * 4);
+  if (e == hipSuccess) e = out.rec.alloc(h.rec.size());
+  if (e == hipSuccess) up.push({{out.desc.p, h.desc.data(), h.desc.size() * 4}, {out.rec.p, h.rec.data(), h.rec.size()}});
+  return e;
 }
 
 // An operator's storage built on the host from its layout: the permuted CSR, the far-gather count, the upper triangle, the tile
@@ -647,21 +604,19 @@ static int build_storage_host(slq_context *ctx, slq_operator *op, const CsrView 
   RawBuf<char> va2;
   std::vector<int32_t> urp, uci;                  // the upper triangle (stored order), also the source of the alpha-only tile stream
   std::vector<char> uva;
-  std::vector<int32_t> tp, tc, lc, si, tpu, tcu, lcu, siu;
-  RawBuf<int32_t> desc, desc_u;  // (the upper stream in buffers of its own: the full stream's upload is still running when it is built)
-  RawBuf<char> rec, rec_u;
+  HostStream hs, hsu;  // (the upper stream in buffers of its own: the full stream's upload is still running when it is built)
   UploadQueue up(ctx->device);
   auto bail = [&](int code, const char *what, hipError_t e) {
     up.wait();
     hipStreamSynchronize(ctx->stream);
     return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : code, "%s: %s", what, hipGetErrorString(e));
   };
-  if (op->perm_h) {
-    const std::vector<int32_t> &perm = *op->perm_h, &inv = L.inv, &rp2 = L.rowptr_stored;
-    hipError_t pe = hipMalloc((void **)&op->perm_d, (size_t)n * 4);
-    if (pe == hipSuccess) pe = hipMalloc((void **)&op->inv_perm_d, (size_t)n * 4);
+  if (!op->perm_h.empty()) {
+    const std::vector<int32_t> &perm = op->perm_h, &inv = L.inv, &rp2 = L.rowptr_stored;
+    hipError_t pe = op->perm_d.alloc((size_t)n * 4);
+    if (pe == hipSuccess) pe = op->inv_perm_d.alloc((size_t)n * 4);
     if (pe != hipSuccess) return bail(SLQ_EHIP, "permutation upload", pe);
-    up.push({{op->perm_d, perm.data(), (size_t)n * 4}, {op->inv_perm_d, inv.data(), (size_t)n * 4}});
+    up.push({{op->perm_d.p, perm.data(), (size_t)n * 4}, {op->inv_perm_d.p, inv.data(), (size_t)n * 4}});
     ci2.alloc((size_t)nnz);
     va2.alloc((size_t)nnz * es);
     const bool pok = parallel_pieces(host_threads(), n, [&](int, int64_t i0, int64_t i1) {
@@ -687,10 +642,9 @@ static int build_storage_host(slq_context *ctx, slq_operator *op, const CsrView 
     vals = va2.data();
   }
   clk.lap("permuted CSR");
-  hipError_t e = hipMalloc((void **)&op->rowptr, (size_t)(n + 1) * 4);
-  if (e == hipSuccess) e = alloc_padded_csr(&op->colind, &op->vals, (size_t)nnz, es, ctx->stream);
+  hipError_t e = op->csr.alloc(n, nnz, es, ctx->stream);
   if (e != hipSuccess) return bail(SLQ_EHIP, "CSR upload", e);
-  up.push({{op->rowptr, rowptr, (size_t)(n + 1) * 4}, {op->colind, colind, (size_t)nnz * 4}, {op->vals, vals, (size_t)nnz * es}});
+  up.push({{op->csr.rowptr.p, rowptr, (size_t)(n + 1) * 4}, {op->csr.colind.p, colind, (size_t)nnz * 4}, {op->csr.vals.p, vals, (size_t)nnz * es}});
   {
     // gathers per row that reach further than any cache-resident halo (|i - j| > 4096 rows in the stored
     // order): what decides between the recompute passes and the store-and-revisit sweeps (enqueue_run)
@@ -717,89 +671,58 @@ static int build_storage_host(slq_context *ctx, slq_operator *op, const CsrView 
                                 : build_symmetric_upper<float>(n, rowptr, colind, (const float *)vals, urp, uci, uva);
     if (sym) {
       const size_t nu = uci.size();
-      op->nnz_u = (int64_t)nu;
-      hipError_t ue = hipMalloc((void **)&op->rowptr_u, (size_t)(n + 1) * 4);
-      if (ue == hipSuccess) ue = alloc_padded_csr(&op->colind_u, &op->vals_u, nu, es, ctx->stream);
+      const hipError_t ue = op->upper.alloc(n, (int64_t)nu, es, ctx->stream);
       if (ue != hipSuccess) return bail(SLQ_EHIP, "upper-triangle upload", ue);
-      up.push({{op->rowptr_u, urp.data(), (size_t)(n + 1) * 4}, {op->colind_u, uci.data(), nu * 4}, {op->vals_u, uva.data(), nu * es}});
+      up.push({{op->upper.rowptr.p, urp.data(), (size_t)(n + 1) * 4}, {op->upper.colind.p, uci.data(), nu * 4}, {op->upper.vals.p, uva.data(), nu * es}});
     }
   }
   clk.lap("upper triangle");
   // workgroup tiles (SLQ_TILES): lists of the stored CSR, uploaded next to it
   if (L.have_tiles) {
-    int mx = 0;
-    build_tile_meta(n, rowptr, colind, tile_row, tp, tc, lc, si, &mx, osw);
-    clk.lap("  tile lists");
-    int32_t *d_tr = nullptr, *d_tp = nullptr, *d_tc = nullptr, *d_lc = nullptr, *d_si = nullptr;
-    // (the per-nonzero lists are read by k_csr_tile_pass only: ring-sized tiles carry them inside their records instead)
-    const bool lists_on_device = osw.tiles != 2;
-    hipError_t te = hipMalloc((void **)&d_tr, tile_row.size() * 4);
-    if (te == hipSuccess) te = hipMalloc((void **)&d_tp, tp.size() * 4);
-    if (te == hipSuccess && lists_on_device) te = hipMalloc((void **)&d_tc, tc.size() * 4);
-    if (te == hipSuccess && lists_on_device) te = hipMalloc((void **)&d_lc, lc.size() * 4);
-    if (te == hipSuccess && lists_on_device) te = hipMalloc((void **)&d_si, si.size() * 4);
-    op->tiles.tile_row = d_tr;
-    op->tiles.tile_ptr = d_tp;
-    op->tiles.tile_cols = d_tc;
-    op->tiles.lcol = d_lc;
-    op->tiles.self_idx = d_si;
-    if (te == hipSuccess) {
-      std::vector<UploadQueue::Job> jobs = {{d_tr, tile_row.data(), tile_row.size() * 4}, {d_tp, tp.data(), tp.size() * 4}};
-      if (lists_on_device) {
-        jobs.push_back({d_tc, tc.data(), tc.size() * 4});
-        jobs.push_back({d_lc, lc.data(), lc.size() * 4});
-        jobs.push_back({d_si, si.data(), si.size() * 4});
-      }
-      up.push(std::move(jobs));
-    }
-    for (int x = 0; x < 9; ++x) op->tiles.xcd_tile[x] = L.xcd_tile[x];
-    op->tiles.max_cols = mx;
+    slq_operator::TileLists &T = op->tiles;
+    TileStreamPair &base = op->streams[0];
     op->tiles_ringed = osw.tiles == 2;
-    if (op->tiles_ringed) op->merged_lock = new (std::nothrow) std::mutex();
-    if (te == hipSuccess && op->tiles_ringed) {
-      if (dtype == SLQ_F64) build_ring_stream<double>(1, rowptr, (const double *)vals, tile_row, tp, tc, lc, si, desc, rec);
-      else build_ring_stream<float>(1, rowptr, (const float *)vals, tile_row, tp, tc, lc, si, desc, rec);
-      clk.lap("  tile stream");
-      te = hipMalloc((void **)&op->tile_desc, desc.size() * 4);
-      if (te == hipSuccess) te = hipMalloc((void **)&op->tile_rec, rec.size());
-      op->tile_desc_bytes = desc.size() * 4, op->tile_rec_bytes = rec.size();
-      if (te == hipSuccess) up.push({{op->tile_desc, desc.data(), desc.size() * 4}, {op->tile_rec, rec.data(), rec.size()}});
-      if (te == hipSuccess && sym) {
-        // the same tiles over the upper triangle (doubled off-diagonals), for the alpha-only pass: a tile's image then holds its
-        // own rows and the neighbours of HIGHER index only - about half the halo, and the pass is bound by what it lands by DMA
-        int mxu = 0;
-        // (its own, longer tiles: runs of the base tiles - the pass pays per tile, regroup_upper_tiles; SLQ_RING_UPPER_REGROUP=0 keeps the base tiles)
-        std::vector<int32_t> tile_row_u;
-        if (regroup_upper_wanted(osw, n, tile_row.size() - 1)) {
-          regroup_upper_tiles(urp.data(), uci.data(), tile_row, L.xcd_tile, tile_row_u, op->xcd_tile_u);
-        } else {
-          tile_row_u = tile_row;
-          for (int x = 0; x < 9; ++x) op->xcd_tile_u[x] = L.xcd_tile[x];
-        }
-        debug_upper_tiles(op, tile_row_u.size() - 1, tile_row.size() - 1);
-        build_tile_meta(n, urp.data(), uci.data(), tile_row_u, tpu, tcu, lcu, siu, &mxu, osw);
-        clk.lap("  upper tile lists");
-        // Worth it while the tiles land at most kTileAlphaColsPerRow panel rows per row (r03, scalar-descriptor loaders and the
-        // padded-row consumer of slq_ring.hpp: 5-point grid, 1.5 rows per row: 0.40 against 0.51 ms for the generic pass; 7-point
-        // grid, 2.5: 0.66 against 0.81 ms)
-        op->tile_max_lines_u = mxu;
-        op->upper_per_row = (double)(tcu.size() - kCsrPad) / (double)n;
-        debug_upper_lists(op);
-        // (built up to kTileAlphaMergedColsPerRow: wide panels take it up to kTileAlphaColsPerRow, slq_plan_create; the merged
-        // tiles of narrow panels share more of their halo and gain from it on 7-point grids too - 100^3, 64 probes: alpha pass
-        // 0.25 against 0.35 ms for the generic upper-triangle pass)
-        if (op->upper_per_row <= kTileAlphaMergedColsPerRow) {
-          bool pad = osw.ring_pad_rows != 0;
-          if (dtype == SLQ_F64) build_ring_stream<double>(1, urp.data(), (const double *)uva.data(), tile_row_u, tpu, tcu, lcu, siu, desc_u, rec_u, &pad);
-          else build_ring_stream<float>(1, urp.data(), (const float *)uva.data(), tile_row_u, tpu, tcu, lcu, siu, desc_u, rec_u, &pad);
-          op->tile_u_padded = pad;
-          clk.lap("  upper tile stream");
-          te = hipMalloc((void **)&op->tile_desc_u, desc_u.size() * 4);
-          if (te == hipSuccess) te = hipMalloc((void **)&op->tile_rec_u, rec_u.size());
-          op->tile_desc_u_bytes = desc_u.size() * 4, op->tile_rec_u_bytes = rec_u.size();
-          if (te == hipSuccess) up.push({{op->tile_desc_u, desc_u.data(), desc_u.size() * 4}, {op->tile_rec_u, rec_u.data(), rec_u.size()}});
-        }
+    hipError_t te = hipSuccess;
+    if (op->tiles_ringed) {
+      te = host_build_stream(op, 1, HostCsr{rowptr, colind, vals}, tile_row, false, 0.0, hs, up, base.full, &clk);
+    } else {
+      build_tile_meta(n, rowptr, colind, tile_row, hs.tp, hs.tc, hs.lc, hs.si, &hs.max_cols, osw);
+      clk.lap("  tile lists");
+    }
+    if (te == hipSuccess) te = T.tile_row.alloc(tile_row.size() * 4);
+    if (te == hipSuccess) te = T.tile_ptr.alloc(hs.tp.size() * 4);
+    if (te == hipSuccess) up.push({{T.tile_row.p, tile_row.data(), tile_row.size() * 4}, {T.tile_ptr.p, hs.tp.data(), hs.tp.size() * 4}});
+    // (the per-nonzero lists are read by k_csr_tile_pass only: ring-sized tiles carry them inside their records instead)
+    if (te == hipSuccess && !op->tiles_ringed) te = T.tile_cols.alloc(hs.tc.size() * 4);
+    if (te == hipSuccess && !op->tiles_ringed) te = T.lcol.alloc(hs.lc.size() * 4);
+    if (te == hipSuccess && !op->tiles_ringed) te = T.self_idx.alloc(hs.si.size() * 4);
+    if (te == hipSuccess && !op->tiles_ringed)
+      up.push({{T.tile_cols.p, hs.tc.data(), hs.tc.size() * 4}, {T.lcol.p, hs.lc.data(), hs.lc.size() * 4}, {T.self_idx.p, hs.si.data(), hs.si.size() * 4}});
+    std::copy(L.xcd_tile, L.xcd_tile + 9, T.xcd_tile);
+    std::copy(L.xcd_tile, L.xcd_tile + 9, base.full.xcd_tile);
+    T.max_cols = hs.max_cols;
+    if (te == hipSuccess && op->tiles_ringed && sym) {
+      // the same tiles over the upper triangle (doubled off-diagonals), for the alpha-only pass: a tile's image then holds its
+      // own rows and the neighbours of HIGHER index only - about half the halo, and the pass is bound by what it lands by DMA
+      // (its own, longer tiles: runs of the base tiles - the pass pays per tile, regroup_upper_tiles; SLQ_RING_UPPER_REGROUP=0 keeps the base tiles)
+      std::vector<int32_t> tile_row_u;
+      if (regroup_upper_wanted(osw, n, tile_row.size() - 1)) {
+        regroup_upper_tiles(urp.data(), uci.data(), tile_row, L.xcd_tile, tile_row_u, base.upper.xcd_tile);
+      } else {
+        tile_row_u = tile_row;
+        std::copy(L.xcd_tile, L.xcd_tile + 9, base.upper.xcd_tile);
       }
+      debug_upper_tiles(op, tile_row_u.size() - 1, tile_row.size() - 1);
+      // Worth it while the tiles land at most kTileAlphaColsPerRow panel rows per row (r03, scalar-descriptor loaders and the
+      // padded-row consumer of slq_ring.hpp: 5-point grid, 1.5 rows per row: 0.40 against 0.51 ms for the generic pass; 7-point
+      // grid, 2.5: 0.66 against 0.81 ms)
+      // (built up to kTileAlphaMergedColsPerRow: wide panels take it up to kTileAlphaColsPerRow, slq_plan_create; the merged
+      // tiles of narrow panels share more of their halo and gain from it on 7-point grids too - 100^3, 64 probes: alpha pass
+      // 0.25 against 0.35 ms for the generic upper-triangle pass)
+      te = host_build_stream(op, 1, HostCsr{urp.data(), uci.data(), uva.data()}, tile_row_u, osw.ring_pad_rows != 0, kTileAlphaMergedColsPerRow, hsu, up, base.upper,
+                             &clk, "upper ");
+      op->upper_per_row = (double)(hsu.tc.size() - kCsrPad) / (double)n;
+      debug_upper_lists(op);
     }
     if (te != hipSuccess) return bail(SLQ_EHIP, "tile upload", te);
   }
@@ -819,7 +742,7 @@ static int build_storage_device(slq_context *ctx, slq_operator *op, const CsrVie
   const int64_t n = A.n, nnz = A.nnz;
   const int dtype = op->dtype;
   const size_t es = esize(dtype);
-  const std::vector<int32_t> &perm = *op->perm_h, &tile_row = L.tile_row;
+  const std::vector<int32_t> &perm = op->perm_h, &tile_row = L.tile_row;
   const int ntiles = (int)tile_row.size() - 1;
   const OperatorSwitches &osw = op->sw;
   const bool want_sym = osw.sym_alpha != 0;
@@ -850,34 +773,33 @@ static int build_storage_device(slq_context *ctx, slq_operator *op, const CsrVie
     }
   }
   auto hip_fail = [&](const char *what, hipError_t e) { return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "%s: %s", what, hipGetErrorString(e)); };
-  int32_t *d_tr = nullptr;
-  hipError_t e = hipMalloc((void **)&op->perm_d, (size_t)n * 4);
-  if (e == hipSuccess) e = hipMalloc((void **)&op->inv_perm_d, (size_t)n * 4);
-  if (e == hipSuccess) e = hipMalloc((void **)&op->rowptr, (size_t)(n + 1) * 4);
-  if (e == hipSuccess) e = alloc_padded_csr(&op->colind, &op->vals, (size_t)nnz, es, st);
-  if (e == hipSuccess) e = hipMalloc((void **)&d_tr, tile_row.size() * 4);
-  op->tiles.tile_row = d_tr;
-  if (e == hipSuccess) e = hipMemcpy(op->perm_d, perm.data(), (size_t)n * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(op->inv_perm_d, L.inv.data(), (size_t)n * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(op->rowptr, L.rowptr_stored.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_tr, tile_row.data(), tile_row.size() * 4, hipMemcpyHostToDevice);
+  CsrArrays &S = op->csr, &U = op->upper;
+  DevBuf &d_tr = op->tiles.tile_row;
+  hipError_t e = op->perm_d.alloc((size_t)n * 4);
+  if (e == hipSuccess) e = op->inv_perm_d.alloc((size_t)n * 4);
+  if (e == hipSuccess) e = S.alloc(n, nnz, es, st);
+  if (e == hipSuccess) e = d_tr.alloc(tile_row.size() * 4);
+  if (e == hipSuccess) e = hipMemcpy(op->perm_d.p, perm.data(), (size_t)n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(op->inv_perm_d.p, L.inv.data(), (size_t)n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(S.rowptr.p, L.rowptr_stored.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_tr.p, tile_row.data(), tile_row.size() * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = early.wait();
   if (e != hipSuccess) return hip_fail("CSR upload", e);
   clk.lap("  order, tile boundaries and the caller's CSR on the device");
   const dim3 grow((unsigned)((n + 255) / 256)), brow(256);
-  if (dtype == SLQ_F64) slqb::k_permute_csr<double><<<grow, brow, 0, st>>>((int)n, src.rp, src.ci, (const double *)src.va, op->perm_d, op->inv_perm_d, op->rowptr, op->colind, (double *)op->vals);
-  else slqb::k_permute_csr<float><<<grow, brow, 0, st>>>((int)n, src.rp, src.ci, (const float *)src.va, op->perm_d, op->inv_perm_d, op->rowptr, op->colind, (float *)op->vals);
+  if (dtype == SLQ_F64) slqb::k_permute_csr<double><<<grow, brow, 0, st>>>((int)n, src.rp, src.ci, (const double *)src.va, op->perm_d.as<int32_t>(), op->inv_perm_d.as<int32_t>(), S.rp(), S.colind.as<int32_t>(), S.vals.as<double>());
+  else slqb::k_permute_csr<float><<<grow, brow, 0, st>>>((int)n, src.rp, src.ci, (const float *)src.va, op->perm_d.as<int32_t>(), op->inv_perm_d.as<int32_t>(), S.rp(), S.colind.as<int32_t>(), S.vals.as<float>());
   DevBuf misc;  // [0..1] far gathers (u64), [2] "not symmetric"
   e = misc.alloc(16);
   if (e == hipSuccess) e = hipMemsetAsync(misc.p, 0, 16, st);
   if (e != hipSuccess) return hip_fail("operator analysis", e);
-  slqb::k_far_count<<<grow, brow, 0, st>>>((int)n, op->rowptr, op->colind, misc.as<unsigned long long>());
+  slqb::k_far_count<<<grow, brow, 0, st>>>((int)n, S.rp(), S.ci(), misc.as<unsigned long long>());
   if (want_sym) {
-    e = hipMalloc((void **)&op->rowptr_u, (size_t)(n + 1) * 4);
-    if (e == hipSuccess) e = hipMemsetAsync(op->rowptr_u, 0, 4, st);
+    e = U.rowptr.alloc((size_t)(n + 1) * 4);
+    if (e == hipSuccess) e = hipMemsetAsync(U.rowptr.p, 0, 4, st);
     if (e != hipSuccess) return hip_fail("upper triangle", e);
-    if (dtype == SLQ_F64) slqb::k_sym_count<double><<<grow, brow, 0, st>>>((int)n, op->rowptr, op->colind, (const double *)op->vals, op->rowptr_u, misc.as<int>() + 2);
-    else slqb::k_sym_count<float><<<grow, brow, 0, st>>>((int)n, op->rowptr, op->colind, (const float *)op->vals, op->rowptr_u, misc.as<int>() + 2);
+    if (dtype == SLQ_F64) slqb::k_sym_count<double><<<grow, brow, 0, st>>>((int)n, S.rp(), S.ci(), S.vals.as<double>(), U.rowptr.as<int32_t>(), misc.as<int>() + 2);
+    else slqb::k_sym_count<float><<<grow, brow, 0, st>>>((int)n, S.rp(), S.ci(), S.vals.as<float>(), U.rowptr.as<int32_t>(), misc.as<int>() + 2);
   }
   struct { unsigned long long far; int bad, spare; } h = {0, 0, 0};
   e = hipGetLastError();
@@ -886,58 +808,43 @@ static int build_storage_device(slq_context *ctx, slq_operator *op, const CsrVie
   if (e != hipSuccess) return hip_fail("operator analysis", e);
   op->far_per_row = (double)h.far / (double)n;
   bool sym = want_sym && !h.bad;
-  if (want_sym && !sym) {
-    hipFree(op->rowptr_u);
-    op->rowptr_u = nullptr;
-  }
+  if (!sym) U.release();
   if (sym) {
-    e = device_scan_inclusive(op->rowptr_u + 1, n, st);
+    e = device_scan_inclusive(U.rowptr.as<int32_t>() + 1, n, st);
     int32_t nu32 = 0;
-    if (e == hipSuccess) e = hipMemcpy(&nu32, op->rowptr_u + n, 4, hipMemcpyDeviceToHost);
-    const size_t nu = (size_t)nu32;
-    op->nnz_u = (int64_t)nu;
-    if (e == hipSuccess) e = alloc_padded_csr(&op->colind_u, &op->vals_u, nu, es, st);
+    if (e == hipSuccess) e = hipMemcpy(&nu32, U.rowptr.as<int32_t>() + n, 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = U.alloc_entries((int64_t)nu32, es, st);
     if (e != hipSuccess) return hip_fail("upper triangle", e);
-    if (dtype == SLQ_F64) slqb::k_upper_fill<double><<<grow, brow, 0, st>>>((int)n, op->rowptr, op->colind, (const double *)op->vals, op->rowptr_u, op->colind_u, (double *)op->vals_u);
-    else slqb::k_upper_fill<float><<<grow, brow, 0, st>>>((int)n, op->rowptr, op->colind, (const float *)op->vals, op->rowptr_u, op->colind_u, (float *)op->vals_u);
+    if (dtype == SLQ_F64) slqb::k_upper_fill<double><<<grow, brow, 0, st>>>((int)n, S.rp(), S.ci(), S.vals.as<double>(), U.rp(), U.colind.as<int32_t>(), U.vals.as<double>());
+    else slqb::k_upper_fill<float><<<grow, brow, 0, st>>>((int)n, S.rp(), S.ci(), S.vals.as<float>(), U.rp(), U.colind.as<int32_t>(), U.vals.as<float>());
   }
   debug_stored_csr(op, " (built on the device)");
   clk.lap("  device: stored CSR, upper triangle");
   // the tiles' stream over the full rows
-  DeviceStream full;
-  int rc = device_build_stream(ctx, dtype, 1, n, op->rowptr, op->colind, op->vals, d_tr, ntiles, false, 0.0, true, full);
+  TileStreamPair &base = op->streams[0];
+  int rc = device_build_stream(ctx, dtype, 1, n, S.rp(), S.ci(), S.vals.p, d_tr.as<int32_t>(), ntiles, false, 0.0, base.full, nullptr, &op->tiles.tile_ptr);
   if (rc != 0) return rc < 0 ? rc : fail(SLQ_EHIP, "tile stream declined");
-  op->tile_desc = full.desc, op->tile_rec = full.rec;
-  op->tile_desc_bytes = full.desc_bytes, op->tile_rec_bytes = full.rec_bytes;
-  op->tiles.tile_ptr = full.tile_ptr;
-  op->tiles.max_cols = full.max_lines;
-  for (int x = 0; x < 9; ++x) op->tiles.xcd_tile[x] = L.xcd_tile[x];
+  op->tiles.max_cols = base.full.max_lines;
+  std::copy(L.xcd_tile, L.xcd_tile + 9, op->tiles.xcd_tile);
+  std::copy(L.xcd_tile, L.xcd_tile + 9, base.full.xcd_tile);
   op->tiles_ringed = true;
-  op->merged_lock = new (std::nothrow) std::mutex();
   clk.lap("  device: tile stream");
   if (sym) {
     if (rg.joinable()) rg.join();
     if (rg_failed) return fail(SLQ_ENOMEM, "host worker failed (upper-triangle tiles)");
     if (!regroup) tile_row_u = tile_row;
-    for (int x = 0; x < 9; ++x) op->xcd_tile_u[x] = xcd_u[x];
+    std::copy(xcd_u, xcd_u + 9, base.upper.xcd_tile);
     const int ntu = (int)tile_row_u.size() - 1;
     debug_upper_tiles(op, (size_t)ntu, (size_t)ntiles);
     DevBuf d_tru;
     e = d_tru.alloc(tile_row_u.size() * 4);
     if (e == hipSuccess) e = hipMemcpy(d_tru.p, tile_row_u.data(), tile_row_u.size() * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess) return hip_fail("upper-triangle tiles", e);
-    DeviceStream us;
-    rc = device_build_stream(ctx, dtype, 1, n, op->rowptr_u, op->colind_u, op->vals_u, d_tru.as<int32_t>(), ntu, osw.ring_pad_rows != 0,
-                             kTileAlphaMergedColsPerRow, false, us);
+    int64_t sum_lines = 0;
+    rc = device_build_stream(ctx, dtype, 1, n, U.rp(), U.ci(), U.vals.p, d_tru.as<int32_t>(), ntu, osw.ring_pad_rows != 0, kTileAlphaMergedColsPerRow, base.upper, &sum_lines);
     if (rc < 0) return rc;
-    op->tile_max_lines_u = us.max_lines;
-    op->upper_per_row = (double)us.sum_lines / (double)n;
+    op->upper_per_row = (double)sum_lines / (double)n;
     debug_upper_lists(op);
-    if (rc == 0) {
-      op->tile_desc_u = us.desc, op->tile_rec_u = us.rec;
-      op->tile_desc_u_bytes = us.desc_bytes, op->tile_rec_u_bytes = us.rec_bytes;
-      op->tile_u_padded = us.padded;
-    }
     clk.lap("  device: upper tile stream");
   }
   e = hipStreamSynchronize(st);
@@ -973,22 +880,14 @@ static int operators_differ(const slq_operator *a, const slq_operator *b);
 // then one of the two storage builders, which consume the same OperatorLayout.
 static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colind,
                            const void *vals, slq_operator **out, int plain, int host_build, DeviceCsr dev) {
-  if (!ctx || !out) return fail(SLQ_EINVAL, "ctx/out is NULL");
-  *out = nullptr;
-  SLQ_TRY(check_dtype(dtype));
-  const OperatorSwitches osw = read_operator_switches();  // (the one read of this creation: everything below, and the operator, keep these values)
+  slq_operator *op = nullptr;
+  SLQ_TRY(operator_new(ctx, OP_CSR, dtype, n, nnz, out, &op));
+  OpGuard guard{op};
+  const OperatorSwitches osw = op->sw;  // (everything below keeps the values the operator was created under; a copy: the analysis reads it in its inner loops)
   PhaseClock clk(osw);
   SLQ_TRY(validate_csr(n, nnz, rowptr, colind));
   if (nnz > 0 && !vals && !dev.va) return fail(SLQ_EINVAL, "CSR arrays are NULL");
-  HIP_TRY(hipSetDevice(ctx->device));
   clk.lap("validation");
-  if (ctx->dead) return fail(SLQ_EINVAL, "the context has been destroyed");
-  slq_operator *op = new (std::nothrow) slq_operator();
-  if (!op) return fail(SLQ_ENOMEM, "host allocation failed");
-  ctx_retain(ctx);
-  *op = slq_operator{ctx, OP_CSR, dtype, n, nnz, nullptr, nullptr, nullptr, 0, true, nullptr, nullptr, nullptr, nullptr, TileMeta{}};
-  op->sw = osw;
-  OpGuard guard{op};
   const CsrView A{n, nnz, rowptr, colind};
   const LayoutPrefilter pre = layout_prefilter(A, osw, plain != 0);
   clk.lap("tile sample");
@@ -1010,7 +909,7 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
   }
   OperatorLayout L = decide_layout(A, osw, pre, &clk);
   op->rms_dist = L.rms_dist;
-  if (!L.perm.empty()) op->perm_h = new std::vector<int32_t>(std::move(L.perm));  // (the operator keeps the order; the builders read it there)
+  op->perm_h = std::move(L.perm);  // (the operator keeps the order; the builders read it there)
   std::vector<char> vals_back;  // the values of a device-resident CSR, fetched when the host needs them
   auto need_host_vals = [&]() -> hipError_t {
     if (vals || nnz == 0) return hipSuccess;
@@ -1044,38 +943,22 @@ static int csr_create_body(slq_context *ctx, int dtype, int64_t n, int64_t nnz, 
 
 // SLQ_DEVICE_BUILD=2: 0 when everything two operators over the same matrix keep is the same, else the number of the first item that is not
 static int operators_differ(const slq_operator *a, const slq_operator *b) {
-  const size_t es = esize(a->dtype);
-  auto same = device_equals_device;
-  const size_t n = (size_t)a->n, nnz = (size_t)a->nnz;
-  if (a->n != b->n || a->nnz != b->nnz || a->nnz_u != b->nnz_u || a->dtype != b->dtype) return 1;
-  if (!a->perm_h || !b->perm_h || *a->perm_h != *b->perm_h) return 2;
-  if (!same(a->perm_d, b->perm_d, n * 4) || !same(a->inv_perm_d, b->inv_perm_d, n * 4)) return 3;
-  if (!same(a->rowptr, b->rowptr, (n + 1) * 4)) return 4;
-  if (!same(a->colind, b->colind, (nnz + kCsrPad) * 4)) return 5;
-  if (!same(a->vals, b->vals, (nnz + kCsrPad) * es)) return 6;
-  if (a->far_per_row != b->far_per_row || a->rms_dist != b->rms_dist) return 7;
-  if ((a->rowptr_u == nullptr) != (b->rowptr_u == nullptr)) return 8;
-  if (a->rowptr_u) {
-    const size_t nu = (size_t)a->nnz_u;
-    if (!same(a->rowptr_u, b->rowptr_u, (n + 1) * 4)) return 9;
-    if (!same(a->colind_u, b->colind_u, (nu + kCsrPad) * 4)) return 10;
-    if (!same(a->vals_u, b->vals_u, (nu + kCsrPad) * es)) return 11;
-  }
-  for (int x = 0; x < 9; ++x)
-    if (a->tiles.xcd_tile[x] != b->tiles.xcd_tile[x] || a->xcd_tile_u[x] != b->xcd_tile_u[x]) return 12;
-  const size_t nt = (size_t)a->tiles.xcd_tile[8];
-  if (!same(a->tiles.tile_row, b->tiles.tile_row, (nt + 1) * 4) || !same(a->tiles.tile_ptr, b->tiles.tile_ptr, (nt + 1) * 4)) return 13;
-  if (a->tiles.max_cols != b->tiles.max_cols || a->tiles_ringed != b->tiles_ringed) return 14;
-  if (a->tile_desc_bytes != b->tile_desc_bytes || a->tile_rec_bytes != b->tile_rec_bytes) return 15;
-  if (!same(a->tile_desc, b->tile_desc, a->tile_desc_bytes)) return 16;
-  if (!same(a->tile_rec, b->tile_rec, a->tile_rec_bytes)) return 17;
-  if (a->tile_max_lines_u != b->tile_max_lines_u || a->upper_per_row != b->upper_per_row || a->tile_u_padded != b->tile_u_padded) return 18;
-  if ((a->tile_desc_u == nullptr) != (b->tile_desc_u == nullptr)) return 19;
-  if (a->tile_desc_u) {
-    if (a->tile_desc_u_bytes != b->tile_desc_u_bytes || a->tile_rec_u_bytes != b->tile_rec_u_bytes) return 20;
-    if (!same(a->tile_desc_u, b->tile_desc_u, a->tile_desc_u_bytes)) return 21;
-    if (!same(a->tile_rec_u, b->tile_rec_u, a->tile_rec_u_bytes)) return 22;
-  }
+  auto csr_differ = [](const CsrArrays &x, const CsrArrays &y) {  // 0, or 1 + the array that differs
+    if ((bool)x != (bool)y || x.nnz != y.nnz) return 1;
+    return !buffers_equal(x.rowptr, y.rowptr) ? 2 : !buffers_equal(x.colind, y.colind) ? 3 : !buffers_equal(x.vals, y.vals) ? 4 : 0;
+  };
+  if (a->n != b->n || a->nnz != b->nnz || a->dtype != b->dtype) return 1;
+  if (a->perm_h.empty() || a->perm_h != b->perm_h) return 2;
+  if (!buffers_equal(a->perm_d, b->perm_d) || !buffers_equal(a->inv_perm_d, b->inv_perm_d)) return 3;
+  if (int d = csr_differ(a->csr, b->csr)) return 3 + d;  // 4 .. 7
+  if (a->far_per_row != b->far_per_row || a->rms_dist != b->rms_dist) return 8;
+  if (int d = csr_differ(a->upper, b->upper)) return 8 + d;  // 9 .. 12
+  if (!std::equal(a->tiles.xcd_tile, a->tiles.xcd_tile + 9, b->tiles.xcd_tile)) return 13;
+  if (!buffers_equal(a->tiles.tile_row, b->tiles.tile_row) || !buffers_equal(a->tiles.tile_ptr, b->tiles.tile_ptr)) return 14;
+  if (a->tiles.max_cols != b->tiles.max_cols || a->tiles_ringed != b->tiles_ringed) return 15;
+  if (int d = streams_differ(a->streams[0].full, b->streams[0].full)) return 15 + d;  // 16 .. 18
+  if (a->upper_per_row != b->upper_per_row) return 19;
+  if (int d = streams_differ(a->streams[0].upper, b->streams[0].upper)) return 19 + d;  // 20 .. 22
   return 0;
 }
 
@@ -1108,9 +991,10 @@ extern "C" int slq_csr_create_device(slq_context *ctx, int dtype, int64_t n, int
 
 static int csr_gram_create_body(slq_context *ctx, int dtype, int64_t mrows, int64_t ncols, int64_t nnz, const int32_t *rowptr,
                                 const int32_t *colind, const void *vals, slq_operator **out) {
-  if (!ctx || !out) return fail(SLQ_EINVAL, "ctx/out is NULL");
-  *out = nullptr;
-  SLQ_TRY(check_dtype(dtype));
+  slq_operator *op = nullptr;
+  SLQ_TRY(operator_new(ctx, OP_GRAM, dtype, ncols, nnz, out, &op));
+  OpGuard guard{op};
+  op->mrows = mrows;
   if (mrows <= 0 || ncols <= 0 || mrows >= (int64_t)1 << 31 || ncols >= (int64_t)1 << 31 || nnz < 0 || nnz >= (int64_t)1 << 31)
     return fail(SLQ_EINVAL, "CSR shape out of range for int32 indices");
   if (!rowptr || (nnz > 0 && (!colind || !vals))) return fail(SLQ_EINVAL, "CSR arrays are NULL");
@@ -1119,15 +1003,6 @@ static int csr_gram_create_body(slq_context *ctx, int dtype, int64_t mrows, int6
     if (rowptr[i + 1] < rowptr[i]) return fail(SLQ_EINVAL, "rowptr is not non-decreasing at %lld", (long long)i);
   for (int64_t q = 0; q < nnz; ++q)
     if (colind[q] < 0 || colind[q] >= ncols) return fail(SLQ_EINVAL, "column index %d out of range at position %lld", colind[q], (long long)q);
-  HIP_TRY(hipSetDevice(ctx->device));
-  if (ctx->dead) return fail(SLQ_EINVAL, "the context has been destroyed");
-  slq_operator *op = new (std::nothrow) slq_operator();
-  if (!op) return fail(SLQ_ENOMEM, "host allocation failed");
-  ctx_retain(ctx);
-  *op = slq_operator{ctx, OP_GRAM, dtype, ncols, nnz, nullptr, nullptr, nullptr, 0, true, nullptr, nullptr, nullptr, nullptr, TileMeta{}};
-  op->sw = read_operator_switches();
-  op->mrows = mrows;
-  OpGuard guard{op};
   const size_t es = esize(dtype);
   // transpose on the host (counting sort by column; rows of A^T come out with ascending indices)
   std::vector<int32_t> tp((size_t)ncols + 1, 0), tc((size_t)nnz);
@@ -1143,16 +1018,15 @@ static int csr_gram_create_body(slq_context *ctx, int dtype, int64_t mrows, int6
         memcpy(tv.data() + (size_t)w * es, (const char *)vals + (size_t)q * es, es);
       }
   }
-  hipError_t e = hipMalloc((void **)&op->rowptr, (size_t)(mrows + 1) * 4);
-  if (e == hipSuccess) e = alloc_padded_csr(&op->colind, &op->vals, (size_t)nnz, es, ctx->stream);
-  if (e == hipSuccess) e = hipMalloc((void **)&op->rowptr_t, (size_t)(ncols + 1) * 4);
-  if (e == hipSuccess) e = alloc_padded_csr(&op->colind_t, &op->vals_t, (size_t)nnz, es, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(op->rowptr, rowptr, (size_t)(mrows + 1) * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && nnz) e = hipMemcpyAsync(op->colind, colind, (size_t)nnz * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && nnz) e = hipMemcpyAsync(op->vals, vals, (size_t)nnz * es, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(op->rowptr_t, tp.data(), (size_t)(ncols + 1) * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && nnz) e = hipMemcpyAsync(op->colind_t, tc.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && nnz) e = hipMemcpyAsync(op->vals_t, tv.data(), (size_t)nnz * es, hipMemcpyHostToDevice, ctx->stream);
+  CsrArrays &S = op->csr, &T = op->transposed;
+  hipError_t e = S.alloc(mrows, nnz, es, ctx->stream);
+  if (e == hipSuccess) e = T.alloc(ncols, nnz, es, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(S.rowptr.p, rowptr, (size_t)(mrows + 1) * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess && nnz) e = hipMemcpyAsync(S.colind.p, colind, (size_t)nnz * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess && nnz) e = hipMemcpyAsync(S.vals.p, vals, (size_t)nnz * es, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(T.rowptr.p, tp.data(), (size_t)(ncols + 1) * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess && nnz) e = hipMemcpyAsync(T.colind.p, tc.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess && nnz) e = hipMemcpyAsync(T.vals.p, tv.data(), (size_t)nnz * es, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "Gram operator upload: %s", hipGetErrorString(e));
   *out = guard.release();
@@ -1214,10 +1088,10 @@ static int csr_affine_create_body(slq_context *ctx, int dtype, int64_t n, int64_
   const int rc = csr_create_impl(ctx, dtype, n, nnz, rp.data(), ci.data(), ua.data(), &op, 1);
   if (rc != SLQ_OK) return rc;
   OpGuard guard{op};
-  hipError_t e = hipMalloc(&op->vals_a, std::max<size_t>((size_t)nnz * es, 8));
-  if (e == hipSuccess) e = hipMalloc(&op->vals_b, std::max<size_t>((size_t)nnz * es, 8));
-  if (e == hipSuccess && nnz) e = hipMemcpyAsync(op->vals_a, ua.data(), (size_t)nnz * es, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess && nnz) e = hipMemcpyAsync(op->vals_b, ub.data(), (size_t)nnz * es, hipMemcpyHostToDevice, ctx->stream);
+  hipError_t e = op->vals_a.alloc((size_t)nnz * es);
+  if (e == hipSuccess) e = op->vals_b.alloc((size_t)nnz * es);
+  if (e == hipSuccess && nnz) e = hipMemcpyAsync(op->vals_a.p, ua.data(), (size_t)nnz * es, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess && nnz) e = hipMemcpyAsync(op->vals_b.p, ub.data(), (size_t)nnz * es, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "affine operator upload: %s", hipGetErrorString(e));
   *out = guard.release();
@@ -1237,26 +1111,19 @@ extern "C" int slq_operator_set_parameter(slq_operator *op, double t) {
   HIP_TRY(hipSetDevice(op->ctx->device));
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (op->nnz + 255) / 256));
   if (op->dtype == SLQ_F64)
-    k_affine_vals<double><<<grid, 256, 0, op->ctx->stream>>>(op->nnz, (const double *)op->vals_a, (const double *)op->vals_b, t, (double *)op->vals);
+    k_affine_vals<double><<<grid, 256, 0, op->ctx->stream>>>(op->nnz, op->vals_a.as<const double>(), op->vals_b.as<const double>(), t, op->csr.vals.as<double>());
   else
-    k_affine_vals<float><<<grid, 256, 0, op->ctx->stream>>>(op->nnz, (const float *)op->vals_a, (const float *)op->vals_b, t, (float *)op->vals);
+    k_affine_vals<float><<<grid, 256, 0, op->ctx->stream>>>(op->nnz, op->vals_a.as<const float>(), op->vals_b.as<const float>(), t, op->csr.vals.as<float>());
   HIP_TRY(hipGetLastError());
   return SLQ_OK;
 }
 
 static int dense_create_body(slq_context *ctx, int dtype, int64_t n, const void *A, int64_t lda, slq_operator **out) {
-  if (!ctx || !out) return fail(SLQ_EINVAL, "ctx/out is NULL");
-  *out = nullptr;
-  SLQ_TRY(check_dtype(dtype));
-  if (n <= 0 || n >= (int64_t)1 << 31 || !A || lda < n) return fail(SLQ_EINVAL, "bad dense operator shape");
-  HIP_TRY(hipSetDevice(ctx->device));
-  if (ctx->dead) return fail(SLQ_EINVAL, "the context has been destroyed");
-  slq_operator *op = new (std::nothrow) slq_operator();
-  if (!op) return fail(SLQ_ENOMEM, "host allocation failed");
-  ctx_retain(ctx);
-  *op = slq_operator{ctx, OP_DENSE, dtype, n, n * n, nullptr, nullptr, nullptr, n, true, nullptr, nullptr, nullptr, nullptr, TileMeta{}};
-  op->sw = read_operator_switches();
+  slq_operator *op = nullptr;
+  SLQ_TRY(operator_new(ctx, OP_DENSE, dtype, n, n * n, out, &op));
   OpGuard guard{op};
+  if (n <= 0 || n >= (int64_t)1 << 31 || !A || lda < n) return fail(SLQ_EINVAL, "bad dense operator shape");
+  op->lda = n;
   const size_t es = esize(dtype);
   // Y = A X for whatever is given (eigen_operators.h:24-30 does not ask for symmetry either). k_dense_mfma_3term reads
   // A(row, k) and is right for any A; k_dense_panel walks row `row` of A as the contiguous COLUMN `row`, which is A^T:
@@ -1269,17 +1136,17 @@ static int dense_create_body(slq_context *ctx, int dtype, int64_t n, const void 
                                          : ((const float *)A)[j * lda + i] == ((const float *)A)[i * lda + j];
       if (!same) { symmetric = false; break; }
     }
-  hipError_t e = hipMalloc(&op->vals, (size_t)n * n * es);
+  hipError_t e = op->csr.vals.alloc((size_t)n * n * es);
   if (e == hipSuccess)
-    e = hipMemcpy2DAsync(op->vals, (size_t)n * es, A, (size_t)lda * es, (size_t)n * es, (size_t)n,
+    e = hipMemcpy2DAsync(op->csr.vals.p, (size_t)n * es, A, (size_t)lda * es, (size_t)n * es, (size_t)n,
                          hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess && !symmetric) {
     std::vector<char> T((size_t)n * n * es);
     for (int64_t j = 0; j < n; ++j)
       for (int64_t i = 0; i < n; ++i)
         memcpy(T.data() + ((size_t)j * n + i) * es, (const char *)A + ((size_t)i * lda + j) * es, es);  // T(i,j) = A(j,i)
-    e = hipMalloc(&op->vals_t, (size_t)n * n * es);
-    if (e == hipSuccess) e = hipMemcpyAsync(op->vals_t, T.data(), (size_t)n * n * es, hipMemcpyHostToDevice, ctx->stream);
+    e = op->dense_t.alloc((size_t)n * n * es);
+    if (e == hipSuccess) e = hipMemcpyAsync(op->dense_t.p, T.data(), (size_t)n * n * es, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -1294,35 +1161,25 @@ extern "C" int slq_dense_create(slq_context *ctx, int dtype, int64_t n, const vo
 
 extern "C" int slq_callback_create(slq_context *ctx, int dtype, int64_t n, slq_matvec_fn fn,
                                    void *user, slq_operator **out) {
-  if (!ctx || !out) return fail(SLQ_EINVAL, "ctx/out is NULL");
-  *out = nullptr;
-  SLQ_TRY(check_dtype(dtype));
+  slq_operator *op = nullptr;
+  SLQ_TRY(operator_new(ctx, OP_CALLBACK, dtype, n, 0, out, &op));
+  OpGuard guard{op};
   if (n <= 0 || n >= (int64_t)1 << 31) return fail(SLQ_EINVAL, "bad operator shape");
   if (!fn) return fail(SLQ_EINVAL, "Supplied object is missing 'matvec' attribute.");
-  if (ctx->dead) return fail(SLQ_EINVAL, "the context has been destroyed");
-  slq_operator *op = new (std::nothrow) slq_operator();
-  if (!op) return fail(SLQ_ENOMEM, "host allocation failed");
-  ctx_retain(ctx);
-  *op = slq_operator{ctx, OP_CALLBACK, dtype, n, 0, nullptr, nullptr, nullptr, 0, false, fn, user, nullptr, nullptr, TileMeta{}};
-  op->sw = read_operator_switches();
-  *out = op;
+  op->fn = fn, op->user = user;
+  *out = guard.release();
   return SLQ_OK;
 }
 
 extern "C" int slq_device_callback_create(slq_context *ctx, int dtype, int64_t n, slq_matmat_device_fn fn, void *user,
                                           slq_operator **out) {
   if (!ctx || !out || !fn) return fail(SLQ_EINVAL, "ctx/out/fn is NULL");
-  *out = nullptr;
-  SLQ_TRY(check_dtype(dtype));
+  slq_operator *op = nullptr;
+  SLQ_TRY(operator_new(ctx, OP_DEVICE_CALLBACK, dtype, n, 0, out, &op));
+  OpGuard guard{op};
   if (n <= 0 || n >= (int64_t)1 << 31) return fail(SLQ_EINVAL, "bad operator size");
-  if (ctx->dead) return fail(SLQ_EINVAL, "the context has been destroyed");
-  slq_operator *op = new (std::nothrow) slq_operator();
-  if (!op) return fail(SLQ_ENOMEM, "host allocation failed");
-  ctx_retain(ctx);
-  *op = slq_operator{ctx, OP_DEVICE_CALLBACK, dtype, n, 0, nullptr, nullptr, nullptr, 0, false, nullptr, user, nullptr, nullptr, TileMeta{}};
-  op->sw = read_operator_switches();
-  op->dev_fn = fn;
-  *out = op;
+  op->dev_fn = fn, op->user = user;
+  *out = guard.release();
   return SLQ_OK;
 }
 
@@ -1332,10 +1189,10 @@ static int kernel_rescale(slq_operator *op) {
   const int n = (int)op->n, npad = (int)op->k_npad;
   const dim3 g((unsigned)((npad + 255) / 256));
   if (op->dtype == SLQ_F64)
-    k_kernel_rescale<double><<<g, dim3(256), 0, op->ctx->stream>>>(n, npad, op->k_d, op->k_dpad, (const double *)op->k_raw, *op->k_scale, (double *)op->k_zt,
+    k_kernel_rescale<double><<<g, dim3(256), 0, op->ctx->stream>>>(n, npad, op->k_d, op->k_dpad, op->k_raw.as<const double>(), *op->k_scale, (double *)op->k_zt,
                                                                   (double *)op->k_nrm, (double *)op->k_params, op->k_s, op->k_noise);
   else
-    k_kernel_rescale<float><<<g, dim3(256), 0, op->ctx->stream>>>(n, npad, op->k_d, op->k_dpad, (const float *)op->k_raw, *op->k_scale, (float *)op->k_zt,
+    k_kernel_rescale<float><<<g, dim3(256), 0, op->ctx->stream>>>(n, npad, op->k_d, op->k_dpad, op->k_raw.as<const float>(), *op->k_scale, (float *)op->k_zt,
                                                                  (float *)op->k_nrm, (float *)op->k_params, op->k_s, op->k_noise);
   HIP_TRY(hipGetLastError());
   return SLQ_OK;
@@ -1351,15 +1208,13 @@ static void kernel_set_scale(slq_operator *op, const double *ls, int nls, double
 }
 static int kernel_create_body(slq_context *ctx, int dtype, int64_t n, int d, const void *points, int64_t ldp, int profile, const double *ls,
                               int nls, double s, double noise, bool on_device, slq_operator **out) {
-  if (!ctx || !out) return fail(SLQ_EINVAL, "ctx/out is NULL");
-  *out = nullptr;
+  slq_operator *op = nullptr;
+  SLQ_TRY(operator_new(ctx, OP_KERNEL, dtype, n, n * d, out, &op));
+  OpGuard guard{op};
   if (!points || !ls) return fail(SLQ_EINVAL, "kernel operator: points/lengthscales is NULL");
-  SLQ_TRY(check_dtype(dtype));
   KernelBad bad = dtype == SLQ_F64 ? kernel_validate<double>(n, d, on_device ? nullptr : (const double *)points, ldp, profile, ls, nls, s, noise)
                                    : kernel_validate<float>(n, d, on_device ? nullptr : (const float *)points, ldp, profile, ls, nls, s, noise);
   if (bad.what != KERNEL_OK) return kernel_bad(bad);
-  HIP_TRY(hipSetDevice(ctx->device));
-  if (ctx->dead) return fail(SLQ_EINVAL, "the context has been destroyed");
   const size_t es = esize(dtype);
   // points on the device: a packed host copy for the checks and the centre (n d words, once per operator)
   std::vector<char> host;
@@ -1373,14 +1228,8 @@ static int kernel_create_body(slq_context *ctx, int dtype, int64_t n, int d, con
                            : kernel_validate<float>(n, d, (const float *)hp, hld, profile, ls, nls, s, noise);
     if (bad.what != KERNEL_OK) return kernel_bad(bad);
   }
-  slq_operator *op = new (std::nothrow) slq_operator();
-  if (!op) return fail(SLQ_ENOMEM, "host allocation failed");
-  ctx_retain(ctx);
-  *op = slq_operator{ctx, OP_KERNEL, dtype, n, n * d, nullptr, nullptr, nullptr, 0, false, nullptr, nullptr, nullptr, nullptr, TileMeta{}};
-  op->sw = read_operator_switches();
-  OpGuard guard{op};
   op->k_d = d, op->k_dpad = kernel_dpad(d), op->k_npad = kernel_npad(n), op->k_profile = profile;
-  op->k_scale = new KernelScale();
+  op->k_scale.reset(new KernelScale());
   for (int k = 0; k < kKernelMaxDim; ++k) op->k_scale->mean[k] = 0.0;
   if (dtype == SLQ_F64) kernel_column_means<double>(n, d, (const double *)hp, hld, op->k_scale->mean);
   else kernel_column_means<float>(n, d, (const float *)hp, hld, op->k_scale->mean);
@@ -1390,14 +1239,14 @@ static int kernel_create_body(slq_context *ctx, int dtype, int64_t n, int d, con
   // one allocation: raw points | z transposed | |z|^2 | {s, sigma2}, each on a 256-byte boundary
   auto up = [](size_t b) { return (b + 255) / 256 * 256; };
   const size_t b_raw = up((size_t)n * d * es), b_zt = up((size_t)op->k_dpad * (size_t)op->k_npad * es), b_nrm = up((size_t)op->k_npad * es);
-  hipError_t e = hipMalloc(&op->k_raw, b_raw + b_zt + b_nrm + 256);
+  hipError_t e = op->k_raw.alloc(b_raw + b_zt + b_nrm + 256);
   if (e == hipSuccess) {
-    op->k_zt = (char *)op->k_raw + b_raw;
+    op->k_zt = op->k_raw.as<char>() + b_raw;
     op->k_nrm = (char *)op->k_zt + b_zt;
     op->k_params = (char *)op->k_nrm + b_nrm;
   }
   if (e == hipSuccess)
-    e = hipMemcpy2DAsync(op->k_raw, (size_t)d * es, hp, (size_t)hld * es, (size_t)d * es, (size_t)n, hipMemcpyHostToDevice, ctx->stream);
+    e = hipMemcpy2DAsync(op->k_raw.p, (size_t)d * es, hp, (size_t)hld * es, (size_t)d * es, (size_t)n, hipMemcpyHostToDevice, ctx->stream);
   if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "kernel operator upload: %s", hipGetErrorString(e));
   SLQ_TRY(kernel_rescale(op));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1459,43 +1308,10 @@ extern "C" int slq_debug_kernel_schedule(int64_t n, int panel_width, int panels,
 
 extern "C" int slq_operator_destroy(slq_operator *op) {
   if (!op) return SLQ_OK;
-  if (op->owns) {
-    hipSetDevice(op->ctx->device);
-    if (op->rowptr) hipFree(op->rowptr);
-    if (op->colind) hipFree(op->colind);
-    if (op->vals) hipFree(op->vals);
-  }
-  if (op->k_raw) hipFree(op->k_raw);  // (z, |z|^2 and the scalars lie behind the points in the same allocation)
-  delete op->k_scale;
-  if (op->vals_t) hipFree(op->vals_t);
-  if (op->rowptr_t) hipFree(op->rowptr_t);
-  if (op->colind_t) hipFree(op->colind_t);
-  if (op->vals_a) hipFree(op->vals_a);
-  if (op->vals_b) hipFree(op->vals_b);
-  if (op->perm_d) hipFree(op->perm_d);
-  if (op->inv_perm_d) hipFree(op->inv_perm_d);
-  delete op->perm_h;
-  if (op->rowptr_u) hipFree(op->rowptr_u);
-  if (op->colind_u) hipFree(op->colind_u);
-  if (op->vals_u) hipFree(op->vals_u);
-  if (op->tiles.tile_row) hipFree((void *)op->tiles.tile_row);
-  if (op->tiles.tile_ptr) hipFree((void *)op->tiles.tile_ptr);
-  if (op->tiles.tile_cols) hipFree((void *)op->tiles.tile_cols);
-  if (op->tiles.lcol) hipFree((void *)op->tiles.lcol);
-  if (op->tiles.self_idx) hipFree((void *)op->tiles.self_idx);
-  if (op->tile_desc) hipFree(op->tile_desc);
-  if (op->tile_rec) hipFree(op->tile_rec);
-  if (op->tile_desc_u) hipFree(op->tile_desc_u);
-  if (op->tile_rec_u) hipFree(op->tile_rec_u);
-  for (auto &m : op->merged) {
-    if (m.desc) hipFree(m.desc);
-    if (m.rec) hipFree(m.rec);
-    if (m.desc_u) hipFree(m.desc_u);
-    if (m.rec_u) hipFree(m.rec_u);
-  }
-  delete op->merged_lock;
-  ctx_release(op->ctx);
-  delete op;
+  hipSetDevice(op->ctx->device);
+  slq_context *ctx = op->ctx;
+  delete op;  // (every device array is a member that frees itself: slq_operator.hpp)
+  ctx_release(ctx);
   return SLQ_OK;
 }
 
@@ -1507,116 +1323,82 @@ extern "C" int slq_operator_destroy(slq_operator *op) {
 // caller's is needed again. Returns false when the operator has no ring-sized tiles (or the build failed: the plan then
 // takes the generic passes).
 static bool ensure_ring_stream(slq_operator *op, int R) {
-  if (R == 1) return op->tile_desc != nullptr;
-  if (!op->tile_desc || !op->tiles_ringed || !op->merged_lock || (R != 2 && R != 4)) return false;
-  slq_operator::MergedStream &m = op->merged[R == 2 ? 0 : 1];
-  std::lock_guard<std::mutex> guard(*op->merged_lock);
-  if (m.tried) return m.desc != nullptr;
+  const TileStreamPair &base = op->streams[0];
+  if (R == 1) return (bool)base.full;
+  if (!base.full || !op->tiles_ringed || (R != 2 && R != 4)) return false;
+  TileStreamPair &m = op->streams[R == 2 ? 1 : 2];
+  std::lock_guard<std::mutex> guard(op->merged_lock);
+  if (m.tried) return (bool)m.full;
   m.tried = true;
-  const int64_t n = op->n, nnz = op->nnz;
+  const int64_t n = op->n;
   const size_t es = esize(op->dtype);
   const int32_t ntiles = op->tiles.xcd_tile[8];
-  auto drop = [](slq_operator::MergedStream &mm) {
-    for (void **q : {(void **)&mm.desc, (void **)&mm.rec, (void **)&mm.desc_u, (void **)&mm.rec_u}) {
-      if (*q) hipFree(*q);
-      *q = nullptr;
-    }
-  };
+  const bool with_upper = base.upper && op->upper;
+  const bool want_pad = op->sw.ring_pad_rows != 0;
   try {
     std::vector<int32_t> tr((size_t)ntiles + 1);
-    if (hipMemcpy(tr.data(), op->tiles.tile_row, ((size_t)ntiles + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    if (hipMemcpy(tr.data(), op->tiles.tile_row.p, ((size_t)ntiles + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
     // merged tile boundaries, chunk by chunk (a merged tile never straddles two XCD chunks; a chunk's last one may be short)
     std::vector<int32_t> mrow;
+    int32_t mxcd[9];
     for (int x = 0; x < 8; ++x) {
-      m.xcd_tile[x] = (int32_t)mrow.size();
+      mxcd[x] = (int32_t)mrow.size();
       for (int32_t t = op->tiles.xcd_tile[x]; t < op->tiles.xcd_tile[x + 1]; t += R) mrow.push_back(tr[(size_t)t]);
     }
-    m.xcd_tile[8] = (int32_t)mrow.size();
+    mxcd[8] = (int32_t)mrow.size();
     mrow.push_back((int32_t)n);
+    std::copy(mxcd, mxcd + 9, m.full.xcd_tile);  // (known whether or not the build below succeeds)
     // the host's way (SLQ_DEVICE_BUILD=0, and the yardstick of SLQ_DEVICE_BUILD=2): the CSR comes back, lists and stream are built
-    // here and uploaded. sizes: bytes of desc, rec, desc_u, rec_u
-    auto build_host = [&](slq_operator::MergedStream &mm, size_t sizes[4]) -> bool {
-      std::vector<int32_t> rp((size_t)n + 1), ci((size_t)nnz);
-      std::vector<char> va((size_t)nnz * es);
-      if (hipMemcpy(rp.data(), op->rowptr, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
-      if (hipMemcpy(ci.data(), op->colind, (size_t)nnz * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
-      if (hipMemcpy(va.data(), op->vals, (size_t)nnz * es, hipMemcpyDeviceToHost) != hipSuccess) return false;
-      auto upload = [&](const int32_t *rowptr, const int32_t *colind, const void *vals, int32_t **desc_d, char **rec_d, int *max_lines, bool *pad, size_t *sz) -> bool {
-        std::vector<int32_t> tp, tc, lc, si;
-        RawBuf<int32_t> desc;
-        RawBuf<char> rec;
-        int mx = 0;
-        build_tile_meta(n, rowptr, colind, mrow, tp, tc, lc, si, &mx, op->sw);
-        *max_lines = mx;
-        if (mx > kRingTileCols * R) return false;  // (cannot happen: a union of R lists of <= 36)
-        if (op->dtype == SLQ_F64) build_ring_stream<double>(R, rowptr, (const double *)vals, mrow, tp, tc, lc, si, desc, rec, pad);
-        else build_ring_stream<float>(R, rowptr, (const float *)vals, mrow, tp, tc, lc, si, desc, rec, pad);
-        sz[0] = desc.size() * 4, sz[1] = rec.size();
-        if (hipMalloc((void **)desc_d, desc.size() * 4) != hipSuccess) return false;
-        if (hipMalloc((void **)rec_d, rec.size()) != hipSuccess) return false;
-        return hipMemcpy(*desc_d, desc.data(), desc.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-               hipMemcpy(*rec_d, rec.data(), rec.size(), hipMemcpyHostToDevice) == hipSuccess;
+    // here and uploaded
+    auto build_host = [&](TileStreamPair &mm) -> bool {
+      struct Fetched { std::vector<int32_t> rp, ci; std::vector<char> va; } F, FU;
+      auto fetch = [&](const CsrArrays &c, Fetched &f) {
+        f.rp.resize((size_t)n + 1), f.ci.resize((size_t)c.nnz), f.va.resize((size_t)c.nnz * es);
+        return hipMemcpy(f.rp.data(), c.rowptr.p, f.rp.size() * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+               hipMemcpy(f.ci.data(), c.colind.p, f.ci.size() * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+               hipMemcpy(f.va.data(), c.vals.p, f.va.size(), hipMemcpyDeviceToHost) == hipSuccess;
       };
-      bool ok = upload(rp.data(), ci.data(), va.data(), &mm.desc, &mm.rec, &mm.max_lines, nullptr, sizes);
-      if (ok && op->tile_desc_u && op->rowptr_u) {
-        const size_t nu = (size_t)op->nnz_u;
-        bool upad = op->sw.ring_pad_rows != 0;
-        std::vector<int32_t> urp((size_t)n + 1), uci(nu);
-        std::vector<char> uva(nu * es);
-        ok = hipMemcpy(urp.data(), op->rowptr_u, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-             hipMemcpy(uci.data(), op->colind_u, nu * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-             hipMemcpy(uva.data(), op->vals_u, nu * es, hipMemcpyDeviceToHost) == hipSuccess &&
-             upload(urp.data(), uci.data(), uva.data(), &mm.desc_u, &mm.rec_u, &mm.max_lines_u, &upad, sizes + 2);
-        mm.u_padded = ok && upad;
-      }
-      if (!ok) drop(mm);
-      return ok;
+      HostStream hs, hsu;
+      UploadQueue up(op->ctx->device);  // (declared after what it reads: joined first)
+      bool ok = fetch(op->csr, F) && host_build_stream(op, R, HostCsr{F.rp.data(), F.ci.data(), F.va.data()}, mrow, false, 0.0, hs, up, mm.full) == hipSuccess && mm.full;
+      if (ok && with_upper)
+        ok = fetch(op->upper, FU) && host_build_stream(op, R, HostCsr{FU.rp.data(), FU.ci.data(), FU.va.data()}, mrow, want_pad, 0.0, hsu, up, mm.upper) == hipSuccess && mm.upper;
+      return up.wait() == hipSuccess && ok;
     };
     // on the device (slq_build.hpp): the operator's CSR never leaves it
-    size_t dsz[4] = {0, 0, 0, 0};
-    auto build_device = [&](slq_operator::MergedStream &mm) -> bool {
+    auto build_device = [&](TileStreamPair &mm) -> bool {
       if (hipSetDevice(op->ctx->device) != hipSuccess) return false;
       DevBuf d_mrow;
       if (d_mrow.alloc(mrow.size() * 4) != hipSuccess) return false;
       if (hipMemcpy(d_mrow.p, mrow.data(), mrow.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return false;
       const int nm = (int)mrow.size() - 1;
-      DeviceStream f;
-      if (device_build_stream(op->ctx, op->dtype, R, n, op->rowptr, op->colind, op->vals, d_mrow.as<int32_t>(), nm, false, 0.0, false, f) != 0) return false;
-      mm.desc = f.desc, mm.rec = f.rec, mm.max_lines = f.max_lines;
-      dsz[0] = f.desc_bytes, dsz[1] = f.rec_bytes;
-      if (op->tile_desc_u && op->rowptr_u) {
-        DeviceStream g;
-        if (device_build_stream(op->ctx, op->dtype, R, n, op->rowptr_u, op->colind_u, op->vals_u, d_mrow.as<int32_t>(), nm, op->sw.ring_pad_rows != 0, 0.0, false, g) != 0) {
-          drop(mm);
-          return false;
-        }
-        mm.desc_u = g.desc, mm.rec_u = g.rec, mm.max_lines_u = g.max_lines, mm.u_padded = g.padded;
-        dsz[2] = g.desc_bytes, dsz[3] = g.rec_bytes;
-      }
-      return true;
+      if (device_build_stream(op->ctx, op->dtype, R, n, op->csr.rp(), op->csr.ci(), op->csr.vals.p, d_mrow.as<int32_t>(), nm, false, 0.0, mm.full) != 0) return false;
+      return !with_upper || device_build_stream(op->ctx, op->dtype, R, n, op->upper.rp(), op->upper.ci(), op->upper.vals.p, d_mrow.as<int32_t>(), nm, want_pad, 0.0, mm.upper) == 0;
     };
-    const int dev_mode = op->sw.ring_order != 0 ? 0 : op->sw.device_build;  // (as the operator was built)
-    size_t hsz[4] = {0, 0, 0, 0};
-    if (dev_mode == 0) return build_host(m, hsz);
-    if (!build_device(m)) return false;
-    if (dev_mode == 2) {  // both, compared
-      slq_operator::MergedStream h;
-      bool same = build_host(h, hsz);
-      auto eq = device_equals_device;
-      for (int q = 0; q < 4 && same; ++q) same = hsz[q] == dsz[q];
-      same = same && h.max_lines == m.max_lines && h.max_lines_u == m.max_lines_u && h.u_padded == m.u_padded;
-      same = same && eq(h.desc, m.desc, dsz[0]) && eq(h.rec, m.rec, dsz[1]) && eq(h.desc_u, m.desc_u, dsz[2]) && eq(h.rec_u, m.rec_u, dsz[3]);
-      drop(h);
-      if (!same) {
-        fprintf(stderr, "[slq] SLQ_DEVICE_BUILD=2: the device-built stream of %d-merged tiles differs from the host-built one\n", R);
-        drop(m);
-        return false;
-      }
+    // (a pair that failed half-way goes with everything it has: only a complete one reaches the operator)
+    TileStreamPair built, ref;
+    for (TileStreamPair *q : {&built, &ref}) {
+      std::copy(mxcd, mxcd + 9, q->full.xcd_tile);
+      if (with_upper) std::copy(mxcd, mxcd + 9, q->upper.xcd_tile);
     }
+    const int dev_mode = op->sw.ring_order != 0 ? 0 : op->sw.device_build;  // (as the operator was built)
+    if (!(dev_mode == 0 ? build_host(built) : build_device(built))) return false;
+    if (dev_mode == 2 && (!build_host(ref) || streams_differ(ref.full, built.full) || streams_differ(ref.upper, built.upper))) {  // both, compared
+      fprintf(stderr, "[slq] SLQ_DEVICE_BUILD=2: the device-built stream of %d-merged tiles differs from the host-built one\n", R);
+      return false;
+    }
+    built.tried = true;
+    m = std::move(built);
     return true;
   } catch (const std::bad_alloc &) {
     return false;
   }
+}
+
+extern "C" int slq_debug_operator_device_bytes(int64_t *live) {
+  if (!live) return fail(SLQ_EINVAL, "live is NULL");
+  *live = g_devbuf_bytes.load();
+  return SLQ_OK;
 }
 
 extern "C" int slq_operator_shape(const slq_operator *op, int64_t *nrows, int64_t *ncols,
@@ -1743,7 +1525,7 @@ template <typename F> __global__ void k_norm_inf(int n, const int32_t *__restric
 }
 }  // namespace slq
 static int operator_norm_inf(slq_operator *op, double *out) {
-  if (op->kind != OP_CSR || op->vals_b != nullptr) return fail(SLQ_EINVAL, "no fixed CSR values to take ||A||_inf of");
+  if (op->kind != OP_CSR || op->vals_b) return fail(SLQ_EINVAL, "no fixed CSR values to take ||A||_inf of");
   if (op->norm_inf < 0.0) {
     unsigned long long *d = nullptr, h = 0;
     hipStream_t st = op->ctx->stream;
@@ -1751,8 +1533,8 @@ static int operator_norm_inf(slq_operator *op, double *out) {
     hipError_t e = hipMemsetAsync(d, 0, 8, st);
     if (e == hipSuccess) {
       const dim3 grid((unsigned)((op->n + 255) / 256));
-      if (op->dtype == SLQ_F64) k_norm_inf<double><<<grid, 256, 0, st>>>((int)op->n, op->rowptr, (const double *)op->vals, d);
-      else k_norm_inf<float><<<grid, 256, 0, st>>>((int)op->n, op->rowptr, (const float *)op->vals, d);
+      if (op->dtype == SLQ_F64) k_norm_inf<double><<<grid, 256, 0, st>>>((int)op->n, op->csr.rp(), op->csr.vals.as<const double>(), d);
+      else k_norm_inf<float><<<grid, 256, 0, st>>>((int)op->n, op->csr.rp(), op->csr.vals.as<const float>(), d);
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, st);
@@ -1771,20 +1553,21 @@ static int operator_norm_inf(slq_operator *op, double *out) {
 // (plan_create_mode builds the one its plan wants first).
 static PlanFacts plan_facts_of(const slq_operator *op, int nprobes, int deg, int orth, PlanKind kind) {
   PlanFacts f;
-  f.kind = op->kind, f.dtype = op->dtype, f.n = op->n, f.nnz = op->nnz, f.nnz_u = op->nnz_u, f.upper = op->rowptr_u != nullptr;
+  const TileStream &upper_stream = op->streams[0].upper;
+  f.kind = op->kind, f.dtype = op->dtype, f.n = op->n, f.nnz = op->nnz, f.nnz_u = op->upper.nnz, f.upper = (bool)op->upper;
   f.mrows = op->mrows, f.lda = op->lda;
-  f.has_tiles = op->tiles.tile_ptr != nullptr, f.tiles_ringed = op->tiles_ringed, f.tiles_max_cols = op->tiles.max_cols;
-  f.upper_per_row = op->upper_per_row, f.upper_stream = op->tile_desc_u != nullptr, f.upper_padded = op->tile_u_padded;
-  f.far_per_row = op->far_per_row, f.affine = op->vals_b != nullptr;
+  f.has_tiles = (bool)op->tiles.tile_ptr, f.tiles_ringed = op->tiles_ringed, f.tiles_max_cols = op->tiles.max_cols;
+  f.upper_per_row = op->upper_per_row, f.upper_stream = (bool)upper_stream, f.upper_padded = upper_stream.padded;
+  f.far_per_row = op->far_per_row, f.affine = (bool)op->vals_b;
   std::copy(op->tiles.xcd_tile, op->tiles.xcd_tile + 9, f.xcd_tile);
-  std::copy(op->xcd_tile_u, op->xcd_tile_u + 9, f.xcd_tile_u);
+  std::copy(upper_stream.xcd_tile, upper_stream.xcd_tile + 9, f.xcd_tile_u);
   {
     std::unique_lock<std::mutex> guard;
-    if (op->merged_lock) guard = std::unique_lock<std::mutex>(*op->merged_lock);  // (another plan's creation may be building one)
+    if (op->tiles_ringed) guard = std::unique_lock<std::mutex>(op->merged_lock);  // (another plan's creation may be building one)
     for (int i = 0; i < 2; ++i) {
-      const slq_operator::MergedStream &m = op->merged[i];
-      f.merged[i].available = m.desc != nullptr, f.merged[i].upper = m.desc_u != nullptr, f.merged[i].u_padded = m.u_padded;
-      std::copy(m.xcd_tile, m.xcd_tile + 9, f.merged[i].xcd_tile);
+      const TileStreamPair &m = op->streams[1 + i];
+      f.merged[i].available = (bool)m.full, f.merged[i].upper = (bool)m.upper, f.merged[i].u_padded = m.upper.padded;
+      std::copy(m.full.xcd_tile, m.full.xcd_tile + 9, f.merged[i].xcd_tile);
     }
   }
   f.num_cus = op->ctx->num_cus;
@@ -1896,17 +1679,13 @@ static void plan_adopt_shape(slq_plan *p) {
   p->pipelined = sh.pipelined != 0;
   p->nblkA = sh.nblkA, p->nblkS = sh.nblkS, p->nblkU = sh.nblkU, p->nblkF = sh.nblkF, p->nblkT = sh.nblkT;
   p->alpha_pad = sh.alpha_pad, p->part_maxblk = sh.part_maxblk, p->dense_ks = sh.dense_ks;
-  p->ringR = sh.ringR, p->rs_u_padded = sh.rs_u_padded != 0, p->ring_staged = sh.ring_staged != 0;
-  std::copy(sh.rs_xcd, sh.rs_xcd + 9, p->rs_xcd);
-  std::copy(sh.rs_xcd_u, sh.rs_xcd_u + 9, p->rs_xcd_u);
-  p->rs_desc = p->rs_desc_u = nullptr;
-  p->rs_rec = p->rs_rec_u = nullptr;
-  if (sh.stream == STREAM_BASE) {
-    p->rs_desc = op->tile_desc, p->rs_rec = op->tile_rec;
-    if (sh.rs_upper) p->rs_desc_u = op->tile_desc_u, p->rs_rec_u = op->tile_rec_u;
-  } else if (sh.stream != STREAM_NONE) {
-    const slq_operator::MergedStream &m = op->merged[sh.stream - STREAM_MERGED2];
-    p->rs_desc = m.desc, p->rs_rec = m.rec, p->rs_desc_u = m.desc_u, p->rs_rec_u = m.rec_u;
+  p->ringR = sh.ringR, p->ring_staged = sh.ring_staged != 0;
+  p->rs_full = p->rs_upper = nullptr;
+  if (sh.stream != STREAM_NONE) {
+    const TileStreamPair &m = op->streams[sh.stream - STREAM_BASE];
+    p->rs_full = &m.full;
+    // (the base stream's upper half only where the shape takes it; a merged pair's whenever it has one)
+    if (m.upper && (sh.stream != STREAM_BASE || sh.rs_upper)) p->rs_upper = &m.upper;
   }
   p->ring_gen = sh.seq.ring_gen, p->ring_deep = sh.seq.ring_deep, p->gram = sh.seq.gram, p->gram_csr = sh.seq.gram_csr, p->last_nostore = sh.seq.last_nostore;
   p->omega_on = sh.omega_on != 0;
@@ -2123,7 +1902,7 @@ extern "C" int slq_plan_describe(const slq_plan *p, slq_plan_info *out) {
   out->sequence = seq::plan_sequence_of(sequence_facts(p));
   out->pipelined = p->pipelined ? 1 : 0;
   out->reordered = p->op->perm_d ? 1 : 0;
-  out->upper_alpha = p->op->rowptr_u ? 1 : 0;
+  out->upper_alpha = p->op->upper ? 1 : 0;
   out->far_per_row = p->op->far_per_row;
   out->tiles = plan_tiled(p) ? (p->op->tiles_ringed ? 2 : 1) : 0;
   return SLQ_OK;
@@ -2340,9 +2119,9 @@ extern "C" int slq_plan_set_probes(slq_plan *p, const void *X, int64_t ldx) {
     dim3 g((p->n + 63) / 64, (nc + 63) / 64);
     PROFILED(p, SLQ_K_PROBES, {
       if (p->dtype == SLQ_F64)
-        hipLaunchKernelGGL(k_cols_to_panel<double>, g, dim3(256), 0, st, p->n, (const double *)p->stage, c0, nc, (double *)slot_ptr(p, 0), p->PW, p->op->perm_d);
+        hipLaunchKernelGGL(k_cols_to_panel<double>, g, dim3(256), 0, st, p->n, (const double *)p->stage, c0, nc, (double *)slot_ptr(p, 0), p->PW, p->op->perm_d.as<int32_t>());
       else
-        hipLaunchKernelGGL(k_cols_to_panel<float>, g, dim3(256), 0, st, p->n, (const float *)p->stage, c0, nc, (float *)slot_ptr(p, 0), p->PW, p->op->perm_d);
+        hipLaunchKernelGGL(k_cols_to_panel<float>, g, dim3(256), 0, st, p->n, (const float *)p->stage, c0, nc, (float *)slot_ptr(p, 0), p->PW, p->op->perm_d.as<int32_t>());
     });
     if (!use_pin) HIP_TRY(hipStreamSynchronize(st));  // the caller's memory and the staging buffer are reused by the next chunk
   }
@@ -2364,7 +2143,7 @@ extern "C" int slq_plan_generate_probes(slq_plan *p, int pdf, uint64_t seed, uin
   PROFILED(p, SLQ_K_PROBES,
            DISPATCH(p->dtype, p->LPR,
                     (k_gen_probes<F, L><<<g, dim3(256), 0, st>>>(p->n,
-                                        (F *)slot_ptr(p, 0), pdf, seed, probe_offset, p->nprobes, p->op->inv_perm_d))));
+                                        (F *)slot_ptr(p, 0), pdf, seed, probe_offset, p->nprobes, p->op->inv_perm_d.as<int32_t>()))));
   p->pdf_sphere = (pdf == SLQ_PDF_SPHERE);
   return init_from_probes(p, p->pdf_sphere, pdf == 0 && p->sw.known_norm != 0);
 }
@@ -2379,9 +2158,9 @@ static int panel_to_host(slq_plan *p, int slot, int c0, int nc, void *X, int64_t
     const int m = std::min(cc, nc - o);
     dim3 g((p->n + 63) / 64, (m + 63) / 64);
     if (p->dtype == SLQ_F64)
-      hipLaunchKernelGGL(k_panel_to_cols<double>, g, dim3(256), 0, st, p->n, (const double *)slot_ptr(p, slot), c0 + o, m, (double *)p->stage, p->PW, d_scale, p->op->perm_d);
+      hipLaunchKernelGGL(k_panel_to_cols<double>, g, dim3(256), 0, st, p->n, (const double *)slot_ptr(p, slot), c0 + o, m, (double *)p->stage, p->PW, d_scale, p->op->perm_d.as<int32_t>());
     else
-      hipLaunchKernelGGL(k_panel_to_cols<float>, g, dim3(256), 0, st, p->n, (const float *)slot_ptr(p, slot), c0 + o, m, (float *)p->stage, p->PW, d_scale, p->op->perm_d);
+      hipLaunchKernelGGL(k_panel_to_cols<float>, g, dim3(256), 0, st, p->n, (const float *)slot_ptr(p, slot), c0 + o, m, (float *)p->stage, p->PW, d_scale, p->op->perm_d.as<int32_t>());
     HIP_TRY(hipMemcpy2DAsync((char *)X + (size_t)o * (size_t)ldx * p->esz, (size_t)ldx * p->esz, p->stage,
                              (size_t)p->n * p->esz, (size_t)p->n * p->esz, (size_t)m, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -2458,9 +2237,9 @@ static int launch_dense_mfma(slq_plan *p, const void *Wc, const void *Wp, void *
     const int ks = p->dense_ks;
     float *raw = (float *)p->T + p->slot_stride;  // slabs 1..ks of T (slab 0 is the unfused product)
     const dim3 g((p->n + kDense32BM - 1) / kDense32BM, p->NP, ks);
-    const int a_vec = op->lda % 4 == 0 && ((uintptr_t)op->vals & 15) == 0;
+    const int a_vec = op->lda % 4 == 0 && ((uintptr_t)op->csr.vals.p & 15) == 0;
     for (int col0 = 0; col0 < p->PW; col0 += kDense32BN)  // PW = 128 / 256: A streamed once per 64 columns (32 flop per byte of A: still MFMA-bound)
-      k_dense_mfma32_lds<<<g, dim3(kBlock), 0, st>>>(p->n, (const float *)op->vals, op->lda, a_vec, (const float *)Wc, p->PW, col0, raw, p->slot_stride);
+      k_dense_mfma32_lds<<<g, dim3(kBlock), 0, st>>>(p->n, op->csr.vals.as<const float>(), op->lda, a_vec, (const float *)Wc, p->PW, col0, raw, p->slot_stride);
     const dim3 gS(p->nblkS, p->NP);
     DISPATCH(SLQ_F32, p->LPR,
              (k_3term_slabs<F, L><<<gS, dim3(kBlock), 0, st>>>(p->n, (const F *)raw, ks, p->slot_stride, (const F *)Wc, (const F *)Wp, (F *)Wn,
@@ -2476,11 +2255,11 @@ static int launch_dense_mfma(slq_plan *p, const void *Wc, const void *Wp, void *
     const dim3 g((p->n + rw - 1) / rw, p->NP, ks);
     for (int col0 = 0; col0 < p->PW; col0 += 32 * ncg) {  // PW = 128: two 64-column halves, A streamed twice
       if (kernel == DENSE_K_LDS)
-        k_dense_mfma_lds<2><<<g, dim3(kBlock), 0, st>>>(p->n, (const double *)op->vals, op->lda, (const double *)Wc, p->PW, col0, raw, p->slot_stride);
+        k_dense_mfma_lds<2><<<g, dim3(kBlock), 0, st>>>(p->n, op->csr.vals.as<const double>(), op->lda, (const double *)Wc, p->PW, col0, raw, p->slot_stride);
       else if (ncg == 2)
-        k_dense_mfma_tile<2><<<g, dim3(kBlock), 0, st>>>(p->n, (const double *)op->vals, op->lda, (const double *)Wc, p->PW, col0, raw, p->slot_stride);
+        k_dense_mfma_tile<2><<<g, dim3(kBlock), 0, st>>>(p->n, op->csr.vals.as<const double>(), op->lda, (const double *)Wc, p->PW, col0, raw, p->slot_stride);
       else
-        k_dense_mfma_tile<1><<<g, dim3(kBlock), 0, st>>>(p->n, (const double *)op->vals, op->lda, (const double *)Wc, p->PW, col0, raw, p->slot_stride);
+        k_dense_mfma_tile<1><<<g, dim3(kBlock), 0, st>>>(p->n, op->csr.vals.as<const double>(), op->lda, (const double *)Wc, p->PW, col0, raw, p->slot_stride);
     }
     // second stage: sum the slabs in slab order, three-term epilogue and alpha partials (or the plain product)
     const dim3 gS(p->nblkS, p->NP);
@@ -2497,7 +2276,7 @@ static int launch_dense_mfma(slq_plan *p, const void *Wc, const void *Wp, void *
 #define DENSE_LAUNCH(TWV, COL0)                                                                             \
   {                                                                                                         \
     const size_t lds = ((size_t)kWaves * (TWV / 16) * 4 * 64 + (size_t)TWV * 4) * sizeof(double);          \
-    k_dense_mfma_3term<TWV><<<g, dim3(kBlock), lds, st>>>(p->n, (const double *)op->vals, op->lda, (const double *)Wc,        \
+    k_dense_mfma_3term<TWV><<<g, dim3(kBlock), lds, st>>>(p->n, op->csr.vals.as<const double>(), op->lda, (const double *)Wc,        \
                                                         (const double *)Wp, (double *)Wn, p->st.coefA, p->part, p->bpad, first, plain, p->PW, COL0); \
   }
   switch (p->PW) {
@@ -2551,7 +2330,7 @@ static int apply_operator_unfused(slq_plan *p, int slot_c) {
     PROFILED(p, SLQ_K_SPMM,
              DISPATCH(p->dtype, p->LPR,
                       (k_dense_panel<F, L><<<g, dim3(kBlock), 0, st>>>(p->n,
-                                          (const F *)(op->vals_t ? op->vals_t : op->vals), op->lda, (const F *)slot_ptr(p, slot_c), (F *)p->T))));
+                                          (op->dense_t ? op->dense_t : op->csr.vals).as<const F>(), op->lda, (const F *)slot_ptr(p, slot_c), (F *)p->T))));
     return SLQ_OK;
   }
   if (op->kind == OP_GRAM) {
@@ -2559,11 +2338,11 @@ static int apply_operator_unfused(slq_plan *p, int slot_c) {
     const dim3 g1(std::max(1, std::min(p->nblkS, (int)((op->mrows + kWaves - 1) / kWaves))), p->NP), g2(p->nblkS, p->NP);
     PROFILED(p, SLQ_K_SPMM,
              DISPATCH(p->dtype, p->LPR,
-                      (k_spmm_plain<F, L><<<g1, dim3(kBlock), 0, st>>>((int)op->mrows, op->rowptr, op->colind, (const F *)op->vals,
+                      (k_spmm_plain<F, L><<<g1, dim3(kBlock), 0, st>>>((int)op->mrows, op->csr.rp(), op->csr.ci(), op->csr.vals.as<const F>(),
                                                                    (const F *)slot_ptr(p, slot_c), (F *)p->T2, p->n))));
     PROFILED(p, SLQ_K_SPMM,
              DISPATCH(p->dtype, p->LPR,
-                      (k_spmm_plain<F, L><<<g2, dim3(kBlock), 0, st>>>(p->n, op->rowptr_t, op->colind_t, (const F *)op->vals_t,
+                      (k_spmm_plain<F, L><<<g2, dim3(kBlock), 0, st>>>(p->n, op->transposed.rp(), op->transposed.ci(), op->transposed.vals.as<const F>(),
                                                                    (const F *)p->T2, (F *)p->T, (int)op->mrows))));
     return SLQ_OK;
   }
@@ -2606,9 +2385,9 @@ static int apply_operator_unfused(slq_plan *p, int slot_c) {
     HIP_TRY(hipMemcpyAsync(p->stage, hy + colb * c0, colb * nc, hipMemcpyHostToDevice, st));
     dim3 g((p->n + 63) / 64, (nc + 63) / 64);
     if (p->dtype == SLQ_F64)
-      hipLaunchKernelGGL(k_cols_to_panel<double>, g, dim3(256), 0, st, p->n, (const double *)p->stage, c0, nc, (double *)p->T, p->PW, p->op->perm_d);
+      hipLaunchKernelGGL(k_cols_to_panel<double>, g, dim3(256), 0, st, p->n, (const double *)p->stage, c0, nc, (double *)p->T, p->PW, p->op->perm_d.as<int32_t>());
     else
-      hipLaunchKernelGGL(k_cols_to_panel<float>, g, dim3(256), 0, st, p->n, (const float *)p->stage, c0, nc, (float *)p->T, p->PW, p->op->perm_d);
+      hipLaunchKernelGGL(k_cols_to_panel<float>, g, dim3(256), 0, st, p->n, (const float *)p->stage, c0, nc, (float *)p->T, p->PW, p->op->perm_d.as<int32_t>());
     HIP_TRY(hipStreamSynchronize(st));
   }
   return SLQ_OK;
@@ -2665,7 +2444,7 @@ static inline void launch_csr_pass(bool pipe_on, dim3 grid, size_t lds, hipStrea
 
 template <typename F, int L, int RC> static inline void launch_csr_updateg_rc(slq_plan *p, bool pipe_on, dim3 grid, size_t lds, hipStream_t st, int j, int xt) {
   const slq_operator *op = p->op;
-  launch_csr_pass<F, L, PASS_UPDATEG, 1, RC>(pipe_on, grid, lds, st, p->n, op->rowptr, op->colind, (const F *)op->vals, (F *)p->ring, p->slot_stride, p->S, j, p->st.coefA,
+  launch_csr_pass<F, L, PASS_UPDATEG, 1, RC>(pipe_on, grid, lds, st, p->n, op->csr.rp(), op->csr.ci(), op->csr.vals.as<const F>(), (F *)p->ring, p->slot_stride, p->S, j, p->st.coefA,
                                              p->st.coefB, p->st.gamma, p->part, p->bpad, xt);
 }
 
@@ -2681,9 +2460,15 @@ static inline void launch_tile_pass(slq_plan *p, dim3 grid, size_t lds, hipStrea
       if (op->tiles_ringed) {
         // the ring-fed variant: flag words and descriptor staging + kRingSlots slots; 16 waves per workgroup
         const size_t lds_ring = kRingHeadBytes + (size_t)kRingSlots * (kRingTileCols * 1024 + kRingMetaBytes);
+        // (the base tiles' full stream whatever stream the plan's other passes read; the upper one is the plan's)
+        const TileStream *ts = upper ? p->rs_upper : &op->streams[0].full;
+        if (!ts) {
+          p->launch_error = true;
+          return;
+        }
         if (upper)
-          for (int x = 0; x < 9; ++x) xr.first[x] = p->rs_xcd_u[x];
-        k_csr_ring_pass<F, PASS, LP, RC><<<grid, dim3(kRingBlock), lds_ring, st>>>(p->n, upper ? p->rs_desc_u : op->tile_desc, upper ? p->rs_rec_u : op->tile_rec, xr, (F *)p->ring, p->slot_stride, p->S, j, p->st.coefA,
+          for (int x = 0; x < 9; ++x) xr.first[x] = p->shape.rs_xcd_u[x];
+        k_csr_ring_pass<F, PASS, LP, RC><<<grid, dim3(kRingBlock), lds_ring, st>>>(p->n, ts->desc.as<int32_t>(), ts->rec.as<char>(), xr, (F *)p->ring, p->slot_stride, p->S, j, p->st.coefA,
                                                                                p->st.coefB, p->st.gamma, p->part, p->bpad, xt, p->ring_fail_d);
         return;
       }
@@ -2693,8 +2478,8 @@ static inline void launch_tile_pass(slq_plan *p, dim3 grid, size_t lds, hipStrea
       return;
     }
     if constexpr (PASS != PASS_SPMM)
-    k_csr_tile_pass<F, PASS, LP, RC><<<grid, dim3(kBlock), lds, st>>>(p->n, op->rowptr, (const F *)op->vals, op->tiles.tile_row, op->tiles.tile_ptr,
-                                                                    op->tiles.tile_cols, op->tiles.lcol, op->tiles.self_idx, xr, op->tiles.max_cols, (F *)p->ring,
+    k_csr_tile_pass<F, PASS, LP, RC><<<grid, dim3(kBlock), lds, st>>>(p->n, op->csr.rp(), op->csr.vals.as<const F>(), op->tiles.tile_row.as<int32_t>(), op->tiles.tile_ptr.as<int32_t>(),
+                                                                    op->tiles.tile_cols.as<int32_t>(), op->tiles.lcol.as<int32_t>(), op->tiles.self_idx.as<int32_t>(), xr, op->tiles.max_cols, (F *)p->ring,
                                                                     p->slot_stride, p->S, j, p->st.coefA, p->st.coefB, p->st.gamma, p->part, p->bpad, xt);
   }
 }
@@ -2716,9 +2501,11 @@ static int launch_ring_gen(slq_plan *p, int pass, int rc, dim3 grid, hipStream_t
   a.grid = grid;
   a.st = st;
   a.n = p->n;
-  a.desc = upper ? p->rs_desc_u : p->rs_desc;
-  a.rec = upper ? p->rs_rec_u : p->rs_rec;
-  for (int x = 0; x < 9; ++x) a.xr.first[x] = upper ? p->rs_xcd_u[x] : p->rs_xcd[x];
+  const TileStream *ts = upper ? p->rs_upper : p->rs_full;
+  if (!ts) return fail(SLQ_EINVAL, "a ring-fed pass without its tile stream");
+  a.desc = ts->desc.as<int32_t>();
+  a.rec = ts->rec.as<char>();
+  for (int x = 0; x < 9; ++x) a.xr.first[x] = upper ? p->shape.rs_xcd_u[x] : p->shape.rs_xcd[x];
   a.ring = p->ring;
   a.slot_stride = p->slot_stride;
   a.S = p->S;
@@ -2790,8 +2577,8 @@ struct RunFrame {
     else                                                                                             \
       DISPATCH(p->dtype, p->LPR,                                                                     \
                (launch_csr_pass<F, L, PASS, LP, RCT>(s.pipe_on != 0, (PASS == PASS_ALPHA ? c.gAf : c.gU), lds, c.st, p->n, \
-                   half ? op->rowptr_u : op->rowptr, half ? op->colind_u : op->colind,               \
-                   (const F *)(half ? op->vals_u : op->vals), (F *)p->ring, p->slot_stride, p->S, j, \
+                   (half ? op->upper : op->csr).rp(), (half ? op->upper : op->csr).ci(),               \
+                   (half ? op->upper : op->csr).vals.as<const F>(), (F *)p->ring, p->slot_stride, p->S, j, \
                    p->st.coefA, p->st.coefB, p->st.gamma, p->part, p->bpad, xt)));                   \
   } while (0)
 #define CSR_PASS(PASS, LP)                                                                           \
@@ -2922,7 +2709,7 @@ static int launch_sweep_product(const RunFrame &c, const seq::StepShape &s, int 
 #define SPMM_LAUNCH(LP, SP)                                                                          \
   DISPATCH(p->dtype, p->LPR,                                                                         \
            (k_spmm_3term<F, L, LP, SP><<<c.gA, dim3(kBlock), spmm_pad, st>>>(                        \
-               p->n, op->rowptr, op->colind, (const F *)op->vals, (const F *)slot_ptr(p, sc_),       \
+               p->n, op->csr.rp(), op->csr.ci(), op->csr.vals.as<const F>(), (const F *)slot_ptr(p, sc_),       \
                (const F *)slot_ptr(p, sp_), (F *)slot_ptr(p, sn_), p->st.coefA, p->part, bp, first)))
       PROFILED(p, SLQ_K_SPMM, {
         switch (c.nt ? 11 : 0) {  // tens digit: load policy, units: store policy
@@ -3741,8 +3528,8 @@ extern "C" int slq_diag_get(slq_diag *d, double *numer, double *denom, double *r
   HIP_TRY(hipStreamSynchronize(st));
   if (running_mean && d->count > 0)
     for (int64_t i = 0; i < d->n; ++i) running_mean[i] /= (double)d->count;
-  if (d->op && d->op->perm_h) {  // stored row i is caller row perm[i]
-    const std::vector<int32_t> &perm = *d->op->perm_h;
+  if (d->op && !d->op->perm_h.empty()) {  // stored row i is caller row perm[i]
+    const std::vector<int32_t> &perm = d->op->perm_h;
     std::vector<double> tmp((size_t)d->n);
     for (double *arr : {numer, denom, running_mean}) {
       if (!arr) continue;
@@ -4095,7 +3882,7 @@ extern "C" int slq_plan_fun_action_dmat(slq_plan *p, int fun_id, const double *f
   hipStream_t st = p->ctx->stream;
   dim3 g((p->n + 63) / 64, (p->nprobes + 63) / 64);
   hipLaunchKernelGGL(k_panel_to_cols<double>, g, dim3(256), 0, st, p->n, (const double *)slot_ptr(p, p->y_slot), 0, p->nprobes,
-                     OUT->d + (size_t)o0 * p->n, p->PW, (const double *)nullptr, p->op->perm_d);
+                     OUT->d + (size_t)o0 * p->n, p->PW, (const double *)nullptr, p->op->perm_d.as<int32_t>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
   return SLQ_OK;
@@ -4111,7 +3898,7 @@ extern "C" int slq_plan_chebyshev_action_dmat(slq_plan *p, double center, double
   hipStream_t st = p->ctx->stream;
   dim3 g((p->n + 63) / 64, (p->nprobes + 63) / 64);
   hipLaunchKernelGGL(k_panel_to_cols<double>, g, dim3(256), 0, st, p->n, (const double *)slot_ptr(p, p->y_slot), 0, p->nprobes,
-                     OUT->d + (size_t)o0 * p->n, p->PW, (const double *)nullptr, p->op->perm_d);
+                     OUT->d + (size_t)o0 * p->n, p->PW, (const double *)nullptr, p->op->perm_d.as<int32_t>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
   return SLQ_OK;
@@ -4129,7 +3916,7 @@ extern "C" int slq_plan_get_probes_dmat(slq_plan *p, slq_dmat *OUT, int o0) {
   k_probe_scale<<<dim3((p->bpad + 255) / 256), dim3(256), 0, st>>>(p->st, p->st.coefB);
   dim3 g((p->n + 63) / 64, (p->nprobes + 63) / 64);
   hipLaunchKernelGGL(k_panel_to_cols<double>, g, dim3(256), 0, st, p->n, (const double *)slot_ptr(p, 0), 0, p->nprobes,
-                     OUT->d + (size_t)o0 * p->n, p->PW, (const double *)p->st.coefB, p->op->perm_d);
+                     OUT->d + (size_t)o0 * p->n, p->PW, (const double *)p->st.coefB, p->op->perm_d.as<int32_t>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
   return SLQ_OK;
@@ -4332,9 +4119,9 @@ extern "C" int slq_plan_set_probes_device(slq_plan *p, const void *d_X, int64_t 
   dim3 g((p->n + 63) / 64, (p->nprobes + 63) / 64);
   PROFILED(p, SLQ_K_PROBES, {
     if (p->dtype == SLQ_F64)
-      hipLaunchKernelGGL(k_cols_to_panel<double>, g, dim3(256), 0, st, p->n, (const double *)d_X, 0, p->nprobes, (double *)slot_ptr(p, 0), p->PW, p->op->perm_d);
+      hipLaunchKernelGGL(k_cols_to_panel<double>, g, dim3(256), 0, st, p->n, (const double *)d_X, 0, p->nprobes, (double *)slot_ptr(p, 0), p->PW, p->op->perm_d.as<int32_t>());
     else
-      hipLaunchKernelGGL(k_cols_to_panel<float>, g, dim3(256), 0, st, p->n, (const float *)d_X, 0, p->nprobes, (float *)slot_ptr(p, 0), p->PW, p->op->perm_d);
+      hipLaunchKernelGGL(k_cols_to_panel<float>, g, dim3(256), 0, st, p->n, (const float *)d_X, 0, p->nprobes, (float *)slot_ptr(p, 0), p->PW, p->op->perm_d.as<int32_t>());
   });
   p->pdf_sphere = 0;
   return init_from_probes(p, 0);
@@ -4538,8 +4325,8 @@ extern "C" int slq_operator_matmat(slq_operator *op, const void *X, int64_t ldx,
     if (op->kind == OP_CSR) {
       dim3 g(p->nblkS, p->NP);
       DISPATCH(p->dtype, p->LPR,
-               (k_spmm_plain<F, L><<<g, dim3(kBlock), 0, st>>>(p->n, op->rowptr, op->colind,
-                                   (const F *)op->vals, (const F *)slot_ptr(p, 0), (F *)slot_ptr(p, 1), p->n)));
+               (k_spmm_plain<F, L><<<g, dim3(kBlock), 0, st>>>(p->n, op->csr.rp(), op->csr.ci(),
+                                   op->csr.vals.as<const F>(), (const F *)slot_ptr(p, 0), (F *)slot_ptr(p, 1), p->n)));
     } else {
       rc = apply_operator_unfused(p, 0);
       if (rc == SLQ_OK) {
@@ -4689,7 +4476,7 @@ static int lanczos_single(slq_context *ctx, slq_operator *op, F *v, int deg, F r
           e = hipMemcpyAsync(p->stage, Q + (size_t)(ncv - k) * n, (size_t)n * sizeof(F), hipMemcpyHostToDevice, st);
           if (e == hipSuccess) {
             dim3 g((n + 63) / 64, 1);
-            k_cols_to_panel<F><<<g, dim3(256), 0, st>>>(n, (const F *)p->stage, 0, 1, (F *)slot_ptr(p, slot), p->PW, op->perm_d);
+            k_cols_to_panel<F><<<g, dim3(256), 0, st>>>(n, (const F *)p->stage, 0, 1, (F *)slot_ptr(p, slot), p->PW, op->perm_d.as<int32_t>());
             e = hipStreamSynchronize(st);
           }
         }

@@ -1,0 +1,158 @@
+// slq_operator.hpp — the operator handle of slq.hip and what it owns, as values: one owning device buffer (DevBuf), a stored CSR
+// (CsrArrays), a ring-fed tile stream (TileStream). Destroying an operator is `delete`: every device array is a member that frees
+// itself, so an array added here cannot leak and a half-built operator goes with everything it has so far.
+#pragma once
+#include "../../include/slq.h"
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <atomic>
+#include <memory>
+#include <mutex>
+#include <utility>
+#include <vector>
+
+#include "slq_common.hpp"
+#include "slq_kernelop.hpp"  // KernelScale
+#include "slq_switches.hpp"
+
+namespace slq {
+
+// bytes the live DevBufs of the process hold (slq_debug_operator_device_bytes: tests)
+inline std::atomic<int64_t> g_devbuf_bytes{0};
+
+// A device allocation that frees itself: every device array an operator owns, and the scratch of a build. Move-only.
+struct DevBuf {
+  void *p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), nbytes(o.nbytes) { o.p = nullptr, o.nbytes = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) {
+      release();
+      std::swap(p, o.p);
+      std::swap(nbytes, o.nbytes);
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  void release() {
+    if (p) {
+      hipFree(p);
+      g_devbuf_bytes -= (int64_t)nbytes;
+    }
+    p = nullptr, nbytes = 0;
+  }
+  hipError_t alloc(size_t bytes) {
+    release();
+    const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 16));
+    if (e != hipSuccess) p = nullptr;
+    else nbytes = bytes, g_devbuf_bytes += (int64_t)bytes;
+    return e;
+  }
+  size_t bytes() const { return nbytes; }  // as asked for (the allocation itself is never shorter than 16)
+  explicit operator bool() const { return p != nullptr; }
+  template <typename T> T *as() const { return (T *)p; }
+
+ private:
+  size_t nbytes = 0;
+};
+
+// A CSR on the device: rowptr [nrows + 1], colind and vals with kCsrPad spare entries behind the nnz stored ones - the batched row
+// gather (slq_kernels.hpp: gather_row_uniform) loads indices and values 8 at a time and may read (never use) up to 7 entries past a
+// row's end. Kernels receive the plain pointers, taken at the launch site.
+struct CsrArrays {
+  DevBuf rowptr, colind, vals;
+  int64_t nnz = 0;
+  // colind and vals alone, for a row pointer that is filled first (the device-side build counts, then fills); the pad is cleared on `st`
+  hipError_t alloc_entries(int64_t nnz_, size_t es, hipStream_t st) {
+    nnz = nnz_;
+    hipError_t e = colind.alloc(((size_t)nnz + kCsrPad) * 4);
+    if (e == hipSuccess) e = vals.alloc(((size_t)nnz + kCsrPad) * es);
+    if (e == hipSuccess) e = hipMemsetAsync(colind.as<int32_t>() + nnz, 0, kCsrPad * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(vals.as<char>() + (size_t)nnz * es, 0, kCsrPad * es, st);
+    return e;
+  }
+  hipError_t alloc(int64_t nrows, int64_t nnz_, size_t es, hipStream_t st) {
+    const hipError_t e = rowptr.alloc((size_t)(nrows + 1) * 4);
+    return e == hipSuccess ? alloc_entries(nnz_, es, st) : e;
+  }
+  void release() {
+    rowptr.release(), colind.release(), vals.release();
+    nnz = 0;
+  }
+  explicit operator bool() const { return (bool)rowptr; }
+  const int32_t *rp() const { return rowptr.as<int32_t>(); }
+  const int32_t *ci() const { return colind.as<int32_t>(); }
+};
+
+// What a ring-fed pass reads: 64 R descriptor words per tile, the tiles' CSR records, the tile ranges of the eight XCD chunks, the
+// longest line list of a tile and whether every row's entries are padded to a multiple of four (build_ring_stream: pad_rows).
+// max_lines may be known of a stream that was then not built (an upper-triangle stream that lands too many panel rows per row).
+struct TileStream {
+  DevBuf desc, rec;
+  int32_t xcd_tile[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int max_lines = 0;
+  bool padded = false;
+  explicit operator bool() const { return (bool)desc; }
+};
+// ... over the full rows, and over the upper triangle (exactly symmetric operators: the alpha-only pass) where the operator has it
+struct TileStreamPair {
+  TileStream full, upper;
+  bool tried = false;  // merged streams: built, or found unbuildable, by the first plan that asked (ensure_ring_stream)
+};
+
+}  // namespace slq
+
+struct slq_context;
+
+struct slq_operator {
+  slq_context *ctx = nullptr;
+  int kind = 0, dtype = 0;
+  int64_t n = 0, nnz = 0;
+  slq::CsrArrays csr;      // the stored rows (OP_GRAM: A, mrows rows; OP_DENSE: vals alone, the matrix)
+  int64_t lda = 0;
+  slq_matvec_fn fn = nullptr;
+  void *user = nullptr;
+  slq_matmat_device_fn dev_fn = nullptr;  // OP_DEVICE_CALLBACK: Y = A X on device buffers, enqueued on our stream
+  slq::DevBuf perm_d, inv_perm_d;  // device: stored row i = caller row perm[i], caller row r = stored row inv_perm[r] (empty: not reordered)
+  std::vector<int32_t> perm_h;     // host copy (diag un-permutation); empty: not reordered
+  // workgroup LDS tiles of the fused passes (tile_ptr empty: none; SLQ_TILES). tile_cols, lcol and self_idx are read by
+  // k_csr_tile_pass only: ring-sized tiles carry them inside their records
+  struct TileLists {
+    slq::DevBuf tile_row, tile_ptr, tile_cols, lcol, self_idx;  // (slq_common.hpp: TileMeta)
+    int32_t xcd_tile[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int max_cols = 0;
+  } tiles;
+  bool tiles_ringed = false;  // ... built to the caps of the ring-fed passes (SLQ_TILES=2), which read streams[]:
+  // by log2 R (slq_plan_shape.hpp: STREAM_BASE, STREAM_MERGED2, STREAM_MERGED4) - [0] the tiles as clustered, whose upper stream has
+  // tiles of its own, runs of the base tiles (regroup_upper_tiles, r04); [1], [2] R = 2, 4 consecutive tiles merged into one for
+  // narrow panels (slq_ring.hpp), built the first time a plan asks for them (ensure_ring_stream), under merged_lock
+  slq::TileStreamPair streams[3];
+  mutable std::mutex merged_lock;  // (taken only where tiles_ringed holds)
+  double upper_per_row = 0.0;      // distinct panel rows per row streams[0].upper lands (what decides whether the alpha-only pass takes it)
+  // exactly symmetric CSR only: upper triangle (diagonal + 2x strict upper) for the alpha pass, whose
+  // q^T A q = sum_i q_i (a_ii q_i + 2 sum_{j>i} a_ij q_j) then gathers half the panel rows (empty: none)
+  slq::CsrArrays upper;
+  double rms_dist = -1.0;    // rms |i - j| over the stored nonzeros inside an XCD chunk (-1: unknown)
+  double far_per_row = 0.0;  // stored nonzeros per row with |i - j| > 4096 (0 when unknown: device-resident CSR)
+  double norm_inf = -1.0;    // largest absolute row sum of a CSR operator (-1: not taken yet; operator_norm_inf takes it once, on the device)
+  // OP_GRAM (x -> A^T (A x), A is mrows x n): csr holds A, transposed its transpose (n rows)
+  int64_t mrows = 0;
+  slq::CsrArrays transposed;
+  slq::DevBuf dense_t;  // OP_DENSE, non-symmetric input only: the transpose, for the kernel that walks A by columns (empty: A == A^T)
+  // affine CSR operator A + t B (slq_csr_affine_create): values of A and B on the union pattern (csr.vals = va + t vb)
+  slq::DevBuf vals_a, vals_b;
+  slq::OperatorSwitches sw;  // the switches as they were when the operator was created (slq_switches.hpp)
+  // OP_KERNEL (slq_kernelop.hpp): the raw points (n x d), z transposed (dpad x npad) and |z|^2 (npad), s and sigma2 in two device
+  // words - all at addresses that never change, so that a captured graph sees a hyperparameter change. nnz reports n d.
+  int k_d = 0, k_dpad = 0, k_profile = 0;
+  int64_t k_npad = 0;
+  slq::DevBuf k_raw;  // one allocation: the points, and behind them what the next three point to
+  void *k_zt = nullptr, *k_nrm = nullptr, *k_params = nullptr;
+  std::unique_ptr<slq::KernelScale> k_scale;  // host: the centre of the points and the lengthscales per dimension
+  double k_s = 1.0, k_noise = 0.0;
+};

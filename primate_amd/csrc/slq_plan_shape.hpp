@@ -35,13 +35,13 @@ struct PlanFacts {
   // operator
   int kind = OP_CSR, dtype = kF64;
   int64_t n = 0, nnz = 0, nnz_u = 0;
-  int upper = 0;            // exactly symmetric CSR: it has the upper-triangle copy (rowptr_u)
+  int upper = 0;            // exactly symmetric CSR: it has the upper-triangle copy (slq_operator::upper)
   int64_t mrows = 0, lda = 0;
   int has_tiles = 0;        // workgroup tiles (tiles.tile_ptr)
   int tiles_ringed = 0;     // ... built to the caps of the ring-fed kernels
   int tiles_max_cols = 0;   // longest line list of a tile
   double upper_per_row = 0.0;  // distinct panel rows per row the upper-triangle stream lands
-  int upper_stream = 0;     // an upper-triangle tile stream exists (tile_desc_u)
+  int upper_stream = 0;     // an upper-triangle tile stream exists (streams[0].upper)
   int upper_padded = 0;     // ... with its rows padded to whole chunks
   double far_per_row = 0.0;
   int affine = 0;           // A + t B: vals_b is set

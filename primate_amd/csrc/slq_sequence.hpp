@@ -19,7 +19,7 @@ struct SequenceFacts {
   int csr = 0;           // a CSR operator (every other kind takes the sweeps)
   int far_le4 = 0;       // far_per_row <= 4: the gathers are served from cache
   int tiles_ringed = 0;  // the operator's tiles are built to the caps of the ring-fed kernels
-  int upper = 0;         // exactly symmetric: it has the upper-triangle copy (rowptr_u)
+  int upper = 0;         // exactly symmetric: it has the upper-triangle copy (slq_operator::upper)
   // plan
   int ringR = 0;         // panel rows per wave instruction of the tile stream the plan uses (0: the plan uses no tiles)
   int rs_desc_u = 0;     // the plan's ring-fed alpha pass has an upper-triangle stream
