@@ -176,6 +176,9 @@ inline void xcd_rcm_permutation(int64_t n, const int32_t *rowptr, const int32_t 
         int32_t far = c;
         bfs(c, false, &far);      // one pseudo-peripheral refinement
         bfs(far, true, nullptr);
+        // a pattern that is not symmetric: the search from `far` follows the stored entries only and need not lead back to c, which no
+        // later pass of this loop would visit again - the order would come out short of the chunk (never taken for a symmetric pattern)
+        if (!seen[(size_t)c]) bfs(c, true, nullptr);
       }
       for (int32_t v : mem) seen[(size_t)v] = 0;
       out.insert(out.end(), order.rbegin(), order.rend());  // reversed (RCM)

@@ -126,7 +126,7 @@ class DeviceOperator:
 				raise ValueError(f"the matrix is on {A.device}, the context on GPU {self.ctx.device}")
 			tdt = torch.float64 if self.dtype == np.float64 else torch.float32
 			crow = A.crow_indices().to(torch.int32).contiguous()
-			col = A.col_indices().to(torch.int32).contiguous()  # (sorted within each row, as torch builds them)
+			col = A.col_indices().to(torch.int32).contiguous()  # (as they are: the library takes unsorted rows and duplicate columns)
 			val = A.values().to(tdt).contiguous()
 			torch.cuda.synchronize(A.device)
 			check(L.slq_csr_create_device(self.ctx._h, dt, self.shape[0], int(val.numel()), C.c_void_p(crow.data_ptr()), C.c_void_p(col.data_ptr()),
