@@ -525,7 +525,7 @@ int slq_plan_window_verify(slq_plan *plan, int *mode, double out[5]);
  * projection coefficient at window position i of step j; len must be (deg + 1) * 9 * panels. */
 int slq_plan_window_census(slq_plan *plan, int32_t *out, int64_t len);
 /* The per-step flags of the last run: read[j * panels + panel] = 1 where the panel's update pass of step j read the oldest column, rescue[...] = 1 where its
- * entry was measured by the rescue kernels; len must be (deg + 1) * panels. (slq_plan_window_verify, _census and _flags are diagnostic entries: the tests' and
+ * entry was measured by the rescue kernel; len must be (deg + 1) * panels. (slq_plan_window_verify, _census and _flags are diagnostic entries: the tests' and
  * the verify mode's view of the recurrence, not part of what a driver needs.) */
 int slq_plan_window_flags(slq_plan *plan, int32_t *read, int32_t *rescue, int64_t len);
 int slq_plan_profile_read(slq_plan *plan, slq_profile *out, int reset);

@@ -192,6 +192,7 @@ struct slq_plan {
   double *om_buf = nullptr;
   int *om_flags = nullptr;
   unsigned long long *om_cnt = nullptr;
+  int *om_ticket = nullptr;   // [NP] tickets of k_omega_rescue_dot, zero between launches (beside the shape's regions: allocated with the plan where omega_on)
   int *om_census = nullptr;   // SLQ_OMEGA=2, any ring-fed Gram plan: non-zero gammas per step, window position and panel (slq_plan_window_census)
   double om_norm = 0.0;       // ||A||_inf of the operator when the plan was created
   bool last_nostore = true;   // the update pass of a run's last step does not store W_deg (plans without a kept basis; SLQ_LAST_STORE=1 stores)
@@ -1451,8 +1452,15 @@ static int prof_begin(slq_plan *p, int kind, ProfEvent *ev) {
     *ev = p->pool.back();
     p->pool.pop_back();
   } else {
-    HIP_TRY(hipEventCreate(&ev->a));
-    HIP_TRY(hipEventCreate(&ev->b));
+    // no system-scope fence behind a record: nothing reads memory on the host behind these events (prof_collect
+    // synchronises the stream first), and the cache writeback would be charged to the kernels around it
+#ifdef SLQ_AB_EVENT_FENCE  // (A/B build: events with the fence)
+    constexpr unsigned ev_flags = hipEventDefault;
+#else
+    constexpr unsigned ev_flags = hipEventDisableSystemFence;
+#endif
+    HIP_TRY(hipEventCreateWithFlags(&ev->a, ev_flags));
+    HIP_TRY(hipEventCreateWithFlags(&ev->b, ev_flags));
   }
   ev->kind = kind;
   HIP_TRY(hipEventRecord(ev->a, p->ctx->stream));
@@ -1631,6 +1639,7 @@ extern "C" int slq_plan_destroy(slq_plan *p) {
   // what later calls allocated on demand
   if (p->at_d) hipFree(p->at_d);
   if (p->at_flags) hipFree(p->at_flags);
+  if (p->om_ticket) hipFree(p->om_ticket);
   if (p->stage) hipFree(p->stage);
   // the workspace table (plan_materialise)
   for (void *q : p->ws)
@@ -1733,7 +1742,12 @@ static int plan_materialise(slq_plan *p) {
     if (ze != hipSuccess) return fail(SLQ_EHIP, "workspace clear: %s", hipGetErrorString(ze));
   }
   SLQ_TRY(set_kernel_attributes(p));
-  if (p->omega_on) SLQ_TRY(operator_norm_inf(p->op, &p->om_norm));
+  if (p->omega_on) {
+    SLQ_TRY(operator_norm_inf(p->op, &p->om_norm));
+    hipError_t te = hipMalloc((void **)&p->om_ticket, (size_t)p->NP * sizeof(int));
+    if (te == hipSuccess) te = hipMemset(p->om_ticket, 0, (size_t)p->NP * sizeof(int));
+    if (te != hipSuccess) return fail(SLQ_EHIP, "rescue tickets: %s", hipGetErrorString(te));
+  }
   return SLQ_OK;
 }
 
@@ -1939,7 +1953,7 @@ extern "C" int slq_plan_window_columns(slq_plan *p, int64_t out[5], int reset) {
 }
 
 // The flags of the last run (diagnostics, tests): read[j * panels + panel] / rescue[...] = 1 where the panel's update pass of step j read the window's
-// oldest column / where its entry was measured by the rescue kernels; rows of steps that were not offered are zero. len = (deg + 1) * panels.
+// oldest column / where its entry was measured by the rescue kernel; rows of steps that were not offered are zero. len = (deg + 1) * panels.
 extern "C" int slq_plan_window_flags(slq_plan *p, int32_t *read, int32_t *rescue, int64_t len) {
   if (!p || !read || !rescue) return fail(SLQ_EINVAL, "plan/read/rescue is NULL");
   const int64_t words = (int64_t)(p->deg + 1) * p->NP;
@@ -2402,6 +2416,20 @@ static int quadrature_lanes(int deg) {
   int lanes = (int)((150 * 1024) / ((size_t)3 * deg * 8));
   return std::max(1, std::min(64, lanes));
 }
+// the launch of k_quadrature: deg <= 64 runs one probe per wave with the Jacobi matrix across the lanes (lanes = 0, no LDS,
+// a workgroup per probe); a longer matrix runs one probe per lane out of LDS
+struct QuadShape {
+  int lanes;
+  unsigned grid;
+  size_t lds;
+};
+static QuadShape quadrature_shape(int deg, int nprobes) {
+#ifndef SLQ_AB_QL_LDS  // (A/B build: the LDS form at every degree)
+  if (deg <= 64) return {0, (unsigned)nprobes, 0};
+#endif
+  const int lanes = quadrature_lanes(deg);
+  return {lanes, (unsigned)((nprobes + lanes - 1) / lanes), (size_t)3 * deg * lanes * 8};
+}
 
 // the generic update pass of the Gram sequence (k_csr_pass<PASS_UPDATEG>, nontemporal streams), r = 1 .. kFusedMaxR ring columns
 template <typename F, int L, int RC> static inline void launch_csr_updateg_rc(slq_plan *p, bool pipe_on, dim3 grid, size_t lds, hipStream_t st, int j, int xt);
@@ -2613,7 +2641,7 @@ static int launch_gram_ring(const RunFrame &c, const seq::StepShape &s, int j) {
   const int bp = p->bpad, r = s.r, S = p->S;
   PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_fused_pass<PASS_ALPHA>(c, s, j, 0, c.lds_alpha(s), s.xt_alpha)));
   // a full window of three columns is offered to the edge recurrence (slq_kernels.hpp: OmegaState): its oldest column is read only
-  // where the panel's flag says so. The launch sequence does not depend on the flags: the two rescue kernels are always there.
+  // where the panel's flag says so. The launch sequence does not depend on the flags: the rescue kernel is always there.
   OmegaState om = c.om_off;
   om.census = p->om_census, om.PW = p->PW, om.NP = p->NP;
   if (s.omega) {
@@ -2631,10 +2659,9 @@ static int launch_gram_ring(const RunFrame &c, const seq::StepShape &s, int j) {
            hipLaunchKernelGGL(k_fin_gram, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, st, p->st, p->part, c.blocks(s.blk_alpha), j, r, c.orth_tol, om));
   if (om.mode == 1 && om.est_prev) {
     double *part_r = p->part + (size_t)p->part_maxblk * bp;  // (behind the alpha partials, which the second pass does not need but the slab layout keeps)
+    // (one launch: the workgroup that finishes a flagged panel last sums its partials and takes the edge position again)
     PROFILED(p, SLQ_K_FINALIZE,
-             DISPATCH(p->dtype, p->LPR, (k_omega_rescue_dot<F, L><<<c.gS, dim3(kBlock), 0, st>>>(p->n, (const F *)p->ring, p->slot_stride, S, j, r, om.rescue + (size_t)j * p->NP, part_r, bp))));
-    PROFILED(p, SLQ_K_FINALIZE,
-             hipLaunchKernelGGL(k_fin_gram_rescue, dim3((bp + 63) / 64), dim3(kFinThreads), 0, st, p->st, part_r, p->nblkS, j, r, c.orth_tol, om));
+             DISPATCH(p->dtype, p->LPR, (k_omega_rescue_dot<F, L><<<c.gS, dim3(kBlock), 0, st>>>(p->n, (const F *)p->ring, p->slot_stride, S, j, r, part_r, p->om_ticket, p->st, c.orth_tol, om))));
   }
   PROFILED(p, SLQ_K_REORTH_UPD, SLQ_TRY(launch_ring_gen(p, PASS_UPDATEG, r, c.gT, st, j, s.xt_update, false, om.mode == 1 ? om.read + (size_t)j * p->NP : nullptr)));
   PROFILED(p, SLQ_K_FINALIZE,
@@ -3187,14 +3214,13 @@ extern "C" int slq_plan_quadrature(slq_plan *p, int fun_id, const double *fun_pa
     hipLaunchKernelGGL(k_rule_reduce, dim3((P + 63) / 64), dim3(64), 0, st, P, deg, p->nodes_d, p->weights_d, p->st.vnorm2, fun_id, p0,
                        p1, p->quad_d);
   } else {
-    const int lanes = quadrature_lanes(deg);
-    const size_t lds = (size_t)3 * deg * lanes * 8;
-    if (lds > 48 * 1024)
+    const QuadShape q = quadrature_shape(deg, P);
+    if (q.lds > 48 * 1024)
       HIP_TRY(hipFuncSetAttribute((const void *)k_quadrature, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIP_TRY(hipMemsetAsync(p->fail_d, 0, sizeof(int), st));
     // (the rule always lands in nodes_d / weights_d: a density update of the same run then needs no QL of its own)
     PROFILED(p, SLQ_K_QUADRATURE,
-             hipLaunchKernelGGL(k_quadrature, dim3((P + lanes - 1) / lanes), dim3(64), lds, st, p->st, lanes, fun_id, p0, p1,
+             hipLaunchKernelGGL(k_quadrature, dim3(q.grid), dim3(64), q.lds, st, p->st, q.lanes, fun_id, p0, p1,
                                 p->quad_d, p->nodes_d, p->weights_d, p->fail_d));
   }
   HIP_TRY(hipGetLastError());
@@ -3672,13 +3698,12 @@ extern "C" int slq_density_update(slq_density *d, slq_plan *p) {
   // the Gauss rule of this run: once per run, whoever asks first (slq_plan_quadrature or a density update)
   int *rule_fail = p->fail_d + 2;
   if (p->rule_src == 0) {
-    const int lanes = quadrature_lanes(deg);
-    const size_t lds = (size_t)3 * deg * lanes * 8;
-    if (lds > 48 * 1024)
+    const QuadShape q = quadrature_shape(deg, P);
+    if (q.lds > 48 * 1024)
       HIP_TRY(hipFuncSetAttribute((const void *)k_quadrature, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIP_TRY(hipMemsetAsync(rule_fail, 0, sizeof(int), st));
     PROFILED(p, SLQ_K_QUADRATURE,
-             hipLaunchKernelGGL(k_quadrature, dim3((P + lanes - 1) / lanes), dim3(64), lds, st, p->st, lanes, (int)SLQ_FUN_NONE, 0.0, 0.0,
+             hipLaunchKernelGGL(k_quadrature, dim3(q.grid), dim3(64), q.lds, st, p->st, q.lanes, (int)SLQ_FUN_NONE, 0.0, 0.0,
                                 (double *)nullptr, p->nodes_d, p->weights_d, rule_fail));
     HIP_TRY(hipGetLastError());
     p->rule_src = 2;
@@ -4195,8 +4220,7 @@ extern "C" int slq_quadrature_batch(slq_context *ctx, int nb, int deg, const dou
   if (!ctx || !d || !e) return fail(SLQ_EINVAL, "ctx/d/e is NULL");
   if (nb <= 0 || deg <= 0 || deg > kMaxDeg) return fail(SLQ_EINVAL, "bad batch size or degree");
   if (fun_id < SLQ_FUN_NONE || fun_id > SLQ_FUN_SOFTSIGN) return fail(SLQ_EINVAL, "Unknown function id %d.", fun_id);
-  const int lanes = quadrature_lanes(deg);
-  const size_t lds = (size_t)3 * deg * lanes * 8;
+  const QuadShape qs = quadrature_shape(deg, nb);
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const int bp = (nb + 63) / 64 * 64;
@@ -4225,12 +4249,12 @@ extern "C" int slq_quadrature_batch(slq_context *ctx, int nb, int deg, const dou
   if (err == hipSuccess) err = hipMemsetAsync(dfail, 0, sizeof(int), st);
   if (err == hipSuccess) {
     k_load_tridiag<<<dim3((bp + 255) / 256), dim3(256), 0, st>>>(s, dd, de, nb);
-    if (lds > 48 * 1024)
+    if (qs.lds > 48 * 1024)
       err = hipFuncSetAttribute((const void *)k_quadrature, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   }
   if (err == hipSuccess) {
     const double p0 = fun_params ? fun_params[0] : 0.0, p1 = fun_params ? fun_params[1] : 0.0;
-    k_quadrature<<<dim3((nb + lanes - 1) / lanes), dim3(64), lds, st>>>(s, lanes, fun_id, p0, p1, dq, dn, dw, dfail);
+    k_quadrature<<<dim3(qs.grid), dim3(64), qs.lds, st>>>(s, qs.lanes, fun_id, p0, p1, dq, dn, dw, dfail);
     err = hipGetLastError();
   }
   int bad = 0;

@@ -1840,9 +1840,8 @@ constexpr int kOmCntOffered = 0, kOmCntRead = 1, kOmCntRescue = 2, kOmCntViol = 
 // slices are folded through LDS in slice order: bitwise reproducible.
 constexpr int kFinSlices = 16;
 constexpr int kFinThreads = 64 * kFinSlices;
-__device__ __forceinline__ double sum_partials(const double *__restrict__ part, int nblk, int bpad,
-                                               int col, double *red /* kFinThreads doubles */) {
-  const int c = threadIdx.x & 63, s = threadIdx.x >> 6;
+// (slice s of one column: partials s, s + kFinSlices, ... on four interleaved accumulators)
+__device__ __forceinline__ double sum_partials_slice(const double *part, int nblk, int bpad, int col, int s) {
   double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
   if (col < bpad) {
     int b = s;
@@ -1854,7 +1853,26 @@ __device__ __forceinline__ double sum_partials(const double *__restrict__ part, 
     }
     for (; b < nblk; b += kFinSlices) a0 += part[(int64_t)b * bpad + col];
   }
-  red[s * 64 + c] = (a0 + a1) + (a2 + a3);
+  return (a0 + a1) + (a2 + a3);
+}
+__device__ __forceinline__ double sum_partials(const double *__restrict__ part, int nblk, int bpad,
+                                               int col, double *red /* kFinThreads doubles */) {
+  const int c = threadIdx.x & 63, s = threadIdx.x >> 6;
+  red[s * 64 + c] = sum_partials_slice(part, nblk, bpad, col, s);
+  __syncthreads();
+  double tot = 0.0;
+#pragma unroll
+  for (int k = 0; k < kFinSlices; ++k) tot += red[k * 64 + c];
+  __syncthreads();
+  return tot;
+}
+// The same sum, bit for bit, by a workgroup of kBlock threads (64 columns x kFinSlices / 2 thread rows: a thread walks
+// the slices s and s + kFinSlices / 2; every addition and the order of the fold are sum_partials').
+__device__ __forceinline__ double sum_partials_kblock(const double *part, int nblk, int bpad, int col, double *red /* kFinThreads doubles */) {
+  static_assert(kBlock * 2 == kFinThreads, "a thread of the sweep workgroup walks two slices");
+  const int c = threadIdx.x & 63, s = threadIdx.x >> 6;
+  red[s * 64 + c] = sum_partials_slice(part, nblk, bpad, col, s);
+  red[(s + kFinSlices / 2) * 64 + c] = sum_partials_slice(part, nblk, bpad, col, s + kFinSlices / 2);
   __syncthreads();
   double tot = 0.0;
 #pragma unroll
@@ -2034,7 +2052,7 @@ __device__ __forceinline__ double omega_edge(const StepState &st, const OmegaSta
     om.D[col] = sproj_m * nut;
     om.rho[col] = rho;
     if (est_in) {
-      // a zero is certified, or the entry is measured after all (k_omega_rescue_dot, k_fin_gram_rescue): never a gamma from an estimate
+      // a zero is certified, or the entry is measured after all (k_omega_rescue_dot): never a gamma from an estimate
       if (!cert) atomicOr(resc_j, 1);
       else need_read = need_read || soon;
     } else {
@@ -2115,16 +2133,26 @@ __global__ __launch_bounds__(kFinThreads) void k_fin_gram(StepState st, const do
 }
 
 // The rescue of an offered step (mode 1): where k_fin_gram could not certify the edge's zero from an estimate, W_j . W_{t-1}
-// is measured after all - W_{t-1} is still in the ring, its slot is the one this step's update pass overwrites. Both kernels
-// are in the launch sequence of every offered step and leave at once where no panel asks (the usual case).
+// is measured after all - W_{t-1} is still in the ring, its slot is the one this step's update pass overwrites. The kernel
+// is in the launch sequence of every offered step and leaves at once where no panel asks (the usual case).
+// A flagged panel: every workgroup writes its partials (partD), makes them visible to the device and draws a ticket from
+// the panel's counter; the one that draws the last ticket sums the partials in sum_partials' order and takes the edge
+// position again on the measured entry (today's rule, nothing estimated), then sets the counter back to zero for the next
+// launch. Nobody waits for anybody: whichever workgroup happens to finish last does the sum, and the sum does not depend
+// on which one it was. The partials come from other XCDs (separate L2s): the ticket is an acquire-release atomic at agent
+// scope and the partials are read behind it.
 template <typename F, int LPR>
 __global__ __launch_bounds__(kBlock) void k_omega_rescue_dot(int n, const F *__restrict__ ring, int64_t slot_stride, int S, int j, int back,
-                                                             const int *__restrict__ rescue /* row j */, double *__restrict__ partD, int bpad) {
+                                                             double *partD, int *ticket /* [NP], zero between launches */, StepState st,
+                                                             double orth_tol, OmegaState om) {
   using VF = typename VecT<F>::type;
   constexpr int V = Geo<F, LPR>::V, PW = Geo<F, LPR>::PW, RPW = Geo<F, LPR>::RPW;
   __shared__ double red[kWaves * 64 * V];
+  __shared__ double red4[kFinThreads];
+  __shared__ int last;
   const int panel = blockIdx.y;
-  if (rescue[panel] == 0) return;  // (uniform over the workgroup)
+  if (om.rescue[(int64_t)j * om.NP + panel] == 0) return;  // (uniform over the workgroup)
+  const int bpad = st.bpad, nblk = gridDim.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane / LPR, cl = lane % LPR;
   const int64_t poff = (int64_t)panel * n * PW + cl * V;
@@ -2137,21 +2165,26 @@ __global__ __launch_bounds__(kBlock) void k_omega_rescue_dot(int n, const F *__r
     acc += *(const VF *)(A + ro) * *(const VF *)(B + ro);
   }
   block_reduce_columns<F, LPR>(acc, red, partD + (int64_t)blockIdx.x * bpad + panel * PW);
-}
-
-// ... and the edge position again on the measured entry: today's rule, nothing estimated. partD: k_omega_rescue_dot's partials.
-__global__ __launch_bounds__(kFinThreads) void k_fin_gram_rescue(StepState st, const double *__restrict__ partD, int nblk, int j, int RC, double orth_tol, OmegaState om) {
-  __shared__ double red4[kFinThreads];
-  const int c0 = blockIdx.x * 64;
-  const int *resc_j = om.rescue + (int64_t)j * om.NP;
-  const int p_lo = min(c0 / om.PW, om.NP - 1), p_hi = min((c0 + 63) / om.PW, om.NP - 1);
-  if ((resc_j[p_lo] | resc_j[p_hi]) == 0) return;  // (uniform over the workgroup; a panel is at least 32 columns wide)
-  const int col = c0 + (threadIdx.x & 63);
-  const double m = sum_partials(partD, nblk, st.bpad, col, red4);
-  if ((threadIdx.x >> 6) == 0 && col < st.bpad && resc_j[min(col / om.PW, om.NP - 1)] != 0) {
-    constexpr int R1 = kFusedMaxR + 1;
-    st.gram[((int64_t)(j & 1) * R1 + RC) * st.bpad + col] = m;
-    st.gamma[(int64_t)(RC - 1) * st.bpad + col] = omega_edge(st, om, j, RC - 1, col, st.coefB[col], orth_tol, true);
+  __threadfence();  // (the writers' own stores, before the workgroup's one ticket)
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int drawn = __hip_atomic_fetch_add(ticket + panel, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    last = drawn == nblk - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  if (threadIdx.x == 0) __hip_atomic_store(ticket + panel, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int RC = back;
+  const int cend = min((panel + 1) * PW, bpad);
+  for (int c0 = panel * PW; c0 < cend; c0 += 64) {  // (uniform over the workgroup: sum_partials_kblock has barriers)
+    const int col = c0 + lane;
+    const double m = sum_partials_kblock(partD, nblk, bpad, col < cend ? col : bpad, red4);
+    if (wave == 0 && col < cend) {
+      constexpr int R1 = kFusedMaxR + 1;
+      st.gram[((int64_t)(j & 1) * R1 + RC) * bpad + col] = m;
+      st.gamma[(int64_t)(RC - 1) * bpad + col] = omega_edge(st, om, j, RC - 1, col, st.coefB[col], orth_tol, true);
+    }
   }
 }
 
@@ -2454,10 +2487,42 @@ __device__ __forceinline__ double apply_fun(int fun_id, double p0, double p1, do
 // (Wilkinson) on the k x k Jacobi matrix one lane holds in LDS columns d, e, z (stride `lanes`; e[i] couples i and
 // i + 1; z = e_1 on entry), carrying only the first row of the eigenvector matrix, then an insertion sort by node
 // (ascending, like LAPACK's output). Returns 1 if an eigenvalue did not converge in 60 sweeps.
-__device__ __forceinline__ int ql_first_row_sorted(double *d, double *e, double *z, int k, int lanes) {
-#define D(i) d[(i) * lanes]
-#define E(i) e[(i) * lanes]
-#define Z(i) z[(i) * lanes]
+// The routine is one text over a storage accessor (D(i) reads, setD(i, v) writes; E, Z alike), so that both forms of storage
+// run the same arithmetic expression for expression:
+//   QlLds   one probe per lane, the matrix in LDS columns of stride `lanes` (any k);
+//   QlWave  one probe per wave, lane i holds d[i], e[i], z[i] in registers (k <= 64). Every index of the QL is uniform over
+//           the wave: a read is a readlane, a write is a write by the owning lane, and every lane runs the scalar
+//           recurrence on equal values. No LDS round trip sits in the chain of hypot and divisions, and a wave runs its
+//           own probe's sweeps, not those of the slowest of 64.
+struct QlLds {
+  double *d, *e, *z;
+  int lanes;
+  __device__ __forceinline__ double D(int i) const { return d[i * lanes]; }
+  __device__ __forceinline__ double E(int i) const { return e[i * lanes]; }
+  __device__ __forceinline__ double Z(int i) const { return z[i * lanes]; }
+  __device__ __forceinline__ void setD(int i, double v) const { d[i * lanes] = v; }
+  __device__ __forceinline__ void setE(int i, double v) const { e[i * lanes] = v; }
+  __device__ __forceinline__ void setZ(int i, double v) const { z[i * lanes] = v; }
+  __device__ __forceinline__ bool owns(int) const { return true; }  // (this lane writes the probe's outputs of index i)
+};
+__device__ __forceinline__ double ql_readlane(double v, int i) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), i), __builtin_amdgcn_readlane(__double2loint(v), i));
+}
+struct QlWave {
+  double d, e, z;
+  int lane;
+  __device__ __forceinline__ double D(int i) const { return ql_readlane(d, i); }
+  __device__ __forceinline__ double E(int i) const { return ql_readlane(e, i); }
+  __device__ __forceinline__ double Z(int i) const { return ql_readlane(z, i); }
+  __device__ __forceinline__ void setD(int i, double v) { d = lane == i ? v : d; }
+  __device__ __forceinline__ void setE(int i, double v) { e = lane == i ? v : e; }
+  __device__ __forceinline__ void setZ(int i, double v) { z = lane == i ? v : z; }
+  __device__ __forceinline__ bool owns(int i) const { return lane == i; }
+};
+template <class A> __device__ __forceinline__ int ql_first_row_sorted(A &a, int k) {
+#define D(i) a.D(i)
+#define E(i) a.E(i)
+#define Z(i) a.Z(i)
   int bad = 0;
   for (int l = 0; l < k; ++l) {
     int iter = 0;
@@ -2482,10 +2547,10 @@ __device__ __forceinline__ int ql_first_row_sorted(double *d, double *e, double 
         double f = s * E(i);
         const double b = c * E(i);
         r = hypot(f, g);
-        E(i + 1) = r;
+        a.setE(i + 1, r);
         if (r == 0.0) {
-          D(i + 1) -= p;
-          E(m) = 0.0;
+          a.setD(i + 1, D(i + 1) - p);
+          a.setE(m, 0.0);
           underflow = true;
           break;
         }
@@ -2494,16 +2559,17 @@ __device__ __forceinline__ int ql_first_row_sorted(double *d, double *e, double 
         g = D(i + 1) - p;
         r = (D(i) - g) * s + 2.0 * c * b;
         p = s * r;
-        D(i + 1) = g + p;
+        a.setD(i + 1, g + p);
         g = c * r - b;
         f = Z(i + 1);
-        Z(i + 1) = s * Z(i) + c * f;
-        Z(i) = c * Z(i) - s * f;
+        const double zi = Z(i);
+        a.setZ(i + 1, s * zi + c * f);
+        a.setZ(i, c * zi - s * f);
       }
       if (underflow) continue;
-      D(l) -= p;
-      E(l) = g;
-      E(m) = 0.0;
+      a.setD(l, D(l) - p);
+      a.setE(l, g);
+      a.setE(m, 0.0);
     }
   }
   // insertion sort by node
@@ -2511,19 +2577,49 @@ __device__ __forceinline__ int ql_first_row_sorted(double *d, double *e, double 
     const double dv = D(i), zv = Z(i);
     int jj = i - 1;
     for (; jj >= 0 && D(jj) > dv; --jj) {
-      D(jj + 1) = D(jj);
-      Z(jj + 1) = Z(jj);
+      a.setD(jj + 1, D(jj));
+      a.setZ(jj + 1, Z(jj));
     }
-    D(jj + 1) = dv;
-    Z(jj + 1) = zv;
+    a.setD(jj + 1, dv);
+    a.setZ(jj + 1, zv);
   }
   return bad;
 #undef D
 #undef E
 #undef Z
 }
+__device__ __forceinline__ int ql_first_row_sorted(double *d, double *e, double *z, int k, int lanes) {
+  QlLds a{d, e, z, lanes};
+  return ql_first_row_sorted(a, k);
+}
 
-// One probe per lane; d, e, z live in LDS as [k][lanes] so a wave's accesses are conflict-free.
+// The rule of probe `col` from the Jacobi matrix in `a`, and f summed over it in index order (both storage forms).
+template <class A>
+__device__ __forceinline__ void quadrature_rule(A &a, const StepState &st, int col, int fun_id, double p0, double p1, double *__restrict__ quad,
+                                                double *__restrict__ nodes, double *__restrict__ weights, int *__restrict__ fail) {
+  const int k = st.deg;
+  const int bad = ql_first_row_sorted(a, k);
+  double s = 0.0;
+  for (int i = 0; i < k; ++i) {
+    const double th = a.D(i), tau = a.Z(i) * a.Z(i);
+    if (a.owns(i)) {
+      if (nodes) nodes[(int64_t)col * k + i] = th;
+      if (weights) weights[(int64_t)col * k + i] = tau;
+    }
+    if (fun_id >= 0) s += apply_fun(fun_id, p0, p1, th) * tau;
+  }
+  if (a.owns(0)) {
+    if (quad) {
+      const double vn2 = st.vnorm2[col];
+      // an all-zero probe is 0/0 in the reference (lanczos.h:120): surface it as NaN
+      quad[col] = (vn2 > 0.0) ? s * vn2 : __builtin_nan("");
+    }
+    if (bad) atomicOr(fail, 1);
+  }
+}
+
+// k > 64 (lanes >= 1): one probe per lane; d, e, z live in LDS as [k][lanes] so a wave's accesses are conflict-free.
+// k <= 64 (lanes = 0): one probe per wave, the matrix across the lanes' registers (QlWave above).
 // Implicit-shift QL (Wilkinson shift) carrying only the first row of the eigenvector matrix:
 // nodes = eigenvalues of T_k, weights = z^2 (Golub-Welsch; reference: integrate.py:61-64 via
 // LAPACK stemr, tridiag.py:10-11). Nodes are sorted ascending like LAPACK's output.
@@ -2537,40 +2633,29 @@ __global__ __launch_bounds__(64) void k_quadrature(StepState st, int lanes, int 
   extern __shared__ double lds[];
   const int k = st.deg;
   const int lane = threadIdx.x;
+  if (lanes == 0) {
+    // k <= 64: one probe per wave (QlWave), the grid is the probes; lane i holds row i of the Jacobi matrix
+    QlWave a;
+    a.lane = lane;
+    a.d = lane < k ? st.alpha[(int64_t)lane * st.bpad + blockIdx.x] : 0.0;
+    a.e = lane + 1 < k ? st.nu[(int64_t)(lane + 1) * st.bpad + blockIdx.x] : 0.0;
+    a.z = lane == 0 ? 1.0 : 0.0;
+    quadrature_rule(a, st, blockIdx.x, fun_id, p0, p1, quad, nodes, weights, fail);
+    return;
+  }
   // `lanes` <= 64 probes per workgroup: the LDS stride, chosen by the host so 3*k*lanes doubles fit
   const int col = blockIdx.x * lanes + lane;
   const int ll = lane < lanes ? lane : 0;
-  double *d = lds + ll, *e = lds + k * lanes + ll, *z = lds + 2 * k * lanes + ll;
-#define D(i) d[(i) * lanes]
-#define E(i) e[(i) * lanes]
-#define Z(i) z[(i) * lanes]
+  QlLds a{lds + ll, lds + k * lanes + ll, lds + 2 * k * lanes + ll, lanes};
   const bool live = lane < lanes && col < st.nprobes;
   if (!live) return;
   for (int i = 0; i < k; ++i) {
-    D(i) = live ? st.alpha[(int64_t)i * st.bpad + col] : 0.0;
+    a.setD(i, st.alpha[(int64_t)i * st.bpad + col]);
     // E(i) couples i and i+1: beta_{i+1} = nu[i+1]
-    E(i) = (live && i + 1 < k) ? st.nu[(int64_t)(i + 1) * st.bpad + col] : 0.0;
-    Z(i) = (i == 0) ? 1.0 : 0.0;
+    a.setE(i, i + 1 < k ? st.nu[(int64_t)(i + 1) * st.bpad + col] : 0.0);
+    a.setZ(i, (i == 0) ? 1.0 : 0.0);
   }
-  if (live) {
-    const int bad = ql_first_row_sorted(d, e, z, k, lanes);
-    double s = 0.0;
-    for (int i = 0; i < k; ++i) {
-      const double th = D(i), tau = Z(i) * Z(i);
-      if (nodes) nodes[(int64_t)col * k + i] = th;
-      if (weights) weights[(int64_t)col * k + i] = tau;
-      if (fun_id >= 0) s += apply_fun(fun_id, p0, p1, th) * tau;
-    }
-    if (quad) {
-      const double vn2 = st.vnorm2[col];
-      // an all-zero probe is 0/0 in the reference (lanczos.h:120): surface it as NaN
-      quad[col] = (vn2 > 0.0) ? s * vn2 : __builtin_nan("");
-    }
-    if (bad) atomicOr(fail, 1);
-  }
-#undef D
-#undef E
-#undef Z
+  quadrature_rule(a, st, col, fun_id, p0, p1, quad, nodes, weights, fail);
 }
 
 

@@ -389,7 +389,8 @@ inline PlanShape plan_shape(const PlanFacts &f, const PlanSwitches &sw) {
     seq::derive_plan_flags(q);  // (the derived flags do not depend on omega_on)
     // the edge recurrence: full windows of three columns on the ring-fed Gram sequence (r = 4 .. 8: not offered; the rescue needs the
     // column that leaves the window still in the ring: orth + 1 slots at least)
-    // (k_fin_gram_rescue's early exit looks at the first and the last panel under a block of 64 columns: panels of 32 columns at least)
+    // (panels of 32 columns at least: the bound of the rescue's former second kernel, whose early exit looked at the first and the last
+    // panel under a block of 64 columns; the single launch does not need it, the plans that are offered stay the same)
     s.omega_on = q.gram && sw.omega != 0 && orth == 3 && s.S >= 4 && !f.affine && s.PW >= 32;
     q.omega_on = s.omega_on;
   }

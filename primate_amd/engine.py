@@ -512,7 +512,7 @@ class LanczosPlan:
 
 	def window_flags(self) -> tuple:
 		"""(read, rescue), each [deg + 1, panels]: where the update pass of step j read the window's oldest column, and where its entry was
-		measured by the rescue kernels, in the last run (slq_plan_window_flags; zero rows for steps that were not offered)."""
+		measured by the rescue kernel, in the last run (slq_plan_window_flags; zero rows for steps that were not offered)."""
 		panels = self.describe()["panels"]
 		rd = np.zeros((self.deg + 1, panels), dtype=np.int32)
 		rs = np.zeros((self.deg + 1, panels), dtype=np.int32)
