@@ -482,6 +482,38 @@ int slq_sddmm_destroy(slq_sddmm *s);
 int slq_debug_sddmm_schedule(int64_t n, const int32_t *rowptr, int32_t *row0, int32_t *nrows, int32_t *kind, int64_t *e0, int64_t *e1,
                              int64_t cap, int64_t *nitems, int64_t *info);
 
+/* ---- Hyperparameter gradients of the kernel operator -------------------------------------------------------
+ * For A = s phi(r2) + sigma2 I of slq_kernel_create (d dimensions) and columns of two device matrices Z, W, with
+ * C_ij = sum_c Z_ic W_jc, D_ijk = z_ik - z_jk on the operator's rounded z and chi = -2 dphi/dr2 (rbf exp(-r2/2); matern12
+ * exp(-r)/r, DEFINED 0 at r2 = 0; matern32 3 exp(-sqrt3 r); matern52 (5/3)(1 + sqrt5 r) exp(-sqrt5 r)), an update computes
+ *   g_l[k]   = (s / l_k) sum_ij C_ij chi(r2_ij) D_ijk^2      = sum_c Z_c^T (dA/dl_k) W_c,   k < d
+ *   g_s      =           sum_ij C_ij phi(r2_ij)
+ *   g_sigma2 =           sum_i  C_ii
+ * with r2_ij the operator's own value (its bits, its clamp, 0 on the diagonal). W = probes, Z = f'(A) probes, alpha = 1/N: the
+ * Girard-Hutchinson estimate of d tr f(A) / d theta; Z = W = A^-1 y: the gradient of y^T A^-1 y up to its sign. Nothing of size
+ * n^2 is held and nothing of size n leaves the device.
+ * slq_kernel_grad_create: op must be a kernel operator in fp64 (SLQ_EINVAL names the kind or the dtype otherwise) of ctx. The
+ *   accumulator reads op at every update and does not own it: destroy the accumulator first. The d + 2 values start at 0.
+ * slq_kernel_grad_update: vals = beta * vals + alpha * (the d + 2 sums over columns [z0, z0 + m) of Z and [w0, w0 + m) of W);
+ *   count += m. Columns go 64 to a launch; the chunks of a wider m fold in one after the other. Asynchronous on the context
+ *   stream; no atomics: identical calls give identical bits. beta == 0 does not read the old values. It reads the operator's
+ *   parameters as they are at the call: a slq_kernel_set_parameters between two updates is honoured by the second, and values
+ *   accumulated across such a change mix two operators. SLQ_EINVAL, the values untouched: a NULL handle, a column range outside
+ *   its matrix, m < 1, a matrix that has not n rows, an object of another context, a non-finite alpha or beta.
+ * slq_kernel_grad_get: nvals == d + 2: [0, d) the lengthscales, ALWAYS per dimension (a scalar lengthscale's gradient is their
+ *   sum), [d] the outputscale, [d + 1] the noise; the columns folded in so far (either may be NULL). Synchronises.
+ * slq_kernel_grad_reset: values and count back to 0 (asynchronous). */
+typedef struct slq_kernel_grad slq_kernel_grad;
+int slq_kernel_grad_create(slq_context *ctx, slq_operator *op, slq_kernel_grad **out);
+int slq_kernel_grad_update(slq_kernel_grad *g, slq_dmat *Z, int z0, slq_dmat *W, int w0, int m, double alpha, double beta);
+int slq_kernel_grad_get(slq_kernel_grad *g, double *vals, int nvals, int64_t *count);
+int slq_kernel_grad_reset(slq_kernel_grad *g);
+int slq_kernel_grad_destroy(slq_kernel_grad *g);
+/* The schedule of one update for n points, m columns and a chip of num_cus compute units (csrc/slq_kernelgrad.hpp:
+ * kernel_grad_schedule): rows per block, row blocks, columns per chunk, chunks (launches), j slabs, then slab_begin[0 .. slabs]
+ * (-1 beyond); nout >= 22. No HIP call. */
+int slq_debug_kernel_grad_schedule(int64_t n, int m, int num_cus, int64_t *out, int nout);
+
 /* Per-kernel device time accumulated by HIP events on the context stream (for bench.py's
  * roofline line). enable != 0 turns event recording on for subsequent slq_plan_run calls. */
 enum {

@@ -124,6 +124,12 @@ _SIGNATURES = {
 	"slq_sddmm_reset": (C.c_int, [_P]),
 	"slq_sddmm_destroy": (C.c_int, [_P]),
 	"slq_debug_sddmm_schedule": (C.c_int, [C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64), _P]),
+	"slq_kernel_grad_create": (C.c_int, [_P, _P, _PP]),
+	"slq_kernel_grad_update": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_double, C.c_double]),
+	"slq_kernel_grad_get": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int64)]),
+	"slq_kernel_grad_reset": (C.c_int, [_P]),
+	"slq_kernel_grad_destroy": (C.c_int, [_P]),
+	"slq_debug_kernel_grad_schedule": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int]),
 	"slq_plan_profile_enable": (C.c_int, [_P, C.c_int]),
 	"slq_plan_action_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
 	"slq_plan_sweep_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),

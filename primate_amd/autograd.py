@@ -6,6 +6,9 @@
 `forward` is one `primate_amd.grad.trace_grad` call with `pattern=A_csr` and probes drawn on the device: the value and the
 gradient come out of the same runs, and the gradient stays in HBM (a clone of the accumulator's values). `backward` scales it.
 The operator is rebuilt on every call - its values changed, which is the point.
+
+`kernel_trace_fun` is the same for a Gaussian process's kernel matrix over points: differentiable with respect to lengthscale,
+outputscale and noise (`primate_amd.grad.kernel_trace_grad`; d + 2 numbers, stored on the parameters' devices).
 """
 
 from __future__ import annotations
@@ -53,6 +56,55 @@ class _TraceFun(torch.autograd.Function):
 		return grad_output * G, None, None
 
 
+class _KernelTraceFun(torch.autograd.Function):
+	@staticmethod
+	def forward(ctx, lengthscale, outputscale, noise, X, opts):
+		from .chebyshev import ChebyshevFunction
+		from .grad import kernel_trace_grad
+		from .operators import KernelOperator, MatrixFunction
+
+		o = dict(opts)
+		kernel, method, fun, deg, count, seed = (o.pop(k) for k in ("kernel", "method", "fun", "deg", "count", "seed"))
+		tg = {k: o.pop(k) for k in ("batch", "pdf", "probes") if k in o}
+		tg.setdefault("pdf", "device:rademacher")
+		## an operator of its own on every call: its parameters changed, which is the point
+		K = KernelOperator(X, kernel, lengthscale=lengthscale.detach().cpu().numpy().astype("float64"), outputscale=float(outputscale),
+						   noise=float(noise), dtype="float64")  # fmt: skip
+		M = (MatrixFunction if method == "lanczos" else ChebyshevFunction)(K, fun, deg=deg, **o)
+		try:
+			est, grads, _ = kernel_trace_grad(M, count=count, seed=seed, **tg)
+		finally:
+			if hasattr(M, "close"):
+				M.close()
+		G = [torch.as_tensor(grads[k], dtype=p.dtype, device=p.device).reshape(p.shape)
+			 for k, p in (("lengthscale", lengthscale), ("outputscale", outputscale), ("noise", noise))]  # fmt: skip
+		ctx.save_for_backward(*G)
+		return lengthscale.new_tensor(est)
+
+	@staticmethod
+	def backward(ctx, grad_output):
+		return tuple(grad_output.to(G.device) * G for G in ctx.saved_tensors) + (None, None)
+
+
+def kernel_trace_fun(X, kernel, lengthscale, outputscale, noise, fun="log", deg: int = 30, count: int = 256, seed: int = 0, method: str = "lanczos", **kw):
+	"""The Girard-Hutchinson estimate of tr f(A), A = outputscale * phi(r2) + noise * I over the points X (the KernelOperator of
+	`primate_amd.operators`), as a 0-d tensor differentiable with respect to the three parameter tensors: `lengthscale` (0-d, one
+	element, or one per dimension), `outputscale`, `noise` (floats are taken as constants). X gets NO gradient: the points are data.
+	The value and the gradients come out of the same `count` probes (primate_amd.grad.kernel_trace_grad, fp64); backward is
+	grad_output times the stored gradients. method: "lanczos" (fun in log, exp, identity) or "chebyshev". kw: batch, pdf (default
+	"device:rademacher"), probes go to kernel_trace_grad, everything else to the operator (orth=, t=, bounds=, ...). The same seed
+	gives the same bits."""
+	if method not in METHODS:
+		raise ValueError(f"unknown method '{method}' (one of {', '.join(METHODS)})")
+	if isinstance(X, torch.Tensor):
+		X = X.detach()
+	ls, s, v = (p if isinstance(p, torch.Tensor) else torch.as_tensor(p, dtype=torch.float64) for p in (lengthscale, outputscale, noise))
+	if s.numel() != 1 or v.numel() != 1:
+		raise ValueError("outputscale and noise are single numbers")
+	opts = dict(kw, kernel=kernel, method=method, fun=fun, deg=int(deg), count=int(count), seed=int(seed))
+	return _KernelTraceFun.apply(ls, s, v, X, opts)
+
+
 def trace_fun(A_csr, fun="log", deg: int = 30, count: int = 256, seed: int = 0, method: str = "lanczos", **kw):
 	"""The Girard-Hutchinson estimate of tr f(A) as a 0-d tensor on A's device, differentiable with respect to `A_csr.values()`:
 	the gradient is the estimate of f'(A) on A's own pattern from the same `count` probes (primate_amd.grad.trace_grad).
@@ -60,7 +112,7 @@ def trace_fun(A_csr, fun="log", deg: int = 30, count: int = 256, seed: int = 0, 
 	"chebyshev" (ChebyshevFunction; `dfun=` for a callable). kw: batch, pdf (default "device:rademacher"), symmetric, dfun go to
 	trace_grad, everything else to the operator (orth=, t=, bounds=, damping=, ...). The same seed gives the same bits."""
 	if getattr(A_csr, "_slq_kind", None) == "kernel":
-		raise ValueError("trace_fun: hyperparameter gradients of a KernelOperator are not built (they need a derivative-kernel product)")
+		raise ValueError("trace_fun differentiates the values of a sparse tensor: the hyperparameter gradients of a KernelOperator come from kernel_trace_fun")
 	if not engine._is_torch_csr(A_csr):
 		raise ValueError("trace_fun takes a torch sparse-CSR tensor")
 	if method not in METHODS:

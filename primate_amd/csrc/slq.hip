@@ -38,6 +38,7 @@
 #include "slq_cheb.hpp"      // Chebyshev moments: the kernels of slq_plan_run_chebyshev, _moment_sum, slq_density_update_moments
 #include "slq_sddmm.hpp"     // sampled dense-dense product on a CSR pattern: schedule (sddmm_schedule) and kernel of slq_sddmm_*
 #include "slq_kernelop.hpp"  // matrix-free kernel operator (slq_kernel_*): validation, schedule, k_kernel_rescale, k_kernel_panel
+#include "slq_kernelgrad.hpp"  // hyperparameter gradients of the kernel operator (slq_kernel_grad_*): schedule, k_kernel_grad, k_kernel_grad_sum
 #include "slq_operator.hpp"  // the operator handle and the values it owns (DevBuf, CsrArrays, TileStream)
 
 using namespace slq;
@@ -4098,6 +4099,124 @@ extern "C" int slq_debug_sddmm_schedule(int64_t n, const int32_t *rowptr, int32_
   } catch (const std::bad_alloc &) {
     return fail(SLQ_ENOMEM, "slq_debug_sddmm_schedule: host allocation failed");
   }
+  return SLQ_OK;
+}
+
+// ---- hyperparameter gradients of the kernel operator (schedule and kernels in slq_kernelgrad.hpp) -------------
+struct slq_kernel_grad {
+  slq_context *ctx;
+  slq_operator *op;  // not owned: read at every update (its z, norms and scalars as they are then)
+  int64_t n, count, nparts;
+  int d, dpad;
+  double *vals;  // d + 2
+  double *part;  // nparts x (dpad + 2): one partial per workgroup of a launch
+};
+static const char *op_kind_name(int kind) {
+  switch (kind) {
+    case OP_CSR: return "csr";
+    case OP_DENSE: return "dense";
+    case OP_CALLBACK: return "callback";
+    case OP_DEVICE_CALLBACK: return "device_callback";
+    case OP_GRAM: return "gram";
+    case OP_KERNEL: return "kernel";
+    default: return "?";
+  }
+}
+
+extern "C" int slq_kernel_grad_create(slq_context *ctx, slq_operator *op, slq_kernel_grad **out) {
+  if (!ctx || !op || !out) return fail(SLQ_EINVAL, "slq_kernel_grad_create: ctx/op/out is NULL");
+  *out = nullptr;
+  if (op->kind != OP_KERNEL)
+    return fail(SLQ_EINVAL, "slq_kernel_grad_create: the operator is of kind '%s', not a kernel operator (slq_kernel_create)", op_kind_name(op->kind));
+  if (op->dtype != SLQ_F64) return fail(SLQ_EINVAL, "slq_kernel_grad_create: the operator's dtype is fp32: the accumulator is fp64 only (the device matrices are fp64)");
+  if (op->ctx != ctx) return fail(SLQ_EINVAL, "slq_kernel_grad_create: the operator belongs to another context");
+  if (ctx->dead) return fail(SLQ_EINVAL, "slq_kernel_grad_create: the context has been destroyed");
+  HIP_TRY(hipSetDevice(ctx->device));
+  const KernelGradSchedule S = kernel_grad_schedule(op->n, 1, ctx->num_cus);
+  slq_kernel_grad *g = new (std::nothrow) slq_kernel_grad();
+  if (!g) return fail(SLQ_ENOMEM, "host allocation failed");
+  *g = slq_kernel_grad{ctx, op, op->n, 0, S.nparts(), op->k_d, op->k_dpad, nullptr, nullptr};
+  hipError_t e = hipMalloc((void **)&g->vals, (size_t)(g->d + 2) * 8);
+  if (e == hipSuccess) e = hipMalloc((void **)&g->part, (size_t)g->nparts * (size_t)(g->dpad + 2) * 8);
+  if (e == hipSuccess) e = hipMemsetAsync(g->vals, 0, (size_t)(g->d + 2) * 8, ctx->stream);
+  if (e != hipSuccess) {
+    for (void *p : {(void *)g->vals, (void *)g->part})
+      if (p) hipFree(p);
+    delete g;  // (not yet retained)
+    return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "slq_kernel_grad_create: %s", hipGetErrorString(e));
+  }
+  ctx_retain(ctx);
+  *out = g;
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_grad_destroy(slq_kernel_grad *g) {
+  if (!g) return SLQ_OK;
+  hipSetDevice(g->ctx->device);
+  hipStreamSynchronize(g->ctx->stream);
+  for (void *p : {(void *)g->vals, (void *)g->part})
+    if (p) hipFree(p);
+  ctx_release(g->ctx);
+  delete g;
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_grad_update(slq_kernel_grad *g, slq_dmat *Z, int z0, slq_dmat *W, int w0, int m, double alpha, double beta) {
+  if (!g) return fail(SLQ_EINVAL, "slq_kernel_grad_update: accumulator is NULL");
+  if (m < 1) return fail(SLQ_EINVAL, "slq_kernel_grad_update: m = %d columns (m >= 1)", m);
+  SLQ_TRY(dmat_range(Z, z0, m, "slq_kernel_grad_update(Z)"));
+  SLQ_TRY(dmat_range(W, w0, m, "slq_kernel_grad_update(W)"));
+  if (W->n != g->n || Z->n != g->n)
+    return fail(SLQ_EINVAL, "slq_kernel_grad_update: the operator has %lld points, Z %lld rows, W %lld", (long long)g->n, (long long)Z->n, (long long)W->n);
+  if (W->ctx != g->ctx || Z->ctx != g->ctx) return fail(SLQ_EINVAL, "slq_kernel_grad_update: a matrix belongs to another context");
+  if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(SLQ_EINVAL, "slq_kernel_grad_update: alpha = %g, beta = %g must be finite", alpha, beta);
+  HIP_TRY(hipSetDevice(g->ctx->device));
+  const slq_operator *op = g->op;
+  const KernelGradSchedule S = kernel_grad_schedule(g->n, m, g->ctx->num_cus);
+  if (S.nparts() != g->nparts) return fail(SLQ_EINVAL, "slq_kernel_grad_update: the schedule has %lld workgroups, the accumulator room for %lld", (long long)S.nparts(), (long long)g->nparts);
+  KernelGradScale sc;
+  for (int k = 0; k < kKernelMaxDim; ++k) sc.ls[k] = op->k_scale->ls[k];
+  hipStream_t st = g->ctx->stream;
+  for (int ch = 0; ch < S.ncol_chunks; ++ch) {
+    const int c0 = ch * S.chunk_cols, mc = std::min(S.chunk_cols, m - c0);
+    const KernelGradArgs a{(int)g->n, (int)op->k_npad, g->dpad / 4, (const double *)op->k_zt, (const double *)op->k_nrm,
+                           Z->d + (size_t)(z0 + c0) * g->n, W->d + (size_t)(w0 + c0) * g->n, mc, S.tiles_per_slab, g->part};
+    if (!kernel_grad_launch(op->k_profile, S, a, st)) return fail(SLQ_EINVAL, "slq_kernel_grad_update: no kernel for profile %d", op->k_profile);
+    HIP_TRY(hipGetLastError());
+    // (the chunks run one after the other on the stream: each reads the partials of its own launch)
+    k_kernel_grad_sum<<<dim3(1), dim3(128), 0, st>>>(g->d, g->dpad, g->nparts, g->part, (const double *)op->k_params, sc, alpha, ch == 0 ? beta : 1.0, g->vals);
+    HIP_TRY(hipGetLastError());
+  }
+  g->count += m;
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_grad_get(slq_kernel_grad *g, double *vals, int nvals, int64_t *count) {
+  if (!g) return fail(SLQ_EINVAL, "slq_kernel_grad_get: accumulator is NULL");
+  if (vals && nvals != g->d + 2) return fail(SLQ_EINVAL, "slq_kernel_grad_get: room for %d values, the accumulator holds d + 2 = %d", nvals, g->d + 2);
+  HIP_TRY(hipSetDevice(g->ctx->device));
+  if (vals) HIP_TRY(hipMemcpyAsync(vals, g->vals, (size_t)(g->d + 2) * 8, hipMemcpyDeviceToHost, g->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(g->ctx->stream));
+  if (count) *count = g->count;
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_grad_reset(slq_kernel_grad *g) {
+  if (!g) return fail(SLQ_EINVAL, "slq_kernel_grad_reset: accumulator is NULL");
+  HIP_TRY(hipSetDevice(g->ctx->device));
+  HIP_TRY(hipMemsetAsync(g->vals, 0, (size_t)(g->d + 2) * 8, g->ctx->stream));
+  g->count = 0;
+  return SLQ_OK;
+}
+
+// kernel_grad_schedule() of slq_kernelgrad.hpp as an array: rows per block, row blocks, columns per chunk, chunks, slabs, then
+// slab_begin[0 .. slabs]. No HIP call.
+extern "C" int slq_debug_kernel_grad_schedule(int64_t n, int m, int num_cus, int64_t *out, int nout) {
+  if (!out || nout < 5 + kKernelMaxSlabs + 1) return fail(SLQ_EINVAL, "slq_debug_kernel_grad_schedule: room for %d values", 5 + kKernelMaxSlabs + 1);
+  if (n <= 0 || n >= ((int64_t)1 << 31) - 16 || m <= 0 || num_cus <= 0) return fail(SLQ_EINVAL, "slq_debug_kernel_grad_schedule: 0 < n < 2^31 - 16, m and num_cus positive");
+  const KernelGradSchedule S = kernel_grad_schedule(n, m, num_cus);
+  out[0] = S.rows_per_block, out[1] = S.nrow_blocks, out[2] = S.chunk_cols, out[3] = S.ncol_chunks, out[4] = S.nslabs;
+  for (int z = 0; z <= kKernelMaxSlabs; ++z) out[5 + z] = z <= S.nslabs ? S.slab_begin[z] : -1;
   return SLQ_OK;
 }
 

@@ -1078,6 +1078,61 @@ class SddmmAccumulator:
 			pass
 
 
+def kernel_grad_schedule(n: int, m: int, num_cus: int = 256) -> dict:
+	"""The schedule of one KernelGradAccumulator.update for n points and m columns, as the library cuts it (slq_debug_kernel_grad_schedule;
+	host arithmetic, no device): rows per block, row blocks, columns per chunk, chunks (launches), slabs and their bounds."""
+	out = (C.c_int64 * 22)()
+	check(_capi.lib().slq_debug_kernel_grad_schedule(int(n), int(m), int(num_cus), out, 22))
+	v = list(out)
+	return dict(rows=v[0], nrb=v[1], chunk_cols=v[2], chunks=v[3], slabs=v[4], begin=v[5 : 5 + v[4] + 1], rest=v[5 + v[4] + 1 :])
+
+
+class KernelGradAccumulator:
+	"""Device-resident hyperparameter gradients of a kernel operator (slq_kernel_grad_*): every `update` folds
+	alpha * sum_c Z_c^T (dA/dtheta) W_c, for theta = the d lengthscales, the outputscale and the noise, into d + 2 values. op: a
+	DeviceOperator of kind "kernel" in fp64. The accumulator keeps `op` alive, as a plan does, and reads its parameters as they are at
+	each update: `set_kernel_parameters` between two updates is honoured by the second, and values accumulated across such a change
+	mix two operators."""
+
+	def __init__(self, op: DeviceOperator):
+		if getattr(op, "kind", None) != "kernel":
+			raise ValueError(f"KernelGradAccumulator needs a kernel operator, not kind '{getattr(op, 'kind', None)}'")
+		if np.dtype(op.dtype) != np.float64:
+			raise ValueError(f"KernelGradAccumulator is fp64 only (the device matrices are fp64): the operator is {np.dtype(op.dtype)}")
+		self.op, self.ctx = op, op.ctx
+		self.n, self.d = int(op.shape[0]), int(op.nnz // op.shape[0])
+		h = C.c_void_p()
+		check(_capi.lib().slq_kernel_grad_create(self.ctx._h, op._h, C.byref(h)))
+		self._h = h
+
+	def update(self, Z: "DeviceMatrix", z0: int, W: "DeviceMatrix", w0: int, m: int, alpha: float = 1.0, beta: float = 1.0):
+		"""vals = beta * vals + alpha * (the d + 2 sums over columns [z0, z0 + m) of Z and [w0, w0 + m) of W). Asynchronous on the
+		context stream."""
+		check(_capi.lib().slq_kernel_grad_update(self._h, Z._h, int(z0), W._h, int(w0), int(m), float(alpha), float(beta)))
+
+	def get(self) -> tuple:
+		"""(vals, count): [0, d) the lengthscale gradients per dimension, [d] the outputscale's, [d + 1] the noise's; the columns
+		folded in."""
+		vals = np.zeros(self.d + 2)
+		cnt = C.c_int64()
+		check(_capi.lib().slq_kernel_grad_get(self._h, ptr(vals), self.d + 2, C.byref(cnt)))
+		return vals, cnt.value
+
+	def reset(self):
+		check(_capi.lib().slq_kernel_grad_reset(self._h))
+
+	def close(self):
+		if getattr(self, "_h", None):
+			_capi.lib().slq_kernel_grad_destroy(self._h)
+			self._h = None
+
+	def __del__(self):
+		try:
+			self.close()
+		except Exception:  # noqa: BLE001
+			pass
+
+
 class _CudaArrayView:
 	"""Flat fp64 device array described by the CUDA array interface (v2); keeps its owner alive."""
 

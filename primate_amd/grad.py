@@ -7,6 +7,11 @@ Both factors are already on the device after a run - the probes (`plan.get_probe
 one Chebyshev action) - and engine.SddmmAccumulator contracts them on the pattern (slq_sddmm_update): nothing of size n leaves
 the GPU, and one run per batch yields the value and the gradient. `primate_amd.autograd.trace_fun` puts a torch
 `autograd.Function` on top.
+
+A KernelOperator has hyperparameters instead of stored entries: `kernel_trace_grad` runs the same batches and contracts the same two
+factors against tiles of dA/dtheta (engine.KernelGradAccumulator, slq_kernel_grad_update) into d + 2 numbers - the lengthscales,
+the outputscale, the noise; `kernel_quadratic_grad` is the same contraction for host vectors, the data-fit term of a marginal
+likelihood. `primate_amd.autograd.kernel_trace_fun` is the torch function on top.
 """
 
 from __future__ import annotations
@@ -148,7 +153,7 @@ def trace_grad(M, pdf: Union[str, None] = "rademacher", count: int = 256, batch:
 	if not isinstance(M, (MatrixFunction, ChebyshevFunction)):
 		raise ValueError("trace_grad takes a MatrixFunction or a ChebyshevFunction")
 	if getattr(getattr(M, "_A", None), "_slq_kind", None) == "kernel" or getattr(getattr(M, "_op", None), "kind", None) == "kernel":
-		raise ValueError("trace_grad: hyperparameter gradients of a KernelOperator are not built (they need a derivative-kernel product)")
+		raise ValueError("trace_grad: a KernelOperator has no stored entries; its hyperparameter gradients come from kernel_trace_grad")
 	if np.dtype(M.dtype) != np.float64:
 		raise ValueError("trace_grad is fp64 only (the device matrices are fp64): build M with dtype=np.float64")
 	count, batch = int(count), int(batch)
@@ -235,6 +240,133 @@ def trace_grad(M, pdf: Union[str, None] = "rademacher", count: int = 256, batch:
 		for d in (W, Z, acc):
 			if d is not None:
 				d.close()
+
+
+def _kernel_grads(K, vals: np.ndarray) -> dict:
+	"""The d + 2 values of a KernelGradAccumulator as a dict shaped like K's parameters (a scalar lengthscale's gradient is the sum
+	over the dimensions, taken on the host)."""
+	d = K.X.shape[1]
+	ls = np.array(vals[:d], dtype=np.float64)
+	if np.size(K.lengthscale) == 1:
+		ls = np.array([ls.sum()])
+	return dict(lengthscale=ls.reshape(np.shape(K.lengthscale)), outputscale=float(vals[d]), noise=float(vals[d + 1]))
+
+
+def kernel_trace_grad(M, pdf: Union[str, None] = "rademacher", count: int = 256, batch: int = 64, seed=None, probes=None) -> tuple:
+	"""(est, grads, info): the Girard-Hutchinson estimate of tr f(A) over `count` probes for A = the KernelOperator under M and, from
+	the same runs, of its gradient with respect to the hyperparameters:
+
+	    grads = dict(lengthscale=array shaped like K.lengthscale, outputscale=float, noise=float),
+
+	the estimate (1/N) sum_i (f'(A) v_i)^T (dA/dtheta) v_i, contracted on the device against tiles of dA/dtheta that are never held
+	(engine.KernelGradAccumulator). The gradient is that of the smooth formula at the operator's rounded points z; there is none
+	with respect to the points. M: a MatrixFunction with a built-in `fun` among log, exp, identity (fp64), or a ChebyshevFunction
+	with a built-in function of the table `derivative_callable`. The batch loop is `trace_grad`'s. identity is exact and runs
+	nothing: tr A = n (outputscale + noise), gradients 0, n, n.
+	info: count, quad (the per-probe quadratic forms; for identity the exact trace in every entry), acc_count (columns the
+	accumulator folded in; 0 where nothing was sampled)."""
+	from .chebyshev import ChebyshevFunction
+	from .operators import MatrixFunction
+
+	if not isinstance(M, (MatrixFunction, ChebyshevFunction)):
+		raise ValueError("kernel_trace_grad takes a MatrixFunction or a ChebyshevFunction")
+	K = getattr(M, "_A", None)
+	if getattr(K, "_slq_kind", None) != "kernel":
+		raise ValueError("kernel_trace_grad needs a function of a KernelOperator (for the gradient on a sparsity pattern use trace_grad)")
+	if np.dtype(M.dtype) != np.float64 or np.dtype(K.dtype) != np.float64:
+		raise ValueError("kernel_trace_grad is fp64 only (the device matrices are fp64): build the KernelOperator and M with dtype=np.float64")
+	count, batch = int(count), int(batch)
+	if count < 1 or batch < 1:
+		raise ValueError(f"count = {count} and batch = {batch} must be >= 1")
+	n = int(M.shape[0])
+	cheb = isinstance(M, ChebyshevFunction)
+	if probes is not None:
+		count = int(np.asarray(probes).shape[1]) if np.asarray(probes).ndim == 2 else count
+	exact = False
+	if cheb:
+		spec = getattr(M._fun, "_slq_builtin", None)
+		if spec is None:
+			raise ValueError("kernel_trace_grad needs a built-in function on the Chebyshev route (its derivative comes from the table)")
+		dcall = derivative_callable(spec[0], **spec[1])
+	else:
+		if M._builtin is None:
+			raise ValueError("kernel_trace_grad needs a built-in `fun` on the Lanczos route (log, exp, identity)")
+		if M._stale_ring or M._adaptive is not None:
+			raise ValueError("kernel_trace_grad runs fixed-degree lock-step batches: no stale_ring, no adaptive degree")
+		name, kw = M._builtin
+		der = lanczos_derivative(name, kw)
+		exact = der is None
+	load = _probe_loader(pdf, seed, probes, n, count, cheb)
+	if exact:
+		d = K.X.shape[1]
+		tr = float(n) * (K.outputscale + K.noise)
+		return tr, _kernel_grads(K, np.concatenate([np.zeros(d), [float(n), float(n)]])), dict(count=count, quad=np.full(count, tr), acc_count=0)
+
+	ctx = M._op.ctx
+	acc = engine.KernelGradAccumulator(M._op)
+	W = Z = None
+	quad = np.empty(count)
+	try:
+		cols = min(batch, count)
+		W, Z = engine.DeviceMatrix(n, cols, ctx=ctx), engine.DeviceMatrix(n, cols, ctx=ctx)
+		done = 0
+		while done < count:
+			m = min(batch, count - done)
+			if cheb:
+				quad[done : done + m] = _chebyshev_batch(M, dcall, load, done, m, W, Z)
+				scale = 1.0
+			else:
+				plan = M._plan(m, True)
+				load(plan, done, m)
+				plan.get_probes_into(W, 0)
+				plan.run(M._rtol)
+				quad[done : done + m] = plan.quadrature(name, **kw)
+				plan.fun_action_into(Z, 0, der[0], **der[1])
+				scale = der[2]
+			acc.update(Z, 0, W, 0, m, alpha=scale / count, beta=1.0)
+			done += m
+		vals, acc_count = acc.get()
+		return float(np.mean(quad)), _kernel_grads(K, vals), dict(count=count, quad=quad, acc_count=acc_count)
+	finally:
+		for dm in (W, Z, acc):
+			if dm is not None:
+				dm.close()
+
+
+def kernel_quadratic_grad(K, U, V=None) -> dict:
+	"""The gradient of sum_c u_c^T A v_c with respect to the hyperparameters of the KernelOperator K (fp64), for host arrays U, V
+	(n x m or n; V=None: V = U), shaped as `kernel_trace_grad`'s: with U = V = A^-1 y and a factor -1 the data-fit term y^T A^-1 y of
+	a marginal likelihood. One KernelGradAccumulator update on K's device operator."""
+	from .lanczos import _as_device_operator
+
+	if getattr(K, "_slq_kind", None) != "kernel":
+		raise ValueError("kernel_quadratic_grad needs a KernelOperator")
+	if np.dtype(K.dtype) != np.float64:
+		raise ValueError("kernel_quadratic_grad is fp64 only (the device matrices are fp64): build the KernelOperator with dtype=np.float64")
+	n = int(K.shape[0])
+	U = np.asarray(U, dtype=np.float64)
+	U = U.reshape(-1, 1) if U.ndim == 1 else U
+	Vh = U if V is None else np.asarray(V, dtype=np.float64)
+	Vh = Vh.reshape(-1, 1) if Vh.ndim == 1 else Vh
+	if U.ndim != 2 or U.shape[0] != n or Vh.shape != U.shape or U.shape[1] < 1:
+		raise ValueError(f"U and V must be n x m = {n} x m arrays of one shape, got {U.shape} and {Vh.shape}")
+	op = _as_device_operator(K, dtype=np.float64)
+	m = U.shape[1]
+	acc = Ud = Vd = None
+	try:
+		acc = engine.KernelGradAccumulator(op)
+		Ud = engine.DeviceMatrix(n, m, ctx=op.ctx)
+		Ud.set(0, U)
+		if V is None:
+			Vd = Ud
+		else:
+			Vd = engine.DeviceMatrix(n, m, ctx=op.ctx)
+			Vd.set(0, Vh)
+		acc.update(Ud, 0, Vd, 0, m, alpha=1.0, beta=0.0)
+		return _kernel_grads(K, acc.get()[0])
+	finally:
+		for dm in {id(x): x for x in (Ud, Vd, acc) if x is not None}.values():
+			dm.close()
 
 
 def _chebyshev_batch(M, dcall: Callable, load: Callable, done: int, m: int, W, Z) -> np.ndarray:
