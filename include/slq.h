@@ -514,6 +514,48 @@ int slq_kernel_grad_destroy(slq_kernel_grad *g);
  * (-1 beyond); nout >= 22. No HIP call. */
 int slq_debug_kernel_grad_schedule(int64_t n, int m, int num_cus, int64_t *out, int nout);
 
+/* ---- Cross-covariance products of the kernel operator -------------------------------------------------------
+ * What a Gaussian-process posterior needs beside A^-1: the rectangular kernel matrix between NEW points and the operator's own.
+ * For a kernel operator op (slq_kernel_create: points x_1..x_n, the centre mean(x) fixed at its creation, lengthscales l,
+ * outputscale s, dtype F) and m new points x*_1..x*_m in the same d dimensions:
+ *   z*_i  = (F)(((double)x*_i - mean(x)) / l)     the TRAINING centre, never the new points' own; double arithmetic rounded once, so
+ *                                                 that a host model reproduces z* bit for bit
+ *   r2_ij = max(0, fma(-2, z*_i.z_j, |z*_i|^2 + |z_j|^2))     NO diagonal rule: a new point equal to a training point gets the
+ *                                                 r2 its arithmetic gives (0 up to rounding), not an exact 0
+ *   C     = s phi(r2)                             m x n, NO noise term
+ * The forward product is Y = C W (W n x b, Y m x b), the adjoint Y = C^T U (U m x b, Y n x b): one kernel with the two point sets
+ * exchanging roles. C is never held. The summed points are walked in a fixed order, slab partials are summed in slab order and
+ * nothing is atomic: identical calls give identical bits.
+ * slq_kernel_cross_create: op must be a kernel operator of ctx; the object takes op's dtype (points: m x d words of it, row-major
+ *   with leading dimension ldp >= d, on the host; _create_device: on the context's GPU, read back once for the check). It holds
+ *   the raw new points, z*^T, |z*|^2 and its slab scratch (sized on first use, grown on demand). It reads op at every product and
+ *   does not own it: destroy the cross object first. SLQ_EINVAL: a NULL handle, an operator of another kind or context, m < 1,
+ *   ldp < d, a point that is not finite (the first one is named).
+ * Hyperparameters: slq_kernel_set_parameters counts its calls on the operator; a cross object remembers the count its z* were
+ *   derived at and re-derives them on the stream - no allocation, no upload - before its next product when the count has moved.
+ *   It never writes the operator's z, |z|^2 or {s, sigma2}.
+ * slq_kernel_cross_matmat: host panels in the object's dtype, column-major; trans == 0: X n x b (ldx >= n), Y m x b (ldy >= m);
+ *   trans == 1: X m x b, Y n x b. Any b >= 1. Synchronises, like slq_operator_matmat.
+ * slq_kernel_cross_dmat: the same on columns [i0, i0 + b) of IN and [o0, o0 + b) of OUT, asynchronous on the context stream;
+ *   fp64 only (an fp32 object is refused, naming the dtype). IN must have n (trans == 0) or m (trans == 1) rows, OUT m or n.
+ * Both: SLQ_EINVAL, nothing launched: a NULL handle, trans not 0 or 1, b < 1, a leading dimension or a row count that does not
+ *   fit the direction, a column range outside its matrix, overlapping ranges of one matrix, a matrix of another context.
+ * slq_debug_kernel_cross_points: z*^T (dpad x mpad; dpad = d rounded up to 4, mpad = m rounded up to 16) and |z*|^2 (mpad) from
+ *   the device, in the object's dtype, after the re-derivation a product would do (either may be NULL). Synchronises. */
+typedef struct slq_kernel_cross slq_kernel_cross;
+int slq_kernel_cross_create(slq_context *ctx, slq_operator *op, int64_t m, const void *points, int64_t ldp, slq_kernel_cross **out);
+int slq_kernel_cross_create_device(slq_context *ctx, slq_operator *op, int64_t m, const void *d_points, int64_t ldp, slq_kernel_cross **out);
+int slq_kernel_cross_matmat(slq_kernel_cross *cross, int trans, const void *X, int64_t ldx, void *Y, int64_t ldy, int b);
+int slq_kernel_cross_dmat(slq_kernel_cross *cross, int trans, slq_dmat *IN, int i0, slq_dmat *OUT, int o0, int b);
+int slq_kernel_cross_destroy(slq_kernel_cross *cross);
+int slq_debug_kernel_cross_points(slq_kernel_cross *cross, void *zt, void *nrm);
+/* The schedule of one product with nrows output rows, nsum summed points and b columns on a chip of num_cus compute units
+ * (csrc/slq_kernelcross.hpp: kernel_cross_schedule): rows per block, row blocks, 16-column tiles per workgroup, 256-column chunks,
+ * slabs of the summed points (at most 64), tiles of 16 points per slab, then slab_begin[0 .. slabs] (-1 beyond); nout >= 71.
+ * Slab z is the tiles [z * tiles_per_slab, (z + 1) * tiles_per_slab) cut at the end: what the kernel computes from its block
+ * index. No HIP call. */
+int slq_debug_kernel_cross_schedule(int64_t nrows, int64_t nsum, int64_t b, int num_cus, int64_t *out, int nout);
+
 /* Per-kernel device time accumulated by HIP events on the context stream (for bench.py's
  * roofline line). enable != 0 turns event recording on for subsequent slq_plan_run calls. */
 enum {

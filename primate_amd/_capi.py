@@ -130,6 +130,13 @@ _SIGNATURES = {
 	"slq_kernel_grad_reset": (C.c_int, [_P]),
 	"slq_kernel_grad_destroy": (C.c_int, [_P]),
 	"slq_debug_kernel_grad_schedule": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+	"slq_kernel_cross_create": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _PP]),
+	"slq_kernel_cross_create_device": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _PP]),
+	"slq_kernel_cross_matmat": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, C.c_int]),
+	"slq_kernel_cross_dmat": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int]),
+	"slq_kernel_cross_destroy": (C.c_int, [_P]),
+	"slq_debug_kernel_cross_points": (C.c_int, [_P, _P, _P]),
+	"slq_debug_kernel_cross_schedule": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int]),
 	"slq_plan_profile_enable": (C.c_int, [_P, C.c_int]),
 	"slq_plan_action_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
 	"slq_plan_sweep_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),

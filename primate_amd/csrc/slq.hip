@@ -39,6 +39,7 @@
 #include "slq_sddmm.hpp"     // sampled dense-dense product on a CSR pattern: schedule (sddmm_schedule) and kernel of slq_sddmm_*
 #include "slq_kernelop.hpp"  // matrix-free kernel operator (slq_kernel_*): validation, schedule, k_kernel_rescale, k_kernel_panel
 #include "slq_kernelgrad.hpp"  // hyperparameter gradients of the kernel operator (slq_kernel_grad_*): schedule, k_kernel_grad, k_kernel_grad_sum
+#include "slq_kernelcross.hpp"  // cross-covariance products (slq_kernel_cross_*): schedule, the launch functions of slq_kernelcross.hip
 #include "slq_operator.hpp"  // the operator handle and the values it owns (DevBuf, CsrArrays, TileStream)
 
 using namespace slq;
@@ -1270,6 +1271,7 @@ extern "C" int slq_kernel_set_parameters(slq_operator *op, const double *lengths
   if (bad.what != KERNEL_OK) return kernel_bad(bad);
   HIP_TRY(hipSetDevice(op->ctx->device));
   kernel_set_scale(op, lengthscales, nls, outputscale, noise);
+  ++op->k_epoch;  // (cross objects re-derive their z* before their next product: slq_kernel_cross_*)
   return kernel_rescale(op);
 }
 extern "C" int slq_kernel_get_parameters(const slq_operator *op, int *d, int *profile, double *lengthscales, int nls, double *outputscale, double *noise) {
@@ -4217,6 +4219,204 @@ extern "C" int slq_debug_kernel_grad_schedule(int64_t n, int m, int num_cus, int
   const KernelGradSchedule S = kernel_grad_schedule(n, m, num_cus);
   out[0] = S.rows_per_block, out[1] = S.nrow_blocks, out[2] = S.chunk_cols, out[3] = S.ncol_chunks, out[4] = S.nslabs;
   for (int z = 0; z <= kKernelMaxSlabs; ++z) out[5 + z] = z <= S.nslabs ? S.slab_begin[z] : -1;
+  return SLQ_OK;
+}
+
+// ---- cross-covariance products of the kernel operator (schedule and kernels in slq_kernelcross.hpp) -----------
+struct slq_kernel_cross {
+  slq_context *ctx = nullptr;
+  slq_operator *op = nullptr;  // not owned: read at every product (its z, norms, s and lengthscales as they are then)
+  int dtype = SLQ_F64;
+  int64_t m = 0, mpad = 0;
+  int d = 0, dpad = 0;
+  DevBuf buf;  // one allocation: the raw new points, and behind them what the next three point to
+  void *zt = nullptr, *nrm = nullptr, *params = nullptr;  // z*^T (dpad x mpad), |z*|^2 (mpad), two words k_kernel_rescale writes (never the operator's)
+  uint64_t epoch = 0;  // the operator's k_epoch the z* were derived at
+  DevBuf scratch;      // slab partials: sized on first use, grown on demand
+  DevBuf stage_in, stage_out;  // device copies of the host panels of slq_kernel_cross_matmat (grown on demand)
+};
+
+// z*, |z*|^2 from the raw new points with the operator's centre and its lengthscales of now, on the stream (no allocation, no upload)
+static int kernel_cross_rescale(slq_kernel_cross *c) {
+  const slq_operator *op = c->op;
+  const int m = (int)c->m, mpad = (int)c->mpad;
+  const dim3 g((unsigned)((mpad + 255) / 256));
+  if (c->dtype == SLQ_F64)
+    k_kernel_rescale<double><<<g, dim3(256), 0, c->ctx->stream>>>(m, mpad, c->d, c->dpad, c->buf.as<const double>(), *op->k_scale, (double *)c->zt, (double *)c->nrm,
+                                                                 (double *)c->params, op->k_s, 0.0);
+  else
+    k_kernel_rescale<float><<<g, dim3(256), 0, c->ctx->stream>>>(m, mpad, c->d, c->dpad, c->buf.as<const float>(), *op->k_scale, (float *)c->zt, (float *)c->nrm,
+                                                                (float *)c->params, op->k_s, 0.0);
+  HIP_TRY(hipGetLastError());
+  c->epoch = op->k_epoch;
+  return SLQ_OK;
+}
+
+template <typename F> static int kernel_cross_check_points(int64_t m, int d, const F *pts, int64_t ldp) {
+  for (int64_t i = 0; i < m; ++i)
+    for (int k = 0; k < d; ++k)
+      if (!std::isfinite((double)pts[i * ldp + k]))
+        return fail(SLQ_EINVAL, "slq_kernel_cross_create: new point %lld, coordinate %d is %g (points must be finite)", (long long)i, k, (double)pts[i * ldp + k]);
+  return SLQ_OK;
+}
+
+static int kernel_cross_create_body(slq_context *ctx, slq_operator *op, int64_t m, const void *points, int64_t ldp, bool on_device, slq_kernel_cross **out) {
+  if (!ctx || !op || !points || !out) return fail(SLQ_EINVAL, "slq_kernel_cross_create: ctx/op/points/out is NULL");
+  *out = nullptr;
+  if (op->kind != OP_KERNEL)
+    return fail(SLQ_EINVAL, "slq_kernel_cross_create: the operator is of kind '%s', not a kernel operator (slq_kernel_create)", op_kind_name(op->kind));
+  if (op->ctx != ctx) return fail(SLQ_EINVAL, "slq_kernel_cross_create: the operator belongs to another context");
+  if (ctx->dead) return fail(SLQ_EINVAL, "slq_kernel_cross_create: the context has been destroyed");
+  if (m < 1 || m >= ((int64_t)1 << 31) - 16) return fail(SLQ_EINVAL, "slq_kernel_cross_create: m = %lld new points (1 <= m < 2^31 - 16)", (long long)m);
+  const int d = op->k_d;
+  if (ldp < d) return fail(SLQ_EINVAL, "slq_kernel_cross_create: ldp = %lld is below d = %d", (long long)ldp, d);
+  const size_t es = esize(op->dtype);
+  HIP_TRY(hipSetDevice(ctx->device));
+  try {
+    // points on the device: a packed host copy for the check (m d words, once per object)
+    std::vector<char> host;
+    const void *hp = points;
+    int64_t hld = ldp;
+    if (on_device) {
+      host.resize((size_t)m * d * es);
+      HIP_TRY(hipMemcpy2D(host.data(), (size_t)d * es, points, (size_t)ldp * es, (size_t)d * es, (size_t)m, hipMemcpyDeviceToHost));
+      hp = host.data(), hld = d;
+    }
+    SLQ_TRY(op->dtype == SLQ_F64 ? kernel_cross_check_points<double>(m, d, (const double *)hp, hld) : kernel_cross_check_points<float>(m, d, (const float *)hp, hld));
+    std::unique_ptr<slq_kernel_cross> c(new slq_kernel_cross());
+    c->ctx = ctx, c->op = op, c->dtype = op->dtype, c->m = m, c->mpad = kernel_npad(m), c->d = d, c->dpad = op->k_dpad;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t b_raw = up((size_t)m * d * es), b_zt = up((size_t)c->dpad * (size_t)c->mpad * es), b_nrm = up((size_t)c->mpad * es);
+    hipError_t e = c->buf.alloc(b_raw + b_zt + b_nrm + 256);
+    if (e == hipSuccess) {
+      c->zt = c->buf.as<char>() + b_raw;
+      c->nrm = (char *)c->zt + b_zt;
+      c->params = (char *)c->nrm + b_nrm;
+      e = hipMemcpy2DAsync(c->buf.p, (size_t)d * es, hp, (size_t)hld * es, (size_t)d * es, (size_t)m, hipMemcpyHostToDevice, ctx->stream);
+    }
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "slq_kernel_cross_create: %s", hipGetErrorString(e));
+    SLQ_TRY(kernel_cross_rescale(c.get()));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // (the host copy of the points goes with this frame)
+    ctx_retain(ctx);
+    *out = c.release();
+  } catch (const std::bad_alloc &) {
+    return fail(SLQ_ENOMEM, "slq_kernel_cross_create: host allocation failed");
+  }
+  return SLQ_OK;
+}
+extern "C" int slq_kernel_cross_create(slq_context *ctx, slq_operator *op, int64_t m, const void *points, int64_t ldp, slq_kernel_cross **out) {
+  return kernel_cross_create_body(ctx, op, m, points, ldp, false, out);
+}
+extern "C" int slq_kernel_cross_create_device(slq_context *ctx, slq_operator *op, int64_t m, const void *d_points, int64_t ldp, slq_kernel_cross **out) {
+  return kernel_cross_create_body(ctx, op, m, d_points, ldp, true, out);
+}
+
+extern "C" int slq_kernel_cross_destroy(slq_kernel_cross *c) {
+  if (!c) return SLQ_OK;
+  hipSetDevice(c->ctx->device);
+  hipStreamSynchronize(c->ctx->stream);
+  slq_context *ctx = c->ctx;
+  delete c;  // (every device array is a member that frees itself)
+  ctx_release(ctx);
+  return SLQ_OK;
+}
+
+// Y = C X (trans == 0: X n x b, Y m x b) or C^T X (X m x b, Y n x b) for device arrays, on the stream. The caller has checked the shapes.
+static int kernel_cross_product(slq_kernel_cross *c, int trans, const void *X, int64_t ldx, void *Y, int64_t ldy, int b, const char *who) {
+  const slq_operator *op = c->op;
+  if (c->epoch != op->k_epoch) SLQ_TRY(kernel_cross_rescale(c));  // the hyperparameters have moved: z* follow, before this product
+  const bool fwd = trans == 0;
+  const int64_t nrows = fwd ? c->m : op->n, nsum = fwd ? op->n : c->m;
+  const KernelCrossSchedule S = kernel_cross_schedule(nrows, nsum, b, c->ctx->num_cus);
+  if (S.ncol_chunks > 65535) return fail(SLQ_EINVAL, "%s: b = %d columns (at most %d)", who, b, 65535 * 16 * kKernelMaxColBlocks);
+  const size_t es = esize(c->dtype);
+  const int64_t slab_stride = nrows * (int64_t)b;
+  if (S.nslabs > 1) {
+    const size_t need = (size_t)S.nslabs * (size_t)slab_stride * es;
+    if (c->scratch.bytes() < need) {
+      const hipError_t e = c->scratch.alloc(need);
+      if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "%s: slab scratch of %zu bytes: %s", who, need, hipGetErrorString(e));
+    }
+  }
+  KernelCrossArgs a;
+  a.nrows = (int)nrows, a.rpad = (int)(fwd ? c->mpad : op->k_npad);
+  a.nsum = (int)nsum, a.spad = (int)(fwd ? op->k_npad : c->mpad);
+  a.dq = c->dpad / 4;
+  a.rzt = fwd ? c->zt : op->k_zt, a.rnrm = fwd ? c->nrm : op->k_nrm;
+  a.szt = fwd ? op->k_zt : c->zt, a.snrm = fwd ? op->k_nrm : c->nrm;
+  a.params = op->k_params;
+  a.W = X, a.ldw = ldx, a.b = b;
+  a.out = S.nslabs > 1 ? c->scratch.p : Y, a.ldo = S.nslabs > 1 ? nrows : ldy, a.slab_stride = slab_stride;
+  if (!kernel_cross_launch(c->dtype == SLQ_F64, op->k_profile, S, a, (void *)c->ctx->stream))
+    return fail(SLQ_EINVAL, "%s: no kernel for profile %d with %d column tiles", who, op->k_profile, S.col_blocks);
+  HIP_TRY(hipGetLastError());
+  if (S.nslabs > 1) {
+    kernel_cross_sum_launch(c->dtype == SLQ_F64, nrows, b, S.nslabs, c->scratch.p, slab_stride, Y, ldy, (void *)c->ctx->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_cross_matmat(slq_kernel_cross *c, int trans, const void *X, int64_t ldx, void *Y, int64_t ldy, int b) {
+  if (!c) return fail(SLQ_EINVAL, "slq_kernel_cross_matmat: cross object is NULL");
+  if (!X || !Y) return fail(SLQ_EINVAL, "slq_kernel_cross_matmat: X/Y is NULL");
+  if (trans != 0 && trans != 1) return fail(SLQ_EINVAL, "slq_kernel_cross_matmat: trans = %d (0: Y = C X, 1: Y = C^T X)", trans);
+  if (b < 1) return fail(SLQ_EINVAL, "slq_kernel_cross_matmat: b = %d columns (b >= 1)", b);
+  const int64_t rin = trans ? c->m : c->op->n, rout = trans ? c->op->n : c->m;
+  if (ldx < rin) return fail(SLQ_EINVAL, "slq_kernel_cross_matmat: ldx = %lld is below the %lld rows of X (trans = %d)", (long long)ldx, (long long)rin, trans);
+  if (ldy < rout) return fail(SLQ_EINVAL, "slq_kernel_cross_matmat: ldy = %lld is below the %lld rows of Y (trans = %d)", (long long)ldy, (long long)rout, trans);
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  const size_t es = esize(c->dtype);
+  const size_t need_in = (size_t)rin * b * es, need_out = (size_t)rout * b * es;
+  if (c->stage_in.bytes() < need_in) HIP_TRY(c->stage_in.alloc(need_in));
+  if (c->stage_out.bytes() < need_out) HIP_TRY(c->stage_out.alloc(need_out));
+  hipStream_t st = c->ctx->stream;
+  HIP_TRY(hipMemcpy2DAsync(c->stage_in.p, (size_t)rin * es, X, (size_t)ldx * es, (size_t)rin * es, (size_t)b, hipMemcpyHostToDevice, st));
+  SLQ_TRY(kernel_cross_product(c, trans, c->stage_in.p, rin, c->stage_out.p, rout, b, "slq_kernel_cross_matmat"));
+  HIP_TRY(hipMemcpy2DAsync(Y, (size_t)ldy * es, c->stage_out.p, (size_t)rout * es, (size_t)rout * es, (size_t)b, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_cross_dmat(slq_kernel_cross *c, int trans, slq_dmat *IN, int i0, slq_dmat *OUT, int o0, int b) {
+  if (!c) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: cross object is NULL");
+  if (c->dtype != SLQ_F64) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: the cross object's dtype is fp32: the device matrices are fp64 (use slq_kernel_cross_matmat)");
+  if (trans != 0 && trans != 1) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: trans = %d (0: OUT = C IN, 1: OUT = C^T IN)", trans);
+  if (b < 1) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: b = %d columns (b >= 1)", b);
+  SLQ_TRY(dmat_range(IN, i0, b, "slq_kernel_cross_dmat(IN)"));
+  SLQ_TRY(dmat_range(OUT, o0, b, "slq_kernel_cross_dmat(OUT)"));
+  const int64_t rin = trans ? c->m : c->op->n, rout = trans ? c->op->n : c->m;
+  if (IN->n != rin) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: IN has %lld rows, the product with trans = %d reads %lld", (long long)IN->n, trans, (long long)rin);
+  if (OUT->n != rout) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: OUT has %lld rows, the product with trans = %d writes %lld", (long long)OUT->n, trans, (long long)rout);
+  if (IN->ctx != c->ctx || OUT->ctx != c->ctx) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: a matrix belongs to another context");
+  if (IN == OUT && i0 < o0 + b && o0 < i0 + b) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: the columns [%d, %d) of IN and [%d, %d) of OUT overlap in one matrix", i0, i0 + b, o0, o0 + b);
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  return kernel_cross_product(c, trans, IN->d + (size_t)i0 * IN->n, IN->n, OUT->d + (size_t)o0 * OUT->n, OUT->n, b, "slq_kernel_cross_dmat");
+}
+
+// z*^T (dpad x mpad, mpad = m rounded up to 16) and |z*|^2 (mpad) in the object's dtype, brought up to the operator's parameters
+// of now first - the re-derivation a product would do (tests)
+extern "C" int slq_debug_kernel_cross_points(slq_kernel_cross *c, void *zt, void *nrm) {
+  if (!c) return fail(SLQ_EINVAL, "slq_debug_kernel_cross_points: cross object is NULL");
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  if (c->epoch != c->op->k_epoch) SLQ_TRY(kernel_cross_rescale(c));
+  HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+  const size_t es = esize(c->dtype);
+  if (zt) HIP_TRY(hipMemcpy(zt, c->zt, (size_t)c->dpad * (size_t)c->mpad * es, hipMemcpyDeviceToHost));
+  if (nrm) HIP_TRY(hipMemcpy(nrm, c->nrm, (size_t)c->mpad * es, hipMemcpyDeviceToHost));
+  return SLQ_OK;
+}
+
+// kernel_cross_schedule() of slq_kernelcross.hpp as an array: rows per block, row blocks, 16-column tiles per workgroup, column
+// chunks, slabs, tiles per slab, then slab_begin[0 .. slabs] (-1 beyond). No HIP call.
+extern "C" int slq_debug_kernel_cross_schedule(int64_t nrows, int64_t nsum, int64_t b, int num_cus, int64_t *out, int nout) {
+  if (!out || nout < 6 + kKernelCrossMaxSlabs + 1) return fail(SLQ_EINVAL, "slq_debug_kernel_cross_schedule: room for %d values", 6 + kKernelCrossMaxSlabs + 1);
+  const int64_t lim = ((int64_t)1 << 31) - 16;
+  if (nrows <= 0 || nrows >= lim || nsum <= 0 || nsum >= lim || b <= 0 || b >= lim || num_cus <= 0)
+    return fail(SLQ_EINVAL, "slq_debug_kernel_cross_schedule: 0 < nrows, nsum, b < 2^31 - 16 and num_cus positive");
+  const KernelCrossSchedule S = kernel_cross_schedule(nrows, nsum, b, num_cus);
+  out[0] = S.rows_per_block, out[1] = S.nrow_blocks, out[2] = S.col_blocks, out[3] = S.ncol_chunks, out[4] = S.nslabs, out[5] = S.tiles_per_slab;
+  for (int z = 0; z <= kKernelCrossMaxSlabs; ++z) out[6 + z] = z <= S.nslabs ? S.slab_begin[z] : -1;
   return SLQ_OK;
 }
 

@@ -155,4 +155,5 @@ struct slq_operator {
   void *k_zt = nullptr, *k_nrm = nullptr, *k_params = nullptr;
   std::unique_ptr<slq::KernelScale> k_scale;  // host: the centre of the points and the lengthscales per dimension
   double k_s = 1.0, k_noise = 0.0;
+  uint64_t k_epoch = 0;  // host: incremented by every slq_kernel_set_parameters; a slq_kernel_cross compares it with the one its z* were derived at
 };

@@ -1133,6 +1133,95 @@ class KernelGradAccumulator:
 			pass
 
 
+def kernel_cross_schedule(nrows: int, nsum: int, b: int, num_cus: int = 256) -> dict:
+	"""The schedule of one cross-covariance product with `nrows` output rows, `nsum` summed points and `b` columns, as the library
+	cuts it (slq_debug_kernel_cross_schedule; host arithmetic, no device): rows per block, row blocks, 16-column tiles per workgroup,
+	256-column chunks, slabs of the summed points, tiles of 16 points per slab and the slabs' bounds."""
+	out = (C.c_int64 * 71)()
+	check(_capi.lib().slq_debug_kernel_cross_schedule(int(nrows), int(nsum), int(b), int(num_cus), out, 71))
+	v = list(out)
+	return dict(rows=v[0], nrb=v[1], col_blocks=v[2], chunks=v[3], slabs=v[4], tiles_per_slab=v[5], begin=v[6 : 6 + v[4] + 1], rest=v[6 + v[4] + 1 :])
+
+
+class KernelCross:
+	"""The cross-covariance C = s phi(r2(X*, X)) between `Xnew` (m x d) and the points of a kernel operator, never formed
+	(slq_kernel_cross_*): `matmat(W)` is C W (m x b), `matmat(U, trans=True)` is C^T U (n x b). z* is taken with
+	the operator's own centre and its lengthscales of now; no diagonal rule, no noise term. op: a DeviceOperator of kind "kernel"; the
+	object takes its dtype and keeps it alive, as a plan does. `Xnew`: a NumPy array, or a torch tensor on the context's GPU.
+	`set_kernel_parameters` on the operator is honoured by the next product (the library re-derives z* on the stream)."""
+
+	def __init__(self, op: DeviceOperator, Xnew):
+		if getattr(op, "kind", None) != "kernel":
+			raise ValueError(f"KernelCross needs a kernel operator, not kind '{getattr(op, 'kind', None)}'")
+		self.op, self.ctx = op, op.ctx
+		self.dtype = np.dtype(op.dtype)
+		self.n, self.d = int(op.shape[0]), int(op.nnz // op.shape[0])
+		L = _capi.lib()
+		h = C.c_void_p()
+		if type(Xnew).__module__.split(".")[0] == "torch" and Xnew.is_cuda:
+			import torch
+
+			if Xnew.device.index != self.ctx.device:
+				raise ValueError(f"the new points are on {Xnew.device}, the context on GPU {self.ctx.device}")
+			Xt = Xnew.detach()
+			Xt = Xt.reshape(-1, 1) if Xt.ndim == 1 else Xt
+			if Xt.ndim != 2 or Xt.shape[1] != self.d or Xt.shape[0] < 1:
+				raise ValueError(f"the new points must be an (m, {self.d}) array with m >= 1, got shape {tuple(Xt.shape)}")
+			Xt = Xt.to(torch.float64 if self.dtype == np.float64 else torch.float32).contiguous()
+			torch.cuda.synchronize(Xt.device)
+			self.m = int(Xt.shape[0])
+			check(L.slq_kernel_cross_create_device(self.ctx._h, op._h, self.m, C.c_void_p(Xt.data_ptr()), self.d, C.byref(h)))
+		else:
+			if type(Xnew).__module__.split(".")[0] == "torch":
+				Xnew = Xnew.detach().cpu().numpy()
+			X = np.asarray(Xnew)
+			X = X.reshape(-1, 1) if X.ndim == 1 else X
+			if X.ndim != 2 or X.shape[1] != self.d or X.shape[0] < 1:
+				raise ValueError(f"the new points must be an (m, {self.d}) array with m >= 1, got shape {X.shape}")
+			X = np.ascontiguousarray(X, dtype=self.dtype)
+			self.m = int(X.shape[0])
+			check(L.slq_kernel_cross_create(self.ctx._h, op._h, self.m, ptr(X), self.d, C.byref(h)))
+		self.shape = (self.m, self.n)
+		self._h = h
+
+	def matmat(self, X: np.ndarray, trans: bool = False) -> np.ndarray:
+		"""C X (trans=False: X is n x b) or C^T X (X is m x b) for a host array, in the operator's dtype."""
+		rin, rout = (self.m, self.n) if trans else (self.n, self.m)
+		X = np.asarray(X)
+		X = X.reshape(-1, 1) if X.ndim == 1 else X
+		if X.ndim != 2 or X.shape[0] != rin or X.shape[1] < 1:
+			raise ValueError(f"dimension mismatch: the product with trans={bool(trans)} reads {rin} rows, the operand has shape {X.shape}")
+		X = np.asfortranarray(X, dtype=self.dtype)
+		Y = np.empty((rout, X.shape[1]), dtype=self.dtype, order="F")
+		check(_capi.lib().slq_kernel_cross_matmat(self._h, int(bool(trans)), ptr(X), rin, ptr(Y), rout, X.shape[1]))
+		return Y
+
+	def matmat_dmat(self, IN: "DeviceMatrix", i0: int, OUT: "DeviceMatrix", o0: int, b: int, trans: bool = False):
+		"""OUT[:, o0:o0+b] = C IN[:, i0:i0+b] (or C^T ...) between DeviceMatrix columns: fp64 only, asynchronous on the context stream."""
+		check(_capi.lib().slq_kernel_cross_dmat(self._h, int(bool(trans)), IN._h, int(i0), OUT._h, int(o0), int(b)))
+
+	def scaled_points(self) -> tuple:
+		"""(z*, |z*|^2): m x d and m, as the device holds them (slq_debug_kernel_cross_points), in the operator's dtype. Sets
+		`padding_is_zero`: whether everything beyond d and m in the device arrays is 0, as the kernel relies on."""
+		dpad, mpad = (self.d + 3) // 4 * 4, (self.m + 15) // 16 * 16
+		zt = np.empty((dpad, mpad), dtype=self.dtype)
+		nrm = np.empty(mpad, dtype=self.dtype)
+		check(_capi.lib().slq_debug_kernel_cross_points(self._h, ptr(zt), ptr(nrm)))
+		self.padding_is_zero = bool(not zt[self.d :].any() and not zt[:, self.m :].any() and not nrm[self.m :].any())
+		return np.ascontiguousarray(zt[: self.d, : self.m].T), nrm[: self.m].copy()
+
+	def close(self):
+		if getattr(self, "_h", None):
+			_capi.lib().slq_kernel_cross_destroy(self._h)
+			self._h = None
+
+	def __del__(self):
+		try:
+			self.close()
+		except Exception:  # noqa: BLE001
+			pass
+
+
 class _CudaArrayView:
 	"""Flat fp64 device array described by the CUDA array interface (v2); keeps its owner alive."""
 

@@ -477,6 +477,106 @@ class KernelOperator(LinearOperator):
 	def _adjoint(self):
 		return self
 
+	def cross(self, Xnew) -> "KernelCrossOperator":
+		"""The cross-covariance between the new points `Xnew` (m x d) and this operator's points: a `KernelCrossOperator` of shape
+		(m, n). It follows this operator's hyperparameters, whenever they are set."""
+		return KernelCrossOperator(self, Xnew)
+
+
+class KernelCrossOperator(LinearOperator):
+	"""C = outputscale * phi(r2(X*, X)), m x n, between new points X* and the n points of the KernelOperator `K`, never formed
+	(DESIGN.md §4.17): z* = (x* - mean(X)) / lengthscale with K's centre - the TRAINING centre, never the new points' own -
+	computed in float64 and rounded once to K's dtype; r2_ij = max(0, |z*_i|^2 + |z_j|^2 - 2 z*_i.z_j) with no diagonal rule
+	(a new point equal to a training point gets what the arithmetic gives); no noise term. `C @ W` is the forward product,
+	`C.T @ U` (or `rmatmat`) the adjoint. It reads K's lengthscale and outputscale at every product, so `K.set_parameters` needs
+	no forwarding. `Xnew`: an (m, d) NumPy array ((m,) for d = 1), or a torch tensor on the context's GPU (`device()` then hands
+	the library the device pointer; the host methods work on a host copy). The host `_matmat` / `_rmatmat` are blocked NumPy in
+	float64 from the definition: the plugin surface, and the model of the tests. `device(op)` is the product on the GPU
+	(engine.KernelCross)."""
+
+	def __init__(self, K: KernelOperator, Xnew, _transposed: bool = False):
+		if getattr(K, "_slq_kind", None) != "kernel":
+			raise ValueError("KernelCrossOperator needs a KernelOperator")
+		self.K = K
+		self._X_device = None
+		self._Xnew_arg = Xnew
+		if type(Xnew).__module__.split(".")[0] == "torch":
+			if Xnew.is_cuda:
+				self._X_device = Xnew
+			Xnew = Xnew.detach().cpu().numpy()
+		X = np.asarray(Xnew)
+		d = K.X.shape[1]
+		if X.ndim == 1:
+			X = X.reshape(-1, 1)
+		if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] != d:
+			raise ValueError(f"the new points must be an (m, {d}) array with m >= 1, got shape {X.shape}")
+		self.Xnew = np.ascontiguousarray(X, dtype=K.dtype)
+		bad = np.argwhere(~np.isfinite(self.Xnew))
+		if bad.size:
+			i, k = (int(v) for v in bad[0])
+			raise ValueError(f"kernel cross: new point {i}, coordinate {k} is {self.Xnew[i, k]} (points must be finite)")
+		self.dtype = np.dtype(K.dtype)
+		self.transposed = bool(_transposed)
+		m, n = self.Xnew.shape[0], K.shape[0]
+		self.shape = (n, m) if self.transposed else (m, n)
+
+	def scaled_points(self) -> np.ndarray:
+		"""z* = (x* - mean(X)) / lengthscale in float64, rounded once to the operator's dtype, with K's parameters of now."""
+		ls = np.broadcast_to(self.K.lengthscale, (self.Xnew.shape[1],))
+		return ((self.Xnew.astype(np.float64) - self.K.mean) / ls).astype(self.dtype)
+
+	def rows(self, idx) -> np.ndarray:
+		"""Rows `idx` of the m x n matrix C in float64, from the definition (norms plus dot product, clamped)."""
+		idx = np.asarray(idx, dtype=np.int64).ravel()
+		zs = self.scaled_points().astype(np.float64)[idx]
+		z = self.K.scaled_points().astype(np.float64)
+		r2 = np.maximum(np.einsum("ij,ij->i", zs, zs)[:, None] + np.einsum("ij,ij->i", z, z)[None, :] - 2.0 * (zs @ z.T), 0.0)
+		return self.K.outputscale * _kernel_profile(self.K.kernel, r2)
+
+	def _product(self, X: np.ndarray, trans: bool) -> np.ndarray:
+		m, n = self.Xnew.shape[0], self.K.shape[0]
+		rin, rout = (m, n) if trans else (n, m)
+		X = np.asarray(X)
+		if X.ndim != 2 or X.shape[0] != rin:
+			raise ValueError(f"dimension mismatch: the product reads {rin} rows, the operand has shape {X.shape}")
+		X64 = X.astype(np.float64, copy=False)
+		Y = np.zeros((rout, X.shape[1]), dtype=np.float64)
+		for i0 in range(0, m, 1024):
+			i1 = min(m, i0 + 1024)
+			Cb = self.rows(np.arange(i0, i1))
+			if trans:
+				Y += Cb.T @ X64[i0:i1]
+			else:
+				Y[i0:i1] = Cb @ X64
+		return Y.astype(self.dtype, copy=False)
+
+	def _matmat(self, X: np.ndarray) -> np.ndarray:
+		return self._product(X, self.transposed)
+
+	def _rmatmat(self, X: np.ndarray) -> np.ndarray:
+		return self._product(X, not self.transposed)
+
+	def _matvec(self, x: np.ndarray) -> np.ndarray:
+		x = np.asarray(x)
+		if x.size != self.shape[1]:
+			raise ValueError(f"dimension mismatch: the operator is {self.shape[0]} x {self.shape[1]}, the operand has {x.size} entries")
+		return self._matmat(x.reshape(-1, 1)).ravel()
+
+	def _rmatvec(self, x: np.ndarray) -> np.ndarray:
+		return self._rmatmat(np.asarray(x).reshape(-1, 1)).ravel()
+
+	def _adjoint(self):
+		return KernelCrossOperator(self.K, self._Xnew_arg, _transposed=not self.transposed)
+
+	def _transpose(self):
+		return self._adjoint()
+
+	def device(self, op=None) -> "engine.KernelCross":
+		"""The products on the GPU: an engine.KernelCross over `op` (default: K's cached device operator). Its `matmat(X, trans)`
+		is that of the m x n matrix, whatever `transposed` says."""
+		op = _as_device_operator(self.K, dtype=self.dtype) if op is None else op
+		return engine.KernelCross(op, self._X_device if self._X_device is not None else self.Xnew)
+
 
 class Toeplitz(LinearOperator):
 	"""Matrix-free symmetric-or-not Toeplitz operator with first column `c` and first row `r` (default r = c),
