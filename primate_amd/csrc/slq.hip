@@ -40,7 +40,7 @@
 #include "slq_kernelop.hpp"  // matrix-free kernel operator (slq_kernel_*): validation, schedule, k_kernel_rescale, k_kernel_panel
 #include "slq_kernelgrad.hpp"  // hyperparameter gradients of the kernel operator (slq_kernel_grad_*): schedule, k_kernel_grad, k_kernel_grad_sum
 #include "slq_kernelcross.hpp"  // cross-covariance products (slq_kernel_cross_*): schedule, the launch functions of slq_kernelcross.hip
-#include "slq_operator.hpp"  // the operator handle and the values it owns (DevBuf, CsrArrays, TileStream)
+#include "slq_operator.hpp"  // the operator handle and the values it owns (DevBuf, CsrArrays, TileStream, KernelPoints)
 
 using namespace slq;
 
@@ -111,7 +111,7 @@ static void ctx_release(slq_context *ctx) {
 // (OP_CSR .. OP_KERNEL, the kinds of an operator: slq_plan_shape.hpp)
 static_assert(kF32 == SLQ_F32 && kF64 == SLQ_F64, "slq_plan_shape.hpp: the dtype codes of include/slq.h");
 
-// (slq_operator, the handle of an operator, and the values it owns - DevBuf, CsrArrays, TileStream: slq_operator.hpp)
+// (slq_operator, the handle of an operator, and the values it owns - DevBuf, CsrArrays, TileStream, KernelPoints: slq_operator.hpp)
 
 struct ProfEvent {
   hipEvent_t a, b;
@@ -1189,16 +1189,14 @@ extern "C" int slq_device_callback_create(slq_context *ctx, int dtype, int64_t n
 // ---- matrix-free kernel operator (slq_kernelop.hpp) ----
 // z, |z|^2, s and sigma2 from the raw points and the operator's host record, on the library's stream (no allocation, no upload)
 static int kernel_rescale(slq_operator *op) {
-  const int n = (int)op->n, npad = (int)op->k_npad;
-  const dim3 g((unsigned)((npad + 255) / 256));
-  if (op->dtype == SLQ_F64)
-    k_kernel_rescale<double><<<g, dim3(256), 0, op->ctx->stream>>>(n, npad, op->k_d, op->k_dpad, op->k_raw.as<const double>(), *op->k_scale, (double *)op->k_zt,
-                                                                  (double *)op->k_nrm, (double *)op->k_params, op->k_s, op->k_noise);
-  else
-    k_kernel_rescale<float><<<g, dim3(256), 0, op->ctx->stream>>>(n, npad, op->k_d, op->k_dpad, op->k_raw.as<const float>(), *op->k_scale, (float *)op->k_zt,
-                                                                 (float *)op->k_nrm, (float *)op->k_params, op->k_s, op->k_noise);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(op->k_pts.rescale(*op->k_scale, op->k_s, op->k_noise, op->dtype, op->ctx->stream));
   return SLQ_OK;
+}
+// a schedule as the array of the slq_debug_kernel*_schedule entries: the words of head (each entry has its own), then
+// slab_begin[0 .. nslabs] and -1 up to max_slabs
+static void kernel_schedule_words(std::initializer_list<int64_t> head, int nslabs, const int64_t *slab_begin, int max_slabs, int64_t *out) {
+  out = std::copy(head.begin(), head.end(), out);
+  for (int z = 0; z <= max_slabs; ++z) out[z] = z <= nslabs ? slab_begin[z] : -1;
 }
 static int kernel_bad(const KernelBad &b) {
   char msg[256];
@@ -1206,7 +1204,7 @@ static int kernel_bad(const KernelBad &b) {
   return fail(SLQ_EINVAL, "%s", msg);
 }
 static void kernel_set_scale(slq_operator *op, const double *ls, int nls, double s, double noise) {
-  for (int k = 0; k < kKernelMaxDim; ++k) op->k_scale->ls[k] = k < op->k_d ? ls[nls == 1 ? 0 : k] : 1.0;
+  for (int k = 0; k < kKernelMaxDim; ++k) op->k_scale->ls[k] = k < op->k_pts.d ? ls[nls == 1 ? 0 : k] : 1.0;
   op->k_s = s, op->k_noise = noise;
 }
 static int kernel_create_body(slq_context *ctx, int dtype, int64_t n, int d, const void *points, int64_t ldp, int profile, const double *ls,
@@ -1215,42 +1213,19 @@ static int kernel_create_body(slq_context *ctx, int dtype, int64_t n, int d, con
   SLQ_TRY(operator_new(ctx, OP_KERNEL, dtype, n, n * d, out, &op));
   OpGuard guard{op};
   if (!points || !ls) return fail(SLQ_EINVAL, "kernel operator: points/lengthscales is NULL");
-  KernelBad bad = dtype == SLQ_F64 ? kernel_validate<double>(n, d, on_device ? nullptr : (const double *)points, ldp, profile, ls, nls, s, noise)
-                                   : kernel_validate<float>(n, d, on_device ? nullptr : (const float *)points, ldp, profile, ls, nls, s, noise);
+  KernelBad bad = kernel_validate<double>(n, d, nullptr, ldp, profile, ls, nls, s, noise);  // (the points: below, on the host copy)
   if (bad.what != KERNEL_OK) return kernel_bad(bad);
-  const size_t es = esize(dtype);
-  // points on the device: a packed host copy for the checks and the centre (n d words, once per operator)
-  std::vector<char> host;
-  const void *hp = points;
-  int64_t hld = ldp;
-  if (on_device) {
-    host.resize((size_t)n * d * es);
-    HIP_TRY(hipMemcpy2D(host.data(), (size_t)d * es, points, (size_t)ldp * es, (size_t)d * es, (size_t)n, hipMemcpyDeviceToHost));
-    hp = host.data(), hld = d;
-    bad = dtype == SLQ_F64 ? kernel_validate<double>(n, d, (const double *)hp, hld, profile, ls, nls, s, noise)
-                           : kernel_validate<float>(n, d, (const float *)hp, hld, profile, ls, nls, s, noise);
-    if (bad.what != KERNEL_OK) return kernel_bad(bad);
-  }
-  op->k_d = d, op->k_dpad = kernel_dpad(d), op->k_npad = kernel_npad(n), op->k_profile = profile;
+  op->k_profile = profile;
   op->k_scale.reset(new KernelScale());
   for (int k = 0; k < kKernelMaxDim; ++k) op->k_scale->mean[k] = 0.0;
-  if (dtype == SLQ_F64) kernel_column_means<double>(n, d, (const double *)hp, hld, op->k_scale->mean);
-  else kernel_column_means<float>(n, d, (const float *)hp, hld, op->k_scale->mean);
+  const hipError_t e = op->k_pts.alloc_and_upload(n, d, points, ldp, on_device, dtype, ctx->stream, &bad, op->k_scale->mean);
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "kernel operator upload: %s", hipGetErrorString(e));
+  if (bad.what != KERNEL_OK) return kernel_bad(bad);
+  // (the centre comes with the points' one host pass, so an overflowing mean is found after the allocation and the upload have been
+  // issued: the guard's delete frees the buffer, and hipFree waits for the upload before the caller's points go away)
   for (int k = 0; k < d; ++k)
     if (!std::isfinite(op->k_scale->mean[k])) return fail(SLQ_EINVAL, "kernel operator: the mean of coordinate %d overflows", k);
   kernel_set_scale(op, ls, nls, s, noise);
-  // one allocation: raw points | z transposed | |z|^2 | {s, sigma2}, each on a 256-byte boundary
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t b_raw = up((size_t)n * d * es), b_zt = up((size_t)op->k_dpad * (size_t)op->k_npad * es), b_nrm = up((size_t)op->k_npad * es);
-  hipError_t e = op->k_raw.alloc(b_raw + b_zt + b_nrm + 256);
-  if (e == hipSuccess) {
-    op->k_zt = op->k_raw.as<char>() + b_raw;
-    op->k_nrm = (char *)op->k_zt + b_zt;
-    op->k_params = (char *)op->k_nrm + b_nrm;
-  }
-  if (e == hipSuccess)
-    e = hipMemcpy2DAsync(op->k_raw.p, (size_t)d * es, hp, (size_t)hld * es, (size_t)d * es, (size_t)n, hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "kernel operator upload: %s", hipGetErrorString(e));
   SLQ_TRY(kernel_rescale(op));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   *out = guard.release();
@@ -1267,7 +1242,7 @@ extern "C" int slq_kernel_create_device(slq_context *ctx, int dtype, int64_t n, 
 extern "C" int slq_kernel_set_parameters(slq_operator *op, const double *lengthscales, int nls, double outputscale, double noise) {
   if (!op) return fail(SLQ_EINVAL, "op is NULL");
   if (op->kind != OP_KERNEL) return fail(SLQ_EINVAL, "slq_kernel_set_parameters: not a kernel operator");
-  const KernelBad bad = kernel_validate_parameters(op->k_d, lengthscales, nls, outputscale, noise);
+  const KernelBad bad = kernel_validate_parameters(op->k_pts.d, lengthscales, nls, outputscale, noise);
   if (bad.what != KERNEL_OK) return kernel_bad(bad);
   HIP_TRY(hipSetDevice(op->ctx->device));
   kernel_set_scale(op, lengthscales, nls, outputscale, noise);
@@ -1277,10 +1252,10 @@ extern "C" int slq_kernel_set_parameters(slq_operator *op, const double *lengths
 extern "C" int slq_kernel_get_parameters(const slq_operator *op, int *d, int *profile, double *lengthscales, int nls, double *outputscale, double *noise) {
   if (!op) return fail(SLQ_EINVAL, "op is NULL");
   if (op->kind != OP_KERNEL) return fail(SLQ_EINVAL, "slq_kernel_get_parameters: not a kernel operator");
-  if (lengthscales && nls != op->k_d) return fail(SLQ_EINVAL, "slq_kernel_get_parameters: room for %d lengthscales, the operator has d = %d", nls, op->k_d);
-  if (d) *d = op->k_d;
+  if (lengthscales && nls != op->k_pts.d) return fail(SLQ_EINVAL, "slq_kernel_get_parameters: room for %d lengthscales, the operator has d = %d", nls, op->k_pts.d);
+  if (d) *d = op->k_pts.d;
   if (profile) *profile = op->k_profile;
-  if (lengthscales) std::copy(op->k_scale->ls, op->k_scale->ls + op->k_d, lengthscales);
+  if (lengthscales) std::copy(op->k_scale->ls, op->k_scale->ls + op->k_pts.d, lengthscales);
   if (outputscale) *outputscale = op->k_s;
   if (noise) *noise = op->k_noise;
   return SLQ_OK;
@@ -1292,10 +1267,7 @@ extern "C" int slq_debug_kernel_points(slq_operator *op, void *zt, void *nrm, vo
   if (op->kind != OP_KERNEL) return fail(SLQ_EINVAL, "slq_debug_kernel_points: not a kernel operator");
   HIP_TRY(hipSetDevice(op->ctx->device));
   HIP_TRY(hipStreamSynchronize(op->ctx->stream));
-  const size_t es = esize(op->dtype);
-  if (zt) HIP_TRY(hipMemcpy(zt, op->k_zt, (size_t)op->k_dpad * (size_t)op->k_npad * es, hipMemcpyDeviceToHost));
-  if (nrm) HIP_TRY(hipMemcpy(nrm, op->k_nrm, (size_t)op->k_npad * es, hipMemcpyDeviceToHost));
-  if (params) HIP_TRY(hipMemcpy(params, op->k_params, 2 * es, hipMemcpyDeviceToHost));
+  HIP_TRY(op->k_pts.download(zt, nrm, params, op->dtype));
   return SLQ_OK;
 }
 // kernel_schedule() of slq_kernelop.hpp as an array: rows per block, row blocks, 16-column tiles per workgroup, column chunks, slabs,
@@ -1305,8 +1277,7 @@ extern "C" int slq_debug_kernel_schedule(int64_t n, int panel_width, int panels,
   if (n <= 0 || panel_width < 16 || (panel_width & (panel_width - 1)) || panels <= 0 || num_cus <= 0)
     return fail(SLQ_EINVAL, "slq_debug_kernel_schedule: n, panels, num_cus positive, panel_width a power of two >= 16");
   const KernelSchedule S = kernel_schedule(n, panel_width, panels, num_cus);
-  out[0] = S.rows_per_block, out[1] = S.nrow_blocks, out[2] = S.col_blocks, out[3] = S.ncol_chunks, out[4] = S.nslabs;
-  for (int z = 0; z <= kKernelMaxSlabs; ++z) out[5 + z] = z <= S.nslabs ? S.slab_begin[z] : -1;
+  kernel_schedule_words({S.rows_per_block, S.nrow_blocks, S.col_blocks, S.ncol_chunks, S.nslabs}, S.nslabs, S.slab_begin, kKernelMaxSlabs, out);
   return SLQ_OK;
 }
 
@@ -2317,7 +2288,7 @@ static int launch_kernel_product(slq_plan *p, const void *Wc) {
   int log2pw = 0;
   while ((1 << log2pw) < p->PW) ++log2pw;
   char *raw = (char *)p->T + (S.nslabs > 1 ? (size_t)p->slot_stride * p->esz : 0);
-  const KernelPanelArgs a{p->n, (int)op->k_npad, op->k_dpad / 4, op->k_zt, op->k_nrm, op->k_params, Wc, log2pw, p->NP * p->PW, raw, p->slot_stride};
+  const KernelPanelArgs a{p->n, (int)op->k_pts.npad, op->k_pts.dpad / 4, op->k_pts.zt, op->k_pts.nrm, op->k_pts.params, Wc, log2pw, p->NP * p->PW, raw, p->slot_stride};
   const bool ok = p->dtype == SLQ_F64 ? kernel_panel_launch<double>(op->k_profile, S, a, st) : kernel_panel_launch<float>(op->k_profile, S, a, st);
   if (!ok) return fail(SLQ_EINVAL, "kernel operator: no product kernel for profile %d with %d column tiles", op->k_profile, S.col_blocks);
   if (S.nslabs > 1) {
@@ -4110,8 +4081,8 @@ struct slq_kernel_grad {
   slq_operator *op;  // not owned: read at every update (its z, norms and scalars as they are then)
   int64_t n, count, nparts;
   int d, dpad;
-  double *vals;  // d + 2
-  double *part;  // nparts x (dpad + 2): one partial per workgroup of a launch
+  DevBuf vals;  // d + 2 doubles
+  DevBuf part;  // nparts x (dpad + 2) doubles: one partial per workgroup of a launch
 };
 static const char *op_kind_name(int kind) {
   switch (kind) {
@@ -4135,20 +4106,14 @@ extern "C" int slq_kernel_grad_create(slq_context *ctx, slq_operator *op, slq_ke
   if (ctx->dead) return fail(SLQ_EINVAL, "slq_kernel_grad_create: the context has been destroyed");
   HIP_TRY(hipSetDevice(ctx->device));
   const KernelGradSchedule S = kernel_grad_schedule(op->n, 1, ctx->num_cus);
-  slq_kernel_grad *g = new (std::nothrow) slq_kernel_grad();
+  std::unique_ptr<slq_kernel_grad> g(new (std::nothrow) slq_kernel_grad{ctx, op, op->n, 0, S.nparts(), op->k_pts.d, op->k_pts.dpad, {}, {}});
   if (!g) return fail(SLQ_ENOMEM, "host allocation failed");
-  *g = slq_kernel_grad{ctx, op, op->n, 0, S.nparts(), op->k_d, op->k_dpad, nullptr, nullptr};
-  hipError_t e = hipMalloc((void **)&g->vals, (size_t)(g->d + 2) * 8);
-  if (e == hipSuccess) e = hipMalloc((void **)&g->part, (size_t)g->nparts * (size_t)(g->dpad + 2) * 8);
-  if (e == hipSuccess) e = hipMemsetAsync(g->vals, 0, (size_t)(g->d + 2) * 8, ctx->stream);
-  if (e != hipSuccess) {
-    for (void *p : {(void *)g->vals, (void *)g->part})
-      if (p) hipFree(p);
-    delete g;  // (not yet retained)
-    return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "slq_kernel_grad_create: %s", hipGetErrorString(e));
-  }
+  hipError_t e = g->vals.alloc((size_t)(g->d + 2) * 8);
+  if (e == hipSuccess) e = g->part.alloc((size_t)g->nparts * (size_t)(g->dpad + 2) * 8);
+  if (e == hipSuccess) e = hipMemsetAsync(g->vals.p, 0, (size_t)(g->d + 2) * 8, ctx->stream);
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "slq_kernel_grad_create: %s", hipGetErrorString(e));
   ctx_retain(ctx);
-  *out = g;
+  *out = g.release();
   return SLQ_OK;
 }
 
@@ -4156,10 +4121,9 @@ extern "C" int slq_kernel_grad_destroy(slq_kernel_grad *g) {
   if (!g) return SLQ_OK;
   hipSetDevice(g->ctx->device);
   hipStreamSynchronize(g->ctx->stream);
-  for (void *p : {(void *)g->vals, (void *)g->part})
-    if (p) hipFree(p);
-  ctx_release(g->ctx);
-  delete g;
+  slq_context *ctx = g->ctx;
+  delete g;  // (every device array is a member that frees itself)
+  ctx_release(ctx);
   return SLQ_OK;
 }
 
@@ -4181,12 +4145,12 @@ extern "C" int slq_kernel_grad_update(slq_kernel_grad *g, slq_dmat *Z, int z0, s
   hipStream_t st = g->ctx->stream;
   for (int ch = 0; ch < S.ncol_chunks; ++ch) {
     const int c0 = ch * S.chunk_cols, mc = std::min(S.chunk_cols, m - c0);
-    const KernelGradArgs a{(int)g->n, (int)op->k_npad, g->dpad / 4, (const double *)op->k_zt, (const double *)op->k_nrm,
-                           Z->d + (size_t)(z0 + c0) * g->n, W->d + (size_t)(w0 + c0) * g->n, mc, S.tiles_per_slab, g->part};
+    const KernelGradArgs a{(int)g->n, (int)op->k_pts.npad, g->dpad / 4, (const double *)op->k_pts.zt, (const double *)op->k_pts.nrm,
+                           Z->d + (size_t)(z0 + c0) * g->n, W->d + (size_t)(w0 + c0) * g->n, mc, S.tiles_per_slab, g->part.as<double>()};
     if (!kernel_grad_launch(op->k_profile, S, a, st)) return fail(SLQ_EINVAL, "slq_kernel_grad_update: no kernel for profile %d", op->k_profile);
     HIP_TRY(hipGetLastError());
     // (the chunks run one after the other on the stream: each reads the partials of its own launch)
-    k_kernel_grad_sum<<<dim3(1), dim3(128), 0, st>>>(g->d, g->dpad, g->nparts, g->part, (const double *)op->k_params, sc, alpha, ch == 0 ? beta : 1.0, g->vals);
+    k_kernel_grad_sum<<<dim3(1), dim3(128), 0, st>>>(g->d, g->dpad, g->nparts, g->part.as<const double>(), (const double *)op->k_pts.params, sc, alpha, ch == 0 ? beta : 1.0, g->vals.as<double>());
     HIP_TRY(hipGetLastError());
   }
   g->count += m;
@@ -4197,7 +4161,7 @@ extern "C" int slq_kernel_grad_get(slq_kernel_grad *g, double *vals, int nvals, 
   if (!g) return fail(SLQ_EINVAL, "slq_kernel_grad_get: accumulator is NULL");
   if (vals && nvals != g->d + 2) return fail(SLQ_EINVAL, "slq_kernel_grad_get: room for %d values, the accumulator holds d + 2 = %d", nvals, g->d + 2);
   HIP_TRY(hipSetDevice(g->ctx->device));
-  if (vals) HIP_TRY(hipMemcpyAsync(vals, g->vals, (size_t)(g->d + 2) * 8, hipMemcpyDeviceToHost, g->ctx->stream));
+  if (vals) HIP_TRY(hipMemcpyAsync(vals, g->vals.p, (size_t)(g->d + 2) * 8, hipMemcpyDeviceToHost, g->ctx->stream));
   HIP_TRY(hipStreamSynchronize(g->ctx->stream));
   if (count) *count = g->count;
   return SLQ_OK;
@@ -4206,7 +4170,7 @@ extern "C" int slq_kernel_grad_get(slq_kernel_grad *g, double *vals, int nvals, 
 extern "C" int slq_kernel_grad_reset(slq_kernel_grad *g) {
   if (!g) return fail(SLQ_EINVAL, "slq_kernel_grad_reset: accumulator is NULL");
   HIP_TRY(hipSetDevice(g->ctx->device));
-  HIP_TRY(hipMemsetAsync(g->vals, 0, (size_t)(g->d + 2) * 8, g->ctx->stream));
+  HIP_TRY(hipMemsetAsync(g->vals.p, 0, (size_t)(g->d + 2) * 8, g->ctx->stream));
   g->count = 0;
   return SLQ_OK;
 }
@@ -4217,8 +4181,7 @@ extern "C" int slq_debug_kernel_grad_schedule(int64_t n, int m, int num_cus, int
   if (!out || nout < 5 + kKernelMaxSlabs + 1) return fail(SLQ_EINVAL, "slq_debug_kernel_grad_schedule: room for %d values", 5 + kKernelMaxSlabs + 1);
   if (n <= 0 || n >= ((int64_t)1 << 31) - 16 || m <= 0 || num_cus <= 0) return fail(SLQ_EINVAL, "slq_debug_kernel_grad_schedule: 0 < n < 2^31 - 16, m and num_cus positive");
   const KernelGradSchedule S = kernel_grad_schedule(n, m, num_cus);
-  out[0] = S.rows_per_block, out[1] = S.nrow_blocks, out[2] = S.chunk_cols, out[3] = S.ncol_chunks, out[4] = S.nslabs;
-  for (int z = 0; z <= kKernelMaxSlabs; ++z) out[5 + z] = z <= S.nslabs ? S.slab_begin[z] : -1;
+  kernel_schedule_words({S.rows_per_block, S.nrow_blocks, S.chunk_cols, S.ncol_chunks, S.nslabs}, S.nslabs, S.slab_begin, kKernelMaxSlabs, out);
   return SLQ_OK;
 }
 
@@ -4227,10 +4190,7 @@ struct slq_kernel_cross {
   slq_context *ctx = nullptr;
   slq_operator *op = nullptr;  // not owned: read at every product (its z, norms, s and lengthscales as they are then)
   int dtype = SLQ_F64;
-  int64_t m = 0, mpad = 0;
-  int d = 0, dpad = 0;
-  DevBuf buf;  // one allocation: the raw new points, and behind them what the next three point to
-  void *zt = nullptr, *nrm = nullptr, *params = nullptr;  // z*^T (dpad x mpad), |z*|^2 (mpad), two words k_kernel_rescale writes (never the operator's)
+  KernelPoints pts;  // the m new points, z*^T (dpad x mpad), |z*|^2 (mpad) and two words k_kernel_rescale writes (never the operator's)
   uint64_t epoch = 0;  // the operator's k_epoch the z* were derived at
   DevBuf scratch;      // slab partials: sized on first use, grown on demand
   DevBuf stage_in, stage_out;  // device copies of the host panels of slq_kernel_cross_matmat (grown on demand)
@@ -4238,25 +4198,8 @@ struct slq_kernel_cross {
 
 // z*, |z*|^2 from the raw new points with the operator's centre and its lengthscales of now, on the stream (no allocation, no upload)
 static int kernel_cross_rescale(slq_kernel_cross *c) {
-  const slq_operator *op = c->op;
-  const int m = (int)c->m, mpad = (int)c->mpad;
-  const dim3 g((unsigned)((mpad + 255) / 256));
-  if (c->dtype == SLQ_F64)
-    k_kernel_rescale<double><<<g, dim3(256), 0, c->ctx->stream>>>(m, mpad, c->d, c->dpad, c->buf.as<const double>(), *op->k_scale, (double *)c->zt, (double *)c->nrm,
-                                                                 (double *)c->params, op->k_s, 0.0);
-  else
-    k_kernel_rescale<float><<<g, dim3(256), 0, c->ctx->stream>>>(m, mpad, c->d, c->dpad, c->buf.as<const float>(), *op->k_scale, (float *)c->zt, (float *)c->nrm,
-                                                                (float *)c->params, op->k_s, 0.0);
-  HIP_TRY(hipGetLastError());
-  c->epoch = op->k_epoch;
-  return SLQ_OK;
-}
-
-template <typename F> static int kernel_cross_check_points(int64_t m, int d, const F *pts, int64_t ldp) {
-  for (int64_t i = 0; i < m; ++i)
-    for (int k = 0; k < d; ++k)
-      if (!std::isfinite((double)pts[i * ldp + k]))
-        return fail(SLQ_EINVAL, "slq_kernel_cross_create: new point %lld, coordinate %d is %g (points must be finite)", (long long)i, k, (double)pts[i * ldp + k]);
+  HIP_TRY(c->pts.rescale(*c->op->k_scale, c->op->k_s, 0.0, c->dtype, c->ctx->stream));
+  c->epoch = c->op->k_epoch;
   return SLQ_OK;
 }
 
@@ -4268,35 +4211,19 @@ static int kernel_cross_create_body(slq_context *ctx, slq_operator *op, int64_t 
   if (op->ctx != ctx) return fail(SLQ_EINVAL, "slq_kernel_cross_create: the operator belongs to another context");
   if (ctx->dead) return fail(SLQ_EINVAL, "slq_kernel_cross_create: the context has been destroyed");
   if (m < 1 || m >= ((int64_t)1 << 31) - 16) return fail(SLQ_EINVAL, "slq_kernel_cross_create: m = %lld new points (1 <= m < 2^31 - 16)", (long long)m);
-  const int d = op->k_d;
+  const int d = op->k_pts.d;
   if (ldp < d) return fail(SLQ_EINVAL, "slq_kernel_cross_create: ldp = %lld is below d = %d", (long long)ldp, d);
-  const size_t es = esize(op->dtype);
   HIP_TRY(hipSetDevice(ctx->device));
   try {
-    // points on the device: a packed host copy for the check (m d words, once per object)
-    std::vector<char> host;
-    const void *hp = points;
-    int64_t hld = ldp;
-    if (on_device) {
-      host.resize((size_t)m * d * es);
-      HIP_TRY(hipMemcpy2D(host.data(), (size_t)d * es, points, (size_t)ldp * es, (size_t)d * es, (size_t)m, hipMemcpyDeviceToHost));
-      hp = host.data(), hld = d;
-    }
-    SLQ_TRY(op->dtype == SLQ_F64 ? kernel_cross_check_points<double>(m, d, (const double *)hp, hld) : kernel_cross_check_points<float>(m, d, (const float *)hp, hld));
     std::unique_ptr<slq_kernel_cross> c(new slq_kernel_cross());
-    c->ctx = ctx, c->op = op, c->dtype = op->dtype, c->m = m, c->mpad = kernel_npad(m), c->d = d, c->dpad = op->k_dpad;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t b_raw = up((size_t)m * d * es), b_zt = up((size_t)c->dpad * (size_t)c->mpad * es), b_nrm = up((size_t)c->mpad * es);
-    hipError_t e = c->buf.alloc(b_raw + b_zt + b_nrm + 256);
-    if (e == hipSuccess) {
-      c->zt = c->buf.as<char>() + b_raw;
-      c->nrm = (char *)c->zt + b_zt;
-      c->params = (char *)c->nrm + b_nrm;
-      e = hipMemcpy2DAsync(c->buf.p, (size_t)d * es, hp, (size_t)hld * es, (size_t)d * es, (size_t)m, hipMemcpyHostToDevice, ctx->stream);
-    }
+    c->ctx = ctx, c->op = op, c->dtype = op->dtype;
+    KernelBad bad;
+    const hipError_t e = c->pts.alloc_and_upload(m, d, points, ldp, on_device, op->dtype, ctx->stream, &bad);
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "slq_kernel_cross_create: %s", hipGetErrorString(e));
+    if (bad.what != KERNEL_OK)
+      return fail(SLQ_EINVAL, "slq_kernel_cross_create: new point %lld, coordinate %d is %g (points must be finite)", (long long)bad.row, (int)bad.col, bad.value);
     SLQ_TRY(kernel_cross_rescale(c.get()));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));  // (the host copy of the points goes with this frame)
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx_retain(ctx);
     *out = c.release();
   } catch (const std::bad_alloc &) {
@@ -4326,8 +4253,8 @@ static int kernel_cross_product(slq_kernel_cross *c, int trans, const void *X, i
   const slq_operator *op = c->op;
   if (c->epoch != op->k_epoch) SLQ_TRY(kernel_cross_rescale(c));  // the hyperparameters have moved: z* follow, before this product
   const bool fwd = trans == 0;
-  const int64_t nrows = fwd ? c->m : op->n, nsum = fwd ? op->n : c->m;
-  const KernelCrossSchedule S = kernel_cross_schedule(nrows, nsum, b, c->ctx->num_cus);
+  const int64_t nrows = fwd ? c->pts.n : op->n, nsum = fwd ? op->n : c->pts.n;
+  const KernelSchedule S = kernel_cross_schedule(nrows, nsum, b, c->ctx->num_cus);
   if (S.ncol_chunks > 65535) return fail(SLQ_EINVAL, "%s: b = %d columns (at most %d)", who, b, 65535 * 16 * kKernelMaxColBlocks);
   const size_t es = esize(c->dtype);
   const int64_t slab_stride = nrows * (int64_t)b;
@@ -4339,12 +4266,12 @@ static int kernel_cross_product(slq_kernel_cross *c, int trans, const void *X, i
     }
   }
   KernelCrossArgs a;
-  a.nrows = (int)nrows, a.rpad = (int)(fwd ? c->mpad : op->k_npad);
-  a.nsum = (int)nsum, a.spad = (int)(fwd ? op->k_npad : c->mpad);
-  a.dq = c->dpad / 4;
-  a.rzt = fwd ? c->zt : op->k_zt, a.rnrm = fwd ? c->nrm : op->k_nrm;
-  a.szt = fwd ? op->k_zt : c->zt, a.snrm = fwd ? op->k_nrm : c->nrm;
-  a.params = op->k_params;
+  a.nrows = (int)nrows, a.rpad = (int)(fwd ? c->pts.npad : op->k_pts.npad);
+  a.nsum = (int)nsum, a.spad = (int)(fwd ? op->k_pts.npad : c->pts.npad);
+  a.dq = c->pts.dpad / 4;
+  a.rzt = fwd ? c->pts.zt : op->k_pts.zt, a.rnrm = fwd ? c->pts.nrm : op->k_pts.nrm;
+  a.szt = fwd ? op->k_pts.zt : c->pts.zt, a.snrm = fwd ? op->k_pts.nrm : c->pts.nrm;
+  a.params = op->k_pts.params;
   a.W = X, a.ldw = ldx, a.b = b;
   a.out = S.nslabs > 1 ? c->scratch.p : Y, a.ldo = S.nslabs > 1 ? nrows : ldy, a.slab_stride = slab_stride;
   if (!kernel_cross_launch(c->dtype == SLQ_F64, op->k_profile, S, a, (void *)c->ctx->stream))
@@ -4362,7 +4289,7 @@ extern "C" int slq_kernel_cross_matmat(slq_kernel_cross *c, int trans, const voi
   if (!X || !Y) return fail(SLQ_EINVAL, "slq_kernel_cross_matmat: X/Y is NULL");
   if (trans != 0 && trans != 1) return fail(SLQ_EINVAL, "slq_kernel_cross_matmat: trans = %d (0: Y = C X, 1: Y = C^T X)", trans);
   if (b < 1) return fail(SLQ_EINVAL, "slq_kernel_cross_matmat: b = %d columns (b >= 1)", b);
-  const int64_t rin = trans ? c->m : c->op->n, rout = trans ? c->op->n : c->m;
+  const int64_t rin = trans ? c->pts.n : c->op->n, rout = trans ? c->op->n : c->pts.n;
   if (ldx < rin) return fail(SLQ_EINVAL, "slq_kernel_cross_matmat: ldx = %lld is below the %lld rows of X (trans = %d)", (long long)ldx, (long long)rin, trans);
   if (ldy < rout) return fail(SLQ_EINVAL, "slq_kernel_cross_matmat: ldy = %lld is below the %lld rows of Y (trans = %d)", (long long)ldy, (long long)rout, trans);
   HIP_TRY(hipSetDevice(c->ctx->device));
@@ -4385,7 +4312,7 @@ extern "C" int slq_kernel_cross_dmat(slq_kernel_cross *c, int trans, slq_dmat *I
   if (b < 1) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: b = %d columns (b >= 1)", b);
   SLQ_TRY(dmat_range(IN, i0, b, "slq_kernel_cross_dmat(IN)"));
   SLQ_TRY(dmat_range(OUT, o0, b, "slq_kernel_cross_dmat(OUT)"));
-  const int64_t rin = trans ? c->m : c->op->n, rout = trans ? c->op->n : c->m;
+  const int64_t rin = trans ? c->pts.n : c->op->n, rout = trans ? c->op->n : c->pts.n;
   if (IN->n != rin) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: IN has %lld rows, the product with trans = %d reads %lld", (long long)IN->n, trans, (long long)rin);
   if (OUT->n != rout) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: OUT has %lld rows, the product with trans = %d writes %lld", (long long)OUT->n, trans, (long long)rout);
   if (IN->ctx != c->ctx || OUT->ctx != c->ctx) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: a matrix belongs to another context");
@@ -4401,9 +4328,7 @@ extern "C" int slq_debug_kernel_cross_points(slq_kernel_cross *c, void *zt, void
   HIP_TRY(hipSetDevice(c->ctx->device));
   if (c->epoch != c->op->k_epoch) SLQ_TRY(kernel_cross_rescale(c));
   HIP_TRY(hipStreamSynchronize(c->ctx->stream));
-  const size_t es = esize(c->dtype);
-  if (zt) HIP_TRY(hipMemcpy(zt, c->zt, (size_t)c->dpad * (size_t)c->mpad * es, hipMemcpyDeviceToHost));
-  if (nrm) HIP_TRY(hipMemcpy(nrm, c->nrm, (size_t)c->mpad * es, hipMemcpyDeviceToHost));
+  HIP_TRY(c->pts.download(zt, nrm, nullptr, c->dtype));
   return SLQ_OK;
 }
 
@@ -4414,9 +4339,8 @@ extern "C" int slq_debug_kernel_cross_schedule(int64_t nrows, int64_t nsum, int6
   const int64_t lim = ((int64_t)1 << 31) - 16;
   if (nrows <= 0 || nrows >= lim || nsum <= 0 || nsum >= lim || b <= 0 || b >= lim || num_cus <= 0)
     return fail(SLQ_EINVAL, "slq_debug_kernel_cross_schedule: 0 < nrows, nsum, b < 2^31 - 16 and num_cus positive");
-  const KernelCrossSchedule S = kernel_cross_schedule(nrows, nsum, b, num_cus);
-  out[0] = S.rows_per_block, out[1] = S.nrow_blocks, out[2] = S.col_blocks, out[3] = S.ncol_chunks, out[4] = S.nslabs, out[5] = S.tiles_per_slab;
-  for (int z = 0; z <= kKernelCrossMaxSlabs; ++z) out[6 + z] = z <= S.nslabs ? S.slab_begin[z] : -1;
+  const KernelSchedule S = kernel_cross_schedule(nrows, nsum, b, num_cus);
+  kernel_schedule_words({S.rows_per_block, S.nrow_blocks, S.col_blocks, S.ncol_chunks, S.nslabs, S.tiles_per_slab}, S.nslabs, S.slab_begin, kKernelCrossMaxSlabs, out);
   return SLQ_OK;
 }
 

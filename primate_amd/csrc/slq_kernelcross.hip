@@ -8,7 +8,7 @@
 
 namespace slq {
 
-bool kernel_cross_launch(int dtype_is_f64, int profile, const KernelCrossSchedule &S, const KernelCrossArgs &a, void *stream) {
+bool kernel_cross_launch(int dtype_is_f64, int profile, const KernelSchedule &S, const KernelCrossArgs &a, void *stream) {
   hipStream_t st = (hipStream_t)stream;
   return dtype_is_f64 ? kernel_cross_launch_profile<double>(profile, S, a, st) : kernel_cross_launch_profile<float>(profile, S, a, st);
 }

@@ -7,7 +7,7 @@
 //   g_sigma2 =           sum_i  C_ii                         (dA/dsigma2 = I)
 // W = probes, Z = f'(A) probes: the Girard-Hutchinson estimate of d tr f(A) / d theta; Z = W = A^-1 y: the data-fit term. Neither A
 // nor C is ever held: a 16 x 16 tile of each is one small MFMA GEMM, both land in the same lanes, and the sums are taken from there.
-// Two parts:
+// The tile walk, r2, the profiles (phi with chi) and the slab rule are those of slq_kerneltile.hpp; here is what is the gradient's own:
 //   host (plain C++, no HIP include; scripts/kernelgrad_check.cpp runs it under the host sanitizers)
 //     kernel_grad_schedule   row blocks, j slabs and column chunks of one update for (n, m, num_cus) (slq_debug_kernel_grad_schedule)
 //   device (hipcc only)
@@ -22,7 +22,7 @@ namespace slq {
 constexpr int kKernelGradCols = 64;  // columns of Z and W one launch contracts: 16 fp64 B fragments of Z_I per lane
 
 // ---- the schedule of one update -----------------------------------------------------------------------------------------
-// Row blocks and j slabs by the rule of kernel_schedule for one column chunk per workgroup (a launch per chunk: the chunks of a
+// Row blocks and j slabs by kernel_slab_split for one column chunk per workgroup - kernel_schedule's slabs of a 16-column product (a launch per chunk: the chunks of a
 // wider m run one after the other on the stream and each folds into the values); slab z covers the points
 // [slab_begin[z], slab_begin[z + 1]) - whole tiles of 16, tiles_per_slab of them but for the last.
 struct KernelGradSchedule {
@@ -36,13 +36,12 @@ struct KernelGradSchedule {
   int64_t nparts() const { return (int64_t)nrow_blocks * nslabs; }  // workgroups, and partials, of one launch
 };
 inline KernelGradSchedule kernel_grad_schedule(int64_t n, int m, int num_cus) {
-  const KernelSchedule K = kernel_schedule(n, 16, 1, num_cus);  // (one column chunk per workgroup, whatever its width)
   KernelGradSchedule S;
-  S.nrow_blocks = K.nrow_blocks;
+  S.nrow_blocks = (int)((n + kKernelRows - 1) / kKernelRows);
   S.ncol_chunks = (m + kKernelGradCols - 1) / kKernelGradCols;
-  S.nslabs = K.nslabs;
-  S.tiles_per_slab = K.tiles_per_slab;
-  for (int z = 0; z <= kKernelMaxSlabs; ++z) S.slab_begin[z] = K.slab_begin[z];
+  const KernelSlabSplit s = kernel_slab_split((n + 15) / 16, (double)S.nrow_blocks, num_cus, kKernelMaxSlabs);  // (one column chunk per workgroup, whatever its width)
+  S.nslabs = s.nslabs, S.tiles_per_slab = s.tiles_per_slab;
+  kernel_slab_begin(s, n, S.slab_begin);
   return S;
 }
 
@@ -52,28 +51,8 @@ struct KernelGradScale {
   double ls[kKernelMaxDim];  // the operator's host scale at update time, per dimension
 };
 
-// phi and chi = -2 dphi/dr2 of one r2 from one exp. matern12: chi = exp(-r) / r is DEFINED 0 at r2 = 0 (the diagonal, duplicate
-// points, a clamped r2): chi D^2 tends to 0 there and must not become inf * 0.
-template <int PROFILE> __device__ __forceinline__ void kernel_profile_pair(double r2, double &phi, double &chi) {
-  if constexpr (PROFILE == KERNEL_RBF) {
-    phi = chi = exp(-0.5 * r2);
-  } else if constexpr (PROFILE == KERNEL_MATERN12) {
-    const double r = sqrt(r2);
-    phi = exp(-r);
-    chi = r2 > 0.0 ? phi / r : 0.0;
-  } else if constexpr (PROFILE == KERNEL_MATERN32) {
-    const double a = 1.7320508075688772935 * sqrt(r2), e = exp(-a);
-    phi = (1.0 + a) * e;
-    chi = 3.0 * e;
-  } else {
-    const double a = 2.2360679774997896964 * sqrt(r2), e = exp(-a);
-    phi = fma(5.0 / 3.0, r2, 1.0 + a) * e;
-    chi = (5.0 / 3.0) * (1.0 + a) * e;
-  }
-}
-
-// Grid (row blocks, j slabs); a wave owns 16 rows I and walks its slab's j in tiles of 16. Per tile J:
-//   G^T = z_J z_I^T   as k_kernel_panel forms it - the same operands in the same order, so r2 carries the operator's bits, with its
+// Grid (row blocks, j slabs); a wave owns 16 rows I and walks its slab's j in tiles of 16 (KernelTile, kernel_tile_walk). Per tile J:
+//   G^T, r2           of KernelTile - the operator's operands in the operator's order, so r2 carries the operator's bits, with its
 //                     clamp and its diagonal rule;
 //   C^T = W_J Z_I^T   MQ MFMAs at most (the chunk's mc <= 64 columns padded to 4 mq): A operand W_J from LDS (column-major: 16
 //                     consecutive words per column), B operand Z_I from registers (loaded once). C^T[j][i] lands in the lane that
@@ -91,10 +70,10 @@ template <int PROFILE, int DQ>
 __global__ __launch_bounds__(64 * kKernelWaves) void k_kernel_grad(int n, int npad, int dq, const double *__restrict__ zt, const double *__restrict__ nrm,
                                                                    const double *__restrict__ Z, const double *__restrict__ W, int mc, int tiles_per_slab,
                                                                    double *__restrict__ part) {
+  using T = KernelTile<double, DQ>;
   constexpr int MQ = kKernelGradCols / 4;
-  constexpr int NT = 64 * kKernelWaves;
+  constexpr int NT = T::NT;
   constexpr int WPT = (16 * kKernelGradCols + NT - 1) / NT;
-  constexpr int ZPT = (DQ * 4 * 16 + NT - 1) / NT;
   __shared__ __attribute__((aligned(16))) double Ws[kKernelGradCols][16];
   __shared__ __attribute__((aligned(16))) double Zs[DQ * 4][16];
   __shared__ double Ns[16];
@@ -102,23 +81,21 @@ __global__ __launch_bounds__(64 * kKernelWaves) void k_kernel_grad(int n, int np
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 15, lk = lane >> 4;
   const int i0 = blockIdx.x * kKernelRows + wave * 16;
-  const int ntiles = npad >> 4;
-  const int t_begin = min(ntiles, (int)blockIdx.y * tiles_per_slab), t_end = min(ntiles, t_begin + tiles_per_slab);
+  int t_begin, t_end;
+  kernel_slab_tiles<int>(npad >> 4, tiles_per_slab, (int)blockIdx.y, &t_begin, &t_end);
   const int mq = (mc + 3) >> 2;
 
   // this wave's rows: z_I^T and Z_I^T as B operands, |z_i|^2 for the lane's column i = lr
-  double zi[DQ], zc[MQ];
-  const bool i_pad = i0 + lr < npad, i_ok = i0 + lr < n;
-#pragma unroll
-  for (int q = 0; q < DQ; ++q) zi[q] = (q < dq && i_pad) ? zt[(int64_t)(4 * q + lk) * npad + i0 + lr] : 0.0;
+  double zi[DQ], ni, zc[MQ];
+  T::rows(zt, nrm, npad, dq, i0, lr, lk, zi, ni);
+  const bool i_ok = i0 + lr < n;
 #pragma unroll
   for (int q = 0; q < MQ; ++q) zc[q] = (i_ok && 4 * q + lk < mc) ? Z[(int64_t)(4 * q + lk) * n + i0 + lr] : 0.0;
-  const double ni = i_pad ? nrm[i0 + lr] : 0.0;
   double acc[DQ], as = 0.0, ad = 0.0;
 #pragma unroll
   for (int q = 0; q < DQ; ++q) acc[q] = 0.0;
 
-  double wreg[WPT], zreg[ZPT], nreg = 0.0;
+  double wreg[WPT], zreg[T::ZPT], nreg = 0.0;
   auto fetch = [&](int t) {
     const int j0 = t * 16;
 #pragma unroll
@@ -127,7 +104,7 @@ __global__ __launch_bounds__(64 * kKernelWaves) void k_kernel_grad(int n, int np
       wreg[u] = (c < mc && j < n) ? W[(int64_t)c * n + j] : 0.0;
     }
 #pragma unroll
-    for (int u = 0; u < ZPT; ++u) {
+    for (int u = 0; u < T::ZPT; ++u) {
       const int e = tid + u * NT, k = e >> 4, jj = e & 15;
       zreg[u] = (e < DQ * 64 && k < 4 * dq) ? zt[(int64_t)k * npad + j0 + jj] : 0.0;
     }
@@ -139,38 +116,20 @@ __global__ __launch_bounds__(64 * kKernelWaves) void k_kernel_grad(int n, int np
       const int e = tid + u * NT;
       if (e < 16 * kKernelGradCols) Ws[e >> 4][e & 15] = wreg[u];
     }
-#pragma unroll
-    for (int u = 0; u < ZPT; ++u) {
-      const int e = tid + u * NT;
-      if (e < DQ * 64) Zs[e >> 4][e & 15] = zreg[u];
-    }
-    if (tid < 16) Ns[tid] = nreg;
+    T::stash(Zs, Ns, tid, zreg, nreg);
   };
-  if (t_begin < t_end) {
-    fetch(t_begin);
-    stash();
-  }
-  __syncthreads();
-  for (int t = t_begin; t < t_end; ++t) {
-    const bool more = t + 1 < t_end;  // (uniform over the workgroup)
-    if (more) fetch(t + 1);
-    kd4_t g = (kd4_t)0.0, c = (kd4_t)0.0;
-#pragma unroll
-    for (int q = 0; q < DQ; ++q)
-      if (q < dq) g = kernel_mfma(Zs[4 * q + lk][lr], zi[q], g);
+  kernel_tile_walk(t_begin, t_end, fetch, stash, [&](int t) {
+    const kd4_t g = T::gram(Zs, zi, dq, lr, lk);
+    kd4_t c = (kd4_t)0.0;
 #pragma unroll
     for (int q = 0; q < MQ; ++q)
       if (q < mq) c = kernel_mfma(Ws[4 * q + lk][lr], zc[q], c);
     double b[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int jr = lk + 4 * r;
-      double r2 = fma(-2.0, g[r], ni + Ns[jr]);
-      r2 = fmax(r2, 0.0);
-      const bool diag = t * 16 + jr == i0 + lr;
-      if (diag) r2 = 0.0;
+      const bool diag = t * 16 + T::jr(lk, r) == i0 + lr;
       double phi, chi;
-      kernel_profile_pair<PROFILE>(r2, phi, chi);
+      kernel_profile_pair<double, PROFILE>(T::r2(g, r, ni, Ns, lk, diag), phi, chi);
       as = fma(phi, c[r], as);
       if (diag) ad += c[r];
       b[r] = chi * c[r];
@@ -187,10 +146,7 @@ __global__ __launch_bounds__(64 * kKernelWaves) void k_kernel_grad(int n, int np
             acc[q] = fma(bj, dlt * dlt, acc[q]);
           }
       }
-    __syncthreads();
-    if (more) stash();
-    __syncthreads();
-  }
+  });
   // lanes: the 16 lr of a coordinate; all 64 for the two scalars
 #pragma unroll
   for (int off = 1; off < 16; off <<= 1) {
@@ -230,28 +186,21 @@ __global__ __launch_bounds__(128) void k_kernel_grad_sum(int d, int dpad, int64_
   vals[t] = fma(alpha, v, old);
 }
 
-// the launch for (profile, d): every instantiation is named here. false: no such kernel (the caller reports it: there is no fallback)
+// false: no such kernel (the caller reports it: there is no fallback)
 struct KernelGradArgs {
   int n, npad, dq;
   const double *zt, *nrm, *Z, *W;
   int mc, tiles_per_slab;
   double *part;
 };
-template <int PROFILE> static inline void kernel_grad_launch_dq(const KernelGradSchedule &S, const KernelGradArgs &a, hipStream_t st) {
-  const dim3 g(S.nrow_blocks, S.nslabs), b(64 * kKernelWaves);
-  if (a.dq <= 4)
-    k_kernel_grad<PROFILE, 4><<<g, b, 0, st>>>(a.n, a.npad, a.dq, a.zt, a.nrm, a.Z, a.W, a.mc, a.tiles_per_slab, a.part);
-  else
-    k_kernel_grad<PROFILE, 16><<<g, b, 0, st>>>(a.n, a.npad, a.dq, a.zt, a.nrm, a.Z, a.W, a.mc, a.tiles_per_slab, a.part);
-}
 static inline bool kernel_grad_launch(int profile, const KernelGradSchedule &S, const KernelGradArgs &a, hipStream_t st) {
-  switch (profile) {
-    case KERNEL_RBF: kernel_grad_launch_dq<KERNEL_RBF>(S, a, st); return true;
-    case KERNEL_MATERN12: kernel_grad_launch_dq<KERNEL_MATERN12>(S, a, st); return true;
-    case KERNEL_MATERN32: kernel_grad_launch_dq<KERNEL_MATERN32>(S, a, st); return true;
-    case KERNEL_MATERN52: kernel_grad_launch_dq<KERNEL_MATERN52>(S, a, st); return true;
-    default: return false;
-  }
+  const dim3 g(S.nrow_blocks, S.nslabs), b(64 * kKernelWaves);
+  return kernel_for_profile(profile, [&](auto P) {
+    return kernel_for_dq(a.dq, [&](auto DQ) {
+      k_kernel_grad<P(), DQ()><<<g, b, 0, st>>>(a.n, a.npad, a.dq, a.zt, a.nrm, a.Z, a.W, a.mc, a.tiles_per_slab, a.part);
+      return true;
+    });
+  });
 }
 #endif  // __HIPCC__
 

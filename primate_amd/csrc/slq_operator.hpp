@@ -1,5 +1,5 @@
 // slq_operator.hpp — the operator handle of slq.hip and what it owns, as values: one owning device buffer (DevBuf), a stored CSR
-// (CsrArrays), a ring-fed tile stream (TileStream). Destroying an operator is `delete`: every device array is a member that frees
+// (CsrArrays), a ring-fed tile stream (TileStream), a set of scaled points (KernelPoints). Destroying an operator is `delete`: every device array is a member that frees
 // itself, so an array added here cannot leak and a half-built operator goes with everything it has so far.
 #pragma once
 #include "../../include/slq.h"
@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "slq_common.hpp"
-#include "slq_kernelop.hpp"  // KernelScale
+#include "slq_kernelop.hpp"  // KernelScale, k_kernel_rescale
 #include "slq_switches.hpp"
 
 namespace slq {
@@ -105,6 +105,63 @@ struct TileStreamPair {
   bool tried = false;  // merged streams: built, or found unbuildable, by the first plan that asked (ensure_ring_stream)
 };
 
+// A set of scaled points on the device (slq_kernelop.hpp): one allocation raw points (n x d, row-major) | z transposed (dpad x
+// npad) | |z|^2 (npad) | two words {s, sigma2}, each on a 256-byte boundary. The addresses never change after alloc_and_upload - a
+// captured graph reads them - and rescale() rewrites everything behind the raw points in place.
+struct KernelPoints {
+  DevBuf buf;
+  void *zt = nullptr, *nrm = nullptr, *params = nullptr;
+  int64_t n = 0, npad = 0;
+  int d = 0, dpad = 0;
+  // n_ points of d_ coordinates, ldp words apart, on the host or (on_device) on the device: checked finite on the host - of device
+  // points a packed host copy is taken, once - and uploaded on `st`. bad->what != KERNEL_OK: the first coordinate that is not
+  // finite, and nothing is allocated. mean (may be NULL): kernel_column_means of the points. The caller's host points are read
+  // until `st` has run.
+  hipError_t alloc_and_upload(int64_t n_, int d_, const void *points, int64_t ldp, bool on_device, int dtype, hipStream_t st, KernelBad *bad, double *mean = nullptr) {
+    const size_t es = dtype == SLQ_F64 ? 8 : 4;
+    std::vector<char> host;
+    if (on_device) {
+      host.resize((size_t)n_ * d_ * es);
+      const hipError_t e = hipMemcpy2D(host.data(), (size_t)d_ * es, points, (size_t)ldp * es, (size_t)d_ * es, (size_t)n_, hipMemcpyDeviceToHost);
+      if (e != hipSuccess) return e;
+      points = host.data(), ldp = d_;
+    }
+    *bad = dtype == SLQ_F64 ? kernel_first_bad_point<double>(n_, d_, (const double *)points, ldp) : kernel_first_bad_point<float>(n_, d_, (const float *)points, ldp);
+    if (bad->what != KERNEL_OK) return hipSuccess;
+    if (mean && dtype == SLQ_F64) kernel_column_means<double>(n_, d_, (const double *)points, ldp, mean);
+    else if (mean) kernel_column_means<float>(n_, d_, (const float *)points, ldp, mean);
+    n = n_, npad = kernel_npad(n_), d = d_, dpad = kernel_dpad(d_);
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t b_raw = up((size_t)n * d * es), b_zt = up((size_t)dpad * (size_t)npad * es), b_nrm = up((size_t)npad * es);
+    hipError_t e = buf.alloc(b_raw + b_zt + b_nrm + 256);
+    if (e != hipSuccess) return e;
+    zt = buf.as<char>() + b_raw;
+    nrm = (char *)zt + b_zt;
+    params = (char *)nrm + b_nrm;
+    e = hipMemcpy2DAsync(buf.p, (size_t)d * es, points, (size_t)ldp * es, (size_t)d * es, (size_t)n, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && on_device) e = hipStreamSynchronize(st);  // (the host copy goes with this frame)
+    return e;
+  }
+  // z, |z|^2, s and sigma2 from the raw points, on `st` (no allocation, no upload)
+  hipError_t rescale(const KernelScale &sc, double s, double noise, int dtype, hipStream_t st) const {
+    const dim3 g((unsigned)((npad + 255) / 256));
+    if (dtype == SLQ_F64)
+      k_kernel_rescale<double><<<g, dim3(256), 0, st>>>((int)n, (int)npad, d, dpad, buf.as<const double>(), sc, (double *)zt, (double *)nrm, (double *)params, s, noise);
+    else
+      k_kernel_rescale<float><<<g, dim3(256), 0, st>>>((int)n, (int)npad, d, dpad, buf.as<const float>(), sc, (float *)zt, (float *)nrm, (float *)params, s, noise);
+    return hipGetLastError();
+  }
+  // what the kernels read, as it is on the device now, to host arrays (any may be NULL); the caller has waited for the stream
+  hipError_t download(void *zt_h, void *nrm_h, void *params_h, int dtype) const {
+    const size_t es = dtype == SLQ_F64 ? 8 : 4;
+    hipError_t e = hipSuccess;
+    if (zt_h) e = hipMemcpy(zt_h, zt, (size_t)dpad * (size_t)npad * es, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && nrm_h) e = hipMemcpy(nrm_h, nrm, (size_t)npad * es, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && params_h) e = hipMemcpy(params_h, params, 2 * es, hipMemcpyDeviceToHost);
+    return e;
+  }
+};
+
 }  // namespace slq
 
 struct slq_context;
@@ -147,12 +204,10 @@ struct slq_operator {
   // affine CSR operator A + t B (slq_csr_affine_create): values of A and B on the union pattern (csr.vals = va + t vb)
   slq::DevBuf vals_a, vals_b;
   slq::OperatorSwitches sw;  // the switches as they were when the operator was created (slq_switches.hpp)
-  // OP_KERNEL (slq_kernelop.hpp): the raw points (n x d), z transposed (dpad x npad) and |z|^2 (npad), s and sigma2 in two device
-  // words - all at addresses that never change, so that a captured graph sees a hyperparameter change. nnz reports n d.
-  int k_d = 0, k_dpad = 0, k_profile = 0;
-  int64_t k_npad = 0;
-  slq::DevBuf k_raw;  // one allocation: the points, and behind them what the next three point to
-  void *k_zt = nullptr, *k_nrm = nullptr, *k_params = nullptr;
+  // OP_KERNEL (slq_kernelop.hpp): the points, their z and |z|^2, s and sigma2 in two device words - all at addresses that never
+  // change, so that a captured graph sees a hyperparameter change. nnz reports n d.
+  int k_profile = 0;
+  slq::KernelPoints k_pts;
   std::unique_ptr<slq::KernelScale> k_scale;  // host: the centre of the points and the lengthscales per dimension
   double k_s = 1.0, k_noise = 0.0;
   uint64_t k_epoch = 0;  // host: incremented by every slq_kernel_set_parameters; a slq_kernel_cross compares it with the one its z* were derived at

@@ -22,7 +22,7 @@ static long g_cases = 0, g_failed = 0;
 
 static void check_schedule(int64_t nrows, int64_t nsum, int64_t b, int cus) {
   ++g_cases;
-  const KernelCrossSchedule S = kernel_cross_schedule(nrows, nsum, b, cus);
+  const KernelSchedule S = kernel_cross_schedule(nrows, nsum, b, cus);
   CHECK(S.rows_per_block == kKernelRows && (int64_t)S.nrow_blocks * kKernelRows >= nrows && (int64_t)(S.nrow_blocks - 1) * kKernelRows < nrows);
   const int64_t first = std::min<int64_t>(b, 256);
   CHECK(S.col_blocks == 1 || S.col_blocks == 2 || S.col_blocks == 4 || S.col_blocks == 8 || S.col_blocks == 16);
@@ -36,7 +36,7 @@ static void check_schedule(int64_t nrows, int64_t nsum, int64_t b, int cus) {
   for (int z = 0; z < S.nslabs; ++z) {
     CHECK(S.slab_begin[z] < S.slab_begin[z + 1] && S.slab_begin[z] % 16 == 0);
     int64_t t0, t1;
-    kernel_cross_slab_tiles(ntiles, S.tiles_per_slab, z, &t0, &t1);  // the kernel's range of slab z
+    kernel_slab_tiles<int64_t>(ntiles, S.tiles_per_slab, z, &t0, &t1);  // the kernel's range of slab z
     CHECK(t0 < t1 && std::min(nsum, t0 * 16) == S.slab_begin[z] && std::min(nsum, t1 * 16) == S.slab_begin[z + 1]);
     for (int64_t j = S.slab_begin[z]; j < S.slab_begin[z + 1]; ++j) ++owners[(size_t)j];
   }

@@ -32,8 +32,8 @@ static void check_schedule(int64_t n, int m, int cus) {
   std::vector<int> owners((size_t)n, 0);
   for (int z = 0; z < S.nslabs; ++z) {
     CHECK(S.slab_begin[z] < S.slab_begin[z + 1] && S.slab_begin[z] % 16 == 0);
-    // the kernel's range of slab z: tiles [z tiles_per_slab, (z + 1) tiles_per_slab) clipped to ntiles
-    const int64_t t0 = std::min<int64_t>(ntiles, (int64_t)z * S.tiles_per_slab), t1 = std::min<int64_t>(ntiles, t0 + S.tiles_per_slab);
+    int64_t t0, t1;
+    kernel_slab_tiles<int64_t>(ntiles, S.tiles_per_slab, z, &t0, &t1);  // the kernel's range of slab z
     CHECK(std::min(n, t0 * 16) == S.slab_begin[z] && std::min(n, t1 * 16) == S.slab_begin[z + 1]);
     // no term passes through more than 2 n + 64 additions: the lane's run, 4 over lanes, 8 over waves, the partials
     CHECK((t1 - t0) * 16 + 4 + 8 + S.nparts() <= 2 * n + 64);

@@ -1,11 +1,14 @@
 // kernelop_check.cpp — the host part of csrc/slq_kernelop.hpp: kernel_schedule() over sizes around the 16-point tile and the
 // 128-row block at every panel shape and several chip sizes, with what the kernel relies on checked on every answer (row blocks
-// and slabs are partitions, slab bounds on tile boundaries, a column-tile count the kernels are instantiated for, grids that fit
-// the launch limits); kernel_validate() on damaged arguments - the first bad value is named; kernel_column_means() against a
+// and slabs are partitions, slab bounds on tile boundaries, the kernel's own slab range from tiles_per_slab equals the schedule's, the
+// schedule equals kernel_cross_schedule(n, n, PW NP) wherever that one picks at most 16 slabs, a column-tile count the kernels are
+// instantiated for, grids that fit the launch limits); kernel_validate() on damaged arguments - the first bad value is named; kernel_column_means() against a
 // long-double sum. A stand-alone host program for the sanitizers:
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I primate_amd/csrc scripts/kernelop_check.cpp -o kernelop_check
 //   ./kernelop_check
-// It includes nothing but the header under test; no device, no library.
+// It includes nothing but the header under test (and slq_kernelcross.hpp, for the schedule the operator's must agree with); no device,
+// no library.
+#include "slq_kernelcross.hpp"
 #include "slq_kernelop.hpp"
 
 #include <cstring>
@@ -35,12 +38,26 @@ static void check_schedule(int64_t n, int PW, int NP, int cus) {
   std::vector<int> owners((size_t)n, 0);
   for (int z = 0; z < S.nslabs; ++z) {
     CHECK(S.slab_begin[z] < S.slab_begin[z + 1] && S.slab_begin[z] % 16 == 0);
-    // the kernel derives its range from gridDim.z alone: tiles [z per, (z + 1) per) of ceil(npad / 16)
+    // the kernel's range of slab z, from tiles_per_slab, is the schedule's; and the split leaves no slack: cutting the tiles evenly
+    // into nslabs gives the same tiles_per_slab
     const int64_t ntiles = kernel_npad(n) / 16, pt = (ntiles + S.nslabs - 1) / S.nslabs;
     CHECK(pt == S.tiles_per_slab && std::min(n, z * pt * 16) == S.slab_begin[z]);
+    int64_t t0, t1;
+    kernel_slab_tiles<int64_t>(ntiles, S.tiles_per_slab, z, &t0, &t1);
+    CHECK(t0 < t1 && std::min(n, t0 * 16) == S.slab_begin[z] && std::min(n, t1 * 16) == S.slab_begin[z + 1]);
+    int i0, i1;  // (as the device computes it: in int)
+    kernel_slab_tiles<int>((int)ntiles, S.tiles_per_slab, z, &i0, &i1);
+    CHECK(i0 == t0 && i1 == t1);
     for (int64_t j = S.slab_begin[z]; j < S.slab_begin[z + 1]; ++j) ++owners[(size_t)j];
   }
   for (int64_t j = 0; j < n; ++j) CHECK(owners[(size_t)j] == 1);
+  // the operator's product is the cross product of the points with themselves, wherever that one stays within the operator's slab cap
+  const KernelSchedule C = kernel_cross_schedule(n, n, ncols, cus);
+  if (C.nslabs <= kKernelMaxSlabs) {
+    CHECK(C.rows_per_block == S.rows_per_block && C.nrow_blocks == S.nrow_blocks && C.col_blocks == S.col_blocks && C.ncol_chunks == S.ncol_chunks);
+    CHECK(C.nslabs == S.nslabs && C.tiles_per_slab == S.tiles_per_slab);
+    for (int z = 0; z <= kKernelCrossMaxSlabs; ++z) CHECK(C.slab_begin[z] == S.slab_begin[z]);
+  }
 }
 
 int main() {

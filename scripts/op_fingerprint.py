@@ -2,7 +2,8 @@
 quadrature values of one seeded 256 x 30 run per operator. Two libraries that print the same lines build the same operators
 (r04: used to show that the device-side build, the stamp-based regrouping and the cached first-level Cuthill-McKee leave every result
 bitwise unchanged; later: that slq_layout.hpp does - the cases then cover the host builder, barrier tiles, a forced reorder without tiles, a
-random graph, creation from device arrays, an affine and a Gram operator).   PRIMATE_AMD_LIBSLQ=<other library> python scripts/op_fingerprint.py"""
+random graph, creation from device arrays, an affine and a Gram operator; later still: that one tile walk for the kernel-operator
+family does - the "kernel ..." lines are sha256 of products, cross products and a gradient update themselves).   PRIMATE_AMD_LIBSLQ=<other library> python scripts/op_fingerprint.py"""
 import hashlib, sys, time
 from pathlib import Path
 import numpy as np
@@ -74,3 +75,47 @@ for name, make, env, P, orth in cases:
 	info = plan.describe()
 	print(f"{name} P={P} orth={orth} tiles={info['tiles']} seq={info['sequence']} sum={float(np.sum(q)):.12e} sha={h.hexdigest()[:16]}", flush=True)
 	plan.close()
+for op, _ in ops.values():
+	op.close()
+
+## the kernel-operator family (slq_kerneltile.hpp: one tile walk under the product, the cross products and the gradient update): sha256 of
+## the operator's product (16 and 256 columns), of forward and adjoint cross products (m = 37 and 300 new points; 5 and 260 columns: the
+## second column chunk and the slab sum) and, in fp64, of one gradient update of 65 columns (two chunks), at the pairs (n, d) = (300, 3),
+## (5000, 20) - both coordinate depths; on a 256-unit chip every one of these is cut into several slabs - and (32768, 3), where 256 row
+## blocks fill the chip: the product, the adjoint cross products and the gradient update run as ONE slab that writes the result directly
+from primate_amd.operators import KernelOperator
+
+def sha(*arrays):
+	h = hashlib.sha256()
+	for x in arrays:
+		h.update(np.ascontiguousarray(x).tobytes())
+	return h.hexdigest()[:16]
+
+rng = np.random.default_rng(2024)
+for dtype, kernels in ((np.float64, ("rbf", "matern12", "matern32", "matern52")), (np.float32, ("rbf", "matern52"))):
+	tag = "f64" if dtype == np.float64 else "f32"
+	for kernel in kernels:
+		for n, d in ((300, 3), (5000, 20), (32768, 3)):
+			X = rng.standard_normal((n, d)).astype(dtype)
+			op = eng.DeviceOperator(KernelOperator(X, kernel, lengthscale=0.7 * np.sqrt(d), outputscale=1.3, noise=0.05, dtype=dtype))
+			for P in (16, 256):
+				W = rng.standard_normal((n, P)).astype(dtype)
+				Y = op.matmat(W)
+				print(f"kernel {kernel} {tag} n={n} d={d} product P={P} sum={float(np.sum(Y, dtype=np.float64)):.12e} sha={sha(Y)}", flush=True)
+			for m in (37, 300):
+				cross = eng.KernelCross(op, rng.standard_normal((m, d)).astype(dtype))
+				for b in (5, 260):
+					F, A = cross.matmat(rng.standard_normal((n, b)).astype(dtype)), cross.matmat(rng.standard_normal((m, b)).astype(dtype), trans=True)
+					print(f"kernel {kernel} {tag} n={n} d={d} cross m={m} b={b} forward sha={sha(F)} adjoint sha={sha(A)}", flush=True)
+				cross.close()
+			if dtype == np.float64:
+				Z, V = eng.DeviceMatrix(n, 65, ctx=op.ctx), eng.DeviceMatrix(n, 65, ctx=op.ctx)
+				Z.set(0, rng.standard_normal((n, 65)))
+				V.set(0, rng.standard_normal((n, 65)))
+				acc = eng.KernelGradAccumulator(op)
+				acc.update(Z, 0, V, 0, 65, alpha=1.0, beta=0.0)
+				vals, _ = acc.get()
+				print(f"kernel {kernel} {tag} n={n} d={d} gradient m=65 sum={float(np.sum(vals)):.12e} sha={sha(vals)}", flush=True)
+				for x in (acc, Z, V):
+					x.close()
+			op.close()

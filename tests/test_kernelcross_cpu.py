@@ -38,6 +38,21 @@ def test_the_build_lists_the_new_header_and_unit():
 	units = {name: (src, deps) for name, src, _, deps in g.UNITS}
 	assert g.CSRC / "slq_kernelcross.hpp" in units["slq"][1]
 	assert units["kernelcross"][0] == g.CSRC / "slq_kernelcross.hip" and g.CSRC / "slq_kernelcross.hpp" in units["kernelcross"][1]
+	assert g.CSRC / "slq_kerneltile.hpp" in units["slq"][1] and g.CSRC / "slq_kerneltile.hpp" in units["kernelcross"][1]
+
+	## every header of the kernel-operator family that a unit includes, directly or through another, is listed for that unit
+	def included(path, seen):
+		for name in re.findall(r'^#include "(slq_[a-z_]+\.hpp)"', path.read_text(), re.M):
+			if g.CSRC / name not in seen:
+				seen.add(g.CSRC / name)
+				included(g.CSRC / name, seen)
+		return seen
+
+	for name in ("slq", "kernelcross"):
+		src, deps = units[name]
+		family = {h for h in included(src, set()) if h.name.startswith("slq_kernel") and h.name != "slq_kernels.hpp"}
+		assert g.CSRC / "slq_kerneltile.hpp" in family
+		assert family <= set(deps), (name, sorted(h.name for h in family - set(deps)))
 
 
 ## ---- the condition, and an emulation inside half the bar, for every cell of the table ---------------------------------------------
