@@ -556,6 +556,46 @@ int slq_debug_kernel_cross_points(slq_kernel_cross *cross, void *zt, void *nrm);
  * index. No HIP call. */
 int slq_debug_kernel_cross_schedule(int64_t nrows, int64_t nsum, int64_t b, int num_cus, int64_t *out, int nout);
 
+/* ---- pivoted-Cholesky preconditioner of a kernel operator (csrc/slq_kernelprecond.hpp), fp64 only ----
+ * K0 = s phi(r2) is the kernel matrix without noise, A = K0 + sigma2 I (sigma2 > 0). L (n x r, r <= rank_max <= 256) is the
+ * greedy partial pivoted Cholesky factor of K0: the residual diagonal starts as d = s; step k takes p = argmax d (ties: the
+ * smallest index), L[:, k] = (K0[:, p] - L[:, :k] L[p, :k]^T) / sqrt(d_p) with r2_pp = 0 exactly, d <- max(0, d - L[:, k]^2),
+ * d_p <- 0 exactly; rows whose d_i is already 0 get L[i, k] = 0; it stops early when d_p <= max(tol, 64 eps) s, the remaining
+ * columns stay zero and rank = the columns produced. P = L L^T + sigma2 I, and with L^T L = V diag(t) V^T
+ *   P^{-1/2} = M = sigma^-1 (I - L G L^T),  G = V diag(g(t)) V^T,  g(t) = (1 - (1 + t / sigma2)^{-1/2}) / t,
+ *   logdet P = sum log1p(t_i / sigma2) + n log sigma2.
+ * The operator handed out is B = M A M, symmetric positive definite: logdet A = tr log B + logdet P, A^-1 y = M B^-1 M y, for
+ * any L. All rank_max steps are launched back to back on the context stream; the pivot search is a two-level reduction across
+ * kernel boundaries (no atomics), so identical calls give identical bits.
+ * slq_kernel_precond_create: kernel_op must be a kernel operator of ctx in fp64 with sigma2 > 0; 1 <= rank_max <= 256 (clamped
+ *   to n); tol >= 0. *out is an ordinary operator of kind "kernel_precond" whose product is B X: it works in
+ *   slq_operator_matmat and in every plan, and goes with slq_operator_destroy. It reads kernel_op at every product and does not
+ *   own it: destroy it first. L (n x rpad, row-major, rpad = rank_max rounded up to 16, zeros in unused columns), G and the
+ *   scalars sit at device addresses that never change.
+ * Staleness: after slq_kernel_set_parameters on kernel_op every product, apply and plan run on the preconditioned operator
+ *   returns SLQ_EINVAL ("stale: call slq_kernel_precond_refresh") until slq_kernel_precond_refresh has refactored in place
+ *   (same rank_max, same addresses: a captured graph sees the new factor).
+ * slq_kernel_set_parameters, slq_kernel_cross_create, slq_kernel_grad_create and slq_operator_set_parameter refuse the
+ *   preconditioned operator (SLQ_EINVAL).
+ * slq_kernel_precond_info: rank_max, the rank reached, logdet P, the residual trace sum d, the largest t (any may be NULL).
+ * slq_kernel_precond_get: pivots (rank_max, -1 beyond the rank), L (n x rank_max, column-major, ldl >= n), G (rank_max x
+ *   rank_max, row-major), the eigenvalues t (rank_max) - any may be NULL. Synchronises.
+ * slq_kernel_precond_apply: Y = P^{-1/2} X on host panels (column-major, ldx, ldy >= n; b >= 1). Synchronises.
+ * slq_kernel_precond_apply_dmat: the same on columns [i0, i0 + b) of IN and [o0, o0 + b) of OUT (overlapping ranges of one
+ *   matrix are refused), asynchronous on the context stream. The two entries give the
+ *   same bits.
+ * slq_debug_kernel_precond_addresses: the device addresses of L, G, the pivots and the residual diagonal as integers (tests). */
+int slq_kernel_precond_create(slq_context *ctx, slq_operator *kernel_op, int rank_max, double tol, slq_operator **out);
+int slq_kernel_precond_refresh(slq_operator *pre);
+int slq_kernel_precond_info(const slq_operator *pre, int *rank_max, int *rank, double *logdet_p, double *residual_trace, double *t_max);
+int slq_kernel_precond_get(slq_operator *pre, int32_t *pivots, double *L, int64_t ldl, double *G, double *eig);
+int slq_kernel_precond_apply(slq_operator *pre, const void *X, int64_t ldx, void *Y, int64_t ldy, int b);
+int slq_kernel_precond_apply_dmat(slq_operator *pre, slq_dmat *IN, int i0, slq_dmat *OUT, int o0, int b);
+int slq_debug_kernel_precond_addresses(const slq_operator *pre, uint64_t *out4);
+/* wall time of the last factorisation (create or refresh) in ms: out2[0] the launches up to the one synchronisation - the
+ * rank_max steps and the Gram matrix -, out2[1] the host part: Jacobi, G and its upload (scripts/bench_kernelprecond.py). */
+int slq_debug_kernel_precond_timing(const slq_operator *pre, double *out2);
+
 /* Per-kernel device time accumulated by HIP events on the context stream (for bench.py's
  * roofline line). enable != 0 turns event recording on for subsequent slq_plan_run calls. */
 enum {

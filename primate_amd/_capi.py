@@ -25,6 +25,7 @@ FUN_IDS = {
 PDF_IDS = {"rademacher": 0, "signs": 0, "normal": 1, "gaussian": 1, "sphere": 2}
 DENSITY_KINDS = {"gaussian": 0, "lorentzian": 1, "histogram": 2, "cdf": 3, "chebyshev": 4}
 KERNEL_PROFILES = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3}
+OP_KERNEL_PRECOND = 6  # the kind of a preconditioned kernel operator (csrc/slq_plan_shape.hpp), "kernel_precond" by name
 KERNEL_CLASSES = ["spmm_3term", "axpy_norm", "reorth_dot", "reorth_update", "finalize", "probes", "quadrature", "fun_combine"]
 
 MATVEC_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
@@ -137,6 +138,14 @@ _SIGNATURES = {
 	"slq_kernel_cross_destroy": (C.c_int, [_P]),
 	"slq_debug_kernel_cross_points": (C.c_int, [_P, _P, _P]),
 	"slq_debug_kernel_cross_schedule": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+	"slq_kernel_precond_create": (C.c_int, [_P, _P, C.c_int, C.c_double, _PP]),
+	"slq_kernel_precond_refresh": (C.c_int, [_P]),
+	"slq_kernel_precond_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+	"slq_kernel_precond_get": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P]),
+	"slq_kernel_precond_apply": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int]),
+	"slq_kernel_precond_apply_dmat": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int]),
+	"slq_debug_kernel_precond_addresses": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+	"slq_debug_kernel_precond_timing": (C.c_int, [_P, C.POINTER(C.c_double)]),
 	"slq_plan_profile_enable": (C.c_int, [_P, C.c_int]),
 	"slq_plan_action_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
 	"slq_plan_sweep_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),

@@ -111,6 +111,8 @@ def trace_fun(A_csr, fun="log", deg: int = 30, count: int = 256, seed: int = 0, 
 	A_csr: a symmetric fp64 torch sparse-CSR tensor on the GPU. method: "lanczos" (MatrixFunction: fun in log, exp, identity) or
 	"chebyshev" (ChebyshevFunction; `dfun=` for a callable). kw: batch, pdf (default "device:rademacher"), symmetric, dfun go to
 	trace_grad, everything else to the operator (orth=, t=, bounds=, damping=, ...). The same seed gives the same bits."""
+	if getattr(A_csr, "_slq_kind", None) == "kernel_precond":
+		raise ValueError("trace_fun: a preconditioned kernel operator is not differentiable here: gradients through the preconditioner are not built")
 	if getattr(A_csr, "_slq_kind", None) == "kernel":
 		raise ValueError("trace_fun differentiates the values of a sparse tensor: the hyperparameter gradients of a KernelOperator come from kernel_trace_fun")
 	if not engine._is_torch_csr(A_csr):

@@ -1110,6 +1110,7 @@ extern "C" int slq_csr_affine_create(slq_context *ctx, int dtype, int64_t n, int
 extern "C" int slq_operator_set_parameter(slq_operator *op, double t) {
   if (!op) return fail(SLQ_EINVAL, "op is NULL");
   if (op->kind == OP_KERNEL) return fail(SLQ_EINVAL, "a kernel operator has no parameter t: its hyperparameters are set by slq_kernel_set_parameters");
+  if (op->kind == OP_KERNEL_PRECOND) return fail(SLQ_EINVAL, "a preconditioned kernel operator has no parameter t: set the hyperparameters of its base operator, then call slq_kernel_precond_refresh");
   if (!op->vals_a || !op->vals_b) return fail(SLQ_EINVAL, "not an affine operator");
   HIP_TRY(hipSetDevice(op->ctx->device));
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (op->nnz + 255) / 256));
@@ -1241,6 +1242,8 @@ extern "C" int slq_kernel_create_device(slq_context *ctx, int dtype, int64_t n, 
 }
 extern "C" int slq_kernel_set_parameters(slq_operator *op, const double *lengthscales, int nls, double outputscale, double noise) {
   if (!op) return fail(SLQ_EINVAL, "op is NULL");
+  if (op->kind == OP_KERNEL_PRECOND)
+    return fail(SLQ_EINVAL, "slq_kernel_set_parameters: a preconditioned kernel operator takes its hyperparameters from its base operator: set them there, then call slq_kernel_precond_refresh");
   if (op->kind != OP_KERNEL) return fail(SLQ_EINVAL, "slq_kernel_set_parameters: not a kernel operator");
   const KernelBad bad = kernel_validate_parameters(op->k_pts.d, lengthscales, nls, outputscale, noise);
   if (bad.what != KERNEL_OK) return kernel_bad(bad);
@@ -1537,7 +1540,7 @@ static PlanFacts plan_facts_of(const slq_operator *op, int nprobes, int deg, int
   PlanFacts f;
   const TileStream &upper_stream = op->streams[0].upper;
   f.kind = op->kind, f.dtype = op->dtype, f.n = op->n, f.nnz = op->nnz, f.nnz_u = op->upper.nnz, f.upper = (bool)op->upper;
-  f.mrows = op->mrows, f.lda = op->lda;
+  f.mrows = op->kind == OP_KERNEL_PRECOND ? op->pre->rpad : op->mrows, f.lda = op->lda;
   f.has_tiles = (bool)op->tiles.tile_ptr, f.tiles_ringed = op->tiles_ringed, f.tiles_max_cols = op->tiles.max_cols;
   f.upper_per_row = op->upper_per_row, f.upper_stream = (bool)upper_stream, f.upper_padded = upper_stream.padded;
   f.far_per_row = op->far_per_row, f.affine = (bool)op->vals_b;
@@ -2278,10 +2281,17 @@ static int launch_dense_mfma(slq_plan *p, const void *Wc, const void *Wp, void *
   return SLQ_OK;
 }
 
+// A preconditioned kernel operator whose base has new hyperparameters is stale until slq_kernel_precond_refresh: its factor, G and
+// logdet P belong to the old ones. Every product, apply and plan run asks here first (a captured graph is not replayed either).
+static int precond_check_fresh(const slq_operator *op, const char *who) {
+  if (op->kind != OP_KERNEL_PRECOND || op->pre->epoch == op->pre->base->k_epoch) return SLQ_OK;
+  return fail(SLQ_EINVAL, "%s: the preconditioner is stale: call slq_kernel_precond_refresh (the base operator's hyperparameters have changed)", who);
+}
+
 // kernel operator: T = A W_c by k_kernel_panel (slq_kernelop.hpp). One slab: straight into T; a j split (small n): slab z into
 // T + (1 + z) slots, summed in slab order into T by k_3term_slabs (plain) - the slabs the plan's shape allocated (dense_ks)
-static int launch_kernel_product(slq_plan *p, const void *Wc) {
-  const slq_operator *op = p->op;
+// op: the operator whose points are read (the plan's own, or the base of a preconditioned one)
+static int launch_kernel_product(slq_plan *p, const slq_operator *op, const void *Wc) {
   hipStream_t st = p->ctx->stream;
   const KernelSchedule S = kernel_schedule(p->n, p->PW, p->NP, p->ctx->num_cus);
   if ((S.nslabs > 1 ? S.nslabs : 0) != p->dense_ks) return fail(SLQ_EINVAL, "kernel operator: the plan holds %d slabs, the schedule asks for %d", p->dense_ks, S.nslabs);
@@ -2306,7 +2316,29 @@ static int apply_operator_unfused(slq_plan *p, int slot_c) {
   hipStream_t st = p->ctx->stream;
   slq_operator *op = p->op;
   if (op->kind == OP_KERNEL) {
-    PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_kernel_product(p, slot_ptr(p, slot_c))));
+    PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_kernel_product(p, op, slot_ptr(p, slot_c))));
+    return SLQ_OK;
+  }
+  if (op->kind == OP_KERNEL_PRECOND) {
+    // T = M A M W_c: V = M W_c, T = A V by the base's product, T = M T in place (slq_kernelprecond.hpp). V, the slab partials
+    // and G L^T W are the plan's own scratch (WS_T2): a captured graph holds their addresses.
+    SLQ_TRY(precond_check_fresh(op, "plan"));
+    const KernelPrecond &pc = *op->pre;
+    double *V = (double *)p->T2, *scratch = V + p->slot_stride;
+    const int cols = p->NP * p->PW;
+    const PrecondPanelLayout lay{p->n, p->PW};
+    const auto apply = [&](const double *X, double *Y) {
+      return precond_apply_launch(p->n, pc.L.as<const double>(), pc.rpad, pc.G.as<const double>(), (const double *)pc.base->k_pts.params, X, Y, cols, lay, scratch,
+                                  p->ctx->num_cus, st);
+    };
+    PROFILED(p, SLQ_K_SPMM, {
+      if (!apply((const double *)slot_ptr(p, slot_c), V)) return fail(SLQ_EINVAL, "preconditioned kernel operator: no apply kernel for rank %d", pc.rpad);
+    });
+    PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_kernel_product(p, pc.base, V)));
+    PROFILED(p, SLQ_K_SPMM, {
+      if (!apply((const double *)p->T, (double *)p->T)) return fail(SLQ_EINVAL, "preconditioned kernel operator: no apply kernel for rank %d", pc.rpad);
+    });
+    HIP_TRY(hipGetLastError());
     return SLQ_OK;
   }
   if (dense_kernel_of(p) >= DENSE_K_3TERM) {
@@ -2878,6 +2910,7 @@ static int launch_cheb_accumulate(slq_plan *p, int t0, int nc, const double *coe
 // launches of seq::cheb_action_piece_after go between the steps.
 static int cheb_run(slq_plan *p, const char *who, double center, double halfwidth, double outside_tol, const double *action_coef) {
   if (!p->probes_ready) return fail(SLQ_EINVAL, "%s: set or generate probes first", who);
+  SLQ_TRY(precond_check_fresh(p->op, who));
   if (!std::isfinite(center) || !std::isfinite(halfwidth) || !(halfwidth > 0.0))
     return fail(SLQ_EINVAL, "%s: center = %g, halfwidth = %g (finite, halfwidth > 0)", who, center, halfwidth);
   HIP_TRY(hipSetDevice(p->ctx->device));
@@ -3069,6 +3102,7 @@ extern "C" int slq_plan_steps_done(const slq_plan *p, int *cur) {
 constexpr size_t kGraphCacheMax = 16;
 
 static int run_range(slq_plan *p, double rtol, int j0, int j1) {
+  SLQ_TRY(precond_check_fresh(p->op, "slq_plan_run"));
   HIP_TRY(hipSetDevice(p->ctx->device));
   hipStream_t st = p->ctx->stream;
   // The launch sequence of a run (7 launches per Lanczos step, ~210 for k = 30) depends only on
@@ -3358,6 +3392,7 @@ static int enqueue_replay(slq_plan *p, double rtol) {
 // Afterwards alpha, nu, steps hold the bits of pass 1 again and the output panel holds sum_t g_t W_t.
 static int replay_action(slq_plan *p) {
   if (!p->stash_ready) return fail(SLQ_EINVAL, "internal: a recompute plan without stashed probes");
+  SLQ_TRY(precond_check_fresh(p->op, "slq_plan_fun_action"));
   hipStream_t st = p->ctx->stream;
   const double rtol = p->run_rtol;
   HIP_TRY(hipMemcpyAsync(slot_ptr(p, 0), slot_ptr(p, p->v_slot), (size_t)p->slot_stride * p->esz, hipMemcpyDeviceToDevice, st));
@@ -4092,6 +4127,7 @@ static const char *op_kind_name(int kind) {
     case OP_DEVICE_CALLBACK: return "device_callback";
     case OP_GRAM: return "gram";
     case OP_KERNEL: return "kernel";
+    case OP_KERNEL_PRECOND: return "kernel_precond";
     default: return "?";
   }
 }
@@ -4341,6 +4377,206 @@ extern "C" int slq_debug_kernel_cross_schedule(int64_t nrows, int64_t nsum, int6
     return fail(SLQ_EINVAL, "slq_debug_kernel_cross_schedule: 0 < nrows, nsum, b < 2^31 - 16 and num_cus positive");
   const KernelSchedule S = kernel_cross_schedule(nrows, nsum, b, num_cus);
   kernel_schedule_words({S.rows_per_block, S.nrow_blocks, S.col_blocks, S.ncol_chunks, S.nslabs, S.tiles_per_slab}, S.nslabs, S.slab_begin, kKernelCrossMaxSlabs, out);
+  return SLQ_OK;
+}
+
+// ---- pivoted-Cholesky preconditioner of a kernel operator (kernels and host analysis in slq_kernelprecond.hpp) ----
+static int precond_handle(const slq_operator *op, const char *who) {
+  if (!op) return fail(SLQ_EINVAL, "%s: the operator is NULL", who);
+  if (op->kind != OP_KERNEL_PRECOND || !op->pre)
+    return fail(SLQ_EINVAL, "%s: the operator is of kind '%s', not a preconditioned kernel operator (slq_kernel_precond_create)", who, op_kind_name(op->kind));
+  return SLQ_OK;
+}
+static int precond_grow(DevBuf &b, size_t need, const char *who) {
+  if (b.bytes() >= need) return SLQ_OK;
+  const hipError_t e = b.alloc(need);
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "%s: scratch of %zu bytes: %s", who, need, hipGetErrorString(e));
+  return SLQ_OK;
+}
+
+// The factor of the base's K0 as its hyperparameters are now, in place: rank_max steps back to back on the stream, the Gram
+// matrix L^T L by the apply's own kernel with L as the panel, then - after the one synchronisation - Jacobi, G and logdet P
+// on the host, and G uploaded to its fixed address.
+static int precond_factorise(slq_operator *op) {
+  KernelPrecond &pc = *op->pre;
+  const slq_operator *base = pc.base;
+  if (!(base->k_noise > 0.0)) return fail(SLQ_EINVAL, "kernel preconditioner: the base operator's noise sigma2 is 0: P^{-1/2} needs sigma2 > 0");
+  hipStream_t st = op->ctx->stream;
+  const int n = (int)op->n, r = pc.rank_max, rpad = pc.rpad, cus = op->ctx->num_cus;
+  HIP_TRY(hipStreamSynchronize(st));  // (what ran before is not this factorisation's time)
+  const auto t0 = std::chrono::steady_clock::now();
+  HIP_TRY(hipMemsetAsync(pc.L.p, 0, (size_t)n * rpad * 8, st));
+  const double thresh = std::max(pc.tol, 64.0 * std::numeric_limits<double>::epsilon());
+  if (!precond_factor_launch(base->k_profile, n, (int)base->k_pts.npad, base->k_pts.d, (const double *)base->k_pts.zt, (const double *)base->k_pts.nrm,
+                             (const double *)base->k_pts.params, pc.L.as<double>(), rpad, r, thresh, pc.dres.as<double>(), pc.pivots, pc.rank_d, pc.dpiv, pc.pv, pc.pi, st))
+    return fail(SLQ_EINVAL, "kernel preconditioner: no factor kernel for profile %d", base->k_profile);
+  HIP_TRY(hipGetLastError());
+  SLQ_TRY(precond_grow(pc.scratch, precond_scratch_words(n, rpad, rpad, cus) * 8, "kernel preconditioner"));
+  const PrecondSlabs S = precond_apply_slabs(n, rpad, cus);
+  const size_t bpad = (size_t)precond_bpad(rpad);
+  double *gram_d = pc.scratch.as<double>() + (size_t)S.nslabs * bpad * rpad;
+  if (!precond_lt_launch(n, pc.L.as<const double>(), rpad, (const double *)nullptr, pc.L.as<const double>(), rpad, PrecondPanelLayout{n, rpad}, pc.scratch.as<double>(), gram_d,
+                         cus, st))
+    return fail(SLQ_EINVAL, "kernel preconditioner: no Gram kernel for rank %d", rpad);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> gram((size_t)rpad * rpad), dres((size_t)n), A((size_t)r * r), V((size_t)r * r), t((size_t)r), G((size_t)rpad * rpad);
+  HIP_TRY(hipMemcpyAsync(gram.data(), gram_d, gram.size() * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(dres.data(), pc.dres.p, dres.size() * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&pc.rank, pc.rank_d, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const auto t1 = std::chrono::steady_clock::now();
+  for (int i = 0; i < r; ++i)
+    for (int j = i; j < r; ++j) A[(size_t)i * r + j] = A[(size_t)j * r + i] = gram[(size_t)i * rpad + j];  // (gram[g][m]: column g of the product, symmetric)
+  if (precond_jacobi(r, A.data(), V.data(), t.data()) >= kPrecondJacobiSweeps) return fail(SLQ_ENOTCONV, "kernel preconditioner: Jacobi did not converge on the %d x %d Gram matrix", r, r);
+  const PrecondSpectrum sp = precond_finish(n, r, rpad, V.data(), t.data(), base->k_noise, G.data());
+  HIP_TRY(hipMemcpyAsync(pc.G.p, G.data(), G.size() * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const auto t2 = std::chrono::steady_clock::now();
+  pc.device_ms = std::chrono::duration<double, std::milli>(t1 - t0).count(), pc.host_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+  pc.logdet_p = sp.logdet_p, pc.t_max = sp.t_max;
+  pc.residual_trace = 0.0;
+  for (double v : dres) pc.residual_trace += v;
+  pc.eig = t;
+  pc.epoch = base->k_epoch;
+  return SLQ_OK;
+}
+
+static int kernel_precond_create_body(slq_context *ctx, slq_operator *base, int rank_max, double tol, slq_operator **out) {
+  if (!ctx || !base || !out) return fail(SLQ_EINVAL, "slq_kernel_precond_create: ctx/kernel_op/out is NULL");
+  *out = nullptr;
+  if (base->kind != OP_KERNEL)
+    return fail(SLQ_EINVAL, "slq_kernel_precond_create: the base operator is of kind '%s', not a kernel operator (slq_kernel_create)", op_kind_name(base->kind));
+  if (base->dtype != SLQ_F64) return fail(SLQ_EINVAL, "slq_kernel_precond_create: the base operator's dtype is fp32: the preconditioner is fp64 only");
+  if (base->ctx != ctx) return fail(SLQ_EINVAL, "slq_kernel_precond_create: the base operator belongs to another context");
+  if (!(base->k_noise > 0.0)) return fail(SLQ_EINVAL, "slq_kernel_precond_create: the base operator's noise sigma2 is 0: P^{-1/2} needs sigma2 > 0");
+  if (rank_max < 1 || rank_max > kPrecondMaxRank) return fail(SLQ_EINVAL, "slq_kernel_precond_create: rank_max = %d (1 <= rank_max <= %d)", rank_max, kPrecondMaxRank);
+  if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(SLQ_EINVAL, "slq_kernel_precond_create: tol = %g (finite, >= 0)", tol);
+  rank_max = (int)std::min<int64_t>(rank_max, base->n);
+  slq_operator *op = nullptr;
+  SLQ_TRY(operator_new(ctx, OP_KERNEL_PRECOND, SLQ_F64, base->n, base->n * rank_max, out, &op));
+  OpGuard guard{op};
+  op->pre.reset(new KernelPrecond());
+  KernelPrecond &pc = *op->pre;
+  pc.base = base, pc.rank_max = rank_max, pc.rpad = precond_rpad(rank_max), pc.tol = tol;
+  const size_t n = (size_t)base->n, nparts = (size_t)precond_factor_parts(base->n);
+  const size_t head_ints = ((size_t)rank_max + 1 + 1) / 2 * 2;  // pivots | rank, padded to whole doubles
+  hipError_t e = pc.L.alloc(n * pc.rpad * 8);
+  if (e == hipSuccess) e = pc.G.alloc((size_t)pc.rpad * pc.rpad * 8);
+  if (e == hipSuccess) e = pc.dres.alloc(n * 8);
+  if (e == hipSuccess) e = pc.words.alloc(head_ints * 4 + ((size_t)rank_max + 2 * nparts) * 8 + 2 * nparts * 4);
+  if (e == hipSuccess) e = hipMemsetAsync(pc.G.p, 0, (size_t)pc.rpad * pc.rpad * 8, ctx->stream);
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "slq_kernel_precond_create: %s", hipGetErrorString(e));
+  pc.pivots = pc.words.as<int>(), pc.rank_d = pc.pivots + rank_max;
+  pc.dpiv = (double *)(pc.pivots + head_ints), pc.pv = pc.dpiv + rank_max;
+  pc.pi = (int *)(pc.pv + 2 * nparts);
+  SLQ_TRY(precond_factorise(op));
+  *out = guard.release();
+  return SLQ_OK;
+}
+extern "C" int slq_kernel_precond_create(slq_context *ctx, slq_operator *kernel_op, int rank_max, double tol, slq_operator **out) {
+  return create_guarded(out, [&]() { return kernel_precond_create_body(ctx, kernel_op, rank_max, tol, out); });
+}
+
+extern "C" int slq_kernel_precond_refresh(slq_operator *op) {
+  SLQ_TRY(precond_handle(op, "slq_kernel_precond_refresh"));
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  return create_guarded(nullptr, [&]() { return precond_factorise(op); });
+}
+
+extern "C" int slq_kernel_precond_info(const slq_operator *op, int *rank_max, int *rank, double *logdet_p, double *residual_trace, double *t_max) {
+  SLQ_TRY(precond_handle(op, "slq_kernel_precond_info"));
+  const KernelPrecond &pc = *op->pre;
+  if (rank_max) *rank_max = pc.rank_max;
+  if (rank) *rank = pc.rank;
+  if (logdet_p) *logdet_p = pc.logdet_p;
+  if (residual_trace) *residual_trace = pc.residual_trace;
+  if (t_max) *t_max = pc.t_max;
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_precond_get(slq_operator *op, int32_t *pivots, double *L, int64_t ldl, double *G, double *eig) {
+  SLQ_TRY(precond_handle(op, "slq_kernel_precond_get"));
+  const KernelPrecond &pc = *op->pre;
+  if (L && ldl < op->n) return fail(SLQ_EINVAL, "slq_kernel_precond_get: ldl = %lld is below n = %lld", (long long)ldl, (long long)op->n);
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  HIP_TRY(hipStreamSynchronize(op->ctx->stream));
+  return create_guarded(nullptr, [&]() {
+    const size_t n = (size_t)op->n, r = (size_t)pc.rank_max, rpad = (size_t)pc.rpad;
+    if (pivots) HIP_TRY(hipMemcpy(pivots, pc.pivots, r * 4, hipMemcpyDeviceToHost));
+    if (L) {
+      std::vector<double> rows(n * rpad);
+      HIP_TRY(hipMemcpy(rows.data(), pc.L.p, rows.size() * 8, hipMemcpyDeviceToHost));
+      for (size_t k = 0; k < r; ++k)
+        for (size_t i = 0; i < n; ++i) L[k * (size_t)ldl + i] = rows[i * rpad + k];
+    }
+    if (G) {
+      std::vector<double> g(rpad * rpad);
+      HIP_TRY(hipMemcpy(g.data(), pc.G.p, g.size() * 8, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < r; ++i) std::copy(g.begin() + i * rpad, g.begin() + i * rpad + r, G + i * r);
+    }
+    if (eig) std::copy(pc.eig.begin(), pc.eig.end(), eig);
+    return (int)SLQ_OK;
+  });
+}
+
+// Y = M X on device columns n apart, on the stream (the caller has checked the shapes)
+static int precond_apply_device(slq_operator *op, const double *X, double *Y, int b, const char *who) {
+  SLQ_TRY(precond_check_fresh(op, who));
+  KernelPrecond &pc = *op->pre;
+  const int cus = op->ctx->num_cus;
+  SLQ_TRY(precond_grow(pc.scratch, precond_scratch_words(op->n, b, pc.rpad, cus) * 8, who));
+  if (!precond_apply_launch((int)op->n, pc.L.as<const double>(), pc.rpad, pc.G.as<const double>(), (const double *)pc.base->k_pts.params, X, Y, b,
+                            PrecondColumnLayout{op->n}, pc.scratch.as<double>(), cus, op->ctx->stream))
+    return fail(SLQ_EINVAL, "%s: no apply kernel for rank %d", who, pc.rpad);
+  HIP_TRY(hipGetLastError());
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_precond_apply(slq_operator *op, const void *X, int64_t ldx, void *Y, int64_t ldy, int b) {
+  SLQ_TRY(precond_handle(op, "slq_kernel_precond_apply"));
+  if (!X || !Y) return fail(SLQ_EINVAL, "slq_kernel_precond_apply: X/Y is NULL");
+  if (b < 1) return fail(SLQ_EINVAL, "slq_kernel_precond_apply: b = %d columns (b >= 1)", b);
+  if (ldx < op->n || ldy < op->n) return fail(SLQ_EINVAL, "slq_kernel_precond_apply: ldx = %lld, ldy = %lld must reach n = %lld", (long long)ldx, (long long)ldy, (long long)op->n);
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  KernelPrecond &pc = *op->pre;
+  const size_t colb = (size_t)op->n * 8;
+  SLQ_TRY(precond_grow(pc.stage_in, colb * b, "slq_kernel_precond_apply"));
+  SLQ_TRY(precond_grow(pc.stage_out, colb * b, "slq_kernel_precond_apply"));
+  hipStream_t st = op->ctx->stream;
+  HIP_TRY(hipMemcpy2DAsync(pc.stage_in.p, colb, X, (size_t)ldx * 8, colb, (size_t)b, hipMemcpyHostToDevice, st));
+  SLQ_TRY(precond_apply_device(op, pc.stage_in.as<const double>(), pc.stage_out.as<double>(), b, "slq_kernel_precond_apply"));
+  HIP_TRY(hipMemcpy2DAsync(Y, (size_t)ldy * 8, pc.stage_out.p, colb, colb, (size_t)b, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_precond_apply_dmat(slq_operator *op, slq_dmat *IN, int i0, slq_dmat *OUT, int o0, int b) {
+  SLQ_TRY(precond_handle(op, "slq_kernel_precond_apply_dmat"));
+  if (b < 1) return fail(SLQ_EINVAL, "slq_kernel_precond_apply_dmat: b = %d columns (b >= 1)", b);
+  SLQ_TRY(dmat_range(IN, i0, b, "slq_kernel_precond_apply_dmat(IN)"));
+  SLQ_TRY(dmat_range(OUT, o0, b, "slq_kernel_precond_apply_dmat(OUT)"));
+  if (IN->n != op->n || OUT->n != op->n)
+    return fail(SLQ_EINVAL, "slq_kernel_precond_apply_dmat: the operator has %lld rows, IN %lld, OUT %lld", (long long)op->n, (long long)IN->n, (long long)OUT->n);
+  if (IN->ctx != op->ctx || OUT->ctx != op->ctx) return fail(SLQ_EINVAL, "slq_kernel_precond_apply_dmat: a matrix belongs to another context");
+  if (IN == OUT && i0 < o0 + b && o0 < i0 + b)
+    return fail(SLQ_EINVAL, "slq_kernel_precond_apply_dmat: the columns [%d, %d) of IN and [%d, %d) of OUT overlap in one matrix", i0, i0 + b, o0, o0 + b);
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  return precond_apply_device(op, IN->d + (size_t)i0 * IN->n, OUT->d + (size_t)o0 * OUT->n, b, "slq_kernel_precond_apply_dmat");
+}
+
+// the device addresses of L, G, the pivots and the residual diagonal (tests: a refresh keeps them)
+extern "C" int slq_debug_kernel_precond_addresses(const slq_operator *op, uint64_t *out4) {
+  SLQ_TRY(precond_handle(op, "slq_debug_kernel_precond_addresses"));
+  if (!out4) return fail(SLQ_EINVAL, "slq_debug_kernel_precond_addresses: out is NULL");
+  const KernelPrecond &pc = *op->pre;
+  out4[0] = (uint64_t)(uintptr_t)pc.L.p, out4[1] = (uint64_t)(uintptr_t)pc.G.p, out4[2] = (uint64_t)(uintptr_t)pc.pivots, out4[3] = (uint64_t)(uintptr_t)pc.dres.p;
+  return SLQ_OK;
+}
+// wall time of the last factorisation in ms: {the launches up to the synchronisation, the host part: Jacobi, G and its upload}
+extern "C" int slq_debug_kernel_precond_timing(const slq_operator *op, double *out2) {
+  SLQ_TRY(precond_handle(op, "slq_debug_kernel_precond_timing"));
+  if (!out2) return fail(SLQ_EINVAL, "slq_debug_kernel_precond_timing: out is NULL");
+  out2[0] = op->pre->device_ms, out2[1] = op->pre->host_ms;
   return SLQ_OK;
 }
 

@@ -14,12 +14,15 @@
 
 #include "slq_format.hpp"
 #include "slq_kernelop.hpp"
+#include "slq_kernelprecond.hpp"
 #include "slq_sequence.hpp"
 #include "slq_switches.hpp"
 
 namespace slq {
 
-enum { OP_CSR = 0, OP_DENSE = 1, OP_CALLBACK = 2, OP_DEVICE_CALLBACK = 3, OP_GRAM = 4, OP_KERNEL = 5 };
+enum { OP_CSR = 0, OP_DENSE = 1, OP_CALLBACK = 2, OP_DEVICE_CALLBACK = 3, OP_GRAM = 4, OP_KERNEL = 5, OP_KERNEL_PRECOND = 6 };
+// (a preconditioned kernel operator - slq_kernelprecond.hpp - is a kernel operator between two applies of M = P^{-1/2})
+inline bool is_kernel_kind(int kind) { return kind == OP_KERNEL || kind == OP_KERNEL_PRECOND; }
 constexpr int kF32 = 0, kF64 = 1;  // == SLQ_F32, SLQ_F64 (include/slq.h; slq.hip asserts the equality)
 
 // Ring: the window of the last orth vectors. KeepBasis: every vector. Recompute: the ring widened for the accumulation launches
@@ -36,7 +39,7 @@ struct PlanFacts {
   int kind = OP_CSR, dtype = kF64;
   int64_t n = 0, nnz = 0, nnz_u = 0;
   int upper = 0;            // exactly symmetric CSR: it has the upper-triangle copy (slq_operator::upper)
-  int64_t mrows = 0, lda = 0;
+  int64_t mrows = 0, lda = 0;  // (OP_KERNEL_PRECOND: mrows is the factor's padded rank)
   int has_tiles = 0;        // workgroup tiles (tiles.tile_ptr)
   int tiles_ringed = 0;     // ... built to the caps of the ring-fed kernels
   int tiles_max_cols = 0;   // longest line list of a tile
@@ -357,11 +360,11 @@ inline PlanShape plan_shape(const PlanFacts &f, const PlanSwitches &sw) {
     }
   }
   // kernel operator (slq_kernelop.hpp): the j slabs of its product take the same place behind T (dense_ks slabs; 0: one slab, straight into T)
-  if (f.kind == OP_KERNEL) {
+  if (is_kernel_kind(f.kind)) {
     const int slabs = kernel_schedule(f.n, s.PW, s.NP, f.num_cus).nslabs;
     s.dense_ks = slabs > 1 ? slabs : 0;
   }
-  s.t_slabs_bound = f.kind == OP_CSR ? 0 : 1 + (((f.kind == OP_DENSE && (f.dtype == kF32 || s.PW >= 32)) || f.kind == OP_KERNEL) ? 16 : 0);
+  s.t_slabs_bound = f.kind == OP_CSR ? 0 : 1 + (((f.kind == OP_DENSE && (f.dtype == kF32 || s.PW >= 32)) || is_kernel_kind(f.kind)) ? 16 : 0);
   // the one decision behind launch_dense_mfma, apply_operator_unfused and the step loop
   if (f.kind != OP_DENSE) s.dense_class = DENSE_K_NONE;
   else if (!sw.dense_mfma || (f.dtype != kF64 && s.dense_ks <= 0)) s.dense_class = DENSE_K_PANEL;  // the VALU kernel (SLQ_DENSE_MFMA=0)
@@ -436,7 +439,10 @@ inline PlanShape plan_shape(const PlanFacts &f, const PlanSwitches &sw) {
   region(WS_CHEB_OUT, cheb ? bp * sizeof(int) : 0, 1, 0);
   region(WS_CHEB_COEF, cheb ? (nmom + 4) * 8 : 0, 0, 0);
   region(WS_T, f.kind == OP_CSR ? 0 : (size_t)(1 + s.dense_ks) * slot_bytes, 0, 1);
-  region(WS_T2, f.kind == OP_GRAM ? (size_t)s.NP * (size_t)f.mrows * s.PW * esz : 0, 0, 1);
+  // (preconditioned kernel operator: V = M W_c, then the slab partials and G L^T W of an apply - scratch of the PLAN, whose captured graphs hold its addresses)
+  region(WS_T2, f.kind == OP_GRAM             ? (size_t)s.NP * (size_t)f.mrows * s.PW * esz
+                : f.kind == OP_KERNEL_PRECOND ? slot_bytes + precond_scratch_words(f.n, s.bpad, (int)f.mrows, f.num_cus) * 8
+                                              : 0, 0, 1);
   return s;
 }
 

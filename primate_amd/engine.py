@@ -195,6 +195,20 @@ class DeviceOperator:
 			import weakref
 
 			A._device_ops.append(weakref.ref(self))
+		elif getattr(A, "_slq_kind", None) == "kernel_precond":
+			## B = M A M, M = P^{-1/2} of a pivoted-Cholesky factor (primate_amd.operators.PreconditionedKernelOperator):
+			## slq_kernel_precond_create over the base's device operator, which this object keeps alive
+			if self.dtype != np.float64:
+				raise ValueError("a preconditioned kernel operator is fp64 only")
+			from .lanczos import _as_device_operator
+
+			self.base = _as_device_operator(A.base, dtype=np.float64)
+			if self.base.ctx is not self.ctx:
+				raise ValueError("the base operator's device operator lives in another context")
+			check(L.slq_kernel_precond_create(self.ctx._h, self.base._h, int(A.rank_max), float(A.tol), C.byref(h)))
+			self.kind, self.nnz = "kernel_precond", int(self.shape[0] * min(int(A.rank_max), self.shape[0]))
+			self._host_params = A.base
+			self._fresh_for = self._param_key()
 		elif hasattr(A, "matmat_device"):
 			## GPU-resident plugin: A.matmat_device(X, Y, stream) receives two objects with
 			## `__cuda_array_interface__` (shape (ncols, n), C order = column-major n x ncols) and a stream handle
@@ -255,6 +269,70 @@ class DeviceOperator:
 		check(L.slq_kernel_get_parameters(self._h, None, None, ptr(ls), d.value, None, None))
 		name = {v_: k for k, v_ in _capi.KERNEL_PROFILES.items()}[prof.value]
 		return dict(d=d.value, kernel=name, lengthscale=ls, outputscale=s.value, noise=v.value)
+
+	## ---- a preconditioned kernel operator (kind "kernel_precond"; slq_kernel_precond_*) ----
+	def _need_precond(self, what: str) -> None:
+		if self.kind != "kernel_precond":
+			raise ValueError(f"{what} needs a preconditioned kernel operator, not kind '{self.kind}'")
+
+	def refresh(self) -> None:
+		"""Refactor in place for the base's hyperparameters of now (slq_kernel_precond_refresh): same rank_max, same addresses."""
+		self._need_precond("refresh")
+		check(_capi.lib().slq_kernel_precond_refresh(self._h))
+		self._fresh_for = self._param_key()
+
+	def _param_key(self):
+		K = self._host_params
+		return (tuple(np.atleast_1d(K.lengthscale).tolist()), float(K.outputscale), float(K.noise))
+
+	def refresh_if_stale(self) -> None:
+		"""The lazy refresh: refactor when the base's parameters have changed since the factor was built."""
+		self._need_precond("refresh_if_stale")
+		if self._fresh_for != self._param_key():
+			self.refresh()
+
+	def info(self) -> dict:
+		"""{rank_max, rank, logdet_p, residual_trace, t_max} of the factor (slq_kernel_precond_info)."""
+		self._need_precond("info")
+		rm, r, ld, rt, tm = C.c_int(), C.c_int(), C.c_double(), C.c_double(), C.c_double()
+		check(_capi.lib().slq_kernel_precond_info(self._h, C.byref(rm), C.byref(r), C.byref(ld), C.byref(rt), C.byref(tm)))
+		return dict(rank_max=rm.value, rank=r.value, logdet_p=ld.value, residual_trace=rt.value, t_max=tm.value)
+
+	def factor(self) -> dict:
+		"""{pivots, L, G, eig} as the device holds them (slq_kernel_precond_get): pivots (rank_max, -1 beyond the rank), L (n x
+		rank_max), G (rank_max x rank_max), the eigenvalues of L^T L."""
+		self._need_precond("factor")
+		r, n = self.info()["rank_max"], self.shape[0]
+		piv, Lf, G, eig = np.empty(r, dtype=np.int32), np.empty((n, r), order="F"), np.empty((r, r)), np.empty(r)
+		check(_capi.lib().slq_kernel_precond_get(self._h, ptr(piv), ptr(Lf), n, ptr(G), ptr(eig)))
+		return dict(pivots=piv, L=Lf, G=G, eig=eig)
+
+	def inv_sqrt(self, X: np.ndarray) -> np.ndarray:
+		"""P^{-1/2} X for a host array (slq_kernel_precond_apply)."""
+		self._need_precond("inv_sqrt")
+		X = np.asfortranarray(np.asarray(X, dtype=np.float64).reshape(self.shape[0], -1))
+		Y = np.empty_like(X, order="F")
+		check(_capi.lib().slq_kernel_precond_apply(self._h, ptr(X), X.shape[0], ptr(Y), Y.shape[0], X.shape[1]))
+		return Y
+
+	def inv_sqrt_dmat(self, IN: "DeviceMatrix", i0: int, OUT: "DeviceMatrix", o0: int, b: int) -> None:
+		"""OUT[:, o0:o0+b] = P^{-1/2} IN[:, i0:i0+b] between DeviceMatrix columns, asynchronous on the context stream."""
+		self._need_precond("inv_sqrt_dmat")
+		check(_capi.lib().slq_kernel_precond_apply_dmat(self._h, IN._h, int(i0), OUT._h, int(o0), int(b)))
+
+	def factor_timing(self) -> dict:
+		"""Wall time of the last factorisation in ms: device_ms (the launches up to the synchronisation), host_ms (Jacobi, G, its upload)."""
+		self._need_precond("factor_timing")
+		out = (C.c_double * 2)()
+		check(_capi.lib().slq_debug_kernel_precond_timing(self._h, out))
+		return dict(device_ms=float(out[0]), host_ms=float(out[1]))
+
+	def precond_addresses(self) -> tuple:
+		"""The device addresses of L, G, the pivots and the residual diagonal (slq_debug_kernel_precond_addresses)."""
+		self._need_precond("precond_addresses")
+		out = (C.c_uint64 * 4)()
+		check(_capi.lib().slq_debug_kernel_precond_addresses(self._h, out))
+		return tuple(int(v) for v in out)
 
 	def matmat(self, X: np.ndarray) -> np.ndarray:
 		X = np.asfortranarray(X.reshape(self.shape[1], -1), dtype=self.dtype)

@@ -1,9 +1,16 @@
-"""Gaussian-process prediction on the matrix-free kernel operator.
+"""Gaussian-process prediction and log-determinants on the matrix-free kernel operator.
 
 With A = K + noise I the operator of a `KernelOperator` on the training points X, C = outputscale * phi(r2(X*, X)) the
 cross-covariance to new points X* (`KernelOperator.cross`, engine.KernelCross) and s the outputscale,
 
     mean = C A^-1 y,        var_i = s - (C A^-1 C^T)_ii.
+
+With a pivoted-Cholesky preconditioner (`KernelOperator.preconditioned`, §4.18) M = P^{-1/2} and B = M A M,
+
+    logdet A = tr log B + logdet P,        A^-1 y = M B^-1 M y,
+
+which is what `logdet` computes and what `posterior(precond_rank > 0)` solves with: the path for small noise, where Lanczos on A
+itself does not converge in any affordable number of steps.
 
 Neither A nor C is ever formed: A^-1 is the Lanczos action `fun_action_into(..., "inv")` of a kept-basis plan over the device
 operator, C and C^T are the cross-covariance products, and the contraction C A^-1 C^T of a batch is `DeviceMatrix.tn`.
@@ -34,8 +41,38 @@ def _finite(a: np.ndarray, what: str, rtol: float) -> None:
 		raise FloatingPointError(f"posterior: {what} is not finite" + (f" (rtol = {rtol} > 0 lets probes stop early, which the 'inv' action does not survive: use rtol = 0)" if rtol > 0 else ""))
 
 
+def logdet(K, rank: int = 100, deg: int = 20, count: int = 64, batch: int = 64, pdf: str = "device:rademacher", seed=None) -> tuple:
+	"""(estimate, info): log det A of the KernelOperator `K` (A = K0 + noise I, float64) by stochastic Lanczos quadrature on the
+	preconditioned operator: `hutch` over `MatrixFunction(K.preconditioned(rank), "log", deg)` with `count` probes in equal batches
+	of at most `batch` (whole batches are drawn: `count` is rounded up to ceil(count / batch) of them, info says how many), plus logdet P of the factor (exact, from its r x r Gram matrix). rank = 0: the plain estimate on A itself.
+	info: rank (the factor's; 0 for the plain estimate), logdet_precond, trace (the stochastic part), std_error (of the estimate:
+	the sample standard deviation of the per-probe values over sqrt(count)), count, deg."""
+	from .operators import MatrixFunction
+	from .trace import hutch
+
+	if getattr(K, "_slq_kind", None) != "kernel":
+		raise ValueError("logdet needs a KernelOperator")
+	if np.dtype(K.dtype) != np.float64:
+		raise ValueError(f"logdet is fp64 only: the KernelOperator is {np.dtype(K.dtype)}")
+	rank, deg, count, batch = int(rank), int(deg), int(count), int(batch)
+	if rank < 0 or deg < 1 or count < 2 or batch < 1:
+		raise ValueError(f"rank = {rank} must be >= 0, deg = {deg} and batch = {batch} >= 1, count = {count} >= 2")
+	B = K.preconditioned(rank) if rank > 0 else K
+	M = MatrixFunction(B, fun="log", deg=deg, dtype=np.float64)
+	pinfo = dict(rank=0, logdet_p=0.0)
+	if rank > 0:
+		pinfo = _as_device_operator(B, dtype=np.float64).info()
+	nb = -(-count // batch)
+	batch = -(-count // nb)  # whole batches of equal size: nb * batch probes, count rounded up by less than nb
+	est, res = hutch(M, batch=batch, pdf=pdf, converge="count", count=count, seed=seed, full=True, record=True)
+	vals = np.asarray(res.estimator.values, dtype=np.float64).ravel()
+	info = dict(rank=int(pinfo["rank"]), logdet_precond=float(pinfo["logdet_p"]), trace=float(est), count=int(vals.size), deg=deg,
+				std_error=float(np.std(vals, ddof=1) / np.sqrt(vals.size)))  # fmt: skip
+	return float(est) + float(pinfo["logdet_p"]), info
+
+
 def posterior(K, y, Xnew, deg: int = 60, orth: Optional[int] = None, rtol: float = 0.0, variance: bool = True, batch: int = 128,
-			  covariance: bool = False, include_noise: bool = False) -> tuple:  # fmt: skip
+			  covariance: bool = False, include_noise: bool = False, precond_rank: int = 0) -> tuple:  # fmt: skip
 	"""(mean, var, info): the posterior of a Gaussian process with the kernel operator `K` (a `KernelOperator` in float64; its
 	noise is the observation noise) and zero prior mean, given observations `y` ((n,) or (n, q)) at K's points, at the new points
 	`Xnew` (m x d; NumPy, or a torch tensor on the context's GPU).
@@ -59,6 +96,10 @@ def posterior(K, y, Xnew, deg: int = 60, orth: Optional[int] = None, rtol: float
 	device with a copy of a non-zero column of the batch (a batch with none runs no plan at all), and their rows and columns of the
 	block are set to 0 afterwards - no other column can see a NaN from them. A zero column of `y` is treated the same way and has
 	mean 0.
+
+	precond_rank > 0: every solve is M B^-1 M on the preconditioned operator B = M A M of `K.preconditioned(precond_rank)` (§4.18) -
+	M is applied on the device to the right-hand sides before they become a plan's probes and to the action's result - so that
+	`deg` steps suffice at small noise. 0 (the default) is the plain path on A.
 
 	info: deg, batches (variance batches run), steps (the Lanczos steps each plan took: first the solve for alpha, then one entry
 	per batch), zero_columns (indices of the new points whose column of B was zero)."""
@@ -90,6 +131,25 @@ def posterior(K, y, Xnew, deg: int = 60, orth: Optional[int] = None, rtol: float
 	ctx = op.ctx
 	q = yh.shape[1]
 	live = []  # device objects, closed in reverse order whatever happens
+	precond_rank = int(precond_rank)
+	if precond_rank < 0:
+		raise ValueError(f"precond_rank = {precond_rank} must be >= 0")
+	## the operator the plans run on: A itself, or B = M A M (the cross products stay on A's operator)
+	pop = _as_device_operator(K.preconditioned(precond_rank), dtype=np.float64) if precond_rank > 0 else None
+	solve_op = op if pop is None else pop
+
+	def solve_into(plan, RHS, OUT, b, tmp):
+		"""OUT[:, :b] = A^-1 RHS[:, :b] by `plan` (on solve_op); tmp: two n x b DeviceMatrix of scratch for the preconditioned path."""
+		if pop is None:
+			plan.set_probes_device(RHS.col_ptr(0))
+			plan.run(rtol)
+			plan.fun_action_into(OUT, 0, "inv")
+			return
+		pop.inv_sqrt_dmat(RHS, 0, tmp[0], 0, b)
+		plan.set_probes_device(tmp[0].col_ptr(0))
+		plan.run(rtol)
+		plan.fun_action_into(tmp[1], 0, "inv")
+		pop.inv_sqrt_dmat(tmp[1], 0, OUT, 0, b)
 
 	def keep(obj):
 		live.append(obj)
@@ -101,12 +161,17 @@ def posterior(K, y, Xnew, deg: int = 60, orth: Optional[int] = None, rtol: float
 		nz = np.flatnonzero(np.any(yh != 0.0, axis=0))
 		mean = np.zeros((m, q))
 		if nz.size:
-			plan = keep(engine.LanczosPlan(op, int(nz.size), deg, orth_arg, basis="keep"))
-			plan.set_probes(np.asfortranarray(yh[:, nz]))
-			plan.run(rtol)
-			info["steps"].append(plan.steps_done)
+			plan = keep(engine.LanczosPlan(solve_op, int(nz.size), deg, orth_arg, basis="keep"))
 			Alpha = keep(engine.DeviceMatrix(n, int(nz.size), ctx=ctx))
-			plan.fun_action_into(Alpha, 0, "inv")
+			if pop is None:
+				plan.set_probes(np.asfortranarray(yh[:, nz]))
+				plan.run(rtol)
+				plan.fun_action_into(Alpha, 0, "inv")
+			else:
+				Yd, t0, t1 = (keep(engine.DeviceMatrix(n, int(nz.size), ctx=ctx)) for _ in range(3))
+				Yd.set(0, np.asfortranarray(yh[:, nz]))
+				solve_into(plan, Yd, Alpha, int(nz.size), (t0, t1))
+			info["steps"].append(plan.steps_done)
 			cross = keep(Cop.device(op))
 			Mean = keep(engine.DeviceMatrix(m, int(nz.size), ctx=ctx))
 			cross.matmat_dmat(Alpha, 0, Mean, 0, int(nz.size))
@@ -120,6 +185,7 @@ def posterior(K, y, Xnew, deg: int = 60, orth: Optional[int] = None, rtol: float
 
 		mb_max = min(batch, m)
 		B, Cv = keep(engine.DeviceMatrix(n, mb_max, ctx=ctx)), keep(engine.DeviceMatrix(n, mb_max, ctx=ctx))
+		tmp = tuple(keep(engine.DeviceMatrix(n, mb_max, ctx=ctx)) for _ in range(2)) if pop is not None else None
 		plans = {}
 		quad = np.zeros(m)
 		block_full = None
@@ -137,11 +203,9 @@ def posterior(K, y, Xnew, deg: int = 60, orth: Optional[int] = None, rtol: float
 				for j in zero:  # (a stand-in the plan can run on; its results are dropped below)
 					B.copy_from(int(j), B, int(good[0]), 1)
 				if mb not in plans:
-					plans[mb] = keep(engine.LanczosPlan(op, mb, deg, orth_arg, basis="keep"))
-				plans[mb].set_probes_device(B.col_ptr(0))
-				plans[mb].run(rtol)
+					plans[mb] = keep(engine.LanczosPlan(solve_op, mb, deg, orth_arg, basis="keep"))
+				solve_into(plans[mb], B, Cv, mb, tmp)
 				info["steps"].append(plans[mb].steps_done)
-				plans[mb].fun_action_into(Cv, 0, "inv")
 				block = B.tn(0, mb, Cv, 0, mb)
 				_finite(block, f"the variance block of the new points [{i0}, {i1})", rtol)
 				block[zero, :] = 0.0

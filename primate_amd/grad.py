@@ -152,6 +152,8 @@ def trace_grad(M, pdf: Union[str, None] = "rademacher", count: int = 256, batch:
 
 	if not isinstance(M, (MatrixFunction, ChebyshevFunction)):
 		raise ValueError("trace_grad takes a MatrixFunction or a ChebyshevFunction")
+	if getattr(getattr(M, "_A", None), "_slq_kind", None) == "kernel_precond" or getattr(getattr(M, "_op", None), "kind", None) == "kernel_precond":
+		raise ValueError("trace_grad: a preconditioned kernel operator has no stored entries, and gradients through the preconditioner are not built")
 	if getattr(getattr(M, "_A", None), "_slq_kind", None) == "kernel" or getattr(getattr(M, "_op", None), "kind", None) == "kernel":
 		raise ValueError("trace_grad: a KernelOperator has no stored entries; its hyperparameter gradients come from kernel_trace_grad")
 	if np.dtype(M.dtype) != np.float64:
@@ -271,6 +273,8 @@ def kernel_trace_grad(M, pdf: Union[str, None] = "rademacher", count: int = 256,
 	if not isinstance(M, (MatrixFunction, ChebyshevFunction)):
 		raise ValueError("kernel_trace_grad takes a MatrixFunction or a ChebyshevFunction")
 	K = getattr(M, "_A", None)
+	if getattr(K, "_slq_kind", None) == "kernel_precond":
+		raise ValueError("kernel_trace_grad: gradients through the pivoted-Cholesky preconditioner are not built: differentiate the function of the base KernelOperator")
 	if getattr(K, "_slq_kind", None) != "kernel":
 		raise ValueError("kernel_trace_grad needs a function of a KernelOperator (for the gradient on a sparsity pattern use trace_grad)")
 	if np.dtype(M.dtype) != np.float64 or np.dtype(K.dtype) != np.float64:
@@ -339,6 +343,8 @@ def kernel_quadratic_grad(K, U, V=None) -> dict:
 	a marginal likelihood. One KernelGradAccumulator update on K's device operator."""
 	from .lanczos import _as_device_operator
 
+	if getattr(K, "_slq_kind", None) == "kernel_precond":
+		raise ValueError("kernel_quadratic_grad: gradients through the pivoted-Cholesky preconditioner are not built: pass the base KernelOperator")
 	if getattr(K, "_slq_kind", None) != "kernel":
 		raise ValueError("kernel_quadratic_grad needs a KernelOperator")
 	if np.dtype(K.dtype) != np.float64:

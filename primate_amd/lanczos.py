@@ -72,6 +72,8 @@ def _as_device_operator(A, dtype=None) -> engine.DeviceOperator:
 		return op
 	cached = getattr(A, "_slq_device_operator", None)
 	if cached is not None and getattr(cached, "_h", None) and (dtype is None or cached.dtype == np.dtype(dtype)):
+		if cached.kind == "kernel_precond":
+			cached.refresh_if_stale()  # (the base's hyperparameters may have changed since the factor was built)
 		return cached
 	op = engine.DeviceOperator(A, dtype=dtype)
 	try:

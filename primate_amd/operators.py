@@ -477,10 +477,139 @@ class KernelOperator(LinearOperator):
 	def _adjoint(self):
 		return self
 
+	def preconditioned(self, rank: int = 100, tol: float = 0.0) -> "PreconditionedKernelOperator":
+		"""B = M A M with M = P^{-1/2} of a rank-`rank` pivoted-Cholesky factor of this operator without its noise (DESIGN.md
+		§4.18): the operator to run Lanczos on when the noise is small. It follows this operator's hyperparameters."""
+		return PreconditionedKernelOperator(self, rank, tol)
+
 	def cross(self, Xnew) -> "KernelCrossOperator":
 		"""The cross-covariance between the new points `Xnew` (m x d) and this operator's points: a `KernelCrossOperator` of shape
 		(m, n). It follows this operator's hyperparameters, whenever they are set."""
 		return KernelCrossOperator(self, Xnew)
+
+
+KERNEL_PRECOND_MAX_RANK = 256
+
+
+def precond_g(t: np.ndarray, sigma2: float) -> np.ndarray:
+	"""g(t) = (1 - (1 + t / sigma2)^{-1/2}) / t, smooth at 0 where it is 1 / (2 sigma2); negative t count as 0."""
+	x = np.maximum(np.asarray(t, dtype=np.float64), 0.0) / sigma2
+	small = ~(x > 2.0**-60)
+	xs = np.where(small, 1.0, x)
+	h = np.where(small, 0.5, np.minimum(-np.expm1(-0.5 * np.log1p(xs)) / xs, 0.5))
+	return h / sigma2
+
+
+class PreconditionedKernelOperator(LinearOperator):
+	"""B = M A M for the KernelOperator `base` (A = K0 + noise I, noise > 0), M = P^{-1/2}, P = L L^T + noise I with L the greedy
+	partial pivoted Cholesky factor of K0 of rank at most `rank`: the residual diagonal starts as d = s; step k
+	takes p = argmax d (ties: the smallest index), L[:, k] = (K0[:, p] - L[:, :k] L[p, :k]^T) / sqrt(d_p), d <- max(0, d - L[:, k]^2),
+	d_p <- 0; rows with d_i = 0 already get 0; it stops when d_p <= max(tol, 64 eps) s. B is symmetric positive definite,
+	logdet A = tr log B + logdet P and A^-1 y = M B^-1 M y for any L. On the device (`slq_kernel_precond_create`) the factor, the
+	applies of M and the product run in HIP kernels. The host side here is the model of the tests, O(n^2) NumPy in float64 from the
+	definition, for small n: `_matmat`, `inv_sqrt`, and the attributes `rank`, `pivots`, `logdet_precond`, `residual_trace`."""
+
+	_slq_kind = "kernel_precond"
+
+	def __init__(self, base: KernelOperator, rank: int = 100, tol: float = 0.0):
+		if getattr(base, "_slq_kind", None) != "kernel":
+			raise ValueError("PreconditionedKernelOperator needs a KernelOperator")
+		if np.dtype(base.dtype) != np.float64:
+			raise ValueError(f"the preconditioner is fp64 only: the KernelOperator is {np.dtype(base.dtype)}")
+		if not base.noise > 0:
+			raise ValueError("the preconditioner needs noise > 0 (P^{-1/2} = (L L^T + noise I)^{-1/2})")
+		rank = int(rank)
+		if not 1 <= rank <= KERNEL_PRECOND_MAX_RANK:
+			raise ValueError(f"rank = {rank} (1 <= rank <= {KERNEL_PRECOND_MAX_RANK})")
+		tol = float(tol)
+		if not (np.isfinite(tol) and tol >= 0):
+			raise ValueError(f"tol = {tol} is not a finite number >= 0")
+		self.base, self.tol = base, tol
+		self.rank_max = min(rank, base.shape[0])
+		self.shape, self.dtype = base.shape, np.dtype(np.float64)
+		self._model, self._model_key = None, None
+
+	def _key(self):
+		K = self.base
+		return (tuple(np.atleast_1d(K.lengthscale).tolist()), float(K.outputscale), float(K.noise))
+
+	def k0(self) -> np.ndarray:
+		"""s phi(r2) of the base's points, dense, without the noise term (exact zeros of r2 on the diagonal)."""
+		K = self.base
+		z = K.scaled_points().astype(np.float64)
+		nrm = np.einsum("ij,ij->i", z, z)
+		r2 = np.maximum(nrm[:, None] + nrm[None, :] - 2.0 * (z @ z.T), 0.0)
+		np.fill_diagonal(r2, 0.0)
+		return K.outputscale * _kernel_profile(K.kernel, r2)
+
+	def host_model(self) -> dict:
+		"""{L, pivots, d, t, V, G, logdet_p} by the definition, for the base's parameters of now (cached per parameter set)."""
+		if self._model is not None and self._model_key == self._key():
+			return self._model
+		K = self.base
+		n, r, s, sigma2 = self.shape[0], self.rank_max, float(K.outputscale), float(K.noise)
+		K0 = self.k0()
+		d = np.full(n, s)
+		L = np.zeros((n, r))
+		piv = []
+		stop = max(self.tol, 64.0 * np.finfo(np.float64).eps) * s
+		for k in range(r):
+			p = int(np.argmax(d))
+			if not d[p] > stop:
+				break
+			col = (K0[:, p] - L[:, :k] @ L[p, :k]) / np.sqrt(d[p])
+			dead = d == 0.0
+			dead[p] = False
+			col[dead] = 0.0
+			L[:, k] = col
+			d = np.maximum(d - col * col, 0.0)
+			d[p] = 0.0
+			piv.append(p)
+		t, V = np.linalg.eigh(L.T @ L)
+		t = np.maximum(t, 0.0)
+		G = (V * precond_g(t, sigma2)) @ V.T
+		self._model = dict(L=L, pivots=np.array(piv, dtype=np.int64), d=d, t=t, V=V, G=G, logdet_p=float(np.sum(np.log1p(t / sigma2)) + n * np.log(sigma2)))
+		self._model_key = self._key()
+		return self._model
+
+	@property
+	def rank(self) -> int:
+		return int(self.host_model()["pivots"].size)
+
+	@property
+	def pivots(self) -> np.ndarray:
+		return self.host_model()["pivots"]
+
+	@property
+	def logdet_precond(self) -> float:
+		return self.host_model()["logdet_p"]
+
+	@property
+	def residual_trace(self) -> float:
+		return float(np.sum(self.host_model()["d"]))
+
+	def inv_sqrt(self, X: np.ndarray) -> np.ndarray:
+		"""P^{-1/2} X = (X - L G L^T X) / sigma."""
+		m = self.host_model()
+		X = np.asarray(X, dtype=np.float64)
+		X2 = X.reshape(self.shape[0], -1)
+		Y = (X2 - m["L"] @ (m["G"] @ (m["L"].T @ X2))) / np.sqrt(float(self.base.noise))
+		return Y.reshape(X.shape)
+
+	def _matmat(self, X: np.ndarray) -> np.ndarray:
+		X = np.asarray(X)
+		if X.ndim != 2 or X.shape[0] != self.shape[1]:
+			raise ValueError(f"dimension mismatch: the operator is {self.shape[0]} x {self.shape[1]}, the operand has {X.shape[0]} rows")
+		return self.inv_sqrt(self.base._matmat(self.inv_sqrt(X)))
+
+	def _matvec(self, x: np.ndarray) -> np.ndarray:
+		x = np.asarray(x)
+		if x.size != self.shape[1]:
+			raise ValueError(f"dimension mismatch: the operator is {self.shape[0]} x {self.shape[1]}, the operand has {x.size} entries")
+		return self._matmat(x.reshape(-1, 1)).ravel()
+
+	def _adjoint(self):
+		return self
 
 
 class KernelCrossOperator(LinearOperator):
