@@ -584,7 +584,18 @@ int slq_debug_kernel_cross_schedule(int64_t nrows, int64_t nsum, int64_t b, int 
  * slq_kernel_precond_apply_dmat: the same on columns [i0, i0 + b) of IN and [o0, o0 + b) of OUT (overlapping ranges of one
  *   matrix are refused), asynchronous on the context stream. The two entries give the
  *   same bits.
- * slq_debug_kernel_precond_addresses: the device addresses of L, G, the pivots and the residual diagonal as integers (tests). */
+ * slq_debug_kernel_precond_addresses: the device addresses of L, G, the pivots and the residual diagonal as integers (tests).
+ * The factor as operands of the gradient kernel. H = (L^T L + sigma2 I)^-1 = V diag(1 / (t + sigma2)) V^T is
+ *   kept next to G (rpad x rpad, same upload, same staleness), so that P^-1 = (I - L H L^T) / sigma2.
+ * slq_kernel_precond_columns: columns [o0, o0 + nc) of OUT = columns [c0, c0 + nc) of L (which = 0: a copy, bit for bit) or of
+ *   L H (which = 1: on the matrix cores), 1 <= nc <= 64, 0 <= c0, c0 + nc <= rpad; asynchronous on the context stream, one writer
+ *   per word: identical calls give identical bits. SLQ_EINVAL names the cause: not a preconditioned operator, stale, the column
+ *   range, a row mismatch (OUT has other than n rows), another context.
+ * slq_kernel_precond_trace_grad: vals = beta vals + alpha tr(P^-1 dA/dtheta) in the accumulator `grad`, which must have been created
+ *   on the BASE operator of `pre` (SLQ_EINVAL "another operator" otherwise): sigma^-2 [tr D - sum_c (L H)_c^T D L_c] with tr D = 0
+ *   for a lengthscale and n for the outputscale and the noise. The columns of the rank reached go through slq_kernel_grad_update 64
+ *   at a time from two n x 64 matrices the preconditioner owns (allocated at the first call); one one-thread kernel then adds
+ *   alpha n / sigma2 on the stream. Deterministic, asynchronous; the accumulator's column count is unchanged. */
 int slq_kernel_precond_create(slq_context *ctx, slq_operator *kernel_op, int rank_max, double tol, slq_operator **out);
 int slq_kernel_precond_refresh(slq_operator *pre);
 int slq_kernel_precond_info(const slq_operator *pre, int *rank_max, int *rank, double *logdet_p, double *residual_trace, double *t_max);
@@ -592,6 +603,10 @@ int slq_kernel_precond_get(slq_operator *pre, int32_t *pivots, double *L, int64_
 int slq_kernel_precond_apply(slq_operator *pre, const void *X, int64_t ldx, void *Y, int64_t ldy, int b);
 int slq_kernel_precond_apply_dmat(slq_operator *pre, slq_dmat *IN, int i0, slq_dmat *OUT, int o0, int b);
 int slq_debug_kernel_precond_addresses(const slq_operator *pre, uint64_t *out4);
+/* H as the device holds it: rank_max x rank_max, row-major (tests). Synchronises. */
+int slq_debug_kernel_precond_h(slq_operator *pre, double *H);
+int slq_kernel_precond_columns(slq_operator *pre, int which, int c0, int nc, slq_dmat *OUT, int o0);
+int slq_kernel_precond_trace_grad(slq_operator *pre, slq_kernel_grad *grad, double alpha, double beta);
 /* wall time of the last factorisation (create or refresh) in ms: out2[0] the launches up to the one synchronisation - the
  * rank_max steps and the Gram matrix -, out2[1] the host part: Jacobi, G and its upload (scripts/bench_kernelprecond.py). */
 int slq_debug_kernel_precond_timing(const slq_operator *pre, double *out2);

@@ -146,6 +146,9 @@ _SIGNATURES = {
 	"slq_kernel_precond_apply_dmat": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int]),
 	"slq_debug_kernel_precond_addresses": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
 	"slq_debug_kernel_precond_timing": (C.c_int, [_P, C.POINTER(C.c_double)]),
+	"slq_debug_kernel_precond_h": (C.c_int, [_P, _P]),
+	"slq_kernel_precond_columns": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int]),
+	"slq_kernel_precond_trace_grad": (C.c_int, [_P, _P, C.c_double, C.c_double]),
 	"slq_plan_profile_enable": (C.c_int, [_P, C.c_int]),
 	"slq_plan_action_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
 	"slq_plan_sweep_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),

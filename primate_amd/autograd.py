@@ -9,6 +9,9 @@ The operator is rebuilt on every call - its values changed, which is the point.
 
 `kernel_trace_fun` is the same for a Gaussian process's kernel matrix over points: differentiable with respect to lengthscale,
 outputscale and noise (`primate_amd.grad.kernel_trace_grad`; d + 2 numbers, stored on the parameters' devices).
+
+`gp_mll_fun` is the marginal log-likelihood of a Gaussian process, differentiable in the same three parameters through the
+pivoted-Cholesky preconditioner (`primate_amd.gp.mll`): what a torch optimiser trains a GP with at small noise.
 """
 
 from __future__ import annotations
@@ -86,6 +89,49 @@ class _KernelTraceFun(torch.autograd.Function):
 		return tuple(grad_output.to(G.device) * G for G in ctx.saved_tensors) + (None, None)
 
 
+class _GpMllFun(torch.autograd.Function):
+	@staticmethod
+	def forward(ctx, lengthscale, outputscale, noise, X, y, opts):
+		from .gp import mll
+		from .operators import KernelOperator
+
+		o = dict(opts)
+		kernel = o.pop("kernel")
+		## an operator of its own on every call: its parameters changed, which is the point
+		K = KernelOperator(X, kernel, lengthscale=lengthscale.detach().cpu().numpy().astype("float64"), outputscale=float(outputscale),
+						   noise=float(noise), dtype="float64")  # fmt: skip
+		value, grads, _ = mll(K, y, **o)
+		G = [torch.as_tensor(grads[k], dtype=p.dtype, device=p.device).reshape(p.shape)
+			 for k, p in (("lengthscale", lengthscale), ("outputscale", outputscale), ("noise", noise))]  # fmt: skip
+		ctx.save_for_backward(*G)
+		return lengthscale.new_tensor(value)
+
+	@staticmethod
+	def backward(ctx, grad_output):
+		return tuple(grad_output.to(G.device) * G for G in ctx.saved_tensors) + (None, None, None)
+
+
+def gp_mll_fun(X, y, kernel, lengthscale, outputscale, noise, rank: int = 100, deg: int = 20, count: int = 64, seed: int = 0, **kw):
+	"""The marginal log-likelihood of a zero-mean Gaussian process over the points X with observations y (`primate_amd.gp.mll`,
+	fp64) as a 0-d tensor differentiable with respect to the three parameter tensors `lengthscale` (0-d, one element, or one per
+	dimension), `outputscale`, `noise` (floats are taken as constants). X and y get NO gradient: they are data. Backward is
+	grad_output times the gradients `gp.mll` returned: the gradient of the marginal likelihood itself (exact data-fit term, exact
+	tr(P^-1 dA/dtheta), sampled remainder), not the derivative of the sampled value. Maximise it with any torch optimiser on
+	`-gp_mll_fun(...)`. kw: solve_deg, batch, pdf, probes, control_variate go to `gp.mll`. The same seed gives the same bits."""
+	if isinstance(X, torch.Tensor):
+		X = X.detach().cpu().numpy()
+	if isinstance(y, torch.Tensor):
+		y = y.detach().cpu().numpy()
+	ls, s, v = (p if isinstance(p, torch.Tensor) else torch.as_tensor(p, dtype=torch.float64) for p in (lengthscale, outputscale, noise))
+	if s.numel() != 1 or v.numel() != 1:
+		raise ValueError("outputscale and noise are single numbers")
+	unknown = set(kw) - {"solve_deg", "batch", "pdf", "probes", "control_variate"}
+	if unknown:
+		raise ValueError(f"gp_mll_fun: unknown arguments {sorted(unknown)}")
+	opts = dict(kw, kernel=kernel, rank=int(rank), deg=int(deg), count=int(count), seed=int(seed))
+	return _GpMllFun.apply(ls, s, v, X, y, opts)
+
+
 def kernel_trace_fun(X, kernel, lengthscale, outputscale, noise, fun="log", deg: int = 30, count: int = 256, seed: int = 0, method: str = "lanczos", **kw):
 	"""The Girard-Hutchinson estimate of tr f(A), A = outputscale * phi(r2) + noise * I over the points X (the KernelOperator of
 	`primate_amd.operators`), as a 0-d tensor differentiable with respect to the three parameter tensors: `lengthscale` (0-d, one
@@ -112,7 +158,7 @@ def trace_fun(A_csr, fun="log", deg: int = 30, count: int = 256, seed: int = 0, 
 	"chebyshev" (ChebyshevFunction; `dfun=` for a callable). kw: batch, pdf (default "device:rademacher"), symmetric, dfun go to
 	trace_grad, everything else to the operator (orth=, t=, bounds=, damping=, ...). The same seed gives the same bits."""
 	if getattr(A_csr, "_slq_kind", None) == "kernel_precond":
-		raise ValueError("trace_fun: a preconditioned kernel operator is not differentiable here: gradients through the preconditioner are not built")
+		raise ValueError("trace_fun: a preconditioned kernel operator is not differentiable here: gradients through the preconditioner are gp.logdet_grad's (autograd.gp_mll_fun)")
 	if getattr(A_csr, "_slq_kind", None) == "kernel":
 		raise ValueError("trace_fun differentiates the values of a sparse tensor: the hyperparameter gradients of a KernelOperator come from kernel_trace_fun")
 	if not engine._is_torch_csr(A_csr):

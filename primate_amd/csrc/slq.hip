@@ -4419,7 +4419,7 @@ static int precond_factorise(slq_operator *op) {
                          cus, st))
     return fail(SLQ_EINVAL, "kernel preconditioner: no Gram kernel for rank %d", rpad);
   HIP_TRY(hipGetLastError());
-  std::vector<double> gram((size_t)rpad * rpad), dres((size_t)n), A((size_t)r * r), V((size_t)r * r), t((size_t)r), G((size_t)rpad * rpad);
+  std::vector<double> gram((size_t)rpad * rpad), dres((size_t)n), A((size_t)r * r), V((size_t)r * r), t((size_t)r), G((size_t)rpad * rpad), H((size_t)rpad * rpad);
   HIP_TRY(hipMemcpyAsync(gram.data(), gram_d, gram.size() * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(dres.data(), pc.dres.p, dres.size() * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(&pc.rank, pc.rank_d, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -4428,8 +4428,9 @@ static int precond_factorise(slq_operator *op) {
   for (int i = 0; i < r; ++i)
     for (int j = i; j < r; ++j) A[(size_t)i * r + j] = A[(size_t)j * r + i] = gram[(size_t)i * rpad + j];  // (gram[g][m]: column g of the product, symmetric)
   if (precond_jacobi(r, A.data(), V.data(), t.data()) >= kPrecondJacobiSweeps) return fail(SLQ_ENOTCONV, "kernel preconditioner: Jacobi did not converge on the %d x %d Gram matrix", r, r);
-  const PrecondSpectrum sp = precond_finish(n, r, rpad, V.data(), t.data(), base->k_noise, G.data());
+  const PrecondSpectrum sp = precond_finish(n, r, rpad, V.data(), t.data(), base->k_noise, G.data(), H.data());
   HIP_TRY(hipMemcpyAsync(pc.G.p, G.data(), G.size() * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(pc.H.p, H.data(), H.size() * 8, hipMemcpyHostToDevice, st));
   HIP_TRY(hipStreamSynchronize(st));
   const auto t2 = std::chrono::steady_clock::now();
   pc.device_ms = std::chrono::duration<double, std::milli>(t1 - t0).count(), pc.host_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
@@ -4462,9 +4463,11 @@ static int kernel_precond_create_body(slq_context *ctx, slq_operator *base, int 
   const size_t head_ints = ((size_t)rank_max + 1 + 1) / 2 * 2;  // pivots | rank, padded to whole doubles
   hipError_t e = pc.L.alloc(n * pc.rpad * 8);
   if (e == hipSuccess) e = pc.G.alloc((size_t)pc.rpad * pc.rpad * 8);
+  if (e == hipSuccess) e = pc.H.alloc((size_t)pc.rpad * pc.rpad * 8);
   if (e == hipSuccess) e = pc.dres.alloc(n * 8);
   if (e == hipSuccess) e = pc.words.alloc(head_ints * 4 + ((size_t)rank_max + 2 * nparts) * 8 + 2 * nparts * 4);
   if (e == hipSuccess) e = hipMemsetAsync(pc.G.p, 0, (size_t)pc.rpad * pc.rpad * 8, ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(pc.H.p, 0, (size_t)pc.rpad * pc.rpad * 8, ctx->stream);
   if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "slq_kernel_precond_create: %s", hipGetErrorString(e));
   pc.pivots = pc.words.as<int>(), pc.rank_d = pc.pivots + rank_max;
   pc.dpiv = (double *)(pc.pivots + head_ints), pc.pv = pc.dpiv + rank_max;
@@ -4564,6 +4567,62 @@ extern "C" int slq_kernel_precond_apply_dmat(slq_operator *op, slq_dmat *IN, int
   return precond_apply_device(op, IN->d + (size_t)i0 * IN->n, OUT->d + (size_t)o0 * OUT->n, b, "slq_kernel_precond_apply_dmat");
 }
 
+// ---- the factor's columns as operands of the gradient kernel, and the exact part tr(P^-1 dA/dtheta) ----
+// columns [c0, c0 + nc) of L (Q null) or L H into a device array of n x nc, column-major; the caller has checked everything
+static int precond_columns_device(slq_operator *op, int which, int c0, int nc, double *OUT, const char *who) {
+  const KernelPrecond &pc = *op->pre;
+  if (!precond_columns_launch((int)op->n, pc.L.as<const double>(), pc.rpad, which ? pc.H.as<const double>() : (const double *)nullptr, c0, nc, OUT, op->ctx->stream))
+    return fail(SLQ_EINVAL, "%s: no column kernel for rank %d", who, pc.rpad);
+  HIP_TRY(hipGetLastError());
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_precond_columns(slq_operator *op, int which, int c0, int nc, slq_dmat *OUT, int o0) {
+  SLQ_TRY(precond_handle(op, "slq_kernel_precond_columns"));
+  SLQ_TRY(precond_check_fresh(op, "slq_kernel_precond_columns"));
+  const KernelPrecond &pc = *op->pre;
+  if (which != 0 && which != 1) return fail(SLQ_EINVAL, "slq_kernel_precond_columns: which = %d (0: L, 1: L H)", which);
+  if (c0 < 0 || nc < 1 || nc > kPrecondChunkCols || c0 + nc > pc.rpad)
+    return fail(SLQ_EINVAL, "slq_kernel_precond_columns: the column range [%d, %d) is outside [0, rpad = %d) or holds more than %d columns", c0, c0 + nc, pc.rpad, kPrecondChunkCols);
+  SLQ_TRY(dmat_range(OUT, o0, nc, "slq_kernel_precond_columns(OUT)"));
+  if (OUT->n != op->n) return fail(SLQ_EINVAL, "slq_kernel_precond_columns: row mismatch: the operator has %lld rows, OUT %lld", (long long)op->n, (long long)OUT->n);
+  if (OUT->ctx != op->ctx) return fail(SLQ_EINVAL, "slq_kernel_precond_columns: OUT belongs to another context");
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  return precond_columns_device(op, which, c0, nc, OUT->d + (size_t)o0 * OUT->n, "slq_kernel_precond_columns");
+}
+
+// vals = beta vals + alpha sigma^-2 [tr D - sum_c (L H)_c^T D L_c] over the columns of the rank reached, 64 at a time: per chunk two
+// column launches and one accumulator update (alpha_u = -alpha / sigma2; beta for the first chunk, 1 after it), then ONE one-thread
+// kernel adds alpha n / sigma2 to the outputscale's and the noise's value - everything on the stream, nothing is read back. The
+// accumulator's column count is left as it was: no probe was folded in.
+extern "C" int slq_kernel_precond_trace_grad(slq_operator *op, slq_kernel_grad *g, double alpha, double beta) {
+  SLQ_TRY(precond_handle(op, "slq_kernel_precond_trace_grad"));
+  if (!g) return fail(SLQ_EINVAL, "slq_kernel_precond_trace_grad: the accumulator is NULL");
+  KernelPrecond &pc = *op->pre;
+  if (g->op != pc.base) return fail(SLQ_EINVAL, "slq_kernel_precond_trace_grad: the accumulator belongs to another operator: create it on the base of this preconditioned operator");
+  SLQ_TRY(precond_check_fresh(op, "slq_kernel_precond_trace_grad"));
+  if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(SLQ_EINVAL, "slq_kernel_precond_trace_grad: alpha = %g, beta = %g must be finite", alpha, beta);
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  const size_t n = (size_t)op->n;
+  SLQ_TRY(precond_grow(pc.cols, 2 * n * kPrecondChunkCols * 8, "slq_kernel_precond_trace_grad"));
+  slq_dmat Z{op->ctx, op->n, kPrecondChunkCols, pc.cols.as<double>()}, W{op->ctx, op->n, kPrecondChunkCols, pc.cols.as<double>() + n * kPrecondChunkCols};
+  const double sigma2 = pc.base->k_noise;
+  const int64_t count = g->count;
+  bool first = true;  // (the rank reached is at least 1: the first pivot's residual is s itself)
+  for (int c0 = 0; c0 < pc.rank; c0 += kPrecondChunkCols) {
+    const int nc = std::min(kPrecondChunkCols, pc.rank - c0);
+    SLQ_TRY(precond_columns_device(op, 1, c0, nc, Z.d, "slq_kernel_precond_trace_grad"));
+    SLQ_TRY(precond_columns_device(op, 0, c0, nc, W.d, "slq_kernel_precond_trace_grad"));
+    SLQ_TRY(slq_kernel_grad_update(g, &Z, 0, &W, 0, nc, -alpha / sigma2, first ? beta : 1.0));
+    first = false;
+  }
+  g->count = count;
+  hipStream_t st = op->ctx->stream;
+  k_precond_trace_add<<<dim3(1), dim3(64), 0, st>>>(g->d, (double)op->n, (const double *)pc.base->k_pts.params, alpha, g->vals.as<double>());
+  HIP_TRY(hipGetLastError());
+  return SLQ_OK;
+}
+
 // the device addresses of L, G, the pivots and the residual diagonal (tests: a refresh keeps them)
 extern "C" int slq_debug_kernel_precond_addresses(const slq_operator *op, uint64_t *out4) {
   SLQ_TRY(precond_handle(op, "slq_debug_kernel_precond_addresses"));
@@ -4571,6 +4630,21 @@ extern "C" int slq_debug_kernel_precond_addresses(const slq_operator *op, uint64
   const KernelPrecond &pc = *op->pre;
   out4[0] = (uint64_t)(uintptr_t)pc.L.p, out4[1] = (uint64_t)(uintptr_t)pc.G.p, out4[2] = (uint64_t)(uintptr_t)pc.pivots, out4[3] = (uint64_t)(uintptr_t)pc.dres.p;
   return SLQ_OK;
+}
+// H as the device holds it, rank_max x rank_max row-major (tests: the operand of slq_kernel_precond_columns). Synchronises.
+extern "C" int slq_debug_kernel_precond_h(slq_operator *op, double *H) {
+  SLQ_TRY(precond_handle(op, "slq_debug_kernel_precond_h"));
+  if (!H) return fail(SLQ_EINVAL, "slq_debug_kernel_precond_h: H is NULL");
+  const KernelPrecond &pc = *op->pre;
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  HIP_TRY(hipStreamSynchronize(op->ctx->stream));
+  return create_guarded(nullptr, [&]() {
+    const size_t r = (size_t)pc.rank_max, rpad = (size_t)pc.rpad;
+    std::vector<double> h(rpad * rpad);
+    HIP_TRY(hipMemcpy(h.data(), pc.H.p, h.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < r; ++i) std::copy(h.begin() + i * rpad, h.begin() + i * rpad + r, H + i * r);
+    return (int)SLQ_OK;
+  });
 }
 // wall time of the last factorisation in ms: {the launches up to the synchronisation, the host part: Jacobi, G and its upload}
 extern "C" int slq_debug_kernel_precond_timing(const slq_operator *op, double *out2) {

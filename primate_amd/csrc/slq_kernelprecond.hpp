@@ -10,10 +10,12 @@
 //     precond_apply_slabs         how the rows are cut into slabs for L^T W: a pure function of (n, columns, num_cus)
 //     precond_scratch_words       what one apply needs behind it: the slab partials and G (L^T W)
 //     precond_jacobi              cyclic Jacobi on the r x r Gram matrix, fixed sweep order
-//     precond_g, precond_finish   g(t), G and logdet P from the eigendecomposition
+//     precond_g, precond_finish   g(t), G, H and logdet P from the eigendecomposition (H = (L^T L + sigma2 I)^-1: P^-1 = (I - L H L^T) / sigma2, §4.19)
 //   device (hipcc only)
 //     k_precond_init, k_precond_column   the factor: one launch per step, no host synchronisation in between
 //     k_precond_lt, k_precond_gz, k_precond_nn   Zt = L^T W in row slabs, their sum in slab order times G, Y = c (X - L (G Zt))
+//     k_precond_columns, k_precond_trace_add     columns of L or L H as a column-major matrix (operands of the gradient kernel), the
+//                                                constant sigma^-2 tr D of tr(P^-1 D) (§4.19)
 #pragma once
 
 #include <stddef.h>
@@ -33,6 +35,7 @@ constexpr int kPrecondMaxSlabs = 64;    // row slabs of L^T W (summed in slab or
 constexpr int kPrecondMaxParts = 1024;  // workgroups of a factor step: (max, index) partials the next step reduces
 constexpr int kPrecondColsPerWg = 64;   // columns a workgroup of k_precond_lt owns: 16 per wave
 constexpr int kPrecondThreads = 256;
+constexpr int kPrecondChunkCols = 64;   // columns of L and L H one gradient update of the exact part takes (slq_kernel_precond_trace_grad)
 
 inline int precond_rpad(int rank_max) { return (rank_max + 15) / 16 * 16; }
 inline int64_t precond_bpad(int64_t cols) { return (cols + kPrecondColsPerWg - 1) / kPrecondColsPerWg * kPrecondColsPerWg; }
@@ -120,16 +123,21 @@ inline int precond_jacobi(int r, double *A, double *V, double *t) {
   return sweep;
 }
 
-// G = V diag(g(t)) V^T (r x r into an rpad x rpad row-major array, zeros in the padding), logdet P and the largest eigenvalue
+// h(t) = 1 / (t + sigma2): H = V diag(h(t)) V^T = (L^T L + sigma2 I)^-1. Negative t count as 0, as in g.
+inline double precond_h(double t, double sigma2) { return 1.0 / ((t > 0.0 ? t : 0.0) + sigma2); }
+
+// G = V diag(g(t)) V^T (r x r into an rpad x rpad row-major array, zeros in the padding), logdet P and the largest eigenvalue;
+// H = V diag(h(t)) V^T in the same layout where H is not null (exactly symmetric: each pair is computed once)
 struct PrecondSpectrum {
   double logdet_p = 0.0, t_max = 0.0;
 };
-inline PrecondSpectrum precond_finish(int64_t n, int r, int rpad, const double *V, const double *t, double sigma2, double *G) {
+inline PrecondSpectrum precond_finish(int64_t n, int r, int rpad, const double *V, const double *t, double sigma2, double *G, double *H = nullptr) {
   PrecondSpectrum sp;
-  std::vector<double> gt((size_t)r);
+  std::vector<double> gt((size_t)r), ht((size_t)r);
   for (int i = 0; i < r; ++i) {
     const double ti = std::max(t[i], 0.0);
     gt[(size_t)i] = precond_g(ti, sigma2);
+    ht[(size_t)i] = precond_h(ti, sigma2);
     sp.logdet_p += std::log1p(ti / sigma2);
     sp.t_max = std::max(sp.t_max, ti);
   }
@@ -141,6 +149,15 @@ inline PrecondSpectrum precond_finish(int64_t n, int r, int rpad, const double *
       for (int k = 0; k < r; ++k) a += V[(size_t)i * r + k] * gt[(size_t)k] * V[(size_t)j * r + k];
       G[(size_t)i * rpad + j] = G[(size_t)j * rpad + i] = a;
     }
+  if (H) {
+    std::fill(H, H + (size_t)rpad * rpad, 0.0);
+    for (int i = 0; i < r; ++i)
+      for (int j = i; j < r; ++j) {
+        double a = 0.0;
+        for (int k = 0; k < r; ++k) a += V[(size_t)i * r + k] * ht[(size_t)k] * V[(size_t)j * r + k];
+        H[(size_t)i * rpad + j] = H[(size_t)j * rpad + i] = a;
+      }
+  }
   return sp;
 }
 
@@ -344,6 +361,57 @@ __global__ __launch_bounds__(kPrecondThreads) void k_precond_nn(int n, const dou
   }
 }
 
+// OUT[i, c] = sum_j L[i, j] Q[j, c0 + c] for c < nc <= 64 (the caller keeps c0 + nc <= rpad), OUT column-major with ld = n: nc
+// columns of L Q as operand columns of the gradient kernel. Q (rpad x rpad, EXACTLY symmetric: H of precond_finish, read along its
+// rows) goes through the matrix cores: a wave owns 16 rows and keeps their rpad / 4 <= 4 MT fragments of L in registers, as
+// k_precond_nn does - here they are the B operand (B[k = lane >> 4][n = lane & 15] = L[i0 + n][4 q + k]) and Q's 16-column tile, from
+// the cache, the A operand (A[m = lane & 15][k] = Q[c0 + 16 ct + m][4 q + k]), so that a lane's four results are four columns of ONE
+// row and the 16 lanes of a group store 16 consecutive rows of a column. Q == NULL: the transposing copy OUT[i, c] = L[i, c0 + c],
+// no MFMA. One writer per output word, no atomics, the sum over j in one fixed order: identical calls give identical bits. A
+// slq_dmat has no padding rows (ld == n): nothing is written at or beyond row n.
+template <int MT>
+__global__ __launch_bounds__(kPrecondThreads) void k_precond_columns(int n, const double *__restrict__ L, int rpad, const double *__restrict__ Q, int c0, int nc,
+                                                                    double *__restrict__ OUT) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, lk = lane >> 4;
+  const int i0 = (blockIdx.x * 4 + wave) * 16;
+  if (i0 >= n) return;
+  const int i = i0 + lr;
+  const bool row_ok = i < n;
+  const double *Li = L + (int64_t)(row_ok ? i : i0) * rpad;
+  if (!Q) {
+    for (int c = lk; c < nc; c += 4)
+      if (row_ok) OUT[(int64_t)c * n + i] = Li[c0 + c];
+    return;
+  }
+  const int nq = rpad >> 2;
+  double b[4 * MT];
+#pragma unroll
+  for (int q = 0; q < 4 * MT; ++q) b[q] = (q < nq && row_ok) ? Li[4 * q + lk] : 0.0;
+  for (int ct = 0; 16 * ct < nc; ++ct) {
+    const int cq = 16 * ct + lr;  // the column of this lane's fragment of Q
+    const double *Qc = Q + (int64_t)(c0 + (cq < nc ? cq : 0)) * rpad + lk;
+    kd4_t acc = (kd4_t)0.0;
+#pragma unroll
+    for (int q = 0; q < 4 * MT; ++q)
+      if (q < nq) acc = kernel_mfma(cq < nc ? Qc[4 * q] : 0.0, b[q], acc);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int c = 16 * ct + lk + 4 * r;
+      if (row_ok && c < nc) OUT[(int64_t)c * n + i] = acc[r];
+    }
+  }
+}
+
+// vals[d] += a n / sigma2, vals[d + 1] += a n / sigma2: a sigma^-2 tr D of tr(P^-1 D) for the outputscale and the noise (tr D is n
+// for both and 0 for every lengthscale), sigma2 read from the operator's device word. One thread.
+__global__ void k_precond_trace_add(int d, double n, const double *__restrict__ params, double a, double *__restrict__ vals) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const double c = a * (n / params[1]);
+    vals[d] += c;
+    vals[d + 1] += c;
+  }
+}
+
 // a run-time rpad to the instantiation compiled for it (MT = 1, 2, 4, 8, 16 tiles of 16 factor columns)
 template <typename Fn> inline bool precond_for_mt(int rpad, Fn f) {
   const int nmt = rpad / 16;
@@ -353,6 +421,14 @@ template <typename Fn> inline bool precond_for_mt(int rpad, Fn f) {
   if (nmt <= 8) return f(std::integral_constant<int, 8>{});
   if (nmt <= 16) return f(std::integral_constant<int, 16>{});
   return false;
+}
+
+// OUT (n x nc, column-major, ld = n) = columns [c0, c0 + nc) of L (Q null) or of L Q; the caller has checked 0 <= c0, 1 <= nc <= 64, c0 + nc <= rpad
+inline bool precond_columns_launch(int n, const double *L, int rpad, const double *Q, int c0, int nc, double *OUT, hipStream_t st) {
+  return precond_for_mt(rpad, [&](auto MT) {
+    k_precond_columns<MT()><<<dim3((n + 63) / 64), dim3(kPrecondThreads), 0, st>>>(n, L, rpad, Q, c0, nc, OUT);
+    return true;
+  });
 }
 
 // out[g][m] = (G or I) sum over the rows of L[i][m] W[i][g], g < bpad(ncols): the slab partials go to scratch, out may follow them

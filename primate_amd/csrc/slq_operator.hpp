@@ -164,18 +164,19 @@ struct KernelPoints {
 
 
 // What a preconditioned kernel operator (OP_KERNEL_PRECOND, slq_kernelprecond.hpp) owns: the factor L (n x rpad, row-major, zeros
-// in unused columns), G (rpad x rpad), the residual diagonal and the device words of the factor's steps - all at addresses that
+// in unused columns), G and H (rpad x rpad each), the residual diagonal and the device words of the factor's steps - all at addresses that
 // never change after creation, so that a captured graph sees a refreshed factor - and the host record of the last factorisation.
 struct KernelPrecond {
   slq_operator *base = nullptr;  // not owned: its points, profile and scalars are read at every product
   int rank_max = 0, rpad = 0, rank = 0;
   double tol = 0.0;
   uint64_t epoch = 0;  // the base's k_epoch the factor was built at
-  DevBuf L, G, dres;
+  DevBuf L, G, H, dres;  // H = (L^T L + sigma2 I)^-1: uploaded with G, stale when G is (§4.19)
   DevBuf words;        // pivots[rank_max] | rank | (pad to 8 bytes) | d_p per step [rank_max] | partials: 2 x nparts doubles, 2 x nparts ints
   int *pivots = nullptr, *rank_d = nullptr, *pi = nullptr;
   double *dpiv = nullptr, *pv = nullptr;
   DevBuf scratch, stage_in, stage_out;  // of the stand-alone applies (grown on demand); a plan has its own
+  DevBuf cols;                          // two n x 64 column-major chunks, L H and L, of slq_kernel_precond_trace_grad (allocated at its first call)
   double logdet_p = 0.0, residual_trace = 0.0, t_max = 0.0;
   std::vector<double> eig;  // the eigenvalues of L^T L (rank_max of them)
   double device_ms = 0.0, host_ms = 0.0;  // wall time of the last factorisation: launches up to the synchronisation, then Jacobi, G and its upload

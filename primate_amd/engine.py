@@ -299,13 +299,15 @@ class DeviceOperator:
 		return dict(rank_max=rm.value, rank=r.value, logdet_p=ld.value, residual_trace=rt.value, t_max=tm.value)
 
 	def factor(self) -> dict:
-		"""{pivots, L, G, eig} as the device holds them (slq_kernel_precond_get): pivots (rank_max, -1 beyond the rank), L (n x
-		rank_max), G (rank_max x rank_max), the eigenvalues of L^T L."""
+		"""{pivots, L, G, eig, H} as the device holds them (slq_kernel_precond_get, slq_debug_kernel_precond_h): pivots (rank_max, -1
+		beyond the rank), L (n x rank_max), G and H = (L^T L + noise I)^-1 (rank_max x rank_max), the eigenvalues of L^T L."""
 		self._need_precond("factor")
 		r, n = self.info()["rank_max"], self.shape[0]
 		piv, Lf, G, eig = np.empty(r, dtype=np.int32), np.empty((n, r), order="F"), np.empty((r, r)), np.empty(r)
 		check(_capi.lib().slq_kernel_precond_get(self._h, ptr(piv), ptr(Lf), n, ptr(G), ptr(eig)))
-		return dict(pivots=piv, L=Lf, G=G, eig=eig)
+		H = np.empty((r, r))
+		check(_capi.lib().slq_debug_kernel_precond_h(self._h, ptr(H)))
+		return dict(pivots=piv, L=Lf, G=G, eig=eig, H=H)
 
 	def inv_sqrt(self, X: np.ndarray) -> np.ndarray:
 		"""P^{-1/2} X for a host array (slq_kernel_precond_apply)."""
@@ -319,6 +321,18 @@ class DeviceOperator:
 		"""OUT[:, o0:o0+b] = P^{-1/2} IN[:, i0:i0+b] between DeviceMatrix columns, asynchronous on the context stream."""
 		self._need_precond("inv_sqrt_dmat")
 		check(_capi.lib().slq_kernel_precond_apply_dmat(self._h, IN._h, int(i0), OUT._h, int(o0), int(b)))
+
+	def factor_columns(self, which: int, c0: int, nc: int, OUT: "DeviceMatrix", o0: int = 0) -> None:
+		"""OUT[:, o0:o0+nc] = columns [c0, c0 + nc) of L (which = 0: a copy) or of L H (which = 1: on the matrix cores), nc <= 64
+		(slq_kernel_precond_columns): the factor as operand columns of a KernelGradAccumulator. Asynchronous."""
+		self._need_precond("factor_columns")
+		check(_capi.lib().slq_kernel_precond_columns(self._h, int(which), int(c0), int(nc), OUT._h, int(o0)))
+
+	def precond_trace_grad(self, acc: "KernelGradAccumulator", alpha: float = 1.0, beta: float = 0.0) -> None:
+		"""acc's values = beta * values + alpha * tr(P^-1 dA/dtheta), exactly (slq_kernel_precond_trace_grad): `acc` is an accumulator
+		on this operator's BASE. Deterministic, asynchronous; acc's column count is unchanged."""
+		self._need_precond("precond_trace_grad")
+		check(_capi.lib().slq_kernel_precond_trace_grad(self._h, acc._h, float(alpha), float(beta)))
 
 	def factor_timing(self) -> dict:
 		"""Wall time of the last factorisation in ms: device_ms (the launches up to the synchronisation), host_ms (Jacobi, G, its upload)."""

@@ -1,4 +1,5 @@
-"""Gaussian-process prediction and log-determinants on the matrix-free kernel operator.
+"""Gaussian-process prediction, log-determinants and the marginal likelihood with its gradients on the matrix-free kernel operator
+(DESIGN.md §4.17, §4.18, §4.19).
 
 With A = K + noise I the operator of a `KernelOperator` on the training points X, C = outputscale * phi(r2(X*, X)) the
 cross-covariance to new points X* (`KernelOperator.cross`, engine.KernelCross) and s the outputscale,
@@ -12,12 +13,18 @@ With a pivoted-Cholesky preconditioner (`KernelOperator.preconditioned`, §4.18)
 which is what `logdet` computes and what `posterior(precond_rank > 0)` solves with: the path for small noise, where Lanczos on A
 itself does not converge in any affordable number of steps.
 
+`logdet_grad` and `mll` (§4.19) differentiate through the same split: tr(A^-1 dA/dtheta) = tr(P^-1 dA/dtheta), exact from the factor,
+plus a sampled remainder on B. What they return is the gradient of logdet A and of the marginal likelihood themselves - an unbiased
+estimate for any factor - NOT the derivative of the sampled value; the factor is never differentiated.
+
 Neither A nor C is ever formed: A^-1 is the Lanczos action `fun_action_into(..., "inv")` of a kept-basis plan over the device
 operator, C and C^T are the cross-covariance products, and the contraction C A^-1 C^T of a batch is `DeviceMatrix.tn`.
 """
 
 from __future__ import annotations
 
+import contextlib
+import time
 from typing import Optional
 
 import numpy as np
@@ -39,6 +46,22 @@ def _prior_block(K, zs: np.ndarray) -> np.ndarray:
 def _finite(a: np.ndarray, what: str, rtol: float) -> None:
 	if not np.all(np.isfinite(a)):
 		raise FloatingPointError(f"posterior: {what} is not finite" + (f" (rtol = {rtol} > 0 lets probes stop early, which the 'inv' action does not survive: use rtol = 0)" if rtol > 0 else ""))
+
+
+def _solve_into(pop, plan, RHS, OUT, b: int, tmp, rtol: float = 0.0) -> None:
+	"""OUT[:, :b] = A^-1 RHS[:, :b] by the kept-basis `plan`: on A's own operator (pop None), or on the preconditioned operator `pop`
+	as M B^-1 M - M applied on the device to the right-hand sides before they become the plan's probes and to the action's result.
+	tmp: two n x b DeviceMatrix of scratch for the preconditioned path."""
+	if pop is None:
+		plan.set_probes_device(RHS.col_ptr(0))
+		plan.run(rtol)
+		plan.fun_action_into(OUT, 0, "inv")
+		return
+	pop.inv_sqrt_dmat(RHS, 0, tmp[0], 0, b)
+	plan.set_probes_device(tmp[0].col_ptr(0))
+	plan.run(rtol)
+	plan.fun_action_into(tmp[1], 0, "inv")
+	pop.inv_sqrt_dmat(tmp[1], 0, OUT, 0, b)
 
 
 def logdet(K, rank: int = 100, deg: int = 20, count: int = 64, batch: int = 64, pdf: str = "device:rademacher", seed=None) -> tuple:
@@ -139,17 +162,7 @@ def posterior(K, y, Xnew, deg: int = 60, orth: Optional[int] = None, rtol: float
 	solve_op = op if pop is None else pop
 
 	def solve_into(plan, RHS, OUT, b, tmp):
-		"""OUT[:, :b] = A^-1 RHS[:, :b] by `plan` (on solve_op); tmp: two n x b DeviceMatrix of scratch for the preconditioned path."""
-		if pop is None:
-			plan.set_probes_device(RHS.col_ptr(0))
-			plan.run(rtol)
-			plan.fun_action_into(OUT, 0, "inv")
-			return
-		pop.inv_sqrt_dmat(RHS, 0, tmp[0], 0, b)
-		plan.set_probes_device(tmp[0].col_ptr(0))
-		plan.run(rtol)
-		plan.fun_action_into(tmp[1], 0, "inv")
-		pop.inv_sqrt_dmat(tmp[1], 0, OUT, 0, b)
+		_solve_into(pop, plan, RHS, OUT, b, tmp, rtol)
 
 	def keep(obj):
 		live.append(obj)
@@ -227,3 +240,316 @@ def posterior(K, y, Xnew, deg: int = 60, orth: Optional[int] = None, rtol: float
 	finally:
 		for obj in reversed(live):
 			obj.close()
+
+
+## ---- the gradient of logdet A through the preconditioner, and the marginal likelihood ---------------------------
+CONTROL_VARIATE_RITZ_MAX = 2.0  # B >= I, and |1 / lam - 1| <= 1 / lam exactly when lam <= 2: beyond it subtracting w makes a probe's term larger
+
+
+def control_variate_auto(ritz_max: float) -> bool:
+	"""The `control_variate="auto"` rule: on iff the largest Ritz value of B over the probes of the first batch is at most 2."""
+	return bool(ritz_max <= CONTROL_VARIATE_RITZ_MAX)
+
+
+def ritz_max(alpha: np.ndarray, beta: np.ndarray, steps: np.ndarray) -> float:
+	"""The largest eigenvalue of the Lanczos tridiagonals of `LanczosPlan.tridiag()` (alpha, beta: nprobes x (deg + 1), beta[:, 0] = 0;
+	steps: the steps each probe took), on the host."""
+	top = -np.inf
+	for a, b, k in zip(np.asarray(alpha, dtype=np.float64), np.asarray(beta, dtype=np.float64), np.asarray(steps).astype(int)):
+		if k < 1:
+			continue
+		T = np.diag(a[:k]) + np.diag(b[1:k], 1) + np.diag(b[1:k], -1)
+		top = max(top, float(np.linalg.eigvalsh(T)[-1]))
+	return top
+
+
+class _Phases:
+	"""Wall time per named phase, each closed by a stream synchronisation (scripts/bench_gp_mll.py); off: no synchronisation at all."""
+
+	def __init__(self, ctx, on: bool):
+		self.ctx, self.on, self.ms = ctx, bool(on), {}
+
+	def __call__(self, name: str):
+		@contextlib.contextmanager
+		def span():
+			if not self.on:
+				yield
+				return
+			self.ctx.synchronize()
+			t = time.perf_counter()
+			try:
+				yield
+			finally:
+				self.ctx.synchronize()
+				self.ms[name] = self.ms.get(name, 0.0) + 1e3 * (time.perf_counter() - t)
+
+		return span()
+
+
+def _kernel_and_precond(K, rank: int, who: str):
+	"""(the base KernelOperator, the PreconditionedKernelOperator or None): K is either; a preconditioned operator brings its own rank."""
+	kind = getattr(K, "_slq_kind", None)
+	if kind == "kernel_precond":
+		base, B = K.base, K
+	elif kind == "kernel":
+		base, B = K, (K.preconditioned(rank) if rank > 0 else None)
+	else:
+		raise ValueError(f"{who} needs a KernelOperator (or its preconditioned(rank))")
+	if np.dtype(base.dtype) != np.float64:
+		raise ValueError(f"{who} is fp64 only: the KernelOperator is {np.dtype(base.dtype)}")
+	return base, B
+
+
+def _batches(count: int, batch: int, probes, n: int, who: str):
+	"""(nb, batch, probes as float64 or None): whole batches of equal size, as `logdet` cuts them; explicit probes must fill them."""
+	nb = -(-count // batch)
+	batch = -(-count // nb)
+	if probes is not None:
+		V = np.asarray(probes, dtype=np.float64)
+		if V.ndim != 2 or V.shape[0] != n or V.shape[1] != nb * batch:
+			raise ValueError(f"{who}: probes must be an n x count array of whole batches ({n} x {nb * batch}), got {V.shape}")
+		return nb, batch, V
+	return nb, batch, None
+
+
+def _logdet_grad(base, B, deg: int, count: int, batch: int, pdf, seed, probes, control_variate, phases=None) -> tuple:
+	"""(value, vals, info) with vals the d + 2 raw gradient values of logdet A; `logdet_grad` behind its argument checks (rank > 0)."""
+	from .estimators import MeanEstimator
+	from .grad import _probe_loader
+	from .operators import MatrixFunction
+
+	if control_variate not in ("auto", True, False):
+		raise ValueError(f"control_variate = {control_variate!r} (one of 'auto', True, False)")
+	n = int(base.shape[0])
+	op = _as_device_operator(base, dtype=np.float64)
+	pop = _as_device_operator(B, dtype=np.float64)  # (refreshes lazily when the base's hyperparameters have changed)
+	ctx = op.ctx
+	phases = phases or _Phases(ctx, False)
+	nb, batch, V = _batches(count, batch, probes, n, "logdet_grad")
+	total = nb * batch
+	load = _probe_loader(pdf, seed, V, n, total, False)
+	M = MatrixFunction(B, fun="log", deg=deg, dtype=np.float64)
+	pinfo = pop.info()
+	estimator = MeanEstimator(covariance=True, record=True)
+	live = []
+	try:
+		acc = engine.KernelGradAccumulator(op)
+		live.append(acc)
+		W, Vm, T, U = (engine.DeviceMatrix(n, batch, ctx=ctx) for _ in range(4))
+		live.extend((W, Vm, T, U))
+		exact = None
+		use_cv, top = (None if control_variate == "auto" else bool(control_variate)), None
+		per_batch = []
+		eye = np.eye(batch)
+		for j in range(nb):
+			with phases("lanczos"):
+				plan = M._plan(batch, True)
+				load(plan, j * batch, batch)
+				plan.get_probes_into(W, 0)
+				plan.run(M._rtol)
+				estimator.update(plan.quadrature("log"))
+				plan.fun_action_into(T, 0, "inv")
+			if j == 0:  # the decision, before this batch's update; held for the whole call
+				top = ritz_max(*plan.tridiag())
+				if use_cv is None:
+					use_cv = control_variate_auto(top)
+			with phases("applies"):
+				pop.inv_sqrt_dmat(W, 0, Vm, 0, batch)
+				if use_cv:
+					T.add_product(0, W, 0, eye, alpha=-1.0, beta=1.0)
+				pop.inv_sqrt_dmat(T, 0, U, 0, batch)
+			with phases("updates"):
+				acc.update(U, 0, Vm, 0, batch, alpha=1.0 / batch, beta=0.0)
+				per_batch.append(acc.get()[0])
+		if use_cv:
+			with phases("exact"):
+				pop.precond_trace_grad(acc, alpha=1.0, beta=0.0)
+				exact = acc.get()[0]
+		per_batch = np.array(per_batch)
+		if not np.all(np.isfinite(per_batch)):
+			raise FloatingPointError("logdet_grad: the sampled gradient is not finite: a probe's Lanczos run stopped before `deg` steps (B is so close to the identity that its Krylov space is exhausted), which the 'inv' action does not survive: lower deg or rank")
+		vals = per_batch.mean(axis=0) + (exact if exact is not None else 0.0)
+		qv = np.asarray(estimator.values, dtype=np.float64).ravel()
+		est = float(estimator.estimate)
+		info = dict(rank=int(pinfo["rank"]), logdet_precond=float(pinfo["logdet_p"]), trace=est, count=int(qv.size), deg=deg,
+					std_error=float(np.std(qv, ddof=1) / np.sqrt(qv.size)), control_variate=bool(use_cv), ritz_max=float(top),
+					grad_exact_values=exact, grad_per_batch=per_batch, batches=nb)  # fmt: skip
+		return est + float(pinfo["logdet_p"]), vals, info
+	finally:
+		if hasattr(M, "close"):
+			M.close()
+		for obj in reversed(live):
+			obj.close()
+
+
+def _fold(base, vals) -> np.ndarray:
+	"""(..., d + 2) raw values to (..., p + 2) shaped like the parameters: a scalar lengthscale's value is the sum over the dimensions."""
+	d = base.X.shape[1]
+	vals = np.asarray(vals, dtype=np.float64)
+	if np.size(base.lengthscale) == 1:
+		return np.concatenate([vals[..., :d].sum(axis=-1, keepdims=True), vals[..., d:]], axis=-1)
+	return vals
+
+
+def _as_params(base, f: np.ndarray) -> dict:
+	p = f.size - 2
+	return dict(lengthscale=np.array(f[:p], dtype=np.float64).reshape(np.shape(base.lengthscale)), outputscale=float(f[p]), noise=float(f[p + 1]))
+
+
+def _shape_grad_info(base, info: dict, scale: float = 1.0) -> dict:
+	"""The raw entries of `_logdet_grad`'s info as dicts shaped like the parameters: grad_exact, and grad_std_error from the per-batch
+	means folded to the parameters' shape first (the error of a scalar lengthscale's summed gradient is that of the sums)."""
+	ex, pb = info.pop("grad_exact_values"), info.pop("grad_per_batch")
+	info["grad_exact"] = None if ex is None else _as_params(base, scale * _fold(base, ex))
+	nb = pb.shape[0]
+	info["grad_std_error"] = None if nb < 2 else _as_params(base, abs(scale) * _fold(base, pb).std(axis=0, ddof=1) / np.sqrt(nb))
+	return info
+
+
+def logdet_grad(K, rank: int = 100, deg: int = 20, count: int = 64, batch: int = 16, pdf: str = "device:rademacher", seed=None, probes=None,
+				control_variate="auto") -> tuple:  # fmt: skip
+	"""(value, grads, info): log det A of the KernelOperator `K` (A = K0 + noise I, float64) as `logdet` estimates it, and the
+	gradient of log det A with respect to the hyperparameters,
+
+	    grads = dict(lengthscale=array shaped like K.lengthscale, outputscale=float, noise=float) ~ tr(A^-1 dA/dtheta),
+
+	through the pivoted-Cholesky preconditioner. With M = P^{-1/2}, B = M A M and probes w,
+
+	    tr(A^-1 D) = tr(P^-1 D) + E_w[(M (B^-1 - I) w)^T D (M w)]     control variate on
+	               =              E_w[(M  B^-1      w)^T D (M w)]     off
+
+	both unbiased for any factor. tr(P^-1 D) is exact and deterministic, from the factor's columns on the device
+	(`DeviceOperator.precond_trace_grad`); the expectation is sampled with the probes of the value, B^-1 w being the "inv" action of
+	the same Lanczos run whose quadrature is the value. This is the gradient of logdet A itself, NOT the derivative of the sampled
+	value, and the factor P is not differentiated.
+
+	K: a KernelOperator (a factor of rank `rank` is built), or a `K.preconditioned(rank)` kept by the caller, whose factor is refreshed
+	only when K's hyperparameters have changed - the form for a training loop. rank = 0: `kernel_trace_grad` on A itself.
+	count, batch: `count` probes in whole batches of equal size, cut as `logdet` cuts them. probes: a host n x count array instead of
+	`pdf` (count must then be whole batches). control_variate: True, False, or "auto": on iff the largest Ritz value of B over the
+	probes of the FIRST batch (from the plan's tridiagonals, on the host) is <= 2 - B >= I, and |1 / lam - 1| <= 1 / lam exactly when
+	lam <= 2; with a poor factor the control variate makes the variance larger. The decision is taken before the first batch's update
+	and holds for the whole call.
+	info: logdet's (rank, logdet_precond, trace, std_error, count, deg), control_variate (the decision), ritz_max, grad_exact (the
+	deterministic part shaped like grads; None with the control variate off), grad_std_error (per component, the sample standard
+	deviation of the per-batch means over sqrt(batches); None with fewer than 2 batches), batches."""
+	from .grad import _kernel_grads
+
+	rank, deg, count, batch = int(rank), int(deg), int(count), int(batch)
+	if rank < 0 or deg < 1 or count < 2 or batch < 1:
+		raise ValueError(f"rank = {rank} must be >= 0, deg = {deg} and batch = {batch} >= 1, count = {count} >= 2")
+	base, B = _kernel_and_precond(K, rank, "logdet_grad")
+	if probes is not None and np.asarray(probes).ndim == 2:
+		count = int(np.asarray(probes).shape[1])
+	if B is None:
+		from .grad import kernel_trace_grad
+		from .operators import MatrixFunction
+
+		M = MatrixFunction(base, fun="log", deg=deg, dtype=np.float64)
+		try:
+			est, grads, ginfo = kernel_trace_grad(M, pdf=pdf, count=count, batch=batch, seed=seed, probes=probes)
+		finally:
+			if hasattr(M, "close"):
+				M.close()
+		q = np.asarray(ginfo["quad"], dtype=np.float64)
+		info = dict(rank=0, logdet_precond=0.0, trace=float(est), count=int(q.size), deg=deg, std_error=float(np.std(q, ddof=1) / np.sqrt(q.size)),
+					control_variate=False, ritz_max=None, grad_exact=None, grad_std_error=None, batches=-(-count // batch))  # fmt: skip
+		return float(est), grads, info
+	value, vals, info = _logdet_grad(base, B, deg, count, batch, pdf, seed, probes, control_variate)
+	return value, _kernel_grads(base, vals), _shape_grad_info(base, info)
+
+
+def _params_vec(grads: dict) -> np.ndarray:
+	return np.concatenate([np.ravel(np.asarray(grads["lengthscale"], dtype=np.float64)), [float(grads["outputscale"])], [float(grads["noise"])]])
+
+
+def mll(K, y, rank: int = 100, deg: int = 20, solve_deg: Optional[int] = None, count: int = 64, batch: int = 16, pdf: str = "device:rademacher",
+		seed=None, probes=None, control_variate="auto", profile: bool = False) -> tuple:  # fmt: skip
+	"""(value, grads, info): the marginal log-likelihood of a zero-mean Gaussian process with the kernel operator `K` (A = K0 + noise I,
+	float64) for the observations `y` ((n,) or (n, q): q independent outputs sharing A), and its gradient with respect to the
+	hyperparameters, shaped as `logdet_grad`'s:
+
+	    value = -1/2 sum_q y_q^T alpha_q - (q / 2) logdet A - (n q / 2) log 2 pi,        alpha = A^-1 y,
+	    grads =  1/2 sum_q alpha_q^T (dA/dtheta) alpha_q - (q / 2) tr(A^-1 dA/dtheta).
+
+	alpha = M B^-1 M y comes from one kept-basis plan of `solve_deg` steps (None: deg) on the preconditioned operator, as in
+	`posterior`; the data-fit gradient is ONE KernelGradAccumulator update on alpha, which never leaves the device; logdet A and
+	tr(A^-1 dA/dtheta) are `logdet_grad`'s (rank, deg, count, batch, pdf, seed, probes, control_variate go there). The data-fit part
+	is deterministic, the log-determinant part sampled: the gradient is that of the marginal likelihood itself - unbiased for any
+	factor -, not the derivative of the sampled value. A zero column of `y` contributes only its log-determinant terms.
+	K: a KernelOperator, or its `preconditioned(rank)` kept by the caller (refreshed only when the hyperparameters have changed).
+	rank = 0: everything on A itself (for large noise).
+	info: datafit and datafit_grad (-1/2 sum y^T alpha and its gradient), logdet and logdet_grad (the log-determinant and its
+	gradient, unscaled), logdet_info (`logdet_grad`'s info), grad_std_error (of grads: q / 2 times logdet_grad's), steps (of the
+	solve), q, zero_columns; with profile=True also timing_ms: wall time per phase, each closed by a synchronisation - refresh (the
+	factor), solve, lanczos (the batches' runs, quadratures and actions), applies (M on the probes and the actions), updates (the
+	accumulator, with its readback per batch), exact (tr(P^-1 dA/dtheta)), datafit (its update)."""
+	from .grad import _kernel_grads
+
+	rank, deg, count, batch = int(rank), int(deg), int(count), int(batch)
+	if rank < 0 or deg < 1 or count < 2 or batch < 1:
+		raise ValueError(f"rank = {rank} must be >= 0, deg = {deg} and batch = {batch} >= 1, count = {count} >= 2")
+	solve_deg = deg if solve_deg is None else int(solve_deg)
+	if solve_deg < 1:
+		raise ValueError(f"solve_deg = {solve_deg} must be >= 1")
+	base, B = _kernel_and_precond(K, rank, "mll")
+	n = int(base.shape[0])
+	yh = np.asarray(y, dtype=np.float64)
+	yh = yh.reshape(-1, 1) if yh.ndim == 1 else yh
+	if yh.ndim != 2 or yh.shape[0] != n or yh.shape[1] < 1:
+		raise ValueError(f"y must be ({n},) or ({n}, q), got shape {np.asarray(y).shape}")
+	if not np.all(np.isfinite(yh)):
+		raise ValueError("y must be finite")
+	q = int(yh.shape[1])
+	op = _as_device_operator(base, dtype=np.float64)
+	ctx = op.ctx
+	phases = _Phases(ctx, profile)
+	with phases("refresh"):
+		pop = _as_device_operator(B, dtype=np.float64) if B is not None else None
+	solve_op = op if pop is None else pop
+	nz = np.flatnonzero(np.any(yh != 0.0, axis=0))
+	live = []
+	fit, fit_vals, steps = 0.0, np.zeros(base.X.shape[1] + 2), None
+	try:
+		if nz.size:
+			m = int(nz.size)
+			with phases("solve"):
+				plan = engine.LanczosPlan(solve_op, m, solve_deg, -1, basis="keep")
+				live.append(plan)
+				Yd, Alpha = engine.DeviceMatrix(n, m, ctx=ctx), engine.DeviceMatrix(n, m, ctx=ctx)
+				live.extend((Yd, Alpha))
+				Yd.set(0, np.asfortranarray(yh[:, nz]))
+				tmp = None
+				if pop is not None:
+					tmp = (engine.DeviceMatrix(n, m, ctx=ctx), engine.DeviceMatrix(n, m, ctx=ctx))
+					live.extend(tmp)
+				_solve_into(pop, plan, Yd, Alpha, m, tmp, 0.0)
+				steps = plan.steps_done
+				fit = float(np.trace(Yd.tn(0, m, Alpha, 0, m)))
+			if not np.isfinite(fit):
+				raise FloatingPointError("mll: y^T A^-1 y is not finite")
+			with phases("datafit"):
+				acc = engine.KernelGradAccumulator(op)
+				live.append(acc)
+				acc.update(Alpha, 0, Alpha, 0, m, alpha=0.5, beta=0.0)
+				fit_vals = acc.get()[0]
+	finally:
+		for obj in reversed(live):
+			obj.close()
+	if B is None:
+		ld, ld_grads, ld_info = logdet_grad(base, rank=0, deg=deg, count=count, batch=batch, pdf=pdf, seed=seed, probes=probes)
+	else:
+		if probes is not None and np.asarray(probes).ndim == 2:
+			count = int(np.asarray(probes).shape[1])
+		ld, ld_vals, ld_info = _logdet_grad(base, B, deg, count, batch, pdf, seed, probes, control_variate, phases)
+		ld_grads, ld_info = _kernel_grads(base, ld_vals), _shape_grad_info(base, ld_info)
+	fit_grads = _kernel_grads(base, fit_vals)
+	total = _params_vec(fit_grads) - 0.5 * q * _params_vec(ld_grads)
+	value = -0.5 * fit - 0.5 * q * ld - 0.5 * n * q * float(np.log(2.0 * np.pi))
+	se = ld_info.get("grad_std_error")
+	info = dict(datafit=-0.5 * fit, datafit_grad=fit_grads, logdet=ld, logdet_grad=ld_grads, logdet_info=ld_info, steps=steps, q=q,
+				zero_columns=[int(c) for c in np.setdiff1d(np.arange(q), nz)],
+				grad_std_error=None if se is None else _as_params(base, 0.5 * q * _params_vec(se)))  # fmt: skip
+	if profile:
+		info["timing_ms"] = dict(phases.ms)
+	return value, _as_params(base, total), info

@@ -153,7 +153,7 @@ def trace_grad(M, pdf: Union[str, None] = "rademacher", count: int = 256, batch:
 	if not isinstance(M, (MatrixFunction, ChebyshevFunction)):
 		raise ValueError("trace_grad takes a MatrixFunction or a ChebyshevFunction")
 	if getattr(getattr(M, "_A", None), "_slq_kind", None) == "kernel_precond" or getattr(getattr(M, "_op", None), "kind", None) == "kernel_precond":
-		raise ValueError("trace_grad: a preconditioned kernel operator has no stored entries, and gradients through the preconditioner are not built")
+		raise ValueError("trace_grad: a preconditioned kernel operator has no stored entries: the hyperparameter gradients through the preconditioner are gp.logdet_grad's")
 	if getattr(getattr(M, "_A", None), "_slq_kind", None) == "kernel" or getattr(getattr(M, "_op", None), "kind", None) == "kernel":
 		raise ValueError("trace_grad: a KernelOperator has no stored entries; its hyperparameter gradients come from kernel_trace_grad")
 	if np.dtype(M.dtype) != np.float64:
@@ -274,7 +274,7 @@ def kernel_trace_grad(M, pdf: Union[str, None] = "rademacher", count: int = 256,
 		raise ValueError("kernel_trace_grad takes a MatrixFunction or a ChebyshevFunction")
 	K = getattr(M, "_A", None)
 	if getattr(K, "_slq_kind", None) == "kernel_precond":
-		raise ValueError("kernel_trace_grad: gradients through the pivoted-Cholesky preconditioner are not built: differentiate the function of the base KernelOperator")
+		raise ValueError("kernel_trace_grad: the function of a preconditioned operator is not differentiated here: the gradient of logdet A through the pivoted-Cholesky preconditioner is gp.logdet_grad (gp.mll for the marginal likelihood)")
 	if getattr(K, "_slq_kind", None) != "kernel":
 		raise ValueError("kernel_trace_grad needs a function of a KernelOperator (for the gradient on a sparsity pattern use trace_grad)")
 	if np.dtype(M.dtype) != np.float64 or np.dtype(K.dtype) != np.float64:
@@ -344,7 +344,7 @@ def kernel_quadratic_grad(K, U, V=None) -> dict:
 	from .lanczos import _as_device_operator
 
 	if getattr(K, "_slq_kind", None) == "kernel_precond":
-		raise ValueError("kernel_quadratic_grad: gradients through the pivoted-Cholesky preconditioner are not built: pass the base KernelOperator")
+		raise ValueError("kernel_quadratic_grad: pass the base KernelOperator, not its preconditioner (the data-fit gradient of a marginal likelihood through the preconditioner is part of gp.mll; gp.logdet_grad has the log-determinant's)")
 	if getattr(K, "_slq_kind", None) != "kernel":
 		raise ValueError("kernel_quadratic_grad needs a KernelOperator")
 	if np.dtype(K.dtype) != np.float64:

@@ -357,6 +357,22 @@ def _kernel_profile(name: str, r2: np.ndarray) -> np.ndarray:
 	return (1.0 + a + (5.0 / 3.0) * r2) * np.exp(-a)
 
 
+def _kernel_chi(name: str, r2: np.ndarray) -> np.ndarray:
+	"""chi = -2 dphi/dr2 of the four profiles; matern12's exp(-r) / r is DEFINED 0 at r2 = 0, as on the device."""
+	if name == "rbf":
+		return np.exp(-0.5 * r2)
+	r = np.sqrt(r2)
+	if name == "matern12":
+		out = np.zeros_like(r2)
+		pos = r2 > 0
+		out[pos] = np.exp(-r[pos]) / r[pos]
+		return out
+	if name == "matern32":
+		return 3.0 * np.exp(-np.sqrt(3.0) * r)
+	a = np.sqrt(5.0) * r
+	return (5.0 / 3.0) * (1.0 + a) * np.exp(-a)
+
+
 class KernelOperator(LinearOperator):
 	"""The kernel matrix of n points in d dimensions, never formed: with z_i = (x_i - mean(x)) / lengthscale rounded to `dtype`
 	(the operator is DEFINED on these z), r2_ij = max(0, |z_i|^2 + |z_j|^2 - 2 z_i.z_j) (0 on the diagonal) and phi the profile
@@ -543,7 +559,7 @@ class PreconditionedKernelOperator(LinearOperator):
 		return K.outputscale * _kernel_profile(K.kernel, r2)
 
 	def host_model(self) -> dict:
-		"""{L, pivots, d, t, V, G, logdet_p} by the definition, for the base's parameters of now (cached per parameter set)."""
+		"""{L, pivots, d, t, V, G, H, logdet_p} by the definition, for the base's parameters of now (cached per parameter set)."""
 		if self._model is not None and self._model_key == self._key():
 			return self._model
 		K = self.base
@@ -568,7 +584,8 @@ class PreconditionedKernelOperator(LinearOperator):
 		t, V = np.linalg.eigh(L.T @ L)
 		t = np.maximum(t, 0.0)
 		G = (V * precond_g(t, sigma2)) @ V.T
-		self._model = dict(L=L, pivots=np.array(piv, dtype=np.int64), d=d, t=t, V=V, G=G, logdet_p=float(np.sum(np.log1p(t / sigma2)) + n * np.log(sigma2)))
+		H = (V / (t + sigma2)) @ V.T  # (L^T L + sigma2 I)^-1: P^-1 = (I - L H L^T) / sigma2 (§4.19)
+		self._model = dict(L=L, pivots=np.array(piv, dtype=np.int64), d=d, t=t, V=V, G=G, H=H, logdet_p=float(np.sum(np.log1p(t / sigma2)) + n * np.log(sigma2)))
 		self._model_key = self._key()
 		return self._model
 
@@ -587,6 +604,35 @@ class PreconditionedKernelOperator(LinearOperator):
 	@property
 	def residual_trace(self) -> float:
 		return float(np.sum(self.host_model()["d"]))
+
+	def trace_grad_exact(self, L: Optional[np.ndarray] = None, H: Optional[np.ndarray] = None) -> np.ndarray:
+		"""tr(P^-1 dA/dtheta) as d + 2 values - the lengthscales per dimension, the outputscale, the noise, as a
+		KernelGradAccumulator holds them - in float64 NumPy from the definition: with C = (L H) L^T
+
+		    sigma^-2 [tr D - sum_ij C_ij D_ij],   D_lk = (s / l_k) chi(r2) (z_ik - z_jk)^2,  D_s = phi(r2),  D_sigma2 = I,
+
+		tr D = 0, n, n. L, H: the host model's (None), or another factor's - the device's, for the tests. This is the exact part of
+		the gradient of logdet A that `gp.logdet_grad` adds its sampled remainder to; P itself is not differentiated."""
+		m = self.host_model() if L is None or H is None else None
+		L = m["L"] if L is None else np.asarray(L, dtype=np.float64)
+		H = m["H"] if H is None else np.asarray(H, dtype=np.float64)
+		K = self.base
+		n, d = K.X.shape
+		s, sigma2 = float(K.outputscale), float(K.noise)
+		ls = np.broadcast_to(np.asarray(K.lengthscale, dtype=np.float64), (d,))
+		z = K.scaled_points().astype(np.float64)
+		nrm = np.einsum("ij,ij->i", z, z)
+		r2 = np.maximum(nrm[:, None] + nrm[None, :] - 2.0 * (z @ z.T), 0.0)
+		np.fill_diagonal(r2, 0.0)
+		Cm = (L @ H) @ L.T
+		Bm = Cm * _kernel_chi(K.kernel, r2)
+		out = np.zeros(d + 2)
+		for k in range(d):
+			D = z[:, k][:, None] - z[None, :, k]
+			out[k] = -(s / ls[k]) * np.sum(Bm * D * D) / sigma2
+		out[d] = (n - np.sum(Cm * _kernel_profile(K.kernel, r2))) / sigma2
+		out[d + 1] = (n - np.trace(Cm)) / sigma2
+		return out
 
 	def inv_sqrt(self, X: np.ndarray) -> np.ndarray:
 		"""P^{-1/2} X = (X - L G L^T X) / sigma."""

@@ -3,7 +3,10 @@ quadrature values of one seeded 256 x 30 run per operator. Two libraries that pr
 (r04: used to show that the device-side build, the stamp-based regrouping and the cached first-level Cuthill-McKee leave every result
 bitwise unchanged; later: that slq_layout.hpp does - the cases then cover the host builder, barrier tiles, a forced reorder without tiles, a
 random graph, creation from device arrays, an affine and a Gram operator; later still: that one tile walk for the kernel-operator
-family does - the "kernel ..." lines are sha256 of products, cross products and a gradient update themselves).   PRIMATE_AMD_LIBSLQ=<other library> python scripts/op_fingerprint.py"""
+family does - the "kernel ..." lines are sha256 of products, cross products and a gradient update themselves; --posterior: only the two
+"posterior ..." lines of tests/_gp_mll_ref.posterior_fingerprint_lines, sha256 of gp.posterior's mean and variance without and with the
+preconditioner - factoring its solve helper out for gp.mll leaves them as they were: profiles/gp_mll_posterior_fingerprint.txt).
+PRIMATE_AMD_LIBSLQ=<other library> python scripts/op_fingerprint.py [--posterior]"""
 import hashlib, sys, time
 from pathlib import Path
 import numpy as np
@@ -11,6 +14,12 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))
 from conftest import laplacian_2d, laplacian_3d
 from primate_amd import engine as eng
+
+if "--posterior" in sys.argv:
+	from _gp_mll_ref import posterior_fingerprint_lines
+	for line in posterior_fingerprint_lines():
+		print(line, flush=True)
+	sys.exit(0)
 
 def random_graph(n=500000, deg=16, seed=1234):  # (the pattern of scripts/time_create.py's random graph plus a dominant diagonal: no tiles, automatic reorder declined)
 	import scipy.sparse as sp
