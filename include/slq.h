@@ -611,6 +611,51 @@ int slq_kernel_precond_trace_grad(slq_operator *pre, slq_kernel_grad *grad, doub
  * rank_max steps and the Gram matrix -, out2[1] the host part: Jacobi, G and its upload (scripts/bench_kernelprecond.py). */
 int slq_debug_kernel_precond_timing(const slq_operator *pre, double *out2);
 
+/* ---- Gradients of the kernel operator with respect to the points (csrc/slq_kernelpointgrad.hpp), fp64 only ----
+ * Notation as for the hyperparameter gradients: z the operator's rounded scaled points, chi = -2 dphi/dr2 (matern12: 0 where
+ * r2 = 0), r2 the operator's own value - its operands, its order, its clamp and, on the training set, its diagonal rule.
+ * Training form (slq_kernel_pointgrad_create): for columns of two device matrices Z, W (n rows), C = Z W^T, one update adds the n x d
+ *   P[a][k] = sum_c Z_c^T (dA/dx_ak) W_c = -(s / l_k) sum_j (C_aj + C_ja) chi(r2_aj) (z_ak - z_jk).
+ * Cross form (slq_kernel_pointgrad_create_cross): for the m new points z* of a slq_kernel_cross (training centre, no diagonal rule),
+ *   U with m rows and W with n rows, the m x d
+ *   R[a][k] = -(s / l_k) sum_j (sum_c U_ac W_jc) chi(r2(z*_a, z_j)) (z*_ak - z_jk),
+ *   the gradient of sum_c U_c^T K(X*, X) W_c in the new points. P = R(Z, W) + R(W, Z) with both sets the training points: ONE
+ *   one-sided kernel, run twice per 64-column chunk in that order (once, with twice the weight, where Z and W are the same matrix and
+ *   column range). Centring drops out of a difference, so d/dx = (1 / l) d/dz exactly as written; the gradient is DEFINED as this
+ *   smooth formula at the rounded z. The coordinate term is taken as the difference z_ak - z_jk: coincident points contribute
+ *   exactly 0. Neither A nor C nor a derivative tile is held; nothing is atomic and the slab partials are added in slab order:
+ *   identical calls give identical bits.
+ * slq_kernel_pointgrad_create: op must be a kernel operator in fp64 of ctx (SLQ_EINVAL names the kind - a preconditioned operator
+ *   is "kernel_precond": pass its base - or the dtype). The accumulator reads op at every update and does not own it: destroy the
+ *   accumulator first. The values start at 0.
+ * slq_kernel_pointgrad_create_cross: borrows the cross object AND its operator (destroy the accumulator first); an fp32 cross
+ *   object is refused. After slq_kernel_set_parameters the z* are re-derived on the stream before the next update, as before a
+ *   cross product.
+ * slq_kernel_pointgrad_update: vals = beta * vals + alpha * (P or R over columns [c0, c0 + m) of Z_or_U and [w0, w0 + m) of W);
+ *   count += m. Columns go 64 to a launch; wider ranges fold in one after the other. Asynchronous on the context stream. beta == 0
+ *   does not read the old values. The operator's parameters are read as they are at the call (the contract of
+ *   slq_kernel_grad_update). SLQ_EINVAL, nothing launched and the values untouched: a NULL handle, a column range outside its
+ *   matrix, m < 1, a row count that does not fit the form (Z_or_U: n, or m new points; W: n), an object of another context, a
+ *   non-finite alpha or beta.
+ * slq_kernel_pointgrad_get: rows x d values, row-major like the points with leading dimension ld >= d, and the columns folded in so
+ *   far (either may be NULL). Synchronises.
+ * slq_kernel_pointgrad_reset: values and count back to 0 (asynchronous).
+ * slq_kernel_precond_trace_pointgrad: vals = beta vals + alpha tr(P^-1 dA/dx) = beta vals - alpha sigma^-2 sum_c (L H)_c^T (dA/dx) L_c
+ *   (tr dA/dx = 0), the columns of the rank reached 64 at a time through the matrices slq_kernel_precond_trace_grad uses. `grad`
+ *   must be a training-form accumulator on the BASE of `pre`; a stale preconditioner is refused. The column count is unchanged. */
+typedef struct slq_kernel_pointgrad slq_kernel_pointgrad;
+int slq_kernel_pointgrad_create(slq_context *ctx, slq_operator *op, slq_kernel_pointgrad **out);
+int slq_kernel_pointgrad_create_cross(slq_context *ctx, slq_kernel_cross *cross, slq_kernel_pointgrad **out);
+int slq_kernel_pointgrad_update(slq_kernel_pointgrad *g, slq_dmat *Z_or_U, int c0, slq_dmat *W, int w0, int m, double alpha, double beta);
+int slq_kernel_pointgrad_get(slq_kernel_pointgrad *g, double *vals, int64_t ld, int64_t *count);
+int slq_kernel_pointgrad_reset(slq_kernel_pointgrad *g);
+int slq_kernel_pointgrad_destroy(slq_kernel_pointgrad *g);
+int slq_kernel_precond_trace_pointgrad(slq_operator *pre, slq_kernel_pointgrad *grad, double alpha, double beta);
+/* The schedule of one pass with nrows row points and nsum summed points on a chip of num_cus compute units
+ * (csrc/slq_kernelpointgrad.hpp: kernel_pointgrad_schedule): rows per block, row blocks, factor columns per launch, slabs of the
+ * summed points (at most 64), tiles of 16 points per slab, then slab_begin[0 .. slabs] (-1 beyond); nout >= 70. No HIP call. */
+int slq_debug_kernel_pointgrad_schedule(int64_t nrows, int64_t nsum, int num_cus, int64_t *out, int nout);
+
 /* Per-kernel device time accumulated by HIP events on the context stream (for bench.py's
  * roofline line). enable != 0 turns event recording on for subsequent slq_plan_run calls. */
 enum {

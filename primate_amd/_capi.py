@@ -149,6 +149,14 @@ _SIGNATURES = {
 	"slq_debug_kernel_precond_h": (C.c_int, [_P, _P]),
 	"slq_kernel_precond_columns": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int]),
 	"slq_kernel_precond_trace_grad": (C.c_int, [_P, _P, C.c_double, C.c_double]),
+	"slq_kernel_pointgrad_create": (C.c_int, [_P, _P, _PP]),
+	"slq_kernel_pointgrad_create_cross": (C.c_int, [_P, _P, _PP]),
+	"slq_kernel_pointgrad_update": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_double, C.c_double]),
+	"slq_kernel_pointgrad_get": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+	"slq_kernel_pointgrad_reset": (C.c_int, [_P]),
+	"slq_kernel_pointgrad_destroy": (C.c_int, [_P]),
+	"slq_kernel_precond_trace_pointgrad": (C.c_int, [_P, _P, C.c_double, C.c_double]),
+	"slq_debug_kernel_pointgrad_schedule": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int]),
 	"slq_plan_profile_enable": (C.c_int, [_P, C.c_int]),
 	"slq_plan_action_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
 	"slq_plan_sweep_columns": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),

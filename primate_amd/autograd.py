@@ -61,7 +61,7 @@ class _TraceFun(torch.autograd.Function):
 
 class _KernelTraceFun(torch.autograd.Function):
 	@staticmethod
-	def forward(ctx, lengthscale, outputscale, noise, X, opts):
+	def forward(ctx, lengthscale, outputscale, noise, X, opts, Xt=None):
 		from .chebyshev import ChebyshevFunction
 		from .grad import kernel_trace_grad
 		from .operators import KernelOperator, MatrixFunction
@@ -75,23 +75,27 @@ class _KernelTraceFun(torch.autograd.Function):
 						   noise=float(noise), dtype="float64")  # fmt: skip
 		M = (MatrixFunction if method == "lanczos" else ChebyshevFunction)(K, fun, deg=deg, **o)
 		try:
-			est, grads, _ = kernel_trace_grad(M, count=count, seed=seed, **tg)
+			est, grads, _ = kernel_trace_grad(M, count=count, seed=seed, points=Xt is not None, **tg)
 		finally:
 			if hasattr(M, "close"):
 				M.close()
 		G = [torch.as_tensor(grads[k], dtype=p.dtype, device=p.device).reshape(p.shape)
 			 for k, p in (("lengthscale", lengthscale), ("outputscale", outputscale), ("noise", noise))]  # fmt: skip
+		ctx.with_points = Xt is not None
+		if ctx.with_points:  # (Xt: the points as the tensor that asked for a gradient; X carries the same values)
+			G.append(torch.as_tensor(grads["points"], dtype=Xt.dtype, device=Xt.device).reshape(Xt.shape))
 		ctx.save_for_backward(*G)
 		return lengthscale.new_tensor(est)
 
 	@staticmethod
 	def backward(ctx, grad_output):
-		return tuple(grad_output.to(G.device) * G for G in ctx.saved_tensors) + (None, None)
+		out = tuple(grad_output.to(G.device) * G for G in ctx.saved_tensors)
+		return out[:3] + (None, None) + ((out[3],) if ctx.with_points else (None,))
 
 
 class _GpMllFun(torch.autograd.Function):
 	@staticmethod
-	def forward(ctx, lengthscale, outputscale, noise, X, y, opts):
+	def forward(ctx, lengthscale, outputscale, noise, X, y, opts, Xt=None):
 		from .gp import mll
 		from .operators import KernelOperator
 
@@ -100,24 +104,32 @@ class _GpMllFun(torch.autograd.Function):
 		## an operator of its own on every call: its parameters changed, which is the point
 		K = KernelOperator(X, kernel, lengthscale=lengthscale.detach().cpu().numpy().astype("float64"), outputscale=float(outputscale),
 						   noise=float(noise), dtype="float64")  # fmt: skip
-		value, grads, _ = mll(K, y, **o)
+		value, grads, _ = mll(K, y, points=Xt is not None, **o)
 		G = [torch.as_tensor(grads[k], dtype=p.dtype, device=p.device).reshape(p.shape)
 			 for k, p in (("lengthscale", lengthscale), ("outputscale", outputscale), ("noise", noise))]  # fmt: skip
+		ctx.with_points = Xt is not None
+		if ctx.with_points:
+			G.append(torch.as_tensor(grads["points"], dtype=Xt.dtype, device=Xt.device).reshape(Xt.shape))
 		ctx.save_for_backward(*G)
 		return lengthscale.new_tensor(value)
 
 	@staticmethod
 	def backward(ctx, grad_output):
-		return tuple(grad_output.to(G.device) * G for G in ctx.saved_tensors) + (None, None, None)
+		out = tuple(grad_output.to(G.device) * G for G in ctx.saved_tensors)
+		return out[:3] + (None, None, None) + ((out[3],) if ctx.with_points else (None,))
 
 
 def gp_mll_fun(X, y, kernel, lengthscale, outputscale, noise, rank: int = 100, deg: int = 20, count: int = 64, seed: int = 0, **kw):
 	"""The marginal log-likelihood of a zero-mean Gaussian process over the points X with observations y (`primate_amd.gp.mll`,
 	fp64) as a 0-d tensor differentiable with respect to the three parameter tensors `lengthscale` (0-d, one element, or one per
-	dimension), `outputscale`, `noise` (floats are taken as constants). X and y get NO gradient: they are data. Backward is
+	dimension), `outputscale`, `noise` (floats are taken as constants). X: when it is a tensor with `requires_grad` (learned inputs,
+	latent variables) it receives grad_output times `gp.mll(points=True)`'s grads["points"], the gradient with respect to the training
+	points (one element of X per coordinate: an (n,) tensor is one dimension); otherwise the points are data, no point
+	gradient is computed and every number keeps its bits. y gets NO gradient. Backward is
 	grad_output times the gradients `gp.mll` returned: the gradient of the marginal likelihood itself (exact data-fit term, exact
 	tr(P^-1 dA/dtheta), sampled remainder), not the derivative of the sampled value. Maximise it with any torch optimiser on
 	`-gp_mll_fun(...)`. kw: solve_deg, batch, pdf, probes, control_variate go to `gp.mll`. The same seed gives the same bits."""
+	Xt = X if isinstance(X, torch.Tensor) and X.requires_grad else None
 	if isinstance(X, torch.Tensor):
 		X = X.detach().cpu().numpy()
 	if isinstance(y, torch.Tensor):
@@ -129,26 +141,33 @@ def gp_mll_fun(X, y, kernel, lengthscale, outputscale, noise, rank: int = 100, d
 	if unknown:
 		raise ValueError(f"gp_mll_fun: unknown arguments {sorted(unknown)}")
 	opts = dict(kw, kernel=kernel, rank=int(rank), deg=int(deg), count=int(count), seed=int(seed))
-	return _GpMllFun.apply(ls, s, v, X, y, opts)
+	if Xt is None:
+		return _GpMllFun.apply(ls, s, v, X, y, opts)
+	return _GpMllFun.apply(ls, s, v, X, y, opts, Xt)
 
 
 def kernel_trace_fun(X, kernel, lengthscale, outputscale, noise, fun="log", deg: int = 30, count: int = 256, seed: int = 0, method: str = "lanczos", **kw):
 	"""The Girard-Hutchinson estimate of tr f(A), A = outputscale * phi(r2) + noise * I over the points X (the KernelOperator of
 	`primate_amd.operators`), as a 0-d tensor differentiable with respect to the three parameter tensors: `lengthscale` (0-d, one
-	element, or one per dimension), `outputscale`, `noise` (floats are taken as constants). X gets NO gradient: the points are data.
-	The value and the gradients come out of the same `count` probes (primate_amd.grad.kernel_trace_grad, fp64); backward is
+	element, or one per dimension), `outputscale`, `noise` (floats are taken as constants). X: when it is a tensor with
+	`requires_grad` it receives grad_output times `kernel_trace_grad(points=True)`'s grads["points"] (the Lanczos
+	method only - the Chebyshev route refuses); otherwise the points are data, no point gradient is computed and every number keeps
+	its bits. The value and the gradients come out of the same `count` probes (primate_amd.grad.kernel_trace_grad, fp64); backward is
 	grad_output times the stored gradients. method: "lanczos" (fun in log, exp, identity) or "chebyshev". kw: batch, pdf (default
 	"device:rademacher"), probes go to kernel_trace_grad, everything else to the operator (orth=, t=, bounds=, ...). The same seed
 	gives the same bits."""
 	if method not in METHODS:
 		raise ValueError(f"unknown method '{method}' (one of {', '.join(METHODS)})")
+	Xt = X if isinstance(X, torch.Tensor) and X.requires_grad else None
 	if isinstance(X, torch.Tensor):
 		X = X.detach()
 	ls, s, v = (p if isinstance(p, torch.Tensor) else torch.as_tensor(p, dtype=torch.float64) for p in (lengthscale, outputscale, noise))
 	if s.numel() != 1 or v.numel() != 1:
 		raise ValueError("outputscale and noise are single numbers")
 	opts = dict(kw, kernel=kernel, method=method, fun=fun, deg=int(deg), count=int(count), seed=int(seed))
-	return _KernelTraceFun.apply(ls, s, v, X, opts)
+	if Xt is None:
+		return _KernelTraceFun.apply(ls, s, v, X, opts)
+	return _KernelTraceFun.apply(ls, s, v, X, opts, Xt)
 
 
 def trace_fun(A_csr, fun="log", deg: int = 30, count: int = 256, seed: int = 0, method: str = "lanczos", **kw):

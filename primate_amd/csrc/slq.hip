@@ -40,6 +40,7 @@
 #include "slq_kernelop.hpp"  // matrix-free kernel operator (slq_kernel_*): validation, schedule, k_kernel_rescale, k_kernel_panel
 #include "slq_kernelgrad.hpp"  // hyperparameter gradients of the kernel operator (slq_kernel_grad_*): schedule, k_kernel_grad, k_kernel_grad_sum
 #include "slq_kernelcross.hpp"  // cross-covariance products (slq_kernel_cross_*): schedule, the launch functions of slq_kernelcross.hip
+#include "slq_kernelpointgrad.hpp"  // gradients in the points (slq_kernel_pointgrad_*): schedule, the launch functions of slq_kernelpointgrad.hip
 #include "slq_operator.hpp"  // the operator handle and the values it owns (DevBuf, CsrArrays, TileStream, KernelPoints)
 
 using namespace slq;
@@ -4620,6 +4621,165 @@ extern "C" int slq_kernel_precond_trace_grad(slq_operator *op, slq_kernel_grad *
   hipStream_t st = op->ctx->stream;
   k_precond_trace_add<<<dim3(1), dim3(64), 0, st>>>(g->d, (double)op->n, (const double *)pc.base->k_pts.params, alpha, g->vals.as<double>());
   HIP_TRY(hipGetLastError());
+  return SLQ_OK;
+}
+
+// ---- gradients with respect to the points (schedule and kernels in slq_kernelpointgrad.hpp) ------------------------
+struct slq_kernel_pointgrad {
+  slq_context *ctx;
+  slq_operator *op;         // not owned: read at every update (its z, norms and scalars as they are then)
+  slq_kernel_cross *cross;  // not owned; null: the training form. Else the cross form: the rows are its new points
+  int64_t nrows, nsum, count;
+  int d, dpad;
+  DevBuf vals;  // nrows x d doubles, row-major like the points
+  DevBuf part;  // nslabs x nrows x dpad doubles: one partial per slab of a pass
+  size_t vals_bytes() const { return (size_t)nrows * (size_t)d * 8; }
+};
+
+static int kernel_pointgrad_create_body(slq_context *ctx, slq_operator *op, slq_kernel_cross *cross, const char *who, slq_kernel_pointgrad **out) {
+  *out = nullptr;
+  if (op->kind != OP_KERNEL)
+    return fail(SLQ_EINVAL, "%s: the operator is of kind '%s', not a kernel operator (slq_kernel_create; of a preconditioned operator pass the base)", who, op_kind_name(op->kind));
+  if (op->dtype != SLQ_F64) return fail(SLQ_EINVAL, "%s: the operator's dtype is fp32: the accumulator is fp64 only (the device matrices are fp64)", who);
+  if (op->ctx != ctx || (cross && cross->ctx != ctx)) return fail(SLQ_EINVAL, "%s: the operator belongs to another context", who);
+  if (ctx->dead) return fail(SLQ_EINVAL, "%s: the context has been destroyed", who);
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int64_t nrows = cross ? cross->pts.n : op->n;
+  const KernelPointGradSchedule S = kernel_pointgrad_schedule(nrows, op->n, ctx->num_cus);
+  std::unique_ptr<slq_kernel_pointgrad> g(new (std::nothrow) slq_kernel_pointgrad{ctx, op, cross, nrows, op->n, 0, op->k_pts.d, op->k_pts.dpad, {}, {}});
+  if (!g) return fail(SLQ_ENOMEM, "host allocation failed");
+  hipError_t e = g->vals.alloc(g->vals_bytes());
+  if (e == hipSuccess) e = g->part.alloc((size_t)S.nslabs * (size_t)nrows * (size_t)g->dpad * 8);
+  if (e == hipSuccess) e = hipMemsetAsync(g->vals.p, 0, g->vals_bytes(), ctx->stream);
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "%s: %s", who, hipGetErrorString(e));
+  ctx_retain(ctx);
+  *out = g.release();
+  return SLQ_OK;
+}
+extern "C" int slq_kernel_pointgrad_create(slq_context *ctx, slq_operator *op, slq_kernel_pointgrad **out) {
+  if (!ctx || !op || !out) return fail(SLQ_EINVAL, "slq_kernel_pointgrad_create: ctx/op/out is NULL");
+  return kernel_pointgrad_create_body(ctx, op, nullptr, "slq_kernel_pointgrad_create", out);
+}
+extern "C" int slq_kernel_pointgrad_create_cross(slq_context *ctx, slq_kernel_cross *cross, slq_kernel_pointgrad **out) {
+  if (!ctx || !cross || !out) return fail(SLQ_EINVAL, "slq_kernel_pointgrad_create_cross: ctx/cross/out is NULL");
+  return kernel_pointgrad_create_body(ctx, cross->op, cross, "slq_kernel_pointgrad_create_cross", out);
+}
+
+extern "C" int slq_kernel_pointgrad_destroy(slq_kernel_pointgrad *g) {
+  if (!g) return SLQ_OK;
+  hipSetDevice(g->ctx->device);
+  hipStreamSynchronize(g->ctx->stream);
+  slq_context *ctx = g->ctx;
+  delete g;  // (every device array is a member that frees itself)
+  ctx_release(ctx);
+  return SLQ_OK;
+}
+
+// one pass of k_kernel_pointgrad and its fold: vals = beta vals + alpha R(U, W) over mc <= 64 columns
+static int kernel_pointgrad_pass(slq_kernel_pointgrad *g, const KernelPointGradSchedule &S, const KernelPointGradScale &sc, const double *U, const double *W,
+                                 int mc, double alpha, double beta) {
+  const slq_operator *op = g->op;
+  const KernelPoints &rows = g->cross ? g->cross->pts : op->k_pts;
+  const KernelPointGradArgs a{(int)g->nrows, (int)rows.npad, (int)g->nsum, (int)op->k_pts.npad, g->dpad / 4, g->cross ? 0 : 1,
+                              (const double *)rows.zt, (const double *)rows.nrm, (const double *)op->k_pts.zt, (const double *)op->k_pts.nrm,
+                              U, W, mc, g->part.as<double>()};
+  if (!kernel_pointgrad_launch(op->k_profile, S, a, (void *)g->ctx->stream)) return fail(SLQ_EINVAL, "slq_kernel_pointgrad_update: no kernel for profile %d", op->k_profile);
+  HIP_TRY(hipGetLastError());
+  // (the passes run one after the other on the stream: each fold reads the partials of its own pass)
+  kernel_pointgrad_sum_launch(g->nrows, g->d, g->dpad, S.nslabs, g->part.as<const double>(), (const double *)op->k_pts.params, sc, alpha, beta, g->vals.as<double>(),
+                              (void *)g->ctx->stream);
+  HIP_TRY(hipGetLastError());
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_pointgrad_update(slq_kernel_pointgrad *g, slq_dmat *Z, int z0, slq_dmat *W, int w0, int m, double alpha, double beta) {
+  if (!g) return fail(SLQ_EINVAL, "slq_kernel_pointgrad_update: accumulator is NULL");
+  if (m < 1) return fail(SLQ_EINVAL, "slq_kernel_pointgrad_update: m = %d columns (m >= 1)", m);
+  SLQ_TRY(dmat_range(Z, z0, m, g->cross ? "slq_kernel_pointgrad_update(U)" : "slq_kernel_pointgrad_update(Z)"));
+  SLQ_TRY(dmat_range(W, w0, m, "slq_kernel_pointgrad_update(W)"));
+  if (Z->n != g->nrows || W->n != g->nsum) {
+    if (g->cross)
+      return fail(SLQ_EINVAL, "slq_kernel_pointgrad_update: the cross form has %lld new points and %lld training points, U %lld rows, W %lld", (long long)g->nrows,
+                  (long long)g->nsum, (long long)Z->n, (long long)W->n);
+    return fail(SLQ_EINVAL, "slq_kernel_pointgrad_update: the operator has %lld points, Z %lld rows, W %lld", (long long)g->nsum, (long long)Z->n, (long long)W->n);
+  }
+  if (W->ctx != g->ctx || Z->ctx != g->ctx) return fail(SLQ_EINVAL, "slq_kernel_pointgrad_update: a matrix belongs to another context");
+  if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(SLQ_EINVAL, "slq_kernel_pointgrad_update: alpha = %g, beta = %g must be finite", alpha, beta);
+  HIP_TRY(hipSetDevice(g->ctx->device));
+  const slq_operator *op = g->op;
+  if (g->cross && g->cross->epoch != op->k_epoch) SLQ_TRY(kernel_cross_rescale(g->cross));  // the hyperparameters have moved: z* follow, before this update
+  const KernelPointGradSchedule S = kernel_pointgrad_schedule(g->nrows, g->nsum, g->ctx->num_cus);
+  KernelPointGradScale sc;
+  for (int k = 0; k < kKernelMaxDim; ++k) sc.ls[k] = op->k_scale->ls[k];
+  // training form: P = R(Z, W) + R(W, Z), in this order per chunk; Z and W one matrix and one column range: one pass, twice its weight
+  const bool same = !g->cross && Z == W && z0 == w0;
+  for (int c0 = 0; c0 < m; c0 += kKernelPointGradCols) {
+    const int mc = std::min(kKernelPointGradCols, m - c0);
+    const double *Zc = Z->d + (size_t)(z0 + c0) * Z->n, *Wc = W->d + (size_t)(w0 + c0) * W->n;
+    SLQ_TRY(kernel_pointgrad_pass(g, S, sc, Zc, Wc, mc, same ? 2.0 * alpha : alpha, c0 == 0 ? beta : 1.0));
+    if (!g->cross && !same) SLQ_TRY(kernel_pointgrad_pass(g, S, sc, Wc, Zc, mc, alpha, 1.0));
+  }
+  g->count += m;
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_pointgrad_get(slq_kernel_pointgrad *g, double *vals, int64_t ld, int64_t *count) {
+  if (!g) return fail(SLQ_EINVAL, "slq_kernel_pointgrad_get: accumulator is NULL");
+  if (vals && ld < g->d) return fail(SLQ_EINVAL, "slq_kernel_pointgrad_get: ld = %lld is below d = %d", (long long)ld, g->d);
+  HIP_TRY(hipSetDevice(g->ctx->device));
+  if (vals)
+    HIP_TRY(hipMemcpy2DAsync(vals, (size_t)ld * 8, g->vals.p, (size_t)g->d * 8, (size_t)g->d * 8, (size_t)g->nrows, hipMemcpyDeviceToHost, g->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(g->ctx->stream));
+  if (count) *count = g->count;
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_pointgrad_reset(slq_kernel_pointgrad *g) {
+  if (!g) return fail(SLQ_EINVAL, "slq_kernel_pointgrad_reset: accumulator is NULL");
+  HIP_TRY(hipSetDevice(g->ctx->device));
+  HIP_TRY(hipMemsetAsync(g->vals.p, 0, g->vals_bytes(), g->ctx->stream));
+  g->count = 0;
+  return SLQ_OK;
+}
+
+// kernel_pointgrad_schedule() of slq_kernelpointgrad.hpp as an array: rows per block, row blocks, columns per launch, slabs, tiles per
+// slab, then slab_begin[0 .. slabs] (-1 beyond). No HIP call.
+extern "C" int slq_debug_kernel_pointgrad_schedule(int64_t nrows, int64_t nsum, int num_cus, int64_t *out, int nout) {
+  if (!out || nout < 5 + kKernelCrossMaxSlabs + 1) return fail(SLQ_EINVAL, "slq_debug_kernel_pointgrad_schedule: room for %d values", 5 + kKernelCrossMaxSlabs + 1);
+  const int64_t lim = ((int64_t)1 << 31) - 16;
+  if (nrows <= 0 || nrows >= lim || nsum <= 0 || nsum >= lim || num_cus <= 0)
+    return fail(SLQ_EINVAL, "slq_debug_kernel_pointgrad_schedule: 0 < nrows, nsum < 2^31 - 16 and num_cus positive");
+  const KernelPointGradSchedule S = kernel_pointgrad_schedule(nrows, nsum, num_cus);
+  kernel_schedule_words({S.rows_per_block, S.nrow_blocks, S.chunk_cols, S.nslabs, S.tiles_per_slab}, S.nslabs, S.slab_begin, kKernelCrossMaxSlabs, out);
+  return SLQ_OK;
+}
+
+// vals = beta vals + alpha tr(P^-1 dA/dx) = beta vals - alpha sigma^-2 sum_c (L H)_c^T (dA/dx) L_c (tr dA/dx = 0: the diagonal of A does
+// not depend on the points), over the columns of the rank reached, 64 at a time through the matrices slq_kernel_precond_trace_grad
+// uses: per chunk two column launches and one accumulator update. Everything on the stream; the column count is left as it was.
+extern "C" int slq_kernel_precond_trace_pointgrad(slq_operator *op, slq_kernel_pointgrad *g, double alpha, double beta) {
+  SLQ_TRY(precond_handle(op, "slq_kernel_precond_trace_pointgrad"));
+  if (!g) return fail(SLQ_EINVAL, "slq_kernel_precond_trace_pointgrad: the accumulator is NULL");
+  KernelPrecond &pc = *op->pre;
+  if (g->cross) return fail(SLQ_EINVAL, "slq_kernel_precond_trace_pointgrad: the accumulator is of the cross form: create it with slq_kernel_pointgrad_create on the base of this preconditioned operator");
+  if (g->op != pc.base) return fail(SLQ_EINVAL, "slq_kernel_precond_trace_pointgrad: the accumulator belongs to another operator: create it on the base of this preconditioned operator");
+  SLQ_TRY(precond_check_fresh(op, "slq_kernel_precond_trace_pointgrad"));
+  if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(SLQ_EINVAL, "slq_kernel_precond_trace_pointgrad: alpha = %g, beta = %g must be finite", alpha, beta);
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  const size_t n = (size_t)op->n;
+  SLQ_TRY(precond_grow(pc.cols, 2 * n * kPrecondChunkCols * 8, "slq_kernel_precond_trace_pointgrad"));
+  slq_dmat Z{op->ctx, op->n, kPrecondChunkCols, pc.cols.as<double>()}, W{op->ctx, op->n, kPrecondChunkCols, pc.cols.as<double>() + n * kPrecondChunkCols};
+  const double sigma2 = pc.base->k_noise;
+  const int64_t count = g->count;
+  bool first = true;  // (the rank reached is at least 1: the first pivot's residual is s itself)
+  for (int c0 = 0; c0 < pc.rank; c0 += kPrecondChunkCols) {
+    const int nc = std::min(kPrecondChunkCols, pc.rank - c0);
+    SLQ_TRY(precond_columns_device(op, 1, c0, nc, Z.d, "slq_kernel_precond_trace_pointgrad"));
+    SLQ_TRY(precond_columns_device(op, 0, c0, nc, W.d, "slq_kernel_precond_trace_pointgrad"));
+    SLQ_TRY(slq_kernel_pointgrad_update(g, &Z, 0, &W, 0, nc, -alpha / sigma2, first ? beta : 1.0));
+    first = false;
+  }
+  g->count = count;
   return SLQ_OK;
 }
 

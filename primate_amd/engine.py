@@ -334,6 +334,12 @@ class DeviceOperator:
 		self._need_precond("precond_trace_grad")
 		check(_capi.lib().slq_kernel_precond_trace_grad(self._h, acc._h, float(alpha), float(beta)))
 
+	def precond_trace_point_grad(self, acc: "KernelPointGradAccumulator", alpha: float = 1.0, beta: float = 0.0) -> None:
+		"""acc's values = beta * values + alpha * tr(P^-1 dA/dx), exactly (slq_kernel_precond_trace_pointgrad): `acc` is a training-form
+		point-gradient accumulator on this operator's BASE. Deterministic, asynchronous; acc's column count is unchanged."""
+		self._need_precond("precond_trace_point_grad")
+		check(_capi.lib().slq_kernel_precond_trace_pointgrad(self._h, acc._h, float(alpha), float(beta)))
+
 	def factor_timing(self) -> dict:
 		"""Wall time of the last factorisation in ms: device_ms (the launches up to the synchronisation), host_ms (Jacobi, G, its upload)."""
 		self._need_precond("factor_timing")
@@ -1305,6 +1311,68 @@ class KernelCross:
 	def close(self):
 		if getattr(self, "_h", None):
 			_capi.lib().slq_kernel_cross_destroy(self._h)
+			self._h = None
+
+	def __del__(self):
+		try:
+			self.close()
+		except Exception:  # noqa: BLE001
+			pass
+
+
+def kernel_pointgrad_schedule(nrows: int, nsum: int, num_cus: int = 256) -> dict:
+	"""The schedule of one pass of a KernelPointGradAccumulator.update with `nrows` row points and `nsum` summed points, as the library
+	cuts it (slq_debug_kernel_pointgrad_schedule; host arithmetic, no device): rows per block, row blocks, factor columns per launch,
+	slabs of the summed points, tiles of 16 points per slab and the slabs' bounds."""
+	out = (C.c_int64 * 70)()
+	check(_capi.lib().slq_debug_kernel_pointgrad_schedule(int(nrows), int(nsum), int(num_cus), out, 70))
+	v = list(out)
+	return dict(rows=v[0], nrb=v[1], chunk_cols=v[2], slabs=v[3], tiles_per_slab=v[4], begin=v[5 : 5 + v[3] + 1], rest=v[5 + v[3] + 1 :])
+
+
+class KernelPointGradAccumulator:
+	"""Device-resident gradients of a kernel operator with respect to the points (slq_kernel_pointgrad_*).
+	On a DeviceOperator of kind "kernel" in fp64 (the training form) every `update` folds alpha * sum_c Z_c^T (dA/dx_ak) W_c into n x d
+	values; on a KernelCross of such an operator (the cross form) alpha * d/dx*_ak sum_c U_c^T K(X*, X) W_c into m x d values, U on the
+	new points and W on the training points. The accumulator keeps what it borrows alive - the operator, and the cross object - and
+	reads the operator's parameters as they are at each update, as a KernelGradAccumulator does; a cross-form accumulator follows a
+	`set_kernel_parameters` as a cross product does."""
+
+	def __init__(self, op_or_cross):
+		cross = op_or_cross if isinstance(op_or_cross, KernelCross) else None
+		op = cross.op if cross is not None else op_or_cross
+		if getattr(op, "kind", None) != "kernel":
+			raise ValueError(f"KernelPointGradAccumulator needs a kernel operator or a KernelCross, not kind '{getattr(op, 'kind', None)}'")
+		if np.dtype(op.dtype) != np.float64:
+			raise ValueError(f"KernelPointGradAccumulator is fp64 only (the device matrices are fp64): the operator is {np.dtype(op.dtype)}")
+		self.op, self.cross, self.ctx = op, cross, op.ctx
+		self.n, self.d = int(op.shape[0]), int(op.nnz // op.shape[0])
+		self.rows = int(cross.m) if cross is not None else self.n
+		h = C.c_void_p()
+		if cross is not None:
+			check(_capi.lib().slq_kernel_pointgrad_create_cross(self.ctx._h, cross._h, C.byref(h)))
+		else:
+			check(_capi.lib().slq_kernel_pointgrad_create(self.ctx._h, op._h, C.byref(h)))
+		self._h = h
+
+	def update(self, Z: "DeviceMatrix", z0: int, W: "DeviceMatrix", w0: int, m: int, alpha: float = 1.0, beta: float = 1.0):
+		"""vals = beta * vals + alpha * (the rows x d sums over columns [z0, z0 + m) of Z - U, on the new points, in the cross form - and
+		[w0, w0 + m) of W). Asynchronous on the context stream."""
+		check(_capi.lib().slq_kernel_pointgrad_update(self._h, Z._h, int(z0), W._h, int(w0), int(m), float(alpha), float(beta)))
+
+	def get(self) -> tuple:
+		"""(vals, count): rows x d, shaped like the points; the columns folded in."""
+		vals = np.zeros((self.rows, self.d))
+		cnt = C.c_int64()
+		check(_capi.lib().slq_kernel_pointgrad_get(self._h, ptr(vals), self.d, C.byref(cnt)))
+		return vals, cnt.value
+
+	def reset(self):
+		check(_capi.lib().slq_kernel_pointgrad_reset(self._h))
+
+	def close(self):
+		if getattr(self, "_h", None):
+			_capi.lib().slq_kernel_pointgrad_destroy(self._h)
 			self._h = None
 
 	def __del__(self):

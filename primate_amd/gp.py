@@ -126,10 +126,16 @@ def posterior(K, y, Xnew, deg: int = 60, orth: Optional[int] = None, rtol: float
 
 	info: deg, batches (variance batches run), steps (the Lanczos steps each plan took: first the solve for alpha, then one entry
 	per batch), zero_columns (indices of the new points whose column of B was zero)."""
+	return _posterior(K, y, Xnew, deg, orth, rtol, variance, batch, covariance, include_noise, precond_rank, False)[:3]
+
+
+def _posterior(K, y, Xnew, deg, orth, rtol, variance, batch, covariance, include_noise, precond_rank, grad: bool, who: str = "posterior") -> tuple:
+	"""(mean, var, info, dmean, dvar): `posterior` behind its docstring; with `grad` also `posterior_grad`'s two arrays, from point-gradient
+	updates placed after the solves they read. Without it not one device call is added or moved: posterior's bits are what they were."""
 	if getattr(K, "_slq_kind", None) != "kernel":
-		raise ValueError("posterior needs a KernelOperator")
+		raise ValueError(f"{who} needs a KernelOperator")
 	if np.dtype(K.dtype) != np.float64:
-		raise ValueError(f"posterior is fp64 only (the device matrices are fp64): the KernelOperator is {np.dtype(K.dtype)}")
+		raise ValueError(f"{who} is fp64 only (the device matrices are fp64): the KernelOperator is {np.dtype(K.dtype)}")
 	n, d = K.X.shape
 	deg, batch = int(deg), int(batch)
 	if deg < 1 or batch < 1:
@@ -173,6 +179,8 @@ def posterior(K, y, Xnew, deg: int = 60, orth: Optional[int] = None, rtol: float
 		## alpha = A^-1 y over the non-zero columns of y, mean = C alpha
 		nz = np.flatnonzero(np.any(yh != 0.0, axis=0))
 		mean = np.zeros((m, q))
+		dmean = np.zeros((m, d, q)) if grad else None
+		dvar = np.zeros((m, d)) if grad and variance else None
 		if nz.size:
 			plan = keep(engine.LanczosPlan(solve_op, int(nz.size), deg, orth_arg, basis="keep"))
 			Alpha = keep(engine.DeviceMatrix(n, int(nz.size), ctx=ctx))
@@ -190,11 +198,22 @@ def posterior(K, y, Xnew, deg: int = 60, orth: Optional[int] = None, rtol: float
 			cross.matmat_dmat(Alpha, 0, Mean, 0, int(nz.size))
 			mean[:, nz] = Mean.get()
 			_finite(mean, "the mean", rtol)
+			if grad:  # d mean_q / d x*: the cross form with U a column of ones and W = alpha_q, one column at a time
+				pacc, Ones = keep(engine.KernelPointGradAccumulator(cross)), keep(engine.DeviceMatrix(m, 1, ctx=ctx))
+				Ones.set(0, np.ones((m, 1)))
+				for c, col in enumerate(nz):
+					pacc.update(Ones, 0, Alpha, c, 1, alpha=1.0, beta=0.0)
+					dmean[:, :, col] = pacc.get()[0]
+				_finite(dmean, "the gradient of the mean", rtol)
+				for obj in (pacc, Ones):
+					obj.close()
 			for obj in (Mean, cross, Alpha, plan):
 				obj.close()
 		mean = mean[:, 0] if vector else mean
+		if grad:
+			dmean = dmean[:, :, 0] if vector else dmean
 		if not variance:
-			return mean, None, info
+			return mean, None, info, dmean, None
 
 		mb_max = min(batch, m)
 		B, Cv = keep(engine.DeviceMatrix(n, mb_max, ctx=ctx)), keep(engine.DeviceMatrix(n, mb_max, ctx=ctx))
@@ -223,6 +242,14 @@ def posterior(K, y, Xnew, deg: int = 60, orth: Optional[int] = None, rtol: float
 				_finite(block, f"the variance block of the new points [{i0}, {i1})", rtol)
 				block[zero, :] = 0.0
 				block[:, zero] = 0.0
+				if grad:  # d var_a / d x*_a = -2 (d k_a / d x*_a)^T A^-1 k_a: U = I picks column a of Cv = A^-1 C_b^T for row a
+					paccb = keep(engine.KernelPointGradAccumulator(crossb))
+					paccb.update(Eye, 0, Cv, 0, mb, alpha=-2.0, beta=0.0)
+					dv = paccb.get()[0]
+					_finite(dv, f"the gradient of the variance of the new points [{i0}, {i1})", rtol)
+					dv[zero, :] = 0.0
+					dvar[i0:i1] = dv
+					paccb.close()
 			info["batches"] += 1
 			info["zero_columns"].extend(int(i0 + j) for j in zero)
 			quad[i0:i1] = np.diag(block)
@@ -235,11 +262,27 @@ def posterior(K, y, Xnew, deg: int = 60, orth: Optional[int] = None, rtol: float
 			cov = _prior_block(K, Cop.scaled_points().astype(np.float64)) - block_full
 			if include_noise:
 				cov[np.diag_indices(m)] += float(K.noise)
-			return mean, cov, info
-		return mean, var, info
+			return mean, cov, info, dmean, dvar
+		return mean, var, info, dmean, dvar
 	finally:
 		for obj in reversed(live):
 			obj.close()
+
+
+def posterior_grad(K, y, Xnew, deg: int = 60, orth: Optional[int] = None, variance: bool = True, batch: int = 128, precond_rank: int = 0) -> tuple:
+	"""(dmean, dvar, info): the gradients of `posterior`'s mean and variance with respect to the NEW points - what
+	Bayesian optimisation differentiates. The solves are exactly `posterior`'s (same plans, same right-hand sides, same order; rtol = 0),
+	and each gradient is a cross-form point-gradient update (engine.KernelPointGradAccumulator) on what a solve left on the device:
+
+	    dmean[a, k]   = d mean_a / d x*_ak       (m x d, or m x d x q for y (n, q)): U a column of ones, W = alpha_q = A^-1 y_q
+	    dvar[a, k]    = d var_a / d x*_ak = -2 R[a, k](U = I, W = A^-1 C_b^T) per batch of at most `batch` new points (None with
+	                    variance=False); the prior variance s does not depend on the point.
+
+	The derivative is that of the smooth formula at the rounded scaled points. A new point whose column of C^T is exactly zero has
+	dvar = 0 exactly (its mean's gradient is 0 by the profile's own underflow); a zero column of y has dmean = 0. Nothing of size n
+	leaves the device: only the m x d arrays do. There is no gradient in the TRAINING points here. info: `posterior`'s."""
+	mean, var, info, dmean, dvar = _posterior(K, y, Xnew, deg, orth, 0.0, variance, batch, False, False, precond_rank, True, who="posterior_grad")
+	return dmean, dvar, info
 
 
 ## ---- the gradient of logdet A through the preconditioner, and the marginal likelihood (DESIGN.md §4.19) ---------------------------
@@ -312,8 +355,10 @@ def _batches(count: int, batch: int, probes, n: int, who: str):
 	return nb, batch, None
 
 
-def _logdet_grad(base, B, deg: int, count: int, batch: int, pdf, seed, probes, control_variate, phases=None) -> tuple:
-	"""(value, vals, info) with vals the d + 2 raw gradient values of logdet A; `logdet_grad` behind its argument checks (rank > 0)."""
+def _logdet_grad(base, B, deg: int, count: int, batch: int, pdf, seed, probes, control_variate, phases=None, points: bool = False) -> tuple:
+	"""(value, vals, info) with vals the d + 2 raw gradient values of logdet A; `logdet_grad` behind its argument checks (rank > 0).
+	points: a point-gradient accumulator is updated at the same places with the same factors - the batches' weights 1 / (batch nb) summed
+	on the device, the exact part on top - and info["points_values"] is its n x d (None without): one readback, at the end."""
 	from .estimators import MeanEstimator
 	from .grad import _probe_loader
 	from .operators import MatrixFunction
@@ -335,6 +380,10 @@ def _logdet_grad(base, B, deg: int, count: int, batch: int, pdf, seed, probes, c
 	try:
 		acc = engine.KernelGradAccumulator(op)
 		live.append(acc)
+		pacc = None
+		if points:
+			pacc = engine.KernelPointGradAccumulator(op)
+			live.append(pacc)
 		W, Vm, T, U = (engine.DeviceMatrix(n, batch, ctx=ctx) for _ in range(4))
 		live.extend((W, Vm, T, U))
 		exact = None
@@ -361,10 +410,22 @@ def _logdet_grad(base, B, deg: int, count: int, batch: int, pdf, seed, probes, c
 			with phases("updates"):
 				acc.update(U, 0, Vm, 0, batch, alpha=1.0 / batch, beta=0.0)
 				per_batch.append(acc.get()[0])
+			if pacc is not None:
+				with phases("points"):
+					pacc.update(U, 0, Vm, 0, batch, alpha=1.0 / (batch * nb), beta=0.0 if j == 0 else 1.0)
 		if use_cv:
 			with phases("exact"):
 				pop.precond_trace_grad(acc, alpha=1.0, beta=0.0)
 				exact = acc.get()[0]
+			if pacc is not None:
+				with phases("points"):
+					pop.precond_trace_point_grad(pacc, alpha=1.0, beta=1.0)
+		pvals = None
+		if pacc is not None:
+			with phases("points"):
+				pvals = pacc.get()[0]
+			if not np.all(np.isfinite(pvals)):
+				raise FloatingPointError("logdet_grad: the sampled gradient in the points is not finite: a probe's Lanczos run stopped before `deg` steps: lower deg or rank")
 		per_batch = np.array(per_batch)
 		if not np.all(np.isfinite(per_batch)):
 			raise FloatingPointError("logdet_grad: the sampled gradient is not finite: a probe's Lanczos run stopped before `deg` steps (B is so close to the identity that its Krylov space is exhausted), which the 'inv' action does not survive: lower deg or rank")
@@ -374,6 +435,8 @@ def _logdet_grad(base, B, deg: int, count: int, batch: int, pdf, seed, probes, c
 		info = dict(rank=int(pinfo["rank"]), logdet_precond=float(pinfo["logdet_p"]), trace=est, count=int(qv.size), deg=deg,
 					std_error=float(np.std(qv, ddof=1) / np.sqrt(qv.size)), control_variate=bool(use_cv), ritz_max=float(top),
 					grad_exact_values=exact, grad_per_batch=per_batch, batches=nb)  # fmt: skip
+		if points:
+			info["points_values"] = pvals
 		return est + float(pinfo["logdet_p"]), vals, info
 	finally:
 		if hasattr(M, "close"):
@@ -407,7 +470,7 @@ def _shape_grad_info(base, info: dict, scale: float = 1.0) -> dict:
 
 
 def logdet_grad(K, rank: int = 100, deg: int = 20, count: int = 64, batch: int = 16, pdf: str = "device:rademacher", seed=None, probes=None,
-				control_variate="auto") -> tuple:  # fmt: skip
+				control_variate="auto", points: bool = False) -> tuple:  # fmt: skip
 	"""(value, grads, info): log det A of the KernelOperator `K` (A = K0 + noise I, float64) as `logdet` estimates it, and the
 	gradient of log det A with respect to the hyperparameters,
 
@@ -432,7 +495,10 @@ def logdet_grad(K, rank: int = 100, deg: int = 20, count: int = 64, batch: int =
 	and holds for the whole call.
 	info: logdet's (rank, logdet_precond, trace, std_error, count, deg), control_variate (the decision), ritz_max, grad_exact (the
 	deterministic part shaped like grads; None with the control variate off), grad_std_error (per component, the sample standard
-	deviation of the per-batch means over sqrt(batches); None with fewer than 2 batches), batches."""
+	deviation of the per-batch means over sqrt(batches); None with fewer than 2 batches), batches.
+	points=True: grads["points"] (n x d) ~ tr(A^-1 dA/dx_ak), the gradient of log det A with respect to the points:
+	a second accumulator updated at the same places with the same factors and weights, the exact part tr(P^-1 dA/dx) included when the
+	control variate is on. With False every number keeps its bits."""
 	from .grad import _kernel_grads
 
 	rank, deg, count, batch = int(rank), int(deg), int(count), int(batch)
@@ -447,7 +513,7 @@ def logdet_grad(K, rank: int = 100, deg: int = 20, count: int = 64, batch: int =
 
 		M = MatrixFunction(base, fun="log", deg=deg, dtype=np.float64)
 		try:
-			est, grads, ginfo = kernel_trace_grad(M, pdf=pdf, count=count, batch=batch, seed=seed, probes=probes)
+			est, grads, ginfo = kernel_trace_grad(M, pdf=pdf, count=count, batch=batch, seed=seed, probes=probes, points=points)
 		finally:
 			if hasattr(M, "close"):
 				M.close()
@@ -455,8 +521,11 @@ def logdet_grad(K, rank: int = 100, deg: int = 20, count: int = 64, batch: int =
 		info = dict(rank=0, logdet_precond=0.0, trace=float(est), count=int(q.size), deg=deg, std_error=float(np.std(q, ddof=1) / np.sqrt(q.size)),
 					control_variate=False, ritz_max=None, grad_exact=None, grad_std_error=None, batches=-(-count // batch))  # fmt: skip
 		return float(est), grads, info
-	value, vals, info = _logdet_grad(base, B, deg, count, batch, pdf, seed, probes, control_variate)
-	return value, _kernel_grads(base, vals), _shape_grad_info(base, info)
+	value, vals, info = _logdet_grad(base, B, deg, count, batch, pdf, seed, probes, control_variate, points=points)
+	grads = _kernel_grads(base, vals)
+	if points:
+		grads["points"] = info.pop("points_values")
+	return value, grads, _shape_grad_info(base, info)
 
 
 def _params_vec(grads: dict) -> np.ndarray:
@@ -464,7 +533,7 @@ def _params_vec(grads: dict) -> np.ndarray:
 
 
 def mll(K, y, rank: int = 100, deg: int = 20, solve_deg: Optional[int] = None, count: int = 64, batch: int = 16, pdf: str = "device:rademacher",
-		seed=None, probes=None, control_variate="auto", profile: bool = False) -> tuple:  # fmt: skip
+		seed=None, probes=None, control_variate="auto", profile: bool = False, points: bool = False) -> tuple:  # fmt: skip
 	"""(value, grads, info): the marginal log-likelihood of a zero-mean Gaussian process with the kernel operator `K` (A = K0 + noise I,
 	float64) for the observations `y` ((n,) or (n, q): q independent outputs sharing A), and its gradient with respect to the
 	hyperparameters, shaped as `logdet_grad`'s:
@@ -483,7 +552,10 @@ def mll(K, y, rank: int = 100, deg: int = 20, solve_deg: Optional[int] = None, c
 	gradient, unscaled), logdet_info (`logdet_grad`'s info), grad_std_error (of grads: q / 2 times logdet_grad's), steps (of the
 	solve), q, zero_columns; with profile=True also timing_ms: wall time per phase, each closed by a synchronisation - refresh (the
 	factor), solve, lanczos (the batches' runs, quadratures and actions), applies (M on the probes and the actions), updates (the
-	accumulator, with its readback per batch), exact (tr(P^-1 dA/dtheta)), datafit (its update)."""
+	accumulator, with its readback per batch), exact (tr(P^-1 dA/dtheta)), datafit (its update).
+	points=True: grads["points"] (n x d), the gradient with respect to the training points X = the data-fit part -
+	ONE point-gradient update on alpha with the weight 1/2 - minus (q / 2) times the log-determinant's (`logdet_grad(points=True)`); info
+	gains datafit_points and logdet_points, timing_ms the phase "points". With False every number keeps its bits."""
 	from .grad import _kernel_grads
 
 	rank, deg, count, batch = int(rank), int(deg), int(count), int(batch)
@@ -510,6 +582,7 @@ def mll(K, y, rank: int = 100, deg: int = 20, solve_deg: Optional[int] = None, c
 	nz = np.flatnonzero(np.any(yh != 0.0, axis=0))
 	live = []
 	fit, fit_vals, steps = 0.0, np.zeros(base.X.shape[1] + 2), None
+	fit_points = np.zeros(base.X.shape) if points else None
 	try:
 		if nz.size:
 			m = int(nz.size)
@@ -533,15 +606,23 @@ def mll(K, y, rank: int = 100, deg: int = 20, solve_deg: Optional[int] = None, c
 				live.append(acc)
 				acc.update(Alpha, 0, Alpha, 0, m, alpha=0.5, beta=0.0)
 				fit_vals = acc.get()[0]
+			if points:
+				with phases("points"):
+					pacc = engine.KernelPointGradAccumulator(op)
+					live.append(pacc)
+					pacc.update(Alpha, 0, Alpha, 0, m, alpha=0.5, beta=0.0)
+					fit_points = pacc.get()[0]
 	finally:
 		for obj in reversed(live):
 			obj.close()
 	if B is None:
-		ld, ld_grads, ld_info = logdet_grad(base, rank=0, deg=deg, count=count, batch=batch, pdf=pdf, seed=seed, probes=probes)
+		ld, ld_grads, ld_info = logdet_grad(base, rank=0, deg=deg, count=count, batch=batch, pdf=pdf, seed=seed, probes=probes, points=points)
+		ld_points = ld_grads.pop("points", None)
 	else:
 		if probes is not None and np.asarray(probes).ndim == 2:
 			count = int(np.asarray(probes).shape[1])
-		ld, ld_vals, ld_info = _logdet_grad(base, B, deg, count, batch, pdf, seed, probes, control_variate, phases)
+		ld, ld_vals, ld_info = _logdet_grad(base, B, deg, count, batch, pdf, seed, probes, control_variate, phases, points=points)
+		ld_points = ld_info.pop("points_values", None)
 		ld_grads, ld_info = _kernel_grads(base, ld_vals), _shape_grad_info(base, ld_info)
 	fit_grads = _kernel_grads(base, fit_vals)
 	total = _params_vec(fit_grads) - 0.5 * q * _params_vec(ld_grads)
@@ -552,4 +633,8 @@ def mll(K, y, rank: int = 100, deg: int = 20, solve_deg: Optional[int] = None, c
 				grad_std_error=None if se is None else _as_params(base, 0.5 * q * _params_vec(se)))  # fmt: skip
 	if profile:
 		info["timing_ms"] = dict(phases.ms)
-	return value, _as_params(base, total), info
+	grads = _as_params(base, total)
+	if points:
+		info["datafit_points"], info["logdet_points"] = fit_points, ld_points
+		grads["points"] = fit_points - 0.5 * q * ld_points
+	return value, grads, info

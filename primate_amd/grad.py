@@ -254,15 +254,17 @@ def _kernel_grads(K, vals: np.ndarray) -> dict:
 	return dict(lengthscale=ls.reshape(np.shape(K.lengthscale)), outputscale=float(vals[d]), noise=float(vals[d + 1]))
 
 
-def kernel_trace_grad(M, pdf: Union[str, None] = "rademacher", count: int = 256, batch: int = 64, seed=None, probes=None) -> tuple:
+def kernel_trace_grad(M, pdf: Union[str, None] = "rademacher", count: int = 256, batch: int = 64, seed=None, probes=None, points: bool = False) -> tuple:
 	"""(est, grads, info): the Girard-Hutchinson estimate of tr f(A) over `count` probes for A = the KernelOperator under M and, from
 	the same runs, of its gradient with respect to the hyperparameters:
 
 	    grads = dict(lengthscale=array shaped like K.lengthscale, outputscale=float, noise=float),
 
 	the estimate (1/N) sum_i (f'(A) v_i)^T (dA/dtheta) v_i, contracted on the device against tiles of dA/dtheta that are never held
-	(engine.KernelGradAccumulator). The gradient is that of the smooth formula at the operator's rounded points z; there is none
-	with respect to the points. M: a MatrixFunction with a built-in `fun` among log, exp, identity (fp64), or a ChebyshevFunction
+	(engine.KernelGradAccumulator). The gradient is that of the smooth formula at the operator's rounded points z. points=True: a
+	second accumulator (engine.KernelPointGradAccumulator) is updated at the same places with the same factors and
+	weights and grads["points"] is the n x d gradient with respect to the points X; with False every number keeps its bits. The
+	Chebyshev route has no point gradient and refuses points=True. M: a MatrixFunction with a built-in `fun` among log, exp, identity (fp64), or a ChebyshevFunction
 	with a built-in function of the table `derivative_callable`. The batch loop is `trace_grad`'s. identity is exact and runs
 	nothing: tr A = n (outputscale + noise), gradients 0, n, n.
 	info: count, quad (the per-probe quadratic forms; for identity the exact trace in every entry), acc_count (columns the
@@ -284,6 +286,8 @@ def kernel_trace_grad(M, pdf: Union[str, None] = "rademacher", count: int = 256,
 		raise ValueError(f"count = {count} and batch = {batch} must be >= 1")
 	n = int(M.shape[0])
 	cheb = isinstance(M, ChebyshevFunction)
+	if points and cheb:
+		raise ValueError("kernel_trace_grad: points=True is not built on the Chebyshev route: use a MatrixFunction (Lanczos) for the gradient with respect to the points")
 	if probes is not None:
 		count = int(np.asarray(probes).shape[1]) if np.asarray(probes).ndim == 2 else count
 	exact = False
@@ -304,13 +308,18 @@ def kernel_trace_grad(M, pdf: Union[str, None] = "rademacher", count: int = 256,
 	if exact:
 		d = K.X.shape[1]
 		tr = float(n) * (K.outputscale + K.noise)
-		return tr, _kernel_grads(K, np.concatenate([np.zeros(d), [float(n), float(n)]])), dict(count=count, quad=np.full(count, tr), acc_count=0)
+		grads = _kernel_grads(K, np.concatenate([np.zeros(d), [float(n), float(n)]]))
+		if points:  # (tr A does not depend on the points)
+			grads["points"] = np.zeros((n, d))
+		return tr, grads, dict(count=count, quad=np.full(count, tr), acc_count=0)
 
 	ctx = M._op.ctx
 	acc = engine.KernelGradAccumulator(M._op)
-	W = Z = None
+	W = Z = pacc = None
 	quad = np.empty(count)
 	try:
+		if points:
+			pacc = engine.KernelPointGradAccumulator(M._op)
 		cols = min(batch, count)
 		W, Z = engine.DeviceMatrix(n, cols, ctx=ctx), engine.DeviceMatrix(n, cols, ctx=ctx)
 		done = 0
@@ -328,11 +337,16 @@ def kernel_trace_grad(M, pdf: Union[str, None] = "rademacher", count: int = 256,
 				plan.fun_action_into(Z, 0, der[0], **der[1])
 				scale = der[2]
 			acc.update(Z, 0, W, 0, m, alpha=scale / count, beta=1.0)
+			if pacc is not None:
+				pacc.update(Z, 0, W, 0, m, alpha=scale / count, beta=1.0)
 			done += m
 		vals, acc_count = acc.get()
-		return float(np.mean(quad)), _kernel_grads(K, vals), dict(count=count, quad=quad, acc_count=acc_count)
+		grads = _kernel_grads(K, vals)
+		if pacc is not None:
+			grads["points"] = pacc.get()[0]
+		return float(np.mean(quad)), grads, dict(count=count, quad=quad, acc_count=acc_count)
 	finally:
-		for dm in (W, Z, acc):
+		for dm in (W, Z, acc, pacc):
 			if dm is not None:
 				dm.close()
 
@@ -372,6 +386,52 @@ def kernel_quadratic_grad(K, U, V=None) -> dict:
 		return _kernel_grads(K, acc.get()[0])
 	finally:
 		for dm in {id(x): x for x in (Ud, Vd, acc) if x is not None}.values():
+			dm.close()
+
+
+def kernel_point_grad(K, U, V=None, Xnew=None) -> np.ndarray:
+	"""The gradient of sum_c u_c^T A v_c with respect to the points of the KernelOperator K (fp64): n x d, shaped like K.X, for host
+	arrays U, V (n x m or n; V=None: V = U). With `Xnew` (m* x d): the gradient of sum_c u_c^T K(Xnew, X) v_c with respect to the NEW
+	points, m* x d - U (m* x b) on the new points, V (n x b, required) on the training points. The smooth formula at the operator's
+	rounded points. One KernelPointGradAccumulator update on K's device operator."""
+	from .lanczos import _as_device_operator
+
+	if getattr(K, "_slq_kind", None) == "kernel_precond":
+		raise ValueError("kernel_point_grad: pass the base KernelOperator, not its preconditioner")
+	if getattr(K, "_slq_kind", None) != "kernel":
+		raise ValueError("kernel_point_grad needs a KernelOperator")
+	if np.dtype(K.dtype) != np.float64:
+		raise ValueError("kernel_point_grad is fp64 only (the device matrices are fp64): build the KernelOperator with dtype=np.float64")
+	n = int(K.shape[0])
+	U = np.asarray(U, dtype=np.float64)
+	U = U.reshape(-1, 1) if U.ndim == 1 else U
+	if Xnew is not None and V is None:
+		raise ValueError("kernel_point_grad: with Xnew, U is on the new points and V on the training points: V is required")
+	Vh = U if V is None else np.asarray(V, dtype=np.float64)
+	Vh = Vh.reshape(-1, 1) if Vh.ndim == 1 else Vh
+	op = _as_device_operator(K, dtype=np.float64)
+	acc = Ud = Vd = cross = None
+	try:
+		if Xnew is not None:
+			cross = engine.KernelCross(op, Xnew)
+			rows = cross.m
+		else:
+			rows = n
+		if U.ndim != 2 or Vh.ndim != 2 or U.shape[0] != rows or Vh.shape[0] != n or U.shape[1] != Vh.shape[1] or U.shape[1] < 1:
+			raise ValueError(f"U must be {rows} x m and V {n} x m, got {U.shape} and {Vh.shape}")
+		m = U.shape[1]
+		acc = engine.KernelPointGradAccumulator(cross if cross is not None else op)
+		Ud = engine.DeviceMatrix(rows, m, ctx=op.ctx)
+		Ud.set(0, U)
+		if V is None:
+			Vd = Ud
+		else:
+			Vd = engine.DeviceMatrix(n, m, ctx=op.ctx)
+			Vd.set(0, Vh)
+		acc.update(Ud, 0, Vd, 0, m, alpha=1.0, beta=0.0)
+		return acc.get()[0]
+	finally:
+		for dm in {id(x): x for x in (acc, Ud, Vd, cross) if x is not None}.values():
 			dm.close()
 
 
