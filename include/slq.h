@@ -556,6 +556,43 @@ int slq_debug_kernel_cross_points(slq_kernel_cross *cross, void *zt, void *nrm);
  * index. No HIP call. */
 int slq_debug_kernel_cross_schedule(int64_t nrows, int64_t nsum, int64_t b, int num_cus, int64_t *out, int nout);
 
+/* ---- Random Fourier features of the kernel operator (csrc/slq_kernelfeature.hpp) --------------------------------
+ * The prior term of a pathwise posterior sample (gp.sample_paths). For a kernel operator op (scaled points z, outputscale s, dtype
+ * F) and F2 >= 1 frequencies Omega (F2 x d, already rounded to F: the map is DEFINED on the rounded Omega)
+ *   g_ij   = sum_k Omega_jk z_ik                                  row point i, frequency j
+ *   Phi(z_i) = a [cos g_i1 .. cos g_iF2 | sin g_i1 .. sin g_iF2],   a = sqrt(s / F2), evaluated in F from s on the device
+ *   Y = Phi W:  Y_ic = a sum_j (cos g_ij W[j, c] + sin g_ij W[F2 + j, c]),   W 2 F2 x b, column-major
+ * Paired features, no random phase: Phi(z) Phi(z')^T = (s / F2) sum_j cos(omega_j.(z - z')) is exactly stationary. The profile is
+ * the law Omega was drawn from (normal for rbf, Student-t with 2 nu degrees of freedom for the Matern family): the kernel has no
+ * profile parameter. The row points are the operator's own (cross == NULL) or the new points z* of a slq_kernel_cross of the SAME
+ * operator (training centre; re-derived on the stream first when the hyperparameters have moved, as before a cross product). No
+ * noise term. sin and cos are the device library's accurate functions with full range reduction. Phi is never held; the
+ * frequencies are walked in a fixed order, slab partials are summed in slab order and nothing is atomic: identical calls give
+ * identical bits. s is read from device memory at every product: slq_kernel_set_parameters on op is honoured by the next one (the
+ * lengthscales through z, the outputscale through a).
+ * slq_kernel_feature_create: omega on the host, F2 x d words of op's dtype, row-major with leading dimension ld >= d. The object
+ *   holds Omega^T (k-major, dpad x F2pad; dpad = d rounded up to 4, F2pad = F2 rounded up to 16; zeros in the padding) and its slab
+ *   scratch. It reads op - and the cross object, if given - at every product and owns neither: destroy the feature map first.
+ *   SLQ_EINVAL, nothing allocated: a NULL handle, an operator of another kind (a preconditioned operator is named: pass its base)
+ *   or context, F2 < 1 or > 2^30, ld < d, a frequency that is not finite (the first one is named).
+ * slq_kernel_feature_matmat: host panels in the object's dtype, column-major; W 2 F2 x b (ldw >= 2 F2), Y n x b - or m x b with a
+ *   cross object - (ldy >= its rows). Any b >= 1. Synchronises.
+ * slq_kernel_feature_dmat: the same on columns [i0, i0 + b) of IN (2 F2 rows) and [o0, o0 + b) of OUT (n or m rows), asynchronous
+ *   on the context stream; fp64 only (an fp32 object is refused, naming the dtype). The two entries give the same bits.
+ * Both: SLQ_EINVAL, nothing launched: a NULL handle, a cross object of another operator, b < 1, a leading dimension or a row
+ *   count that does not fit, a column range outside its matrix, overlapping ranges of one matrix, a matrix of another context.
+ * fp64 workgroups take at most 128 columns (two staged halves of W beside the accumulators), fp32 ones 256.
+ * slq_debug_kernel_feature_frequencies: Omega^T as the device holds it, dpad x F2pad words of the object's dtype. Synchronises.
+ * slq_debug_kernel_feature_schedule: the schedule of one product (csrc/slq_kernelfeature.hpp: kernel_feature_schedule) in the
+ *   order of slq_debug_kernel_cross_schedule, the column chunks 128 wide with is_f64 != 0 and 256 otherwise; nout >= 71. No HIP call. */
+typedef struct slq_kernel_feature slq_kernel_feature;
+int slq_kernel_feature_create(slq_context *ctx, slq_operator *op, int64_t F2, const void *omega, int64_t ld, slq_kernel_feature **out);
+int slq_kernel_feature_matmat(slq_kernel_feature *feat, slq_kernel_cross *cross, const void *W, int64_t ldw, void *Y, int64_t ldy, int b);
+int slq_kernel_feature_dmat(slq_kernel_feature *feat, slq_kernel_cross *cross, slq_dmat *IN, int i0, slq_dmat *OUT, int o0, int b);
+int slq_kernel_feature_destroy(slq_kernel_feature *feat);
+int slq_debug_kernel_feature_frequencies(slq_kernel_feature *feat, void *omega_t);
+int slq_debug_kernel_feature_schedule(int64_t nrows, int64_t F2, int64_t b, int num_cus, int is_f64, int64_t *out, int nout);
+
 /* ---- pivoted-Cholesky preconditioner of a kernel operator (csrc/slq_kernelprecond.hpp), fp64 only ----
  * K0 = s phi(r2) is the kernel matrix without noise, A = K0 + sigma2 I (sigma2 > 0). L (n x r, r <= rank_max <= 256) is the
  * greedy partial pivoted Cholesky factor of K0: the residual diagonal starts as d = s; step k takes p = argmax d (ties: the

@@ -40,6 +40,7 @@
 #include "slq_kernelop.hpp"  // matrix-free kernel operator (slq_kernel_*): validation, schedule, k_kernel_rescale, k_kernel_panel
 #include "slq_kernelgrad.hpp"  // hyperparameter gradients of the kernel operator (slq_kernel_grad_*): schedule, k_kernel_grad, k_kernel_grad_sum
 #include "slq_kernelcross.hpp"  // cross-covariance products (slq_kernel_cross_*): schedule, the launch functions of slq_kernelcross.hip
+#include "slq_kernelfeature.hpp"  // random Fourier features (slq_kernel_feature_*): schedule, the launch function of slq_kernelfeature.hip
 #include "slq_kernelpointgrad.hpp"  // gradients in the points (slq_kernel_pointgrad_*): schedule, the launch functions of slq_kernelpointgrad.hip
 #include "slq_operator.hpp"  // the operator handle and the values it owns (DevBuf, CsrArrays, TileStream, KernelPoints)
 
@@ -4377,6 +4378,173 @@ extern "C" int slq_debug_kernel_cross_schedule(int64_t nrows, int64_t nsum, int6
   if (nrows <= 0 || nrows >= lim || nsum <= 0 || nsum >= lim || b <= 0 || b >= lim || num_cus <= 0)
     return fail(SLQ_EINVAL, "slq_debug_kernel_cross_schedule: 0 < nrows, nsum, b < 2^31 - 16 and num_cus positive");
   const KernelSchedule S = kernel_cross_schedule(nrows, nsum, b, num_cus);
+  kernel_schedule_words({S.rows_per_block, S.nrow_blocks, S.col_blocks, S.ncol_chunks, S.nslabs, S.tiles_per_slab}, S.nslabs, S.slab_begin, kKernelCrossMaxSlabs, out);
+  return SLQ_OK;
+}
+
+// ---- random Fourier features of the kernel operator (schedule and kernel in slq_kernelfeature.hpp) ----------------
+struct slq_kernel_feature {
+  slq_context *ctx = nullptr;
+  slq_operator *op = nullptr;  // not owned: read at every product (its z, its s as they are then)
+  int dtype = SLQ_F64;
+  int64_t f2 = 0, f2pad = 0;
+  int d = 0, dpad = 0;
+  DevBuf omt;                  // Omega^T, k-major: dpad x f2pad, zeros in the padding
+  DevBuf scratch;              // slab partials: sized on first use, grown on demand
+  DevBuf stage_in, stage_out;  // device copies of the host panels of slq_kernel_feature_matmat (grown on demand)
+};
+
+template <typename F> static void kernel_feature_transpose(int64_t f2, int64_t f2pad, int d, const F *omega, int64_t ld, F *omt, int64_t *bad_row, int *bad_col) {
+  *bad_row = -1, *bad_col = 0;
+  for (int64_t j = 0; j < f2; ++j)
+    for (int k = 0; k < d; ++k) {
+      const F v = omega[j * ld + k];
+      if (!std::isfinite(v) && *bad_row < 0) *bad_row = j, *bad_col = k;
+      omt[(int64_t)k * f2pad + j] = v;
+    }
+}
+
+extern "C" int slq_kernel_feature_create(slq_context *ctx, slq_operator *op, int64_t F2, const void *omega, int64_t ld, slq_kernel_feature **out) {
+  if (!ctx || !op || !omega || !out) return fail(SLQ_EINVAL, "slq_kernel_feature_create: ctx/op/omega/out is NULL");
+  *out = nullptr;
+  if (op->kind == OP_KERNEL_PRECOND)
+    return fail(SLQ_EINVAL, "slq_kernel_feature_create: the operator is of kind 'kernel_precond': the features belong to the kernel operator it was built on (pass its base)");
+  if (op->kind != OP_KERNEL)
+    return fail(SLQ_EINVAL, "slq_kernel_feature_create: the operator is of kind '%s', not a kernel operator (slq_kernel_create)", op_kind_name(op->kind));
+  if (op->ctx != ctx) return fail(SLQ_EINVAL, "slq_kernel_feature_create: the operator belongs to another context");
+  if (ctx->dead) return fail(SLQ_EINVAL, "slq_kernel_feature_create: the context has been destroyed");
+  if (F2 < 1 || F2 > kKernelFeatureMaxFreq) return fail(SLQ_EINVAL, "slq_kernel_feature_create: F2 = %lld frequencies (1 <= F2 <= 2^30)", (long long)F2);
+  const int d = op->k_pts.d, dpad = op->k_pts.dpad;
+  if (ld < d) return fail(SLQ_EINVAL, "slq_kernel_feature_create: ld = %lld is below d = %d", (long long)ld, d);
+  HIP_TRY(hipSetDevice(ctx->device));
+  try {
+    std::unique_ptr<slq_kernel_feature> f(new slq_kernel_feature());
+    f->ctx = ctx, f->op = op, f->dtype = op->dtype, f->f2 = F2, f->f2pad = kernel_npad(F2), f->d = d, f->dpad = dpad;
+    const size_t es = esize(op->dtype), words = (size_t)dpad * (size_t)f->f2pad;
+    std::vector<char> host(words * es, 0);
+    int64_t bad_row;
+    int bad_col;
+    if (op->dtype == SLQ_F64) kernel_feature_transpose<double>(F2, f->f2pad, d, (const double *)omega, ld, (double *)host.data(), &bad_row, &bad_col);
+    else kernel_feature_transpose<float>(F2, f->f2pad, d, (const float *)omega, ld, (float *)host.data(), &bad_row, &bad_col);
+    if (bad_row >= 0)
+      return fail(SLQ_EINVAL, "slq_kernel_feature_create: frequency %lld, coordinate %d is not finite (frequencies must be finite)", (long long)bad_row, bad_col);
+    const hipError_t e = f->omt.alloc(words * es);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "slq_kernel_feature_create: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(f->omt.p, host.data(), words * es, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // (the host copy goes with this frame)
+    ctx_retain(ctx);
+    *out = f.release();
+  } catch (const std::bad_alloc &) {
+    return fail(SLQ_ENOMEM, "slq_kernel_feature_create: host allocation failed");
+  }
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_feature_destroy(slq_kernel_feature *f) {
+  if (!f) return SLQ_OK;
+  hipSetDevice(f->ctx->device);
+  hipStreamSynchronize(f->ctx->stream);
+  slq_context *ctx = f->ctx;
+  delete f;  // (every device array is a member that frees itself)
+  ctx_release(ctx);
+  return SLQ_OK;
+}
+
+// the row points of a product: the operator's own (cross NULL) or the new points of a cross object of the same operator
+static int kernel_feature_rows(const slq_kernel_feature *f, const slq_kernel_cross *cross, const char *who) {
+  if (cross && cross->op != f->op) return fail(SLQ_EINVAL, "%s: the cross object belongs to another operator than the feature map", who);
+  return SLQ_OK;
+}
+
+// Y = Phi W for device arrays (W 2 F2 x b, Y rows x b), on the stream. The caller has checked the shapes.
+static int kernel_feature_product_run(slq_kernel_feature *f, slq_kernel_cross *cross, const void *W, int64_t ldw, void *Y, int64_t ldy, int b, const char *who) {
+  const slq_operator *op = f->op;
+  if (cross && cross->epoch != op->k_epoch) SLQ_TRY(kernel_cross_rescale(cross));  // the hyperparameters have moved: z* follow, before this product
+  const KernelPoints &pts = cross ? cross->pts : op->k_pts;
+  const bool f64 = f->dtype == SLQ_F64;
+  const int64_t nrows = pts.n;
+  const KernelSchedule S = kernel_feature_schedule(nrows, f->f2, b, f->ctx->num_cus, f64);
+  if (S.ncol_chunks > 65535) return fail(SLQ_EINVAL, "%s: b = %d columns (at most %d)", who, b, 65535 * kernel_feature_chunk_cols(f64));
+  const size_t es = esize(f->dtype);
+  const int64_t slab_stride = nrows * (int64_t)b;
+  if (S.nslabs > 1) {
+    const size_t need = (size_t)S.nslabs * (size_t)slab_stride * es;
+    if (f->scratch.bytes() < need) {
+      const hipError_t e = f->scratch.alloc(need);
+      if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "%s: slab scratch of %zu bytes: %s", who, need, hipGetErrorString(e));
+    }
+  }
+  KernelFeatureArgs a;
+  a.nrows = (int)nrows, a.rpad = (int)pts.npad;
+  a.nfreq = (int)f->f2, a.fpad = (int)f->f2pad;
+  a.dq = f->dpad / 4;
+  a.rzt = pts.zt, a.rnrm = pts.nrm;
+  a.omt = f->omt.p;
+  a.params = op->k_pts.params;
+  a.W = W, a.ldw = ldw, a.b = b;
+  a.out = S.nslabs > 1 ? f->scratch.p : Y, a.ldo = S.nslabs > 1 ? nrows : ldy, a.slab_stride = slab_stride;
+  if (!kernel_feature_launch(f64, S, a, (void *)f->ctx->stream)) return fail(SLQ_EINVAL, "%s: no kernel for %d column tiles", who, S.col_blocks);
+  HIP_TRY(hipGetLastError());
+  if (S.nslabs > 1) {
+    kernel_cross_sum_launch(f64, nrows, b, S.nslabs, f->scratch.p, slab_stride, Y, ldy, (void *)f->ctx->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_feature_matmat(slq_kernel_feature *f, slq_kernel_cross *cross, const void *W, int64_t ldw, void *Y, int64_t ldy, int b) {
+  if (!f) return fail(SLQ_EINVAL, "slq_kernel_feature_matmat: feature map is NULL");
+  if (!W || !Y) return fail(SLQ_EINVAL, "slq_kernel_feature_matmat: W/Y is NULL");
+  SLQ_TRY(kernel_feature_rows(f, cross, "slq_kernel_feature_matmat"));
+  if (b < 1) return fail(SLQ_EINVAL, "slq_kernel_feature_matmat: b = %d columns (b >= 1)", b);
+  const int64_t rin = 2 * f->f2, rout = cross ? cross->pts.n : f->op->n;
+  if (ldw < rin) return fail(SLQ_EINVAL, "slq_kernel_feature_matmat: ldw = %lld is below the %lld rows of W (2 F2)", (long long)ldw, (long long)rin);
+  if (ldy < rout) return fail(SLQ_EINVAL, "slq_kernel_feature_matmat: ldy = %lld is below the %lld rows of Y", (long long)ldy, (long long)rout);
+  HIP_TRY(hipSetDevice(f->ctx->device));
+  const size_t es = esize(f->dtype);
+  const size_t need_in = (size_t)rin * b * es, need_out = (size_t)rout * b * es;
+  if (f->stage_in.bytes() < need_in) HIP_TRY(f->stage_in.alloc(need_in));
+  if (f->stage_out.bytes() < need_out) HIP_TRY(f->stage_out.alloc(need_out));
+  hipStream_t st = f->ctx->stream;
+  HIP_TRY(hipMemcpy2DAsync(f->stage_in.p, (size_t)rin * es, W, (size_t)ldw * es, (size_t)rin * es, (size_t)b, hipMemcpyHostToDevice, st));
+  SLQ_TRY(kernel_feature_product_run(f, cross, f->stage_in.p, rin, f->stage_out.p, rout, b, "slq_kernel_feature_matmat"));
+  HIP_TRY(hipMemcpy2DAsync(Y, (size_t)ldy * es, f->stage_out.p, (size_t)rout * es, (size_t)rout * es, (size_t)b, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_feature_dmat(slq_kernel_feature *f, slq_kernel_cross *cross, slq_dmat *IN, int i0, slq_dmat *OUT, int o0, int b) {
+  if (!f) return fail(SLQ_EINVAL, "slq_kernel_feature_dmat: feature map is NULL");
+  if (f->dtype != SLQ_F64) return fail(SLQ_EINVAL, "slq_kernel_feature_dmat: the feature map's dtype is fp32: the device matrices are fp64 (use slq_kernel_feature_matmat)");
+  SLQ_TRY(kernel_feature_rows(f, cross, "slq_kernel_feature_dmat"));
+  if (b < 1) return fail(SLQ_EINVAL, "slq_kernel_feature_dmat: b = %d columns (b >= 1)", b);
+  SLQ_TRY(dmat_range(IN, i0, b, "slq_kernel_feature_dmat(IN)"));
+  SLQ_TRY(dmat_range(OUT, o0, b, "slq_kernel_feature_dmat(OUT)"));
+  const int64_t rin = 2 * f->f2, rout = cross ? cross->pts.n : f->op->n;
+  if (IN->n != rin) return fail(SLQ_EINVAL, "slq_kernel_feature_dmat: IN has %lld rows, the product reads %lld (2 F2)", (long long)IN->n, (long long)rin);
+  if (OUT->n != rout) return fail(SLQ_EINVAL, "slq_kernel_feature_dmat: OUT has %lld rows, the product writes %lld", (long long)OUT->n, (long long)rout);
+  if (IN->ctx != f->ctx || OUT->ctx != f->ctx) return fail(SLQ_EINVAL, "slq_kernel_feature_dmat: a matrix belongs to another context");
+  if (IN == OUT && i0 < o0 + b && o0 < i0 + b) return fail(SLQ_EINVAL, "slq_kernel_feature_dmat: the columns [%d, %d) of IN and [%d, %d) of OUT overlap in one matrix", i0, i0 + b, o0, o0 + b);
+  HIP_TRY(hipSetDevice(f->ctx->device));
+  return kernel_feature_product_run(f, cross, IN->d + (size_t)i0 * IN->n, IN->n, OUT->d + (size_t)o0 * OUT->n, OUT->n, b, "slq_kernel_feature_dmat");
+}
+
+// Omega^T as the device holds it: dpad x F2pad in the object's dtype (tests: the padding must be zero)
+extern "C" int slq_debug_kernel_feature_frequencies(slq_kernel_feature *f, void *omega_t) {
+  if (!f || !omega_t) return fail(SLQ_EINVAL, "slq_debug_kernel_feature_frequencies: feature map / omega_t is NULL");
+  HIP_TRY(hipSetDevice(f->ctx->device));
+  HIP_TRY(hipStreamSynchronize(f->ctx->stream));
+  HIP_TRY(hipMemcpy(omega_t, f->omt.p, (size_t)f->dpad * (size_t)f->f2pad * esize(f->dtype), hipMemcpyDeviceToHost));
+  return SLQ_OK;
+}
+
+// kernel_feature_schedule() of slq_kernelfeature.hpp as an array, in the order of slq_debug_kernel_cross_schedule. No HIP call.
+extern "C" int slq_debug_kernel_feature_schedule(int64_t nrows, int64_t F2, int64_t b, int num_cus, int is_f64, int64_t *out, int nout) {
+  if (!out || nout < 6 + kKernelCrossMaxSlabs + 1) return fail(SLQ_EINVAL, "slq_debug_kernel_feature_schedule: room for %d values", 6 + kKernelCrossMaxSlabs + 1);
+  const int64_t lim = ((int64_t)1 << 31) - 16;
+  if (nrows <= 0 || nrows >= lim || F2 <= 0 || F2 > kKernelFeatureMaxFreq || b <= 0 || b >= lim || num_cus <= 0)
+    return fail(SLQ_EINVAL, "slq_debug_kernel_feature_schedule: 0 < nrows, b < 2^31 - 16, 0 < F2 <= 2^30 and num_cus positive");
+  const KernelSchedule S = kernel_feature_schedule(nrows, F2, b, num_cus, is_f64 != 0);
   kernel_schedule_words({S.rows_per_block, S.nrow_blocks, S.col_blocks, S.ncol_chunks, S.nslabs, S.tiles_per_slab}, S.nslabs, S.slab_begin, kKernelCrossMaxSlabs, out);
   return SLQ_OK;
 }

@@ -1320,6 +1320,84 @@ class KernelCross:
 			pass
 
 
+def kernel_feature_schedule(nrows: int, num_features: int, b: int, num_cus: int = 256, dtype=np.float64) -> dict:
+	"""The schedule of one feature product with `nrows` row points, `num_features` frequencies and `b` columns, as the library cuts it
+	(slq_debug_kernel_feature_schedule; host arithmetic, no device), in the form of `kernel_cross_schedule`: the column chunks are 128
+	wide in float64 and 256 in float32."""
+	out = (C.c_int64 * 71)()
+	check(_capi.lib().slq_debug_kernel_feature_schedule(int(nrows), int(num_features), int(b), int(num_cus), int(np.dtype(dtype) == np.float64), out, 71))
+	v = list(out)
+	return dict(rows=v[0], nrb=v[1], col_blocks=v[2], chunks=v[3], slabs=v[4], tiles_per_slab=v[5], begin=v[6 : 6 + v[4] + 1], rest=v[6 + v[4] + 1 :])
+
+
+class KernelFeatureMap:
+	"""Random Fourier features of a kernel operator's profile on the GPU, never formed (slq_kernel_feature_*):
+	`matmat(W)` is Phi W with Phi(z) = sqrt(s / F2) [cos(Omega z) | sin(Omega z)] at the operator's scaled points - or, with
+	`rows=` a KernelCross of the same operator, at its new points - for W of 2 F2 rows. `omega`: F2 x d, rounded once to the operator's
+	dtype (the map is defined on the rounded values, `self.omega`). op: a DeviceOperator of kind "kernel"; the object takes its dtype
+	and keeps it alive, as a plan does. `set_kernel_parameters` on the operator is honoured by the next product."""
+
+	def __init__(self, op: DeviceOperator, omega):
+		if getattr(op, "kind", None) != "kernel":
+			raise ValueError(f"KernelFeatureMap needs a kernel operator, not kind '{getattr(op, 'kind', None)}'")
+		self.op, self.ctx = op, op.ctx
+		self.dtype = np.dtype(op.dtype)
+		self.n, self.d = int(op.shape[0]), int(op.nnz // op.shape[0])
+		om = np.asarray(omega)
+		om = om.reshape(-1, 1) if om.ndim == 1 else om
+		if om.ndim != 2 or om.shape[1] != self.d or om.shape[0] < 1:
+			raise ValueError(f"the frequencies must be an (F2, {self.d}) array with F2 >= 1, got shape {om.shape}")
+		self.omega = np.ascontiguousarray(om, dtype=self.dtype)
+		self.num_features = int(self.omega.shape[0])
+		h = C.c_void_p()
+		check(_capi.lib().slq_kernel_feature_create(self.ctx._h, op._h, self.num_features, ptr(self.omega), self.d, C.byref(h)))
+		self._h = h
+
+	def _rows(self, rows) -> tuple:
+		if rows is None:
+			return None, self.n
+		if not isinstance(rows, KernelCross):
+			raise ValueError("rows must be None (the operator's points) or a KernelCross")
+		return rows._h, rows.m
+
+	def matmat(self, W: np.ndarray, rows: Optional["KernelCross"] = None) -> np.ndarray:
+		"""Phi W for a host array W (2 F2 x b), in the operator's dtype: n x b, or m x b at the new points of `rows`."""
+		rh, rout = self._rows(rows)
+		W = np.asarray(W)
+		W = W.reshape(-1, 1) if W.ndim == 1 else W
+		if W.ndim != 2 or W.shape[0] != 2 * self.num_features or W.shape[1] < 1:
+			raise ValueError(f"dimension mismatch: the product reads {2 * self.num_features} rows (2 F2), the operand has shape {W.shape}")
+		W = np.asfortranarray(W, dtype=self.dtype)
+		Y = np.empty((rout, W.shape[1]), dtype=self.dtype, order="F")
+		check(_capi.lib().slq_kernel_feature_matmat(self._h, rh, ptr(W), W.shape[0], ptr(Y), rout, W.shape[1]))
+		return Y
+
+	def matmat_dmat(self, IN: "DeviceMatrix", i0: int, OUT: "DeviceMatrix", o0: int, b: int, rows: Optional["KernelCross"] = None):
+		"""OUT[:, o0:o0+b] = Phi IN[:, i0:i0+b] between DeviceMatrix columns: fp64 only, asynchronous on the context stream."""
+		rh, _ = self._rows(rows)
+		check(_capi.lib().slq_kernel_feature_dmat(self._h, rh, IN._h, int(i0), OUT._h, int(o0), int(b)))
+
+	def frequencies(self) -> np.ndarray:
+		"""Omega (F2 x d) as the device holds it (slq_debug_kernel_feature_frequencies), in the operator's dtype. Sets
+		`padding_is_zero`: whether everything beyond d and F2 in the device array is 0, as the kernel relies on."""
+		dpad, fpad = (self.d + 3) // 4 * 4, (self.num_features + 15) // 16 * 16
+		omt = np.empty((dpad, fpad), dtype=self.dtype)
+		check(_capi.lib().slq_debug_kernel_feature_frequencies(self._h, ptr(omt)))
+		self.padding_is_zero = bool(not omt[self.d :].any() and not omt[:, self.num_features :].any())
+		return np.ascontiguousarray(omt[: self.d, : self.num_features].T)
+
+	def close(self):
+		if getattr(self, "_h", None):
+			_capi.lib().slq_kernel_feature_destroy(self._h)
+			self._h = None
+
+	def __del__(self):
+		try:
+			self.close()
+		except Exception:  # noqa: BLE001
+			pass
+
+
 def kernel_pointgrad_schedule(nrows: int, nsum: int, num_cus: int = 256) -> dict:
 	"""The schedule of one pass of a KernelPointGradAccumulator.update with `nrows` row points and `nsum` summed points, as the library
 	cuts it (slq_debug_kernel_pointgrad_schedule; host arithmetic, no device): rows per block, row blocks, factor columns per launch,

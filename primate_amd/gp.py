@@ -1,5 +1,5 @@
-"""Gaussian-process prediction, log-determinants and the marginal likelihood with its gradients on the matrix-free kernel operator
-(DESIGN.md §4.17, §4.18, §4.19).
+"""Gaussian-process prediction, log-determinants, the marginal likelihood with its gradients and posterior function samples on the
+matrix-free kernel operator.
 
 With A = K + noise I the operator of a `KernelOperator` on the training points X, C = outputscale * phi(r2(X*, X)) the
 cross-covariance to new points X* (`KernelOperator.cross`, engine.KernelCross) and s the outputscale,
@@ -638,3 +638,226 @@ def mll(K, y, rank: int = 100, deg: int = 20, solve_deg: Optional[int] = None, c
 		info["datafit_points"], info["logdet_points"] = fit_points, ld_points
 		grads["points"] = fit_points - 0.5 * q * ld_points
 	return value, grads, info
+
+
+## ---- posterior function samples by pathwise conditioning ----------------------------------------------------------
+SAMPLE_SOLVE_CHUNK = 128  # columns of one solve: a kept-basis plan of that many probes
+
+
+def _param_key(K) -> tuple:
+	return (tuple(np.ravel(np.asarray(K.lengthscale, dtype=np.float64)).tolist()), float(K.outputscale), float(K.noise))
+
+
+class PosteriorPaths:
+	"""`count` sample functions of a Gaussian process, each a function that can be evaluated and differentiated at any later points
+	(`sample_paths` makes them):
+
+	    f_c(x) = Phi(x) w_c + K(x, X) v_c,        v_c = A^-1 (y - Phi(X) w_c - sqrt(noise) eps_c)        (prior paths: the first term alone)
+
+	It holds on the device the feature map (engine.KernelFeatureMap), the weights W (2 F2 x count) and V (n x count; None for prior
+	paths), and keeps the device operator alive. Attributes: `features` (the KernelFeatures), `weights` (the host 2 F2 x count array),
+	`info` (deg, steps: the Lanczos steps of each solve chunk, rank, count, num_features). The hyperparameters are those at creation:
+	`evaluate` raises if K's have changed since - V belongs to that A. `close()` frees the device arrays; a context manager does."""
+
+	def __init__(self, K, op, features, fmap, weights, Wd, V, E, info):
+		self.K, self._op, self.features, self._fmap, self.weights, self._Wd, self._V, self._E, self.info = K, op, features, fmap, weights, Wd, V, E, info
+		self.count = int(weights.shape[1])
+		self._key = _param_key(K)
+
+	def noise_draws(self) -> Optional[np.ndarray]:
+		"""eps (n x count) as the solve used it, read back from the device; None where none was drawn (prior paths, noise = 0)."""
+		return None if self._E is None else self._E.get()
+
+	def evaluate(self, Xnew, grad: bool = False):
+		"""F (m x count), F[a, c] = f_c(x*_a), computed on the device: only the m x count result leaves it. grad=True: (F, dF) with
+		dF (m x d x count) = d f_c / d x*_a: the data term is the cross form of the point gradient with U a column of ones and W = v_c, one
+		column at a time; the feature term is the same feature product on the weights W'[j] = Omega_jk w_{F2+j}, W'[F2+j] = -Omega_jk w_j,
+		divided by the lengthscale of coordinate k."""
+		if self._fmap is None:
+			raise ValueError("the paths have been closed")
+		if _param_key(self.K) != self._key:
+			raise ValueError("the KernelOperator's hyperparameters have changed since these paths were drawn: V belongs to the A of then (draw new paths)")
+		Cop = self.K.cross(Xnew)  # (checks the shape and the values of the new points)
+		m, d = Cop.Xnew.shape
+		count, ctx = self.count, self._op.ctx
+		live = []
+
+		def keep(obj):
+			live.append(obj)
+			return obj
+
+		try:
+			cross = keep(Cop.device(self._op))
+			Fd = keep(engine.DeviceMatrix(m, count, ctx=ctx))
+			self._fmap.matmat_dmat(self._Wd, 0, Fd, 0, count, rows=cross)
+			if self._V is not None:
+				Td = keep(engine.DeviceMatrix(m, count, ctx=ctx))
+				cross.matmat_dmat(self._V, 0, Td, 0, count)
+				for c0 in range(0, count, SAMPLE_SOLVE_CHUNK):  # (the axpy we have: a product with an identity)
+					cb = min(SAMPLE_SOLVE_CHUNK, count - c0)
+					Fd.add_product(c0, Td, c0, np.eye(cb), alpha=1.0, beta=1.0)
+			F = Fd.get()
+			if not np.all(np.isfinite(F)):
+				raise FloatingPointError("evaluate: the paths' values are not finite")
+			if not grad:
+				return F
+			dF = np.zeros((m, d, count))
+			om = self.features.rounded().astype(np.float64)
+			F2 = om.shape[0]
+			ls = np.broadcast_to(np.asarray(self.K.lengthscale, dtype=np.float64), (d,))
+			Wk = keep(engine.DeviceMatrix(2 * F2, count, ctx=ctx))
+			for k in range(d):
+				Wk.set(0, np.vstack([om[:, k][:, None] * self.weights[F2:], -om[:, k][:, None] * self.weights[:F2]]))
+				self._fmap.matmat_dmat(Wk, 0, Fd, 0, count, rows=cross)
+				dF[:, k, :] = Fd.get() / ls[k]
+			if self._V is not None:
+				pacc, Ones = keep(engine.KernelPointGradAccumulator(cross)), keep(engine.DeviceMatrix(m, 1, ctx=ctx))
+				Ones.set(0, np.ones((m, 1)))
+				for c in range(count):
+					pacc.update(Ones, 0, self._V, c, 1, alpha=1.0, beta=0.0)
+					dF[:, :, c] += pacc.get()[0]
+			if not np.all(np.isfinite(dF)):
+				raise FloatingPointError("evaluate: the paths' gradients are not finite")
+			return F, dF
+		finally:
+			for obj in reversed(live):
+				obj.close()
+
+	def close(self):
+		for name in ("_E", "_V", "_Wd", "_fmap"):
+			obj = getattr(self, name, None)
+			if obj is not None:
+				obj.close()
+			setattr(self, name, None)
+
+	def __enter__(self):
+		return self
+
+	def __exit__(self, *exc):
+		self.close()
+
+	def __del__(self):
+		try:
+			self.close()
+		except Exception:  # noqa: BLE001
+			pass
+
+
+def sample_paths(K, y=None, count: int = 16, num_features: int = 2048, deg: int = 60, orth: Optional[int] = None, precond_rank: int = 0, seed=None,
+				 features=None, weights=None, noise_draws=None) -> PosteriorPaths:  # fmt: skip
+	"""`count` function samples of the Gaussian process with the kernel operator `K` (a `KernelOperator` in float64; its noise is the
+	observation noise) and zero prior mean, conditioned on the observations `y` ((n,)) at K's points - or of the prior, with y=None -
+	by pathwise conditioning with a random-feature prior (Matheron's rule; Wilson et al. 2020). For each sample c
+
+	    f_c(x) = Phi(x) w_c + K(x, X) v_c,        v_c = A^-1 (y - Phi(X) w_c - sqrt(noise) eps_c),        w_c ~ N(0, I),  eps_c ~ N(0, I)
+
+	with Phi the `num_features` paired random Fourier features of K's profile (`KernelOperator.features`; `features=` takes a
+	`KernelFeatures` instead of the draw). One feature product at the training points, the residual formed on the device, ONE solve
+	over `count` columns - kept-basis Lanczos plans of `deg` steps (`orth` vectors of re-orthogonalisation, None: all) on A, or on
+	`K.preconditioned(precond_rank)` as M B^-1 M for small noise - in chunks of at most 128 columns; V (n x count) stays on the device.
+	A V that is not finite raises FloatingPointError, as `posterior` does. y=None: no solve, no V. noise = 0 draws no eps.
+
+	Draws: `numpy.random.default_rng(seed)` gives the frequencies, then `weights` (2 F2 x count, standard normal), then the seed of eps;
+	eps (n x count) is drawn on the device (`DeviceMatrix.generate(pdf="normal")`), so that nothing of size n crosses the bus.
+	`weights=` and `noise_draws=` (a host n x count array) take explicit values, for tests.
+
+	Given the frequencies, the paths have the mean C A^-1 y exactly, whatever the frequencies, and the covariance
+	(Phi* - C A^-1 Phi_X)(...)^T + noise C A^-2 C^T, which tends to the posterior covariance as 1 / sqrt(F2).
+	Returns a `PosteriorPaths`: `.evaluate(Xnew, grad=False)`."""
+	from .operators import KernelFeatures, draw_kernel_frequencies
+
+	if getattr(K, "_slq_kind", None) != "kernel":
+		raise ValueError("sample_paths needs a KernelOperator")
+	if np.dtype(K.dtype) != np.float64:
+		raise ValueError(f"sample_paths is fp64 only (the device matrices are fp64): the KernelOperator is {np.dtype(K.dtype)}")
+	n, d = K.X.shape
+	count, deg, precond_rank = int(count), int(deg), int(precond_rank)
+	if count < 1 or deg < 1 or precond_rank < 0:
+		raise ValueError(f"count = {count} and deg = {deg} must be >= 1, precond_rank = {precond_rank} >= 0")
+	yh = None
+	if y is not None:
+		yh = np.asarray(y, dtype=np.float64)
+		if yh.shape != (n,):
+			raise ValueError(f"y must be ({n},), got shape {yh.shape} (multi-output y is not built)")
+		if not np.all(np.isfinite(yh)):
+			raise ValueError("y must be finite")
+	rng = np.random.default_rng(seed)
+	if features is None:
+		features = KernelFeatures(K, draw_kernel_frequencies(K.kernel, int(num_features), d, rng))
+	elif not isinstance(features, KernelFeatures) or features.K is not K:
+		raise ValueError("features must be a KernelFeatures of this KernelOperator (K.features(...))")
+	F2 = features.num_features
+	if weights is None:
+		Wh = rng.standard_normal((2 * F2, count))
+	else:
+		Wh = np.array(weights, dtype=np.float64)
+		if Wh.shape != (2 * F2, count) or not np.all(np.isfinite(Wh)):
+			raise ValueError(f"weights must be a finite (2 F2, count) = ({2 * F2}, {count}) array, got shape {Wh.shape}")
+	eps_seed = int(rng.integers(0, 2**63 - 1))
+	sigma2 = float(K.noise)
+	Eh = None
+	if noise_draws is not None:
+		Eh = np.asarray(noise_draws, dtype=np.float64)
+		if Eh.shape != (n, count) or not np.all(np.isfinite(Eh)):
+			raise ValueError(f"noise_draws must be a finite (n, count) = ({n}, {count}) array, got shape {Eh.shape}")
+
+	op = _as_device_operator(K, dtype=np.float64)
+	ctx = op.ctx
+	orth_arg = -1 if orth is None else int(orth)
+	info = dict(deg=min(deg, n), steps=[], rank=0, count=count, num_features=F2)
+	kept, live = [], []
+	try:
+		fmap = features.device(op)
+		kept.append(fmap)
+		Wd = engine.DeviceMatrix(2 * F2, count, ctx=ctx)
+		kept.append(Wd)
+		Wd.set(0, Wh)
+		V = E = None
+		if yh is not None:
+			pop = _as_device_operator(K.preconditioned(precond_rank), dtype=np.float64) if precond_rank > 0 else None
+			if pop is not None:
+				info["rank"] = int(pop.info()["rank"])
+			solve_op = op if pop is None else pop
+			## the residual y - Phi W - sqrt(noise) E, on the device
+			R = engine.DeviceMatrix(n, count, ctx=ctx)
+			live.append(R)
+			fmap.matmat_dmat(Wd, 0, R, 0, count)
+			Yd = engine.DeviceMatrix(n, 1, ctx=ctx)
+			live.append(Yd)
+			Yd.set(0, yh.reshape(-1, 1))
+			R.add_product(0, Yd, 0, np.ones((1, count)), alpha=1.0, beta=-1.0)
+			if sigma2 > 0.0:
+				E = engine.DeviceMatrix(n, count, ctx=ctx)
+				kept.append(E)
+				if Eh is not None:
+					E.set(0, Eh)
+				else:
+					E.generate(0, count, pdf="normal", seed=eps_seed)
+				for c0 in range(0, count, SAMPLE_SOLVE_CHUNK):  # (the axpy we have: a product with an identity)
+					cb = min(SAMPLE_SOLVE_CHUNK, count - c0)
+					R.add_product(c0, E, c0, np.eye(cb), alpha=-float(np.sqrt(sigma2)), beta=1.0)
+			V = engine.DeviceMatrix(n, count, ctx=ctx)
+			kept.append(V)
+			plans = {}
+			for c0 in range(0, count, SAMPLE_SOLVE_CHUNK):
+				cb = min(SAMPLE_SOLVE_CHUNK, count - c0)
+				if cb not in plans:  # a plan of cb probes with its right-hand sides, its solution and the preconditioned path's scratch
+					plan = engine.LanczosPlan(solve_op, cb, deg, orth_arg, basis="keep")
+					live.append(plan)
+					mats = [engine.DeviceMatrix(n, cb, ctx=ctx) for _ in range(2 if pop is None else 4)]
+					live.extend(mats)
+					plans[cb] = (plan, mats[0], mats[1], tuple(mats[2:]) or None)
+				plan, rhs, sol, tmp = plans[cb]
+				rhs.copy_from(0, R, c0, cb)
+				_solve_into(pop, plan, rhs, sol, cb, tmp, 0.0)
+				info["steps"].append(plan.steps_done)
+				V.copy_from(c0, sol, 0, cb)
+				g = np.diag(sol.tn(0, cb, sol, 0, cb))  # (cb x cb on the host: nothing of size n leaves the device)
+				if not np.all(np.isfinite(g)):
+					raise FloatingPointError(f"sample_paths: V is not finite in the columns [{c0}, {c0 + cb}) (a Lanczos run stopped before `deg` steps, which the 'inv' action does not survive: lower deg)")
+		paths = PosteriorPaths(K, op, features, fmap, Wh, Wd, V, E, info)
+		kept = []
+		return paths
+	finally:
+		for obj in reversed(live + kept):
+			obj.close()

@@ -503,6 +503,68 @@ class KernelOperator(LinearOperator):
 		(m, n). It follows this operator's hyperparameters, whenever they are set."""
 		return KernelCrossOperator(self, Xnew)
 
+	def features(self, num_features: int = 2048, seed=None, frequencies=None) -> "KernelFeatures":
+		"""Random Fourier features of this operator's profile: a host value `KernelFeatures` with `num_features`
+		frequencies drawn from the profile's spectral measure by `numpy.random.default_rng(seed)` - or the explicit `frequencies`
+		(F2 x d) instead of the draw. Host-only: no GPU, no library. `.device(op)` is the product on the GPU."""
+		if frequencies is not None:
+			return KernelFeatures(self, frequencies)
+		return KernelFeatures(self, draw_kernel_frequencies(self.kernel, int(num_features), self.X.shape[1], np.random.default_rng(seed)))
+
+
+def draw_kernel_frequencies(kernel: str, num_features: int, d: int, rng) -> np.ndarray:
+	"""F2 x d frequencies of the profile's spectral measure in the scaled coordinates, float64, in ONE defined order of draws from
+	`rng`: G = standard_normal((F2, d)); rbf: Omega = G; matern with 2 nu in {1, 3, 5}: then u = chisquare(2 nu, F2) and
+	Omega_j = G_j sqrt(2 nu / u_j) - the multivariate Student-t with 2 nu degrees of freedom."""
+	if kernel not in KERNEL_PROFILES:
+		raise ValueError(f"unknown profile {kernel!r} (one of {', '.join(KERNEL_PROFILES)})")
+	if num_features < 1:
+		raise ValueError(f"num_features = {num_features} must be >= 1")
+	G = rng.standard_normal((num_features, d))
+	if kernel == "rbf":
+		return G
+	dof = {"matern12": 1.0, "matern32": 3.0, "matern52": 5.0}[kernel]
+	u = rng.chisquare(dof, num_features)
+	return G * np.sqrt(dof / u)[:, None]
+
+
+class KernelFeatures:
+	"""The feature map Phi(z) = sqrt(s / F2) [cos(Omega z) | sin(Omega z)] of a KernelOperator `K` as a host value:
+	`omega` (float64, F2 x d), the profile's name, and K itself for its scaled points and outputscale of now. Paired features, no random
+	phase: Phi(z) Phi(z')^T = (s / F2) sum_j cos(omega_j.(z - z')) is exactly stationary, its diagonal exactly s. The map is DEFINED on
+	`rounded()`, Omega rounded once to K's dtype. `matrix(Xnew)` is the host model in float64; `device(op)` the product on the GPU
+	(engine.KernelFeatureMap)."""
+
+	def __init__(self, K: "KernelOperator", omega):
+		if getattr(K, "_slq_kind", None) != "kernel":
+			raise ValueError("KernelFeatures needs a KernelOperator")
+		d = K.X.shape[1]
+		om = np.array(omega, dtype=np.float64)
+		om = om.reshape(-1, 1) if om.ndim == 1 else om
+		if om.ndim != 2 or om.shape[1] != d or om.shape[0] < 1:
+			raise ValueError(f"the frequencies must be an (F2, {d}) array with F2 >= 1, got shape {om.shape}")
+		if not np.all(np.isfinite(om)):
+			j, k = (int(v) for v in np.argwhere(~np.isfinite(om))[0])
+			raise ValueError(f"kernel features: frequency {j}, coordinate {k} is {om[j, k]} (frequencies must be finite)")
+		self.K, self.kernel, self.omega = K, K.kernel, om
+		self.num_features = int(om.shape[0])
+		self.dtype = np.dtype(K.dtype)
+
+	def rounded(self) -> np.ndarray:
+		"""Omega rounded once to the operator's dtype: what the device holds."""
+		return self.omega.astype(self.dtype)
+
+	def matrix(self, Xnew=None) -> np.ndarray:
+		"""Phi in float64 from the definition, rows x 2 F2, at K's points (None) or at new points (K's centre and lengthscales of now)."""
+		z = (self.K.scaled_points() if Xnew is None else self.K.cross(Xnew).scaled_points()).astype(np.float64)
+		g = z @ self.rounded().astype(np.float64).T
+		return np.sqrt(self.K.outputscale / self.num_features) * np.hstack([np.cos(g), np.sin(g)])
+
+	def device(self, op=None) -> "engine.KernelFeatureMap":
+		"""The product on the GPU: an engine.KernelFeatureMap over `op` (default: K's cached device operator)."""
+		op = _as_device_operator(self.K, dtype=self.dtype) if op is None else op
+		return engine.KernelFeatureMap(op, self.omega)
+
 
 KERNEL_PRECOND_MAX_RANK = 256
 
