@@ -592,6 +592,19 @@ int slq_kernel_feature_dmat(slq_kernel_feature *feat, slq_kernel_cross *cross, s
 int slq_kernel_feature_destroy(slq_kernel_feature *feat);
 int slq_debug_kernel_feature_frequencies(slq_kernel_feature *feat, void *omega_t);
 int slq_debug_kernel_feature_schedule(int64_t nrows, int64_t F2, int64_t b, int num_cus, int is_f64, int64_t *out, int nout);
+/* The adjoint of the map (csrc/slq_kernelfeatureadj.hpp): Z = Phi^T U,
+ *   Z[j, c] = a sum_i cos g_ij U[i, c],     Z[F2 + j, c] = a sum_i sin g_ij U[i, c]
+ * for U of n rows (or m, with a cross object of the same operator) and Z of 2 F2 rows in the row order of the forward product's W.
+ * slq_kernel_feature_rmatmat: host panels in the object's dtype, column-major; U rows x b (ldu >= rows), Z 2 F2 x b (ldz >= 2 F2).
+ *   Synchronises.
+ * slq_kernel_feature_rdmat: the same on columns [i0, i0 + b) of IN (n or m rows) and [o0, o0 + b) of OUT (2 F2 rows), asynchronous
+ *   on the context's stream; fp64 objects only. The same bits as the host entry.
+ * Deterministic; s is read from the operator at every product. Refusals (SLQ_EINVAL, nothing launched) mirror the forward entries.
+ * slq_debug_kernel_feature_adjoint_schedule: the schedule of one adjoint product (kernel_feature_adjoint_schedule: row blocks of
+ *   the frequencies, slabs of the row points) in the out-array convention of slq_debug_kernel_feature_schedule. No device. */
+int slq_kernel_feature_rmatmat(slq_kernel_feature *feat, slq_kernel_cross *cross, const void *U, int64_t ldu, void *Z, int64_t ldz, int b);
+int slq_kernel_feature_rdmat(slq_kernel_feature *feat, slq_kernel_cross *cross, slq_dmat *IN, int i0, slq_dmat *OUT, int o0, int b);
+int slq_debug_kernel_feature_adjoint_schedule(int64_t F2, int64_t nrows, int64_t b, int num_cus, int is_f64, int64_t *out, int nout);
 
 /* ---- pivoted-Cholesky preconditioner of a kernel operator (csrc/slq_kernelprecond.hpp), fp64 only ----
  * K0 = s phi(r2) is the kernel matrix without noise, A = K0 + sigma2 I (sigma2 > 0). L (n x r, r <= rank_max <= 256) is the

@@ -144,6 +144,9 @@ _SIGNATURES = {
 	"slq_kernel_feature_destroy": (C.c_int, [_P]),
 	"slq_debug_kernel_feature_frequencies": (C.c_int, [_P, _P]),
 	"slq_debug_kernel_feature_schedule": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+	"slq_kernel_feature_rmatmat": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int64, C.c_int]),
+	"slq_kernel_feature_rdmat": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_int]),
+	"slq_debug_kernel_feature_adjoint_schedule": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int]),
 	"slq_kernel_precond_create": (C.c_int, [_P, _P, C.c_int, C.c_double, _PP]),
 	"slq_kernel_precond_refresh": (C.c_int, [_P]),
 	"slq_kernel_precond_info": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -41,6 +41,7 @@
 #include "slq_kernelgrad.hpp"  // hyperparameter gradients of the kernel operator (slq_kernel_grad_*): schedule, k_kernel_grad, k_kernel_grad_sum
 #include "slq_kernelcross.hpp"  // cross-covariance products (slq_kernel_cross_*): schedule, the launch functions of slq_kernelcross.hip
 #include "slq_kernelfeature.hpp"  // random Fourier features (slq_kernel_feature_*): schedule, the launch function of slq_kernelfeature.hip
+#include "slq_kernelfeatureadj.hpp"  // their adjoint (slq_kernel_feature_rmatmat / _rdmat): schedule, the launch function of slq_kernelfeatureadj.hip
 #include "slq_kernelpointgrad.hpp"  // gradients in the points (slq_kernel_pointgrad_*): schedule, the launch functions of slq_kernelpointgrad.hip
 #include "slq_operator.hpp"  // the operator handle and the values it owns (DevBuf, CsrArrays, TileStream, KernelPoints)
 
@@ -4527,6 +4528,90 @@ extern "C" int slq_kernel_feature_dmat(slq_kernel_feature *f, slq_kernel_cross *
   if (IN == OUT && i0 < o0 + b && o0 < i0 + b) return fail(SLQ_EINVAL, "slq_kernel_feature_dmat: the columns [%d, %d) of IN and [%d, %d) of OUT overlap in one matrix", i0, i0 + b, o0, o0 + b);
   HIP_TRY(hipSetDevice(f->ctx->device));
   return kernel_feature_product_run(f, cross, IN->d + (size_t)i0 * IN->n, IN->n, OUT->d + (size_t)o0 * OUT->n, OUT->n, b, "slq_kernel_feature_dmat");
+}
+
+// Z = Phi^T U for device arrays (U rows x b, Z 2 F2 x b), on the stream. The caller has checked the shapes.
+static int kernel_feature_adjoint_run(slq_kernel_feature *f, slq_kernel_cross *cross, const void *U, int64_t ldu, void *Z, int64_t ldz, int b, const char *who) {
+  const slq_operator *op = f->op;
+  if (cross && cross->epoch != op->k_epoch) SLQ_TRY(kernel_cross_rescale(cross));  // the hyperparameters have moved: z* follow, before this product
+  const KernelPoints &pts = cross ? cross->pts : op->k_pts;
+  const bool f64 = f->dtype == SLQ_F64;
+  const int64_t nrows = pts.n, rout = 2 * f->f2;
+  const KernelSchedule S = kernel_feature_adjoint_schedule(f->f2, nrows, b, f->ctx->num_cus, f64);
+  if (S.ncol_chunks > 65535) return fail(SLQ_EINVAL, "%s: b = %d columns (at most %d)", who, b, 65535 * kernel_feature_adjoint_chunk_cols(f64));
+  const size_t es = esize(f->dtype);
+  const int64_t slab_stride = rout * (int64_t)b;
+  if (S.nslabs > 1) {
+    const size_t need = (size_t)S.nslabs * (size_t)slab_stride * es;
+    if (f->scratch.bytes() < need) {
+      const hipError_t e = f->scratch.alloc(need);
+      if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "%s: slab scratch of %zu bytes: %s", who, need, hipGetErrorString(e));
+    }
+  }
+  KernelFeatureAdjArgs a;
+  a.nfreq = (int)f->f2, a.fpad = (int)f->f2pad;
+  a.nrows = (int)nrows, a.rpad = (int)pts.npad;
+  a.dq = f->dpad / 4;
+  a.omt = f->omt.p, a.rzt = pts.zt;
+  a.params = op->k_pts.params;
+  a.U = U, a.ldu = ldu, a.b = b;
+  a.out = S.nslabs > 1 ? f->scratch.p : Z, a.ldo = S.nslabs > 1 ? rout : ldz, a.slab_stride = slab_stride;
+  if (!kernel_feature_adjoint_launch(f64, S, a, (void *)f->ctx->stream)) return fail(SLQ_EINVAL, "%s: no kernel for %d column tiles", who, S.col_blocks);
+  HIP_TRY(hipGetLastError());
+  if (S.nslabs > 1) {
+    kernel_cross_sum_launch(f64, rout, b, S.nslabs, f->scratch.p, slab_stride, Z, ldz, (void *)f->ctx->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_feature_rmatmat(slq_kernel_feature *f, slq_kernel_cross *cross, const void *U, int64_t ldu, void *Z, int64_t ldz, int b) {
+  if (!f) return fail(SLQ_EINVAL, "slq_kernel_feature_rmatmat: feature map is NULL");
+  if (!U || !Z) return fail(SLQ_EINVAL, "slq_kernel_feature_rmatmat: U/Z is NULL");
+  SLQ_TRY(kernel_feature_rows(f, cross, "slq_kernel_feature_rmatmat"));
+  if (b < 1) return fail(SLQ_EINVAL, "slq_kernel_feature_rmatmat: b = %d columns (b >= 1)", b);
+  const int64_t rin = cross ? cross->pts.n : f->op->n, rout = 2 * f->f2;
+  if (ldu < rin) return fail(SLQ_EINVAL, "slq_kernel_feature_rmatmat: ldu = %lld is below the %lld rows of U", (long long)ldu, (long long)rin);
+  if (ldz < rout) return fail(SLQ_EINVAL, "slq_kernel_feature_rmatmat: ldz = %lld is below the %lld rows of Z (2 F2)", (long long)ldz, (long long)rout);
+  HIP_TRY(hipSetDevice(f->ctx->device));
+  const size_t es = esize(f->dtype);
+  const size_t need_in = (size_t)rin * b * es, need_out = (size_t)rout * b * es;
+  if (f->stage_in.bytes() < need_in) HIP_TRY(f->stage_in.alloc(need_in));
+  if (f->stage_out.bytes() < need_out) HIP_TRY(f->stage_out.alloc(need_out));
+  hipStream_t st = f->ctx->stream;
+  HIP_TRY(hipMemcpy2DAsync(f->stage_in.p, (size_t)rin * es, U, (size_t)ldu * es, (size_t)rin * es, (size_t)b, hipMemcpyHostToDevice, st));
+  SLQ_TRY(kernel_feature_adjoint_run(f, cross, f->stage_in.p, rin, f->stage_out.p, rout, b, "slq_kernel_feature_rmatmat"));
+  HIP_TRY(hipMemcpy2DAsync(Z, (size_t)ldz * es, f->stage_out.p, (size_t)rout * es, (size_t)rout * es, (size_t)b, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return SLQ_OK;
+}
+
+extern "C" int slq_kernel_feature_rdmat(slq_kernel_feature *f, slq_kernel_cross *cross, slq_dmat *IN, int i0, slq_dmat *OUT, int o0, int b) {
+  if (!f) return fail(SLQ_EINVAL, "slq_kernel_feature_rdmat: feature map is NULL");
+  if (f->dtype != SLQ_F64) return fail(SLQ_EINVAL, "slq_kernel_feature_rdmat: the feature map's dtype is fp32: the device matrices are fp64 (use slq_kernel_feature_rmatmat)");
+  SLQ_TRY(kernel_feature_rows(f, cross, "slq_kernel_feature_rdmat"));
+  if (b < 1) return fail(SLQ_EINVAL, "slq_kernel_feature_rdmat: b = %d columns (b >= 1)", b);
+  SLQ_TRY(dmat_range(IN, i0, b, "slq_kernel_feature_rdmat(IN)"));
+  SLQ_TRY(dmat_range(OUT, o0, b, "slq_kernel_feature_rdmat(OUT)"));
+  const int64_t rin = cross ? cross->pts.n : f->op->n, rout = 2 * f->f2;
+  if (IN->n != rin) return fail(SLQ_EINVAL, "slq_kernel_feature_rdmat: IN has %lld rows, the product reads %lld", (long long)IN->n, (long long)rin);
+  if (OUT->n != rout) return fail(SLQ_EINVAL, "slq_kernel_feature_rdmat: OUT has %lld rows, the product writes %lld (2 F2)", (long long)OUT->n, (long long)rout);
+  if (IN->ctx != f->ctx || OUT->ctx != f->ctx) return fail(SLQ_EINVAL, "slq_kernel_feature_rdmat: a matrix belongs to another context");
+  if (IN == OUT && i0 < o0 + b && o0 < i0 + b) return fail(SLQ_EINVAL, "slq_kernel_feature_rdmat: the columns [%d, %d) of IN and [%d, %d) of OUT overlap in one matrix", i0, i0 + b, o0, o0 + b);
+  HIP_TRY(hipSetDevice(f->ctx->device));
+  return kernel_feature_adjoint_run(f, cross, IN->d + (size_t)i0 * IN->n, IN->n, OUT->d + (size_t)o0 * OUT->n, OUT->n, b, "slq_kernel_feature_rdmat");
+}
+
+// kernel_feature_adjoint_schedule() of slq_kernelfeatureadj.hpp as an array, in the order of slq_debug_kernel_feature_schedule (the
+// row blocks are those of the frequencies, the slabs those of the row points). No HIP call.
+extern "C" int slq_debug_kernel_feature_adjoint_schedule(int64_t F2, int64_t nrows, int64_t b, int num_cus, int is_f64, int64_t *out, int nout) {
+  if (!out || nout < 6 + kKernelCrossMaxSlabs + 1) return fail(SLQ_EINVAL, "slq_debug_kernel_feature_adjoint_schedule: room for %d values", 6 + kKernelCrossMaxSlabs + 1);
+  const int64_t lim = ((int64_t)1 << 31) - 16;
+  if (nrows <= 0 || nrows >= lim || F2 <= 0 || F2 > kKernelFeatureMaxFreq || b <= 0 || b >= lim || num_cus <= 0)
+    return fail(SLQ_EINVAL, "slq_debug_kernel_feature_adjoint_schedule: 0 < nrows, b < 2^31 - 16, 0 < F2 <= 2^30 and num_cus positive");
+  const KernelSchedule S = kernel_feature_adjoint_schedule(F2, nrows, b, num_cus, is_f64 != 0);
+  kernel_schedule_words({S.rows_per_block, S.nrow_blocks, S.col_blocks, S.ncol_chunks, S.nslabs, S.tiles_per_slab}, S.nslabs, S.slab_begin, kKernelCrossMaxSlabs, out);
+  return SLQ_OK;
 }
 
 // Omega^T as the device holds it: dpad x F2pad in the object's dtype (tests: the padding must be zero)

@@ -1330,6 +1330,19 @@ def kernel_feature_schedule(nrows: int, num_features: int, b: int, num_cus: int 
 	return dict(rows=v[0], nrb=v[1], col_blocks=v[2], chunks=v[3], slabs=v[4], tiles_per_slab=v[5], begin=v[6 : 6 + v[4] + 1], rest=v[6 + v[4] + 1 :])
 
 
+def kernel_feature_adjoint_schedule(num_features: int, nrows: int, b: int, num_cus: int = 256, dtype=np.float64) -> dict:
+	"""The schedule of one adjoint feature product Phi^T U with `num_features` frequencies (the row blocks), `nrows` row points (the
+	slabs) and `b` columns, as the library cuts it (slq_debug_kernel_feature_adjoint_schedule; host arithmetic, no device), in the form
+	of `kernel_feature_schedule`: the column chunks are 128 wide in float64 and 256 in float32."""
+	out = (C.c_int64 * 71)()
+	check(_capi.lib().slq_debug_kernel_feature_adjoint_schedule(int(num_features), int(nrows), int(b), int(num_cus), int(np.dtype(dtype) == np.float64), out, 71))
+	v = list(out)
+	return dict(rows=v[0], nrb=v[1], col_blocks=v[2], chunks=v[3], slabs=v[4], tiles_per_slab=v[5], begin=v[6 : 6 + v[4] + 1], rest=v[6 + v[4] + 1 :])
+
+
+GRAM_CHUNK = 128  # identity columns of one forward + adjoint pair of KernelFeatureMap.gram: the fp64 column chunk of both kernels
+
+
 class KernelFeatureMap:
 	"""Random Fourier features of a kernel operator's profile on the GPU, never formed (slq_kernel_feature_*):
 	`matmat(W)` is Phi W with Phi(z) = sqrt(s / F2) [cos(Omega z) | sin(Omega z)] at the operator's scaled points - or, with
@@ -1376,6 +1389,60 @@ class KernelFeatureMap:
 		"""OUT[:, o0:o0+b] = Phi IN[:, i0:i0+b] between DeviceMatrix columns: fp64 only, asynchronous on the context stream."""
 		rh, _ = self._rows(rows)
 		check(_capi.lib().slq_kernel_feature_dmat(self._h, rh, IN._h, int(i0), OUT._h, int(o0), int(b)))
+
+	def rmatmat(self, U: np.ndarray, rows: Optional["KernelCross"] = None) -> np.ndarray:
+		"""Phi^T U for a host array U (n x b, or m x b with the new points of `rows`), in the operator's dtype: 2 F2 x b, the cosine rows
+		first (slq_kernel_feature_rmatmat)."""
+		rh, rin = self._rows(rows)
+		U = np.asarray(U)
+		U = U.reshape(-1, 1) if U.ndim == 1 else U
+		if U.ndim != 2 or U.shape[0] != rin or U.shape[1] < 1:
+			raise ValueError(f"dimension mismatch: the adjoint product reads {rin} rows, the operand has shape {U.shape}")
+		U = np.asfortranarray(U, dtype=self.dtype)
+		rout = 2 * self.num_features
+		Z = np.empty((rout, U.shape[1]), dtype=self.dtype, order="F")
+		check(_capi.lib().slq_kernel_feature_rmatmat(self._h, rh, ptr(U), U.shape[0], ptr(Z), rout, U.shape[1]))
+		return Z
+
+	def rmatmat_dmat(self, IN: "DeviceMatrix", i0: int, OUT: "DeviceMatrix", o0: int, b: int, rows: Optional["KernelCross"] = None):
+		"""OUT[:, o0:o0+b] = Phi^T IN[:, i0:i0+b] between DeviceMatrix columns: fp64 only, asynchronous on the context stream."""
+		rh, _ = self._rows(rows)
+		check(_capi.lib().slq_kernel_feature_rdmat(self._h, rh, IN._h, int(i0), OUT._h, int(o0), int(b)))
+
+	def gram(self, rows: Optional["KernelCross"] = None, chunk: int = GRAM_CHUNK) -> np.ndarray:
+		"""Phi^T Phi (2 F2 x 2 F2, host float64) formed on the device without Phi: for each `chunk` of identity columns a forward product
+		into an nrows x chunk scratch DeviceMatrix, the adjoint of that into 2 F2 x chunk, and that block read back. fp64 only. Returns
+		the symmetrised (G + G^T) / 2; `gram_asymmetry` is the largest |G - G^T| seen."""
+		if self.dtype != np.float64:
+			raise ValueError(f"gram is fp64 only (the device matrices are fp64): the feature map is {self.dtype}")
+		chunk = int(chunk)
+		if chunk < 1:
+			raise ValueError(f"chunk = {chunk} must be >= 1")
+		_, nrows = self._rows(rows)
+		m2 = 2 * self.num_features
+		chunk = min(chunk, m2)
+		G = np.empty((m2, m2))
+		live = []
+		try:
+			Id = DeviceMatrix(m2, chunk, ctx=self.ctx)
+			live.append(Id)
+			T = DeviceMatrix(nrows, chunk, ctx=self.ctx)
+			live.append(T)
+			Zd = DeviceMatrix(m2, chunk, ctx=self.ctx)
+			live.append(Zd)
+			for c0 in range(0, m2, chunk):
+				cb = min(chunk, m2 - c0)
+				E = np.zeros((m2, cb))
+				E[c0 + np.arange(cb), np.arange(cb)] = 1.0
+				Id.set(0, E)
+				self.matmat_dmat(Id, 0, T, 0, cb, rows=rows)
+				self.rmatmat_dmat(T, 0, Zd, 0, cb, rows=rows)
+				G[:, c0 : c0 + cb] = Zd.get(0, cb)
+		finally:
+			for obj in reversed(live):
+				obj.close()
+		self.gram_asymmetry = float(np.max(np.abs(G - G.T)))
+		return 0.5 * (G + G.T)
 
 	def frequencies(self) -> np.ndarray:
 		"""Omega (F2 x d) as the device holds it (slq_debug_kernel_feature_frequencies), in the operator's dtype. Sets

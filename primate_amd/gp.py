@@ -861,3 +861,179 @@ def sample_paths(K, y=None, count: int = 16, num_features: int = 2048, deg: int 
 	finally:
 		for obj in reversed(live + kept):
 			obj.close()
+
+
+## ---- weight-space regression with the feature model K ~ Phi Phi^T -------------------------------------------------
+FEATURE_POSTERIOR_MAX_WEIGHTS = 8192  # 2 F2: the weight-space system is factorised on the host by NumPy
+FEATURE_PREDICT_CHUNK = 128  # columns of L^-T per feature product of the predictive variance
+
+
+class FeaturePosterior:
+	"""The Gaussian process with the kernel Phi Phi^T in the place of K's (`feature_posterior` makes it): w ~ N(0, I),
+	y = Phi w + noise. Attributes: `mll` (the log marginal likelihood of that model), `mean_weights` (w_bar = M^-1 Phi^T y, M = Phi^T Phi
+	+ sigma2 I = L L^T), `features` (the KernelFeatures), `info` (num_features, gram_asymmetry, m_diag_min, m_diag_max). The
+	hyperparameters are those at creation: `predict` and `sample_paths` raise if K's have changed since. `close()` frees the device
+	feature map; a context manager does."""
+
+	def __init__(self, K, op, features, fmap, L, mean_weights, mll, info):
+		self.K, self._op, self.features, self._fmap, self._L = K, op, features, fmap, L
+		self.mean_weights, self.mll, self.info = mean_weights, float(mll), info
+		self._sigma2 = float(K.noise)
+		self._key = _param_key(K)
+
+	def _check(self, who: str):
+		if self._fmap is None:
+			raise ValueError("the feature posterior has been closed")
+		if _param_key(self.K) != self._key:
+			raise ValueError(f"{who}: the KernelOperator's hyperparameters have changed since this feature posterior was made: its weights belong to the Phi of then (make a new one)")
+
+	def predict(self, Xnew, variance: bool = True, include_noise: bool = False) -> tuple:
+		"""(mean, var) at the new points (m x d): mean = Phi(X*) w_bar, one feature product; var = sigma2 |L^-1 phi*|^2, feature products
+		on column chunks of L^-T with the row sums of squares of the m x chunk blocks accumulated on the host (None with variance=False);
+		include_noise adds sigma2."""
+		from scipy.linalg import solve_triangular
+
+		self._check("predict")
+		Cop = self.K.cross(Xnew)  # (checks the shape and the values of the new points)
+		m = Cop.Xnew.shape[0]
+		m2, ctx = self.mean_weights.shape[0], self._op.ctx
+		live = []
+		try:
+			cross = Cop.device(self._op)
+			live.append(cross)
+			chunk = min(FEATURE_PREDICT_CHUNK, m2)
+			Wd = engine.DeviceMatrix(m2, chunk, ctx=ctx)
+			live.append(Wd)
+			Fd = engine.DeviceMatrix(m, chunk, ctx=ctx)
+			live.append(Fd)
+			Wd.set(0, np.hstack([self.mean_weights[:, None], np.zeros((m2, chunk - 1))]))
+			self._fmap.matmat_dmat(Wd, 0, Fd, 0, 1, rows=cross)
+			mean = Fd.get(0, 1)[:, 0].copy()
+			var = None
+			if variance:
+				acc = np.zeros(m)
+				for c0 in range(0, m2, chunk):
+					cb = min(chunk, m2 - c0)
+					E = np.zeros((m2, cb))
+					E[c0 + np.arange(cb), np.arange(cb)] = 1.0
+					B = solve_triangular(self._L, E, lower=True, trans="T", check_finite=False)  # columns [c0, c0 + cb) of L^-T
+					Wd.set(0, np.hstack([B, np.zeros((m2, chunk - cb))]))
+					self._fmap.matmat_dmat(Wd, 0, Fd, 0, cb, rows=cross)
+					acc += np.sum(Fd.get(0, cb) ** 2, axis=1)
+				var = self._sigma2 * acc + (self._sigma2 if include_noise else 0.0)
+			if not np.all(np.isfinite(mean)) or (var is not None and not np.all(np.isfinite(var))):
+				raise FloatingPointError("predict: the feature model's prediction is not finite")
+			return mean, var
+		finally:
+			for obj in reversed(live):
+				obj.close()
+
+	def sample_paths(self, count: int = 16, seed=None, normals=None) -> PosteriorPaths:
+		"""`count` sample functions of the weight-space posterior as a `PosteriorPaths` without a data term (V = None): the weights are
+		W = w_bar 1^T + sqrt(sigma2) L^-T Xi with Xi = default_rng(seed).standard_normal((2 F2, count)), or `normals` given explicitly."""
+		from scipy.linalg import solve_triangular
+
+		self._check("sample_paths")
+		count = int(count)
+		m2 = self.mean_weights.shape[0]
+		if count < 1:
+			raise ValueError(f"count = {count} must be >= 1")
+		if normals is None:
+			Xi = np.random.default_rng(seed).standard_normal((m2, count))
+		else:
+			Xi = np.array(normals, dtype=np.float64)
+			if Xi.shape != (m2, count) or not np.all(np.isfinite(Xi)):
+				raise ValueError(f"normals must be a finite (2 F2, count) = ({m2}, {count}) array, got shape {Xi.shape}")
+		Wh = self.mean_weights[:, None] + np.sqrt(self._sigma2) * solve_triangular(self._L, Xi, lower=True, trans="T", check_finite=False)
+		kept = []
+		try:
+			fmap = self.features.device(self._op)  # (the paths own and close their map)
+			kept.append(fmap)
+			Wd = engine.DeviceMatrix(m2, count, ctx=self._op.ctx)
+			kept.append(Wd)
+			Wd.set(0, Wh)
+			paths = PosteriorPaths(self.K, self._op, self.features, fmap, Wh, Wd, None, None, dict(count=count, num_features=self.features.num_features))
+			kept = []
+			return paths
+		finally:
+			for obj in reversed(kept):
+				obj.close()
+
+	def close(self):
+		if getattr(self, "_fmap", None) is not None:
+			self._fmap.close()
+		self._fmap = None
+
+	def __enter__(self):
+		return self
+
+	def __exit__(self, *exc):
+		self.close()
+
+	def __del__(self):
+		try:
+			self.close()
+		except Exception:  # noqa: BLE001
+			pass
+
+
+def feature_posterior(K, y, num_features: int = 1024, seed=None, features=None) -> FeaturePosterior:
+	"""Sparse-spectrum GP regression: the Gaussian process with the kernel Phi Phi^T in the place of K's, Phi the `num_features` paired
+	random Fourier features of K's profile (the frequency draw and `features=` as in `sample_paths`), zero mean, w ~ N(0, I) and
+	noise sigma2 = K.noise > 0. K: a `KernelOperator` in float64; y: (n,), finite; 2 F2 <= 8192.
+
+	    h = Phi^T y (one adjoint product)        G = Phi^T Phi (KernelFeatureMap.gram)        M = G + sigma2 I = L L^T (host)
+	    w_bar = M^-1 h        mll = -1/2 [ (y^T y - h^T w_bar) / sigma2 + 2 sum log L_jj + (n - 2 F2) log sigma2 + n log 2 pi ]
+
+	Only y, h and the blocks of G cross the bus; nothing of size n x F2 is held. A failed Cholesky raises FloatingPointError.
+	Returns a `FeaturePosterior`: `.mll`, `.mean_weights`, `.predict(Xnew)`, `.sample_paths(count)`."""
+	from .operators import KernelFeatures, draw_kernel_frequencies
+
+	if getattr(K, "_slq_kind", None) != "kernel":
+		raise ValueError("feature_posterior needs a KernelOperator")
+	if np.dtype(K.dtype) != np.float64:
+		raise ValueError(f"feature_posterior is fp64 only (the device matrices are fp64): the KernelOperator is {np.dtype(K.dtype)}")
+	n, d = K.X.shape
+	yh = np.asarray(y, dtype=np.float64)
+	if yh.shape != (n,):
+		raise ValueError(f"y must be ({n},), got shape {yh.shape} (multi-output y is not built)")
+	if not np.all(np.isfinite(yh)):
+		raise ValueError("y must be finite")
+	sigma2 = float(K.noise)
+	if not sigma2 > 0.0:
+		raise ValueError(f"feature_posterior needs noise > 0, got {sigma2}: Phi^T Phi alone is singular when 2 F2 > n")
+	rng = np.random.default_rng(seed)
+	if features is None:
+		if 2 * int(num_features) > FEATURE_POSTERIOR_MAX_WEIGHTS:
+			raise ValueError(f"feature_posterior: 2 F2 = {2 * int(num_features)} weights exceed the limit of {FEATURE_POSTERIOR_MAX_WEIGHTS} (the weight-space system is solved on the host)")
+		features = KernelFeatures(K, draw_kernel_frequencies(K.kernel, int(num_features), d, rng))
+	elif not isinstance(features, KernelFeatures) or features.K is not K:
+		raise ValueError("features must be a KernelFeatures of this KernelOperator (K.features(...))")
+	F2 = features.num_features
+	if 2 * F2 > FEATURE_POSTERIOR_MAX_WEIGHTS:
+		raise ValueError(f"feature_posterior: 2 F2 = {2 * F2} weights exceed the limit of {FEATURE_POSTERIOR_MAX_WEIGHTS} (the weight-space system is solved on the host)")
+
+	op = _as_device_operator(K, dtype=np.float64)
+	fmap = features.device(op)
+	try:
+		from scipy.linalg import solve_triangular
+
+		h = fmap.rmatmat(yh.reshape(-1, 1))[:, 0]
+		G = fmap.gram()
+		M = G + sigma2 * np.eye(2 * F2)
+		if not np.all(np.isfinite(M)):
+			raise FloatingPointError("feature_posterior: Phi^T Phi is not finite")
+		try:
+			L = np.linalg.cholesky(M)
+		except np.linalg.LinAlgError as e:
+			raise FloatingPointError(f"feature_posterior: the Cholesky factorisation of Phi^T Phi + sigma2 I failed ({e})") from None
+		wbar = solve_triangular(L, solve_triangular(L, h, lower=True, check_finite=False), lower=True, trans="T", check_finite=False)
+		dg = np.diag(M)
+		mll = -0.5 * ((float(yh @ yh) - float(h @ wbar)) / sigma2 + 2.0 * float(np.sum(np.log(np.diag(L)))) + (n - 2 * F2) * np.log(sigma2) + n * np.log(2.0 * np.pi))
+		info = dict(num_features=F2, gram_asymmetry=fmap.gram_asymmetry, m_diag_min=float(dg.min()), m_diag_max=float(dg.max()))
+		post = FeaturePosterior(K, op, features, fmap, L, wbar, mll, info)
+		fmap = None
+		return post
+	finally:
+		if fmap is not None:
+			fmap.close()
