@@ -264,8 +264,21 @@ int slq_plan_run(slq_plan *plan, double rtol);
 int slq_plan_run_steps(slq_plan *plan, double rtol, int upto);
 int slq_plan_steps_done(const slq_plan *plan, int *cur);
 /* alpha, beta: nprobes x (deg+1) row-major of the plan dtype; steps: nprobes ints. Any may be
- * NULL. Synchronises. */
+ * NULL. Synchronises.
+ * beta_deg of a plan without a kept basis is computed at its first request: a run that reaches deg leaves out the update
+ * pass of its last step, which stores no vector and whose scalars no quadrature reads (the closing tail; SLQ_LAST_STORE=2 keeps it in the run,
+ * slq_plan_closing_state), and this call launches it on the plan's stream before it copies. The numbers are those of a
+ * run that launched it at once, bit for bit: nothing the pass reads can change in between (new probes drop it; plans of an
+ * affine operator, whose values slq_operator_set_parameter rewrites, never leave it out). */
 int slq_plan_get_tridiag(slq_plan *plan, void *alpha, void *beta, int32_t *steps);
+/* The closing tail of a plan: the update pass of step deg - 1 and the scalar kernel behind it. *lazy: runs of this plan
+ * leave it out (plain quadrature plans whose last update pass stores nothing, on operators with fixed values - not the
+ * affine A + t B -, unless created under SLQ_LAST_STORE=2); *pending: the last
+ * run left it out and nothing has asked for it yet. slq_plan_get_tridiag, slq_plan_quadrature_at with the Gauss-Radau
+ * rule at m = deg and the slq_plan_window_* diagnostics launch a pending tail first; slq_plan_quadrature,
+ * slq_density_update, slq_plan_describe and slq_plan_profile_read never do; new probes and slq_plan_destroy drop it
+ * without a launch. Either pointer may be NULL. No device work. */
+int slq_plan_closing_state(slq_plan *plan, int *lazy, int *pending);
 /* Gauss quadrature of every probe's Jacobi matrix on the device, then
  * quad[i] = sum_k f(nodes[i,k]) * weights[i,k] * ||v_i||^2 (src/primate/operators.py:149-150).
  * quad: nprobes doubles or NULL; nodes/weights: nprobes x deg row-major doubles or NULL.
@@ -733,7 +746,10 @@ int slq_plan_sweep_columns(slq_plan *plan, uint64_t *read, uint64_t *offered, in
 /* The oldest column of a full three-column window (ring-fed Gram sequence, orth = 3) is read by the update pass only where its zero projection is not
  * certified from the inner products the step already has (SLQ_OMEGA: 1 on, 0 every column read, 2 verify: every column read and the certificate checked
  * against the measurement). out: columns offered, columns read, rescues (the missing entry measured by a dot of its own), verify-mode violations,
- * read -> skip transitions; summed over steps and panels since the last reset; zeros for a plan that offers nothing. Synchronises. */
+ * read -> skip transitions; summed over steps and panels since the last reset; zeros for a plan that offers nothing. Synchronises.
+ * The last step of a run is counted by the run's closing tail (slq_plan_closing_state): this call, _verify, _census, _flags and slq_plan_get_tridiag launch a
+ * pending one, but new probes drop it, so a run whose tail nobody asked for before the next probes adds its steps 2 .. deg - 2 only (`panels` offered fewer,
+ * and whatever that step read or rescued). Read or reset the counters after each run, or create the plan under SLQ_LAST_STORE=2, for sums over every step. */
 int slq_plan_window_columns(slq_plan *plan, int64_t out[5], int reset);
 /* Which kernel computes the product of a plan on a dense operator, and over how many K slabs (a diagnostic entry: what the plan will launch, from the
  * panel width, the operator's leading dimension and the SLQ_DENSE_* switches read when it was created). kernel: 0 the operator is not dense,
@@ -770,6 +786,10 @@ int slq_debug_plan_mark_stale(slq_plan *plan, int nstale);
  * behind barriers / 2 ring-fed); out: the 18 values of seq::shape_to_array, then what slq_plan_describe reports as
  * `sequence` for such a plan. No HIP call. */
 int slq_debug_step_shape(const int *facts, int nfacts, int j, int prev_xt, int *out, int nout);
+/* Whether a plan of these facts leaves its closing tail to the first request (seq::has_lazy_tail; lazy_close: 0 for a plan created under
+ * SLQ_LAST_STORE=2, which keeps the pass in the run, else 1; values_fixed: 0 for an affine operator A + t B, whose values
+ * slq_operator_set_parameter rewrites under a live plan - its plans have no lazy tail -, else 1): *out = 1 or 0. No HIP call. */
+int slq_debug_lazy_tail(const int *facts, int nfacts, int lazy_close, int values_fixed, int *out);
 /* The same for step j of a Chebyshev run of facts[7] (deg) steps (seq::cheb_step_shape, derived from step_shape's answer at
  * orth = 0): out receives the 9 values of seq::cheb_shape_to_array - sweeps, tiled, gen, pipe_on, the update pass's xt word,
  * the sweeps' product kernel and its grid, the grid behind the partials, alpha_pass (always 0). No HIP call. */

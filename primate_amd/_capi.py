@@ -185,6 +185,8 @@ _SIGNATURES = {
 	"slq_debug_plan_poke_ring_flag": (C.c_int, [_P, C.c_int]),
 	"slq_debug_step_shape": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
 	"slq_debug_cheb_step_shape": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
+	"slq_debug_lazy_tail": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+	"slq_plan_closing_state": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 	"slq_debug_csr_layout": (C.c_int, [C.c_int64, C.c_int64, _P, _P, C.c_int, _P, _P, C.c_int64, _P, _P]),
 	"slq_debug_plan_shape": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int]),
 	"slq_debug_plan_shape_of": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int]),

@@ -171,6 +171,14 @@ struct slq_plan {
   int cur = 0;
   double run_rtol = 0.0;
   bool prev_xt = false;
+  // the closing tail (slq_sequence.hpp: has_lazy_tail): a run that reached deg left the update pass of step
+  // deg - 1 and its scalar kernel out; what they need to be launched later (flush_closing_tail). New probes drop it.
+  struct ClosingTail {
+    bool pending = false;
+    int j = 0;             // the step: deg - 1
+    double rtol = 0.0;     // the run's rtol (the stop rule of k_fin_beta / k_fin_beta_gram)
+    seq::StepShape shape;  // the step as the run saw it: xt bits, grids, the edge recurrence's flags
+  } closing;
   // slq_plan_quadrature_at (allocated by its first call): quad | gauss | stage[4] | nodes | weights (P x (deg + 1) each), two flag words
   double *at_d = nullptr;
   int *at_flags = nullptr;
@@ -242,6 +250,12 @@ static int need_chebyshev(const slq_plan *p, const char *who) {
   if (!p->cheb) return fail(SLQ_EINVAL, "%s: not a Chebyshev plan (slq_plan_create_chebyshev)", who);
   return SLQ_OK;
 }
+
+// the closing tail of the last run (slq_plan::ClosingTail): launched by the entries that read what it writes, ...
+static int flush_closing_tail(slq_plan *p);
+// ... dropped, with no launch, by whatever replaces the probes: the ring slot it would read is about to be overwritten. `ran`
+// is left to init_from_probes and run_range, as it always was.
+static void drop_closing_tail(slq_plan *p) { p->closing.pending = false; }
 
 // SLQ_TILES: 0 none, 1 workgroup tiles landed behind barriers (k_csr_tile_pass), 2 tiles fed through a ring of LDS slots by
 // loader waves (k_csr_ring_pass). Read when an operator is created (the rows are regrouped into the tiles) and when a plan
@@ -1611,6 +1625,7 @@ static int plan_bytes_on(const slq_operator *op, int nprobes, int deg, int orth,
 extern "C" int slq_plan_destroy(slq_plan *p) {
   if (!p) return SLQ_OK;
   hipSetDevice(p->ctx->device);
+  drop_closing_tail(p);  // (a pending closing tail goes with the plan: nothing is launched)
   hipStreamSynchronize(p->ctx->stream);
   for (auto &ev : p->events) { hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
   for (auto &ev : p->pool) { hipEventDestroy(ev.a); hipEventDestroy(ev.b); }
@@ -1924,6 +1939,7 @@ extern "C" int slq_plan_window_columns(slq_plan *p, int64_t out[5], int reset) {
   for (int k = 0; k < 5; ++k) out[k] = 0;
   if (!p->omega_on) return SLQ_OK;
   HIP_TRY(hipSetDevice(p->ctx->device));
+  SLQ_TRY(flush_closing_tail(p));  // (k_fin_beta_gram counts the closing step)
   unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   HIP_TRY(hipMemcpyAsync(h, p->om_cnt, sizeof(h), hipMemcpyDeviceToHost, p->ctx->stream));
   if (reset) HIP_TRY(hipMemsetAsync(p->om_cnt, 0, sizeof(h), p->ctx->stream));
@@ -1942,6 +1958,7 @@ extern "C" int slq_plan_window_flags(slq_plan *p, int32_t *read, int32_t *rescue
   memset(rescue, 0, (size_t)words * sizeof(int32_t));
   if (!p->omega_on) return SLQ_OK;
   HIP_TRY(hipSetDevice(p->ctx->device));
+  SLQ_TRY(flush_closing_tail(p));
   HIP_TRY(hipMemcpyAsync(read, p->om_flags, (size_t)words * sizeof(int), hipMemcpyDeviceToHost, p->ctx->stream));
   HIP_TRY(hipMemcpyAsync(rescue, p->om_flags + words, (size_t)words * sizeof(int), hipMemcpyDeviceToHost, p->ctx->stream));
   HIP_TRY(hipStreamSynchronize(p->ctx->stream));
@@ -1956,6 +1973,7 @@ extern "C" int slq_plan_window_census(slq_plan *p, int32_t *out, int64_t len) {
   if (!p->om_census) return fail(SLQ_EINVAL, "the plan keeps no census (ring-fed Gram sequence created under SLQ_OMEGA=2)");
   if (len != words) return fail(SLQ_EINVAL, "census buffer: %lld words expected", (long long)words);
   HIP_TRY(hipSetDevice(p->ctx->device));
+  SLQ_TRY(flush_closing_tail(p));
   HIP_TRY(hipMemcpyAsync(out, p->om_census, (size_t)words * sizeof(int), hipMemcpyDeviceToHost, p->ctx->stream));
   HIP_TRY(hipStreamSynchronize(p->ctx->stream));
   return SLQ_OK;
@@ -1971,6 +1989,7 @@ extern "C" int slq_plan_window_verify(slq_plan *p, int *mode, double out[5]) {
   out[0] = 0.0, out[1] = std::numeric_limits<double>::infinity(), out[2] = kOmegaC, out[3] = kOmegaKappa, out[4] = p->om_norm;
   if (!p->omega_on) return SLQ_OK;
   HIP_TRY(hipSetDevice(p->ctx->device));
+  SLQ_TRY(flush_closing_tail(p));  // (asked for the numbers: `out` is null when only the mode is wanted, which flushes nothing)
   unsigned long long h[8];
   HIP_TRY(hipMemcpyAsync(h, p->om_cnt, sizeof(h), hipMemcpyDeviceToHost, p->ctx->stream));
   HIP_TRY(hipStreamSynchronize(p->ctx->stream));
@@ -2050,6 +2069,7 @@ static int init_from_probes(slq_plan *p, int sphere, bool unit_entries = false, 
   p->probes_ready = true;
   p->ran = false;
   p->cur = 0;
+  p->closing.pending = false;
   return SLQ_OK;
 }
 
@@ -2087,6 +2107,7 @@ extern "C" int slq_plan_set_probes(slq_plan *p, const void *X, int64_t ldx) {
   const bool use_pin = pinned && ensure_pinned(ctx, (size_t)cc * col_bytes);
   if (!use_pin) cc = stage_chunk_cols(p);
   SLQ_TRY(ensure_stage(p, cc));
+  drop_closing_tail(p);  // (from here on ring slot 0 is written)
   // padding columns must be zero
   if (p->nprobes < p->bpad)
     HIP_TRY(hipMemsetAsync(slot_ptr(p, 0), 0, (size_t)p->slot_stride * p->esz, st));
@@ -2128,6 +2149,7 @@ extern "C" int slq_plan_generate_probes(slq_plan *p, int pdf, uint64_t seed, uin
   if (!p) return fail(SLQ_EINVAL, "plan is NULL");
   if (pdf < 0 || pdf > 2) return fail(SLQ_EINVAL, "Invalid distribution id %d supplied.", pdf);
   HIP_TRY(hipSetDevice(p->ctx->device));
+  drop_closing_tail(p);
   hipStream_t st = p->ctx->stream;
   const int RPW = 64 / p->LPR;
   const int items = (p->n + (pdf == 0 ? 127 : 1)) / (pdf == 0 ? 128 : 2);
@@ -2644,11 +2666,13 @@ template <int PASS> static int launch_fused_pass(const RunFrame &c, const seq::S
 
 // Gram sequence on ring-fed plans (r >= 1): alpha-only pass, projections from the Gram rows of the last two update passes
 // (k_fin_gram), update pass that also takes the new vector against every ring column it reads (slq_kernels.hpp)
-static int launch_gram_ring(const RunFrame &c, const seq::StepShape &s, int j) {
+// part (here and in the three launchers below): the whole step, or what stands in front of its update pass / the update pass
+// and the scalar kernel behind it alone (seq::StepPart: the closing tail of a run)
+static int launch_gram_ring(const RunFrame &c, const seq::StepShape &s, int j, int part) {
   slq_plan *p = c.p;
   hipStream_t st = c.st;
   const int bp = p->bpad, r = s.r, S = p->S;
-  PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_fused_pass<PASS_ALPHA>(c, s, j, 0, c.lds_alpha(s), s.xt_alpha)));
+  if (part & seq::STEP_FRONT) PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_fused_pass<PASS_ALPHA>(c, s, j, 0, c.lds_alpha(s), s.xt_alpha)));
   // a full window of three columns is offered to the edge recurrence (slq_kernels.hpp: OmegaState): its oldest column is read only
   // where the panel's flag says so. The launch sequence does not depend on the flags: the rescue kernel is always there.
   OmegaState om = c.om_off;
@@ -2664,14 +2688,16 @@ static int launch_gram_ring(const RunFrame &c, const seq::StepShape &s, int j) {
     om.theta = kOmegaC * om.eps_norm;
     om.tol_k = c.orth_tol / kOmegaKappa;
   }
-  PROFILED(p, SLQ_K_FINALIZE,
-           hipLaunchKernelGGL(k_fin_gram, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, st, p->st, p->part, c.blocks(s.blk_alpha), j, r, c.orth_tol, om));
-  if (om.mode == 1 && om.est_prev) {
+  if (part & seq::STEP_FRONT)
+    PROFILED(p, SLQ_K_FINALIZE,
+             hipLaunchKernelGGL(k_fin_gram, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, st, p->st, p->part, c.blocks(s.blk_alpha), j, r, c.orth_tol, om, (int)(part == seq::STEP_FRONT)));
+  if ((part & seq::STEP_FRONT) && om.mode == 1 && om.est_prev) {
     double *part_r = p->part + (size_t)p->part_maxblk * bp;  // (behind the alpha partials, which the second pass does not need but the slab layout keeps)
     // (one launch: the workgroup that finishes a flagged panel last sums its partials and takes the edge position again)
     PROFILED(p, SLQ_K_FINALIZE,
              DISPATCH(p->dtype, p->LPR, (k_omega_rescue_dot<F, L><<<c.gS, dim3(kBlock), 0, st>>>(p->n, (const F *)p->ring, p->slot_stride, S, j, r, part_r, p->om_ticket, p->st, c.orth_tol, om))));
   }
+  if (!(part & seq::STEP_TAIL)) return SLQ_OK;
   PROFILED(p, SLQ_K_REORTH_UPD, SLQ_TRY(launch_ring_gen(p, PASS_UPDATEG, r, c.gT, st, j, s.xt_update, false, om.mode == 1 ? om.read + (size_t)j * p->NP : nullptr)));
   PROFILED(p, SLQ_K_FINALIZE,
            hipLaunchKernelGGL(k_fin_beta_gram, dim3((bp + 63) / 64, r + 1), dim3(kFinThreads), 0, st, p->st, p->part, c.blocks(s.blk_beta), j, r, c.residual_tol, om));
@@ -2679,13 +2705,16 @@ static int launch_gram_ring(const RunFrame &c, const seq::StepShape &s, int j) {
 }
 
 // the same sequence on the generic passes (k_csr_pass<PASS_UPDATEG>; r04): alpha-only pass over the upper triangle, projections from Gram rows
-static int launch_gram_csr(const RunFrame &c, const seq::StepShape &s, int j) {
+static int launch_gram_csr(const RunFrame &c, const seq::StepShape &s, int j, int part) {
   slq_plan *p = c.p;
   hipStream_t st = c.st;
   const int bp = p->bpad, r = s.r;
-  PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_fused_pass<PASS_ALPHA>(c, s, j, 0, c.lds_alpha(s), s.xt_alpha)));
-  PROFILED(p, SLQ_K_FINALIZE,
-           hipLaunchKernelGGL(k_fin_gram, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, st, p->st, p->part, c.blocks(s.blk_alpha), j, r, c.orth_tol, c.om_off));
+  if (part & seq::STEP_FRONT) {
+    PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_fused_pass<PASS_ALPHA>(c, s, j, 0, c.lds_alpha(s), s.xt_alpha)));
+    PROFILED(p, SLQ_K_FINALIZE,
+             hipLaunchKernelGGL(k_fin_gram, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, st, p->st, p->part, c.blocks(s.blk_alpha), j, r, c.orth_tol, c.om_off, (int)(part == seq::STEP_FRONT)));
+  }
+  if (!(part & seq::STEP_TAIL)) return SLQ_OK;
   PROFILED(p, SLQ_K_REORTH_UPD, DISPATCH(p->dtype, p->LPR, (launch_csr_updateg<F, L>(p, r, s.pipe_on != 0, c.gU, c.lds_fused(s), st, j, s.xt_update))));
   PROFILED(p, SLQ_K_FINALIZE,
            hipLaunchKernelGGL(k_fin_beta_gram, dim3((bp + 63) / 64, r + 1), dim3(kFinThreads), 0, st, p->st, p->part, c.blocks(s.blk_beta), j, r, c.residual_tol, c.om_off));
@@ -2694,28 +2723,34 @@ static int launch_gram_csr(const RunFrame &c, const seq::StepShape &s, int j) {
 
 // fused passes, r >= 1: alpha comes out of the dots pass (PASS_ADOTS: two gather passes per step instead of three); the
 // stored-u sequence is this one with the bits that make the first pass store u and the second read it back
-static int launch_merged(const RunFrame &c, const seq::StepShape &s, int j) {
+static int launch_merged(const RunFrame &c, const seq::StepShape &s, int j, int part) {
   slq_plan *p = c.p;
   const int bp = p->bpad, r = s.r;
-  PROFILED(p, SLQ_K_REORTH_DOT, SLQ_TRY(launch_fused_pass<PASS_ADOTS>(c, s, j, r, c.lds_fused(s), s.xt_dots)));
-  PROFILED(p, SLQ_K_FINALIZE,
-           hipLaunchKernelGGL(k_fin_adots, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, c.st, p->st, p->part, c.blocks(s.blk_dots), j, r, c.orth_tol));
+  if (part & seq::STEP_FRONT) {
+    PROFILED(p, SLQ_K_REORTH_DOT, SLQ_TRY(launch_fused_pass<PASS_ADOTS>(c, s, j, r, c.lds_fused(s), s.xt_dots)));
+    PROFILED(p, SLQ_K_FINALIZE,
+             hipLaunchKernelGGL(k_fin_adots, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, c.st, p->st, p->part, c.blocks(s.blk_dots), j, r, c.orth_tol, (int)(part == seq::STEP_FRONT)));
+  }
+  if (!(part & seq::STEP_TAIL)) return SLQ_OK;
   PROFILED(p, SLQ_K_REORTH_UPD, SLQ_TRY(launch_fused_pass<PASS_UPDATE>(c, s, j, r, c.lds_fused(s), s.xt_update)));
   return SLQ_OK;
 }
 
 // fused passes with the alpha pass on its own (r == 0, or SLQ_MERGED=0): alpha, dots (r > 0), update
-static int launch_separate(const RunFrame &c, const seq::StepShape &s, int j) {
+static int launch_separate(const RunFrame &c, const seq::StepShape &s, int j, int part) {
   slq_plan *p = c.p;
   const int bp = p->bpad, r = s.r;
-  PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_fused_pass<PASS_ALPHA>(c, s, j, 0, c.lds_alpha(s), s.xt_alpha)));
-  PROFILED(p, SLQ_K_FINALIZE,
-           hipLaunchKernelGGL(k_fin_alpha, c.gF, dim3(kFinThreads), 0, c.st, p->st, p->part, c.blocks(s.blk_alpha), j, s.xt_alpha & 1));
-  if (r > 0) {
+  if (part & seq::STEP_FRONT) {
+    PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_fused_pass<PASS_ALPHA>(c, s, j, 0, c.lds_alpha(s), s.xt_alpha)));
+    PROFILED(p, SLQ_K_FINALIZE,
+             hipLaunchKernelGGL(k_fin_alpha, c.gF, dim3(kFinThreads), 0, c.st, p->st, p->part, c.blocks(s.blk_alpha), j, s.xt_alpha & 1, (int)(part == seq::STEP_FRONT)));
+  }
+  if ((part & seq::STEP_FRONT) && r > 0) {
     PROFILED(p, SLQ_K_REORTH_DOT, SLQ_TRY(launch_fused_pass<PASS_DOTS>(c, s, j, r, c.lds_fused(s), s.xt_dots)));
     PROFILED(p, SLQ_K_FINALIZE,
              hipLaunchKernelGGL(k_fin_gamma, dim3((bp + 63) / 64, r), dim3(kFinThreads), 0, c.st, p->st, p->part, c.blocks(s.blk_dots), j, 0, c.orth_tol));
   }
+  if (!(part & seq::STEP_TAIL)) return SLQ_OK;
   PROFILED(p, (r == 0 ? SLQ_K_AXPY_NORM : SLQ_K_REORTH_UPD), SLQ_TRY(launch_fused_pass<PASS_UPDATE>(c, s, j, r, c.lds_fused(s), s.xt_update)));
   return SLQ_OK;
 }
@@ -2778,7 +2813,7 @@ static int launch_sweep_product(const RunFrame &c, const seq::StepShape &s, int 
       break;
   }
   if (cheb) return SLQ_OK;
-  PROFILED(p, SLQ_K_FINALIZE, hipLaunchKernelGGL(k_fin_alpha, c.gF, dim3(kFinThreads), 0, st, p->st, p->part, nblk, j, 0));
+  PROFILED(p, SLQ_K_FINALIZE, hipLaunchKernelGGL(k_fin_alpha, c.gF, dim3(kFinThreads), 0, st, p->st, p->part, nblk, j, 0, 0));
   return SLQ_OK;
 }
 
@@ -2830,7 +2865,31 @@ static RunFrame run_frame(slq_plan *p, double rtol) {
   return c;
 }
 
-static int enqueue_run(slq_plan *p, double rtol, int j0, int j1) {
+// one step, or one part of it (seq::StepPart; the sweeps are never split: no plan with a lazy tail closes on them)
+static int launch_step(const RunFrame &c, const seq::StepShape &s, int j, int part) {
+  slq_plan *p = c.p;
+  switch (s.seq) {
+    case seq::SEQ_GRAM_RING: return launch_gram_ring(c, s, j, part);  // (k_fin_beta_gram closes the step)
+    case seq::SEQ_GRAM_CSR: return launch_gram_csr(c, s, j, part);
+    case seq::SEQ_MERGED:
+    case seq::SEQ_STORED_U: SLQ_TRY(launch_merged(c, s, j, part)); break;
+    case seq::SEQ_SEPARATE: SLQ_TRY(launch_separate(c, s, j, part)); break;
+    default:
+      if (part != seq::STEP_WHOLE) return fail(SLQ_EINVAL, "internal: a step of the store-and-revisit sweeps has no closing tail");
+      SLQ_TRY(launch_sweeps(c, s, j));
+      break;
+  }
+  if (part & seq::STEP_TAIL)
+    PROFILED(p, SLQ_K_FINALIZE,
+             hipLaunchKernelGGL(k_fin_beta, c.gF, dim3(kFinThreads), 0, c.st, p->st, p->part, c.blocks(s.blk_beta), j, c.residual_tol, s.prev_xt ? 1 : 0));
+  return SLQ_OK;
+}
+
+// the plan leaves the closing tail of a run that reaches deg to the first entry that asks for it
+static bool plan_lazy_tail(const slq_plan *p) { return !p->cheb && seq::has_lazy_tail(sequence_facts(p), p->sw.last_store != 2, !p->facts.affine); }
+
+// lazy_tail: a run that reaches deg launches the front of step deg - 1 only (run_range marks the tail pending)
+static int enqueue_run(slq_plan *p, double rtol, int j0, int j1, bool lazy_tail = false) {
   hipStream_t st = p->ctx->stream;
   const int bp = p->bpad, deg = p->deg;
   const RunFrame c = run_frame(p, rtol);
@@ -2850,16 +2909,7 @@ static int enqueue_run(slq_plan *p, double rtol, int j0, int j1) {
   for (int j = j0; j < j1; ++j) {
     const seq::StepShape s = seq::step_shape(facts, j, prev_xt);
     prev_xt = s.prev_xt != 0;
-    switch (s.seq) {
-      case seq::SEQ_GRAM_RING: SLQ_TRY(launch_gram_ring(c, s, j)); continue;  // (k_fin_beta_gram has closed the step)
-      case seq::SEQ_GRAM_CSR: SLQ_TRY(launch_gram_csr(c, s, j)); continue;
-      case seq::SEQ_MERGED:
-      case seq::SEQ_STORED_U: SLQ_TRY(launch_merged(c, s, j)); break;
-      case seq::SEQ_SEPARATE: SLQ_TRY(launch_separate(c, s, j)); break;
-      default: SLQ_TRY(launch_sweeps(c, s, j)); break;
-    }
-    PROFILED(p, SLQ_K_FINALIZE,
-             hipLaunchKernelGGL(k_fin_beta, c.gF, dim3(kFinThreads), 0, st, p->st, p->part, c.blocks(s.blk_beta), j, c.residual_tol, prev_xt ? 1 : 0));
+    SLQ_TRY(launch_step(c, s, j, (lazy_tail && j == deg - 1) ? seq::STEP_FRONT : seq::STEP_WHOLE));
   }
   p->prev_xt = prev_xt;
   HIP_TRY(hipGetLastError());
@@ -3113,8 +3163,12 @@ static int run_range(slq_plan *p, double rtol, int j0, int j1) {
   // a few per cent for n = 1e6. Not used while per-kernel events are recorded, nor for host-callback
   // operators (they synchronise with the host every step).
   const bool graph_ok = p->sw.graph && !p->prof && p->op->kind != OP_CALLBACK && p->op->kind != OP_DEVICE_CALLBACK;
+  // the stage that reaches deg leaves its closing tail out, of the captured graph too (the key does not change: whether a plan has
+  // a lazy tail follows from the plan's switches and from nstale, which is the key's variant); a flush launches it directly
+  // (a run from step 0 needs new probes, and init_from_probes has dropped what the run before left pending)
+  const bool lazy_tail = j1 == p->deg && plan_lazy_tail(p);
   if (!graph_ok) {
-    SLQ_TRY(enqueue_run(p, rtol, j0, j1));
+    SLQ_TRY(enqueue_run(p, rtol, j0, j1, lazy_tail));
   } else {
     const unsigned variant = (unsigned)p->nstale;
     size_t gi = 0;
@@ -3140,7 +3194,7 @@ static int run_range(slq_plan *p, double rtol, int j0, int j1) {
       hipGraph_t graph = nullptr;
       const bool xt_in = p->prev_xt;
       HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      const int rc = enqueue_run(p, rtol, j0, j1);
+      const int rc = enqueue_run(p, rtol, j0, j1, lazy_tail);
       hipError_t ce = hipStreamEndCapture(st, &graph);
       if (rc != SLQ_OK) {
         if (graph) hipGraphDestroy(graph);
@@ -3166,6 +3220,45 @@ static int run_range(slq_plan *p, double rtol, int j0, int j1) {
   p->cur = j1;
   p->run_rtol = rtol;
   p->rule_src = 0;
+  if (lazy_tail) {
+    p->closing.pending = true;
+    p->closing.j = p->deg - 1;
+    p->closing.rtol = rtol;
+    p->closing.shape = seq::step_shape(sequence_facts(p), p->deg - 1, false);  // (prev_xt enters the alpha pass's word only: the front's)
+  }
+  return SLQ_OK;
+}
+
+// The closing tail of the last run, launched now: on the plan's stream, the launches the run would have made behind the front of
+// step deg - 1 (same kernels, same arguments, PROFILED like them), directly - a graph of two launches saves nothing. Called by
+// every entry that reads what they write: nu[deg], steps and active of the stop rule at deg, the Gram row and sc / cp behind
+// it, the edge recurrence's counters of that step.
+static int flush_closing_tail(slq_plan *p) {
+  if (!p->closing.pending) return SLQ_OK;
+  HIP_TRY(hipSetDevice(p->ctx->device));
+  const RunFrame c = run_frame(p, p->closing.rtol);
+  const int rc = launch_step(c, p->closing.shape, p->closing.j, seq::STEP_TAIL);
+  if (rc != SLQ_OK) return rc;
+  HIP_TRY(hipGetLastError());
+  if (p->launch_error) {
+    p->launch_error = false;
+    return fail(SLQ_EINVAL, "internal: a pass of the launch sequence had no kernel for this plan's tiles");
+  }
+  p->closing.pending = false;
+  return SLQ_OK;
+}
+
+extern "C" int slq_plan_closing_state(slq_plan *p, int *lazy, int *pending) {
+  if (!p) return fail(SLQ_EINVAL, "plan is NULL");
+  if (lazy) *lazy = plan_lazy_tail(p) ? 1 : 0;
+  if (pending) *pending = p->closing.pending ? 1 : 0;
+  return SLQ_OK;
+}
+
+// has_lazy_tail() of slq_sequence.hpp on facts given as slq_debug_step_shape takes them: no HIP call
+extern "C" int slq_debug_lazy_tail(const int *facts, int nfacts, int lazy_close, int values_fixed, int *out) {
+  if (!facts || !out || nfacts != seq::kNumFacts) return fail(SLQ_EINVAL, "slq_debug_lazy_tail: %d facts in, one value out", seq::kNumFacts);
+  *out = seq::has_lazy_tail(seq::facts_from_array(facts), lazy_close, values_fixed) ? 1 : 0;
   return SLQ_OK;
 }
 
@@ -3182,6 +3275,7 @@ extern "C" int slq_plan_get_tridiag(slq_plan *p, void *alpha, void *beta, int32_
   SLQ_TRY(need_lanczos(p, "slq_plan_get_tridiag"));
   if (!p->ran) return fail(SLQ_EINVAL, "slq_plan_get_tridiag: no completed run");
   HIP_TRY(hipSetDevice(p->ctx->device));
+  SLQ_TRY(flush_closing_tail(p));  // (beta_deg, steps)
   hipStream_t st = p->ctx->stream;
   const int bp = p->bpad, deg = p->deg, P = p->nprobes;
   std::vector<double> ha((size_t)(deg + 1) * bp), hn((size_t)(deg + 1) * bp);
@@ -3284,6 +3378,7 @@ extern "C" int slq_plan_quadrature_at(slq_plan *p, int m, int rule, double endpo
     HIP_TRY(hipFuncSetAttribute((const void *)k_quadrature_at, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIP_TRY(hipMemsetAsync(p->at_flags, 0, 2 * sizeof(int), st));
   const double residual_tol = std::sqrt((double)p->n) * p->run_rtol;  // (the stop rule of the run: lanczos.h:110)
+  if (rule == 1 && m == deg) SLQ_TRY(flush_closing_tail(p));  // (the border of the Radau rule at m = deg is beta_deg; nothing else here reads the tail)
   PROFILED(p, SLQ_K_QUADRATURE,
            hipLaunchKernelGGL(k_quadrature_at, dim3((P + lanes - 1) / lanes), dim3(64), lds, st, p->st, m, rule, endpoint, residual_tol, lanes,
                               fun_id, p0, p1, quad_d, gauss_d, nodes_d, weights_d, p->at_flags));
@@ -5106,6 +5201,7 @@ extern "C" int slq_plan_set_probes_device(slq_plan *p, const void *d_X, int64_t 
   HIP_TRY(hipSetDevice(p->ctx->device));
   hipStream_t st = p->ctx->stream;
   if (ldx != p->n) return fail(SLQ_EINVAL, "device probes must be contiguous columns (ldx == n)");
+  drop_closing_tail(p);
   if (p->nprobes < p->bpad) HIP_TRY(hipMemsetAsync(slot_ptr(p, 0), 0, (size_t)p->slot_stride * p->esz, st));
   dim3 g((p->n + 63) / 64, (p->nprobes + 63) / 64);
   PROFILED(p, SLQ_K_PROBES, {

@@ -1902,8 +1902,10 @@ __global__ __launch_bounds__(kFinThreads) void k_fin_init(StepState st, const do
 }
 
 // After sweep A of step j: alpha_j, and the sweep-B coefficient cB = alpha_j / nu_j.
+// closing (here, in k_fin_adots and in k_fin_gram): step j is the run's last and its update pass is not launched with the run
+// (the closing tail, slq_sequence.hpp): the probes still active take steps = j + 1 here, as k_fin_beta would have set it.
 __global__ __launch_bounds__(kFinThreads) void k_fin_alpha(StepState st, const double *__restrict__ partA,
-                                                   int nblk, int j, int xt) {
+                                                   int nblk, int j, int xt, int closing) {
   __shared__ double red4[kFinThreads];
   const int col = blockIdx.x * 64 + (threadIdx.x & 63);
   double a = sum_partials(partA, nblk, st.bpad, col, red4);
@@ -1913,6 +1915,7 @@ __global__ __launch_bounds__(kFinThreads) void k_fin_alpha(StepState st, const d
     if (xt) a -= st.coefA[col] * st.coefA[st.bpad + col] * st.cross[col];
     if (act) st.alpha[(int64_t)j * st.bpad + col] = a;
     st.coefB[col] = act ? a / st.nu[(int64_t)j * st.bpad + col] : 0.0;
+    if (closing && act) st.steps[col] = j + 1;
   }
 }
 
@@ -1948,7 +1951,7 @@ __global__ __launch_bounds__(kFinThreads) void k_fin_beta(StepState st, const do
 //   i = 0: alpha_j, cB = alpha_j / nu_j, gamma_0 = 0;
 //   i >= 1: W_t.(u - alpha q_c) = d_i - cB g_i, then the threshold and scaling of k_fin_gamma.
 __global__ __launch_bounds__(kFinThreads) void k_fin_adots(StepState st, const double *__restrict__ part, int nblk,
-                                                   int j, int RC, double orth_tol) {
+                                                   int j, int RC, double orth_tol, int closing) {
   __shared__ double red4[kFinThreads];
   const int i = blockIdx.y;
   const int col = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -1967,6 +1970,7 @@ __global__ __launch_bounds__(kFinThreads) void k_fin_adots(StepState st, const d
       if (act) st.alpha[(int64_t)j * st.bpad + col] = a;
       st.coefB[col] = cb;
       st.gamma[col] = 0.0;
+      if (closing && act) st.steps[col] = j + 1;
     } else {
       const double nu = st.nu[(int64_t)(j - i) * st.bpad + col];
       double gm = 0.0;
@@ -2092,7 +2096,7 @@ __device__ __forceinline__ double omega_edge(const StepState &st, const OmegaSta
 }
 
 // k_fin_gram: blockIdx.y = i as in k_fin_adots. part: alpha partials of the alpha-only pass.
-__global__ __launch_bounds__(kFinThreads) void k_fin_gram(StepState st, const double *__restrict__ part, int nblk, int j, int RC, double orth_tol, OmegaState om) {
+__global__ __launch_bounds__(kFinThreads) void k_fin_gram(StepState st, const double *__restrict__ part, int nblk, int j, int RC, double orth_tol, OmegaState om, int closing) {
   __shared__ double red4[kFinThreads];
   const int i = blockIdx.y;
   const int col = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -2111,6 +2115,7 @@ __global__ __launch_bounds__(kFinThreads) void k_fin_gram(StepState st, const do
       if (act) st.alpha[(int64_t)j * bp + col] = a;
       st.coefB[col] = cb;
       st.gamma[col] = 0.0;
+      if (closing && act) st.steps[col] = j + 1;
     } else if (om.mode != 0 && i == RC - 1) {
       const double gm = omega_edge(st, om, j, i, col, cb, orth_tol, false);
       st.gamma[(int64_t)i * bp + col] = gm;

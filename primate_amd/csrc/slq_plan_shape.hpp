@@ -387,7 +387,7 @@ inline PlanShape plan_shape(const PlanFacts &f, const PlanSwitches &sw) {
     q.dense_class = s.dense_class, q.pipelined = s.pipelined;
     q.fused = sw.fused, q.merged = sw.merged, q.mgs = sw.mgs, q.stored_u = sw.stored_u, q.nt = sw.nt, q.cross = sw.cross, q.sw_gram = sw.gram;
     q.sw_gram_csr = sw.gram_csr, q.sw_ring_gen = sw.ring_gen, q.sw_ring_deep = sw.ring_deep;
-    q.last_store = (sw.last_store || action) ? 1 : 0;  // (an action reads w_nsteps: the last step stores it)
+    q.last_store = (sw.last_store == 1 || action) ? 1 : 0;  // (an action reads w_nsteps: the last step stores it)
     q.ring_alpha = sw.ring_alpha, q.ring_rev = sw.ring_rev;
     seq::derive_plan_flags(q);  // (the derived flags do not depend on omega_on)
     // the edge recurrence: full windows of three columns on the ring-fed Gram sequence (r = 4 .. 8: not offered; the rescue needs the

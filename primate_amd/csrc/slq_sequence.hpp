@@ -181,6 +181,24 @@ inline int plan_sequence_of(const SequenceFacts &f) {
   }
 }
 
+// ---- the closing tail ("the closing tail") ------------------------------------------------------------
+// The update pass of a run's last step, j = deg - 1, and the scalar kernel behind it (k_fin_beta_gram / k_fin_beta) produce
+// beta_deg, a Gram row, the next sc / cp, the stop rule's flags and the edge recurrence's counters of that step: no quadrature
+// reads any of them (k_quadrature: alpha[0 .. deg), nu[1 .. deg)). Where that pass also stores nothing, a run that reaches deg
+// leaves both launches out and the plan launches them when an entry first asks for what they write (slq.hip:
+// flush_closing_tail). A step can be launched in these two parts:
+enum StepPart { STEP_FRONT = 1, STEP_TAIL = 2, STEP_WHOLE = 3 };
+// A plan has a lazy tail where its closing update pass carries the no-store bit and the plan is a plain quadrature plan
+// (basis_mode 0: a recompute plan's runs, forward and replay, stay whole). lazy_close: the plan was not created under
+// SLQ_LAST_STORE=2, which keeps the pass in the run. values_fixed: nothing rewrites the operator's values under a live plan - a
+// deferred pass reads the CSR again, so the plans of an affine operator A + t B (slq_operator_set_parameter rewrites its values
+// in place) stay whole: their beta_deg must be that of the t the run saw. Stale ring columns put every step on the sweeps, which
+// have no such bit.
+inline bool has_lazy_tail(const SequenceFacts &f, int lazy_close, int values_fixed) {
+  if (!lazy_close || !values_fixed || f.deg < 1 || f.basis_mode != 0) return false;
+  return (step_shape(f, f.deg - 1, false).xt_update & 16) != 0;
+}
+
 // ---- Chebyshev runs (slq_cheb.hpp) ----------------------------------------------------------------
 // A Chebyshev step w_{j+1} = 2 A~ w_j - w_{j-1} IS the update pass of the orth-0 Lanczos step with constant coefficients:
 // no alpha pass, no dots pass. What it launches is therefore read off step_shape's answer for the same facts at orth = 0 (deg =

@@ -46,7 +46,7 @@ constexpr int kAuto = INT_MIN;  // "unset": the code that uses the switch picks 
   PLAN(ring_alpha, "SLQ_RING_ALPHA", 2, "alpha-only pass of a tiled symmetric operator: 2 ring over the upper-triangle stream, 1 over full rows, 0 generic") \
   PLAN(ring_alpha_max_x100, "SLQ_RING_ALPHA_MAX_X100", 260, "... takes the upper-triangle stream up to this many (x100) landed rows per row")        \
   PLAN(ring_rev, "SLQ_RING_REV", 1, "the ring-fed update pass sweeps panels and tiles in reverse")                                                   \
-  PLAN(last_store, "SLQ_LAST_STORE", 0, "1: the update pass of a run's last step stores W_deg although it is never read")                            \
+  PLAN(last_store, "SLQ_LAST_STORE", 0, "the update pass of a run's last step: 0 stores nothing and is launched when beta_deg is first asked for, 1 stores W_deg although it is never read, 2 stores nothing, launched with the run") \
   PLAN(sweep_skip, "SLQ_SWEEP_SKIP", 1, "the update sweep skips ring columns whose coefficient is zero for the whole panel")                         \
   PLAN(acc_skip, "SLQ_ACC_SKIP", 1, "the accumulation of a recompute plan's replay skips such columns")                                              \
   PLAN(defer_axpy, "SLQ_DEFER_AXPY", 1, "block-CGS sweeps: the dots sweeps are read-only, the update sweep applies the three-term axpy")             \

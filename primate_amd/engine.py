@@ -527,8 +527,16 @@ class LanczosPlan:
 		out = (quad,) + ((nodes, weights) if return_rule else ()) + ((stage,) if return_stage else ())
 		return out[0] if len(out) == 1 else out
 
+	def closing(self) -> dict:
+		"""{lazy, pending} (slq_plan_closing_state): runs of this plan leave the update pass of their last step to the first entry that
+		asks for beta_deg (`tridiag`, the Gauss-Radau rule at m = deg, the window diagnostics); the last run's is still outstanding."""
+		lazy, pending = C.c_int(), C.c_int()
+		check(_capi.lib().slq_plan_closing_state(self._h, C.byref(lazy), C.byref(pending)))
+		return {"lazy": bool(lazy.value), "pending": bool(pending.value)}
+
 	def tridiag(self) -> tuple:
-		"""(alpha, beta, steps): alpha/beta are (nprobes, deg+1) with beta[:, 0] = 0."""
+		"""(alpha, beta, steps): alpha/beta are (nprobes, deg+1) with beta[:, 0] = 0. beta[:, deg] of a plan without a kept
+		basis is computed by this call where the run left it out (`closing`)."""
 		a = np.zeros((self.nprobes, self.deg + 1), dtype=self.op.dtype)
 		b = np.zeros((self.nprobes, self.deg + 1), dtype=self.op.dtype)
 		s = np.zeros(self.nprobes, dtype=np.int32)
@@ -596,7 +604,9 @@ class LanczosPlan:
 
 	def window_columns(self, reset: bool = False) -> dict:
 		"""Accounting of the window's oldest column in the Gram sequence (slq_plan_window_columns), summed over steps and panels since the last
-		reset: columns offered and read, rescues, verify-mode violations, read -> skip transitions."""
+		reset: columns offered and read, rescues, verify-mode violations, read -> skip transitions. The last step of a run is counted when
+		its closing tail is launched (`closing`): this call and `tridiag` do that, new probes drop it - read the counters after each run
+		for sums over every step."""
 		out = (C.c_int64 * 5)()
 		check(_capi.lib().slq_plan_window_columns(self._h, out, int(reset)))
 		return dict(zip(("offered", "read", "rescues", "violations", "transitions"), (int(v) for v in out)))
