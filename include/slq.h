@@ -167,6 +167,27 @@ int slq_kernel_get_parameters(const slq_operator *op, int *d, int *profile, doub
  * out[1] row blocks, out[2] 16-column tiles per workgroup, out[3] column chunks, out[4] j slabs, out[5 ..] the slabs + 1 bounds
  * of the slabs in [0, n] (then -1); nout >= 22. */
 int slq_debug_kernel_points(slq_operator *op, void *zt, void *nrm, void *params);
+/* A diagonally scaled kernel operator: with a vector c of n entries, finite and >= 0, given in double and ROUNDED
+ * ONCE to the operator's dtype (the operator is defined on the rounded c, as on the rounded z),
+ *   A = s diag(c) phi(r2) diag(c) + sigma2 I,     A_ii = s c_i^2 + sigma2 (r2_ii = 0 as before); c_i = 0 makes row i sigma2 e_i^T.
+ * Fixed per-point noise K0 + diag(e) is E^{1/2} (D K0 D + I) E^{1/2} with D = diag(e^{-1/2}); the B = I + W^{1/2} K0 W^{1/2} of a Laplace
+ * approximation is D K0 D + I with c = W^{1/2}. The scale sits inside the product kernel (k_kernel_panel_scaled: four multiplies per
+ * lane and tile on values already in registers, one per output row in the epilogue); c = 1 everywhere gives the bits of the unscaled
+ * operator, and an operator without a scale runs the kernels and produces the bits it did before this entry existed.
+ * slq_kernel_set_diag_scale: c of n == the operator's n entries, read before the call returns; c == NULL clears the scale. The device
+ *   words (npad of them, zeros in the padding) are allocated by the first set and never move: a plan created before the call - and a
+ *   graph it captured while the operator was scaled - computes with new VALUES from its next run on. Whether a scale is set is part of a
+ *   plan's graph key (scaled and unscaled are different kernels), so setting, changing and clearing are all honoured by live plans.
+ *   SLQ_EINVAL names the first bad entry (negative, nan, inf, or not finite in the operator's dtype) or the wrong length.
+ * slq_kernel_get_diag_scale: *is_set (may be NULL); c (NULL: not wanted; else n entries, the ROUNDED values, and a scale must be set).
+ * slq_debug_kernel_diag_scale: the npad words as the kernel reads them, in the operator's dtype (tests).
+ * NOT built for a scaled operator, and refusing with SLQ_EINVAL at every use (not only at creation): slq_kernel_grad_*,
+ * slq_kernel_pointgrad_* of the training form, slq_kernel_precond_create / _refresh and every apply, product or plan run on a
+ * preconditioned operator whose base is scaled. slq_kernel_cross_*, slq_kernel_feature_* and the cross form of slq_kernel_pointgrad_*
+ * are defined on K0's points and profile: they IGNORE the scale, as they ignore the noise. */
+int slq_kernel_set_diag_scale(slq_operator *op, const double *c, int64_t n);
+int slq_kernel_get_diag_scale(const slq_operator *op, double *c, int64_t n, int *is_set);
+int slq_debug_kernel_diag_scale(slq_operator *op, void *c_dev_words);
 int slq_debug_kernel_schedule(int64_t n, int panel_width, int panels, int num_cus, int64_t *out, int nout);
 /* Bytes of device memory the process's operators (and the scratch of operator builds in flight) hold now: back where it was once
  * every operator created since has been destroyed (tests). No HIP call. */
@@ -515,7 +536,8 @@ int slq_debug_sddmm_schedule(int64_t n, const int32_t *rowptr, int32_t *row0, in
  *   its matrix, m < 1, a matrix that has not n rows, an object of another context, a non-finite alpha or beta.
  * slq_kernel_grad_get: nvals == d + 2: [0, d) the lengthscales, ALWAYS per dimension (a scalar lengthscale's gradient is their
  *   sum), [d] the outputscale, [d + 1] the noise; the columns folded in so far (either may be NULL). Synchronises.
- * slq_kernel_grad_reset: values and count back to 0 (asynchronous). */
+ * slq_kernel_grad_reset: values and count back to 0 (asynchronous).
+ * Not built for an operator with a diagonal scale (slq_kernel_set_diag_scale): create and every update refuse it with SLQ_EINVAL. */
 typedef struct slq_kernel_grad slq_kernel_grad;
 int slq_kernel_grad_create(slq_context *ctx, slq_operator *op, slq_kernel_grad **out);
 int slq_kernel_grad_update(slq_kernel_grad *g, slq_dmat *Z, int z0, slq_dmat *W, int w0, int m, double alpha, double beta);
@@ -554,7 +576,9 @@ int slq_debug_kernel_grad_schedule(int64_t n, int m, int num_cus, int64_t *out, 
  * Both: SLQ_EINVAL, nothing launched: a NULL handle, trans not 0 or 1, b < 1, a leading dimension or a row count that does not
  *   fit the direction, a column range outside its matrix, overlapping ranges of one matrix, a matrix of another context.
  * slq_debug_kernel_cross_points: z*^T (dpad x mpad; dpad = d rounded up to 4, mpad = m rounded up to 16) and |z*|^2 (mpad) from
- *   the device, in the object's dtype, after the re-derivation a product would do (either may be NULL). Synchronises. */
+ *   the device, in the object's dtype, after the re-derivation a product would do (either may be NULL). Synchronises.
+ * A diagonal scale of the operator (slq_kernel_set_diag_scale) is IGNORED, as the noise is: C is defined on K0's points and profile. A
+ *   product over the training points of a scaled operator carries the bits of the same product on the unscaled one. */
 typedef struct slq_kernel_cross slq_kernel_cross;
 int slq_kernel_cross_create(slq_context *ctx, slq_operator *op, int64_t m, const void *points, int64_t ldp, slq_kernel_cross **out);
 int slq_kernel_cross_create_device(slq_context *ctx, slq_operator *op, int64_t m, const void *d_points, int64_t ldp, slq_kernel_cross **out);
@@ -597,7 +621,8 @@ int slq_debug_kernel_cross_schedule(int64_t nrows, int64_t nsum, int64_t b, int 
  * fp64 workgroups take at most 128 columns (two staged halves of W beside the accumulators), fp32 ones 256.
  * slq_debug_kernel_feature_frequencies: Omega^T as the device holds it, dpad x F2pad words of the object's dtype. Synchronises.
  * slq_debug_kernel_feature_schedule: the schedule of one product (csrc/slq_kernelfeature.hpp: kernel_feature_schedule) in the
- *   order of slq_debug_kernel_cross_schedule, the column chunks 128 wide with is_f64 != 0 and 256 otherwise; nout >= 71. No HIP call. */
+ *   order of slq_debug_kernel_cross_schedule, the column chunks 128 wide with is_f64 != 0 and 256 otherwise; nout >= 71. No HIP call.
+ * A diagonal scale of the operator (slq_kernel_set_diag_scale) is IGNORED, as the noise is: the features are those of K0's profile. */
 typedef struct slq_kernel_feature slq_kernel_feature;
 int slq_kernel_feature_create(slq_context *ctx, slq_operator *op, int64_t F2, const void *omega, int64_t ld, slq_kernel_feature **out);
 int slq_kernel_feature_matmat(slq_kernel_feature *feat, slq_kernel_cross *cross, const void *W, int64_t ldw, void *Y, int64_t ldy, int b);
@@ -658,7 +683,9 @@ int slq_debug_kernel_feature_adjoint_schedule(int64_t F2, int64_t nrows, int64_t
  *   on the BASE operator of `pre` (SLQ_EINVAL "another operator" otherwise): sigma^-2 [tr D - sum_c (L H)_c^T D L_c] with tr D = 0
  *   for a lengthscale and n for the outputscale and the noise. The columns of the rank reached go through slq_kernel_grad_update 64
  *   at a time from two n x 64 matrices the preconditioner owns (allocated at the first call); one one-thread kernel then adds
- *   alpha n / sigma2 on the stream. Deterministic, asynchronous; the accumulator's column count is unchanged. */
+ *   alpha n / sigma2 on the stream. Deterministic, asynchronous; the accumulator's column count is unchanged.
+ * Not built for a base with a diagonal scale (slq_kernel_set_diag_scale): create and refresh refuse it, and so does every product,
+ *   apply and plan run on a preconditioned operator whose base was scaled later (SLQ_EINVAL; clear the scale, then refresh). */
 int slq_kernel_precond_create(slq_context *ctx, slq_operator *kernel_op, int rank_max, double tol, slq_operator **out);
 int slq_kernel_precond_refresh(slq_operator *pre);
 int slq_kernel_precond_info(const slq_operator *pre, int *rank_max, int *rank, double *logdet_p, double *residual_trace, double *t_max);
@@ -705,7 +732,9 @@ int slq_debug_kernel_precond_timing(const slq_operator *pre, double *out2);
  * slq_kernel_pointgrad_reset: values and count back to 0 (asynchronous).
  * slq_kernel_precond_trace_pointgrad: vals = beta vals + alpha tr(P^-1 dA/dx) = beta vals - alpha sigma^-2 sum_c (L H)_c^T (dA/dx) L_c
  *   (tr dA/dx = 0), the columns of the rank reached 64 at a time through the matrices slq_kernel_precond_trace_grad uses. `grad`
- *   must be a training-form accumulator on the BASE of `pre`; a stale preconditioner is refused. The column count is unchanged. */
+ *   must be a training-form accumulator on the BASE of `pre`; a stale preconditioner is refused. The column count is unchanged.
+ * A diagonal scale of the operator (slq_kernel_set_diag_scale): the training form is not built for it (create and every update refuse
+ *   with SLQ_EINVAL); the cross form is defined on K0's points and profile and ignores it, as a cross product does. */
 typedef struct slq_kernel_pointgrad slq_kernel_pointgrad;
 int slq_kernel_pointgrad_create(slq_context *ctx, slq_operator *op, slq_kernel_pointgrad **out);
 int slq_kernel_pointgrad_create_cross(slq_context *ctx, slq_kernel_cross *cross, slq_kernel_pointgrad **out);

@@ -65,6 +65,9 @@ _SIGNATURES = {
 	"slq_kernel_set_parameters": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double]),
 	"slq_kernel_get_parameters": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), _P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 	"slq_debug_kernel_points": (C.c_int, [_P, _P, _P, _P]),
+	"slq_kernel_set_diag_scale": (C.c_int, [_P, _P, C.c_int64]),
+	"slq_kernel_get_diag_scale": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int)]),
+	"slq_debug_kernel_diag_scale": (C.c_int, [_P, _P]),
 	"slq_debug_kernel_schedule": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int]),
 	"slq_debug_operator_device_bytes": (C.c_int, [C.POINTER(C.c_int64)]),
 	"slq_callback_create": (C.c_int, [_P, C.c_int, C.c_int64, MATVEC_FN, _P, _PP]),

@@ -158,6 +158,9 @@ def kernel_trace_fun(X, kernel, lengthscale, outputscale, noise, fun="log", deg:
 	gives the same bits."""
 	if method not in METHODS:
 		raise ValueError(f"unknown method '{method}' (one of {', '.join(METHODS)})")
+	if kw.get("diag_scale") is not None or getattr(X, "diag_scale", None) is not None:
+		raise ValueError("kernel_trace_fun is not built for a KernelOperator with a diagonal scale (diag_scale / set_diag_scale): "
+						 "use gp.fixed_noise_posterior for per-point noise and gp.laplace for a non-Gaussian likelihood")  # fmt: skip
 	Xt = X if isinstance(X, torch.Tensor) and X.requires_grad else None
 	if isinstance(X, torch.Tensor):
 		X = X.detach()

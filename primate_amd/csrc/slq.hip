@@ -161,7 +161,7 @@ struct slq_plan {
   struct GraphEntry {
     int j0, j1;
     double rtol;
-    unsigned variant;
+    unsigned variant;  // (graph_variant: nstale, and the top bit for a kernel operator with a diagonal scale)
     hipGraphExec_t exec;
     bool xt_out;  // prev_xt after step j1 - 1
   };
@@ -1290,6 +1290,73 @@ extern "C" int slq_debug_kernel_points(slq_operator *op, void *zt, void *nrm, vo
   HIP_TRY(op->k_pts.download(zt, nrm, params, op->dtype));
   return SLQ_OK;
 }
+// ---- the diagonal scale: A = s diag(c) phi(r2) diag(c) + sigma2 I ----
+// The entries that are not built for a scaled operator ask here, at every use: the gradients, the preconditioner and everything on it.
+static int kernel_refuse_scaled(const slq_operator *op, const char *who) {
+  if (!op->k_scaled) return SLQ_OK;
+  return fail(SLQ_EINVAL, "%s: the kernel operator has a diagonal scale (slq_kernel_set_diag_scale): this entry is not built for a scaled operator", who);
+}
+extern "C" int slq_kernel_set_diag_scale(slq_operator *op, const double *c, int64_t n) {
+  if (!op) return fail(SLQ_EINVAL, "op is NULL");
+  if (op->kind == OP_KERNEL_PRECOND)
+    return fail(SLQ_EINVAL, "slq_kernel_set_diag_scale: a preconditioned kernel operator is not built for a diagonal scale");
+  if (op->kind != OP_KERNEL) return fail(SLQ_EINVAL, "slq_kernel_set_diag_scale: not a kernel operator");
+  if (!c) {  // clear: the operator is today's unscaled one again (the buffer stays where it is)
+    if (op->k_scaled) ++op->k_epoch;
+    op->k_scaled = false;
+    op->k_c_host.clear();
+    return SLQ_OK;
+  }
+  const bool f64 = op->dtype == SLQ_F64;
+  const KernelBad bad = f64 ? kernel_validate_diag_scale<double>(op->n, c, n) : kernel_validate_diag_scale<float>(op->n, c, n);
+  if (bad.what != KERNEL_OK) return kernel_bad(bad);
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  return create_guarded(nullptr, [&]() {
+    const size_t npad = (size_t)op->k_pts.npad;
+    if (!op->k_c) {
+      hipError_t e = op->k_c.alloc(npad * (f64 ? 8 : 4));
+      if (e == hipSuccess) e = op->k_c_stage.alloc((size_t)op->n * 8);
+      if (e != hipSuccess) {
+        op->k_c.release(), op->k_c_stage.release();
+        return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "slq_kernel_set_diag_scale: %s", hipGetErrorString(e));
+      }
+    }
+    std::vector<double> rounded((size_t)op->n);
+    for (size_t i = 0; i < rounded.size(); ++i) rounded[i] = f64 ? c[i] : (double)(float)c[i];
+    hipStream_t st = op->ctx->stream;
+    HIP_TRY(hipMemcpyAsync(op->k_c_stage.p, c, (size_t)op->n * 8, hipMemcpyHostToDevice, st));
+    const dim3 g((unsigned)((npad + 255) / 256));
+    if (f64) k_kernel_diag_scale<double><<<g, dim3(256), 0, st>>>((int)op->n, (int)npad, op->k_c_stage.as<const double>(), op->k_c.as<double>());
+    else k_kernel_diag_scale<float><<<g, dim3(256), 0, st>>>((int)op->n, (int)npad, op->k_c_stage.as<const double>(), op->k_c.as<float>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));  // (the caller's c has been read when this returns)
+    op->k_c_host.swap(rounded);
+    op->k_scaled = true;
+    ++op->k_epoch;
+    return (int)SLQ_OK;
+  });
+}
+extern "C" int slq_kernel_get_diag_scale(const slq_operator *op, double *c, int64_t n, int *is_set) {
+  if (!op) return fail(SLQ_EINVAL, "op is NULL");
+  if (op->kind != OP_KERNEL) return fail(SLQ_EINVAL, "slq_kernel_get_diag_scale: not a kernel operator");
+  if (is_set) *is_set = op->k_scaled ? 1 : 0;
+  if (c) {
+    if (n != op->n) return fail(SLQ_EINVAL, "slq_kernel_get_diag_scale: room for %lld entries, the operator has n = %lld points", (long long)n, (long long)op->n);
+    if (!op->k_scaled) return fail(SLQ_EINVAL, "slq_kernel_get_diag_scale: no diagonal scale is set (is_set reports it; pass c = NULL to ask)");
+    std::copy(op->k_c_host.begin(), op->k_c_host.end(), c);
+  }
+  return SLQ_OK;
+}
+// the npad words of the scale as the product kernel reads them, in the operator's dtype (tests)
+extern "C" int slq_debug_kernel_diag_scale(slq_operator *op, void *c_dev_words) {
+  if (!op || !c_dev_words) return fail(SLQ_EINVAL, "slq_debug_kernel_diag_scale: op/c_dev_words is NULL");
+  if (op->kind != OP_KERNEL) return fail(SLQ_EINVAL, "slq_debug_kernel_diag_scale: not a kernel operator");
+  if (!op->k_scaled) return fail(SLQ_EINVAL, "slq_debug_kernel_diag_scale: no diagonal scale is set");
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  HIP_TRY(hipStreamSynchronize(op->ctx->stream));
+  HIP_TRY(hipMemcpy(c_dev_words, op->k_c.p, (size_t)op->k_pts.npad * (op->dtype == SLQ_F64 ? 8 : 4), hipMemcpyDeviceToHost));
+  return SLQ_OK;
+}
 // kernel_schedule() of slq_kernelop.hpp as an array: rows per block, row blocks, 16-column tiles per workgroup, column chunks, slabs,
 // then slab_begin[0 .. slabs]. No HIP call.
 extern "C" int slq_debug_kernel_schedule(int64_t n, int panel_width, int panels, int num_cus, int64_t *out, int nout) {
@@ -2309,6 +2376,7 @@ static int launch_dense_mfma(slq_plan *p, const void *Wc, const void *Wp, void *
 // A preconditioned kernel operator whose base has new hyperparameters is stale until slq_kernel_precond_refresh: its factor, G and
 // logdet P belong to the old ones. Every product, apply and plan run asks here first (a captured graph is not replayed either).
 static int precond_check_fresh(const slq_operator *op, const char *who) {
+  if (op->kind == OP_KERNEL_PRECOND) SLQ_TRY(kernel_refuse_scaled(op->pre->base, who));  // (a base scaled after the factor was built: DESIGN.md §4.23)
   if (op->kind != OP_KERNEL_PRECOND || op->pre->epoch == op->pre->base->k_epoch) return SLQ_OK;
   return fail(SLQ_EINVAL, "%s: the preconditioner is stale: call slq_kernel_precond_refresh (the base operator's hyperparameters have changed)", who);
 }
@@ -2323,8 +2391,12 @@ static int launch_kernel_product(slq_plan *p, const slq_operator *op, const void
   int log2pw = 0;
   while ((1 << log2pw) < p->PW) ++log2pw;
   char *raw = (char *)p->T + (S.nslabs > 1 ? (size_t)p->slot_stride * p->esz : 0);
-  const KernelPanelArgs a{p->n, (int)op->k_pts.npad, op->k_pts.dpad / 4, op->k_pts.zt, op->k_pts.nrm, op->k_pts.params, Wc, log2pw, p->NP * p->PW, raw, p->slot_stride};
-  const bool ok = p->dtype == SLQ_F64 ? kernel_panel_launch<double>(op->k_profile, S, a, st) : kernel_panel_launch<float>(op->k_profile, S, a, st);
+  const KernelPanelArgs a{p->n, (int)op->k_pts.npad, op->k_pts.dpad / 4, op->k_pts.zt, op->k_pts.nrm, op->k_pts.params, Wc, log2pw, p->NP * p->PW, raw, p->slot_stride,
+                          op->k_scaled ? op->k_c.p : nullptr};
+  // (a diagonal scale, DESIGN.md §4.23: another kernel, the same schedule and slab sum - which is why the scale is in the graph key, graph_variant)
+  bool ok;
+  if (op->k_scaled) ok = p->dtype == SLQ_F64 ? kernel_panel_scaled_launch<double>(op->k_profile, S, a, st) : kernel_panel_scaled_launch<float>(op->k_profile, S, a, st);
+  else ok = p->dtype == SLQ_F64 ? kernel_panel_launch<double>(op->k_profile, S, a, st) : kernel_panel_launch<float>(op->k_profile, S, a, st);
   if (!ok) return fail(SLQ_EINVAL, "kernel operator: no product kernel for profile %d with %d column tiles", op->k_profile, S.col_blocks);
   if (S.nslabs > 1) {
     const dim3 gS(p->nblkS, p->NP);
@@ -3153,6 +3225,12 @@ extern "C" int slq_plan_steps_done(const slq_plan *p, int *cur) {
 }
 
 constexpr size_t kGraphCacheMax = 16;
+// What can change under a live plan and changes the launch sequence: the number of stale ring columns, and whether the plan's kernel
+// operator has a diagonal scale - k_kernel_panel_scaled is another kernel than k_kernel_panel, so a graph captured in one state must not
+// be replayed in the other. New VALUES of the scale need no new graph: the kernel reads them from a fixed address.
+static unsigned graph_variant(const slq_plan *p) {
+  return (unsigned)p->nstale | (p->op->kind == OP_KERNEL && p->op->k_scaled ? 0x80000000u : 0u);
+}
 
 static int run_range(slq_plan *p, double rtol, int j0, int j1) {
   SLQ_TRY(precond_check_fresh(p->op, "slq_plan_run"));
@@ -3170,7 +3248,7 @@ static int run_range(slq_plan *p, double rtol, int j0, int j1) {
   if (!graph_ok) {
     SLQ_TRY(enqueue_run(p, rtol, j0, j1, lazy_tail));
   } else {
-    const unsigned variant = (unsigned)p->nstale;
+    const unsigned variant = graph_variant(p);
     size_t gi = 0;
     for (; gi < p->graphs.size(); ++gi) {
       const auto &g = p->graphs[gi];
@@ -3500,7 +3578,7 @@ static int replay_action(slq_plan *p) {
   if (!graph_ok) {
     rc = enqueue_replay(p, rtol);
   } else {
-    const unsigned variant = (unsigned)p->nstale;  // (the replay has a cache of its own: replay_exec)
+    const unsigned variant = graph_variant(p);  // (the replay has a cache of its own: replay_exec)
     if (p->replay_exec && (p->replay_rtol != rtol || p->replay_variant != variant)) {
       HIP_TRY(hipGraphExecDestroy(p->replay_exec));
       p->replay_exec = nullptr;
@@ -4235,6 +4313,7 @@ extern "C" int slq_kernel_grad_create(slq_context *ctx, slq_operator *op, slq_ke
   *out = nullptr;
   if (op->kind != OP_KERNEL)
     return fail(SLQ_EINVAL, "slq_kernel_grad_create: the operator is of kind '%s', not a kernel operator (slq_kernel_create)", op_kind_name(op->kind));
+  SLQ_TRY(kernel_refuse_scaled(op, "slq_kernel_grad_create"));
   if (op->dtype != SLQ_F64) return fail(SLQ_EINVAL, "slq_kernel_grad_create: the operator's dtype is fp32: the accumulator is fp64 only (the device matrices are fp64)");
   if (op->ctx != ctx) return fail(SLQ_EINVAL, "slq_kernel_grad_create: the operator belongs to another context");
   if (ctx->dead) return fail(SLQ_EINVAL, "slq_kernel_grad_create: the context has been destroyed");
@@ -4270,6 +4349,7 @@ extern "C" int slq_kernel_grad_update(slq_kernel_grad *g, slq_dmat *Z, int z0, s
     return fail(SLQ_EINVAL, "slq_kernel_grad_update: the operator has %lld points, Z %lld rows, W %lld", (long long)g->n, (long long)Z->n, (long long)W->n);
   if (W->ctx != g->ctx || Z->ctx != g->ctx) return fail(SLQ_EINVAL, "slq_kernel_grad_update: a matrix belongs to another context");
   if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(SLQ_EINVAL, "slq_kernel_grad_update: alpha = %g, beta = %g must be finite", alpha, beta);
+  SLQ_TRY(kernel_refuse_scaled(g->op, "slq_kernel_grad_update"));
   HIP_TRY(hipSetDevice(g->ctx->device));
   const slq_operator *op = g->op;
   const KernelGradSchedule S = kernel_grad_schedule(g->n, m, g->ctx->num_cus);
@@ -4796,6 +4876,7 @@ static int kernel_precond_create_body(slq_context *ctx, slq_operator *base, int 
   *out = nullptr;
   if (base->kind != OP_KERNEL)
     return fail(SLQ_EINVAL, "slq_kernel_precond_create: the base operator is of kind '%s', not a kernel operator (slq_kernel_create)", op_kind_name(base->kind));
+  SLQ_TRY(kernel_refuse_scaled(base, "slq_kernel_precond_create"));
   if (base->dtype != SLQ_F64) return fail(SLQ_EINVAL, "slq_kernel_precond_create: the base operator's dtype is fp32: the preconditioner is fp64 only");
   if (base->ctx != ctx) return fail(SLQ_EINVAL, "slq_kernel_precond_create: the base operator belongs to another context");
   if (!(base->k_noise > 0.0)) return fail(SLQ_EINVAL, "slq_kernel_precond_create: the base operator's noise sigma2 is 0: P^{-1/2} needs sigma2 > 0");
@@ -4831,6 +4912,7 @@ extern "C" int slq_kernel_precond_create(slq_context *ctx, slq_operator *kernel_
 
 extern "C" int slq_kernel_precond_refresh(slq_operator *op) {
   SLQ_TRY(precond_handle(op, "slq_kernel_precond_refresh"));
+  SLQ_TRY(kernel_refuse_scaled(op->pre->base, "slq_kernel_precond_refresh"));
   HIP_TRY(hipSetDevice(op->ctx->device));
   return create_guarded(nullptr, [&]() { return precond_factorise(op); });
 }
@@ -4988,6 +5070,7 @@ static int kernel_pointgrad_create_body(slq_context *ctx, slq_operator *op, slq_
   *out = nullptr;
   if (op->kind != OP_KERNEL)
     return fail(SLQ_EINVAL, "%s: the operator is of kind '%s', not a kernel operator (slq_kernel_create; of a preconditioned operator pass the base)", who, op_kind_name(op->kind));
+  if (!cross) SLQ_TRY(kernel_refuse_scaled(op, who));  // (the cross form is defined on K0's points and profile, as a cross product is)
   if (op->dtype != SLQ_F64) return fail(SLQ_EINVAL, "%s: the operator's dtype is fp32: the accumulator is fp64 only (the device matrices are fp64)", who);
   if (op->ctx != ctx || (cross && cross->ctx != ctx)) return fail(SLQ_EINVAL, "%s: the operator belongs to another context", who);
   if (ctx->dead) return fail(SLQ_EINVAL, "%s: the context has been destroyed", who);
@@ -5053,6 +5136,7 @@ extern "C" int slq_kernel_pointgrad_update(slq_kernel_pointgrad *g, slq_dmat *Z,
   }
   if (W->ctx != g->ctx || Z->ctx != g->ctx) return fail(SLQ_EINVAL, "slq_kernel_pointgrad_update: a matrix belongs to another context");
   if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(SLQ_EINVAL, "slq_kernel_pointgrad_update: alpha = %g, beta = %g must be finite", alpha, beta);
+  if (!g->cross) SLQ_TRY(kernel_refuse_scaled(g->op, "slq_kernel_pointgrad_update"));
   HIP_TRY(hipSetDevice(g->ctx->device));
   const slq_operator *op = g->op;
   if (g->cross && g->cross->epoch != op->k_epoch) SLQ_TRY(kernel_cross_rescale(g->cross));  // the hyperparameters have moved: z* follow, before this update

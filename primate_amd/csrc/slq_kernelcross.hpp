@@ -57,7 +57,7 @@ void kernel_cross_sum_launch(int dtype_is_f64, int64_t nrows, int b, int nslabs,
 // stride = 32 words mod 64): that shape would put 8 rows on one bank; 4 rows x 16 columns per wave - 32-byte runs of a column - is two
 // lanes per bank, what a 512-byte store costs anyway.
 struct KernelColumnLayout {
-  static constexpr bool kDiagonal = false, kNoise = false;
+  static constexpr bool kDiagonal = false, kNoise = false, kScaled = false;  // (a cross product is defined on K0's points and profile: it ignores a diagonal scale)
   int64_t ldw, ldo;
   template <int NC> __device__ __forceinline__ static constexpr int chunk_cols() { return 16 * kKernelMaxColBlocks; }
   template <typename F, int NC> __device__ __forceinline__ static int w_row(int e) { return sizeof(F) == 8 ? ((e & 3) | ((e >> 4) & 12)) : (e & 15); }

@@ -15,7 +15,7 @@
 //     kernel_profile_pair, kernel_profile   phi and chi = -2 dphi/dr2 of the four profiles
 //     KernelTile              the z tile and the norms of the summed points in LDS, the row points' fragments, G^T and r2
 //     kernel_tile_walk        the double-buffered loop over a slab's tiles
-//     kernel_product          Y = s phi(r2) W (+ sigma2 W) for a Layout of W and Y: the body of k_kernel_panel and k_kernel_cross
+//     kernel_product          Y = s phi(r2) W (+ sigma2 W) for a Layout of W and Y: the body of k_kernel_panel, k_kernel_panel_scaled and k_kernel_cross
 //     kernel_for_profile / _ncb / _dq   the launch ladder: a run-time (profile, column tiles, depth) to its instantiation
 #pragma once
 
@@ -255,6 +255,16 @@ __device__ __forceinline__ void kernel_tile_walk(int t_begin, int t_end, const F
 //                                      there is a second workgroup (each layout keeps the constant its kernel was compiled with)
 //   kDiagonal                          r2 = 0 where the summed point IS the row point (one point set), or no such rule (two sets)
 //   finish(sig, W, off, v)             the epilogue on v = s * acc; kNoise: sig = sigma2 in slab 0, else no sigma2 is read
+//   kScaled, scale<F>()                a diagonal scale c of the (one) point set: Y = s diag(c) phi(r2) diag(c) W. c_j of
+//                                      the summed points travels with |z_j|^2 - one word per point, fetched into a register, stashed to
+//                                      Cs[16] between the two barriers - and multiplies the lane's four K values after the profile, once per
+//                                      tile whatever NCB is; c_i meets s in the epilogue. Padding points carry c = 0. The branch is
+//                                      compile-time: a layout with kScaled == false compiles to what it compiled to without it.
+// (the LDS words of a scaled layout's c tile: a function, so that an unscaled instantiation does not hold them)
+template <typename F> __device__ __forceinline__ F *kernel_scale_tile() {
+  __shared__ F Cs[16];
+  return Cs;
+}
 template <typename F, int PROFILE, int NCB, int DQ, typename Layout>
 __device__ __forceinline__ void kernel_product(int nrows, int rpad, int nsum, int spad, int dq, const F *rzt, const F *rnrm, const F *szt, const F *snrm,
                                                const F *params, const F *W, int ncols, int tiles_per_slab, F *out, int64_t slab_stride, const Layout L) {
@@ -282,6 +292,9 @@ __device__ __forceinline__ void kernel_product(int nrows, int rpad, int nsum, in
   for (int cb = 0; cb < NCB; ++cb) acc[cb] = (V4)(F)0;
 
   F wreg[WPT], zreg[T::ZPT], nreg = (F)0;
+  [[maybe_unused]] F creg = (F)0;
+  [[maybe_unused]] F *Cs = nullptr;
+  if constexpr (Layout::kScaled) Cs = kernel_scale_tile<F>();
   auto fetch = [&](int t) {
     const int j0 = t * 16;
 #pragma unroll
@@ -298,6 +311,8 @@ __device__ __forceinline__ void kernel_product(int nrows, int rpad, int nsum, in
       zreg[u] = (e < DQ * 64 && k < 4 * dq) ? szt[(int64_t)k * spad + j0 + jj] : (F)0;
     }
     if (tid < 16) nreg = snrm[j0 + tid];
+    if constexpr (Layout::kScaled)
+      if (tid < 16) creg = L.template scale<F>()[j0 + tid];  // (j0 + tid < spad: the scale has spad words, zeros beyond nsum)
   };
   auto stash = [&]() {
 #pragma unroll
@@ -306,6 +321,8 @@ __device__ __forceinline__ void kernel_product(int nrows, int rpad, int nsum, in
       if (e < 16 * NC) Ws[Layout::template w_row<F, NC>(e)][Layout::template w_col<F, NC>(e)] = wreg[u];
     }
     T::stash(Zs, Ns, tid, zreg, nreg);
+    if constexpr (Layout::kScaled)
+      if (tid < 16) Cs[tid] = creg;
   };
   kernel_tile_walk(t_begin, t_end, fetch, stash, [&](int t) {
     const V4 g = T::gram(Zs, zi, dq, lr, lk);
@@ -313,6 +330,10 @@ __device__ __forceinline__ void kernel_product(int nrows, int rpad, int nsum, in
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       kv[r] = kernel_profile<F, PROFILE>(T::r2(g, r, ni, Ns, lk, Layout::kDiagonal && t * 16 + T::jr(lk, r) == i0 + lr));
+    if constexpr (Layout::kScaled) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) kv[r] *= Cs[T::jr(lk, r)];
+    }
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
@@ -322,6 +343,14 @@ __device__ __forceinline__ void kernel_product(int nrows, int rpad, int nsum, in
   F sig = (F)0;
   if constexpr (Layout::kNoise) sig = blockIdx.z == 0 ? params[1] : (F)0;
   F *o = out + (int64_t)blockIdx.z * slab_stride;
+  [[maybe_unused]] F sc[4];  // s c_i of the lane's four rows
+  if constexpr (Layout::kScaled) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = i0 + T::jr(lk, r);
+      sc[r] = i < nrows ? s * L.template scale<F>()[i] : (F)0;
+    }
+  }
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb) {
     const int g = col0 + cb * 16 + lr;
@@ -330,7 +359,8 @@ __device__ __forceinline__ void kernel_product(int nrows, int rpad, int nsum, in
       const int i = i0 + T::jr(lk, r);
       if (i < nrows && g < ncols) {
         const int64_t off = L.out_off(i, g);
-        o[off] = L.finish(sig, W, off, s * acc[cb][r]);
+        if constexpr (Layout::kScaled) o[off] = L.finish(sig, W, off, sc[r] * acc[cb][r]);
+        else o[off] = L.finish(sig, W, off, s * acc[cb][r]);
       }
     }
   }

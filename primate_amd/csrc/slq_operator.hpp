@@ -232,4 +232,11 @@ struct slq_operator {
   double k_s = 1.0, k_noise = 0.0;
   std::unique_ptr<slq::KernelPrecond> pre;  // OP_KERNEL_PRECOND: B = M A M on the points of pre->base
   uint64_t k_epoch = 0;  // host: incremented by every slq_kernel_set_parameters; a slq_kernel_cross compares it with the one its z* were derived at
+  // the diagonal scale c of slq_kernel_set_diag_scale: A = s diag(c) phi(r2) diag(c) + sigma2 I. k_c: npad words in
+  // the operator's dtype, allocated by the first set and never moved (a captured graph of the scaled product sees new values);
+  // k_c_stage: the n doubles as given, on their way to k_kernel_diag_scale; k_c_host: c as rounded, for slq_kernel_get_diag_scale.
+  // Setting or clearing the scale bumps k_epoch; whether it is set is part of a plan's graph key (scaled and unscaled are two kernels).
+  bool k_scaled = false;
+  slq::DevBuf k_c, k_c_stage;
+  std::vector<double> k_c_host;
 };

@@ -191,6 +191,9 @@ class DeviceOperator:
 			else:
 				check(L.slq_kernel_create(self.ctx._h, dt, n, d, ptr(A.X), d, prof, ptr(ls), ls.size, float(A.outputscale), float(A.noise), C.byref(h)))
 			self.kind, self.nnz = "kernel", int(n * d)
+			if getattr(A, "diag_scale", None) is not None:
+				self._h = h  # (close() frees the handle if the scale is refused)
+				self.set_kernel_diag_scale(A.diag_scale)
 			A._device_ops = getattr(A, "_device_ops", [])
 			import weakref
 
@@ -260,15 +263,40 @@ class DeviceOperator:
 		ls = np.ascontiguousarray(np.atleast_1d(lengthscale), dtype=np.float64)
 		check(_capi.lib().slq_kernel_set_parameters(self._h, ptr(ls), ls.size, float(outputscale), float(noise)))
 
+	def set_kernel_diag_scale(self, c) -> None:
+		"""The diagonal scale of a kernel operator (slq_kernel_set_diag_scale): A = s diag(c) phi(r2) diag(c) + noise I,
+		c of n entries, finite and >= 0, rounded once to the operator's dtype; None clears it. Live plans, and the graphs they captured,
+		compute with the new state from their next run."""
+		if c is None:
+			check(_capi.lib().slq_kernel_set_diag_scale(self._h, None, 0))
+			return
+		c = np.ascontiguousarray(np.asarray(c, dtype=np.float64).ravel())
+		check(_capi.lib().slq_kernel_set_diag_scale(self._h, ptr(c), c.size))
+
+	def kernel_diag_scale(self):
+		"""The diagonal scale as rounded to the operator's dtype (float64 array of n entries), or None when none is set
+		(slq_kernel_get_diag_scale)."""
+		L = _capi.lib()
+		is_set = C.c_int()
+		check(L.slq_kernel_get_diag_scale(self._h, None, 0, C.byref(is_set)))
+		if not is_set.value:
+			return None
+		c = np.empty(self.shape[0])
+		check(L.slq_kernel_get_diag_scale(self._h, ptr(c), c.size, None))
+		return c
+
 	def kernel_parameters(self) -> dict:
-		"""What slq_kernel_get_parameters reports: d, kernel, the d lengthscales, outputscale, noise."""
+		"""What slq_kernel_get_parameters reports: d, kernel, the d lengthscales, outputscale, noise; and `scaled`: whether a diagonal
+		scale is set (slq_kernel_get_diag_scale)."""
 		L = _capi.lib()
 		d, prof, s, v = C.c_int(), C.c_int(), C.c_double(), C.c_double()
 		check(L.slq_kernel_get_parameters(self._h, C.byref(d), C.byref(prof), None, 0, C.byref(s), C.byref(v)))
 		ls = np.empty(d.value)
 		check(L.slq_kernel_get_parameters(self._h, None, None, ptr(ls), d.value, None, None))
 		name = {v_: k for k, v_ in _capi.KERNEL_PROFILES.items()}[prof.value]
-		return dict(d=d.value, kernel=name, lengthscale=ls, outputscale=s.value, noise=v.value)
+		is_set = C.c_int()
+		check(L.slq_kernel_get_diag_scale(self._h, None, 0, C.byref(is_set)))
+		return dict(d=d.value, kernel=name, lengthscale=ls, outputscale=s.value, noise=v.value, scaled=bool(is_set.value))
 
 	## ---- a preconditioned kernel operator (kind "kernel_precond"; slq_kernel_precond_*, DESIGN.md §4.18) ----
 	def _need_precond(self, what: str) -> None:

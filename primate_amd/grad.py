@@ -279,6 +279,9 @@ def kernel_trace_grad(M, pdf: Union[str, None] = "rademacher", count: int = 256,
 		raise ValueError("kernel_trace_grad: the function of a preconditioned operator is not differentiated here: the gradient of logdet A through the pivoted-Cholesky preconditioner is gp.logdet_grad (gp.mll for the marginal likelihood)")
 	if getattr(K, "_slq_kind", None) != "kernel":
 		raise ValueError("kernel_trace_grad needs a function of a KernelOperator (for the gradient on a sparsity pattern use trace_grad)")
+	from .operators import refuse_diag_scale
+
+	refuse_diag_scale(K, "kernel_trace_grad")
 	if np.dtype(M.dtype) != np.float64 or np.dtype(K.dtype) != np.float64:
 		raise ValueError("kernel_trace_grad is fp64 only (the device matrices are fp64): build the KernelOperator and M with dtype=np.float64")
 	count, batch = int(count), int(batch)
@@ -361,6 +364,9 @@ def kernel_quadratic_grad(K, U, V=None) -> dict:
 		raise ValueError("kernel_quadratic_grad: pass the base KernelOperator, not its preconditioner (the data-fit gradient of a marginal likelihood through the preconditioner is part of gp.mll; gp.logdet_grad has the log-determinant's)")
 	if getattr(K, "_slq_kind", None) != "kernel":
 		raise ValueError("kernel_quadratic_grad needs a KernelOperator")
+	from .operators import refuse_diag_scale
+
+	refuse_diag_scale(K, "kernel_quadratic_grad")
 	if np.dtype(K.dtype) != np.float64:
 		raise ValueError("kernel_quadratic_grad is fp64 only (the device matrices are fp64): build the KernelOperator with dtype=np.float64")
 	n = int(K.shape[0])
@@ -400,6 +406,10 @@ def kernel_point_grad(K, U, V=None, Xnew=None) -> np.ndarray:
 		raise ValueError("kernel_point_grad: pass the base KernelOperator, not its preconditioner")
 	if getattr(K, "_slq_kind", None) != "kernel":
 		raise ValueError("kernel_point_grad needs a KernelOperator")
+	from .operators import refuse_diag_scale
+
+	if Xnew is None:  # (the cross form is defined on K0's points and profile, as a cross product is: it ignores the scale)
+		refuse_diag_scale(K, "kernel_point_grad")
 	if np.dtype(K.dtype) != np.float64:
 		raise ValueError("kernel_point_grad is fp64 only (the device matrices are fp64): build the KernelOperator with dtype=np.float64")
 	n = int(K.shape[0])

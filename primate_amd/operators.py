@@ -387,11 +387,21 @@ class KernelOperator(LinearOperator):
 	`lengthscale`: a scalar or one per dimension. mean(x) is fixed at construction: per dimension the sum over the points in row
 	order in float64, divided by n. `set_parameters` changes lengthscale / outputscale / noise, also on operators already wrapped in
 	a `MatrixFunction` - live plans compute with the new values from their next run. The host `_matvec` / `_matmat` are blocked
-	NumPy in float64 from the definition: the plugin surface, and the model of the tests."""
+	NumPy in float64 from the definition: the plugin surface, and the model of the tests.
+
+	`diag_scale`: an optional vector c of n entries, finite and >= 0, rounded once to `dtype` (the operator is defined
+	on the rounded c, `self.diag_scale`), with which
+
+	    A = outputscale * diag(c) phi(r2) diag(c) + noise * I.
+
+	Fixed per-point noise K0 + diag(e) is E^{1/2} (D K0 D + I) E^{1/2} with c = e^{-1/2}; the B of a Laplace approximation is this
+	operator with c = W^{1/2} and noise = 1 (`gp.fixed_noise_posterior`, `gp.laplace`). `set_diag_scale(c_or_None)` changes or clears
+	it, on live device operators too. `cross()` and `features()` are defined on K0's points and profile and ignore the scale;
+	`preconditioned()`, the gradients and the Gaussian-likelihood entries of `gp` refuse a scaled operator."""
 
 	_slq_kind = "kernel"
 
-	def __init__(self, X, kernel: str = "rbf", lengthscale=1.0, outputscale: float = 1.0, noise: float = 0.0, dtype=None):
+	def __init__(self, X, kernel: str = "rbf", lengthscale=1.0, outputscale: float = 1.0, noise: float = 0.0, dtype=None, diag_scale=None):
 		self._X_device = None
 		if type(X).__module__.split(".")[0] == "torch":
 			if dtype is None:
@@ -425,6 +435,30 @@ class KernelOperator(LinearOperator):
 		self.mean = np.cumsum(self.X, axis=0, dtype=np.float64)[-1] / np.float64(n)
 		self.lengthscale, self.outputscale, self.noise = self._check_parameters(lengthscale, outputscale, noise)
 		self._z = None
+		self.diag_scale = self._check_diag_scale(diag_scale)
+
+	def _check_diag_scale(self, c):
+		"""None, or c as the operator holds it: n entries, finite and >= 0, rounded once to the operator's dtype."""
+		if c is None:
+			return None
+		n = self.shape[0]
+		c = np.asarray(c, dtype=np.float64).ravel()
+		if c.size != n:
+			raise ValueError(f"kernel operator: the diagonal scale has {c.size} entries, the operator n = {n} points")
+		with np.errstate(over="ignore"):
+			cr = c.astype(self.dtype)
+		bad = np.flatnonzero(~(np.isfinite(c) & (c >= 0) & np.isfinite(cr)))
+		if bad.size:
+			raise ValueError(f"kernel operator: diag_scale[{int(bad[0])}] = {c[bad[0]]} is not a finite number >= 0 in the operator's dtype")
+		return cr
+
+	def set_diag_scale(self, c) -> None:
+		"""A new diagonal scale (None: clear it), forwarded to every live device operator built from this object."""
+		self.diag_scale = self._check_diag_scale(c)
+		for ref in getattr(self, "_device_ops", []):
+			op = ref()
+			if op is not None and getattr(op, "_h", None):
+				op.set_kernel_diag_scale(self.diag_scale)
 
 	def _check_parameters(self, lengthscale, outputscale, noise):
 		d = self.X.shape[1]
@@ -469,6 +503,9 @@ class KernelOperator(LinearOperator):
 		r2 = np.maximum(nrm[idx, None] + nrm[None, :] - 2.0 * (z[idx] @ z.T), 0.0)
 		r2[np.arange(idx.size), idx] = 0.0
 		K = self.outputscale * _kernel_profile(self.kernel, r2)
+		if self.diag_scale is not None:
+			c = self.diag_scale.astype(np.float64)
+			K = K * (c[idx, None] * c[None, :])
 		K[np.arange(idx.size), idx] += self.noise
 		return K
 
@@ -495,7 +532,8 @@ class KernelOperator(LinearOperator):
 
 	def preconditioned(self, rank: int = 100, tol: float = 0.0) -> "PreconditionedKernelOperator":
 		"""B = M A M with M = P^{-1/2} of a rank-`rank` pivoted-Cholesky factor of this operator without its noise (DESIGN.md
-		§4.18): the operator to run Lanczos on when the noise is small. It follows this operator's hyperparameters."""
+		§4.18): the operator to run Lanczos on when the noise is small. It follows this operator's hyperparameters. Not built for an
+		operator with a diagonal scale."""
 		return PreconditionedKernelOperator(self, rank, tol)
 
 	def cross(self, Xnew) -> "KernelCrossOperator":
@@ -510,6 +548,18 @@ class KernelOperator(LinearOperator):
 		if frequencies is not None:
 			return KernelFeatures(self, frequencies)
 		return KernelFeatures(self, draw_kernel_frequencies(self.kernel, int(num_features), self.X.shape[1], np.random.default_rng(seed)))
+
+
+def refuse_diag_scale(K, what: str) -> None:
+	"""ValueError where `K` is a KernelOperator with a diagonal scale: `what` is not built for one. Host-only: called
+	before the library is touched."""
+	if getattr(K, "_slq_kind", None) == "kernel_precond":
+		K = K.base
+	if getattr(K, "diag_scale", None) is not None:
+		raise ValueError(
+			f"{what} is not built for a KernelOperator with a diagonal scale (diag_scale / set_diag_scale): "
+			"use gp.fixed_noise_posterior for per-point noise and gp.laplace for a non-Gaussian likelihood"
+		)
 
 
 def draw_kernel_frequencies(kernel: str, num_features: int, d: int, rng) -> np.ndarray:
@@ -592,6 +642,7 @@ class PreconditionedKernelOperator(LinearOperator):
 	def __init__(self, base: KernelOperator, rank: int = 100, tol: float = 0.0):
 		if getattr(base, "_slq_kind", None) != "kernel":
 			raise ValueError("PreconditionedKernelOperator needs a KernelOperator")
+		refuse_diag_scale(base, "the pivoted-Cholesky preconditioner")
 		if np.dtype(base.dtype) != np.float64:
 			raise ValueError(f"the preconditioner is fp64 only: the KernelOperator is {np.dtype(base.dtype)}")
 		if not base.noise > 0:
