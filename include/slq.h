@@ -189,6 +189,29 @@ int slq_kernel_set_diag_scale(slq_operator *op, const double *c, int64_t n);
 int slq_kernel_get_diag_scale(const slq_operator *op, double *c, int64_t n, int *is_set);
 int slq_debug_kernel_diag_scale(slq_operator *op, void *c_dev_words);
 int slq_debug_kernel_schedule(int64_t n, int panel_width, int panels, int num_cus, int64_t *out, int nout);
+/* A Toeplitz operator: A_ij = c[i-j] for i >= j, r[j-i] for j > i (r[0] is ignored, as in SciPy; r == NULL: r = c), with
+ * c and r given in double and ROUNDED ONCE to the operator's dtype. The operator is SYMMETRIC iff the rounded r[1:] equals c[1:] bitwise.
+ * A product is three FFT passes of length L (the smallest power of two >= 2n) along the rows of the probe panel as it stands in memory: a
+ * panel row of PW reals is PW/2 complex numbers, and T real gives T(x1 + i x2) = T x1 + i T x2, so one complex column carries the probes 2q
+ * and 2q+1. The symbol FFT_L([c, 0.., r_{n-1} .. r_1]) and every twiddle table are computed on the host in double and uploaded once per set.
+ * ERROR: for the output column k of the pair q, |got[:,k] - exact[:,k]|_2 <= eps log2(L) (sum|c| + sum|r[1:]|) |[x_2q, x_2q+1]|_2 - the error
+ * of a column is relative to the norm of its PAIR, not of the column (a zero probe next to a large one receives its rounding error).
+ * Padding columns of a plan's panel enter every product as zeros. n in [1, 2^22] (L <= 2^23). slq_operator_shape reports nnz = 2n - 1;
+ * slq_operator_set_parameter refuses the kind; slq_operator_matmat serves symmetric and non-symmetric operators; EVERY plan creation
+ * (slq_plan_create, _recompute, _chebyshev, _chebyshev_action, and the one-shot entries over them) refuses a non-symmetric one.
+ * slq_toeplitz_set_values: new c, r of n == the operator's n entries: the symbol is rewritten IN PLACE on the context stream (the call
+ *   returns when it is there); plans created before the call, and the graphs they captured, compute with the new values from their next
+ *   run. A set that would change the symmetry is refused. SLQ_EINVAL names the first entry that is not finite in the dtype.
+ * slq_toeplitz_get_values: the ROUNDED c and r (n entries each; NULL: not wanted) and whether the operator is symmetric.
+ * slq_debug_toeplitz_plan (no device): out[0] L, [1] levels (1: one kernel per panel, 2: three, 3: five), [2..4] the pass lengths
+ *   (product L; 1 where unused), [5] LDS bytes per workgroup of the largest kernel, [6] complex columns per workgroup, [7] workspace bytes of
+ *   a plan (one panel in flight; 0 with one kernel), [8] launches per panel, [9] the largest n supported; nout >= 10.
+ * slq_debug_toeplitz_symbol: the symbol the device holds, in natural order and at the scale of FFT_L(e): L complex numbers of the dtype. */
+int slq_toeplitz_create(slq_context *ctx, int dtype, int64_t n, const double *c, const double *r, slq_operator **out);
+int slq_toeplitz_set_values(slq_operator *op, const double *c, const double *r, int64_t n);
+int slq_toeplitz_get_values(const slq_operator *op, double *c, double *r, int64_t n, int *symmetric);
+int slq_debug_toeplitz_plan(int64_t n, int dtype, int panel_width, int64_t *out, int nout);
+int slq_debug_toeplitz_symbol(slq_operator *op, void *symbol_natural_order);
 /* Bytes of device memory the process's operators (and the scratch of operator builds in flight) hold now: back where it was once
  * every operator created since has been destroyed (tests). No HIP call. */
 int slq_debug_operator_device_bytes(int64_t *live);

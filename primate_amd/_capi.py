@@ -69,6 +69,11 @@ _SIGNATURES = {
 	"slq_kernel_get_diag_scale": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int)]),
 	"slq_debug_kernel_diag_scale": (C.c_int, [_P, _P]),
 	"slq_debug_kernel_schedule": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+	"slq_toeplitz_create": (C.c_int, [_P, C.c_int, C.c_int64, _P, _P, _PP]),
+	"slq_toeplitz_set_values": (C.c_int, [_P, _P, _P, C.c_int64]),
+	"slq_toeplitz_get_values": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int)]),
+	"slq_debug_toeplitz_plan": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+	"slq_debug_toeplitz_symbol": (C.c_int, [_P, _P]),
 	"slq_debug_operator_device_bytes": (C.c_int, [C.POINTER(C.c_int64)]),
 	"slq_callback_create": (C.c_int, [_P, C.c_int, C.c_int64, MATVEC_FN, _P, _PP]),
 	"slq_operator_destroy": (C.c_int, [_P]),

@@ -43,6 +43,7 @@
 #include "slq_kernelfeature.hpp"  // random Fourier features (slq_kernel_feature_*): schedule, the launch function of slq_kernelfeature.hip
 #include "slq_kernelfeatureadj.hpp"  // their adjoint (slq_kernel_feature_rmatmat / _rdmat): schedule, the launch function of slq_kernelfeatureadj.hip
 #include "slq_kernelpointgrad.hpp"  // gradients in the points (slq_kernel_pointgrad_*): schedule, the launch functions of slq_kernelpointgrad.hip
+#include "slq_toeplitz.hpp"  // the Toeplitz operator (slq_toeplitz_*): pass structure, host symbol transform, the launch functions of slq_toeplitz.hip
 #include "slq_operator.hpp"  // the operator handle and the values it owns (DevBuf, CsrArrays, TileStream, KernelPoints)
 
 using namespace slq;
@@ -1128,6 +1129,7 @@ extern "C" int slq_operator_set_parameter(slq_operator *op, double t) {
   if (!op) return fail(SLQ_EINVAL, "op is NULL");
   if (op->kind == OP_KERNEL) return fail(SLQ_EINVAL, "a kernel operator has no parameter t: its hyperparameters are set by slq_kernel_set_parameters");
   if (op->kind == OP_KERNEL_PRECOND) return fail(SLQ_EINVAL, "a preconditioned kernel operator has no parameter t: set the hyperparameters of its base operator, then call slq_kernel_precond_refresh");
+  if (op->kind == OP_TOEPLITZ) return fail(SLQ_EINVAL, "a Toeplitz operator has no parameter t: its values are set by slq_toeplitz_set_values");
   if (!op->vals_a || !op->vals_b) return fail(SLQ_EINVAL, "not an affine operator");
   HIP_TRY(hipSetDevice(op->ctx->device));
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (op->nnz + 255) / 256));
@@ -1457,6 +1459,137 @@ static bool ensure_ring_stream(slq_operator *op, int R) {
   }
 }
 
+// ---- Toeplitz operator (slq_toeplitz.hpp, slq_toeplitz.hip) ----
+static int toeplitz_check_n(const char *who, int64_t n) {
+  if (n < 1) return fail(SLQ_EINVAL, "%s: n = %lld must be at least 1", who, (long long)n);
+  if (n > kToeplitzMaxN) return fail(SLQ_EINVAL, "%s: n = %lld exceeds the supported maximum %lld (L = 2^%d)", who, (long long)n, (long long)kToeplitzMaxN, kToeplitzMaxLog2L);
+  return SLQ_OK;
+}
+// the symbol of (cr, rr) in double on the host, rounded to the dtype in the order the passes read it, into op->tz_sym on the
+// context stream (the buffer exists and keeps its address); waits for the upload (the host words go with this frame)
+template <typename F> static int toeplitz_upload_symbol(slq_operator *op, const std::vector<double> &cr, const std::vector<double> &rr) {
+  const ToeplitzPlan P = toeplitz_plan(op->n, (int)sizeof(F), 16);
+  const std::vector<std::complex<double>> s = toeplitz_symbol(P, cr, rr);
+  std::vector<F> words((size_t)2 * P.L);
+  toeplitz_device_symbol<F>(P, s, words.data());
+  for (const F v : words)
+    if (!std::isfinite(v)) return fail(SLQ_EINVAL, "Toeplitz operator: the symbol overflows the operator's dtype");
+  HIP_TRY(hipMemcpyAsync(op->tz_sym.p, words.data(), words.size() * sizeof(F), hipMemcpyHostToDevice, op->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(op->ctx->stream));
+  return SLQ_OK;
+}
+template <typename F> static int toeplitz_upload_tables(slq_operator *op) {
+  const ToeplitzPlan P = toeplitz_plan(op->n, (int)sizeof(F), 16);
+  hipStream_t st = op->ctx->stream;
+  std::vector<F> tab((size_t)kToeplitzTab);
+  toeplitz_device_tab<F>(tab.data());
+  hipError_t e = op->tz_sym.alloc((size_t)2 * P.L * sizeof(F));
+  if (e == hipSuccess) e = op->tz_tab.alloc(tab.size() * sizeof(F));
+  if (e == hipSuccess) e = hipMemcpyAsync(op->tz_tab.p, tab.data(), tab.size() * sizeof(F), hipMemcpyHostToDevice, st);
+  std::vector<F> tw[2];
+  for (int j = 0; j + 1 < P.levels && e == hipSuccess; ++j) {
+    const size_t count = (size_t)1 << (P.lg[j] + (int)toeplitz_level_stride_log2(P, j));
+    tw[j].resize(2 * count);
+    toeplitz_device_twiddles<F>(P, j, tw[j].data());
+    e = op->tz_tw[j].alloc(2 * count * sizeof(F));
+    if (e == hipSuccess) e = hipMemcpyAsync(op->tz_tw[j].p, tw[j].data(), 2 * count * sizeof(F), hipMemcpyHostToDevice, st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "Toeplitz operator upload: %s", hipGetErrorString(e));
+  return SLQ_OK;
+}
+static int toeplitz_create_body(slq_context *ctx, int dtype, int64_t n, const double *c, const double *r, slq_operator **out) {
+  if (!ctx || !out) return fail(SLQ_EINVAL, "ctx/out is NULL");
+  *out = nullptr;
+  SLQ_TRY(check_dtype(dtype));
+  SLQ_TRY(toeplitz_check_n("slq_toeplitz_create", n));
+  if (!c) return fail(SLQ_EINVAL, "slq_toeplitz_create: c is NULL");
+  std::vector<double> cr, rr;
+  bool sym = true;
+  char msg[160];
+  if (!toeplitz_round_values(n, (int)esize(dtype), c, r, cr, rr, &sym, msg, sizeof msg)) return fail(SLQ_EINVAL, "%s", msg);
+  slq_operator *op = nullptr;
+  SLQ_TRY(operator_new(ctx, OP_TOEPLITZ, dtype, n, 2 * n - 1, out, &op));
+  OpGuard guard{op};
+  if (!toeplitz_prepare()) return fail(SLQ_EHIP, "Toeplitz operator: the LDS limit of the product kernels could not be raised");
+  SLQ_TRY(dtype == SLQ_F64 ? toeplitz_upload_tables<double>(op) : toeplitz_upload_tables<float>(op));
+  SLQ_TRY(dtype == SLQ_F64 ? toeplitz_upload_symbol<double>(op, cr, rr) : toeplitz_upload_symbol<float>(op, cr, rr));
+  op->tz_c = std::move(cr), op->tz_r = std::move(rr), op->tz_symmetric = sym;
+  *out = guard.release();
+  return SLQ_OK;
+}
+extern "C" int slq_toeplitz_create(slq_context *ctx, int dtype, int64_t n, const double *c, const double *r, slq_operator **out) {
+  return create_guarded(out, [&]() { return toeplitz_create_body(ctx, dtype, n, c, r, out); });
+}
+extern "C" int slq_toeplitz_set_values(slq_operator *op, const double *c, const double *r, int64_t n) {
+  if (!op || !c) return fail(SLQ_EINVAL, "slq_toeplitz_set_values: op/c is NULL");
+  if (op->kind != OP_TOEPLITZ) return fail(SLQ_EINVAL, "slq_toeplitz_set_values: not a Toeplitz operator");
+  if (n != op->n) return fail(SLQ_EINVAL, "slq_toeplitz_set_values: %lld values, the operator has n = %lld", (long long)n, (long long)op->n);
+  try {
+    std::vector<double> cr, rr;
+    bool sym = true;
+    char msg[160];
+    if (!toeplitz_round_values(n, (int)esize(op->dtype), c, r, cr, rr, &sym, msg, sizeof msg)) return fail(SLQ_EINVAL, "%s", msg);
+    if (sym != op->tz_symmetric)
+      return fail(SLQ_EINVAL, "slq_toeplitz_set_values: the new values are %s, the operator is %s: a set may not change the symmetry (a live plan relies on it); create a new operator",
+                  sym ? "symmetric" : "non-symmetric", op->tz_symmetric ? "symmetric" : "non-symmetric");
+    HIP_TRY(hipSetDevice(op->ctx->device));
+    SLQ_TRY(op->dtype == SLQ_F64 ? toeplitz_upload_symbol<double>(op, cr, rr) : toeplitz_upload_symbol<float>(op, cr, rr));
+    op->tz_c = std::move(cr), op->tz_r = std::move(rr);
+  } catch (const std::bad_alloc &) {
+    return fail(SLQ_ENOMEM, "host allocation failed while computing the symbol");
+  }
+  return SLQ_OK;
+}
+extern "C" int slq_toeplitz_get_values(const slq_operator *op, double *c, double *r, int64_t n, int *symmetric) {
+  if (!op) return fail(SLQ_EINVAL, "slq_toeplitz_get_values: op is NULL");
+  if (op->kind != OP_TOEPLITZ) return fail(SLQ_EINVAL, "slq_toeplitz_get_values: not a Toeplitz operator");
+  if ((c || r) && n != op->n) return fail(SLQ_EINVAL, "slq_toeplitz_get_values: room for %lld values, the operator has n = %lld", (long long)n, (long long)op->n);
+  if (c) std::copy(op->tz_c.begin(), op->tz_c.end(), c);
+  if (r) std::copy(op->tz_r.begin(), op->tz_r.end(), r);
+  if (symmetric) *symmetric = op->tz_symmetric ? 1 : 0;
+  return SLQ_OK;
+}
+// the pass structure of a product, without a device: out[0] L, [1] levels (1: one kernel, 2: three, 3: five), [2..4] the pass lengths
+// L_1, L_2, L_3 (1 where unused), [5] LDS bytes of the largest kernel's workgroup, [6] complex columns of a workgroup, [7] workspace
+// bytes of a plan (one panel in flight), [8] launches per panel, [9] the largest n supported
+extern "C" int slq_debug_toeplitz_plan(int64_t n, int dtype, int panel_width, int64_t *out, int nout) {
+  if (!out || nout < 10) return fail(SLQ_EINVAL, "slq_debug_toeplitz_plan: room for 10 values");
+  SLQ_TRY(check_dtype(dtype));
+  SLQ_TRY(toeplitz_check_n("slq_debug_toeplitz_plan", n));
+  const int es = (int)esize(dtype);
+  if (panel_width < 128 / es || panel_width > 1024 / es || (panel_width & (panel_width - 1)))  // (8 .. 64 lanes per row of 16 bytes)
+    return fail(SLQ_EINVAL, "slq_debug_toeplitz_plan: panel_width = %d is not a panel width of the dtype", panel_width);
+  const ToeplitzPlan P = toeplitz_plan(n, es, panel_width);
+  out[0] = P.L, out[1] = P.levels;
+  for (int j = 0; j < 3; ++j) out[2 + j] = j < P.levels ? (int64_t)1 << P.lg[j] : 1;
+  out[5] = (int64_t)P.lds_bytes, out[6] = P.cg, out[7] = (int64_t)P.ws_bytes, out[8] = P.launches, out[9] = kToeplitzMaxN;
+  return SLQ_OK;
+}
+// the symbol as the device holds it, brought back to natural order and to the scale of FFT_L(e): L complex numbers of the dtype (tests)
+extern "C" int slq_debug_toeplitz_symbol(slq_operator *op, void *symbol_natural_order) {
+  if (!op || !symbol_natural_order) return fail(SLQ_EINVAL, "slq_debug_toeplitz_symbol: op/symbol is NULL");
+  if (op->kind != OP_TOEPLITZ) return fail(SLQ_EINVAL, "slq_debug_toeplitz_symbol: not a Toeplitz operator");
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  HIP_TRY(hipStreamSynchronize(op->ctx->stream));
+  const size_t es = esize(op->dtype);
+  const ToeplitzPlan P = toeplitz_plan(op->n, (int)es, 16);
+  try {
+    std::vector<char> dev((size_t)2 * P.L * es);
+    HIP_TRY(hipMemcpy(dev.data(), op->tz_sym.p, dev.size(), hipMemcpyDeviceToHost));
+    for (int64_t pos = 0; pos < P.L; ++pos) {
+      const int64_t k = toeplitz_freq_of(P, pos);
+      for (int w = 0; w < 2; ++w) {
+        if (es == 8) ((double *)symbol_natural_order)[2 * k + w] = ((const double *)dev.data())[2 * pos + w] * (double)P.L;
+        else ((float *)symbol_natural_order)[2 * k + w] = ((const float *)dev.data())[2 * pos + w] * (float)P.L;
+      }
+    }
+  } catch (const std::bad_alloc &) {
+    return fail(SLQ_ENOMEM, "host allocation failed");
+  }
+  return SLQ_OK;
+}
+
 extern "C" int slq_debug_operator_device_bytes(int64_t *live) {
   if (!live) return fail(SLQ_EINVAL, "live is NULL");
   *live = g_devbuf_bytes.load();
@@ -1714,7 +1847,7 @@ extern "C" int slq_plan_destroy(slq_plan *p) {
 static int set_kernel_attributes(slq_plan *p);
 static seq::SequenceFacts sequence_facts(const slq_plan *p);
 
-static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, PlanKind kind, slq_plan **out);
+static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, PlanKind kind, slq_plan **out, bool product_only = false);
 
 extern "C" int slq_plan_create(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth,
                                int keep_basis, slq_plan **out) {
@@ -1813,10 +1946,13 @@ static int plan_materialise(slq_plan *p) {
   return SLQ_OK;
 }
 
-static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, PlanKind kind, slq_plan **out) {
+// product_only: the two-slot plan of slq_operator_matmat, which runs no recurrence (the one plan a non-symmetric Toeplitz operator gets)
+static int plan_create_mode(slq_context *ctx, slq_operator *op, int nprobes, int deg, int orth, PlanKind kind, slq_plan **out, bool product_only) {
   if (!ctx || !op || !out) return fail(SLQ_EINVAL, "ctx/op/out is NULL");
   *out = nullptr;
   if (op->ctx != ctx) return fail(SLQ_EINVAL, "operator belongs to another context");
+  if (op->kind == OP_TOEPLITZ && !op->tz_symmetric && !product_only)
+    return fail(SLQ_EINVAL, "the Toeplitz operator is non-symmetric (r differs from c): Lanczos and Chebyshev plans need a symmetric operator; slq_operator_matmat computes its products");
   if (nprobes <= 0) return fail(SLQ_EINVAL, "nprobes must be positive");
   // a Chebyshev plan: deg steps of the orth-0 geometry, bounded by kMaxChebSteps (neither by n nor by kMaxDeg: nothing is orthogonalised or diagonalised)
   if (is_cheb(kind) && (deg < 1 || deg > kMaxChebSteps)) return fail(SLQ_EINVAL, "slq_plan_create_chebyshev: nsteps = %d must lie in [1, %d]", deg, kMaxChebSteps);
@@ -2408,12 +2544,36 @@ static int launch_kernel_product(slq_plan *p, const slq_operator *op, const void
   return SLQ_OK;
 }
 
+// Toeplitz operator: T = A W_c by FFT passes along the rows of the panel as it stands (slq_toeplitz.hip): panel after panel through the
+// plan's one complex workspace (WS_T2), one to five launches each. Every address is fixed: a captured graph replays it.
+static int launch_toeplitz_product(slq_plan *p, const slq_operator *op, const char *Wc) {
+  const ToeplitzPlan P = toeplitz_plan(p->n, (int)p->esz, p->PW);
+  if (P.ws_bytes != p->shape.ws[WS_T2].bytes) return fail(SLQ_EINVAL, "Toeplitz operator: the plan holds %zu workspace bytes, the product asks for %zu", p->shape.ws[WS_T2].bytes, P.ws_bytes);
+  const size_t panel_bytes = (size_t)p->n * p->PW * p->esz;
+  for (int pnl = 0; pnl < p->NP; ++pnl) {
+    ToeplitzLaunch a;
+    a.W = Wc + (size_t)pnl * panel_bytes;
+    a.T = (char *)p->T + (size_t)pnl * panel_bytes;
+    a.ws = p->T2;
+    a.sym = op->tz_sym.p, a.tab = op->tz_tab.p, a.tw[0] = op->tz_tw[0].p, a.tw[1] = op->tz_tw[1].p;
+    a.pw = p->PW, a.col0 = pnl * p->PW, a.nprobes = p->nprobes;
+    const int rc = toeplitz_launch(p->dtype == SLQ_F64, P, a, p->ctx->stream);
+    if (rc == kToeplitzBadGeometry) return fail(SLQ_EINVAL, "Toeplitz product: a panel of %d columns is no multiple of the %d a workgroup owns", p->PW, 2 * P.cg);
+    if (rc != 0) return fail(SLQ_EHIP, "Toeplitz product: %s", hipGetErrorString((hipError_t)rc));
+  }
+  return SLQ_OK;
+}
+
 // T = A * (slot c), unscaled, for operators without a fused kernel
 static int apply_operator_unfused(slq_plan *p, int slot_c) {
   hipStream_t st = p->ctx->stream;
   slq_operator *op = p->op;
   if (op->kind == OP_KERNEL) {
     PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_kernel_product(p, op, slot_ptr(p, slot_c))));
+    return SLQ_OK;
+  }
+  if (op->kind == OP_TOEPLITZ) {
+    PROFILED(p, SLQ_K_SPMM, SLQ_TRY(launch_toeplitz_product(p, op, slot_ptr(p, slot_c))));
     return SLQ_OK;
   }
   if (op->kind == OP_KERNEL_PRECOND) {
@@ -4304,6 +4464,7 @@ static const char *op_kind_name(int kind) {
     case OP_GRAM: return "gram";
     case OP_KERNEL: return "kernel";
     case OP_KERNEL_PRECOND: return "kernel_precond";
+    case OP_TOEPLITZ: return "toeplitz";
     default: return "?";
   }
 }
@@ -5488,7 +5649,7 @@ extern "C" int slq_operator_matmat(slq_operator *op, const void *X, int64_t ldx,
   if (ldx < op->n || ldy < op->n) return fail(SLQ_EINVAL, "leading dimension < n");
   slq_plan *p = nullptr;
   // a keep_basis plan with deg = 1 gives two slots: 0 = X, 1 = Y
-  SLQ_TRY(slq_plan_create(op->ctx, op, b, 1, 0, 1, &p));
+  SLQ_TRY(plan_create_mode(op->ctx, op, b, 1, 0, PlanKind::KeepBasis, &p, true));
   hipStream_t st = op->ctx->stream;
   int rc = slq_plan_set_probes(p, X, ldx);
   if (rc == SLQ_OK) {

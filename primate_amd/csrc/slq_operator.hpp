@@ -239,4 +239,10 @@ struct slq_operator {
   bool k_scaled = false;
   slq::DevBuf k_c, k_c_stage;
   std::vector<double> k_c_host;
+  // OP_TOEPLITZ (slq_toeplitz.hpp): the symbol in the order the forward passes leave (L complex words of the dtype, 1/L
+  // folded in), the W_1024 table and the twiddles of the outer levels - at addresses that never change after creation, so that a captured
+  // graph computes with the values of the last slq_toeplitz_set_values. tz_c, tz_r: the values as rounded (host). nnz reports 2n - 1.
+  slq::DevBuf tz_sym, tz_tab, tz_tw[2];
+  std::vector<double> tz_c, tz_r;
+  bool tz_symmetric = true;
 };

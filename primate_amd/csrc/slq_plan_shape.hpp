@@ -17,10 +17,11 @@
 #include "slq_kernelprecond.hpp"
 #include "slq_sequence.hpp"
 #include "slq_switches.hpp"
+#include "slq_toeplitz.hpp"
 
 namespace slq {
 
-enum { OP_CSR = 0, OP_DENSE = 1, OP_CALLBACK = 2, OP_DEVICE_CALLBACK = 3, OP_GRAM = 4, OP_KERNEL = 5, OP_KERNEL_PRECOND = 6 };
+enum { OP_CSR = 0, OP_DENSE = 1, OP_CALLBACK = 2, OP_DEVICE_CALLBACK = 3, OP_GRAM = 4, OP_KERNEL = 5, OP_KERNEL_PRECOND = 6, OP_TOEPLITZ = 7 };
 // (a preconditioned kernel operator - slq_kernelprecond.hpp - is a kernel operator between two applies of M = P^{-1/2})
 inline bool is_kernel_kind(int kind) { return kind == OP_KERNEL || kind == OP_KERNEL_PRECOND; }
 constexpr int kF32 = 0, kF64 = 1;  // == SLQ_F32, SLQ_F64 (include/slq.h; slq.hip asserts the equality)
@@ -126,7 +127,7 @@ enum WorkspaceId {
   WS_QUAD,        // quad[bpad] | nodes[hist][bpad] | weights[hist][bpad]
   WS_CHEB_MU, WS_CHEB_OUT, WS_CHEB_COEF,
   WS_T,           // product panel of dense / callback / Gram operators, the K-split slabs of the big-tile dense kernels behind it
-  WS_T2,          // Gram: the m-row intermediate
+  WS_T2,          // Gram: the m-row intermediate; preconditioned kernel operator: V and scratch; Toeplitz: the complex workspace of the multi-kernel product
   kNumRegions
 };
 struct Region {
@@ -442,6 +443,8 @@ inline PlanShape plan_shape(const PlanFacts &f, const PlanSwitches &sw) {
   // (preconditioned kernel operator: V = M W_c, then the slab partials and G L^T W of an apply - scratch of the PLAN, whose captured graphs hold its addresses)
   region(WS_T2, f.kind == OP_GRAM             ? (size_t)s.NP * (size_t)f.mrows * s.PW * esz
                 : f.kind == OP_KERNEL_PRECOND ? slot_bytes + precond_scratch_words(f.n, s.bpad, (int)f.mrows, f.num_cus) * 8
+                // (Toeplitz operator, DESIGN.md §4.24: L x PW words, ONE panel in flight - the panels of a product run one after the other)
+                : f.kind == OP_TOEPLITZ       ? toeplitz_plan(f.n, (int)esz, s.PW).ws_bytes
                                               : 0, 0, 1);
   return s;
 }

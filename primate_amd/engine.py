@@ -212,6 +212,17 @@ class DeviceOperator:
 			self.kind, self.nnz = "kernel_precond", int(self.shape[0] * min(int(A.rank_max), self.shape[0]))
 			self._host_params = A.base
 			self._fresh_for = self._param_key()
+		elif getattr(A, "_slq_kind", None) == "toeplitz":
+			## Toeplitz operator (primate_amd.operators.ToeplitzOperator): slq_toeplitz_create; the values follow A.set_values
+			if self.dtype != np.dtype(A.dtype):
+				raise ValueError(f"the ToeplitzOperator is {A.dtype}: its device operator cannot be {self.dtype} (the operator is defined on values rounded to its dtype)")
+			c64, r64 = (np.ascontiguousarray(v, dtype=np.float64) for v in (A.c, A.r))
+			check(L.slq_toeplitz_create(self.ctx._h, dt, c64.size, ptr(c64), ptr(r64), C.byref(h)))
+			self.kind, self.nnz = "toeplitz", int(2 * c64.size - 1)
+			A._device_ops = getattr(A, "_device_ops", [])
+			import weakref
+
+			A._device_ops.append(weakref.ref(self))
 		elif hasattr(A, "matmat_device"):
 			## GPU-resident plugin: A.matmat_device(X, Y, stream) receives two objects with
 			## `__cuda_array_interface__` (shape (ncols, n), C order = column-major n x ncols) and a stream handle
@@ -262,6 +273,20 @@ class DeviceOperator:
 		context stream; live plans, and the graphs they captured, see the new values from their next run."""
 		ls = np.ascontiguousarray(np.atleast_1d(lengthscale), dtype=np.float64)
 		check(_capi.lib().slq_kernel_set_parameters(self._h, ptr(ls), ls.size, float(outputscale), float(noise)))
+
+	def set_toeplitz_values(self, c, r=None) -> None:
+		"""c and r of a Toeplitz operator (slq_toeplitz_set_values): the symbol is rewritten in place; live plans, and the graphs they
+		captured, compute with the new values from their next run. A change of symmetry is refused."""
+		c64 = np.ascontiguousarray(c, dtype=np.float64)
+		r64 = None if r is None else np.ascontiguousarray(r, dtype=np.float64)
+		check(_capi.lib().slq_toeplitz_set_values(self._h, ptr(c64), ptr(r64), c64.size))
+
+	def toeplitz_values(self) -> dict:
+		"""The rounded c and r of a Toeplitz operator and whether it is symmetric (slq_toeplitz_get_values)."""
+		n = self.shape[0]
+		c, r, sym = np.empty(n), np.empty(n), C.c_int(0)
+		check(_capi.lib().slq_toeplitz_get_values(self._h, ptr(c), ptr(r), n, C.byref(sym)))
+		return {"c": c, "r": r, "symmetric": bool(sym.value)}
 
 	def set_kernel_diag_scale(self, c) -> None:
 		"""The diagonal scale of a kernel operator (slq_kernel_set_diag_scale): A = s diag(c) phi(r2) diag(c) + noise I,

@@ -889,6 +889,103 @@ class Toeplitz(LinearOperator):
 		return np.real(y[:n]).astype(self.dtype)
 
 
+class ToeplitzOperator(Toeplitz):
+	"""The Toeplitz matrix A_ij = c[i-j] (i >= j), r[j-i] (j > i) as a DEVICE operator (`slq_toeplitz_create`): a
+	product is three FFT passes of length L = 2^ceil(log2 2n) along the rows of the probe panel as it stands in memory - two probes per
+	complex column, O(n log n) per probe, n up to 2^22. `c` and `r` (default r = c; r[0] is ignored, as in SciPy) are rounded once to
+	`dtype`: the operator is defined on the rounded values (`self.c`, `self.r`), and is `symmetric` iff the rounded r[1:] equals c[1:].
+	A stationary kernel on a regular 1-D grid is such a matrix: `ToeplitzOperator.from_kernel("rbf", n, spacing, ...)`.
+
+	`lanczos`, `MatrixFunction`, `ChebyshevFunction`, `hutch`, `xtrace` and `spectral_density` take a symmetric one like any other
+	operator; a non-symmetric one has products (`engine.DeviceOperator(T).matmat`) and no plans. `set_values(c, r)` rewrites the values,
+	also on operators already wrapped in a `MatrixFunction` - live plans compute with them from their next run; it may not change the
+	symmetry. The host `_matvec` / `_matmat` (NumPy FFTs in double on the rounded values) are the plugin surface inherited from `Toeplitz`,
+	which itself stays the host plugin it was."""
+
+	_slq_kind = "toeplitz"
+	MAX_N = 1 << 22
+
+	def __init__(self, c, r=None, dtype=np.float64):
+		self.dtype = np.dtype(dtype)
+		if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+			raise ValueError("Only 32- or 64-bit floats are supported.")
+		self._set(*self._check_values(c, r, None))
+
+	def _check_values(self, c, r, n):
+		c = np.asarray(c, dtype=np.float64)
+		if c.ndim != 1:
+			raise ValueError(f"Toeplitz operator: c must be a vector, got shape {c.shape}")
+		if n is not None and c.size != n:
+			raise ValueError(f"Toeplitz operator: c has {c.size} entries, the operator n = {n}")
+		if c.size < 1:
+			raise ValueError("Toeplitz operator: n = 0 must be at least 1")
+		if c.size > self.MAX_N:
+			raise ValueError(f"Toeplitz operator: n = {c.size} exceeds the supported maximum {self.MAX_N}")
+		r = c if r is None else np.asarray(r, dtype=np.float64)
+		if r.shape != c.shape:
+			raise ValueError(f"Toeplitz operator: r has shape {r.shape}, c has {c.size} entries")
+		with np.errstate(over="ignore"):
+			cr, rr = c.astype(self.dtype), r.astype(self.dtype)
+		rr[0] = cr[0]  # (r[0] is ignored)
+		for name, given, rounded in (("c", c, cr), ("r", r, rr)):
+			bad = np.flatnonzero(~np.isfinite(rounded))
+			if bad.size:
+				raise ValueError(f"Toeplitz operator: {name}[{int(bad[0])}] = {given[bad[0]]} is not finite in the operator's dtype")
+		return cr, rr
+
+	def _set(self, cr, rr):
+		n = cr.size
+		self.c, self.r = cr, rr
+		self.symmetric = bool(cr[1:].tobytes() == rr[1:].tobytes())
+		self.shape = (n, n)
+		self._symbol = np.fft.fft(np.concatenate((cr.astype(np.float64), [0.0], rr[:0:-1].astype(np.float64))))
+		self._pad = np.zeros(2 * n)
+
+	def set_values(self, c, r=None) -> None:
+		"""New c and r of the same n (and the same symmetry), forwarded to every live device operator built from this object."""
+		cr, rr = self._check_values(c, r, self.shape[0])
+		if bool(cr[1:].tobytes() == rr[1:].tobytes()) != self.symmetric:
+			raise ValueError("Toeplitz operator: set_values may not change the symmetry of the operator (create a new one)")
+		## the live device operators first, the host state after: a refused or failed device call leaves the host object as it was, and
+		## the device operators already changed are put back
+		live = [op for op in (ref() for ref in getattr(self, "_device_ops", [])) if op is not None and getattr(op, "_h", None)]
+		done = []
+		try:
+			for op in live:
+				op.set_toeplitz_values(cr, rr)
+				done.append(op)
+		except Exception:
+			for op in done:
+				op.set_toeplitz_values(self.c, self.r)
+			raise
+		self._set(cr, rr)
+
+	def _matmat(self, X: np.ndarray) -> np.ndarray:
+		n = self.shape[0]
+		X = np.asarray(X, dtype=np.float64).reshape(n, -1)
+		F = np.fft.fft(np.concatenate((X, np.zeros((self._symbol.size - n, X.shape[1]))), axis=0), axis=0)
+		return np.real(np.fft.ifft(self._symbol[:, None] * F, axis=0)[:n]).astype(self.dtype)
+
+	def _adjoint(self):
+		return ToeplitzOperator(self.r, self.c, dtype=self.dtype)
+
+	@classmethod
+	def from_kernel(cls, kernel: str, n: int, spacing: float, lengthscale: float = 1.0, outputscale: float = 1.0, noise: float = 0.0, dtype=np.float64):
+		"""The kernel matrix of `KernelOperator`'s profiles on the grid spacing * arange(n): first column
+		outputscale * phi((k spacing / lengthscale)^2) + noise [k = 0]."""
+		if not isinstance(kernel, str) or kernel not in KERNEL_PROFILES:
+			raise ValueError(f"Toeplitz operator: unknown profile {kernel!r} (one of {', '.join(KERNEL_PROFILES)})")
+		for name, v, ok in (("spacing", spacing, spacing > 0), ("lengthscale", lengthscale, lengthscale > 0), ("outputscale", outputscale, outputscale > 0), ("noise", noise, noise >= 0)):
+			if not (np.isfinite(v) and ok):
+				raise ValueError(f"Toeplitz operator: {name} = {v} is out of range")
+		if int(n) < 1:
+			raise ValueError(f"Toeplitz operator: n = {n} must be at least 1")
+		k = np.arange(int(n), dtype=np.float64)
+		c = float(outputscale) * _kernel_profile(kernel, (k * float(spacing) / float(lengthscale)) ** 2)
+		c[0] += float(noise)
+		return cls(c, dtype=dtype)
+
+
 class TorchOperator(LinearOperator):
 	"""A symmetric operator given as a function on GPU-resident torch tensors, `fn(X) -> A X` for X of shape
 	(n, b) on this process's GPU. Used as `A` in `lanczos` / `MatrixFunction` / `hutch`, its products run inside
