@@ -111,6 +111,26 @@ static void ctx_free(slq_context *ctx) {
 static void ctx_release(slq_context *ctx) {
   if (--ctx->refs == 0 && ctx->dead) ctx_free(ctx);
 }
+// The end of every side object (accumulators, cross objects, feature maps, device matrices): a struct that holds `slq_context *ctx`
+// and owns its device arrays as DevBuf members. Work queued on the stream may still read those arrays, so the stream is waited for
+// before they go. (slq_diag and slq_density did not wait explicitly before their arrays became DevBufs: their hipFree waited for the
+// device, so nothing observable has changed.)
+template <typename H> static int handle_destroy(H *h) {
+  if (!h) return SLQ_OK;
+  hipSetDevice(h->ctx->device);
+  hipStreamSynchronize(h->ctx->stream);
+  slq_context *ctx = h->ctx;
+  delete h;
+  ctx_release(ctx);
+  return SLQ_OK;
+}
+// b holds at least `need` bytes: the one way a scratch, staging or column buffer grows (what it held is gone; it never shrinks)
+static int devbuf_grow(DevBuf &b, size_t need, const char *who, const char *what = "scratch") {
+  if (b.bytes() >= need) return SLQ_OK;
+  const hipError_t e = b.alloc(need);
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "%s: %s of %zu bytes: %s", who, what, need, hipGetErrorString(e));
+  return SLQ_OK;
+}
 
 // (OP_CSR .. OP_KERNEL, the kinds of an operator: slq_plan_shape.hpp)
 static_assert(kF32 == SLQ_F32 && kF64 == SLQ_F64, "slq_plan_shape.hpp: the dtype codes of include/slq.h");
@@ -1218,6 +1238,22 @@ static void kernel_schedule_words(std::initializer_list<int64_t> head, int nslab
   out = std::copy(head.begin(), head.end(), out);
   for (int z = 0; z <= max_slabs; ++z) out[z] = z <= nslabs ? slab_begin[z] : -1;
 }
+// What the slq_debug_kernel*_schedule entries that write a KernelSchedule share: room for the words, the entry's own bounds on its
+// arguments (args_ok; `bounds` says them), then the head - rows per block, row blocks, 16-column tiles per workgroup, column chunks,
+// slabs and, of the products with a summed side of their own (head = 6), tiles per slab - and slab_begin. No HIP call.
+static bool kernel_extents_ok(std::initializer_list<int64_t> extents, int num_cus) {
+  return num_cus > 0 && std::all_of(extents.begin(), extents.end(), [](int64_t e) { return e > 0 && e < ((int64_t)1 << 31) - 16; });
+}
+template <typename Make>
+static int kernel_schedule_debug(const char *who, bool args_ok, const char *bounds, int head, int max_slabs, int64_t *out, int nout, Make make) {
+  if (!out || nout < head + max_slabs + 1) return fail(SLQ_EINVAL, "%s: room for %d values", who, head + max_slabs + 1);
+  if (!args_ok) return fail(SLQ_EINVAL, "%s: %s", who, bounds);
+  const KernelSchedule S = make();
+  const int64_t words[6] = {S.rows_per_block, S.nrow_blocks, S.col_blocks, S.ncol_chunks, S.nslabs, S.tiles_per_slab};
+  std::copy(words, words + head, out);
+  kernel_schedule_words({}, S.nslabs, S.slab_begin, max_slabs, out + head);
+  return SLQ_OK;
+}
 static int kernel_bad(const KernelBad &b) {
   char msg[256];
   kernel_bad_message(b, msg, sizeof msg);
@@ -1362,12 +1398,9 @@ extern "C" int slq_debug_kernel_diag_scale(slq_operator *op, void *c_dev_words) 
 // kernel_schedule() of slq_kernelop.hpp as an array: rows per block, row blocks, 16-column tiles per workgroup, column chunks, slabs,
 // then slab_begin[0 .. slabs]. No HIP call.
 extern "C" int slq_debug_kernel_schedule(int64_t n, int panel_width, int panels, int num_cus, int64_t *out, int nout) {
-  if (!out || nout < 5 + kKernelMaxSlabs + 1) return fail(SLQ_EINVAL, "slq_debug_kernel_schedule: room for %d values", 5 + kKernelMaxSlabs + 1);
-  if (n <= 0 || panel_width < 16 || (panel_width & (panel_width - 1)) || panels <= 0 || num_cus <= 0)
-    return fail(SLQ_EINVAL, "slq_debug_kernel_schedule: n, panels, num_cus positive, panel_width a power of two >= 16");
-  const KernelSchedule S = kernel_schedule(n, panel_width, panels, num_cus);
-  kernel_schedule_words({S.rows_per_block, S.nrow_blocks, S.col_blocks, S.ncol_chunks, S.nslabs}, S.nslabs, S.slab_begin, kKernelMaxSlabs, out);
-  return SLQ_OK;
+  const bool ok = n > 0 && panel_width >= 16 && !(panel_width & (panel_width - 1)) && panels > 0 && num_cus > 0;
+  return kernel_schedule_debug("slq_debug_kernel_schedule", ok, "n, panels, num_cus positive, panel_width a power of two >= 16", 5, kKernelMaxSlabs, out, nout,
+                               [&]() { return kernel_schedule(n, panel_width, panels, num_cus); });
 }
 
 extern "C" int slq_operator_destroy(slq_operator *op) {
@@ -3839,33 +3872,26 @@ extern "C" int slq_plan_fun_action(slq_plan *p, int fun_id, const double *fun_pa
 struct slq_diag {
   slq_context *ctx;
   int64_t n, count;
-  double *buf;  // numer | denom | msum, n doubles each (in the operator's stored row order)
+  DevBuf buf;  // numer | denom | msum, n doubles each (in the operator's stored row order)
   const slq_operator *op;
+  double *acc(int k) const { return buf.as<double>() + k * n; }
 };
 
 extern "C" int slq_diag_create(slq_context *ctx, int64_t n, slq_diag **out) {
   if (!ctx || !out || n <= 0) return fail(SLQ_EINVAL, "bad arguments");
   *out = nullptr;
   HIP_TRY(hipSetDevice(ctx->device));
-  slq_diag *d = new (std::nothrow) slq_diag();
+  std::unique_ptr<slq_diag> d(new (std::nothrow) slq_diag{ctx, n, 0, {}, nullptr});
   if (!d) return fail(SLQ_ENOMEM, "host allocation failed");
-  d->ctx = ctx; d->n = n; d->count = 0; d->buf = nullptr; d->op = nullptr;
-  hipError_t e = hipMalloc((void **)&d->buf, (size_t)3 * n * 8);
-  if (e == hipSuccess) e = hipMemsetAsync(d->buf, 0, (size_t)3 * n * 8, ctx->stream);
-  if (e != hipSuccess) { delete d; /* not yet retained */ return fail(SLQ_ENOMEM, "diag accumulators: %s", hipGetErrorString(e)); }
+  hipError_t e = d->buf.alloc((size_t)3 * n * 8);
+  if (e == hipSuccess) e = hipMemsetAsync(d->buf.p, 0, (size_t)3 * n * 8, ctx->stream);
+  if (e != hipSuccess) return fail(SLQ_ENOMEM, "diag accumulators: %s", hipGetErrorString(e));
   ctx_retain(ctx);
-  *out = d;
+  *out = d.release();
   return SLQ_OK;
 }
 
-extern "C" int slq_diag_destroy(slq_diag *d) {
-  if (!d) return SLQ_OK;
-  hipSetDevice(d->ctx->device);
-  if (d->buf) hipFree(d->buf);
-  ctx_release(d->ctx);
-  delete d;
-  return SLQ_OK;
-}
+extern "C" int slq_diag_destroy(slq_diag *d) { return handle_destroy(d); }
 
 extern "C" int slq_diag_update(slq_diag *d, slq_plan *p, int fun_id, const double *fun_params) {
   if (!d || !p) return fail(SLQ_EINVAL, "diag/plan is NULL");
@@ -3880,10 +3906,10 @@ extern "C" int slq_diag_update(slq_diag *d, slq_plan *p, int fun_id, const doubl
   const dim3 g((p->n + 63) / 64);
   if (p->dtype == SLQ_F64)
     k_diag_accumulate<double><<<g, dim3(64), 0, st>>>(p->n, (const double *)slot_ptr(p, p->v_slot), (const double *)slot_ptr(p, p->y_slot),
-                                                      p->PW, p->nprobes, p->st.coefB, d->buf, d->buf + d->n, d->buf + 2 * d->n);
+                                                      p->PW, p->nprobes, p->st.coefB, d->acc(0), d->acc(1), d->acc(2));
   else
     k_diag_accumulate<float><<<g, dim3(64), 0, st>>>(p->n, (const float *)slot_ptr(p, p->v_slot), (const float *)slot_ptr(p, p->y_slot),
-                                                     p->PW, p->nprobes, p->st.coefB, d->buf, d->buf + d->n, d->buf + 2 * d->n);
+                                                     p->PW, p->nprobes, p->st.coefB, d->acc(0), d->acc(1), d->acc(2));
   HIP_TRY(hipGetLastError());
   d->count += p->nprobes;
   return SLQ_OK;
@@ -3893,9 +3919,9 @@ extern "C" int slq_diag_get(slq_diag *d, double *numer, double *denom, double *r
   if (!d) return fail(SLQ_EINVAL, "diag is NULL");
   HIP_TRY(hipSetDevice(d->ctx->device));
   hipStream_t st = d->ctx->stream;
-  if (numer) HIP_TRY(hipMemcpyAsync(numer, d->buf, (size_t)d->n * 8, hipMemcpyDeviceToHost, st));
-  if (denom) HIP_TRY(hipMemcpyAsync(denom, d->buf + d->n, (size_t)d->n * 8, hipMemcpyDeviceToHost, st));
-  if (running_mean) HIP_TRY(hipMemcpyAsync(running_mean, d->buf + 2 * d->n, (size_t)d->n * 8, hipMemcpyDeviceToHost, st));
+  if (numer) HIP_TRY(hipMemcpyAsync(numer, d->acc(0), (size_t)d->n * 8, hipMemcpyDeviceToHost, st));
+  if (denom) HIP_TRY(hipMemcpyAsync(denom, d->acc(1), (size_t)d->n * 8, hipMemcpyDeviceToHost, st));
+  if (running_mean) HIP_TRY(hipMemcpyAsync(running_mean, d->acc(2), (size_t)d->n * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (running_mean && d->count > 0)
     for (int64_t i = 0; i < d->n; ++i) running_mean[i] /= (double)d->count;
@@ -3919,11 +3945,10 @@ struct slq_density {
   int kind, G;
   double c0, c1;     // the kernel's constants (k_density_eval)
   int64_t count;     // probes folded so far
-  double *grid;      // G points or G + 1 edges
-  double *stat;      // mean | M2, G + 2 doubles each (columns G, G + 1: node mass below / above the grid)
-  int *flags;        // [0] QL non-convergence, [1] ring bail-out word of a plan
-  double *phi;       // P x (G + 2) scratch of the per-probe values
-  int64_t phi_cap;   // probes the scratch holds
+  DevBuf grid;       // G points or G + 1 edges
+  DevBuf stat;       // mean | M2, G + 2 doubles each (columns G, G + 1: node mass below / above the grid), then the two flag words
+  int *flags;        // [0] QL non-convergence, [1] ring bail-out word of a plan (behind stat's doubles)
+  DevBuf phi;        // P x (G + 2) scratch of the per-probe values (density_scratch)
   std::vector<double> grid_h;  // SLQ_DENSITY_CHEBYSHEV: the grid on the host (checked against the bounds of every run folded in)
 };
 
@@ -3940,59 +3965,36 @@ extern "C" int slq_density_create(slq_context *ctx, int kind, int ngrid, const d
   const bool smooth = kind == SLQ_DENSITY_GAUSSIAN || kind == SLQ_DENSITY_LORENTZIAN;
   if (smooth && !(bw > 0.0 && std::isfinite(bw))) return fail(SLQ_EINVAL, "slq_density_create: bandwidth %g must be > 0", bw);
   HIP_TRY(hipSetDevice(ctx->device));
-  slq_density *d = new (std::nothrow) slq_density();
+  std::unique_ptr<slq_density> d(new (std::nothrow) slq_density());
   if (!d) return fail(SLQ_ENOMEM, "host allocation failed");
   d->ctx = ctx; d->kind = kind; d->G = ngrid; d->count = 0;
   d->c0 = d->c1 = 0.0;
   if (kind == SLQ_DENSITY_GAUSSIAN) { d->c0 = 1.0 / (2.0 * bw * bw); d->c1 = 1.0 / (bw * std::sqrt(2.0 * M_PI)); }
   if (kind == SLQ_DENSITY_LORENTZIAN) { d->c0 = bw * bw; d->c1 = bw / M_PI; }
-  d->grid = d->stat = d->phi = nullptr; d->flags = nullptr; d->phi_cap = 0;
+  d->flags = nullptr;
   if (kind == SLQ_DENSITY_CHEBYSHEV) d->grid_h.assign(grid, grid + ngrid);
   const size_t G2 = (size_t)ngrid + 2;
-  hipError_t e = hipMalloc((void **)&d->grid, (size_t)npts * 8);
-  if (e == hipSuccess) e = hipMalloc((void **)&d->stat, 2 * G2 * 8 + 2 * sizeof(int));
+  hipError_t e = d->grid.alloc((size_t)npts * 8);
+  if (e == hipSuccess) e = d->stat.alloc(2 * G2 * 8 + 2 * sizeof(int));
   if (e == hipSuccess) {
-    d->flags = (int *)(d->stat + 2 * G2);
-    e = hipMemcpyAsync(d->grid, grid, (size_t)npts * 8, hipMemcpyHostToDevice, ctx->stream);
+    d->flags = (int *)(d->stat.as<double>() + 2 * G2);
+    e = hipMemcpyAsync(d->grid.p, grid, (size_t)npts * 8, hipMemcpyHostToDevice, ctx->stream);
   }
-  if (e == hipSuccess) e = hipMemsetAsync(d->stat, 0, 2 * G2 * 8 + 2 * sizeof(int), ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d->stat.p, 0, 2 * G2 * 8 + 2 * sizeof(int), ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (the host grid may go away when this returns)
-  if (e != hipSuccess) {
-    if (d->grid) hipFree(d->grid);
-    if (d->stat) hipFree(d->stat);
-    delete d;  // (not yet retained)
-    return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "density accumulators: %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "density accumulators: %s", hipGetErrorString(e));
   ctx_retain(ctx);
-  *out = d;
+  *out = d.release();
   return SLQ_OK;
 }
 
-extern "C" int slq_density_destroy(slq_density *d) {
-  if (!d) return SLQ_OK;
-  hipSetDevice(d->ctx->device);
-  if (d->grid) hipFree(d->grid);
-  if (d->stat) hipFree(d->stat);
-  if (d->phi) hipFree(d->phi);
-  ctx_release(d->ctx);
-  delete d;
-  return SLQ_OK;
-}
+extern "C" int slq_density_destroy(slq_density *d) { return handle_destroy(d); }
 
 // the P x (G + 2) scratch of an update
 static int density_scratch(slq_density *d, int P, hipStream_t st) {
-  const int G2 = d->G + 2;
-  if (d->phi_cap >= P) return SLQ_OK;
-  if (d->phi) {
-    HIP_TRY(hipStreamSynchronize(st));  // (the old scratch may still be read by the previous update)
-    hipFree(d->phi);
-    d->phi = nullptr;
-    d->phi_cap = 0;
-  }
-  hipError_t e = hipMalloc((void **)&d->phi, (size_t)P * G2 * 8);
-  if (e != hipSuccess) return fail(SLQ_ENOMEM, "density scratch (%zu bytes): %s", (size_t)P * G2 * 8, hipGetErrorString(e));
-  d->phi_cap = P;
-  return SLQ_OK;
+  const size_t need = (size_t)P * (size_t)(d->G + 2) * 8;
+  if (d->phi && d->phi.bytes() < need) HIP_TRY(hipStreamSynchronize(st));  // (the old scratch may still be read by the previous update)
+  return devbuf_grow(d->phi, need, "density scratch");
 }
 
 // The density of the kernel polynomial method from the moments of a plan's last Chebyshev run (k_cheb_density_eval), folded by
@@ -4020,10 +4022,10 @@ extern "C" int slq_density_update_moments(slq_density *d, slq_plan *p, int nweig
   const int nbg = (G2 + kDensEvalThreads - 1) / kDensEvalThreads;
   PROFILED(p, SLQ_K_QUADRATURE,
            hipLaunchKernelGGL(k_cheb_density_eval, dim3((unsigned)((int64_t)P * nbg)), dim3(kDensEvalThreads), 0, st, d->G, nweights, p->bpad,
-                              (const double *)p->cheb_mu, damp ? (const double *)p->cheb_coef : (const double *)nullptr, (const double *)d->grid,
-                              p->cheb_c, p->cheb_h, nbg, d->phi));
+                              (const double *)p->cheb_mu, damp ? (const double *)p->cheb_coef : (const double *)nullptr, d->grid.as<const double>(),
+                              p->cheb_c, p->cheb_h, nbg, d->phi.as<double>()));
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_density_fold, dim3((G2 + 63) / 64), dim3(64 * kDensFoldWaves), 0, st, P, G2, d->count, d->phi, d->stat, d->stat + G2,
+  hipLaunchKernelGGL(k_density_fold, dim3((G2 + 63) / 64), dim3(64 * kDensFoldWaves), 0, st, P, G2, d->count, d->phi.as<double>(), d->stat.as<double>(), d->stat.as<double>() + G2,
                      (const int *)nullptr, 0, (const int *)p->ring_fail_d, d->flags);
   HIP_TRY(hipGetLastError());
   d->count += P;
@@ -4055,10 +4057,10 @@ extern "C" int slq_density_update(slq_density *d, slq_plan *p) {
   }
   const int nbg = (G2 + kDensEvalThreads - 1) / kDensEvalThreads;
   hipLaunchKernelGGL(k_density_eval, dim3((unsigned)((int64_t)P * nbg)), dim3(kDensEvalThreads), 0, st, d->kind, d->G, deg, p->nodes_d,
-                     p->weights_d, p->st.vnorm2, d->grid, d->c0, d->c1, nbg, d->phi);
+                     p->weights_d, p->st.vnorm2, d->grid.as<double>(), d->c0, d->c1, nbg, d->phi.as<double>());
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_density_fold, dim3((G2 + 63) / 64), dim3(64 * kDensFoldWaves), 0, st, P, G2, d->count, d->phi, d->stat,
-                     d->stat + G2, (p->rule_src == 2 ? (const int *)rule_fail : nullptr), (p->rule_src == 1 ? p->rule_fail_h : 0),
+  hipLaunchKernelGGL(k_density_fold, dim3((G2 + 63) / 64), dim3(64 * kDensFoldWaves), 0, st, P, G2, d->count, d->phi.as<double>(), d->stat.as<double>(),
+                     d->stat.as<double>() + G2, (p->rule_src == 2 ? (const int *)rule_fail : nullptr), (p->rule_src == 1 ? p->rule_fail_h : 0),
                      (const int *)p->ring_fail_d, d->flags);
   HIP_TRY(hipGetLastError());
   d->count += P;
@@ -4072,7 +4074,7 @@ extern "C" int slq_density_get(slq_density *d, double *mean, double *m2, double 
   const size_t G = (size_t)d->G, G2 = G + 2;
   std::vector<double> h(2 * G2);
   int flags[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(h.data(), d->stat, 2 * G2 * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h.data(), d->stat.p, 2 * G2 * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(flags, d->flags, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (mean) memcpy(mean, h.data(), G * 8);
@@ -4092,37 +4094,62 @@ struct slq_dmat {
   slq_context *ctx;
   int64_t n;
   int cols;
-  double *d;  // column-major, ld = n
+  double *d;    // column-major, ld = n: what every call site reads
+  DevBuf own;   // the allocation behind d (slq_dmat_create); empty in a view of somebody else's columns (precond_trace_columns)
 };
 
 extern "C" int slq_dmat_create(slq_context *ctx, int64_t n, int cols, slq_dmat **out) {
   if (!ctx || !out || n <= 0 || cols <= 0) return fail(SLQ_EINVAL, "bad arguments");
   *out = nullptr;
   HIP_TRY(hipSetDevice(ctx->device));
-  slq_dmat *m = new (std::nothrow) slq_dmat();
+  std::unique_ptr<slq_dmat> m(new (std::nothrow) slq_dmat{ctx, n, cols, nullptr, {}});
   if (!m) return fail(SLQ_ENOMEM, "host allocation failed");
-  m->ctx = ctx; m->n = n; m->cols = cols; m->d = nullptr;
-  hipError_t e = hipMalloc((void **)&m->d, (size_t)n * cols * 8);
+  hipError_t e = m->own.alloc((size_t)n * cols * 8);
+  m->d = m->own.as<double>();
   if (e == hipSuccess) e = hipMemsetAsync(m->d, 0, (size_t)n * cols * 8, ctx->stream);
-  if (e != hipSuccess) { delete m; return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "dmat: %s", hipGetErrorString(e)); }
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "dmat: %s", hipGetErrorString(e));
   ctx_retain(ctx);
-  *out = m;
+  *out = m.release();
   return SLQ_OK;
 }
 
-extern "C" int slq_dmat_destroy(slq_dmat *m) {
-  if (!m) return SLQ_OK;
-  hipSetDevice(m->ctx->device);
-  hipStreamSynchronize(m->ctx->stream);
-  if (m->d) hipFree(m->d);
-  ctx_release(m->ctx);
-  delete m;
-  return SLQ_OK;
-}
+extern "C" int slq_dmat_destroy(slq_dmat *m) { return handle_destroy(m); }
 
 static int dmat_range(const slq_dmat *m, int c0, int nc, const char *what) {
   if (!m) return fail(SLQ_EINVAL, "%s: matrix is NULL", what);
   if (c0 < 0 || nc <= 0 || c0 + nc > m->cols) return fail(SLQ_EINVAL, "%s: columns [%d, %d) outside [0, %d)", what, c0, c0 + nc, m->cols);
+  return SLQ_OK;
+}
+// The operands of a product OUT[:, o0 : o0 + b] = (rout x rin operator) IN[:, i0 : i0 + b] on device matrices of the context ctx:
+// the column ranges, the row counts, the context, no overlap inside one matrix; then the addresses of the first columns. The caller
+// has checked b >= 1.
+static int dmat_operands(slq_dmat *IN, int i0, slq_dmat *OUT, int o0, int b, int64_t rin, int64_t rout, const slq_context *ctx, const char *who, const double **in,
+                         double **out) {
+  char what[96];
+  snprintf(what, sizeof what, "%s(IN)", who);
+  SLQ_TRY(dmat_range(IN, i0, b, what));
+  snprintf(what, sizeof what, "%s(OUT)", who);
+  SLQ_TRY(dmat_range(OUT, o0, b, what));
+  if (IN->n != rin) return fail(SLQ_EINVAL, "%s: IN has %lld rows, the product reads %lld", who, (long long)IN->n, (long long)rin);
+  if (OUT->n != rout) return fail(SLQ_EINVAL, "%s: OUT has %lld rows, the product writes %lld", who, (long long)OUT->n, (long long)rout);
+  if (IN->ctx != ctx || OUT->ctx != ctx) return fail(SLQ_EINVAL, "%s: a matrix belongs to another context", who);
+  if (IN == OUT && i0 < o0 + b && o0 < i0 + b) return fail(SLQ_EINVAL, "%s: the columns [%d, %d) of IN and [%d, %d) of OUT overlap in one matrix", who, i0, i0 + b, o0, o0 + b);
+  *in = IN->d + (size_t)i0 * IN->n, *out = OUT->d + (size_t)o0 * OUT->n;
+  return SLQ_OK;
+}
+// Y = (operator) X for host panels (X rin x b, ldx apart; Y rout x b, ldy apart; elements of es bytes) through the two staging
+// buffers of the object: both grown on demand, a pitched copy in, run(in, ld_in, out, ld_out) enqueues the device product on the
+// context's stream, a pitched copy out, and the one synchronisation. The caller has checked X, Y, b and the leading dimensions.
+template <typename Run>
+static int staged_panel_product(slq_context *ctx, size_t es, DevBuf &stage_in, DevBuf &stage_out, const void *X, int64_t ldx, int64_t rin, void *Y, int64_t ldy,
+                                int64_t rout, int b, const char *who, Run run) {
+  HIP_TRY(hipSetDevice(ctx->device));
+  SLQ_TRY(devbuf_grow(stage_in, (size_t)rin * b * es, who, "staging buffer"));
+  SLQ_TRY(devbuf_grow(stage_out, (size_t)rout * b * es, who, "staging buffer"));
+  HIP_TRY(hipMemcpy2DAsync(stage_in.p, (size_t)rin * es, X, (size_t)ldx * es, (size_t)rin * es, (size_t)b, hipMemcpyHostToDevice, ctx->stream));
+  SLQ_TRY(run(stage_in.p, rin, stage_out.p, rout));
+  HIP_TRY(hipMemcpy2DAsync(Y, (size_t)ldy * es, stage_out.p, (size_t)rout * es, (size_t)rout * es, (size_t)b, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
   return SLQ_OK;
 }
 
@@ -4296,9 +4323,9 @@ extern "C" int slq_plan_get_probes_dmat(slq_plan *p, slq_dmat *OUT, int o0) {
 struct slq_sddmm {
   slq_context *ctx;
   int64_t n, nnz, count, nitems, grid;
-  int32_t *rowptr, *colind;  // the caller's pattern as validated on the host (never the caller's own device arrays)
-  SddmmItem *items;
-  double *vals;
+  DevBuf rowptr, colind;  // int32: the caller's pattern as validated on the host (never the caller's own device arrays)
+  DevBuf items;           // SddmmItem
+  DevBuf vals;            // nnz doubles
 };
 
 static int sddmm_create_body(slq_context *ctx, int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colind, slq_sddmm **out, const char *what) {
@@ -4309,27 +4336,21 @@ static int sddmm_create_body(slq_context *ctx, int64_t n, int64_t nnz, const int
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->dead) return fail(SLQ_EINVAL, "%s: the context has been destroyed", what);
   const SddmmSchedule S = sddmm_schedule(n, rowptr);
-  slq_sddmm *s = new (std::nothrow) slq_sddmm();
+  std::unique_ptr<slq_sddmm> s(new (std::nothrow) slq_sddmm{ctx, n, nnz, 0, (int64_t)S.items.size(), S.grid, {}, {}, {}, {}});
   if (!s) return fail(SLQ_ENOMEM, "host allocation failed");
-  *s = slq_sddmm{ctx, n, nnz, 0, (int64_t)S.items.size(), S.grid, nullptr, nullptr, nullptr, nullptr};
   hipStream_t st = ctx->stream;
-  hipError_t e = hipMalloc((void **)&s->rowptr, ((size_t)n + 1) * 4);
-  if (e == hipSuccess) e = hipMalloc((void **)&s->colind, std::max<size_t>((size_t)nnz, 1) * 4);
-  if (e == hipSuccess) e = hipMalloc((void **)&s->vals, std::max<size_t>((size_t)nnz, 1) * 8);
-  if (e == hipSuccess) e = hipMalloc((void **)&s->items, std::max<size_t>(S.items.size(), 1) * sizeof(SddmmItem));
-  if (e == hipSuccess) e = hipMemcpyAsync(s->rowptr, rowptr, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && nnz) e = hipMemcpyAsync(s->colind, colind, (size_t)nnz * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && !S.items.empty()) e = hipMemcpyAsync(s->items, S.items.data(), S.items.size() * sizeof(SddmmItem), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemsetAsync(s->vals, 0, std::max<size_t>((size_t)nnz, 1) * 8, st);
+  hipError_t e = s->rowptr.alloc(((size_t)n + 1) * 4);
+  if (e == hipSuccess) e = s->colind.alloc(std::max<size_t>((size_t)nnz, 1) * 4);
+  if (e == hipSuccess) e = s->vals.alloc(std::max<size_t>((size_t)nnz, 1) * 8);
+  if (e == hipSuccess) e = s->items.alloc(std::max<size_t>(S.items.size(), 1) * sizeof(SddmmItem));
+  if (e == hipSuccess) e = hipMemcpyAsync(s->rowptr.p, rowptr, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && nnz) e = hipMemcpyAsync(s->colind.p, colind, (size_t)nnz * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && !S.items.empty()) e = hipMemcpyAsync(s->items.p, S.items.data(), S.items.size() * sizeof(SddmmItem), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(s->vals.p, 0, std::max<size_t>((size_t)nnz, 1) * 8, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);  // (the host arrays are the caller's, or locals of this call)
-  if (e != hipSuccess) {
-    for (void *p : {(void *)s->rowptr, (void *)s->colind, (void *)s->vals, (void *)s->items})
-      if (p) hipFree(p);
-    delete s;  // (not yet retained)
-    return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "%s: %s", what, hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "%s: %s", what, hipGetErrorString(e));
   ctx_retain(ctx);
-  *out = s;
+  *out = s.release();
   return SLQ_OK;
 }
 
@@ -4364,16 +4385,7 @@ extern "C" int slq_sddmm_create_device(slq_context *ctx, int64_t n, int64_t nnz,
   }
 }
 
-extern "C" int slq_sddmm_destroy(slq_sddmm *s) {
-  if (!s) return SLQ_OK;
-  hipSetDevice(s->ctx->device);
-  hipStreamSynchronize(s->ctx->stream);
-  for (void *p : {(void *)s->rowptr, (void *)s->colind, (void *)s->vals, (void *)s->items})
-    if (p) hipFree(p);
-  ctx_release(s->ctx);
-  delete s;
-  return SLQ_OK;
-}
+extern "C" int slq_sddmm_destroy(slq_sddmm *s) { return handle_destroy(s); }
 
 extern "C" int slq_sddmm_update(slq_sddmm *s, slq_dmat *W, int w0, slq_dmat *Z, int z0, int m, double alpha, double beta, int symmetric) {
   if (!s) return fail(SLQ_EINVAL, "slq_sddmm_update: accumulator is NULL");
@@ -4388,9 +4400,9 @@ extern "C" int slq_sddmm_update(slq_sddmm *s, slq_dmat *W, int w0, slq_dmat *Z, 
     const double *w = W->d + (size_t)w0 * s->n, *z = Z->d + (size_t)z0 * s->n;
     const dim3 g((unsigned)s->grid), b(64 * kSddmmWaves);
     if (symmetric)
-      k_sddmm<true><<<g, b, 0, s->ctx->stream>>>(s->nitems, s->items, s->rowptr, s->colind, s->n, w, z, m, 0.5 * alpha, beta, s->vals);
+      k_sddmm<true><<<g, b, 0, s->ctx->stream>>>(s->nitems, s->items.as<SddmmItem>(), s->rowptr.as<int32_t>(), s->colind.as<int32_t>(), s->n, w, z, m, 0.5 * alpha, beta, s->vals.as<double>());
     else
-      k_sddmm<false><<<g, b, 0, s->ctx->stream>>>(s->nitems, s->items, s->rowptr, s->colind, s->n, w, z, m, alpha, beta, s->vals);
+      k_sddmm<false><<<g, b, 0, s->ctx->stream>>>(s->nitems, s->items.as<SddmmItem>(), s->rowptr.as<int32_t>(), s->colind.as<int32_t>(), s->n, w, z, m, alpha, beta, s->vals.as<double>());
     HIP_TRY(hipGetLastError());
   }
   s->count += m;
@@ -4400,7 +4412,7 @@ extern "C" int slq_sddmm_update(slq_sddmm *s, slq_dmat *W, int w0, slq_dmat *Z, 
 extern "C" int slq_sddmm_get(slq_sddmm *s, double *vals, int64_t *count) {
   if (!s) return fail(SLQ_EINVAL, "slq_sddmm_get: accumulator is NULL");
   HIP_TRY(hipSetDevice(s->ctx->device));
-  if (vals && s->nnz) HIP_TRY(hipMemcpyAsync(vals, s->vals, (size_t)s->nnz * 8, hipMemcpyDeviceToHost, s->ctx->stream));
+  if (vals && s->nnz) HIP_TRY(hipMemcpyAsync(vals, s->vals.p, (size_t)s->nnz * 8, hipMemcpyDeviceToHost, s->ctx->stream));
   HIP_TRY(hipStreamSynchronize(s->ctx->stream));
   if (count) *count = s->count;
   return SLQ_OK;
@@ -4408,14 +4420,14 @@ extern "C" int slq_sddmm_get(slq_sddmm *s, double *vals, int64_t *count) {
 
 extern "C" int slq_sddmm_ptr(slq_sddmm *s, void **d_vals) {
   if (!s || !d_vals) return fail(SLQ_EINVAL, "slq_sddmm_ptr: NULL argument");
-  *d_vals = s->vals;
+  *d_vals = s->vals.p;
   return SLQ_OK;
 }
 
 extern "C" int slq_sddmm_reset(slq_sddmm *s) {
   if (!s) return fail(SLQ_EINVAL, "slq_sddmm_reset: accumulator is NULL");
   HIP_TRY(hipSetDevice(s->ctx->device));
-  HIP_TRY(hipMemsetAsync(s->vals, 0, std::max<size_t>((size_t)s->nnz, 1) * 8, s->ctx->stream));
+  HIP_TRY(hipMemsetAsync(s->vals.p, 0, std::max<size_t>((size_t)s->nnz, 1) * 8, s->ctx->stream));
   s->count = 0;
   return SLQ_OK;
 }
@@ -4468,16 +4480,24 @@ static const char *op_kind_name(int kind) {
     default: return "?";
   }
 }
+// "A kernel operator this object may be built on", for the creates of the side objects: a kernel operator (of a preconditioned one
+// its base: hint_base says so), unscaled where the object is not built for a diagonal scale, fp64 where the object is, on ctx, and
+// ctx alive.
+static int kernel_base_check(slq_context *ctx, const slq_operator *op, const char *who, bool f64_only, bool refuse_scaled, bool hint_base) {
+  if (hint_base && op->kind == OP_KERNEL_PRECOND)
+    return fail(SLQ_EINVAL, "%s: the operator is of kind 'kernel_precond': the object belongs to the kernel operator it was built on (pass its base)", who);
+  if (op->kind != OP_KERNEL) return fail(SLQ_EINVAL, "%s: the operator is of kind '%s', not a kernel operator (slq_kernel_create)", who, op_kind_name(op->kind));
+  if (refuse_scaled) SLQ_TRY(kernel_refuse_scaled(op, who));
+  if (f64_only && op->dtype != SLQ_F64) return fail(SLQ_EINVAL, "%s: the operator's dtype is fp32: the object is fp64 only (the device matrices are fp64)", who);
+  if (op->ctx != ctx) return fail(SLQ_EINVAL, "%s: the operator belongs to another context", who);
+  if (ctx->dead) return fail(SLQ_EINVAL, "%s: the context has been destroyed", who);
+  return SLQ_OK;
+}
 
 extern "C" int slq_kernel_grad_create(slq_context *ctx, slq_operator *op, slq_kernel_grad **out) {
   if (!ctx || !op || !out) return fail(SLQ_EINVAL, "slq_kernel_grad_create: ctx/op/out is NULL");
   *out = nullptr;
-  if (op->kind != OP_KERNEL)
-    return fail(SLQ_EINVAL, "slq_kernel_grad_create: the operator is of kind '%s', not a kernel operator (slq_kernel_create)", op_kind_name(op->kind));
-  SLQ_TRY(kernel_refuse_scaled(op, "slq_kernel_grad_create"));
-  if (op->dtype != SLQ_F64) return fail(SLQ_EINVAL, "slq_kernel_grad_create: the operator's dtype is fp32: the accumulator is fp64 only (the device matrices are fp64)");
-  if (op->ctx != ctx) return fail(SLQ_EINVAL, "slq_kernel_grad_create: the operator belongs to another context");
-  if (ctx->dead) return fail(SLQ_EINVAL, "slq_kernel_grad_create: the context has been destroyed");
+  SLQ_TRY(kernel_base_check(ctx, op, "slq_kernel_grad_create", true, true, false));
   HIP_TRY(hipSetDevice(ctx->device));
   const KernelGradSchedule S = kernel_grad_schedule(op->n, 1, ctx->num_cus);
   std::unique_ptr<slq_kernel_grad> g(new (std::nothrow) slq_kernel_grad{ctx, op, op->n, 0, S.nparts(), op->k_pts.d, op->k_pts.dpad, {}, {}});
@@ -4491,15 +4511,7 @@ extern "C" int slq_kernel_grad_create(slq_context *ctx, slq_operator *op, slq_ke
   return SLQ_OK;
 }
 
-extern "C" int slq_kernel_grad_destroy(slq_kernel_grad *g) {
-  if (!g) return SLQ_OK;
-  hipSetDevice(g->ctx->device);
-  hipStreamSynchronize(g->ctx->stream);
-  slq_context *ctx = g->ctx;
-  delete g;  // (every device array is a member that frees itself)
-  ctx_release(ctx);
-  return SLQ_OK;
-}
+extern "C" int slq_kernel_grad_destroy(slq_kernel_grad *g) { return handle_destroy(g); }
 
 extern "C" int slq_kernel_grad_update(slq_kernel_grad *g, slq_dmat *Z, int z0, slq_dmat *W, int w0, int m, double alpha, double beta) {
   if (!g) return fail(SLQ_EINVAL, "slq_kernel_grad_update: accumulator is NULL");
@@ -4581,10 +4593,7 @@ static int kernel_cross_rescale(slq_kernel_cross *c) {
 static int kernel_cross_create_body(slq_context *ctx, slq_operator *op, int64_t m, const void *points, int64_t ldp, bool on_device, slq_kernel_cross **out) {
   if (!ctx || !op || !points || !out) return fail(SLQ_EINVAL, "slq_kernel_cross_create: ctx/op/points/out is NULL");
   *out = nullptr;
-  if (op->kind != OP_KERNEL)
-    return fail(SLQ_EINVAL, "slq_kernel_cross_create: the operator is of kind '%s', not a kernel operator (slq_kernel_create)", op_kind_name(op->kind));
-  if (op->ctx != ctx) return fail(SLQ_EINVAL, "slq_kernel_cross_create: the operator belongs to another context");
-  if (ctx->dead) return fail(SLQ_EINVAL, "slq_kernel_cross_create: the context has been destroyed");
+  SLQ_TRY(kernel_base_check(ctx, op, "slq_kernel_cross_create", false, false, false));
   if (m < 1 || m >= ((int64_t)1 << 31) - 16) return fail(SLQ_EINVAL, "slq_kernel_cross_create: m = %lld new points (1 <= m < 2^31 - 16)", (long long)m);
   const int d = op->k_pts.d;
   if (ldp < d) return fail(SLQ_EINVAL, "slq_kernel_cross_create: ldp = %lld is below d = %d", (long long)ldp, d);
@@ -4613,13 +4622,25 @@ extern "C" int slq_kernel_cross_create_device(slq_context *ctx, slq_operator *op
   return kernel_cross_create_body(ctx, op, m, d_points, ldp, true, out);
 }
 
-extern "C" int slq_kernel_cross_destroy(slq_kernel_cross *c) {
-  if (!c) return SLQ_OK;
-  hipSetDevice(c->ctx->device);
-  hipStreamSynchronize(c->ctx->stream);
-  slq_context *ctx = c->ctx;
-  delete c;  // (every device array is a member that frees itself)
-  ctx_release(ctx);
+extern "C" int slq_kernel_cross_destroy(slq_kernel_cross *c) { return handle_destroy(c); }
+
+// The slab scaffold of the cross, feature and adjoint feature products, whose schedules S split the summed side into slabs: more
+// than 65535 column chunks are refused (max_cols_msg: the b that still fits), launch(out, ldo, slab_stride) fills the product's own
+// args and calls its own *_launch - with one slab straight into Y, else into `scratch` (grown on demand: nslabs partials of
+// rows_out x b, packed), which kernel_cross_sum_launch then folds into Y. Everything on the context's stream.
+template <typename Launch>
+static int slab_product(slq_context *ctx, bool is_f64, const KernelSchedule &S, int64_t rows_out, int b, int max_cols_msg, DevBuf &scratch, void *Y, int64_t ldy,
+                        const char *who, Launch launch) {
+  if (S.ncol_chunks > 65535) return fail(SLQ_EINVAL, "%s: b = %d columns (at most %d)", who, b, max_cols_msg);
+  const int64_t slab_stride = rows_out * (int64_t)b;
+  const bool slabs = S.nslabs > 1;
+  if (slabs) SLQ_TRY(devbuf_grow(scratch, (size_t)S.nslabs * (size_t)slab_stride * (is_f64 ? 8 : 4), who, "slab scratch"));
+  if (!launch(slabs ? scratch.p : Y, slabs ? rows_out : ldy, slab_stride)) return fail(SLQ_EINVAL, "%s: no kernel for %d column tiles", who, S.col_blocks);
+  HIP_TRY(hipGetLastError());
+  if (slabs) {
+    kernel_cross_sum_launch(is_f64, rows_out, b, S.nslabs, scratch.p, slab_stride, Y, ldy, (void *)ctx->stream);
+    HIP_TRY(hipGetLastError());
+  }
   return SLQ_OK;
 }
 
@@ -4630,16 +4651,6 @@ static int kernel_cross_product(slq_kernel_cross *c, int trans, const void *X, i
   const bool fwd = trans == 0;
   const int64_t nrows = fwd ? c->pts.n : op->n, nsum = fwd ? op->n : c->pts.n;
   const KernelSchedule S = kernel_cross_schedule(nrows, nsum, b, c->ctx->num_cus);
-  if (S.ncol_chunks > 65535) return fail(SLQ_EINVAL, "%s: b = %d columns (at most %d)", who, b, 65535 * 16 * kKernelMaxColBlocks);
-  const size_t es = esize(c->dtype);
-  const int64_t slab_stride = nrows * (int64_t)b;
-  if (S.nslabs > 1) {
-    const size_t need = (size_t)S.nslabs * (size_t)slab_stride * es;
-    if (c->scratch.bytes() < need) {
-      const hipError_t e = c->scratch.alloc(need);
-      if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "%s: slab scratch of %zu bytes: %s", who, need, hipGetErrorString(e));
-    }
-  }
   KernelCrossArgs a;
   a.nrows = (int)nrows, a.rpad = (int)(fwd ? c->pts.npad : op->k_pts.npad);
   a.nsum = (int)nsum, a.spad = (int)(fwd ? op->k_pts.npad : c->pts.npad);
@@ -4648,15 +4659,11 @@ static int kernel_cross_product(slq_kernel_cross *c, int trans, const void *X, i
   a.szt = fwd ? op->k_pts.zt : c->pts.zt, a.snrm = fwd ? op->k_pts.nrm : c->pts.nrm;
   a.params = op->k_pts.params;
   a.W = X, a.ldw = ldx, a.b = b;
-  a.out = S.nslabs > 1 ? c->scratch.p : Y, a.ldo = S.nslabs > 1 ? nrows : ldy, a.slab_stride = slab_stride;
-  if (!kernel_cross_launch(c->dtype == SLQ_F64, op->k_profile, S, a, (void *)c->ctx->stream))
-    return fail(SLQ_EINVAL, "%s: no kernel for profile %d with %d column tiles", who, op->k_profile, S.col_blocks);
-  HIP_TRY(hipGetLastError());
-  if (S.nslabs > 1) {
-    kernel_cross_sum_launch(c->dtype == SLQ_F64, nrows, b, S.nslabs, c->scratch.p, slab_stride, Y, ldy, (void *)c->ctx->stream);
-    HIP_TRY(hipGetLastError());
-  }
-  return SLQ_OK;
+  const bool f64 = c->dtype == SLQ_F64;
+  return slab_product(c->ctx, f64, S, nrows, b, 65535 * 16 * kKernelMaxColBlocks, c->scratch, Y, ldy, who, [&](void *out, int64_t ldo, int64_t slab_stride) {
+    a.out = out, a.ldo = ldo, a.slab_stride = slab_stride;
+    return kernel_cross_launch(f64, op->k_profile, S, a, (void *)c->ctx->stream);
+  });
 }
 
 extern "C" int slq_kernel_cross_matmat(slq_kernel_cross *c, int trans, const void *X, int64_t ldx, void *Y, int64_t ldy, int b) {
@@ -4667,17 +4674,8 @@ extern "C" int slq_kernel_cross_matmat(slq_kernel_cross *c, int trans, const voi
   const int64_t rin = trans ? c->pts.n : c->op->n, rout = trans ? c->op->n : c->pts.n;
   if (ldx < rin) return fail(SLQ_EINVAL, "slq_kernel_cross_matmat: ldx = %lld is below the %lld rows of X (trans = %d)", (long long)ldx, (long long)rin, trans);
   if (ldy < rout) return fail(SLQ_EINVAL, "slq_kernel_cross_matmat: ldy = %lld is below the %lld rows of Y (trans = %d)", (long long)ldy, (long long)rout, trans);
-  HIP_TRY(hipSetDevice(c->ctx->device));
-  const size_t es = esize(c->dtype);
-  const size_t need_in = (size_t)rin * b * es, need_out = (size_t)rout * b * es;
-  if (c->stage_in.bytes() < need_in) HIP_TRY(c->stage_in.alloc(need_in));
-  if (c->stage_out.bytes() < need_out) HIP_TRY(c->stage_out.alloc(need_out));
-  hipStream_t st = c->ctx->stream;
-  HIP_TRY(hipMemcpy2DAsync(c->stage_in.p, (size_t)rin * es, X, (size_t)ldx * es, (size_t)rin * es, (size_t)b, hipMemcpyHostToDevice, st));
-  SLQ_TRY(kernel_cross_product(c, trans, c->stage_in.p, rin, c->stage_out.p, rout, b, "slq_kernel_cross_matmat"));
-  HIP_TRY(hipMemcpy2DAsync(Y, (size_t)ldy * es, c->stage_out.p, (size_t)rout * es, (size_t)rout * es, (size_t)b, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return SLQ_OK;
+  return staged_panel_product(c->ctx, esize(c->dtype), c->stage_in, c->stage_out, X, ldx, rin, Y, ldy, rout, b, "slq_kernel_cross_matmat",
+                              [&](const void *in, int64_t ld_in, void *out, int64_t ld_out) { return kernel_cross_product(c, trans, in, ld_in, out, ld_out, b, "slq_kernel_cross_matmat"); });
 }
 
 extern "C" int slq_kernel_cross_dmat(slq_kernel_cross *c, int trans, slq_dmat *IN, int i0, slq_dmat *OUT, int o0, int b) {
@@ -4685,15 +4683,12 @@ extern "C" int slq_kernel_cross_dmat(slq_kernel_cross *c, int trans, slq_dmat *I
   if (c->dtype != SLQ_F64) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: the cross object's dtype is fp32: the device matrices are fp64 (use slq_kernel_cross_matmat)");
   if (trans != 0 && trans != 1) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: trans = %d (0: OUT = C IN, 1: OUT = C^T IN)", trans);
   if (b < 1) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: b = %d columns (b >= 1)", b);
-  SLQ_TRY(dmat_range(IN, i0, b, "slq_kernel_cross_dmat(IN)"));
-  SLQ_TRY(dmat_range(OUT, o0, b, "slq_kernel_cross_dmat(OUT)"));
   const int64_t rin = trans ? c->pts.n : c->op->n, rout = trans ? c->op->n : c->pts.n;
-  if (IN->n != rin) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: IN has %lld rows, the product with trans = %d reads %lld", (long long)IN->n, trans, (long long)rin);
-  if (OUT->n != rout) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: OUT has %lld rows, the product with trans = %d writes %lld", (long long)OUT->n, trans, (long long)rout);
-  if (IN->ctx != c->ctx || OUT->ctx != c->ctx) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: a matrix belongs to another context");
-  if (IN == OUT && i0 < o0 + b && o0 < i0 + b) return fail(SLQ_EINVAL, "slq_kernel_cross_dmat: the columns [%d, %d) of IN and [%d, %d) of OUT overlap in one matrix", i0, i0 + b, o0, o0 + b);
+  const double *in;
+  double *out;
+  SLQ_TRY(dmat_operands(IN, i0, OUT, o0, b, rin, rout, c->ctx, "slq_kernel_cross_dmat", &in, &out));
   HIP_TRY(hipSetDevice(c->ctx->device));
-  return kernel_cross_product(c, trans, IN->d + (size_t)i0 * IN->n, IN->n, OUT->d + (size_t)o0 * OUT->n, OUT->n, b, "slq_kernel_cross_dmat");
+  return kernel_cross_product(c, trans, in, rin, out, rout, b, "slq_kernel_cross_dmat");
 }
 
 // z*^T (dpad x mpad, mpad = m rounded up to 16) and |z*|^2 (mpad) in the object's dtype, brought up to the operator's parameters
@@ -4710,13 +4705,8 @@ extern "C" int slq_debug_kernel_cross_points(slq_kernel_cross *c, void *zt, void
 // kernel_cross_schedule() of slq_kernelcross.hpp as an array: rows per block, row blocks, 16-column tiles per workgroup, column
 // chunks, slabs, tiles per slab, then slab_begin[0 .. slabs] (-1 beyond). No HIP call.
 extern "C" int slq_debug_kernel_cross_schedule(int64_t nrows, int64_t nsum, int64_t b, int num_cus, int64_t *out, int nout) {
-  if (!out || nout < 6 + kKernelCrossMaxSlabs + 1) return fail(SLQ_EINVAL, "slq_debug_kernel_cross_schedule: room for %d values", 6 + kKernelCrossMaxSlabs + 1);
-  const int64_t lim = ((int64_t)1 << 31) - 16;
-  if (nrows <= 0 || nrows >= lim || nsum <= 0 || nsum >= lim || b <= 0 || b >= lim || num_cus <= 0)
-    return fail(SLQ_EINVAL, "slq_debug_kernel_cross_schedule: 0 < nrows, nsum, b < 2^31 - 16 and num_cus positive");
-  const KernelSchedule S = kernel_cross_schedule(nrows, nsum, b, num_cus);
-  kernel_schedule_words({S.rows_per_block, S.nrow_blocks, S.col_blocks, S.ncol_chunks, S.nslabs, S.tiles_per_slab}, S.nslabs, S.slab_begin, kKernelCrossMaxSlabs, out);
-  return SLQ_OK;
+  return kernel_schedule_debug("slq_debug_kernel_cross_schedule", kernel_extents_ok({nrows, nsum, b}, num_cus), "0 < nrows, nsum, b < 2^31 - 16 and num_cus positive", 6,
+                               kKernelCrossMaxSlabs, out, nout, [&]() { return kernel_cross_schedule(nrows, nsum, b, num_cus); });
 }
 
 // ---- random Fourier features of the kernel operator (schedule and kernel in slq_kernelfeature.hpp) ----------------
@@ -4744,12 +4734,7 @@ template <typename F> static void kernel_feature_transpose(int64_t f2, int64_t f
 extern "C" int slq_kernel_feature_create(slq_context *ctx, slq_operator *op, int64_t F2, const void *omega, int64_t ld, slq_kernel_feature **out) {
   if (!ctx || !op || !omega || !out) return fail(SLQ_EINVAL, "slq_kernel_feature_create: ctx/op/omega/out is NULL");
   *out = nullptr;
-  if (op->kind == OP_KERNEL_PRECOND)
-    return fail(SLQ_EINVAL, "slq_kernel_feature_create: the operator is of kind 'kernel_precond': the features belong to the kernel operator it was built on (pass its base)");
-  if (op->kind != OP_KERNEL)
-    return fail(SLQ_EINVAL, "slq_kernel_feature_create: the operator is of kind '%s', not a kernel operator (slq_kernel_create)", op_kind_name(op->kind));
-  if (op->ctx != ctx) return fail(SLQ_EINVAL, "slq_kernel_feature_create: the operator belongs to another context");
-  if (ctx->dead) return fail(SLQ_EINVAL, "slq_kernel_feature_create: the context has been destroyed");
+  SLQ_TRY(kernel_base_check(ctx, op, "slq_kernel_feature_create", false, false, true));
   if (F2 < 1 || F2 > kKernelFeatureMaxFreq) return fail(SLQ_EINVAL, "slq_kernel_feature_create: F2 = %lld frequencies (1 <= F2 <= 2^30)", (long long)F2);
   const int d = op->k_pts.d, dpad = op->k_pts.dpad;
   if (ld < d) return fail(SLQ_EINVAL, "slq_kernel_feature_create: ld = %lld is below d = %d", (long long)ld, d);
@@ -4777,15 +4762,7 @@ extern "C" int slq_kernel_feature_create(slq_context *ctx, slq_operator *op, int
   return SLQ_OK;
 }
 
-extern "C" int slq_kernel_feature_destroy(slq_kernel_feature *f) {
-  if (!f) return SLQ_OK;
-  hipSetDevice(f->ctx->device);
-  hipStreamSynchronize(f->ctx->stream);
-  slq_context *ctx = f->ctx;
-  delete f;  // (every device array is a member that frees itself)
-  ctx_release(ctx);
-  return SLQ_OK;
-}
+extern "C" int slq_kernel_feature_destroy(slq_kernel_feature *f) { return handle_destroy(f); }
 
 // the row points of a product: the operator's own (cross NULL) or the new points of a cross object of the same operator
 static int kernel_feature_rows(const slq_kernel_feature *f, const slq_kernel_cross *cross, const char *who) {
@@ -4801,16 +4778,6 @@ static int kernel_feature_product_run(slq_kernel_feature *f, slq_kernel_cross *c
   const bool f64 = f->dtype == SLQ_F64;
   const int64_t nrows = pts.n;
   const KernelSchedule S = kernel_feature_schedule(nrows, f->f2, b, f->ctx->num_cus, f64);
-  if (S.ncol_chunks > 65535) return fail(SLQ_EINVAL, "%s: b = %d columns (at most %d)", who, b, 65535 * kernel_feature_chunk_cols(f64));
-  const size_t es = esize(f->dtype);
-  const int64_t slab_stride = nrows * (int64_t)b;
-  if (S.nslabs > 1) {
-    const size_t need = (size_t)S.nslabs * (size_t)slab_stride * es;
-    if (f->scratch.bytes() < need) {
-      const hipError_t e = f->scratch.alloc(need);
-      if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "%s: slab scratch of %zu bytes: %s", who, need, hipGetErrorString(e));
-    }
-  }
   KernelFeatureArgs a;
   a.nrows = (int)nrows, a.rpad = (int)pts.npad;
   a.nfreq = (int)f->f2, a.fpad = (int)f->f2pad;
@@ -4819,14 +4786,10 @@ static int kernel_feature_product_run(slq_kernel_feature *f, slq_kernel_cross *c
   a.omt = f->omt.p;
   a.params = op->k_pts.params;
   a.W = W, a.ldw = ldw, a.b = b;
-  a.out = S.nslabs > 1 ? f->scratch.p : Y, a.ldo = S.nslabs > 1 ? nrows : ldy, a.slab_stride = slab_stride;
-  if (!kernel_feature_launch(f64, S, a, (void *)f->ctx->stream)) return fail(SLQ_EINVAL, "%s: no kernel for %d column tiles", who, S.col_blocks);
-  HIP_TRY(hipGetLastError());
-  if (S.nslabs > 1) {
-    kernel_cross_sum_launch(f64, nrows, b, S.nslabs, f->scratch.p, slab_stride, Y, ldy, (void *)f->ctx->stream);
-    HIP_TRY(hipGetLastError());
-  }
-  return SLQ_OK;
+  return slab_product(f->ctx, f64, S, nrows, b, 65535 * kernel_feature_chunk_cols(f64), f->scratch, Y, ldy, who, [&](void *out, int64_t ldo, int64_t slab_stride) {
+    a.out = out, a.ldo = ldo, a.slab_stride = slab_stride;
+    return kernel_feature_launch(f64, S, a, (void *)f->ctx->stream);
+  });
 }
 
 extern "C" int slq_kernel_feature_matmat(slq_kernel_feature *f, slq_kernel_cross *cross, const void *W, int64_t ldw, void *Y, int64_t ldy, int b) {
@@ -4837,17 +4800,8 @@ extern "C" int slq_kernel_feature_matmat(slq_kernel_feature *f, slq_kernel_cross
   const int64_t rin = 2 * f->f2, rout = cross ? cross->pts.n : f->op->n;
   if (ldw < rin) return fail(SLQ_EINVAL, "slq_kernel_feature_matmat: ldw = %lld is below the %lld rows of W (2 F2)", (long long)ldw, (long long)rin);
   if (ldy < rout) return fail(SLQ_EINVAL, "slq_kernel_feature_matmat: ldy = %lld is below the %lld rows of Y", (long long)ldy, (long long)rout);
-  HIP_TRY(hipSetDevice(f->ctx->device));
-  const size_t es = esize(f->dtype);
-  const size_t need_in = (size_t)rin * b * es, need_out = (size_t)rout * b * es;
-  if (f->stage_in.bytes() < need_in) HIP_TRY(f->stage_in.alloc(need_in));
-  if (f->stage_out.bytes() < need_out) HIP_TRY(f->stage_out.alloc(need_out));
-  hipStream_t st = f->ctx->stream;
-  HIP_TRY(hipMemcpy2DAsync(f->stage_in.p, (size_t)rin * es, W, (size_t)ldw * es, (size_t)rin * es, (size_t)b, hipMemcpyHostToDevice, st));
-  SLQ_TRY(kernel_feature_product_run(f, cross, f->stage_in.p, rin, f->stage_out.p, rout, b, "slq_kernel_feature_matmat"));
-  HIP_TRY(hipMemcpy2DAsync(Y, (size_t)ldy * es, f->stage_out.p, (size_t)rout * es, (size_t)rout * es, (size_t)b, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return SLQ_OK;
+  return staged_panel_product(f->ctx, esize(f->dtype), f->stage_in, f->stage_out, W, ldw, rin, Y, ldy, rout, b, "slq_kernel_feature_matmat",
+                              [&](const void *in, int64_t ld_in, void *out, int64_t ld_out) { return kernel_feature_product_run(f, cross, in, ld_in, out, ld_out, b, "slq_kernel_feature_matmat"); });
 }
 
 extern "C" int slq_kernel_feature_dmat(slq_kernel_feature *f, slq_kernel_cross *cross, slq_dmat *IN, int i0, slq_dmat *OUT, int o0, int b) {
@@ -4855,15 +4809,12 @@ extern "C" int slq_kernel_feature_dmat(slq_kernel_feature *f, slq_kernel_cross *
   if (f->dtype != SLQ_F64) return fail(SLQ_EINVAL, "slq_kernel_feature_dmat: the feature map's dtype is fp32: the device matrices are fp64 (use slq_kernel_feature_matmat)");
   SLQ_TRY(kernel_feature_rows(f, cross, "slq_kernel_feature_dmat"));
   if (b < 1) return fail(SLQ_EINVAL, "slq_kernel_feature_dmat: b = %d columns (b >= 1)", b);
-  SLQ_TRY(dmat_range(IN, i0, b, "slq_kernel_feature_dmat(IN)"));
-  SLQ_TRY(dmat_range(OUT, o0, b, "slq_kernel_feature_dmat(OUT)"));
   const int64_t rin = 2 * f->f2, rout = cross ? cross->pts.n : f->op->n;
-  if (IN->n != rin) return fail(SLQ_EINVAL, "slq_kernel_feature_dmat: IN has %lld rows, the product reads %lld (2 F2)", (long long)IN->n, (long long)rin);
-  if (OUT->n != rout) return fail(SLQ_EINVAL, "slq_kernel_feature_dmat: OUT has %lld rows, the product writes %lld", (long long)OUT->n, (long long)rout);
-  if (IN->ctx != f->ctx || OUT->ctx != f->ctx) return fail(SLQ_EINVAL, "slq_kernel_feature_dmat: a matrix belongs to another context");
-  if (IN == OUT && i0 < o0 + b && o0 < i0 + b) return fail(SLQ_EINVAL, "slq_kernel_feature_dmat: the columns [%d, %d) of IN and [%d, %d) of OUT overlap in one matrix", i0, i0 + b, o0, o0 + b);
+  const double *in;
+  double *out;
+  SLQ_TRY(dmat_operands(IN, i0, OUT, o0, b, rin, rout, f->ctx, "slq_kernel_feature_dmat", &in, &out));
   HIP_TRY(hipSetDevice(f->ctx->device));
-  return kernel_feature_product_run(f, cross, IN->d + (size_t)i0 * IN->n, IN->n, OUT->d + (size_t)o0 * OUT->n, OUT->n, b, "slq_kernel_feature_dmat");
+  return kernel_feature_product_run(f, cross, in, rin, out, rout, b, "slq_kernel_feature_dmat");
 }
 
 // Z = Phi^T U for device arrays (U rows x b, Z 2 F2 x b), on the stream. The caller has checked the shapes.
@@ -4874,16 +4825,6 @@ static int kernel_feature_adjoint_run(slq_kernel_feature *f, slq_kernel_cross *c
   const bool f64 = f->dtype == SLQ_F64;
   const int64_t nrows = pts.n, rout = 2 * f->f2;
   const KernelSchedule S = kernel_feature_adjoint_schedule(f->f2, nrows, b, f->ctx->num_cus, f64);
-  if (S.ncol_chunks > 65535) return fail(SLQ_EINVAL, "%s: b = %d columns (at most %d)", who, b, 65535 * kernel_feature_adjoint_chunk_cols(f64));
-  const size_t es = esize(f->dtype);
-  const int64_t slab_stride = rout * (int64_t)b;
-  if (S.nslabs > 1) {
-    const size_t need = (size_t)S.nslabs * (size_t)slab_stride * es;
-    if (f->scratch.bytes() < need) {
-      const hipError_t e = f->scratch.alloc(need);
-      if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "%s: slab scratch of %zu bytes: %s", who, need, hipGetErrorString(e));
-    }
-  }
   KernelFeatureAdjArgs a;
   a.nfreq = (int)f->f2, a.fpad = (int)f->f2pad;
   a.nrows = (int)nrows, a.rpad = (int)pts.npad;
@@ -4891,14 +4832,10 @@ static int kernel_feature_adjoint_run(slq_kernel_feature *f, slq_kernel_cross *c
   a.omt = f->omt.p, a.rzt = pts.zt;
   a.params = op->k_pts.params;
   a.U = U, a.ldu = ldu, a.b = b;
-  a.out = S.nslabs > 1 ? f->scratch.p : Z, a.ldo = S.nslabs > 1 ? rout : ldz, a.slab_stride = slab_stride;
-  if (!kernel_feature_adjoint_launch(f64, S, a, (void *)f->ctx->stream)) return fail(SLQ_EINVAL, "%s: no kernel for %d column tiles", who, S.col_blocks);
-  HIP_TRY(hipGetLastError());
-  if (S.nslabs > 1) {
-    kernel_cross_sum_launch(f64, rout, b, S.nslabs, f->scratch.p, slab_stride, Z, ldz, (void *)f->ctx->stream);
-    HIP_TRY(hipGetLastError());
-  }
-  return SLQ_OK;
+  return slab_product(f->ctx, f64, S, rout, b, 65535 * kernel_feature_adjoint_chunk_cols(f64), f->scratch, Z, ldz, who, [&](void *out, int64_t ldo, int64_t slab_stride) {
+    a.out = out, a.ldo = ldo, a.slab_stride = slab_stride;
+    return kernel_feature_adjoint_launch(f64, S, a, (void *)f->ctx->stream);
+  });
 }
 
 extern "C" int slq_kernel_feature_rmatmat(slq_kernel_feature *f, slq_kernel_cross *cross, const void *U, int64_t ldu, void *Z, int64_t ldz, int b) {
@@ -4909,17 +4846,8 @@ extern "C" int slq_kernel_feature_rmatmat(slq_kernel_feature *f, slq_kernel_cros
   const int64_t rin = cross ? cross->pts.n : f->op->n, rout = 2 * f->f2;
   if (ldu < rin) return fail(SLQ_EINVAL, "slq_kernel_feature_rmatmat: ldu = %lld is below the %lld rows of U", (long long)ldu, (long long)rin);
   if (ldz < rout) return fail(SLQ_EINVAL, "slq_kernel_feature_rmatmat: ldz = %lld is below the %lld rows of Z (2 F2)", (long long)ldz, (long long)rout);
-  HIP_TRY(hipSetDevice(f->ctx->device));
-  const size_t es = esize(f->dtype);
-  const size_t need_in = (size_t)rin * b * es, need_out = (size_t)rout * b * es;
-  if (f->stage_in.bytes() < need_in) HIP_TRY(f->stage_in.alloc(need_in));
-  if (f->stage_out.bytes() < need_out) HIP_TRY(f->stage_out.alloc(need_out));
-  hipStream_t st = f->ctx->stream;
-  HIP_TRY(hipMemcpy2DAsync(f->stage_in.p, (size_t)rin * es, U, (size_t)ldu * es, (size_t)rin * es, (size_t)b, hipMemcpyHostToDevice, st));
-  SLQ_TRY(kernel_feature_adjoint_run(f, cross, f->stage_in.p, rin, f->stage_out.p, rout, b, "slq_kernel_feature_rmatmat"));
-  HIP_TRY(hipMemcpy2DAsync(Z, (size_t)ldz * es, f->stage_out.p, (size_t)rout * es, (size_t)rout * es, (size_t)b, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return SLQ_OK;
+  return staged_panel_product(f->ctx, esize(f->dtype), f->stage_in, f->stage_out, U, ldu, rin, Z, ldz, rout, b, "slq_kernel_feature_rmatmat",
+                              [&](const void *in, int64_t ld_in, void *out, int64_t ld_out) { return kernel_feature_adjoint_run(f, cross, in, ld_in, out, ld_out, b, "slq_kernel_feature_rmatmat"); });
 }
 
 extern "C" int slq_kernel_feature_rdmat(slq_kernel_feature *f, slq_kernel_cross *cross, slq_dmat *IN, int i0, slq_dmat *OUT, int o0, int b) {
@@ -4927,27 +4855,20 @@ extern "C" int slq_kernel_feature_rdmat(slq_kernel_feature *f, slq_kernel_cross 
   if (f->dtype != SLQ_F64) return fail(SLQ_EINVAL, "slq_kernel_feature_rdmat: the feature map's dtype is fp32: the device matrices are fp64 (use slq_kernel_feature_rmatmat)");
   SLQ_TRY(kernel_feature_rows(f, cross, "slq_kernel_feature_rdmat"));
   if (b < 1) return fail(SLQ_EINVAL, "slq_kernel_feature_rdmat: b = %d columns (b >= 1)", b);
-  SLQ_TRY(dmat_range(IN, i0, b, "slq_kernel_feature_rdmat(IN)"));
-  SLQ_TRY(dmat_range(OUT, o0, b, "slq_kernel_feature_rdmat(OUT)"));
   const int64_t rin = cross ? cross->pts.n : f->op->n, rout = 2 * f->f2;
-  if (IN->n != rin) return fail(SLQ_EINVAL, "slq_kernel_feature_rdmat: IN has %lld rows, the product reads %lld", (long long)IN->n, (long long)rin);
-  if (OUT->n != rout) return fail(SLQ_EINVAL, "slq_kernel_feature_rdmat: OUT has %lld rows, the product writes %lld (2 F2)", (long long)OUT->n, (long long)rout);
-  if (IN->ctx != f->ctx || OUT->ctx != f->ctx) return fail(SLQ_EINVAL, "slq_kernel_feature_rdmat: a matrix belongs to another context");
-  if (IN == OUT && i0 < o0 + b && o0 < i0 + b) return fail(SLQ_EINVAL, "slq_kernel_feature_rdmat: the columns [%d, %d) of IN and [%d, %d) of OUT overlap in one matrix", i0, i0 + b, o0, o0 + b);
+  const double *in;
+  double *out;
+  SLQ_TRY(dmat_operands(IN, i0, OUT, o0, b, rin, rout, f->ctx, "slq_kernel_feature_rdmat", &in, &out));
   HIP_TRY(hipSetDevice(f->ctx->device));
-  return kernel_feature_adjoint_run(f, cross, IN->d + (size_t)i0 * IN->n, IN->n, OUT->d + (size_t)o0 * OUT->n, OUT->n, b, "slq_kernel_feature_rdmat");
+  return kernel_feature_adjoint_run(f, cross, in, rin, out, rout, b, "slq_kernel_feature_rdmat");
 }
 
 // kernel_feature_adjoint_schedule() of slq_kernelfeatureadj.hpp as an array, in the order of slq_debug_kernel_feature_schedule (the
 // row blocks are those of the frequencies, the slabs those of the row points). No HIP call.
 extern "C" int slq_debug_kernel_feature_adjoint_schedule(int64_t F2, int64_t nrows, int64_t b, int num_cus, int is_f64, int64_t *out, int nout) {
-  if (!out || nout < 6 + kKernelCrossMaxSlabs + 1) return fail(SLQ_EINVAL, "slq_debug_kernel_feature_adjoint_schedule: room for %d values", 6 + kKernelCrossMaxSlabs + 1);
-  const int64_t lim = ((int64_t)1 << 31) - 16;
-  if (nrows <= 0 || nrows >= lim || F2 <= 0 || F2 > kKernelFeatureMaxFreq || b <= 0 || b >= lim || num_cus <= 0)
-    return fail(SLQ_EINVAL, "slq_debug_kernel_feature_adjoint_schedule: 0 < nrows, b < 2^31 - 16, 0 < F2 <= 2^30 and num_cus positive");
-  const KernelSchedule S = kernel_feature_adjoint_schedule(F2, nrows, b, num_cus, is_f64 != 0);
-  kernel_schedule_words({S.rows_per_block, S.nrow_blocks, S.col_blocks, S.ncol_chunks, S.nslabs, S.tiles_per_slab}, S.nslabs, S.slab_begin, kKernelCrossMaxSlabs, out);
-  return SLQ_OK;
+  return kernel_schedule_debug("slq_debug_kernel_feature_adjoint_schedule", kernel_extents_ok({nrows, F2, b}, num_cus) && F2 <= kKernelFeatureMaxFreq,
+                               "0 < nrows, b < 2^31 - 16, 0 < F2 <= 2^30 and num_cus positive", 6, kKernelCrossMaxSlabs, out, nout,
+                               [&]() { return kernel_feature_adjoint_schedule(F2, nrows, b, num_cus, is_f64 != 0); });
 }
 
 // Omega^T as the device holds it: dpad x F2pad in the object's dtype (tests: the padding must be zero)
@@ -4961,13 +4882,9 @@ extern "C" int slq_debug_kernel_feature_frequencies(slq_kernel_feature *f, void 
 
 // kernel_feature_schedule() of slq_kernelfeature.hpp as an array, in the order of slq_debug_kernel_cross_schedule. No HIP call.
 extern "C" int slq_debug_kernel_feature_schedule(int64_t nrows, int64_t F2, int64_t b, int num_cus, int is_f64, int64_t *out, int nout) {
-  if (!out || nout < 6 + kKernelCrossMaxSlabs + 1) return fail(SLQ_EINVAL, "slq_debug_kernel_feature_schedule: room for %d values", 6 + kKernelCrossMaxSlabs + 1);
-  const int64_t lim = ((int64_t)1 << 31) - 16;
-  if (nrows <= 0 || nrows >= lim || F2 <= 0 || F2 > kKernelFeatureMaxFreq || b <= 0 || b >= lim || num_cus <= 0)
-    return fail(SLQ_EINVAL, "slq_debug_kernel_feature_schedule: 0 < nrows, b < 2^31 - 16, 0 < F2 <= 2^30 and num_cus positive");
-  const KernelSchedule S = kernel_feature_schedule(nrows, F2, b, num_cus, is_f64 != 0);
-  kernel_schedule_words({S.rows_per_block, S.nrow_blocks, S.col_blocks, S.ncol_chunks, S.nslabs, S.tiles_per_slab}, S.nslabs, S.slab_begin, kKernelCrossMaxSlabs, out);
-  return SLQ_OK;
+  return kernel_schedule_debug("slq_debug_kernel_feature_schedule", kernel_extents_ok({nrows, F2, b}, num_cus) && F2 <= kKernelFeatureMaxFreq,
+                               "0 < nrows, b < 2^31 - 16, 0 < F2 <= 2^30 and num_cus positive", 6, kKernelCrossMaxSlabs, out, nout,
+                               [&]() { return kernel_feature_schedule(nrows, F2, b, num_cus, is_f64 != 0); });
 }
 
 // ---- pivoted-Cholesky preconditioner of a kernel operator (kernels and host analysis in slq_kernelprecond.hpp) ----
@@ -4975,12 +4892,6 @@ static int precond_handle(const slq_operator *op, const char *who) {
   if (!op) return fail(SLQ_EINVAL, "%s: the operator is NULL", who);
   if (op->kind != OP_KERNEL_PRECOND || !op->pre)
     return fail(SLQ_EINVAL, "%s: the operator is of kind '%s', not a preconditioned kernel operator (slq_kernel_precond_create)", who, op_kind_name(op->kind));
-  return SLQ_OK;
-}
-static int precond_grow(DevBuf &b, size_t need, const char *who) {
-  if (b.bytes() >= need) return SLQ_OK;
-  const hipError_t e = b.alloc(need);
-  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? SLQ_ENOMEM : SLQ_EHIP, "%s: scratch of %zu bytes: %s", who, need, hipGetErrorString(e));
   return SLQ_OK;
 }
 
@@ -5001,7 +4912,7 @@ static int precond_factorise(slq_operator *op) {
                              (const double *)base->k_pts.params, pc.L.as<double>(), rpad, r, thresh, pc.dres.as<double>(), pc.pivots, pc.rank_d, pc.dpiv, pc.pv, pc.pi, st))
     return fail(SLQ_EINVAL, "kernel preconditioner: no factor kernel for profile %d", base->k_profile);
   HIP_TRY(hipGetLastError());
-  SLQ_TRY(precond_grow(pc.scratch, precond_scratch_words(n, rpad, rpad, cus) * 8, "kernel preconditioner"));
+  SLQ_TRY(devbuf_grow(pc.scratch, precond_scratch_words(n, rpad, rpad, cus) * 8, "kernel preconditioner"));
   const PrecondSlabs S = precond_apply_slabs(n, rpad, cus);
   const size_t bpad = (size_t)precond_bpad(rpad);
   double *gram_d = pc.scratch.as<double>() + (size_t)S.nslabs * bpad * rpad;
@@ -5035,11 +4946,7 @@ static int precond_factorise(slq_operator *op) {
 static int kernel_precond_create_body(slq_context *ctx, slq_operator *base, int rank_max, double tol, slq_operator **out) {
   if (!ctx || !base || !out) return fail(SLQ_EINVAL, "slq_kernel_precond_create: ctx/kernel_op/out is NULL");
   *out = nullptr;
-  if (base->kind != OP_KERNEL)
-    return fail(SLQ_EINVAL, "slq_kernel_precond_create: the base operator is of kind '%s', not a kernel operator (slq_kernel_create)", op_kind_name(base->kind));
-  SLQ_TRY(kernel_refuse_scaled(base, "slq_kernel_precond_create"));
-  if (base->dtype != SLQ_F64) return fail(SLQ_EINVAL, "slq_kernel_precond_create: the base operator's dtype is fp32: the preconditioner is fp64 only");
-  if (base->ctx != ctx) return fail(SLQ_EINVAL, "slq_kernel_precond_create: the base operator belongs to another context");
+  SLQ_TRY(kernel_base_check(ctx, base, "slq_kernel_precond_create", true, true, false));
   if (!(base->k_noise > 0.0)) return fail(SLQ_EINVAL, "slq_kernel_precond_create: the base operator's noise sigma2 is 0: P^{-1/2} needs sigma2 > 0");
   if (rank_max < 1 || rank_max > kPrecondMaxRank) return fail(SLQ_EINVAL, "slq_kernel_precond_create: rank_max = %d (1 <= rank_max <= %d)", rank_max, kPrecondMaxRank);
   if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(SLQ_EINVAL, "slq_kernel_precond_create: tol = %g (finite, >= 0)", tol);
@@ -5119,7 +5026,7 @@ static int precond_apply_device(slq_operator *op, const double *X, double *Y, in
   SLQ_TRY(precond_check_fresh(op, who));
   KernelPrecond &pc = *op->pre;
   const int cus = op->ctx->num_cus;
-  SLQ_TRY(precond_grow(pc.scratch, precond_scratch_words(op->n, b, pc.rpad, cus) * 8, who));
+  SLQ_TRY(devbuf_grow(pc.scratch, precond_scratch_words(op->n, b, pc.rpad, cus) * 8, who));
   if (!precond_apply_launch((int)op->n, pc.L.as<const double>(), pc.rpad, pc.G.as<const double>(), (const double *)pc.base->k_pts.params, X, Y, b,
                             PrecondColumnLayout{op->n}, pc.scratch.as<double>(), cus, op->ctx->stream))
     return fail(SLQ_EINVAL, "%s: no apply kernel for rank %d", who, pc.rpad);
@@ -5132,31 +5039,18 @@ extern "C" int slq_kernel_precond_apply(slq_operator *op, const void *X, int64_t
   if (!X || !Y) return fail(SLQ_EINVAL, "slq_kernel_precond_apply: X/Y is NULL");
   if (b < 1) return fail(SLQ_EINVAL, "slq_kernel_precond_apply: b = %d columns (b >= 1)", b);
   if (ldx < op->n || ldy < op->n) return fail(SLQ_EINVAL, "slq_kernel_precond_apply: ldx = %lld, ldy = %lld must reach n = %lld", (long long)ldx, (long long)ldy, (long long)op->n);
-  HIP_TRY(hipSetDevice(op->ctx->device));
-  KernelPrecond &pc = *op->pre;
-  const size_t colb = (size_t)op->n * 8;
-  SLQ_TRY(precond_grow(pc.stage_in, colb * b, "slq_kernel_precond_apply"));
-  SLQ_TRY(precond_grow(pc.stage_out, colb * b, "slq_kernel_precond_apply"));
-  hipStream_t st = op->ctx->stream;
-  HIP_TRY(hipMemcpy2DAsync(pc.stage_in.p, colb, X, (size_t)ldx * 8, colb, (size_t)b, hipMemcpyHostToDevice, st));
-  SLQ_TRY(precond_apply_device(op, pc.stage_in.as<const double>(), pc.stage_out.as<double>(), b, "slq_kernel_precond_apply"));
-  HIP_TRY(hipMemcpy2DAsync(Y, (size_t)ldy * 8, pc.stage_out.p, colb, colb, (size_t)b, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return SLQ_OK;
+  return staged_panel_product(op->ctx, 8, op->pre->stage_in, op->pre->stage_out, X, ldx, op->n, Y, ldy, op->n, b, "slq_kernel_precond_apply",
+                              [&](const void *in, int64_t, void *out, int64_t) { return precond_apply_device(op, (const double *)in, (double *)out, b, "slq_kernel_precond_apply"); });
 }
 
 extern "C" int slq_kernel_precond_apply_dmat(slq_operator *op, slq_dmat *IN, int i0, slq_dmat *OUT, int o0, int b) {
   SLQ_TRY(precond_handle(op, "slq_kernel_precond_apply_dmat"));
   if (b < 1) return fail(SLQ_EINVAL, "slq_kernel_precond_apply_dmat: b = %d columns (b >= 1)", b);
-  SLQ_TRY(dmat_range(IN, i0, b, "slq_kernel_precond_apply_dmat(IN)"));
-  SLQ_TRY(dmat_range(OUT, o0, b, "slq_kernel_precond_apply_dmat(OUT)"));
-  if (IN->n != op->n || OUT->n != op->n)
-    return fail(SLQ_EINVAL, "slq_kernel_precond_apply_dmat: the operator has %lld rows, IN %lld, OUT %lld", (long long)op->n, (long long)IN->n, (long long)OUT->n);
-  if (IN->ctx != op->ctx || OUT->ctx != op->ctx) return fail(SLQ_EINVAL, "slq_kernel_precond_apply_dmat: a matrix belongs to another context");
-  if (IN == OUT && i0 < o0 + b && o0 < i0 + b)
-    return fail(SLQ_EINVAL, "slq_kernel_precond_apply_dmat: the columns [%d, %d) of IN and [%d, %d) of OUT overlap in one matrix", i0, i0 + b, o0, o0 + b);
+  const double *in;
+  double *out;
+  SLQ_TRY(dmat_operands(IN, i0, OUT, o0, b, op->n, op->n, op->ctx, "slq_kernel_precond_apply_dmat", &in, &out));
   HIP_TRY(hipSetDevice(op->ctx->device));
-  return precond_apply_device(op, IN->d + (size_t)i0 * IN->n, OUT->d + (size_t)o0 * OUT->n, b, "slq_kernel_precond_apply_dmat");
+  return precond_apply_device(op, in, out, b, "slq_kernel_precond_apply_dmat");
 }
 
 // ---- the factor's columns as operands of the gradient kernel, and the exact part tr(P^-1 dA/dtheta) ----
@@ -5187,27 +5081,35 @@ extern "C" int slq_kernel_precond_columns(slq_operator *op, int which, int c0, i
 // column launches and one accumulator update (alpha_u = -alpha / sigma2; beta for the first chunk, 1 after it), then ONE one-thread
 // kernel adds alpha n / sigma2 to the outputscale's and the noise's value - everything on the stream, nothing is read back. The
 // accumulator's column count is left as it was: no probe was folded in.
+// The column loop of the two exact-part entries below, after their own checks of the accumulator: a fresh factor, finite weights,
+// then the columns of the rank reached, kPrecondChunkCols at a time, as two views Z = (L H)_c, W = L_c of pc.cols (grown on demand):
+// two column launches and update(Z, W, nc, -alpha / sigma2, beta for the first chunk and 1 after it) - the accumulator's own update.
+template <typename Update> static int precond_trace_columns(slq_operator *op, const char *who, double alpha, double beta, Update update) {
+  KernelPrecond &pc = *op->pre;
+  SLQ_TRY(precond_check_fresh(op, who));
+  if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(SLQ_EINVAL, "%s: alpha = %g, beta = %g must be finite", who, alpha, beta);
+  HIP_TRY(hipSetDevice(op->ctx->device));
+  const size_t n = (size_t)op->n;
+  SLQ_TRY(devbuf_grow(pc.cols, 2 * n * kPrecondChunkCols * 8, who));
+  slq_dmat Z{op->ctx, op->n, kPrecondChunkCols, pc.cols.as<double>()}, W{op->ctx, op->n, kPrecondChunkCols, pc.cols.as<double>() + n * kPrecondChunkCols};
+  const double sigma2 = pc.base->k_noise;
+  for (int c0 = 0; c0 < pc.rank; c0 += kPrecondChunkCols) {  // (the rank reached is at least 1: the first pivot's residual is s itself)
+    const int nc = std::min(kPrecondChunkCols, pc.rank - c0);
+    SLQ_TRY(precond_columns_device(op, 1, c0, nc, Z.d, who));
+    SLQ_TRY(precond_columns_device(op, 0, c0, nc, W.d, who));
+    SLQ_TRY(update(&Z, &W, nc, -alpha / sigma2, c0 == 0 ? beta : 1.0));
+  }
+  return SLQ_OK;
+}
+
 extern "C" int slq_kernel_precond_trace_grad(slq_operator *op, slq_kernel_grad *g, double alpha, double beta) {
   SLQ_TRY(precond_handle(op, "slq_kernel_precond_trace_grad"));
   if (!g) return fail(SLQ_EINVAL, "slq_kernel_precond_trace_grad: the accumulator is NULL");
   KernelPrecond &pc = *op->pre;
   if (g->op != pc.base) return fail(SLQ_EINVAL, "slq_kernel_precond_trace_grad: the accumulator belongs to another operator: create it on the base of this preconditioned operator");
-  SLQ_TRY(precond_check_fresh(op, "slq_kernel_precond_trace_grad"));
-  if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(SLQ_EINVAL, "slq_kernel_precond_trace_grad: alpha = %g, beta = %g must be finite", alpha, beta);
-  HIP_TRY(hipSetDevice(op->ctx->device));
-  const size_t n = (size_t)op->n;
-  SLQ_TRY(precond_grow(pc.cols, 2 * n * kPrecondChunkCols * 8, "slq_kernel_precond_trace_grad"));
-  slq_dmat Z{op->ctx, op->n, kPrecondChunkCols, pc.cols.as<double>()}, W{op->ctx, op->n, kPrecondChunkCols, pc.cols.as<double>() + n * kPrecondChunkCols};
-  const double sigma2 = pc.base->k_noise;
   const int64_t count = g->count;
-  bool first = true;  // (the rank reached is at least 1: the first pivot's residual is s itself)
-  for (int c0 = 0; c0 < pc.rank; c0 += kPrecondChunkCols) {
-    const int nc = std::min(kPrecondChunkCols, pc.rank - c0);
-    SLQ_TRY(precond_columns_device(op, 1, c0, nc, Z.d, "slq_kernel_precond_trace_grad"));
-    SLQ_TRY(precond_columns_device(op, 0, c0, nc, W.d, "slq_kernel_precond_trace_grad"));
-    SLQ_TRY(slq_kernel_grad_update(g, &Z, 0, &W, 0, nc, -alpha / sigma2, first ? beta : 1.0));
-    first = false;
-  }
+  SLQ_TRY(precond_trace_columns(op, "slq_kernel_precond_trace_grad", alpha, beta,
+                                [&](slq_dmat *Z, slq_dmat *W, int nc, double a, double b) { return slq_kernel_grad_update(g, Z, 0, W, 0, nc, a, b); }));
   g->count = count;
   hipStream_t st = op->ctx->stream;
   k_precond_trace_add<<<dim3(1), dim3(64), 0, st>>>(g->d, (double)op->n, (const double *)pc.base->k_pts.params, alpha, g->vals.as<double>());
@@ -5229,12 +5131,7 @@ struct slq_kernel_pointgrad {
 
 static int kernel_pointgrad_create_body(slq_context *ctx, slq_operator *op, slq_kernel_cross *cross, const char *who, slq_kernel_pointgrad **out) {
   *out = nullptr;
-  if (op->kind != OP_KERNEL)
-    return fail(SLQ_EINVAL, "%s: the operator is of kind '%s', not a kernel operator (slq_kernel_create; of a preconditioned operator pass the base)", who, op_kind_name(op->kind));
-  if (!cross) SLQ_TRY(kernel_refuse_scaled(op, who));  // (the cross form is defined on K0's points and profile, as a cross product is)
-  if (op->dtype != SLQ_F64) return fail(SLQ_EINVAL, "%s: the operator's dtype is fp32: the accumulator is fp64 only (the device matrices are fp64)", who);
-  if (op->ctx != ctx || (cross && cross->ctx != ctx)) return fail(SLQ_EINVAL, "%s: the operator belongs to another context", who);
-  if (ctx->dead) return fail(SLQ_EINVAL, "%s: the context has been destroyed", who);
+  SLQ_TRY(kernel_base_check(ctx, op, who, true, !cross, true));  // (the cross form is defined on K0's points and profile, as a cross product is: a scale does not stop it)
   HIP_TRY(hipSetDevice(ctx->device));
   const int64_t nrows = cross ? cross->pts.n : op->n;
   const KernelPointGradSchedule S = kernel_pointgrad_schedule(nrows, op->n, ctx->num_cus);
@@ -5257,15 +5154,7 @@ extern "C" int slq_kernel_pointgrad_create_cross(slq_context *ctx, slq_kernel_cr
   return kernel_pointgrad_create_body(ctx, cross->op, cross, "slq_kernel_pointgrad_create_cross", out);
 }
 
-extern "C" int slq_kernel_pointgrad_destroy(slq_kernel_pointgrad *g) {
-  if (!g) return SLQ_OK;
-  hipSetDevice(g->ctx->device);
-  hipStreamSynchronize(g->ctx->stream);
-  slq_context *ctx = g->ctx;
-  delete g;  // (every device array is a member that frees itself)
-  ctx_release(ctx);
-  return SLQ_OK;
-}
+extern "C" int slq_kernel_pointgrad_destroy(slq_kernel_pointgrad *g) { return handle_destroy(g); }
 
 // one pass of k_kernel_pointgrad and its fold: vals = beta vals + alpha R(U, W) over mc <= 64 columns
 static int kernel_pointgrad_pass(slq_kernel_pointgrad *g, const KernelPointGradSchedule &S, const KernelPointGradScale &sc, const double *U, const double *W,
@@ -5339,8 +5228,7 @@ extern "C" int slq_kernel_pointgrad_reset(slq_kernel_pointgrad *g) {
 // slab, then slab_begin[0 .. slabs] (-1 beyond). No HIP call.
 extern "C" int slq_debug_kernel_pointgrad_schedule(int64_t nrows, int64_t nsum, int num_cus, int64_t *out, int nout) {
   if (!out || nout < 5 + kKernelCrossMaxSlabs + 1) return fail(SLQ_EINVAL, "slq_debug_kernel_pointgrad_schedule: room for %d values", 5 + kKernelCrossMaxSlabs + 1);
-  const int64_t lim = ((int64_t)1 << 31) - 16;
-  if (nrows <= 0 || nrows >= lim || nsum <= 0 || nsum >= lim || num_cus <= 0)
+  if (!kernel_extents_ok({nrows, nsum}, num_cus))
     return fail(SLQ_EINVAL, "slq_debug_kernel_pointgrad_schedule: 0 < nrows, nsum < 2^31 - 16 and num_cus positive");
   const KernelPointGradSchedule S = kernel_pointgrad_schedule(nrows, nsum, num_cus);
   kernel_schedule_words({S.rows_per_block, S.nrow_blocks, S.chunk_cols, S.nslabs, S.tiles_per_slab}, S.nslabs, S.slab_begin, kKernelCrossMaxSlabs, out);
@@ -5356,22 +5244,9 @@ extern "C" int slq_kernel_precond_trace_pointgrad(slq_operator *op, slq_kernel_p
   KernelPrecond &pc = *op->pre;
   if (g->cross) return fail(SLQ_EINVAL, "slq_kernel_precond_trace_pointgrad: the accumulator is of the cross form: create it with slq_kernel_pointgrad_create on the base of this preconditioned operator");
   if (g->op != pc.base) return fail(SLQ_EINVAL, "slq_kernel_precond_trace_pointgrad: the accumulator belongs to another operator: create it on the base of this preconditioned operator");
-  SLQ_TRY(precond_check_fresh(op, "slq_kernel_precond_trace_pointgrad"));
-  if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(SLQ_EINVAL, "slq_kernel_precond_trace_pointgrad: alpha = %g, beta = %g must be finite", alpha, beta);
-  HIP_TRY(hipSetDevice(op->ctx->device));
-  const size_t n = (size_t)op->n;
-  SLQ_TRY(precond_grow(pc.cols, 2 * n * kPrecondChunkCols * 8, "slq_kernel_precond_trace_pointgrad"));
-  slq_dmat Z{op->ctx, op->n, kPrecondChunkCols, pc.cols.as<double>()}, W{op->ctx, op->n, kPrecondChunkCols, pc.cols.as<double>() + n * kPrecondChunkCols};
-  const double sigma2 = pc.base->k_noise;
   const int64_t count = g->count;
-  bool first = true;  // (the rank reached is at least 1: the first pivot's residual is s itself)
-  for (int c0 = 0; c0 < pc.rank; c0 += kPrecondChunkCols) {
-    const int nc = std::min(kPrecondChunkCols, pc.rank - c0);
-    SLQ_TRY(precond_columns_device(op, 1, c0, nc, Z.d, "slq_kernel_precond_trace_pointgrad"));
-    SLQ_TRY(precond_columns_device(op, 0, c0, nc, W.d, "slq_kernel_precond_trace_pointgrad"));
-    SLQ_TRY(slq_kernel_pointgrad_update(g, &Z, 0, &W, 0, nc, -alpha / sigma2, first ? beta : 1.0));
-    first = false;
-  }
+  SLQ_TRY(precond_trace_columns(op, "slq_kernel_precond_trace_pointgrad", alpha, beta,
+                                [&](slq_dmat *Z, slq_dmat *W, int nc, double a, double b) { return slq_kernel_pointgrad_update(g, Z, 0, W, 0, nc, a, b); }));
   g->count = count;
   return SLQ_OK;
 }

@@ -23,7 +23,8 @@ namespace slq {
 // bytes the live DevBufs of the process hold (slq_debug_operator_device_bytes: tests)
 inline std::atomic<int64_t> g_devbuf_bytes{0};
 
-// A device allocation that frees itself: every device array an operator owns, and the scratch of a build. Move-only.
+// A device allocation that frees itself: every device array an operator or a side object (accumulators, cross objects, feature maps,
+// device matrices) owns, and the scratch of a build. Move-only.
 struct DevBuf {
   void *p = nullptr;
   DevBuf() = default;

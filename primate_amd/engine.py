@@ -89,7 +89,25 @@ def default_context() -> Context:
 	return _default_ctx
 
 
-class DeviceOperator:
+class _Handle:
+	"""A C handle `_h` and its end: `close()` destroys it once (the class names the library's destroy entry), and so does garbage collection."""
+
+	_destroy: str
+	_h = None
+
+	def close(self):
+		if getattr(self, "_h", None):
+			getattr(_capi.lib(), self._destroy)(self._h)
+			self._h = None
+
+	def __del__(self):
+		try:
+			self.close()
+		except Exception:  # noqa: BLE001
+			pass
+
+
+class DeviceOperator(_Handle):
 	"""Operator plugin resident on the GPU: the counterpart of the reference's C++ operator
 	wrappers (src/primate/include/eigen_operators.h:17-104, src/primate/include/pylinop.h:16-73).
 
@@ -98,6 +116,8 @@ class DeviceOperator:
 	with int32 indices), or any object with `.matvec` and `.shape` (host-callback fallback); beyond them a
 	torch sparse-CSR tensor that already lives on the context's GPU (slq_csr_create_device).
 	"""
+
+	_destroy = "slq_operator_destroy"
 
 	def __init__(self, A, dtype=None, ctx: Optional[Context] = None):
 		import scipy.sparse as sp
@@ -413,17 +433,6 @@ class DeviceOperator:
 		check(_capi.lib().slq_operator_matmat(self._h, ptr(X), X.shape[0], ptr(Y), Y.shape[0], X.shape[1]))
 		return Y
 
-	def close(self):
-		if getattr(self, "_h", None):
-			_capi.lib().slq_operator_destroy(self._h)
-			self._h = None
-
-	def __del__(self):
-		try:
-			self.close()
-		except Exception:  # noqa: BLE001
-			pass
-
 
 BASIS_MODES = {None: 0, "keep": 1, "recompute": 2}
 
@@ -452,13 +461,15 @@ def plan_query_bytes(dtype, n: int, nprobes: int, deg: int, orth: int = 0, basis
 	return int(b.value)
 
 
-class LanczosPlan:
+class LanczosPlan(_Handle):
 	"""Workspace + state of one batched lock-step Lanczos run over `nprobes` probes.
 
 	`basis` (or the older `keep_basis=True`, which is `basis="keep"`) says what the f(A)v action runs on: "keep" retains all deg
 	Lanczos vectors (deg + 1 panels); "recompute" keeps none - `fun_action`, `fun_action_into` and `DiagAccumulator.update`
 	replay the run (two-pass Lanczos) and add g_t W_t into an output panel as the vectors pass through a short ring: a
 	footprint independent of deg, one more run per action call. None: a quadrature plan (no action)."""
+
+	_destroy = "slq_plan_destroy"
 
 	def __init__(self, op: DeviceOperator, nprobes: int, deg: int, orth: int = 0, keep_basis: bool = False, basis: Optional[str] = None):
 		basis = _basis_arg(keep_basis, basis)
@@ -695,17 +706,6 @@ class LanczosPlan:
 		a, b = C.c_uint64(), C.c_uint64()
 		check(_capi.lib().slq_plan_action_columns(self._h, C.byref(a), C.byref(b), int(reset)))
 		return int(a.value), int(b.value)
-
-	def close(self):
-		if getattr(self, "_h", None):
-			_capi.lib().slq_plan_destroy(self._h)
-			self._h = None
-
-	def __del__(self):
-		try:
-			self.close()
-		except Exception:  # noqa: BLE001
-			pass
 
 
 RULE_IDS = {"gauss": 0, "radau": 1}
@@ -1060,8 +1060,10 @@ def fttr_batch(theta: np.ndarray, alpha: np.ndarray, beta: np.ndarray, k: Option
 	return w
 
 
-class DiagAccumulator:
+class DiagAccumulator(_Handle):
 	"""Device-resident numer / denom / running-mean accumulators of the diagonal estimator."""
+
+	_destroy = "slq_diag_destroy"
 
 	def __init__(self, n: int, ctx: Optional[Context] = None):
 		self.ctx = ctx or default_context()
@@ -1082,24 +1084,15 @@ class DiagAccumulator:
 		check(_capi.lib().slq_diag_get(self._h, ptr(nu), ptr(de), ptr(rm), C.byref(cnt)))
 		return nu, de, rm, cnt.value
 
-	def close(self):
-		if getattr(self, "_h", None):
-			_capi.lib().slq_diag_destroy(self._h)
-			self._h = None
 
-	def __del__(self):
-		try:
-			self.close()
-		except Exception:  # noqa: BLE001
-			pass
-
-
-class DensityAccumulator:
+class DensityAccumulator(_Handle):
 	"""Device-resident (count, mean, M2) of a spectral density estimate over a fixed grid (slq_density_*): every
 	`update(plan)` folds the per-probe values ||v||^2 sum_k tau_k K(x_g, theta_k) of a completed run, in probe order.
 	kind: "gaussian" | "lorentzian" (G points, bandwidth bw > 0), "histogram" (G bins: G + 1 edges), "cdf"
 	(G thresholds) or "chebyshev" (G points strictly inside the bounds of the runs folded in; bw ignored): the density of
 	the kernel polynomial method from the moments of a ChebyshevPlan."""
+
+	_destroy = "slq_density_destroy"
 
 	def __init__(self, kind: str, grid: np.ndarray, bw: float = 0.0, ctx: Optional[Context] = None):
 		if kind not in _capi.DENSITY_KINDS:
@@ -1136,17 +1129,6 @@ class DensityAccumulator:
 		check(_capi.lib().slq_density_get(self._h, ptr(mean), ptr(m2), ptr(out), C.byref(cnt)))
 		return mean, m2, out, cnt.value
 
-	def close(self):
-		if getattr(self, "_h", None):
-			_capi.lib().slq_density_destroy(self._h)
-			self._h = None
-
-	def __del__(self):
-		try:
-			self.close()
-		except Exception:  # noqa: BLE001
-			pass
-
 
 def _is_torch_csr(A) -> bool:
 	return type(A).__module__.split(".")[0] == "torch" and str(getattr(A, "layout", "")) == "torch.sparse_csr"
@@ -1168,11 +1150,13 @@ def sddmm_schedule(indptr) -> dict:
 	return dict(row0=row0, nrows=nrows, kind=kind, e0=e0, e1=e1, grid=int(info[0]), nlong=int(info[1]), long_row=int(info[2]), waves=int(info[3]))
 
 
-class SddmmAccumulator:
+class SddmmAccumulator(_Handle):
 	"""Device-resident values on a CSR pattern (slq_sddmm_*): every `update` folds alpha * sum_j W[row(e), w0 + j] Z[col(e), z0 + j]
 	into the value of every stored nonzero e. pattern: a SciPy sparse matrix (its `indptr` / `indices` as given - not sorted, not
 	deduplicated; any other format is converted to CSR first) or a torch sparse-CSR tensor on the context's GPU. Only the pattern
 	is read; the values come out aligned with `pattern.data` / `pattern.values()`, entry for entry."""
+
+	_destroy = "slq_sddmm_destroy"
 
 	def __init__(self, pattern, ctx: Optional[Context] = None):
 		import scipy.sparse as sp
@@ -1227,17 +1211,6 @@ class SddmmAccumulator:
 	def reset(self):
 		check(_capi.lib().slq_sddmm_reset(self._h))
 
-	def close(self):
-		if getattr(self, "_h", None):
-			_capi.lib().slq_sddmm_destroy(self._h)
-			self._h = None
-
-	def __del__(self):
-		try:
-			self.close()
-		except Exception:  # noqa: BLE001
-			pass
-
 
 def kernel_grad_schedule(n: int, m: int, num_cus: int = 256) -> dict:
 	"""The schedule of one KernelGradAccumulator.update for n points and m columns, as the library cuts it (slq_debug_kernel_grad_schedule;
@@ -1248,12 +1221,14 @@ def kernel_grad_schedule(n: int, m: int, num_cus: int = 256) -> dict:
 	return dict(rows=v[0], nrb=v[1], chunk_cols=v[2], chunks=v[3], slabs=v[4], begin=v[5 : 5 + v[4] + 1], rest=v[5 + v[4] + 1 :])
 
 
-class KernelGradAccumulator:
+class KernelGradAccumulator(_Handle):
 	"""Device-resident hyperparameter gradients of a kernel operator (slq_kernel_grad_*): every `update` folds
 	alpha * sum_c Z_c^T (dA/dtheta) W_c, for theta = the d lengthscales, the outputscale and the noise, into d + 2 values. op: a
 	DeviceOperator of kind "kernel" in fp64. The accumulator keeps `op` alive, as a plan does, and reads its parameters as they are at
 	each update: `set_kernel_parameters` between two updates is honoured by the second, and values accumulated across such a change
 	mix two operators."""
+
+	_destroy = "slq_kernel_grad_destroy"
 
 	def __init__(self, op: DeviceOperator):
 		if getattr(op, "kind", None) != "kernel":
@@ -1282,17 +1257,6 @@ class KernelGradAccumulator:
 	def reset(self):
 		check(_capi.lib().slq_kernel_grad_reset(self._h))
 
-	def close(self):
-		if getattr(self, "_h", None):
-			_capi.lib().slq_kernel_grad_destroy(self._h)
-			self._h = None
-
-	def __del__(self):
-		try:
-			self.close()
-		except Exception:  # noqa: BLE001
-			pass
-
 
 def kernel_cross_schedule(nrows: int, nsum: int, b: int, num_cus: int = 256) -> dict:
 	"""The schedule of one cross-covariance product with `nrows` output rows, `nsum` summed points and `b` columns, as the library
@@ -1304,12 +1268,14 @@ def kernel_cross_schedule(nrows: int, nsum: int, b: int, num_cus: int = 256) -> 
 	return dict(rows=v[0], nrb=v[1], col_blocks=v[2], chunks=v[3], slabs=v[4], tiles_per_slab=v[5], begin=v[6 : 6 + v[4] + 1], rest=v[6 + v[4] + 1 :])
 
 
-class KernelCross:
+class KernelCross(_Handle):
 	"""The cross-covariance C = s phi(r2(X*, X)) between `Xnew` (m x d) and the points of a kernel operator, never formed
 	(slq_kernel_cross_*): `matmat(W)` is C W (m x b), `matmat(U, trans=True)` is C^T U (n x b). z* is taken with
 	the operator's own centre and its lengthscales of now; no diagonal rule, no noise term. op: a DeviceOperator of kind "kernel"; the
 	object takes its dtype and keeps it alive, as a plan does. `Xnew`: a NumPy array, or a torch tensor on the context's GPU.
 	`set_kernel_parameters` on the operator is honoured by the next product (the library re-derives z* on the stream)."""
+
+	_destroy = "slq_kernel_cross_destroy"
 
 	def __init__(self, op: DeviceOperator, Xnew):
 		if getattr(op, "kind", None) != "kernel":
@@ -1371,17 +1337,6 @@ class KernelCross:
 		self.padding_is_zero = bool(not zt[self.d :].any() and not zt[:, self.m :].any() and not nrm[self.m :].any())
 		return np.ascontiguousarray(zt[: self.d, : self.m].T), nrm[: self.m].copy()
 
-	def close(self):
-		if getattr(self, "_h", None):
-			_capi.lib().slq_kernel_cross_destroy(self._h)
-			self._h = None
-
-	def __del__(self):
-		try:
-			self.close()
-		except Exception:  # noqa: BLE001
-			pass
-
 
 def kernel_feature_schedule(nrows: int, num_features: int, b: int, num_cus: int = 256, dtype=np.float64) -> dict:
 	"""The schedule of one feature product with `nrows` row points, `num_features` frequencies and `b` columns, as the library cuts it
@@ -1406,12 +1361,14 @@ def kernel_feature_adjoint_schedule(num_features: int, nrows: int, b: int, num_c
 GRAM_CHUNK = 128  # identity columns of one forward + adjoint pair of KernelFeatureMap.gram: the fp64 column chunk of both kernels
 
 
-class KernelFeatureMap:
+class KernelFeatureMap(_Handle):
 	"""Random Fourier features of a kernel operator's profile on the GPU, never formed (slq_kernel_feature_*):
 	`matmat(W)` is Phi W with Phi(z) = sqrt(s / F2) [cos(Omega z) | sin(Omega z)] at the operator's scaled points - or, with
 	`rows=` a KernelCross of the same operator, at its new points - for W of 2 F2 rows. `omega`: F2 x d, rounded once to the operator's
 	dtype (the map is defined on the rounded values, `self.omega`). op: a DeviceOperator of kind "kernel"; the object takes its dtype
 	and keeps it alive, as a plan does. `set_kernel_parameters` on the operator is honoured by the next product."""
+
+	_destroy = "slq_kernel_feature_destroy"
 
 	def __init__(self, op: DeviceOperator, omega):
 		if getattr(op, "kind", None) != "kernel":
@@ -1516,17 +1473,6 @@ class KernelFeatureMap:
 		self.padding_is_zero = bool(not omt[self.d :].any() and not omt[:, self.num_features :].any())
 		return np.ascontiguousarray(omt[: self.d, : self.num_features].T)
 
-	def close(self):
-		if getattr(self, "_h", None):
-			_capi.lib().slq_kernel_feature_destroy(self._h)
-			self._h = None
-
-	def __del__(self):
-		try:
-			self.close()
-		except Exception:  # noqa: BLE001
-			pass
-
 
 def kernel_pointgrad_schedule(nrows: int, nsum: int, num_cus: int = 256) -> dict:
 	"""The schedule of one pass of a KernelPointGradAccumulator.update with `nrows` row points and `nsum` summed points, as the library
@@ -1538,13 +1484,15 @@ def kernel_pointgrad_schedule(nrows: int, nsum: int, num_cus: int = 256) -> dict
 	return dict(rows=v[0], nrb=v[1], chunk_cols=v[2], slabs=v[3], tiles_per_slab=v[4], begin=v[5 : 5 + v[3] + 1], rest=v[5 + v[3] + 1 :])
 
 
-class KernelPointGradAccumulator:
+class KernelPointGradAccumulator(_Handle):
 	"""Device-resident gradients of a kernel operator with respect to the points (slq_kernel_pointgrad_*).
 	On a DeviceOperator of kind "kernel" in fp64 (the training form) every `update` folds alpha * sum_c Z_c^T (dA/dx_ak) W_c into n x d
 	values; on a KernelCross of such an operator (the cross form) alpha * d/dx*_ak sum_c U_c^T K(X*, X) W_c into m x d values, U on the
 	new points and W on the training points. The accumulator keeps what it borrows alive - the operator, and the cross object - and
 	reads the operator's parameters as they are at each update, as a KernelGradAccumulator does; a cross-form accumulator follows a
 	`set_kernel_parameters` as a cross product does."""
+
+	_destroy = "slq_kernel_pointgrad_destroy"
 
 	def __init__(self, op_or_cross):
 		cross = op_or_cross if isinstance(op_or_cross, KernelCross) else None
@@ -1578,17 +1526,6 @@ class KernelPointGradAccumulator:
 	def reset(self):
 		check(_capi.lib().slq_kernel_pointgrad_reset(self._h))
 
-	def close(self):
-		if getattr(self, "_h", None):
-			_capi.lib().slq_kernel_pointgrad_destroy(self._h)
-			self._h = None
-
-	def __del__(self):
-		try:
-			self.close()
-		except Exception:  # noqa: BLE001
-			pass
-
 
 class _CudaArrayView:
 	"""Flat fp64 device array described by the CUDA array interface (v2); keeps its owner alive."""
@@ -1604,9 +1541,11 @@ class _CudaArrayView:
 		}  # fmt: skip
 
 
-class DeviceMatrix:
+class DeviceMatrix(_Handle):
 	"""Column-major n x cols fp64 matrix on the GPU with the two tall-skinny products of the
 	exchangeable estimators (slq_dmat_*: fp64 MFMA)."""
+
+	_destroy = "slq_dmat_destroy"
 
 	def __init__(self, n: int, cols: int, ctx: Optional[Context] = None):
 		self.ctx = ctx or default_context()
@@ -1660,14 +1599,3 @@ class DeviceMatrix:
 		Cm = np.ascontiguousarray(Cm, dtype=np.float64)
 		ma, mb = Cm.shape
 		check(_capi.lib().slq_dmat_gemm_nn(self._h, int(o0), A._h, int(a0), ma, ptr(Cm), mb, float(alpha), float(beta)))
-
-	def close(self):
-		if getattr(self, "_h", None):
-			_capi.lib().slq_dmat_destroy(self._h)
-			self._h = None
-
-	def __del__(self):
-		try:
-			self.close()
-		except Exception:  # noqa: BLE001
-			pass

@@ -3,7 +3,8 @@ quadrature values of one seeded 256 x 30 run per operator. Two libraries that pr
 (r04: used to show that the device-side build, the stamp-based regrouping and the cached first-level Cuthill-McKee leave every result
 bitwise unchanged; later: that slq_layout.hpp does - the cases then cover the host builder, barrier tiles, a forced reorder without tiles, a
 random graph, creation from device arrays, an affine and a Gram operator; later still: that one tile walk for the kernel-operator
-family does - the "kernel ..." lines are sha256 of products, cross products and a gradient update themselves; --posterior: only the two
+family does - the "kernel ..." lines are sha256 of products, cross products and a gradient update themselves; and that one product
+driver and one handle life cycle for the side objects do - side_objects(), profiles/side_objects_fingerprint.txt; --posterior: only the two
 "posterior ..." lines of tests/_gp_mll_ref.posterior_fingerprint_lines, sha256 of gp.posterior's mean and variance without and with the
 preconditioner - factoring its solve helper out for gp.mll leaves them as they were: profiles/gp_mll_posterior_fingerprint.txt).
 PRIMATE_AMD_LIBSLQ=<other library> python scripts/op_fingerprint.py [--posterior]"""
@@ -100,6 +101,59 @@ def sha(*arrays):
 		h.update(np.ascontiguousarray(x).tobytes())
 	return h.hexdigest()[:16]
 
+def side_objects(op, X, kernel, tag, dtype):
+	"""The side objects of the C ABI at the small pair (n, d) = (300, 3) (their shared host paths): feature and adjoint
+	feature products host-staged and - like everything below, in fp64 - through DeviceMatrix, point-gradient updates of both forms, the
+	preconditioner's inv_sqrt both ways and its two exact trace parts, and one update each of an SddmmAccumulator, a DiagAccumulator and
+	a DensityAccumulator."""
+	import scipy.sparse as sp
+	n, d, m, f2, b = X.shape[0], X.shape[1], 37, 45, 21
+	r = np.random.default_rng(77)
+	head = f"kernel {kernel} {tag} n={n} d={d}"
+	cross = eng.KernelCross(op, r.standard_normal((m, d)).astype(dtype))
+	fmap = eng.KernelFeatureMap(op, r.standard_normal((f2, d)).astype(dtype))
+	Wf, Un, Um = r.standard_normal((2 * f2, b)).astype(dtype), r.standard_normal((n, b)).astype(dtype), r.standard_normal((m, b)).astype(dtype)
+	print(f"{head} feature F2={f2} b={b} staged sha={sha(fmap.matmat(Wf))} rows sha={sha(fmap.matmat(Wf, rows=cross))} adjoint sha={sha(fmap.rmatmat(Un))} rows sha={sha(fmap.rmatmat(Um, rows=cross))}", flush=True)
+	if dtype != np.float64:
+		for x in (fmap, cross):
+			x.close()
+		return
+	ctx = op.ctx
+	F, N, M = eng.DeviceMatrix(2 * f2, 2 * b, ctx=ctx), eng.DeviceMatrix(n, 2 * b, ctx=ctx), eng.DeviceMatrix(m, 2 * b, ctx=ctx)
+	F.set(0, Wf), N.set(0, Un), M.set(0, Um)
+	fmap.matmat_dmat(F, 0, N, b, b)
+	fmap.matmat_dmat(F, 0, M, b, b, rows=cross)
+	got = [N.get(b, b), M.get(b, b)]
+	fmap.rmatmat_dmat(N, 0, F, b, b)
+	got.append(F.get(b, b))
+	fmap.rmatmat_dmat(M, 0, F, b, b, rows=cross)
+	got.append(F.get(b, b))
+	print(f"{head} feature F2={f2} b={b} dmat sha={sha(got[0])} rows sha={sha(got[1])} adjoint sha={sha(got[2])} rows sha={sha(got[3])}", flush=True)
+	pg, pgc = eng.KernelPointGradAccumulator(op), eng.KernelPointGradAccumulator(cross)
+	N.set(b, r.standard_normal((n, b)))
+	pg.update(N, 0, N, b, b, alpha=1.0, beta=0.0)
+	pgc.update(M, 0, N, 0, b, alpha=1.0, beta=0.0)
+	print(f"{head} point gradient m={b} training sha={sha(pg.get()[0])} cross sha={sha(pgc.get()[0])}", flush=True)
+	pre = eng.DeviceOperator(KernelOperator(X, kernel, lengthscale=0.7 * np.sqrt(d), outputscale=1.3, noise=0.05).preconditioned(70), ctx=ctx)
+	staged = pre.inv_sqrt(Un)
+	pre.inv_sqrt_dmat(N, 0, N, b, b)
+	acc, pacc = eng.KernelGradAccumulator(pre.base), eng.KernelPointGradAccumulator(pre.base)
+	pre.precond_trace_grad(acc, 1.0, 0.0)
+	pre.precond_trace_point_grad(pacc, 1.0, 0.0)
+	print(f"{head} precond rank 70 inv_sqrt sha={sha(staged)} dmat sha={sha(N.get(b, b))} trace_grad sha={sha(acc.get()[0])} trace_point_grad sha={sha(pacc.get()[0])}", flush=True)
+	pattern = sp.random(n, n, density=0.03, random_state=5, format="csr") + sp.identity(n, format="csr")
+	sd = eng.SddmmAccumulator(pattern, ctx=ctx)
+	sd.update(N, 0, N, b, b, alpha=0.5, beta=0.0, symmetric=True)
+	plan = eng.LanczosPlan(op, 16, 20, 3, keep_basis=True)
+	plan.generate_probes("rademacher", seed=5)
+	plan.run()
+	dg, dens = eng.DiagAccumulator(n, ctx=ctx), eng.DensityAccumulator("gaussian", np.linspace(0.0, 40.0, 33), bw=0.5, ctx=ctx)
+	dg.update(plan, "log")
+	dens.update(plan)
+	print(f"{head} sddmm sha={sha(sd.get()[0])} diag sha={sha(*dg.get()[:3])} density sha={sha(*dens.get()[:3])}", flush=True)
+	for x in (dens, dg, plan, sd, pacc, acc, pre, pgc, pg, F, N, M, fmap, cross):
+		x.close()
+
 rng = np.random.default_rng(2024)
 for dtype, kernels in ((np.float64, ("rbf", "matern12", "matern32", "matern52")), (np.float32, ("rbf", "matern52"))):
 	tag = "f64" if dtype == np.float64 else "f32"
@@ -127,4 +181,6 @@ for dtype, kernels in ((np.float64, ("rbf", "matern12", "matern32", "matern52"))
 				print(f"kernel {kernel} {tag} n={n} d={d} gradient m=65 sum={float(np.sum(vals)):.12e} sha={sha(vals)}", flush=True)
 				for x in (acc, Z, V):
 					x.close()
+			if (n, d) == (300, 3):
+				side_objects(op, X, kernel, tag, dtype)
 			op.close()
